@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: clips/sec of Synchformer offset prediction (14 x 0.64 s segments, 21 offset classes).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 (a plain `python bench.py --gpus N` with N > 1 re-executes itself through torch.distributed.run, one rank per GPU.)
@@ -11,13 +11,16 @@ synthetic 224x224 @ 25 fps uint8 frames + 128x66 log-mel spectrograms already re
 full Synchformer.forward() (RGB front-end -> Motionformer -> AST -> sync transformer -> logits) over B clips per GPU.
 Multi-GPU: inference shards by clip with no data-path collective ("replicas only"): every rank runs
 its own B clips; value = all clips / max-over-ranks time (weak scaling).
-Prints ONE JSON line on rank 0 with
+A plain run sets up, warms up, times exactly K steps, writes the last timed step's outputs if --dump-outputs is given and prints ONE JSON line on
+rank 0 (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).  With --full the line also carries
   * `roofline`: every GEMM-family kernel of the step timed live with HIP events on the launch stream in a second pass of the same K steps
-    (`roofline.kernels`, one entry per kernel symbol as rocprofv3 names it; `roofline.kernel` = the dominant one by time),
+    (`roofline.kernels`, one entry per kernel symbol as rocprofv3 names it; `roofline.kernel` = the dominant one by time), and `power`,
   * `cpu_baseline`: the CPU oracle timed on this box's host cores (N = 1 only),
   * `workloads`: BASELINE configs[2] / [3] / [4] (Stage-2 train step, Stage-1 AVCLIP train step at 2 clips per GPU, synchronizability fine-tune on
     MXFP8 extractor GEMMs), a few steps each AFTER the headline region - on N > 1 these run their RCCL collectives (gradient all-reduce, bucketed
     overlap); a watchdog prints the headline line without them if they do not finish.
+--dump-outputs DIR: what the timed step returned in its last step (`logits` (B, n_out) of the inference workload, the `loss` of a train workload), rank 0's,
+as DIR/<name>.npy in float32.  Weights and inputs come from fixed seeds, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -64,7 +67,21 @@ def parse():
     ap.add_argument('--graph', action='store_true', help='replay the forward as one captured HIP graph (infer workload only)')
     ap.add_argument('--dropin', action='store_true', help="train workload through the drop-in nn.Module + torch.optim.Adam + GradScaler "
                     "(the reference's loop body, train_utils.py:373-386) instead of SyncTrainer's fused step: the wrapper overhead as a number")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help="write the last timed step's outputs (rank 0) as DIR/<name>.npy, float32")
+    ap.add_argument('--full', action='store_true', help='also run what the headline does not need: the roofline kernel pass and power probe, the other '
+                    'workloads, the CPU baseline (each still switchable off with its --no-* option)')
     return ap.parse_args()
+
+
+def dump_outputs(out_dir, arrays):
+    """{name: tensor} -> out_dir/<name>.npy in float32 (the timed step's outputs are a few KB: logits (B, n_out) or a scalar loss)."""
+    import numpy as np
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    assert sum(a.nbytes for a in host.values()) <= 64 << 20, {k: a.shape for k, a in host.items()}
+    for k, a in host.items():
+        np.save(out_dir / f'{k}.npy', a)
 
 
 def respawn_distributed(args):
@@ -700,6 +717,8 @@ def main():
     barrier()
     dt_local = time.perf_counter() - t0
     assert torch.isfinite(logits).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'logits' if name == 'infer' else 'loss': logits})
     comm_ms = []
     if timed_trainer is not None and world > 1:
         timed_trainer.time_comm = False
@@ -729,7 +748,7 @@ def main():
     kernels = by = None
     dt_roof = 0.0
     roofline_error = None
-    if not args.no_kernel_timing and not args.graph:
+    if args.full and not args.no_kernel_timing and not args.graph:
         try:
             kernels, by, dt_roof = kernel_pass(w, args.steps)
         except Exception as ex:                                    # noqa: BLE001 - instrumentation must not cost the headline number
@@ -767,7 +786,7 @@ def main():
                                    'Stage-1: 7 buckets launched under the backward, the wait is for what did not overlap)'}
         if roofline_error:
             out['roofline_error'] = roofline_error
-        if name == 'infer' and world == 1 and not args.no_kernel_timing and not args.graph:
+        if args.full and name == 'infer' and world == 1 and not args.no_kernel_timing and not args.graph:
             pw = power_probe(step_fn, w['vis'], w['aud'])
             if pw:
                 out['power'] = pw
@@ -797,7 +816,7 @@ def main():
         if rank == 0 and out is not None:
             print(json.dumps(out), flush=True)
 
-    if name == 'infer' and not args.no_workloads and not args.graph:
+    if args.full and name == 'infer' and not args.no_workloads and not args.graph:
         done = threading.Event()
 
         def watchdog():                                            # a hung collective in an extra workload must not cost the headline number
@@ -857,7 +876,7 @@ def main():
         if rank == 0:
             out['workloads'] = wl_out
         done.set()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline()
     emit()
     if world > 1:

@@ -231,6 +231,23 @@ def avclip(B=2, S=3, gain=2.0):
           'gathered losses', float(gath['gathered_loss_rank0']), float(gath['gathered_loss_rank1']), 'clamps', clamped_hi, float(out_lo['logit_scales'][0]))
 
 
+def oracle_parity():
+    """The REAL reference's visual / audio extractors on 2 segments of one clip and its sync transformer on seeded random tokens, with the
+    state-dict key order of the reference module: what tests/test_oracle_cpu.py::test_oracle_matches_real_reference compares the oracle against."""
+    model = ref_import.build_reference_synchformer()
+    sd = synth.make_state_dict(SEED)
+    model.load_state_dict(sd, strict=True)
+    vis = rgb_frontend_ref(synth.make_video_u8(1, 2, 7)).float()
+    aud = synth.make_spectrogram(1, 2, 7)
+    g = torch.Generator().manual_seed(1)
+    v, a = torch.randn(2, 112, 768, generator=g), torch.randn(2, 84, 768, generator=g)
+    with torch.no_grad():
+        out = {'names': np.array(list(model.state_dict().keys())), 'vfeats': model.extract_vfeats(vis, for_loop=False).numpy(),
+               'afeats': model.extract_afeats(aud, for_loop=False).numpy(), 'transformer': model.transformer(v, a).numpy()}
+    np.savez_compressed(HERE / 'oracle_parity_B1S2.npz', **out)
+    print('oracle_parity:', {k: v.shape for k, v in out.items()})
+
+
 def shift_preds():
     """Stage-1 zero-shot read-out `shift_and_get_preds` (train_clip_src/training/train.py:549-579) - the REAL function (its module imports
     torchvision / torchaudio / matplotlib at module scope: import-only stand-ins, tests/golden/ref_shims_late) on seeded random features."""
@@ -591,7 +608,10 @@ def checkpoints():
 
 if __name__ == '__main__':
     torch.manual_seed(0)
-    which = sys.argv[1:] or ['sync', 'sync_gain2', 'syncability', 'train', 'train_ft', 'avclip', 'shift_preds', 'segments', 'avclip_grads', 'masked', 'checkpoints']
+    which = sys.argv[1:] or ['sync', 'sync_gain2', 'syncability', 'train', 'train_ft', 'avclip', 'shift_preds', 'segments', 'avclip_grads', 'masked', 'checkpoints',
+                             'oracle_parity']
+    if 'oracle_parity' in which:
+        oracle_parity()
     if 'sync' in which:
         e2e_sync(2)
     if 'sync_gain2' in which:

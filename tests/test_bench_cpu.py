@@ -21,3 +21,18 @@ def test_gemm_timer_wrappers_accept_the_ops_keywords():
     for name in ('sf_gemm_tn_pp', 'sf_gemm_tn_splitk', 'sf_gemm_bf16_gelu_dual'):
         assert getattr(lib, name) is gt.lib_orig[name]
         assert len(inspect.signature(gt.lib_orig[name].__call__).parameters) >= 0
+
+
+def test_dump_outputs_writes_float32_npy(tmp_path):
+    """--dump-outputs: every array the timed step returned lands as <name>.npy in float32 whatever its dtype; more than 64 MB in all is refused."""
+    import numpy as np
+    import pytest
+    import torch
+    import bench
+    logits = torch.randn(16, 21, generator=torch.Generator().manual_seed(0)).bfloat16()
+    bench.dump_outputs(tmp_path / 'out', {'logits': logits, 'loss': torch.tensor(2.5)})
+    got = np.load(tmp_path / 'out' / 'logits.npy')
+    assert got.dtype == np.float32 and got.shape == (16, 21) and np.array_equal(got, logits.float().numpy())
+    assert np.load(tmp_path / 'out' / 'loss.npy') == np.float32(2.5)
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(tmp_path / 'big', {'x': torch.zeros(16 << 20 | 1)})

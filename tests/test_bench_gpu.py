@@ -9,6 +9,7 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 import torch
 
@@ -16,11 +17,11 @@ ROOT = Path(__file__).resolve().parent.parent
 pytestmark = pytest.mark.gpu
 
 
-def _run_bench(*extra, timeout=900, gpus=2, steps=2):
+def _run_bench(*extra, timeout=900, gpus=2, steps=2, full=True):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0', MASTER_ADDR='127.0.0.1')
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_PORT'):
         env.pop(k, None)
-    cmd = [sys.executable, str(ROOT / 'bench.py'), '--gpus', str(gpus), '--steps', str(steps), '--warmup', '1', '--workload-steps', '1', '--no-cpu-baseline', *extra]
+    cmd = [sys.executable, str(ROOT / 'bench.py'), '--gpus', str(gpus), '--steps', str(steps), '--warmup', '1', *(['--full', '--workload-steps', '1', '--no-cpu-baseline'] if full else []), *extra]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env, cwd=str(ROOT))
     assert r.returncode == 0, f'bench.py failed (rc {r.returncode}):\n{r.stdout[-2000:]}\n{r.stderr[-4000:]}'
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
@@ -79,3 +80,18 @@ def test_bench_eight_ranks_single_device(gpu, workload):
     if workload != 'infer':
         comm = d['comm']['exposed_ms_last_step_by_rank']
         assert len(comm) == 8 and all(c >= 0 for c in comm)
+
+
+def test_bench_plain_run_times_steps_and_dumps_outputs(gpu, tmp_path):
+    """A plain `bench.py --gpus 1` run (no --full) is the headline alone: exactly --steps timed steps, the result line without the --full sections, and
+    --dump-outputs writes the last timed step's logits in float32.  Inputs and weights come from seeds: a second run with the same arguments computes the same."""
+    runs = []
+    for tag in ('a', 'b'):
+        d = _run_bench('--batch', '2', '--dump-outputs', str(tmp_path / tag), gpus=1, steps=3, full=False)
+        assert d['steps'] == 3 and d['warmup'] == 1 and d['n_gpus'] == 1 and d['unit'] == 'clips/s' and d['higher_is_better'] is True and d['dtype'] == 'bf16'
+        assert d['value'] > 0 and abs(d['ms_per_step'] - 1e3 * 2 / d['value']) < 0.01 * d['ms_per_step']
+        assert not {'roofline', 'power', 'workloads', 'cpu_baseline', 'latency_b1_ms'} & set(d), sorted(d)
+        logits = np.load(tmp_path / tag / 'logits.npy')
+        assert logits.dtype == np.float32 and logits.shape == (2, 21) and np.isfinite(logits).all()
+        runs.append(logits)
+    assert np.abs(runs[0] - runs[1]).max() < 1e-3, np.abs(runs[0] - runs[1]).max()

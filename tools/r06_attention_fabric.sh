@@ -24,7 +24,7 @@ cd $R
 for rep in 1 2 3; do
   for hc in 6 3; do
     echo "=== e2e SF_QT2_PAIR_CHUNK=$hc SF_QS_PAIR_CHUNK=$hc (rep $rep)"
-    SF_QT2_PAIR_CHUNK=$hc SF_QS_PAIR_CHUNK=$hc python bench.py --steps 10 --warmup 3 --no-workloads --no-cpu-baseline 2>/dev/null | python -c "
+    SF_QT2_PAIR_CHUNK=$hc SF_QS_PAIR_CHUNK=$hc python bench.py --full --steps 10 --warmup 3 --no-workloads --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):
