@@ -29,7 +29,7 @@ extern "C" {
 enum { SF_F32 = 0, SF_BF16 = 1, SF_F16 = 2, SF_U8 = 3 };   /* element types */
 enum { SF_EPI_NONE = 0, SF_EPI_GELU = 1 };                  /* GEMM epilogue activation */
 
-#define SF_ABI_VERSION 10
+#define SF_ABI_VERSION 11
 int sf_abi_version(void);
 const char* sf_last_error(void);
 /* "gfx950" + build flags; lets the host assert it loaded the library it built */
@@ -401,6 +401,21 @@ int sf_im2col_video_tokens(const void* vid, int dtype, int64_t n_clips, int64_t 
 int sf_mel_frontend_clips(const float* wave, int64_t n_clips, int64_t clip_samples, int64_t sample0, int64_t seg_stride, int n_seg,
                           int n_samples, int hop, const float* tw_cos, const float* tw_sin, const float* fb, const int* fb_lo,
                           const int* fb_hi, int n_mels, float* power_ws, float* out, int pad_to, float mean, float std, void* stream);
+
+/* ---- train-time inputs from raw clips (TemporalCropAndOffset(ForSyncabilityTraining), RGBSpatialCrop(is_random=True), RandomHorizontalFlip,
+ * GenerateMultipleSegments(is_start_random=True); dataset/transforms.py:56-95, 200-215, 242-630) ------------------------------------------
+ * Every clip has its own window, drawn on the host (synchformer_amd.augment) and passed as a DEVICE table, so nothing forces a host sync.
+ * sf_im2col_video_crops: vid uint8 (n_clips, clip_frames, 3, H, W), H, W >= 224; table int32 [n_clips][table_ld >= 4] = frame0, y0, x0, flip.
+ * Segment (clip, s) = frames frame0 + s*seg_stride .. +16, spatial crop [y0, +224) x [x0, +224), mirrored along W when flip != 0, RGB
+ * normalisation as in sf_im2col_video.  out: the layout of sf_im2col_video_clips (tok_rows 1568) or sf_im2col_video_tokens (1569).
+ * sf_mel_frontend_starts: sf_mel_frontend_clips with a per-clip device array sample0[n_clips] (int64) instead of one start.
+ * The launchers cannot read the device tables: the kernels clamp every entry into its clip (a bad row reads wrong data, never out of bounds);
+ * the host validates the rows before upload. */
+int sf_im2col_video_crops(const uint8_t* vid, int64_t n_clips, int64_t clip_frames, int H, int W, const int* table, int table_ld, int seg_stride,
+                          int n_seg, uint16_t* out, int tok_rows, void* stream);
+int sf_mel_frontend_starts(const float* wave, int64_t n_clips, int64_t clip_samples, const int64_t* sample0, int64_t seg_stride, int n_seg,
+                           int n_samples, int hop, const float* tw_cos, const float* tw_sin, const float* fb, const int* fb_lo,
+                           const int* fb_hi, int n_mels, float* power_ws, float* out, int pad_to, float mean, float std, void* stream);
 
 /* ---- token masks (Synchformer.forward(vis_mask=, aud_mask=), sync_model.py:38-89) -------------------------------
  * content_keep: bool bytes shaped like the input ((n,16,3,224,224) / (n,F,Ta)), 1 = kept.  tok_keep[n*L + t] = 0 iff the masked

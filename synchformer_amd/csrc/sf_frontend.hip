@@ -17,17 +17,14 @@
 
 // P[seg][t][k] = | sum_m hann[m] * x[reflect(t*hop - 200 + m)] * exp(-2 pi i k (312 + m) / 1024) |^2
 // tw_cos / tw_sin: [MEL_WIN][MEL_BINS] fp32 with the window already multiplied in.
-__global__ __launch_bounds__(192) void mel_stft_power_kernel(const float* __restrict__ wave, int n_samples, int hop, int n_frames,
-                                                              const float* __restrict__ tw_cos, const float* __restrict__ tw_sin,
-                                                              float* __restrict__ P, int n_seg_clip, int64_t clip_samples, int64_t sample0,
-                                                              int64_t seg_stride) {
-  __shared__ float xs[MEL_FT * 160 + MEL_WIN];     // the samples this frame group touches (<= 13*160 + 400 = 2480)
-  const int seg = blockIdx.z, fgp = blockIdx.y, bgp = blockIdx.x;
+// The body of both STFT kernels below: segment `seg` of the launch reads its n_samples from w.
+__device__ __forceinline__ void mel_stft_power_body(const float* __restrict__ w, int seg, int n_samples, int hop, int n_frames,
+                                                    const float* __restrict__ tw_cos, const float* __restrict__ tw_sin, float* __restrict__ P,
+                                                    float* xs) {
+  const int fgp = blockIdx.y, bgp = blockIdx.x;
   const int t0 = fgp * MEL_FT;
   const int nt = min(MEL_FT, n_frames - t0);
   const int span = (nt - 1) * hop + MEL_WIN;
-  // segment seg = (clip, s) starts at sample clip * clip_samples + sample0 + s * seg_stride; reflection stays inside the segment
-  const float* w = wave + (int64_t)(seg / n_seg_clip) * clip_samples + sample0 + (int64_t)(seg % n_seg_clip) * seg_stride;
   for (int i = threadIdx.x; i < span; i += blockDim.x) {
     int idx = t0 * hop - (MEL_NFFT / 2 - (MEL_NFFT - MEL_WIN) / 2) + i;       // t*hop - 512 + 312 + m
     if (idx < 0) idx = -idx;                                                  // reflect padding (center=True)
@@ -54,6 +51,32 @@ __global__ __launch_bounds__(192) void mel_stft_power_kernel(const float* __rest
     if (f < nt) P[((int64_t)seg * n_frames + t0 + f) * MEL_BINS + k] = re[f] * re[f] + im[f] * im[f];
 }
 
+__global__ __launch_bounds__(192) void mel_stft_power_kernel(const float* __restrict__ wave, int n_samples, int hop, int n_frames,
+                                                              const float* __restrict__ tw_cos, const float* __restrict__ tw_sin,
+                                                              float* __restrict__ P, int n_seg_clip, int64_t clip_samples, int64_t sample0,
+                                                              int64_t seg_stride) {
+  __shared__ float xs[MEL_FT * 160 + MEL_WIN];     // the samples this frame group touches (<= 13*160 + 400 = 2480)
+  const int seg = blockIdx.z;
+  // segment seg = (clip, s) starts at sample clip * clip_samples + sample0 + s * seg_stride; reflection stays inside the segment
+  const float* w = wave + (int64_t)(seg / n_seg_clip) * clip_samples + sample0 + (int64_t)(seg % n_seg_clip) * seg_stride;
+  mel_stft_power_body(w, seg, n_samples, hop, n_frames, tw_cos, tw_sin, P, xs);
+}
+
+// Per-clip window starts (train-time offsets and audio jitter, dataset/transforms.py:242-400): segment (clip, s) starts at sample
+// clip * clip_samples + sample0[clip] + s * seg_stride.  sample0 lives on the device, so the launcher cannot check it: the kernel clamps it
+// into [0, max_start] (a bad entry reads wrong samples of its own clip, never outside it); the host validates the starts before upload.
+__global__ __launch_bounds__(192) void mel_stft_power_starts_kernel(const float* __restrict__ wave, int n_samples, int hop, int n_frames,
+                                                                     const float* __restrict__ tw_cos, const float* __restrict__ tw_sin,
+                                                                     float* __restrict__ P, int n_seg_clip, int64_t clip_samples,
+                                                                     const int64_t* __restrict__ sample0, int64_t max_start, int64_t seg_stride) {
+  __shared__ float xs[MEL_FT * 160 + MEL_WIN];
+  const int seg = blockIdx.z;
+  const int64_t clip = seg / n_seg_clip;
+  const int64_t s0 = min(max(sample0[clip], (int64_t)0), max_start);
+  const float* w = wave + clip * clip_samples + s0 + (int64_t)(seg % n_seg_clip) * seg_stride;
+  mel_stft_power_body(w, seg, n_samples, hop, n_frames, tw_cos, tw_sin, P, xs);
+}
+
 // out[seg][j][t] = (log(sum_k P[seg][t][k] * fb[k][j] + 1e-6) - mean) / (2 std) for t < n_frames; (0 - mean)/(2 std) for the
 // padded frames t in [n_frames, pad_to).  fb_lo/fb_hi give each mel filter's non-zero bin range (triangular filters).
 __global__ __launch_bounds__(128) void mel_log_norm_kernel(const float* __restrict__ P, int n_frames, const float* __restrict__ fb,
@@ -73,7 +96,8 @@ __global__ __launch_bounds__(128) void mel_log_norm_kernel(const float* __restri
 
 static int launch_mel(const float* wave, int64_t n_seg, int n_samples, int hop, const float* tw_cos, const float* tw_sin, const float* fb,
                       const int* fb_lo, const int* fb_hi, int n_mels, float* power_ws, float* out, int pad_to, float mean, float std,
-                      int n_seg_clip, int64_t clip_samples, int64_t sample0, int64_t seg_stride, hipStream_t s, const char* who) {
+                      int n_seg_clip, int64_t clip_samples, int64_t sample0, int64_t seg_stride, hipStream_t s, const char* who,
+                      const int64_t* starts = nullptr) {
   SF_CHECK_ARG(wave && tw_cos && tw_sin && fb && fb_lo && fb_hi && power_ws && out, "%s: null pointer", who);
   SF_CHECK_ARG(hop == 160, "%s: hop %d unsupported (160)", who, hop);
   SF_CHECK_ARG(n_mels > 0 && n_mels <= 128, "%s: n_mels %d out of range", who, n_mels);
@@ -84,8 +108,12 @@ static int launch_mel(const float* wave, int64_t n_seg, int n_samples, int hop, 
   SF_CHECK_ARG(n_seg < 65536, "%s: at most 65535 segments per call", who);
   const int use_frames = n_frames < pad_to ? n_frames : pad_to;               // PadOrTruncate truncates longer inputs
   dim3 g1(3, (use_frames + MEL_FT - 1) / MEL_FT, (unsigned)n_seg);
-  hipLaunchKernelGGL(mel_stft_power_kernel, g1, dim3(192), 0, s, wave, n_samples, hop, use_frames, tw_cos, tw_sin, power_ws, n_seg_clip, clip_samples,
-                     sample0, seg_stride);
+  if (starts)
+    hipLaunchKernelGGL(mel_stft_power_starts_kernel, g1, dim3(192), 0, s, wave, n_samples, hop, use_frames, tw_cos, tw_sin, power_ws, n_seg_clip,
+                       clip_samples, starts, clip_samples - (int64_t)(n_seg_clip - 1) * seg_stride - n_samples, seg_stride);
+  else
+    hipLaunchKernelGGL(mel_stft_power_kernel, g1, dim3(192), 0, s, wave, n_samples, hop, use_frames, tw_cos, tw_sin, power_ws, n_seg_clip, clip_samples,
+                       sample0, seg_stride);
   SF_LAUNCH_CHECK();
   dim3 g2((unsigned)pad_to, (unsigned)n_seg);
   hipLaunchKernelGGL(mel_log_norm_kernel, g2, dim3(128), 0, s, power_ws, use_frames, fb, fb_lo, fb_hi, n_mels, out, pad_to, mean,
@@ -109,4 +137,15 @@ extern "C" int sf_mel_frontend_clips(const float* wave, int64_t n_clips, int64_t
                (long long)clip_samples);
   return launch_mel(wave, n_clips * n_seg, n_samples, hop, tw_cos, tw_sin, fb, fb_lo, fb_hi, n_mels, power_ws, out, pad_to, mean, std, n_seg,
                     clip_samples, sample0, seg_stride, (hipStream_t)stream, "sf_mel_frontend_clips");
+}
+
+extern "C" int sf_mel_frontend_starts(const float* wave, int64_t n_clips, int64_t clip_samples, const int64_t* sample0, int64_t seg_stride, int n_seg,
+                                      int n_samples, int hop, const float* tw_cos, const float* tw_sin, const float* fb, const int* fb_lo,
+                                      const int* fb_hi, int n_mels, float* power_ws, float* out, int pad_to, float mean, float std, void* stream) {
+  SF_CHECK_ARG(sample0, "sf_mel_frontend_starts: null sample0");
+  SF_CHECK_ARG(n_seg >= 1 && seg_stride >= 0 && (int64_t)(n_seg - 1) * seg_stride + n_samples <= clip_samples,
+               "sf_mel_frontend_starts: %d segments [s*%lld, +%d) do not fit %lld samples", n_seg, (long long)seg_stride, n_samples,
+               (long long)clip_samples);
+  return launch_mel(wave, n_clips * n_seg, n_samples, hop, tw_cos, tw_sin, fb, fb_lo, fb_hi, n_mels, power_ws, out, pad_to, mean, std, n_seg,
+                    clip_samples, 0, seg_stride, (hipStream_t)stream, "sf_mel_frontend_starts", sample0);
 }

@@ -405,6 +405,88 @@ extern "C" int sf_im2col_video_tokens(const void* vid, int dtype, int64_t n_clip
 }
 
 // ------------------------------------------------------------------------------------------------------
+// The same gather from UNCROPPED uint8 clips (n_clips, clip_frames, 3, H, W), H, W >= 224, with the train-time spatial crop, horizontal
+// flip and temporal window of every clip taken from a device table (RGBSpatialCrop(is_random=True) / RandomHorizontalFlip /
+// TemporalCropAndOffset + GenerateMultipleSegments(is_start_random=True), dataset/transforms.py:56-95, 200-215, 292-500):
+//   table[clip * table_ld + 0..3] = frame0, y0, x0, flip;  segment s of the clip = frames frame0 + s*seg_stride .. +16,
+//   crop pixel (y, x) = source (y0 + y, flip ? x0 + 223 - x : x0 + x).
+// A 16-pixel run now starts at any byte (x0 is random, W arbitrary), so the single 16-byte load of im2col_video_kernel does not apply: the
+// thread reads the 4-byte-aligned words covering its 16 bytes (one dwordx4 at the aligned base + one dword when the run is misaligned) and
+// funnel-shifts them into place with v_alignbyte; a flipped run reads source columns x0 + 208 - 16w .. +15 and reverses the byte order
+// (bswap of the words, taken in reverse).  The bytes then go through load16<SF_U8> - the same fp16 roundings as the uncropped gather.
+// The table is on the device, so the launcher cannot check it: rows are validated on the host before upload (synchformer_amd.augment),
+// and the kernel CLAMPS every row into the clip as a guard - a bad row reads wrong pixels, never outside the clip.
+// ------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void im2col_video_crops_kernel(const uint8_t* __restrict__ vid, const int* __restrict__ table, int table_ld,
+                                                                  bf16_t* __restrict__ out, int64_t total_runs, int n_seg_clip, int64_t clip_frames,
+                                                                  int H, int W, int seg_stride, int tok_rows) {
+  const int64_t run = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (run >= total_runs) {
+    const int64_t z = run - total_runs, n_total = total_runs / (16 * 3 * 224 * 14);
+    if (tok_rows == 1569 && z < n_total * 96) {
+      uint4* dst = reinterpret_cast<uint4*>(out + (z / 96) * 1569 * 1536 + (z % 96) * 16);
+      dst[0] = make_uint4(0u, 0u, 0u, 0u); dst[1] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    return;
+  }
+  const int w = (int)(run % 14);
+  int64_t t = run / 14;
+  const int y = (int)(t % 224); t /= 224;
+  const int c = (int)(t % 3); t /= 3;
+  const int dt = (int)(t % 2); t /= 2;
+  const int f = (int)(t % 8);
+  const int64_t n = t / 8;
+  const int64_t clip = n / n_seg_clip, sidx = n - clip * n_seg_clip;
+  const int* row = table + clip * table_ld;
+  const int span = (n_seg_clip - 1) * seg_stride + 16;
+  const int frame0 = min(max(row[0], 0), (int)(clip_frames - span));
+  const int y0 = min(max(row[1], 0), H - 224), x0 = min(max(row[2], 0), W - 224);
+  const bool flip = row[3] != 0;
+  const int64_t frame = clip * clip_frames + frame0 + sidx * seg_stride + (f * 2 + dt);
+  const int64_t a = ((frame * 3 + c) * H + (y0 + y)) * (int64_t)W + (flip ? x0 + 208 - 16 * w : x0 + 16 * w);
+  const int sh = (int)(a & 3);
+  const uint32_t* base = reinterpret_cast<const uint32_t*>(vid + (a - sh));
+  typedef uint32_t u32x4a4 __attribute__((ext_vector_type(4), aligned(4)));
+  const u32x4a4 lo = *reinterpret_cast<const u32x4a4*>(base);
+  const uint32_t hi = sh ? base[4] : 0u;                        // the fifth word holds bytes of this run only when it is misaligned
+  uint32_t s[4];
+  s[0] = __builtin_amdgcn_alignbyte(lo.y, lo.x, sh);
+  s[1] = __builtin_amdgcn_alignbyte(lo.z, lo.y, sh);
+  s[2] = __builtin_amdgcn_alignbyte(lo.w, lo.z, sh);
+  s[3] = __builtin_amdgcn_alignbyte(hi, lo.w, sh);
+  uint4 px;
+  if (flip) px = make_uint4(__builtin_bswap32(s[3]), __builtin_bswap32(s[2]), __builtin_bswap32(s[1]), __builtin_bswap32(s[0]));
+  else px = make_uint4(s[0], s[1], s[2], s[3]);
+  float v[16];
+  load16<SF_U8>(&px, v);
+  const int h = y >> 4, dh = y & 15;
+  const int64_t orow = n * tok_rows + (tok_rows - 1568) + f * 196 + h * 14 + w;
+  const int col = ((c * 2 + dt) * 16 + dh) * 16;
+  uint4 o0, o1;
+  o0.x = pack_bf2(v[0], v[1]); o0.y = pack_bf2(v[2], v[3]); o0.z = pack_bf2(v[4], v[5]); o0.w = pack_bf2(v[6], v[7]);
+  o1.x = pack_bf2(v[8], v[9]); o1.y = pack_bf2(v[10], v[11]); o1.z = pack_bf2(v[12], v[13]); o1.w = pack_bf2(v[14], v[15]);
+  uint4* dst = reinterpret_cast<uint4*>(out + orow * 1536 + col);
+  dst[0] = o0; dst[1] = o1;
+}
+
+extern "C" int sf_im2col_video_crops(const uint8_t* vid, int64_t n_clips, int64_t clip_frames, int H, int W, const int* table, int table_ld, int seg_stride,
+                                     int n_seg, uint16_t* out, int tok_rows, void* stream) {
+  SF_CHECK_ARG(vid && table && out, "sf_im2col_video_crops: null pointer");
+  SF_CHECK_ARG(H >= 224 && W >= 224 && table_ld >= 4, "sf_im2col_video_crops: frames %dx%d smaller than the 224 crop or table row of %d < 4 entries", H, W, table_ld);
+  SF_CHECK_ARG(tok_rows == 1568 || tok_rows == 1569, "sf_im2col_video_crops: tok_rows %d (1568 or 1569)", tok_rows);
+  SF_CHECK_ARG(n_seg >= 1 && seg_stride >= 0 && (int64_t)(n_seg - 1) * seg_stride + 16 <= clip_frames,
+               "sf_im2col_video_crops: %d segments of stride %d do not fit %lld frames", n_seg, seg_stride, (long long)clip_frames);
+  SF_CHECK_ARG(clip_frames < (1 << 30) && n_clips < (1 << 30), "sf_im2col_video_crops: clip size out of range");
+  const int64_t total = n_clips * n_seg * 16 * 3 * 224 * 14;
+  if (total <= 0) return 0;
+  dim3 grid((unsigned)((total + (tok_rows == 1569 ? n_clips * n_seg * 96 : 0) + 255) / 256)), block(256);
+  hipLaunchKernelGGL(im2col_video_crops_kernel, grid, block, 0, (hipStream_t)stream, vid, table, table_ld, reinterpret_cast<bf16_t*>(out), total, n_seg,
+                     clip_frames, H, W, seg_stride, tok_rows);
+  SF_LAUNCH_CHECK();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------
 // Spectrogram patch gather (im2col for Conv2d(1->768, k16, stride 10), modeling_ast.py:113-117).
 //   spec: fp32 (N, F=128, Ta=66) - the layout Synchformer.forward receives (B,S,1,F,Ta); the reference's
 //         permute to (Ta,F) and transpose back (sync_model.py:84, modeling_ast.py:114-115) cancel out.

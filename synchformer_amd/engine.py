@@ -275,7 +275,9 @@ class SynchformerEngine:
     # ------------------------------------------------------------------------------------------------
     def _visual_chunk(self, vid, out, clip_seg=None, keep=None):
         """vid (n, 16, 3, 224, 224) u8|f16|bf16|f32 on device -> out fp32 (n*8, 768).  a3-a9 of SURVEY §8a.
-        With clip_seg = (frame0, seg_stride, n_seg), vid is (clips, T, 3, 224, 224) and the segments are read in place."""
+        With clip_seg = (frame0, seg_stride, n_seg), vid is (clips, T, 3, 224, 224) and the segments are read in place; with clip_seg = (table, seg_stride, n_seg)
+        (table an int32 device tensor of (frame0, y0, x0, flip) rows, one per clip) vid is uint8 (clips, T, 3, H, W) and every clip is cropped / flipped on the fly."""
+        crops = clip_seg is not None and torch.is_tensor(clip_seg[0])
         n = vid.shape[0] if clip_seg is None else vid.shape[0] * clip_seg[2]
         rows = n * VIS_L
         X = self._buf('X', rows * D, torch.float32).view(rows, D)
@@ -288,6 +290,8 @@ class SynchformerEngine:
             patches = big[:rows * 1536].view(rows, 1536)
             if clip_seg is None:
                 ops.im2col_video_tokens(vid, patches)
+            elif crops:
+                ops.im2col_video_crops(vid, clip_seg[0], patches, clip_seg[1], clip_seg[2], tokens=True)
             else:
                 ops.im2col_video_tokens(vid, patches, *clip_seg)
             ops.broadcast_rows(X, self.v_table_pe, n_seq=n, dst_seq_rows=VIS_L)
@@ -296,6 +300,8 @@ class SynchformerEngine:
             patches = big[:n * VIS_P * 1536].view(n * VIS_P, 1536)
             if clip_seg is None:
                 ops.im2col_video(vid, patches)
+            elif crops:
+                ops.im2col_video_crops(vid, clip_seg[0], patches, clip_seg[1], clip_seg[2], tokens=False)
             else:
                 ops.im2col_video_clips(vid, patches, *clip_seg)
             ops.broadcast_rows(X, self.v_table, n_seq=n, dst_seq_rows=VIS_L)
@@ -783,6 +789,28 @@ class SynchformerEngine:
             nb = min(per, B - b0)
             self._visual_chunk(frames[b0:b0 + nb], out[b0 * n_seg * 8:(b0 + nb) * n_seg * 8], clip_seg=(v_start, v_stride, n_seg))
         return out.view(B, n_seg, 8, D)
+
+    def extract_vfeats_crops(self, frames: torch.Tensor, table: torch.Tensor, seg_stride: int, n_seg: int) -> torch.Tensor:
+        """Uncropped uint8 clips frames (B, T, 3, H, W), H, W >= 224, on device + an int32 device table (B, 4) of (frame0, y0, x0, flip) rows
+        (synchformer_amd.augment.ClipBatch.table) -> (B, n_seg, 8, 768): segment s of clip b = frames table[b, 0] + s*seg_stride .. +16, cropped
+        to 224 x 224 at (y0, x0) and mirrored when flip != 0 - the train-time RGBSpatialCrop / RandomHorizontalFlip / GenerateMultipleSegments
+        done inside the patch gather (sf_im2col_video_crops).  The table stays on the device: nothing here synchronises with the host."""
+        B = frames.shape[0]
+        frames = frames.contiguous()
+        if table.shape[0] != B:
+            raise ValueError(f'extract_vfeats_crops: {table.shape[0]} table rows for {B} clips')
+        out = torch.empty(B * n_seg * 8, D, device=self.dev, dtype=torch.float32)
+        per = max(1, self.seg_chunk // n_seg)                                 # clips per chunk; each chunk gets its own slice of the table rows
+        for b0 in range(0, B, per):
+            nb = min(per, B - b0)
+            self._visual_chunk(frames[b0:b0 + nb], out[b0 * n_seg * 8:(b0 + nb) * n_seg * 8], clip_seg=(table[b0:b0 + nb], seg_stride, n_seg))
+        return out.view(B, n_seg, 8, D)
+
+    def forward_crops(self, frames: torch.Tensor, wave: torch.Tensor, mel, batch) -> torch.Tensor:
+        """Raw clips + per-clip parameters -> logits: frames (B, T, 3, H, W) uint8, wave (B, n_samples) fp32 16 kHz on device, `batch` a
+        synchformer_amd.augment.ClipBatch on the device (e.g. ClipSampler.fixed(...) for the valid / test splits' fixed offsets), `mel` a MelFrontend."""
+        aud = mel.segments_at(wave, batch.sample0, batch.a_stride, batch.n_seg, batch.a_size)
+        return self.sync_transformer(*self.both_towers(lambda: self.extract_vfeats_crops(frames, batch.table, batch.v_stride, batch.n_seg), aud))
 
     def forward_clips(self, frames: torch.Tensor, wave: torch.Tensor, mel, v_fps: int = 25, a_fps: int = 16000, n_segments: int = 14,
                       segment_size_vframes: int = 16, step_size_seg: float = 0.5) -> torch.Tensor:

@@ -106,6 +106,13 @@ class MelFrontend:
         _lib.check(rc, 'sf_mel_frontend_clips')
         return out.reshape(B, n_seg, 1, self.n_mels, self.pad_to)
 
+    def segments_at(self, wave: torch.Tensor, sample0: torch.Tensor, a_stride: int, n_seg: int, a_size: int) -> torch.Tensor:
+        """wave (B, clip_samples) fp32 on device, sample0 int64 (B,) on device -> (B, n_seg, 1, n_mels, pad_to): segments
+        [sample0[b] + s*a_stride, +a_size) of every clip, each clip at its own start (train-time offsets and audio jitter) - `segments` with
+        a per-clip device start, read in place (sf_mel_frontend_starts).  sample0 is read on the device only."""
+        from . import ops
+        return ops.mel_frontend_starts(self, wave, sample0, a_stride, n_seg, a_size)
+
 
 class HostClipPipeline:
     """Raw clips from HOST memory to logits, with the host-to-device transfer of batch i+1 overlapped with the forward of batch i.

@@ -234,6 +234,42 @@ def im2col_video_tokens(vid: torch.Tensor, out: torch.Tensor, frame0: int = 0, s
     return out
 
 
+def im2col_video_crops(vid: torch.Tensor, table: torch.Tensor, out: torch.Tensor, seg_stride: int, n_seg: int, tokens: bool = True):
+    """Uncropped uint8 clips vid (n_clips, T, 3, H, W), H, W >= 224, and a device int32 table (n_clips, >= 4) of rows (frame0, y0, x0, flip) ->
+    out bf16: segment (clip, s) = frames frame0 + s*seg_stride .. +16 of the clip, cropped at (y0, x0) to 224 x 224 and mirrored along W when
+    flip != 0.  tokens=True: the layout of im2col_video_tokens (segments * 1569 rows); False: that of im2col_video_clips (segments * 1568).
+    The table is read on the device only (no host sync); rows are clamped into the clip there, validated on the host by synchformer_amd.augment."""
+    assert vid.is_contiguous() and vid.dim() == 5 and vid.dtype == torch.uint8 and vid.shape[2] == 3, (vid.dtype, tuple(vid.shape))
+    assert table.is_cuda and table.dtype == torch.int32 and table.dim() == 2 and table.shape[0] == vid.shape[0] and table.stride(1) == 1, \
+        (table.dtype, tuple(table.shape))
+    tok_rows = 1569 if tokens else 1568
+    assert out.dtype == torch.bfloat16 and out.is_contiguous() and out.shape[1] == 1536 and out.shape[0] >= vid.shape[0] * n_seg * tok_rows
+    rc = _lib.load().sf_im2col_video_crops(_dev(vid, 'vid'), vid.shape[0], vid.shape[1], vid.shape[3], vid.shape[4], _dev(table, 'table'), table.stride(0),
+                                           seg_stride, n_seg, _dev(out, 'out'), tok_rows, _stream())
+    _lib.check(rc, 'sf_im2col_video_crops')
+    return out
+
+
+def mel_frontend_starts(mel, wave: torch.Tensor, sample0: torch.Tensor, seg_stride: int, n_seg: int, n_samples: int) -> torch.Tensor:
+    """wave fp32 (B, clip_samples) + int64 device sample0 (B,) -> log-mel (B, n_seg, 1, n_mels, pad_to) of the segments [sample0[b] + s*seg_stride,
+    +n_samples) of every clip, with the tables and workspace of `mel` (a frontend.MelFrontend).  Output equals sf_mel_frontend on the materialised
+    segments; sample0 is read on the device only (clamped into the clip there; synchformer_amd.augment validates it on the host)."""
+    w = wave.to(torch.float32).contiguous()
+    assert w.dim() == 2 and sample0.is_cuda and sample0.dtype == torch.int64 and sample0.is_contiguous() and sample0.numel() == w.shape[0], \
+        (tuple(w.shape), sample0.dtype, tuple(sample0.shape))
+    B, clip = w.shape
+    frames = min(n_samples // mel.hop + 1, mel.pad_to)
+    need = B * n_seg * frames * 513
+    if mel._ws is None or mel._ws.numel() < need:
+        mel._ws = torch.empty(need, device=mel.dev, dtype=torch.float32)
+    out = torch.empty(B * n_seg, mel.n_mels, mel.pad_to, device=mel.dev, dtype=torch.float32)
+    rc = _lib.load().sf_mel_frontend_starts(_dev(w, 'wave'), B, clip, _dev(sample0, 'sample0'), seg_stride, n_seg, n_samples, mel.hop, mel.tw_cos.data_ptr(),
+                                            mel.tw_sin.data_ptr(), mel.fb.data_ptr(), mel.fb_lo.data_ptr(), mel.fb_hi.data_ptr(), mel.n_mels,
+                                            mel._ws.data_ptr(), out.data_ptr(), mel.pad_to, mel.mean, mel.std, _stream())
+    _lib.check(rc, 'sf_mel_frontend_starts')
+    return out.reshape(B, n_seg, 1, mel.n_mels, mel.pad_to)
+
+
 def im2col_spec(spec: torch.Tensor, out: torch.Tensor):
     """spec fp32 (n_seg, F, Ta) contiguous -> out bf16 (n_seg*nf*nt, 256)."""
     assert spec.is_contiguous() and spec.dtype == torch.float32 and spec.dim() == 3

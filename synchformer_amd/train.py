@@ -616,6 +616,17 @@ class SyncTrainer(FlatTrainer):
         self.optimizer_step(lr)
         return loss
 
+    def train_step_clips(self, frames: torch.Tensor, wave: torch.Tensor, mel, batch, lr: Optional[float] = None) -> torch.Tensor:
+        """train_step from RAW clips: uint8 frames (B, T, 3, H, W) and fp32 wave (B, n_samples) on device, `batch` a device
+        synchformer_amd.augment.ClipBatch (crop / flip / segment table, per-clip audio starts, targets), `mel` a MelFrontend.  The towers read
+        the clips through sf_im2col_video_crops and sf_mel_frontend_starts; the targets are batch.targets.  No host synchronisation."""
+        aud = mel.segments_at(wave, batch.sample0, batch.a_stride, batch.n_seg, batch.a_size)
+        vf, af = self.engine.both_towers(lambda: self.engine.extract_vfeats_crops(frames, batch.table, batch.v_stride, batch.n_seg), aud)
+        loss = self.forward_backward(vf, af, batch.targets)
+        self.allreduce_grads()
+        self.optimizer_step(lr)
+        return loss
+
 
 class SyncTrainFunction(torch.autograd.Function):
     """autograd bridge: logits = f(frozen features; trainable params).  backward runs the HIP backward and hands the
