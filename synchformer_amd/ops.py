@@ -494,7 +494,7 @@ def qkv_time_attention_mx(x_q: torch.Tensor, x_s: torch.Tensor, w_q: torch.Tenso
 
 def attention_cls_partial_mx(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out_q: torch.Tensor, out_s: torch.Tensor, partials: torch.Tensor, *, n_seq: int,
                              seq_rows: int, n_groups: int, row0: int, group_stride: int, tok_stride: int, n_tok: int, cls_row: int, heads: int, scale: float):
-    """`attention_cls_partial` (head_dim 64, 192 <= n_tok <= 207) writing MXFP8: out_q uint8 (rows, heads*64), out_s uint8 scale planes (heads*64/128, rows_padded, 4)
+    """`attention_cls_partial` (head_dim 64, 193 <= n_tok <= 207) writing MXFP8: out_q uint8 (rows, heads*64), out_s uint8 scale planes (heads*64/128, rows_padded, 4)
     as `mx_scale_planes` lays them out - byte for byte what `quantize_mxfp8` makes of the bf16 output."""
     assert q.dtype == k.dtype == v.dtype == torch.bfloat16 and out_q.dtype == out_s.dtype == torch.uint8 and partials.dtype == torch.float32
     assert _ld(q) == _ld(k) == _ld(v) and partials.numel() >= n_seq * heads * n_groups * 66 and out_s.dim() == 3 and out_s.shape[0] * 2 == heads
