@@ -29,7 +29,7 @@ extern "C" {
 enum { SF_F32 = 0, SF_BF16 = 1, SF_F16 = 2, SF_U8 = 3 };   /* element types */
 enum { SF_EPI_NONE = 0, SF_EPI_GELU = 1 };                  /* GEMM epilogue activation */
 
-#define SF_ABI_VERSION 11
+#define SF_ABI_VERSION 12
 int sf_abi_version(void);
 const char* sf_last_error(void);
 /* "gfx950" + build flags; lets the host assert it loaded the library it built */
@@ -100,6 +100,14 @@ int sf_gemm_mxfp8(const uint8_t* A, int64_t lda, const uint8_t* sA, int64_t ldsa
 /* LayerNorm(768) whose output leaves as MXFP8 (the A operand of the qkv / fc1 MX GEMMs): sf_layernorm768 followed by sf_quantize_mxfp8, in one pass. */
 int sf_layernorm768_mxfp8(const float* x, int64_t ldx, const float* gamma, const float* beta, uint8_t* q, int64_t ldq, uint8_t* scales, int64_t lds,
                           int64_t rows, float eps, void* stream);
+/* sf_gemm_res_ln768 with a PERIODIC residual: X[m,:] = A[m,:] W^T + bias + R[m % period,:], R a table of `period` (>= 64) rows that is not X; everything else
+ * as above (the same kernel body, the product schedule, no measurement hooks).  The patch embedding in one launch - Conv3d vit_helper.py:436-443 on the token-layout
+ * im2col rows + the position / time tables (video_model_builder.py:248-254; period = 1569 rows per segment) + block 0's norm3 (vit_helper.py:366): the table is
+ * read from cache, its broadcast copy is neither written nor read back. */
+int sf_gemm_res_ln768_periodic(const uint16_t* A, int64_t lda, const uint16_t* W, int64_t ldw, const float* bias, const float* R, int64_t ldr, int64_t period,
+                               float* X, int64_t ldx, const float* gamma, const float* beta, float eps, uint16_t* Y, int64_t ldy, int64_t M, int64_t K,
+                               void* stream);
+
 /* sf_gemm_res_ln768 on MXFP8 operands with an MXFP8 output: X = dq(A) dq(W)^T + bias + R (fp32, 768 columns, X may alias R), (Y, sY) = the MXFP8
  * quantisation of bf16(LayerNorm(X) * gamma + beta) - sf_gemm_mxfp8 with the residual epilogue followed by sf_layernorm768_mxfp8, in one launch
  * (`x = x + proj(...)` / `x = x + fc2(...)` and the LayerNorm that opens the next sub-layer, vit_helper.py:364-376, in the fp8 towers).  A (M x K) / W (768 x K)
@@ -274,6 +282,20 @@ int sf_qkv_time_attention(const uint16_t* X, int64_t ldx, const uint16_t* W, int
 int sf_attention_cls(const uint16_t* q, int64_t q_seq_rows, int q_row, const uint16_t* k, const uint16_t* v, int64_t ld,
                      int64_t kv_seq_rows, int kv_row0, int n_keys, uint16_t* out, int64_t ldo, int64_t out_seq_rows,
                      int out_row, int64_t n_seq, int heads, int head_dim, float scale, void* stream);
+
+/* The aggregator layer's attention for its CLS query, pooled in one pass over the fp32 residual stream (motionformer.py:231-245 final norm + regrouping,
+ * 301-334 BaseEncoderLayer of which only output row 0 is read, :332).  That row's query is the layer's cls_token - a parameter - so with zn = norm1(norm(x)) rounded
+ * to bf16 the scores are s[h][j] = U[h] . zn_j + c[h]  (U[h] = scale W_k[h]^T q_h, c[h] = scale q_h . b_k[h], prepared once per weight load) and the value side is
+ * W_v[h] (sum_j p[h][j] zn_j) + b_v[h]: no Q, K or V of the token rows is formed.  Sequence sq = segment * n_groups + g has the keys [zn_cls; token t = 0 .. n_tok - 1
+ * at X row segment * seq_rows + row0 + g * group_stride + t * tok_stride] (the descriptor of sf_attention; visual 1569, 1, 8, 196, 1, 196, audio 74, 2, 6, 1, 6, 12).
+ * x fp32 (row stride ldx), read exactly once; gamma1 / beta1 / eps1 the tower's final norm, gamma2 / beta2 / eps2 the aggregator's norm1; u 12 x 768 fp32, c 12 fp32,
+ * zn_cls 768 fp32 = norm1(cls_token); key_keep NULL or one byte per row of x (0 = masked key, an additive -inf; the CLS key is always kept; all-ones == NULL bit for bit).
+ * g bf16 (n_seq, 12 * 2 * 768), row stride ldg: with G[sq][h][:] = sum_j softmax_j(s[h][.])_j zn_j (fp32), g[sq][h][0][:] = bf16(G) and g[sq][h][1][:] = bf16(G - hi):
+ * the A operand of a bf16 GEMM against [W | W] that sees G at ~16 bits.  fp32 base-2 online softmax, deterministic, one workgroup per sequence:
+ * a sequence's output bits depend on its own rows only. */
+int sf_agg_cls_pool(const float* x, int64_t ldx, int64_t n_seq, int64_t seq_rows, int row0, int n_groups, int group_stride, int tok_stride, int n_tok,
+                    const float* gamma1, const float* beta1, float eps1, const float* gamma2, const float* beta2, float eps2, const float* u, const float* c,
+                    const float* zn_cls, const uint8_t* key_keep, uint16_t* g, int64_t ldg, void* stream);
 
 /* Audio front-end (dataset/transforms.py:815-889; configs/sync.yaml:183-202): wave fp32 (n_seg, n_samples) ->
  * out fp32 (n_seg, n_mels, pad_to) = ((log(mel(|STFT|^2) + 1e-6), right-padded with 0.0) - mean) / (2 std), the

@@ -62,12 +62,16 @@ struct ResLnArgs {
   uint32_t tiles;
   uint32_t phases;
   uint32_t stagger;                                               // measurement hook (SF_RL_STAGGER): every other workgroup of an XCD starts stagger x ~1.2 us late
+  uint32_t r_period;                                              // periodic residual (gemm_res_ln768_periodic_kernel): row m adds R[m % r_period], R a table of r_period rows
 };
 
 // ABL: ablation mask of the measurement builds (tools/bench_gemm_ln.py, SF_RL_ABL): 1 = no residual loads, 2 = no X stores, 4 = no Y stores,
 // 8 = no operand refills after the first two stages, 16 = no MFMAs, 32 = only half of the W pieces are refilled.  The product instantiation is ABL = 0.
-template <int ABL, bool PP>
-__global__ __launch_bounds__(512, 2) void gemm_res_ln768_kernel(ResLnArgs p) {
+// PERIODIC: the residual of row m is row m % r_period of a table R (the patch embedding adds its position table, the same 1569 rows for every segment: the table
+// stays in cache, the broadcast copy of it that R used to be is neither written nor read back).  The only difference is where a wave tile's 64 residual rows are
+// fetched from: one remainder per tile, one conditional subtract per row.
+template <int ABL, bool PP, bool PERIODIC>
+__device__ __forceinline__ void gemm_res_ln768_body(const ResLnArgs& p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -370,7 +374,8 @@ __global__ __launch_bounds__(512, 2) void gemm_res_ln768_kernel(ResLnArgs p) {
     if (rrow0 > p.M - 1) rrow0 = p.M - 1;
     const int64_t rleft = p.M - 1 - rrow0;
     const int rlast = rleft < 63 ? (int)rleft : 63;
-    const void* rbase = reinterpret_cast<const char*>(p.R) + rrow0 * p.ldr * 4;
+    const void* rbase = reinterpret_cast<const char*>(p.R) + (PERIODIC ? (int64_t)0 : rrow0 * p.ldr * 4);
+    const int rper0 = PERIODIC ? (int)((uint32_t)rrow0 % p.r_period) : 0;   // table row of the wave tile's row 0 (r_period >= 64: a tile wraps at most once)
     auto issue_res = [&](int s) {
       if (ABL & 1) return;
       const int c = s >> 2, g = s & 3;
@@ -379,6 +384,7 @@ __global__ __launch_bounds__(512, 2) void gemm_res_ln768_kernel(ResLnArgs p) {
       for (int ps = 0; ps < 4; ++ps) {
         int rl = g * 16 + ps * 4 + lr;
         if (rl > rlast) rl = rlast;
+        if (PERIODIC) { rl += rper0; if (rl >= (int)p.r_period) rl -= (int)p.r_period; }
         vo[ps] = (uint32_t)(rl * (int)p.ldr + gcol0 + c * 64) * 4u;
       }
       rl_dma_r4(vo[0], vo[1], vo[2], vo[3], rbase, ring_lds + (s % 3) * 4096);
@@ -507,6 +513,11 @@ __global__ __launch_bounds__(512, 2) void gemm_res_ln768_kernel(ResLnArgs p) {
   }
 }
 
+template <int ABL, bool PP>
+__global__ __launch_bounds__(512, 2) void gemm_res_ln768_kernel(ResLnArgs p) { gemm_res_ln768_body<ABL, PP, false>(p); }
+template <bool PP>
+__global__ __launch_bounds__(512, 2) void gemm_res_ln768_periodic_kernel(ResLnArgs p) { gemm_res_ln768_body<0, PP, true>(p); }
+
 static thread_local int g_rl_force_sched = -1;   // test hook (per calling thread): -1 default, 0 round 2's loop, 1 quadrant-phased
 extern "C" void sf_gemm_res_ln_force_schedule(int sched) { g_rl_force_sched = sched; }
 
@@ -552,7 +563,7 @@ extern "C" int sf_gemm_res_ln768(const bf16_t* A, int64_t lda, const bf16_t* W, 
   ResLnArgs a;
   a.wk = w_kmajor ? (uint32_t)(RL_N * RL_BK * 2) : (uint32_t)(RL_BK * 2);
   a.A = A; a.lda = lda; a.W = W; a.ldw = ldw; a.bias = bias; a.R = R; a.ldr = ldr; a.X = X; a.ldx = ldx; a.gamma = gamma; a.beta = beta;
-  a.Y = Y; a.ldy = ldy; a.M = M; a.K = (int)K; a.eps = eps;
+  a.Y = Y; a.ldy = ldy; a.M = M; a.K = (int)K; a.eps = eps; a.r_period = 0;
   const int64_t tiles = m_pad / RL_BM;
   SF_CHECK_ARG(tiles < ((int64_t)1 << 31), "sf_gemm_res_ln768: too many tiles");
   a.tiles = (uint32_t)tiles;
@@ -589,6 +600,51 @@ extern "C" int sf_gemm_res_ln768(const bf16_t* A, int64_t lda, const bf16_t* W, 
       case 17: RL_LAUNCH(17, false, RL_LDS); break;
       default: sf_set_error("sf_gemm_res_ln768: unknown SF_RL_ABL %d", abl); return -1;
     }
+  }
+  SF_LAUNCH_CHECK();
+  return 0;
+}
+
+// The same launch with a PERIODIC residual: X[m,:] = A[m,:] W^T + bias + R[m % period,:], R a table of `period` rows (not X).  The patch embedding's call
+// (vit_helper.py:436-443 + the position / time tables added at video_model_builder.py:248-254): period = 1569, the table is read from cache by every segment.
+// Always the product schedule (quadrant-phased when K % 64 == 0 and K >= 128); no measurement hooks.
+extern "C" int sf_gemm_res_ln768_periodic(const bf16_t* A, int64_t lda, const bf16_t* W, int64_t ldw, const float* bias, const float* R, int64_t ldr, int64_t period,
+                                          float* X, int64_t ldx, const float* gamma, const float* beta, float eps, bf16_t* Y, int64_t ldy, int64_t M, int64_t K,
+                                          void* stream) {
+  SF_CHECK_ARG(A && W && R && X && gamma && beta && Y, "sf_gemm_res_ln768_periodic: null pointer");
+  SF_CHECK_ARG(K > 0 && (K % RL_BK) == 0 && K < (1 << 20), "sf_gemm_res_ln768_periodic: K=%lld must be a positive multiple of 32", (long long)K);
+  const bool w_kmajor = ldw == RL_BK && K > RL_BK;
+  SF_CHECK_ARG((lda % 8) == 0 && (ldw % 8) == 0 && lda >= K && (ldw >= K || w_kmajor), "sf_gemm_res_ln768_periodic: lda/ldw must be >= K and multiples of 8 elements");
+  SF_CHECK_ARG((ldr % 4) == 0 && (ldx % 4) == 0 && (ldy % 4) == 0 && ldr >= RL_N && ldx >= RL_N && ldy >= RL_N,
+               "sf_gemm_res_ln768_periodic: ldr/ldx/ldy must be >= 768 and multiples of 4 elements");
+  SF_CHECK_ARG(((uintptr_t)A % 16) == 0 && ((uintptr_t)W % 16) == 0 && ((uintptr_t)R % 16) == 0 && ((uintptr_t)X % 16) == 0 &&
+                   ((uintptr_t)Y % 8) == 0 && ((uintptr_t)gamma % 16) == 0 && ((uintptr_t)beta % 16) == 0 && (!bias || ((uintptr_t)bias % 16) == 0),
+               "sf_gemm_res_ln768_periodic: operands must be 16-byte aligned");
+  SF_CHECK_ARG(period >= 64 && period * ldr * 4 < ((int64_t)1 << 32), "sf_gemm_res_ln768_periodic: period=%lld must be >= 64 rows and the table below 4 GiB", (long long)period);
+  SF_CHECK_ARG((const void*)R != (const void*)X, "sf_gemm_res_ln768_periodic: the residual table cannot be X");
+  if (M <= 0) return 0;
+  const int64_t m_pad = ((M + RL_BM - 1) / RL_BM) * RL_BM;
+  SF_CHECK_ARG(m_pad * ldx * 4 < ((int64_t)1 << 32) && m_pad * ldy * 2 < ((int64_t)1 << 32), "sf_gemm_res_ln768_periodic: X / Y must stay below 4 GiB");
+  SF_CHECK_ARG(128 * lda * 2 + K * 2 < ((int64_t)1 << 31) && 16 * ldw * 2 + K * 2 < ((int64_t)1 << 31), "sf_gemm_res_ln768_periodic: row strides too large");
+  const int n_cu = sf_cu_count("sf_gemm_res_ln768_periodic");
+  if (n_cu <= 0) return -1;
+  ResLnArgs a;
+  a.wk = w_kmajor ? (uint32_t)(RL_N * RL_BK * 2) : (uint32_t)(RL_BK * 2);
+  a.A = A; a.lda = lda; a.W = W; a.ldw = ldw; a.bias = bias; a.R = R; a.ldr = ldr; a.X = X; a.ldx = ldx; a.gamma = gamma; a.beta = beta;
+  a.Y = Y; a.ldy = ldy; a.M = M; a.K = (int)K; a.eps = eps;
+  const int64_t tiles = m_pad / RL_BM;
+  a.tiles = (uint32_t)tiles;
+  a.stagger = K >= 768 ? 12u : 0u;                                  // the late start of the workgroups that own one tile fewer, as in sf_gemm_res_ln768
+  a.phases = 1u;
+  a.r_period = (uint32_t)period;
+  const dim3 grid((unsigned)(tiles < n_cu ? tiles : n_cu)), blk(512);
+  hipStream_t st = (hipStream_t)stream;
+  if ((K % 64) == 0 && K >= 128) {
+    if (int rc = sf_prepare_kernel((const void*)gemm_res_ln768_periodic_kernel<true>, RP_LDS, "sf_gemm_res_ln768_periodic")) return rc;
+    hipLaunchKernelGGL((gemm_res_ln768_periodic_kernel<true>), grid, blk, RP_LDS, st, a);
+  } else {
+    if (int rc = sf_prepare_kernel((const void*)gemm_res_ln768_periodic_kernel<false>, RL_LDS, "sf_gemm_res_ln768_periodic")) return rc;
+    hipLaunchKernelGGL((gemm_res_ln768_periodic_kernel<false>), grid, blk, RL_LDS, st, a);
   }
   SF_LAUNCH_CHECK();
   return 0;

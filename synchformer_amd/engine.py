@@ -69,6 +69,32 @@ class _LN:
         self.b = sd[name + '.bias'].detach().to(dev, torch.float32).contiguous()
 
 
+def agg_cls_operands(cls_token, g1, b1, w_in, b_in, w_o, b_o, heads: int = 12, eps: float = EPS_VIS):
+    """Constant operands of an aggregator layer's attention (BaseEncoderLayer, motionformer.py:301-334).  Only its output row 0 is read (:332) and that row's query
+    is the layer's own cls_token.  With zn = norm1(.) and q = W_q zn_cls + b_q, per head h:  u[h] = scale W_k[h]^T q_h,  c[h] = scale q_h . b_k[h]  (the scores are
+    s_j = u[h] . zn_j + c[h]), and the value and output projections fold into one Linear over the pooled rows G (n_seq, heads, 768):
+        y = sum_h W_o[:, h] W_v[h] G[h] + (W_o b_v + b_o + cls_token)        (the softmax weights sum to one; cls_token is the residual of row 0).
+    sf_agg_cls_pool writes G[h] as bf16 hi | lo (n_seq, heads, 2, 768), so every head's block of w_vo appears twice: [W_o[:, h] W_v[h] | W_o[:, h] W_v[h]].
+    Computed in float64 on the host from the bf16-rounded weights the GEMMs use.  Returns fp32 CPU tensors u (heads, 768), c (heads,), zn_cls (768,), w_vo (768,
+    heads * 2 * 768), b_vo (768,)."""
+    f64 = lambda t: t.detach().to('cpu', torch.float32).to(torch.float64)
+    bfr = lambda t: t.to(torch.float32).to(torch.bfloat16).to(torch.float64)          # the operand values a bf16 GEMM sees
+    x = f64(cls_token).reshape(-1)
+    d = x.numel()
+    zn_cls = (x - x.mean()) / torch.sqrt(x.var(unbiased=False) + eps) * f64(g1) + f64(b1)
+    w_in, b_in, w_o, b_o = bfr(f64(w_in)), f64(b_in), bfr(f64(w_o)), f64(b_o)
+    hd = d // heads
+    scale = hd ** -0.5
+    q = (w_in[:d] @ bfr(zn_cls) + b_in[:d]).view(heads, hd)
+    w_k, b_k = w_in[d:2 * d].view(heads, hd, d), b_in[d:2 * d].view(heads, hd)
+    w_v, b_v = w_in[2 * d:].view(heads, hd, d), b_in[2 * d:]
+    u = scale * torch.einsum('hd,hdk->hk', q, w_k)
+    c = scale * (q * b_k).sum(1)
+    w_vo = torch.cat([(w_o[:, h * hd:(h + 1) * hd] @ w_v[h]).repeat(1, 2) for h in range(heads)], 1)
+    b_vo = w_o @ b_v + b_o + x
+    return tuple(t.to(torch.float32).contiguous() for t in (u, c, zn_cls, w_vo, b_vo))
+
+
 class SynchformerEngine:
     def __init__(self, state_dict: Dict[str, torch.Tensor], device='cuda:0', seg_chunk: int = 224, fp8_towers: bool = False):
         self.dev = torch.device(device)
@@ -202,11 +228,13 @@ class SynchformerEngine:
         self.n_out = self.s_head.w.shape[0]
 
     def _agg(self, sd, p):
+        """Aggregator layer (BaseEncoderLayer, motionformer.py:301-334): its attention is prepared once per weight load for sf_agg_cls_pool, see agg_cls_operands
+        (the towers are frozen in inference and in Stage-2 training)."""
         dev = self.dev
-        return dict(cls=sd[p + '.cls_token'].detach().to(dev, torch.float32).reshape(1, D).contiguous(),
+        u, c, zn_cls, w_vo, b_vo = agg_cls_operands(sd[p + '.cls_token'], sd[p + '.norm1.weight'], sd[p + '.norm1.bias'], sd[p + '.self_attn.in_proj_weight'],
+                                                    sd[p + '.self_attn.in_proj_bias'], sd[p + '.self_attn.out_proj.weight'], sd[p + '.self_attn.out_proj.bias'])
+        return dict(u=u.to(dev), c=c.to(dev), zn_cls=zn_cls.to(dev), vo=_Lin(w_vo, b_vo, dev),
                     norm1=_LN(sd, p + '.norm1', dev), norm2=_LN(sd, p + '.norm2', dev),
-                    qkv=_Lin(sd[p + '.self_attn.in_proj_weight'], sd[p + '.self_attn.in_proj_bias'], dev),
-                    o=_Lin(sd[p + '.self_attn.out_proj.weight'], sd[p + '.self_attn.out_proj.bias'], dev),
                     fc1=_Lin(sd[p + '.linear1.weight'], sd[p + '.linear1.bias'], dev),
                     fc2=_Lin(sd[p + '.linear2.weight'], sd[p + '.linear2.bias'], dev))
 
@@ -236,21 +264,15 @@ class SynchformerEngine:
     # ------------------------------------------------------------------------------------------------
     # shared sub-schedules
     # ------------------------------------------------------------------------------------------------
-    def _agg_layer(self, Z, n_seq, L, agg, out, tag, key_keep=None):
-        """BaseEncoderLayer (motionformer.py:301-334): Z fp32 (n_seq*L, 768) already holds [agg_cls; tokens].
-        Only output row 0 of each sequence is ever read (:332), so everything after K/V is computed for row 0 only."""
-        rows = n_seq * L
-        sfx = 'a' if tag == 'aagg' else ''                              # audio-side workspaces, see extract_afeats
-        zn = self._buf('XN' + sfx, rows * D, torch.bfloat16).view(rows, D)
-        qkv = self._buf('BIG' + sfx, rows * 3 * D, torch.bfloat16).view(rows, 3 * D)
-        ops.layernorm(Z, agg['norm1'].g, agg['norm1'].b, zn, EPS_VIS)
-        ops.gemm(zn, agg['qkv'].w, agg['qkv'].b, qkv)
-        att = self._buf(tag + '_att', n_seq * D, torch.bfloat16).view(n_seq, D)
-        ops.attention_cls(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], att, n_seq=n_seq, q_seq_rows=L, q_row=0,
-                          kv_seq_rows=L, kv_row0=0, n_keys=L, out_seq_rows=1, out_row=0, heads=12, head_dim=64,
-                          scale=0.125, key_keep=key_keep)
+    def _agg_layer(self, X, n_seq, desc, fin, eps_fin, agg, out, tag, key_keep=None):
+        """Final tower norm + BaseEncoderLayer (motionformer.py:231-245, 301-334) on the fp32 residual stream X; `desc` places the aggregator sequences in X
+        (sf_attention's descriptor).  Only output row 0 of each sequence is ever read (:332) and its query is a parameter: one pass over X pools the normalised
+        rows per head (sf_agg_cls_pool), the folded value + output projection (see _agg) runs on the n_seq pooled rows.  key_keep: one flag per row of X."""
+        G = self._buf(tag + '_G', n_seq * 24 * D, torch.bfloat16).view(n_seq, 24 * D)             # per head hi | lo
+        ops.agg_cls_pool(X, G, n_seq=n_seq, norm_a=(fin.g, fin.b), eps_a=eps_fin, norm_b=(agg['norm1'].g, agg['norm1'].b), eps_b=EPS_VIS,
+                         u=agg['u'], c=agg['c'], zn_cls=agg['zn_cls'], key_keep=key_keep, **desc)
         y = self._buf(tag + '_y', n_seq * D, torch.float32).view(n_seq, D)
-        ops.gemm(att, agg['o'].w, agg['o'].b, y, residual=Z, r_map=ops.rowmap(1, 1, L, 0, 0, 0))
+        ops.gemm(G, agg['vo'].w, agg['vo'].b, y)
         yn = self._buf(tag + '_yn', n_seq * D, torch.bfloat16).view(n_seq, D)
         ops.layernorm(y, agg['norm2'].g, agg['norm2'].b, yn, EPS_VIS)
         h = self._buf(tag + '_h', n_seq * FF, torch.bfloat16).view(n_seq, FF)
@@ -281,8 +303,9 @@ class SynchformerEngine:
         n = vid.shape[0] if clip_seg is None else vid.shape[0] * clip_seg[2]
         rows = n * VIS_L
         X = self._buf('X', rows * D, torch.float32).view(rows, D)
-        xn = self._buf('XN', n * 8 * AGG_V * D, torch.bfloat16)[:rows * D].view(rows, D)
-        big = self._buf('BIG', n * 8 * AGG_V * FF, torch.bfloat16)
+        xn = self._buf('XN', rows * D, torch.bfloat16).view(rows, D)
+        big = self._buf('BIG', rows * FF, torch.bfloat16)
+        pe_fused = False
         if rows >= 128 * 64 and self.pe_tokens:
             # patches in the TOKEN layout (a zero row in every segment's CLS slot): the patch-embedding GEMM runs with identity row maps on the persistent kernel
             # (with the row maps it took the 128 x 128 kernel: 1.5 ms per 224-segment launch at 0.55 PFLOP/s).  The CLS rows come out as table + 0 W + bias; the
@@ -294,8 +317,15 @@ class SynchformerEngine:
                 ops.im2col_video_crops(vid, clip_seg[0], patches, clip_seg[1], clip_seg[2], tokens=True)
             else:
                 ops.im2col_video_tokens(vid, patches, *clip_seg)
-            ops.broadcast_rows(X, self.v_table_pe, n_seq=n, dst_seq_rows=VIS_L)
-            ops.gemm(patches, self.v_pe.w, self.v_pe.b, X, residual=X)
+            if self.fuse_ln and not self.fp8_towers:
+                # one launch: patch embedding + position / time table (a periodic residual: row m adds table row m % 1569, read from cache - no broadcast copy
+                # of the table is written or read back) + block 0's norm3
+                n3 = self.v_blocks[0]['norm3']
+                ops.gemm_res_ln(patches, self.v_pe.wk, self.v_pe.b, X, n3.g, n3.b, xn, EPS_VIS, residual=self.v_table_pe, period=VIS_L)
+                pe_fused = True
+            else:
+                ops.broadcast_rows(X, self.v_table_pe, n_seq=n, dst_seq_rows=VIS_L)
+                ops.gemm(patches, self.v_pe.w, self.v_pe.b, X, residual=X)
         else:
             patches = big[:n * VIS_P * 1536].view(n * VIS_P, 1536)
             if clip_seg is None:
@@ -358,7 +388,7 @@ class SynchformerEngine:
         qkv_cls = self._buf('qkv_cls', n * 3 * D, torch.bfloat16).view(n, 3 * D)
         nb = len(self.v_blocks)
         for bi, b in enumerate(self.v_blocks):
-            if bi == 0 or not fuse_ln:
+            if (bi == 0 and not pe_fused) or not fuse_ln:
                 ops.layernorm(X, b['norm3'].g, b['norm3'].b, xn, EPS_VIS)
             if fuse_time2:
                 # temporal qkv + time attention in one launch on 24-patch blocks (sf_qkv_time_attention2); the rows it does not project itself - the CLS row and
@@ -455,7 +485,7 @@ class SynchformerEngine:
         proj_bf16 = 'proj' in self.mx_bf16 and fuse and fuse_space and fuse_time2
         fc2_bf16 = 'fc2' in self.mx_bf16 and fuse and rows >= 128 * 64
         if proj_bf16 or fc2_bf16:
-            big = self._buf('BIG', n * 8 * AGG_V * FF, torch.bfloat16)
+            big = self._buf('BIG', rows * FF, torch.bfloat16)
             att_b, hid_b = big[:rows * D].view(rows, D), big[:rows * FF].view(rows, FF)
         for bi, b in enumerate(self.v_blocks):
             mx = b['mx']
@@ -550,17 +580,10 @@ class SynchformerEngine:
                 ops.gemm_mxfp8(hq, hs, mx['fc2'].q, mx['fc2'].s, mx['fc2'].b, X, residual=X)
 
     def _visual_tail(self, X, n, out, tok_keep):
-        # drop CLS -> final norm -> per-frame sequences with the aggregator CLS in front (mf:231-232, 356-375)
-        Z = self._buf('Z', n * 8 * AGG_V * D, torch.float32).view(n * 8 * AGG_V, D)
-        ops.broadcast_rows(Z, self.v_agg['cls'], n_seq=n * 8, dst_seq_rows=AGG_V)
-        ops.layernorm(X, self.v_norm.g, self.v_norm.b, Z, EPS_VIS, rows=n * VIS_P,
-                      in_map=ops.rowmap(VIS_P, VIS_P, VIS_L, 0, 1, 1), out_map=ops.rowmap(VIS_P, 196, 8 * AGG_V, AGG_V, 1, 1))
-        zkeep = None
-        if tok_keep is not None:                                        # per-frame key mask [agg cls = keep; 196 patches] (motionformer.py:237-243, 308-317)
-            zkeep = torch.ones(n * 8, AGG_V, device=self.dev, dtype=torch.uint8)
-            zkeep[:, 1:] = tok_keep.view(n, VIS_L)[:, 1:].reshape(n * 8, 196)
-            zkeep = zkeep.reshape(-1)
-        self._agg_layer(Z, n * 8, AGG_V, self.v_agg, out, 'vagg', key_keep=zkeep)
+        # drop CLS -> final norm -> per-frame sequences with the aggregator CLS in front (mf:231-232, 356-375): all inside the pooled launch, which reads the
+        # 196 patch rows of frame g of a segment in place (the token keep flags are per row of X already; motionformer.py:237-243, 308-317)
+        self._agg_layer(X, n * 8, dict(seq_rows=VIS_L, row0=1, n_groups=8, group_stride=196, tok_stride=1, n_tok=196), self.v_norm, EPS_VIS, self.v_agg, out, 'vagg',
+                        key_keep=tok_keep)
 
     def extract_vfeats(self, vis: torch.Tensor, vis_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """vis (B, S, Tv=16, C=3, H, W) -> (B, S, 8, 768) fp32 (Synchformer.extract_vfeats, sync_model.py:72-80).
@@ -627,9 +650,8 @@ class SynchformerEngine:
             raise ValueError(f'spectrogram gives {L} tokens but position table has {self.a_table.shape[0]}')
         rows = n * L
         X = self._buf('Xa', rows * D, torch.float32).view(rows, D)
-        agg_rows = n * nt * (nf + 1)
-        xn = self._buf('XNa', max(rows, agg_rows) * D, torch.bfloat16)[:rows * D].view(rows, D)      # the audio branch has its own workspaces:
-        big = self._buf('BIGa', max(rows, agg_rows) * FF, torch.bfloat16)                              # it runs next to the visual one (both_towers)
+        xn = self._buf('XNa', rows * D, torch.bfloat16).view(rows, D)                                  # the audio branch has its own workspaces:
+        big = self._buf('BIGa', rows * FF, torch.bfloat16)                                             # it runs next to the visual one (both_towers)
         patches = big[:n * P * 256].view(n * P, 256)
         ops.im2col_spec(spec, patches)
         ops.broadcast_rows(X, self.a_table, n_seq=n, dst_seq_rows=L)
@@ -647,19 +669,11 @@ class SynchformerEngine:
         for ly in self.a_layers:   # ASTLayer.forward (modeling_ast.py:294-322)
             self._encoder_layer(X, rows, xn, big, ly['ln1'], ly['qkv'], full_attn, ly['o'], ly['ln2'], ly['fc1'], ly['fc2'],
                                 EPS_AST)
-        # final layernorm, drop CLS/DISTILL, regroup (fi, ti) -> per-time-step sequences (ast.py:232-236, 265-266)
-        La = nf + 1
-        Z = self._buf('Za', agg_rows * D, torch.float32).view(agg_rows, D)
-        ops.broadcast_rows(Z, self.a_agg['cls'], n_seq=n * nt, dst_seq_rows=La)
-        ops.layernorm(X, self.a_norm.g, self.a_norm.b, Z, EPS_AST, rows=n * P, in_map=ops.rowmap(P, P, L, 0, 1, 2),
-                      out_map=ops.rowmap(P, nt, nt * La, 1, La, 1))
+        # final layernorm, drop CLS/DISTILL, regroup (fi, ti) -> per-time-step sequences (ast.py:232-236, 265-266): the pooled launch reads token (fi, ti) of a
+        # segment at row 2 + fi * nt + ti, i.e. sequence ti = group ti, token stride nt; the token keep flags are per row of X (ast.py:188-193, 269-271)
         out = torch.empty(n * nt, D, device=self.dev, dtype=torch.float32)
-        zkeep = None
-        if tok_keep is not None:                                        # per-time-step key mask [agg cls = keep; 12 frequency tokens] (ast.py:188-193, 269-271)
-            zkeep = torch.ones(n * nt, La, device=self.dev, dtype=torch.uint8)
-            zkeep[:, 1:] = tok_keep.view(n, L)[:, 2:].reshape(n, nf, nt).transpose(1, 2).reshape(n * nt, nf)
-            zkeep = zkeep.reshape(-1)
-        self._agg_layer(Z, n * nt, La, self.a_agg, out, 'aagg', key_keep=zkeep)
+        self._agg_layer(X, n * nt, dict(seq_rows=L, row0=2, n_groups=nt, group_stride=1, tok_stride=nt, n_tok=nf), self.a_norm, EPS_AST, self.a_agg, out, 'aagg',
+                        key_keep=tok_keep)
         return out.view(B, S, nt, D)
 
     # ------------------------------------------------------------------------------------------------

@@ -144,9 +144,10 @@ def gemm_mx_res_ln(a_q: torch.Tensor, a_s: torch.Tensor, w_q: torch.Tensor, w_s:
 
 
 def gemm_res_ln(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
-                y: torch.Tensor, eps: float, *, M: Optional[int] = None, residual: Optional[torch.Tensor] = None):
+                y: torch.Tensor, eps: float, *, M: Optional[int] = None, residual: Optional[torch.Tensor] = None, period: Optional[int] = None):
     """x[m] = a[m] @ w.T + bias + residual[m] (fp32, in place when residual is None or x), y[m] = LayerNorm(x[m]) * gamma + beta (bf16).
-    a (>= M, K) bf16, w (768, K) bf16; y may be the buffer `a` lives in (each 128-row tile reads its A rows before it writes them)."""
+    a (>= M, K) bf16, w (768, K) bf16; y may be the buffer `a` lives in (each 128-row tile reads its A rows before it writes them).
+    With `period`, `residual` is a table of that many rows and row m adds residual[m % period] (sf_gemm_res_ln768_periodic)."""
     assert a.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and x.dtype == torch.float32 and y.dtype == torch.bfloat16
     K = a.shape[1]
     if w.dim() == 3:                                        # k-step-major weight (K / 32, 768, 32), see kmajor_weight()
@@ -159,6 +160,13 @@ def gemm_res_ln(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], 
     M = a.shape[0] if M is None else M
     r = x if residual is None else residual
     assert r.dtype == torch.float32
+    if period is not None:
+        assert residual is not None and residual.shape[0] >= period and residual.shape[1] == 768 and x.shape[0] >= M and y.shape[0] >= M
+        rc = _lib.load().sf_gemm_res_ln768_periodic(_dev(a, 'a'), _ld(a), w_ptr, ldw, _dev(bias, 'bias') if bias is not None else None,
+                                                    _dev(r, 'residual'), _ld(r), int(period), _dev(x, 'x'), _ld(x), _dev(gamma, 'gamma'), _dev(beta, 'beta'),
+                                                    float(eps), _dev(y, 'y'), _ld(y), M, K, _stream())
+        _lib.check(rc, 'sf_gemm_res_ln768_periodic')
+        return x, y
     rc = _lib.load().sf_gemm_res_ln768(_dev(a, 'a'), _ld(a), w_ptr, ldw, _dev(bias, 'bias') if bias is not None else None,
                                        _dev(r, 'residual'), _ld(r), _dev(x, 'x'), _ld(x), _dev(gamma, 'gamma'), _dev(beta, 'beta'), float(eps),
                                        _dev(y, 'y'), _ld(y), M, K, _stream())
@@ -539,6 +547,25 @@ def attention_cls(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.
     return out
 
 
+def agg_cls_pool(x: torch.Tensor, out: torch.Tensor, *, n_seq: int, seq_rows: int, row0: int, n_groups: int, group_stride: int, tok_stride: int, n_tok: int,
+                 norm_a, eps_a: float, norm_b, eps_b: float, u: torch.Tensor, c: torch.Tensor, zn_cls: torch.Tensor, key_keep: Optional[torch.Tensor] = None):
+    """The aggregator's CLS-query attention pooled in one pass over x (sf_agg_cls_pool): out bf16 (n_seq, 12 * 2 * 768), out[sq, h] = (hi | lo) of sum_j softmax_j(u[h] . zn_j + c[h]) zn_j
+    (hi = bf16 of the fp32 sum, lo = bf16 of the rest; a GEMM against [W | W] sees the sum at ~16 bits) over the keys [zn_cls; zn of the sequence's n_tok token rows], zn = bf16(LN_b(LN_a(x row))).  norm_a / norm_b: (gamma, beta) fp32 pairs; u (12, 768), c (12,),
+    zn_cls (768,) fp32; key_keep uint8, one flag per row of x.  n_seq counts pooled sequences (segments * n_groups)."""
+    assert x.dtype == torch.float32 and x.shape[1] == 768 and out.dtype == torch.bfloat16 and out.shape[1] == 12 * 2 * 768 and out.shape[0] >= n_seq
+    assert n_seq % n_groups == 0 and row0 + (n_groups - 1) * group_stride + max(n_tok - 1, 0) * tok_stride < seq_rows and x.shape[0] >= (n_seq // n_groups) * seq_rows
+    for t, n in ((norm_a[0], 768), (norm_a[1], 768), (norm_b[0], 768), (norm_b[1], 768), (u, 12 * 768), (c, 12), (zn_cls, 768)):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n
+    if key_keep is not None:
+        assert key_keep.dtype == torch.uint8 and key_keep.is_contiguous() and key_keep.numel() >= (n_seq // n_groups) * seq_rows
+    rc = _lib.load().sf_agg_cls_pool(_dev(x, 'x'), _ld(x), n_seq, seq_rows, row0, n_groups, group_stride, tok_stride, n_tok,
+                                     _dev(norm_a[0], 'gamma1'), _dev(norm_a[1], 'beta1'), float(eps_a), _dev(norm_b[0], 'gamma2'), _dev(norm_b[1], 'beta2'), float(eps_b),
+                                     _dev(u, 'u'), _dev(c, 'c'), _dev(zn_cls, 'zn_cls'), _dev(key_keep, 'key_keep') if key_keep is not None else None,
+                                     _dev(out, 'out'), _ld(out), _stream())
+    _lib.check(rc, 'sf_agg_cls_pool')
+    return out
+
+
 def token_mask_video(content_keep: torch.Tensor, w0_sign: torch.Tensor, out: torch.Tensor):
     """content_keep (n, 16, 3, 224, 224) bool|uint8 (True = kept) -> out uint8 (n*1569,) token keep flags (CLS kept)."""
     m = content_keep.contiguous().view(torch.uint8)
@@ -698,9 +725,9 @@ class via_dispatcher:
             count(t.layernorm768)(x, gamma, beta, out, eps)
             return out
 
-        def gemm_res_ln_(a, w, bias, x, gamma, beta, y, eps, *, M=None, residual=None):
+        def gemm_res_ln_(a, w, bias, x, gamma, beta, y, eps, *, M=None, residual=None, period=None):
             if M is not None or residual is not None:
-                return o['gemm_res_ln'](a, w, bias, x, gamma, beta, y, eps, M=M, residual=residual)
+                return o['gemm_res_ln'](a, w, bias, x, gamma, beta, y, eps, M=M, residual=residual, period=period)
             count(t.gemm_res_ln768)(a, w, bias, x, gamma, beta, y, eps)
             return x, y
 
