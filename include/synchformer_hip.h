@@ -29,7 +29,7 @@ extern "C" {
 enum { SF_F32 = 0, SF_BF16 = 1, SF_F16 = 2, SF_U8 = 3 };   /* element types */
 enum { SF_EPI_NONE = 0, SF_EPI_GELU = 1 };                  /* GEMM epilogue activation */
 
-#define SF_ABI_VERSION 12
+#define SF_ABI_VERSION 13
 int sf_abi_version(void);
 const char* sf_last_error(void);
 /* "gfx950" + build flags; lets the host assert it loaded the library it built */
@@ -438,6 +438,43 @@ int sf_im2col_video_crops(const uint8_t* vid, int64_t n_clips, int64_t clip_fram
 int sf_mel_frontend_starts(const float* wave, int64_t n_clips, int64_t clip_samples, const int64_t* sample0, int64_t seg_stride, int n_seg,
                            int n_samples, int hop, const float* tw_cos, const float* tw_sin, const float* fb, const int* fb_lo,
                            const int* fb_hi, int n_mels, float* power_ws, float* out, int pad_to, float mean, float std, void* stream);
+
+/* ---- Stage-1 train-time augmentations from raw clips (transform_sequence_train of configs/segment_avclip.yaml: RGBSpatialCropSometimesUpscale,
+ * GenerateMultipleSegments(is_start_random, audio_jitter_sec), RandomApplyColorDistortion, RandomHorizontalFlip, AudioRandomVolume,
+ * AudioRandomLowpassFilter, AudioRandomGaussNoise; dataset/transforms.py:110-218, 402-500, 672-812) ------------------------------------------
+ * The host draws the decisions (synchformer_amd.augment.Stage1Sampler) into two int32 DEVICE tables; floats are stored as their bit patterns.
+ *   clip table [n_clips][clip_ld >= SF_S1_CLIP_COLS]: frame0, y0, x0, side (224, or 192 = a 192 crop resampled to 224), sample0 (audio jitter included).
+ *   segment table [n_clips * n_seg][seg_ld >= SF_S1_SEG_COLS], row of segment (clip, s) at clip * n_seg + s:
+ *     [0] colour jitter on;  [1..4] the order of its four ops (torchvision's fn_idx: 0 brightness, 1 contrast, 2 saturation, 3 hue; any other
+ *     code is no op; the host sends a permutation - contrast takes the frame mean in front of its FIRST occurrence);
+ *     [5, 6] / [7, 8] / [9, 10] brightness / contrast / saturation blend pair r32 = float32(ratio), q32 = float32(1.0 - ratio), the
+ *     subtraction in double;  [11] hue shift;  [12] gray;  [13] flip;  [14] audio flags SF_S1_AUDIO_*;  [15] noise seed (uint32).
+ * sf_stage1_video_augment: vid uint8 (n_clips, clip_frames, 3, H, W), 4-byte aligned, H, W >= 224 -> out uint8 (n_clips * n_seg, 16, 3, 224, 224),
+ *   16-byte aligned (the input of sf_im2col_video): segment (clip, s) = frames frame0 + s*seg_stride .. +16, crop [y0, +side) x [x0, +side).
+ *   side 192: bilinear to 224, align_corners=False, no antialias, source coordinate (dst + 0.5) * 192/224 - 0.5 with edges clamped, rounded half to even.
+ *   Then, per segment, torchvision 0.15's uint8 tensor arithmetic in fp32 without contraction:
+ *     blend(a, b) = trunc(clamp(r32 * a + q32 * b, 0, 255));  gray = trunc(0.2989 r + 0.587 g + 0.114 b), left to right;
+ *     brightness = blend(x, 0), saturation = blend(x, gray), contrast = blend(x, mean) with mean = float(sum of gray over the FRAME as it is
+ *     when contrast is reached) / 50176;  hue: x / 255 -> RGB->HSV -> h = (h + f) mod 1 -> HSV->RGB -> trunc(v * 255.999);
+ *     then gray into all three channels (RandomGrayscale) and the mirror along W.
+ *   frame_sums: int32 workspace (n_clips * n_seg * 16), the per-frame gray sums (written for jittered segments only).  Two launches.
+ * sf_stage1_audio_augment: wave fp32 (n_clips, clip_samples) -> out fp32 (n_clips * n_seg, n_samples): samples [sample0 + s*seg_stride, +n_samples),
+ *   then per segment, in this order: SF_S1_AUDIO_VOLUME clamp(2 x, -1, 1) (Vol(2.0, 'amplitude')); SF_S1_AUDIO_LOWPASS the biquad
+ *   y[i] = (b0 x[i] + b1 x[i-1] + b2 x[i-2]) - (a1 y[i-1] + a2 y[i-2]) from zero state, output clamped to [-1, 1] (lowpass_biquad -> lfilter(clamp=True);
+ *   coefficients already divided by a0, computed by the host in double); SF_S1_AUDIO_NOISE x + noise_amp * n, n ~ N(0, 1) by Box-Muller from
+ *   Philox4x32-10 with key (seed, 0) and counter (sample index, 0, 0, 0): the same seed gives the same noise.  Two launches.
+ * AudioRandomReverb and AudioRandomPitchShift (sox effects) are NOT built.
+ * The launchers cannot read the device tables: the kernels clamp every entry into its clip (a bad row reads wrong data, never out of bounds);
+ * the host validates the rows before upload. */
+enum { SF_S1_CLIP_FRAME0 = 0, SF_S1_CLIP_Y0 = 1, SF_S1_CLIP_X0 = 2, SF_S1_CLIP_SIDE = 3, SF_S1_CLIP_SAMPLE0 = 4, SF_S1_CLIP_COLS = 5 };
+enum { SF_S1_SEG_JITTER = 0, SF_S1_SEG_OP0 = 1, SF_S1_SEG_BRIGHT_R = 5, SF_S1_SEG_CONTRAST_R = 7, SF_S1_SEG_SATUR_R = 9, SF_S1_SEG_HUE = 11,
+       SF_S1_SEG_GRAY = 12, SF_S1_SEG_FLIP = 13, SF_S1_SEG_AUDIO = 14, SF_S1_SEG_SEED = 15, SF_S1_SEG_COLS = 16 };
+enum { SF_S1_AUDIO_VOLUME = 1, SF_S1_AUDIO_LOWPASS = 2, SF_S1_AUDIO_NOISE = 4 };
+int sf_stage1_video_augment(const uint8_t* vid, int64_t n_clips, int64_t clip_frames, int H, int W, const int* clip_table, int clip_ld,
+                            const int* seg_table, int seg_ld, int seg_stride, int n_seg, int* frame_sums, uint8_t* out, void* stream);
+int sf_stage1_audio_augment(const float* wave, int64_t n_clips, int64_t clip_samples, const int* clip_table, int clip_ld, const int* seg_table,
+                            int seg_ld, int64_t seg_stride, int n_seg, int n_samples, float b0, float b1, float b2, float a1, float a2,
+                            float noise_amp, float* out, void* stream);
 
 /* ---- token masks (Synchformer.forward(vis_mask=, aud_mask=), sync_model.py:38-89) -------------------------------
  * content_keep: bool bytes shaped like the input ((n,16,3,224,224) / (n,F,Ta)), 1 = kept.  tok_keep[n*L + t] = 0 iff the masked

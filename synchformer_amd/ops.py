@@ -278,6 +278,50 @@ def mel_frontend_starts(mel, wave: torch.Tensor, sample0: torch.Tensor, seg_stri
     return out.reshape(B, n_seg, 1, mel.n_mels, mel.pad_to)
 
 
+from .augment import S1_CLIP_COLS, S1_SEG_COLS     # noqa: E402  the table layouts of include/synchformer_hip.h (SF_S1_CLIP_COLS, SF_S1_SEG_COLS)
+
+
+def _stage1_tables(clip_table: torch.Tensor, seg_table: torch.Tensor, n_clips: int, n_seg: int):
+    assert clip_table.is_cuda and clip_table.dtype == torch.int32 and clip_table.dim() == 2 and clip_table.shape[0] == n_clips and \
+        clip_table.shape[1] >= S1_CLIP_COLS and clip_table.stride(1) == 1, (clip_table.dtype, tuple(clip_table.shape))
+    assert seg_table.is_cuda and seg_table.dtype == torch.int32 and seg_table.dim() == 2 and seg_table.shape[0] == n_clips * n_seg and \
+        seg_table.shape[1] >= S1_SEG_COLS and seg_table.stride(1) == 1, (seg_table.dtype, tuple(seg_table.shape))
+
+
+def stage1_video_augment(vid: torch.Tensor, clip_table: torch.Tensor, seg_table: torch.Tensor, out: torch.Tensor, frame_sums: torch.Tensor,
+                         seg_stride: int, n_seg: int):
+    """Uncropped uint8 clips vid (n_clips, T, 3, H, W), H, W >= 224, and the two device int32 tables of a synchformer_amd.augment.Stage1Batch ->
+    out uint8 (n_clips * n_seg, 16, 3, 224, 224): the Stage-1 train transforms on the device (crop or 192 -> 224 upscale, segmenting, colour
+    jitter in the drawn order, gray, flip; include/synchformer_hip.h has the tables and the arithmetic).  frame_sums: int32 workspace of
+    n_clips * n_seg * 16.  The tables are read on the device only (no host sync); entries are clamped into the clip there, validated on the host."""
+    assert vid.is_contiguous() and vid.dim() == 5 and vid.dtype == torch.uint8 and vid.shape[2] == 3, (vid.dtype, tuple(vid.shape))
+    n = vid.shape[0] * n_seg
+    _stage1_tables(clip_table, seg_table, vid.shape[0], n_seg)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == n * 16 * 3 * 224 * 224, (out.dtype, tuple(out.shape))
+    assert frame_sums.dtype == torch.int32 and frame_sums.is_contiguous() and frame_sums.numel() >= n * 16
+    rc = _lib.load().sf_stage1_video_augment(_dev(vid, 'vid'), vid.shape[0], vid.shape[1], vid.shape[3], vid.shape[4], _dev(clip_table, 'clip_table'),
+                                             clip_table.stride(0), _dev(seg_table, 'seg_table'), seg_table.stride(0), seg_stride, n_seg,
+                                             _dev(frame_sums, 'frame_sums'), _dev(out, 'out'), _stream())
+    _lib.check(rc, 'sf_stage1_video_augment')
+    return out
+
+
+def stage1_audio_augment(wave: torch.Tensor, clip_table: torch.Tensor, seg_table: torch.Tensor, out: torch.Tensor, seg_stride: int, n_seg: int,
+                         lowpass: Sequence[float], noise_amp: float = 0.01):
+    """fp32 wave (n_clips, clip_samples) + the two device tables -> out fp32 (n_clips * n_seg, n_samples): the windows [sample0 + s*seg_stride,
+    +n_samples) of every clip, then per segment volume, lowpass biquad (`lowpass` = b0, b1, b2, a1, a2 already divided by a0) and Gaussian
+    noise as the segment's flags say (include/synchformer_hip.h)."""
+    assert wave.is_contiguous() and wave.dim() == 2 and wave.dtype == torch.float32, (wave.dtype, tuple(wave.shape))
+    _stage1_tables(clip_table, seg_table, wave.shape[0], n_seg)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 2 and out.shape[0] == wave.shape[0] * n_seg, (out.dtype, tuple(out.shape))
+    assert len(lowpass) == 5
+    rc = _lib.load().sf_stage1_audio_augment(_dev(wave, 'wave'), wave.shape[0], wave.shape[1], _dev(clip_table, 'clip_table'), clip_table.stride(0),
+                                             _dev(seg_table, 'seg_table'), seg_table.stride(0), seg_stride, n_seg, out.shape[1],
+                                             *[float(c) for c in lowpass], float(noise_amp), _dev(out, 'out'), _stream())
+    _lib.check(rc, 'sf_stage1_audio_augment')
+    return out
+
+
 def im2col_spec(spec: torch.Tensor, out: torch.Tensor):
     """spec fp32 (n_seg, F, Ta) contiguous -> out bf16 (n_seg*nf*nt, 256)."""
     assert spec.is_contiguous() and spec.dtype == torch.float32 and spec.dim() == 3

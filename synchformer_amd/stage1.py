@@ -726,6 +726,31 @@ class AVCLIPTrainer(FlatTrainer):
         self.optimizer_step(lr)
         return loss
 
+    @torch.no_grad()
+    def augment_clips(self, frames: torch.Tensor, wave: torch.Tensor, mel, batch):
+        """RAW clips - uint8 frames (B, T, 3, H, W) and fp32 wave (B, n_samples) on the device - and a device synchformer_amd.augment.Stage1Batch ->
+        the inputs of forward_backward: uint8 segments (B, S, 16, 3, 224, 224), cropped / upscaled, colour-jittered, grayed and flipped by
+        sf_stage1_video_augment, and the log-mel (B, S, 1, F, Ta) of the gathered, volume- / lowpass- / noise-augmented windows
+        (sf_stage1_audio_augment, then `mel`, a MelFrontend).  Four launches in front of the towers, on the current stream; the tables stay on the
+        device, nothing here synchronises with the host.  The buffers are the trainer's workspaces, overwritten by the next call."""
+        B, S = frames.shape[0], batch.n_seg
+        vis = self._buf('s1_segments', (B * S, 16, 3, 224, 224), torch.uint8)
+        ops.stage1_video_augment(frames, batch.clip_table, batch.seg_table, vis, self._buf('s1_frame_sums', (B * S * 16,), torch.int32), batch.v_stride, S)
+        seg_wave = self._buf('s1_wave', (B * S, batch.a_size), torch.float32)
+        ops.stage1_audio_augment(wave, batch.clip_table, batch.seg_table, seg_wave, batch.a_stride, S, batch.lowpass, batch.noise_amp)
+        return vis.view(B, S, 16, 3, 224, 224), mel(seg_wave.view(B, S, batch.a_size))
+
+    def forward_backward_clips(self, frames: torch.Tensor, wave: torch.Tensor, mel, batch, on_ready=None) -> torch.Tensor:
+        """forward_backward from RAW clips (see augment_clips): the augmentation launches, then the unchanged towers, head and backward."""
+        vis, aud = self.augment_clips(frames, wave, mel, batch)
+        return self.forward_backward(vis, aud, on_ready)
+
+    def train_step_clips(self, frames: torch.Tensor, wave: torch.Tensor, mel, batch, lr: Optional[float] = None) -> torch.Tensor:
+        """train_step from RAW clips: the host only draws the decisions (augment.Stage1Sampler), every pixel and sample operation of the Stage-1
+        train transforms runs on the device in front of the towers.  No host synchronisation is added."""
+        vis, aud = self.augment_clips(frames, wave, mel, batch)
+        return self.train_step(vis, aud, lr)
+
     def exposed_comm_ms(self) -> float:
         """Milliseconds the compute stream waited for the gradient buckets in the last train_step (0 without a process group)."""
         if self._comm_ev is None:
