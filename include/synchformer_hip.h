@@ -29,7 +29,7 @@ extern "C" {
 enum { SF_F32 = 0, SF_BF16 = 1, SF_F16 = 2, SF_U8 = 3 };   /* element types */
 enum { SF_EPI_NONE = 0, SF_EPI_GELU = 1 };                  /* GEMM epilogue activation */
 
-#define SF_ABI_VERSION 13
+#define SF_ABI_VERSION 14
 int sf_abi_version(void);
 const char* sf_last_error(void);
 /* "gfx950" + build flags; lets the host assert it loaded the library it built */
@@ -504,6 +504,16 @@ int sf_qkv_time_attention_masked(const uint16_t* X, int64_t ldx, const uint16_t*
  * (n_clips*S x n_clips*S, fp32, clip-major); per clip, window sims are W-long diagonal sums of its S x S block;
  * preds_a[b, j] = argmax_i, preds_v[b, i] = argmax_j over the S - W + 1 (<= 32) shifts. */
 int sf_shift_window_preds(const float* G, int64_t ldg, int n_clips, int S, int W, int64_t* preds_a, int64_t* preds_v, void* stream);
+
+/* Track read-out of a recording: logits (W, C) fp32 (row stride ldl >= C) of W overlapping windows, in time order -> per window the argmax class (lowest index
+ * on ties) and its softmax probability (cls_raw, conf_raw), and the Viterbi path under a cost lam >= 0 per class step (cls_path, conf_path = softmax probability
+ * of the path's class):  e[w, c] = logits[w, c] - max_c logits[w, .];  s_0 = e[0];  s_w[c] = max_p (s_{w-1}[p] - lam * |p - c|) + e[w, c], lowest p on ties ->
+ * backptr[w, c];  s_w -= max_c s_w[c] after every step;  end state = argmax s_{W-1}, lowest index on ties;  backtrace through backptr (W * C bytes, caller-owned
+ * workspace).  2 <= C <= 64 (one lane per class); W == 0 launches nothing.  Non-finite logits give unspecified classes, all inside [0, C).  fp32 statistics.
+ * Stands next to the reference's single-window read-out, decode_single_video_prediction (example.py:38-56), on the class grid of make_class_grid
+ * (dataset/transforms.py:221-239); the reference itself has no recording-level read-out. */
+int sf_track_decode(const float* logits, int64_t ldl, int W, int C, float lam, int32_t* cls_raw, float* conf_raw, int32_t* cls_path, float* conf_path,
+                    uint8_t* backptr, void* stream);
 
 /* Backward of sf_attention for tiny groups (n_tok <= 8, head_dim 64: Motionformer time attention, vit_helper.py:343-344): same
  * addressing as the forward; dq | dk | dv rows of the group's tokens are written (=), the CLS key's dk | dv of every (seq, group) goes to

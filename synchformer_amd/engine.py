@@ -729,6 +729,13 @@ class SynchformerEngine:
         """GlobalTransformer.forward (sync_model.py:150-173).  v (B, Sv, 768), a (B, Sa, 768) fp32 on device (already
         projected) -> logits fp32 (B, n_out); apply_head=False (`attempt_to_apply_heads=False`, :170-172): ln_f of every token, fp32 (B, L, 768)."""
         B, Sv, Sa = v.shape[0], v.shape[1], a.shape[1]
+        v2, a2 = v.reshape(B * Sv, D), a.reshape(B * Sa, D)
+        return self._sync_stack(v2 if v2.is_contiguous() else v2.contiguous(), a2 if a2.is_contiguous() else a2.contiguous(), B, Sv, Sa, apply_head)
+
+    def _sync_stack(self, v2: torch.Tensor, a2: torch.Tensor, B: int, Sv: int, Sa: int, apply_head: bool = True, src_maps=(None, None)) -> torch.Tensor:
+        """The body of global_transformer on 2-D token matrices.  Sequence b reads its Sv visual rows at src_maps[0](b * Sv + i) of v2 and its Sa audio rows at
+        src_maps[1](b * Sa + i) of a2 (row maps; None = the sequences lie back to back): a map whose sequence stride is below Sv / Sa makes the sequences
+        OVERLAPPING windows of one token bank (sync_windows), read in place by the input LayerNorms."""
         L = 2 + Sv + Sa
         table = self._sync_table(Sv, Sa)
         rows = B * L
@@ -736,11 +743,8 @@ class SynchformerEngine:
         xn = self._buf('XNs', rows * D, torch.bfloat16).view(rows, D)
         big = self._buf('BIGs', rows * FF, torch.bfloat16)
         ops.broadcast_rows(X, table, n_seq=B, dst_seq_rows=L)
-        for feat, ln, n_tok, off in ((v, self.s_vln, Sv, 1), (a, self.s_aln, Sa, 2 + Sv)):
-            f2 = feat.reshape(B * n_tok, D)
-            if not f2.is_contiguous():
-                f2 = f2.contiguous()
-            ops.layernorm(f2, ln.g, ln.b, X, EPS_SYNC, out_map=ops.rowmap(n_tok, n_tok, L, 0, 1, off), accumulate=True)
+        for f2, ln, n_tok, off, src in ((v2, self.s_vln, Sv, 1, src_maps[0]), (a2, self.s_aln, Sa, 2 + Sv, src_maps[1])):
+            ops.layernorm(f2, ln.g, ln.b, X, EPS_SYNC, rows=B * n_tok, in_map=src, out_map=ops.rowmap(n_tok, n_tok, L, 0, 1, off), accumulate=True)
         hd = D // self.s_heads
 
         def full_attn(q3, o):
@@ -758,6 +762,65 @@ class SynchformerEngine:
         ops.layernorm(X, self.s_lnf.g, self.s_lnf.b, cls, EPS_SYNC, rows=B, in_map=ops.rowmap(1, 1, L, 0, 0, 0))
         logits = torch.empty(B, self.n_out, device=self.dev, dtype=torch.float32)
         ops.gemm(cls, self.s_head.w, self.s_head.b, logits, M=B)
+        return logits
+
+    # ------------------------------------------------------------------------------------------------
+    # whole recordings: every segment through the towers ONCE (the bank), windows as row-map views of the bank
+    # ------------------------------------------------------------------------------------------------
+    def extract_recording(self, frames: torch.Tensor, wave: torch.Tensor, mel, seg_chunk: Optional[int] = None):
+        """One recording -> its segment feature bank: frames (T, 3, 224, 224) uint8 (after the spatial crop), wave (n,) fp32 16 kHz, each on the device or in
+        host memory (pinned or not), `mel` a frontend.MelFrontend -> (vbank (N, 8, 768), abank (N, 6, 768)) fp32 on the device.  The segment grid is anchored
+        at frame 0 (frontend.recording_geometry): segment s = frames [8 s, 8 s + 16) and samples [5120 s, 5120 s + 10240), N = the whole segments both
+        streams hold; ValueError below one window (14 segments).  The towers run over at most `seg_chunk` (default: the engine's) segments at a time, each
+        chunk on the slice frames[8 s0 : 8 (s0 + n) + 8] / wave[5120 s0 : 5120 (s0 + n) + 5120] (uploaded per chunk when the recording is on the host), so
+        device memory holds one chunk of frames plus the two banks.  Every segment crosses the towers once, however many windows later read it.
+        One recording per call; chunk uploads are not double-buffered and the overlapped tubelets inside a chunk's patch gather are not de-duplicated."""
+        from .frontend import recording_geometry
+        if frames.dim() != 4 or frames.dtype != torch.uint8 or wave.dim() != 1:
+            raise ValueError(f'extract_recording: expected uint8 frames (T, 3, H, W) and a 1-D wave, got {frames.dtype} {tuple(frames.shape)} / {tuple(wave.shape)}')
+        g = recording_geometry(frames.shape[0], wave.shape[0])
+        N = g['n_segments']
+        if N < g['n_window']:
+            raise ValueError(f"extract_recording: {frames.shape[0]} frames / {wave.shape[0]} samples hold {N} segments, one window needs {g['n_window']}")
+        chunk = self.seg_chunk if seg_chunk is None else int(seg_chunk)
+        if chunk < 1:
+            raise ValueError(f'extract_recording: seg_chunk = {chunk}')
+        vs, vz, as_, az = g['v_stride'], g['v_size'], g['a_stride'], g['a_size']
+        vbank = abank = None
+        for s0 in range(0, N, chunk):
+            n = min(chunk, N - s0)
+            f = frames[vs * s0:vs * (s0 + n - 1) + vz].to(self.dev, non_blocking=True)
+            w = wave[as_ * s0:as_ * (s0 + n - 1) + az].to(self.dev, torch.float32, non_blocking=True)
+            aud = mel.segments(w[None], 0, as_, n, az)
+            vf, af = self.both_towers(lambda: self.extract_vfeats_clips(f[None], 0, vs, n), aud)
+            if vbank is None:
+                vbank = torch.empty(N, *vf.shape[2:], device=self.dev, dtype=torch.float32)
+                abank = torch.empty(N, *af.shape[2:], device=self.dev, dtype=torch.float32)
+            vbank[s0:s0 + n].copy_(vf[0])
+            abank[s0:s0 + n].copy_(af[0])
+        return vbank, abank
+
+    def sync_windows(self, vbank: torch.Tensor, abank: torch.Tensor, hop: int = 1, win_chunk: int = 256, n_window: int = 14) -> torch.Tensor:
+        """Segment feature banks (N, tv, 768) / (N, ta, 768) fp32 on the device -> logits (W, n_out) of the W = (N - 14) // hop + 1 windows of 14 segments, window w =
+        segments [w hop, w hop + 14).  vproj / aproj run once over the whole bank; the sync transformer's input LayerNorms then read window w's 14 tv / 14 ta rows
+        through a row map whose sequence stride is hop tv / hop ta: the overlapping windows are never materialised.  `win_chunk` windows per pass bound the workspace."""
+        if vbank.dim() != 3 or abank.dim() != 3 or vbank.shape[0] != abank.shape[0] or vbank.shape[2] != D or abank.shape[2] != D:
+            raise ValueError(f'sync_windows: expected banks (N, tv, {D}) / (N, ta, {D}), got {tuple(vbank.shape)} / {tuple(abank.shape)}')
+        if hop < 1 or win_chunk < 1:
+            raise ValueError(f'sync_windows: hop = {hop}, win_chunk = {win_chunk}')
+        N, tv, ta = vbank.shape[0], vbank.shape[1], abank.shape[1]
+        if N < n_window:
+            raise ValueError(f'sync_windows: a bank of {N} segments holds no window of {n_window}')
+        Sv, Sa = n_window * tv, n_window * ta
+        self._sync_table(Sv, Sa)                                                # ValueError when pos_emb is too short for one window
+        W = (N - n_window) // hop + 1
+        v2 = self.project(vbank.to(self.dev, torch.float32).unsqueeze(0), 'v')[0]
+        a2 = self.project(abank.to(self.dev, torch.float32).unsqueeze(0), 'a')[0]
+        logits = torch.empty(W, self.n_out, device=self.dev, dtype=torch.float32)
+        for w0 in range(0, W, win_chunk):
+            nw = min(win_chunk, W - w0)
+            maps = (ops.rowmap(Sv, Sv, hop * tv, 0, 1, w0 * hop * tv), ops.rowmap(Sa, Sa, hop * ta, 0, 1, w0 * hop * ta))
+            logits[w0:w0 + nw].copy_(self._sync_stack(v2, a2, nw, Sv, Sa, src_maps=maps))
         return logits
 
     def sync_transformer(self, vfeat: torch.Tensor, afeat: torch.Tensor) -> torch.Tensor:
@@ -798,7 +861,15 @@ class SynchformerEngine:
         B = frames.shape[0]
         frames = frames.contiguous()
         out = torch.empty(B * n_seg * 8, D, device=self.dev, dtype=torch.float32)
-        per = max(1, self.seg_chunk // n_seg)                                 # clips per chunk
+        if n_seg > self.seg_chunk:
+            # a clip of more segments than one chunk holds: seg_chunk bounds the workspace here as well - each clip in runs of at most seg_chunk segments, a run
+            # starting at segment s0 reads the clip from frame v_start + s0 * v_stride (segments are independent until vproj)
+            for b in range(B):
+                for s0 in range(0, n_seg, self.seg_chunk):
+                    n = min(self.seg_chunk, n_seg - s0)
+                    self._visual_chunk(frames[b:b + 1], out[(b * n_seg + s0) * 8:(b * n_seg + s0 + n) * 8], clip_seg=(v_start + s0 * v_stride, v_stride, n))
+            return out.view(B, n_seg, 8, D)
+        per = self.seg_chunk // n_seg                                         # clips per chunk
         for b0 in range(0, B, per):
             nb = min(per, B - b0)
             self._visual_chunk(frames[b0:b0 + nb], out[b0 * n_seg * 8:(b0 + nb) * n_seg * 8], clip_seg=(v_start, v_stride, n_seg))

@@ -47,6 +47,22 @@ def segment_ranges(v_len_frames: int, a_len_frames: int, v_fps: int = 25, a_fps:
                 a_size=seg_a)
 
 
+def recording_geometry(v_len_frames: int, a_len_frames: int, hop_segments: int = 1, **segment_kw) -> dict:
+    """Segment grid and window count of a whole recording (engine.extract_recording / engine.sync_windows).  The grid is anchored at frame 0: segment s
+    is frames [s * v_stride, + v_size) and samples [s * a_stride, + a_size), with the strides and sizes of `segment_ranges` for one window (`n_window` =
+    its n_segments, 14); n_segments = how many whole segments BOTH streams hold; window w = segments [w * hop_segments, + n_window),
+    n_windows = (n_segments - n_window) // hop_segments + 1 (0 when the recording is shorter than one window).  A recording of exactly one window
+    (120 frames, 76800 samples) gives segment_ranges' own v_start = a_start = 0."""
+    if hop_segments < 1:
+        raise ValueError(f'hop_segments = {hop_segments}: windows advance by at least one segment')
+    one = segment_ranges(10 ** 9, 10 ** 12, **segment_kw)                        # strides / sizes only: the recording's own lengths enter below
+    v_size, v_stride, a_size, a_stride, n_window = one['v_size'], one['v_stride'], one['a_size'], one['a_stride'], one['n_segments']
+    n_seg = max(0, min((v_len_frames - v_size) // v_stride + 1, (a_len_frames - a_size) // a_stride + 1))
+    n_win = (n_seg - n_window) // hop_segments + 1 if n_seg >= n_window else 0
+    return dict(n_segments=n_seg, n_windows=n_win, n_window=n_window, hop_segments=hop_segments, v_stride=v_stride, v_size=v_size, a_stride=a_stride,
+                a_size=a_size)
+
+
 class MelFrontend:
     def __init__(self, device, sample_rate=16000, n_mels=128, pad_to=66, mean=AST_MEAN, std=AST_STD):
         self.dev = torch.device(device)

@@ -655,6 +655,22 @@ def cross_entropy(logits: torch.Tensor, targets: torch.Tensor, loss: torch.Tenso
     return loss
 
 
+def track_decode(logits: torch.Tensor, lam: float):
+    """Track read-out of a recording's window logits (sf_track_decode): logits fp32 (W, C) on device, rows in time order, 2 <= C <= 64 ->
+    (cls_raw int32 (W,), conf_raw fp32 (W,), cls_path int32 (W,), conf_path fp32 (W,)): the per-window argmax and its softmax probability, and the
+    Viterbi path under a cost `lam` per class step with the softmax probability of the path's class.  Allocates the W * C bytes of back pointers."""
+    assert logits.dtype == torch.float32 and logits.dim() == 2
+    W, C = logits.shape
+    dev = logits.device
+    cls_raw, cls_path = torch.empty(W, device=dev, dtype=torch.int32), torch.empty(W, device=dev, dtype=torch.int32)
+    conf_raw, conf_path = torch.empty(W, device=dev, dtype=torch.float32), torch.empty(W, device=dev, dtype=torch.float32)
+    back = torch.empty(max(W, 1) * C, device=dev, dtype=torch.uint8)
+    rc = _lib.load().sf_track_decode(_dev(logits, 'logits'), _ld(logits) if W else C, W, C, float(lam), _dev(cls_raw, 'cls_raw'), _dev(conf_raw, 'conf_raw'),
+                                     _dev(cls_path, 'cls_path'), _dev(conf_path, 'conf_path'), _dev(back, 'backptr'), _stream())
+    _lib.check(rc, 'sf_track_decode')
+    return cls_raw, conf_raw, cls_path, conf_path
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # PyTorch dispatcher registration (SURVEY §8b "custom-op contract"): the C-ABI launchers as `torch.ops.synchformer.*`
 # out-variant custom ops (device_types = "cuda", i.e. HIP on ROCm).  They mutate their `out` argument and return nothing,
