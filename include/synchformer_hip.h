@@ -26,10 +26,10 @@
 extern "C" {
 #endif
 
-enum { SF_F32 = 0, SF_BF16 = 1, SF_F16 = 2, SF_U8 = 3 };   /* element types */
+enum { SF_F32 = 0, SF_BF16 = 1, SF_F16 = 2, SF_U8 = 3, SF_I16 = 4 };   /* element types (SF_I16: PCM input of sf_resample_wave only) */
 enum { SF_EPI_NONE = 0, SF_EPI_GELU = 1 };                  /* GEMM epilogue activation */
 
-#define SF_ABI_VERSION 14
+#define SF_ABI_VERSION 15
 int sf_abi_version(void);
 const char* sf_last_error(void);
 /* "gfx950" + build flags; lets the host assert it loaded the library it built */
@@ -514,6 +514,28 @@ int sf_shift_window_preds(const float* G, int64_t ldg, int n_clips, int S, int W
  * (dataset/transforms.py:221-239); the reference itself has no recording-level read-out. */
 int sf_track_decode(const float* logits, int64_t ldl, int W, int C, float lam, int32_t* cls_raw, float* conf_raw, int32_t* cls_path, float* conf_path,
                     uint8_t* backptr, void* stream);
+
+/* ---- Ingest of a decoded recording at its native frame rate, size and sample rate: the step the reference leaves to an ffmpeg subprocess in front of its code
+ * (example.py:16-53: fps=25, short side 256, even dimensions, -ar 16000), plus the centre 224 crop of RGBSpatialCrop (dataset/transforms.py:68-95).  The host
+ * computes the geometry (synchformer_amd.ingest) into DEVICE tables.
+ * sf_ingest_video: raw uint8, element (frame f, channel c, row y, column x) at byte f * stride_frame + c * stride_channel + y * stride_row + x * stride_col
+ *   (planar (T, 3, H, W): H W, then W, 1; decoder-style (T, H, W, 3): 1, 3 W, 3), n_src frames of H x W.  Output frame j < T_out is source frame frame_table[j]
+ *   (int32; repeats and skips allowed, clamped into [0, n_src)), resampled by the separable filter
+ *       out[c, r, x] = sum_i y_w[r, i] * sum_k x_w[x, k] * raw[c, y_first[r] + i, x_first[x] + k]        (r, x < 224; horizontal pass first, fp32)
+ *   rounded half to even, clamped to [0, 255], written uint8 planar (T_out, 3, 224, 224), 4-byte aligned: the input of sf_im2col_video_clips.  y_first / x_first
+ *   int32 (224), y_w / x_w fp32 (224, taps), rows zero-padded to taps: the antialiased bicubic tables of F.interpolate(mode='bicubic', antialias=True), already
+ *   sliced to the crop, so the 256-side picture never exists.  Taps that fall outside the picture are skipped (they carry the zero padding); x_first[0] is the lowest
+ *   column read, x_first is expected non-decreasing.  1 <= taps <= 35 (a short side up to 2160 at resize side 256), T_out <= 65535 per launch, W + taps_x <= 5108 (four
+ *   source rows are staged at a time); -1 otherwise.  One launch; the launcher cannot read the tables: the kernel bounds every address.
+ * sf_resample_wave: x (ch, len) fp32 (SF_F32) or int16 PCM (SF_I16, scaled by 1 / 32768), channel stride ld elements, 1 <= ch <= 8 averaged to mono on read ->
+ *   y (len_out) fp32, len_out <= ceil(n len / o):  y[p + n q] = sum_{i < taps} xpad[q o + i] * kernel[p, i],  xpad[m] = x[m - width], 0 outside [0, len): the
+ *   polyphase windowed-sinc bank of torchaudio.functional.resample (kernel fp32 (n, taps), taps = 2 width + o; ingest.resample_kernel).  The filter is centred: no
+ *   delay.  ((255 / n) + 1) o + taps <= 12288 (the input span of 256 outputs is staged in LDS).  fp32 accumulation, taps in ascending order.  One launch. */
+int sf_ingest_video(const uint8_t* raw, int64_t stride_frame, int64_t stride_channel, int64_t stride_row, int64_t stride_col, int n_src, int H, int W,
+                    const int32_t* frame_table, const int32_t* y_first, const float* y_w, int taps_y, const int32_t* x_first, const float* x_w, int taps_x,
+                    uint8_t* out, int T_out, void* stream);
+int sf_resample_wave(const void* x, int dtype, int ch, int64_t ld, int64_t len, const float* kernel, int n, int taps, int o, int width, float* y, int64_t len_out,
+                     void* stream);
 
 /* Backward of sf_attention for tiny groups (n_tok <= 8, head_dim 64: Motionformer time attention, vit_helper.py:343-344): same
  * addressing as the forward; dq | dk | dv rows of the group's tokens are written (=), the CLS key's dk | dv of every (seq, group) goes to

@@ -1,0 +1,286 @@
+// Ingest of a decoded recording at its native geometry: what the reference leaves to an ffmpeg subprocess before any of its code runs
+// (example.py:16-53: fps=25, short side 256, even dimensions, -ar 16000) plus the centre 224 crop of RGBSpatialCrop, as two launches.
+//   sf_ingest_video:   frame pick (frame_table) + antialiased bicubic resize + crop, uint8 -> uint8 planar (T_out, 3, 224, 224).  The resize is separable and the
+//                      two filter tables arrive already sliced to the crop, so only the 224 x 224 outputs are computed: a horizontal pass over the source rows a
+//                      tile of output rows needs (fp32, kept in LDS), then the vertical pass over those rows.
+//   sf_resample_wave:  zero-delay polyphase windowed-sinc resampler (the bank of ingest.resample_kernel), channels averaged on read, zero padding by bounds checks.
+// Both kernels bound every address they form by the sizes the launcher was given: a table with entries outside the source only changes the picture, never the
+// addresses (frame index, first-tap row / column and every tap are clamped or skipped).
+#include "sf_common.h"
+#include "../../include/synchformer_hip.h"
+
+#define ING_OUT 224            // output rows = columns (the model's input size)
+#define ING_TY 8               // output rows per workgroup: 28 row tiles x 3 channels x T_out workgroups
+#define ING_MAX_TAPS 35        // 2 * ceil(2 * scale) + 1 at scale <= 8.5: a short side up to 2160 at resize_side 256
+#define ING_MAX_ROWS 8         // source rows per chunk (4 when the source is wide: the launcher sizes it so that everything fits 64 KiB of LDS)
+#define ING_LDS_BYTES 65536
+#define ING_PF 20              // staged dwords per lane per chunk at most: R * RP / 4 <= 5120
+#define ING_ROW_SLACK 8        // bytes behind a staged row that the horizontal pass may read (always against a zero weight)
+
+// One workgroup = output rows [r0, r0 + 8) of one channel of one output frame, 256 threads.
+//   LDS:  xw   [TW][224]     fp32   the horizontal table transposed (lane x reads xw[.][x]: no bank conflicts), tap j in row j + 3, zero rows around it
+//         yw   [8][taps_y]   fp32   this tile's vertical weights
+//         mid  [R][224]      fp32   the horizontal pass of the current chunk of R source rows
+//         rows [R][RP]       uint8  those source rows from column xlo on, zero beyond the picture (RP = W + taps_x rounded up to 4, + 8)
+// Per chunk:
+//  (1) staging: a lane fetches 4 neighbouring source bytes (one dword where the layout allows it, else 4 byte loads at stride sx: 3 for channels-last) and writes
+//      one LDS dword; consecutive lanes cover consecutive bytes of the row.  The loads of chunk k + 1 are issued into registers before the horizontal pass of
+//      chunk k and written to LDS after its vertical pass: two barriers per chunk, no global latency between them;
+//  (2) horizontal pass, lane = output column, four source rows at a time: the taps [off, off + taps_x) are read as the aligned dwords that cover them, and byte
+//      k of dword d meets weight row 4 d + k + 3 - (off & 3) - tap j = 4 d + k - (off & 3), or a zero row outside [0, taps_x): sums run in ascending j;
+//  (3) vertical pass, lane = four output columns of output rows ty and ty + 4: acc += yw[ty][row - first] * mid[row], rows ascending.
+// Then round half to even, clamp, one 4-byte store per lane: 56 lanes write one full 224-byte line.
+__global__ __launch_bounds__(256) void ingest_video_kernel(const uint8_t* __restrict__ raw, int64_t sf, int64_t sc, int64_t sy, int64_t sx, int n_src, int H, int W,
+                                                            const int32_t* __restrict__ frame_table, const int32_t* __restrict__ y_first,
+                                                            const float* __restrict__ y_w, int taps_y, const int32_t* __restrict__ x_first,
+                                                            const float* __restrict__ x_w, int taps_x, uint8_t* __restrict__ out, int R, int RP, int TW) {
+  extern __shared__ __align__(16) unsigned char ing_lds[];
+  float* xw = (float*)ing_lds;
+  float* yw = xw + TW * ING_OUT;
+  float* mid = yw + ING_TY * taps_y;
+  uint32_t* rows = (uint32_t*)(mid + R * ING_OUT);
+  const int tid = threadIdx.x;
+  const int r0 = blockIdx.x * ING_TY, ch = blockIdx.y, fo = blockIdx.z;
+  int fs = frame_table[fo];
+  fs = fs < 0 ? 0 : (fs >= n_src ? n_src - 1 : fs);
+  const uint8_t* src = raw + (int64_t)fs * sf + (int64_t)ch * sc;
+
+  for (int i = tid; i < TW * ING_OUT; i += 256) {
+    const int row = i / ING_OUT;
+    if (row < 3 || row >= taps_x + 3) xw[i] = 0.f;
+  }
+  for (int i = tid; i < taps_x * ING_OUT; i += 256) {
+    const int x = i / taps_x, j = i - x * taps_x;                               // coalesced read of the (224, taps_x) table
+    xw[(j + 3) * ING_OUT + x] = x_w[i];
+  }
+  for (int i = tid; i < ING_TY * taps_y; i += 256) yw[i] = y_w[(int64_t)r0 * taps_y + i];
+
+  int xlo = x_first[0];
+  xlo = xlo < 0 ? 0 : (xlo > W ? W : xlo);
+  int ys = y_first[r0], ye = y_first[r0 + ING_TY - 1] + taps_y;
+  ys = ys < 0 ? 0 : ys;
+  ye = ye > H ? H : ye;                                                        // rows past the picture carry the tables' zero padding: never read
+
+  // vertical pass ownership: lanes 0..223 = (quad q of 4 columns, row pair rg): output rows r0 + rg and r0 + rg + 4
+  const int q = tid % 56, rg = tid / 56;
+  const bool vert = tid < 224;
+  int yf0 = 0, yf1 = 0;
+  if (vert) { yf0 = y_first[r0 + rg]; yf1 = y_first[r0 + rg + 4]; }
+  float acc0[4] = {0.f, 0.f, 0.f, 0.f}, acc1[4] = {0.f, 0.f, 0.f, 0.f};
+  const int Q4 = RP >> 2;                                                       // dwords per staged row
+  const int nd = (taps_x + 6) >> 2;                                             // aligned dwords that cover taps_x bytes at any byte offset (TW = 4 nd + 3)
+  const int valid_x = W - xlo;
+  const int n_stage = R * Q4;                                                   // <= 256 * ING_PF (launcher)
+
+  // horizontal pass ownership: items (group of 4 source rows, output column) tid and tid + 256 of (R / 4) * 224 <= 448; their table entries are read here, so
+  // that the chunk loop issues no global load but the prefetch
+  const uint32_t* hp[2];
+  const float* hw[2];
+  float* hm[2];
+  bool hon[2];
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int it = tid + 256 * k;
+    hon[k] = it < (R / 4) * ING_OUT;
+    const int g = it / ING_OUT, x = it - g * ING_OUT;
+    int off = hon[k] ? x_first[x] - xlo : 0;
+    off = off < 0 ? 0 : (off > RP - ING_ROW_SLACK - taps_x ? RP - ING_ROW_SLACK - taps_x : off);
+    hp[k] = rows + (g * 4) * Q4 + (off >> 2);
+    hw[k] = xw + (3 - (off & 3)) * ING_OUT + x;
+    hm[k] = mid + (g * 4) * ING_OUT + x;
+  }
+
+  // staging of the R source rows from yc on, through registers: fetch() issues the loads (rows at or beyond ye and columns at or beyond W are zero), commit()
+  // writes them to LDS a phase later, so the loads of chunk k + 1 travel under the horizontal pass of chunk k
+  uint32_t pf[ING_PF];
+  auto fetch = [&](int yc) {
+#pragma unroll
+    for (int k = 0; k < ING_PF; ++k) {
+      const int it = tid + 256 * k;
+      uint32_t v = 0;
+      if (it < n_stage) {
+        const int r = it / Q4, p = (it - r * Q4) * 4;
+        const int y = yc + r;
+        if (y < ye && p < valid_x) {
+          const uint8_t* g = src + (int64_t)y * sy + (int64_t)(xlo + p) * sx;
+          if (sx == 1 && p + 3 < valid_x && ((uintptr_t)g & 3) == 0) {
+            v = *(const uint32_t*)g;
+          } else {
+            v = g[0];
+            if (p + 1 < valid_x) v |= (uint32_t)g[sx] << 8;
+            if (p + 2 < valid_x) v |= (uint32_t)g[2 * sx] << 16;
+            if (p + 3 < valid_x) v |= (uint32_t)g[3 * sx] << 24;
+          }
+        }
+      }
+      pf[k] = v;
+    }
+  };
+  auto commit = [&]() {
+#pragma unroll
+    for (int k = 0; k < ING_PF; ++k) {
+      const int it = tid + 256 * k;
+      if (it < n_stage) rows[it] = pf[k];
+    }
+  };
+
+  if (ys < ye) {
+    fetch(ys);
+    commit();
+  }
+  __syncthreads();                                                             // rows of the first chunk, xw, yw
+  for (int yc = ys; yc < ye; yc += R) {
+    const bool more = yc + R < ye;                                             // block-uniform
+    if (more) fetch(yc + R);
+    // horizontal pass: the taps as aligned dwords against the zero-padded table
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      if (hon[k]) {
+        const uint32_t* p0 = hp[k];
+        const float* wp = hw[k];
+        float h0 = 0.f, h1 = 0.f, h2 = 0.f, h3 = 0.f;
+        for (int d = 0; d < nd; ++d) {
+          const uint32_t v0 = p0[d], v1 = p0[Q4 + d], v2 = p0[2 * Q4 + d], v3 = p0[3 * Q4 + d];
+#pragma unroll
+          for (int b = 0; b < 4; ++b) {
+            const float w = wp[(4 * d + b) * ING_OUT];
+            h0 = fmaf(w, (float)((v0 >> (8 * b)) & 255u), h0);
+            h1 = fmaf(w, (float)((v1 >> (8 * b)) & 255u), h1);
+            h2 = fmaf(w, (float)((v2 >> (8 * b)) & 255u), h2);
+            h3 = fmaf(w, (float)((v3 >> (8 * b)) & 255u), h3);
+          }
+        }
+        float* m = hm[k];
+        m[0] = h0; m[ING_OUT] = h1; m[2 * ING_OUT] = h2; m[3 * ING_OUT] = h3;
+      }
+    }
+    __syncthreads();                                                           // mid complete; every lane is past its reads of rows
+    // vertical pass over the chunk's rows
+    if (vert) {
+      const int n = ye - yc < R ? ye - yc : R;
+      for (int r = 0; r < n; ++r) {
+        const int j0 = yc + r - yf0, j1 = yc + r - yf1;
+        const bool in0 = j0 >= 0 && j0 < taps_y, in1 = j1 >= 0 && j1 < taps_y;
+        if (in0 || in1) {
+          const f32x4 v = *(const f32x4*)(mid + r * ING_OUT + 4 * q);
+          if (in0) {
+            const float w = yw[rg * taps_y + j0];
+            acc0[0] = fmaf(w, v.x, acc0[0]); acc0[1] = fmaf(w, v.y, acc0[1]); acc0[2] = fmaf(w, v.z, acc0[2]); acc0[3] = fmaf(w, v.w, acc0[3]);
+          }
+          if (in1) {
+            const float w = yw[(rg + 4) * taps_y + j1];
+            acc1[0] = fmaf(w, v.x, acc1[0]); acc1[1] = fmaf(w, v.y, acc1[1]); acc1[2] = fmaf(w, v.z, acc1[2]); acc1[3] = fmaf(w, v.w, acc1[3]);
+          }
+        }
+      }
+    }
+    if (more) {
+      commit();
+      __syncthreads();                                                         // rows of the next chunk complete; every lane is past its reads of mid
+    }
+  }
+  if (vert) {
+    uint8_t* o = out + (((int64_t)fo * 3 + ch) * ING_OUT + r0 + rg) * ING_OUT + 4 * q;
+    uint32_t w0 = 0, w1 = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float a = fminf(fmaxf(rintf(acc0[k]), 0.f), 255.f), b = fminf(fmaxf(rintf(acc1[k]), 0.f), 255.f);
+      w0 |= (uint32_t)a << (8 * k);
+      w1 |= (uint32_t)b << (8 * k);
+    }
+    *(uint32_t*)o = w0;
+    *(uint32_t*)(o + 4 * ING_OUT) = w1;
+  }
+}
+
+extern "C" int sf_ingest_video(const uint8_t* raw, int64_t stride_frame, int64_t stride_channel, int64_t stride_row, int64_t stride_col, int n_src, int H, int W,
+                               const int32_t* frame_table, const int32_t* y_first, const float* y_w, int taps_y, const int32_t* x_first, const float* x_w,
+                               int taps_x, uint8_t* out, int T_out, void* stream) {
+  SF_CHECK_ARG(T_out >= 0 && T_out <= 65535, "sf_ingest_video: T_out = %d output frames per launch (0 .. 65535: grid z)", T_out);
+  SF_CHECK_ARG(n_src >= 1 && H >= 1 && W >= 1, "sf_ingest_video: source of %d frames %d x %d", n_src, H, W);
+  SF_CHECK_ARG(taps_y >= 1 && taps_y <= ING_MAX_TAPS && taps_x >= 1 && taps_x <= ING_MAX_TAPS,
+               "sf_ingest_video: taps_y = %d, taps_x = %d out of range (1 .. %d: a short side up to 2160 at resize side 256)", taps_y, taps_x, ING_MAX_TAPS);
+  SF_CHECK_ARG(stride_frame >= 0 && stride_channel >= 0 && stride_row >= 0 && stride_col >= 1, "sf_ingest_video: negative or zero byte stride");
+  if (T_out == 0) return 0;
+  SF_CHECK_ARG(raw && frame_table && y_first && y_w && x_first && x_w && out, "sf_ingest_video: null pointer");
+  SF_CHECK_ARG(((uintptr_t)out & 3) == 0, "sf_ingest_video: out must be 4-byte aligned");
+  SF_CHECK_ARG(W <= 1 << 20, "sf_ingest_video: W = %d is too wide for four staged source rows in LDS at taps_x = %d", W, taps_x);
+  const int RP = ((W + taps_x + 3) & ~3) + ING_ROW_SLACK;
+  const int TW = 4 * ((taps_x + 6) >> 2) + 3;
+  const int fixed = (TW * ING_OUT + ING_TY * taps_y) * 4;
+  int R = (ING_LDS_BYTES - fixed) / (RP + ING_OUT * 4);
+  R = R > ING_MAX_ROWS ? ING_MAX_ROWS : R;
+  if (R > 256 * ING_PF * 4 / RP) R = 256 * ING_PF * 4 / RP;                     // a chunk is staged through ING_PF registers per lane
+  R &= ~3;
+  SF_CHECK_ARG(R >= 4, "sf_ingest_video: W = %d is too wide for four staged source rows in LDS at taps_x = %d", W, taps_x);
+  const int lds = fixed + R * (RP + ING_OUT * 4);
+  hipLaunchKernelGGL(ingest_video_kernel, dim3(ING_OUT / ING_TY, 3, (unsigned)T_out), dim3(256), lds, (hipStream_t)stream, raw, stride_frame, stride_channel,
+                     stride_row, stride_col, n_src, H, W, frame_table, y_first, y_w, taps_y, x_first, x_w, taps_x, out, R, RP, TW);
+  SF_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- audio ---------------------------------------------------------------------------------------------------------------------------------------------------
+#define RES_TILE 256           // output samples per workgroup, one per lane
+#define RES_MAX_SPAN 12288     // floats of input one tile may need (48 KiB of LDS)
+
+// y[p + n q] = sum_i xpad[q o + i] * k[p][i],  xpad[m] = x[m - width] (0 outside [0, len)),  x = the mean of the channels.  One workgroup = 256 consecutive
+// outputs; their input span [q_first o - width, q_last o - width + taps) is staged once in LDS (mono, fp32), then lane t walks the taps of its phase in ascending
+// order.  T = float or int16_t (scaled by 1 / 32768, exact).
+template <typename T>
+__global__ __launch_bounds__(RES_TILE) void resample_wave_kernel(const T* __restrict__ x, int ch, int64_t ld, int64_t len, const float* __restrict__ kern, int n,
+                                                                  int taps, int o, int width, float* __restrict__ y, int64_t len_out) {
+  extern __shared__ __align__(16) float res_lds[];
+  const int64_t j0 = (int64_t)blockIdx.x * RES_TILE;
+  int64_t j1 = j0 + RES_TILE;
+  j1 = j1 > len_out ? len_out : j1;
+  const int64_t q0 = j0 / n, q1 = (j1 - 1) / n;
+  const int span = (int)(q1 - q0) * o + taps;
+  const int64_t s0 = q0 * o - width;
+  const float inv = (sizeof(T) == 2 ? 1.0f / 32768.0f : 1.0f) / (float)ch;
+  for (int m = threadIdx.x; m < span; m += RES_TILE) {
+    const int64_t s = s0 + m;
+    float v = 0.f;
+    if (s >= 0 && s < len) {
+      for (int c = 0; c < ch; ++c) v += (float)x[(int64_t)c * ld + s];
+      v *= inv;
+    }
+    res_lds[m] = v;
+  }
+  __syncthreads();
+  const int64_t j = j0 + threadIdx.x;
+  if (j >= j1) return;
+  const int64_t qq = j / n;
+  const int p = (int)(j - qq * n);
+  const float* xs = res_lds + (int)(qq - q0) * o;
+  const float* kp = kern + (int64_t)p * taps;
+  float acc = 0.f;
+  for (int i = 0; i < taps; ++i) acc = fmaf(xs[i], kp[i], acc);
+  y[j] = acc;
+}
+
+extern "C" int sf_resample_wave(const void* x, int dtype, int ch, int64_t ld, int64_t len, const float* kernel, int n, int taps, int o, int width, float* y,
+                                int64_t len_out, void* stream) {
+  SF_CHECK_ARG(dtype == SF_F32 || dtype == SF_I16, "sf_resample_wave: dtype %d (fp32 = %d or int16 = %d)", dtype, SF_F32, SF_I16);
+  SF_CHECK_ARG(ch >= 1 && ch <= 8, "sf_resample_wave: %d channels out of range (1 .. 8)", ch);
+  SF_CHECK_ARG(len >= 0 && len_out >= 0 && ld >= len, "sf_resample_wave: len = %lld, len_out = %lld, channel stride ld = %lld", (long long)len, (long long)len_out,
+               (long long)ld);
+  SF_CHECK_ARG(n >= 1 && o >= 1 && taps >= 1 && width >= 0, "sf_resample_wave: n = %d phases, o = %d, taps = %d, width = %d", n, o, taps, width);
+  SF_CHECK_ARG(len_out <= (len * n + o - 1) / o, "sf_resample_wave: len_out = %lld above ceil(n len / o) = %lld", (long long)len_out,
+               (long long)((len * n + o - 1) / o));
+  const int64_t span = (int64_t)((RES_TILE - 1) / n + 1) * o + taps;            // q_last - q_first <= (255 / n) + 1
+  SF_CHECK_ARG(span <= RES_MAX_SPAN, "sf_resample_wave: a tile of %d outputs spans %lld input samples (o = %d, n = %d, taps = %d), above %d", RES_TILE,
+               (long long)span, o, n, taps, RES_MAX_SPAN);
+  SF_CHECK_ARG((len_out + RES_TILE - 1) / RES_TILE <= 0x7fffffffLL, "sf_resample_wave: len_out = %lld is too long for one launch", (long long)len_out);
+  if (len_out == 0) return 0;
+  SF_CHECK_ARG(x && kernel && y, "sf_resample_wave: null pointer");
+  const dim3 grid((unsigned)((len_out + RES_TILE - 1) / RES_TILE));
+  const int lds = (int)span * 4;
+  if (dtype == SF_F32)
+    hipLaunchKernelGGL(resample_wave_kernel<float>, grid, dim3(RES_TILE), lds, (hipStream_t)stream, (const float*)x, ch, ld, len, kernel, n, taps, o, width, y, len_out);
+  else
+    hipLaunchKernelGGL(resample_wave_kernel<int16_t>, grid, dim3(RES_TILE), lds, (hipStream_t)stream, (const int16_t*)x, ch, ld, len, kernel, n, taps, o, width, y,
+                       len_out);
+  SF_LAUNCH_CHECK();
+  return 0;
+}

@@ -775,13 +775,23 @@ class SynchformerEngine:
         chunk on the slice frames[8 s0 : 8 (s0 + n) + 8] / wave[5120 s0 : 5120 (s0 + n) + 5120] (uploaded per chunk when the recording is on the host), so
         device memory holds one chunk of frames plus the two banks.  Every segment crosses the towers once, however many windows later read it.
         One recording per call; chunk uploads are not double-buffered and the overlapped tubelets inside a chunk's patch gather are not de-duplicated."""
-        from .frontend import recording_geometry
         if frames.dim() != 4 or frames.dtype != torch.uint8 or wave.dim() != 1:
             raise ValueError(f'extract_recording: expected uint8 frames (T, 3, H, W) and a 1-D wave, got {frames.dtype} {tuple(frames.shape)} / {tuple(wave.shape)}')
-        g = recording_geometry(frames.shape[0], wave.shape[0])
+        return self.extract_recording_from(lambda f0, f1: frames[f0:f1].to(self.dev, non_blocking=True), frames.shape[0], wave, mel, seg_chunk)
+
+    def extract_recording_from(self, frame_fn, n_frames: int, wave16k: torch.Tensor, mel, seg_chunk: Optional[int] = None):
+        """The chunk loop of extract_recording with the frames supplied by a callable: frame_fn(f0, f1) -> uint8 (f1 - f0, 3, 224, 224) on the device, the 25 fps
+        frames [f0, f1) of a recording of `n_frames` (0 <= f0 < f1 <= n_frames; consecutive chunks overlap by 8 frames); wave16k (n,) fp32 16 kHz on the device or
+        in host memory.  ingest.RecordingIngest.frames is such a callable for a recording at its native frame rate and size: the resized recording is
+        never materialised, device memory holds one chunk of it."""
+        from .frontend import recording_geometry
+        if wave16k.dim() != 1:
+            raise ValueError(f'extract_recording: expected a 1-D wave, got {tuple(wave16k.shape)}')
+        wave = wave16k
+        g = recording_geometry(n_frames, wave.shape[0])
         N = g['n_segments']
         if N < g['n_window']:
-            raise ValueError(f"extract_recording: {frames.shape[0]} frames / {wave.shape[0]} samples hold {N} segments, one window needs {g['n_window']}")
+            raise ValueError(f"extract_recording: {n_frames} frames / {wave.shape[0]} samples hold {N} segments, one window needs {g['n_window']}")
         chunk = self.seg_chunk if seg_chunk is None else int(seg_chunk)
         if chunk < 1:
             raise ValueError(f'extract_recording: seg_chunk = {chunk}')
@@ -789,7 +799,7 @@ class SynchformerEngine:
         vbank = abank = None
         for s0 in range(0, N, chunk):
             n = min(chunk, N - s0)
-            f = frames[vs * s0:vs * (s0 + n - 1) + vz].to(self.dev, non_blocking=True)
+            f = frame_fn(vs * s0, vs * (s0 + n - 1) + vz)
             w = wave[as_ * s0:as_ * (s0 + n - 1) + az].to(self.dev, torch.float32, non_blocking=True)
             aud = mel.segments(w[None], 0, as_, n, az)
             vf, af = self.both_towers(lambda: self.extract_vfeats_clips(f[None], 0, vs, n), aud)

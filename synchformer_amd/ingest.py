@@ -1,0 +1,202 @@
+"""Ingest a decoded recording at its native frame rate, size and sample rate.
+
+The reference re-encodes every input through an ffmpeg subprocess before any of its code runs (example.py:16-53: fps=25, short side scaled to 256, dimensions
+cropped to even, -ar 16000) and then takes the centre 224 crop of RGBSpatialCrop.  Here the same step is host geometry (this module: pure Python / torch,
+no device needed) plus two launches (ops.ingest_video: frame pick + antialiased bicubic resize + crop; ops.resample_wave: zero-delay polyphase resampler):
+
+    ing = RecordingIngest(dev, fps_in=(30000, 1001), size_in=(1080, 1920), rate_in=48000, channels_last=True)
+    track = tracker.track_raw(raw_frames, raw_wave, ing)        # raw_frames (T, 1080, 1920, 3) uint8, raw_wave (2, n) int16 or fp32; device or host
+
+What is pinned: the frame pick restates the documented "near" rounding of ffmpeg's fps filter; the resize is F.interpolate(mode='bicubic', antialias=True,
+align_corners=False) (NOT swscale's bicubic: no bit parity with an ffmpeg build is claimed or checkable here); the resampler is
+torchaudio.functional.resample at its defaults (sinc_interp_hann), not swresample.  Out of scope: decoding, YUV input, double-buffered uploads, several
+recordings per call.
+"""
+import math
+from fractions import Fraction
+from typing import Tuple
+
+import torch
+
+CROP = 224
+MAX_TAPS = 35                    # sf_ingest_video's range: a short side up to 2160 at resize_side 256
+
+
+def _fraction(fps) -> Fraction:
+    if isinstance(fps, (tuple, list)):
+        if len(fps) != 2:
+            raise ValueError(f'fps = {fps}: expected a number or a (num, den) pair')
+        f = Fraction(int(fps[0]), int(fps[1]))
+    elif isinstance(fps, float):
+        f = Fraction(fps).limit_denominator(1001)
+    else:
+        f = Fraction(fps)
+    if f <= 0:
+        raise ValueError(f'fps = {fps}')
+    return f
+
+
+def fps_frame_table(n_in: int, fps_in, fps_out=25) -> torch.Tensor:
+    """Which source frame each output frame shows when `n_in` frames at `fps_in` are converted to `fps_out`: int32 (T_out,).
+    fps_in / fps_out: an int, a float (taken as Fraction(fps).limit_denominator(1001): 29.97 -> 30000/1001) or a (num, den) pair; exact rational arithmetic.
+    The rule is the default rounding ("near") of ffmpeg's fps filter as documented: source frame i lands on output slot
+    p_i = floor(i * fps_out / fps_in + 1/2) (half away from zero for i >= 0), the output has T_out = p_{n_in - 1} + 1 frames, and slot j shows the last source
+    frame that landed at or before it, src[j] = max{i : p_i <= j} (frames that share a slot are dropped but the last, empty slots repeat).
+    This RESTATES the documented rule; parity with a particular ffmpeg build (its end-of-stream handling in particular) cannot be checked here and is not claimed."""
+    fi, fo = _fraction(fps_in), _fraction(fps_out)
+    n_in = int(n_in)
+    if n_in <= 0:
+        return torch.empty(0, dtype=torch.int32)
+    if fi == fo:
+        return torch.arange(n_in, dtype=torch.int32)
+    r = fo / fi
+    half = Fraction(1, 2)
+    slots = [math.floor(i * r + half) for i in range(n_in)]                      # non-decreasing
+    src = [0] * (slots[-1] + 1)
+    i = 0
+    for j in range(len(src)):
+        while i + 1 < n_in and slots[i + 1] <= j:
+            i += 1
+        src[j] = i
+    return torch.tensor(src, dtype=torch.int32)
+
+
+def resized_dims(H: int, W: int, side: int = 256) -> Tuple[int, int]:
+    """(Hr, Wr) after `scale=-2:side` / `side:-2` style resizing of example.py:16-53: the short side becomes `side`, the other one d * side // short, cut to even."""
+    H, W, side = int(H), int(W), int(side)
+    if H < 1 or W < 1 or side < 1:
+        raise ValueError(f'resized_dims: {H} x {W} to side {side}')
+    if H <= W:
+        return side, (W * side // H) // 2 * 2
+    return (H * side // W) // 2 * 2, side
+
+
+def _cubic(x: torch.Tensor, a: float = -0.5) -> torch.Tensor:
+    x = x.abs()
+    near = ((a + 2) * x - (a + 3)) * x * x + 1
+    far = ((a * x - 5 * a) * x + 8 * a) * x - 4 * a
+    return torch.where(x < 1, near, torch.where(x < 2, far, torch.zeros_like(x)))
+
+
+def aa_bicubic_table(n_in: int, n_out: int, dtype=torch.float32):
+    """The separable filter of F.interpolate(mode='bicubic', antialias=True, align_corners=False) along one axis, n_in -> n_out samples (cubic a = -0.5):
+    (first int32 (n_out,), weights fp32 (n_out, taps), taps) with out[i] = sum_j weights[i, j] * in[first[i] + j].  scale = n_in / n_out; when downscaling the
+    kernel is stretched by scale (support 2 scale), otherwise support 2; taps = 2 ceil(support) + 1; rows are normalised to sum 1 in float64, stored fp32,
+    zero-padded to `taps` (first[i] + j may then pass n_in - 1: those weights are zero).  At scale 1 it is the identity.  dtype=torch.float64 returns the weights
+    before the fp32 rounding (for checks of the formula itself)."""
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f'aa_bicubic_table: {n_in} -> {n_out}')
+    scale = n_in / n_out
+    support = 2.0 * scale if scale >= 1.0 else 2.0
+    inv = 1.0 / scale if scale >= 1.0 else 1.0
+    taps = 2 * math.ceil(support) + 1
+    first = torch.zeros(n_out, dtype=torch.int32)
+    w = torch.zeros(n_out, taps, dtype=torch.float64)
+    j = torch.arange(taps, dtype=torch.float64)
+    for i in range(n_out):
+        c = scale * (i + 0.5)
+        xmin = max(0, int(c - support + 0.5))
+        xsize = min(n_in, int(c + support + 0.5)) - xmin
+        row = _cubic((j[:xsize] + xmin - c + 0.5) * inv)
+        first[i] = xmin
+        w[i, :xsize] = row / row.sum()
+    return first, w.to(dtype), taps
+
+
+def resample_kernel(rate_in: int, rate_out: int = 16000, lowpass_filter_width: int = 6, rolloff: float = 0.99):
+    """The polyphase windowed-sinc bank of torchaudio.functional.resample at its defaults (sinc_interp_hann): (kernel fp32 (n, 2 width + o), width, o, n) with
+    o = rate_in / gcd, n = rate_out / gcd.  Output y[p + n q] = sum_i xpad[q o + i] * kernel[p, i] on x zero-padded by (width, width + o), cut to
+    ceil(n len / o) samples.  The filter is centred on the output sample's own time: no delay (a sync model cannot tolerate one)."""
+    rate_in, rate_out = int(rate_in), int(rate_out)
+    if rate_in < 1 or rate_out < 1:
+        raise ValueError(f'resample_kernel: {rate_in} -> {rate_out} Hz')
+    g = math.gcd(rate_in, rate_out)
+    o, n = rate_in // g, rate_out // g
+    base = min(o, n) * rolloff
+    width = math.ceil(lowpass_filter_width * o / base)
+    idx = torch.arange(-width, width + o, dtype=torch.float64) / o
+    t = (-torch.arange(n, dtype=torch.float64)[:, None] / n + idx[None]) * base
+    t = t.clamp(-lowpass_filter_width, lowpass_filter_width)
+    win = torch.cos(t * math.pi / lowpass_filter_width / 2) ** 2
+    tp = t * math.pi
+    sinc = torch.where(tp == 0, torch.ones_like(tp), tp.sin() / torch.where(tp == 0, torch.ones_like(tp), tp))
+    return (sinc * win * (base / o)).float(), width, o, n
+
+
+class RecordingIngest:
+    """The geometry of one kind of recording, tables on the device, built once.
+    fps_in: int, float or (num, den); size_in = (H, W) of the raw frames; rate_in: Hz; channels_last: raw frames are (T, H, W, 3) as decoders hand them out,
+    otherwise planar (T, 3, H, W); resize_side: what the short side is scaled to (256, the even cut of the other side as in example.py); crop stays 224, centred
+    with RGBSpatialCrop's origin int(round((Hr - 224) / 2.)).  ValueError on resize_side < crop, crop != 224, or a source so large that a filter row passes
+    35 taps (short side above ~2160 at resize_side 256)."""
+
+    def __init__(self, device, fps_in, size_in, rate_in: int, channels_last: bool = False, resize_side: int = 256, crop: int = CROP):
+        if crop != CROP:
+            raise ValueError(f'crop = {crop}: the model takes {CROP} x {CROP} frames')
+        if resize_side < crop:
+            raise ValueError(f'resize_side = {resize_side} below the {crop} crop')
+        self.dev = torch.device(device)
+        self.fps_in, self.rate_in, self.channels_last = _fraction(fps_in), int(rate_in), bool(channels_last)
+        self.H, self.W = int(size_in[0]), int(size_in[1])
+        self.Hr, self.Wr = resized_dims(self.H, self.W, resize_side)
+        if self.Hr < crop or self.Wr < crop:
+            raise ValueError(f'{self.H} x {self.W} resizes to {self.Hr} x {self.Wr}, below the {crop} crop')
+        self.y0, self.x0 = int(round((self.Hr - crop) / 2.)), int(round((self.Wr - crop) / 2.))
+        yf, yw, ty = aa_bicubic_table(self.H, self.Hr)
+        xf, xw, tx = aa_bicubic_table(self.W, self.Wr)
+        if max(ty, tx) > MAX_TAPS:
+            raise ValueError(f'{self.H} x {self.W} -> {self.Hr} x {self.Wr} needs {ty} x {tx} filter taps, the kernel takes {MAX_TAPS} (a short side up to 2160 at 256)')
+        self.taps_y, self.taps_x = ty, tx
+        self.y_first, self.y_w = yf[self.y0:self.y0 + crop].contiguous().to(self.dev), yw[self.y0:self.y0 + crop].contiguous().to(self.dev)
+        self.x_first, self.x_w = xf[self.x0:self.x0 + crop].contiguous().to(self.dev), xw[self.x0:self.x0 + crop].contiguous().to(self.dev)
+        if self.rate_in == 16000:
+            self.kernel, self.width, self.o, self.n = torch.ones(1, 1), 0, 1, 1   # down-mix / PCM scaling only
+        else:
+            self.kernel, self.width, self.o, self.n = resample_kernel(self.rate_in)
+        self.kernel = self.kernel.contiguous().to(self.dev)
+        self._tables = {}
+
+    def frame_table(self, n_in: int) -> torch.Tensor:
+        """fps_frame_table(n_in, fps_in) (host, cached per n_in)."""
+        if n_in not in self._tables:
+            self._tables = {n_in: fps_frame_table(n_in, self.fps_in)}
+        return self._tables[n_in]
+
+    def n_frames(self, n_in: int) -> int:
+        """25 fps frames that n_in raw frames give."""
+        return int(self.frame_table(n_in).numel())
+
+    def n_samples(self, n_in: int) -> int:
+        """16 kHz samples that n_in raw samples give: ceil(n * n_in / o)."""
+        return -(-self.n * int(n_in) // self.o)
+
+    def _check_frames(self, raw: torch.Tensor):
+        want = (self.H, self.W, 3) if self.channels_last else (3, self.H, self.W)
+        if raw.dim() != 4 or raw.dtype != torch.uint8 or tuple(raw.shape[1:]) != want:
+            raise ValueError(f'raw frames: expected uint8 (T, {", ".join(map(str, want))}), got {raw.dtype} {tuple(raw.shape)}')
+
+    def frames(self, raw: torch.Tensor, j0: int, j1: int) -> torch.Tensor:
+        """25 fps frames [j0, j1) of the recording, resized and cropped: uint8 (j1 - j0, 3, 224, 224) on the device.  raw: all the raw frames, device or host; from
+        a host tensor only the source frames frame_table[j0:j1] spans are uploaded."""
+        self._check_frames(raw)
+        table = self.frame_table(raw.shape[0])
+        if not 0 <= j0 <= j1 <= table.numel():
+            raise ValueError(f'frames [{j0}, {j1}) of {table.numel()}')
+        from . import ops
+        if j1 == j0:
+            return torch.empty(0, 3, CROP, CROP, device=self.dev, dtype=torch.uint8)
+        t = table[j0:j1]
+        lo, hi = int(t[0]), int(t[-1]) + 1                                       # the table is non-decreasing
+        src = raw[lo:hi].to(self.dev, non_blocking=True)
+        return ops.ingest_video(src, self.channels_last, (t - lo).to(self.dev, non_blocking=True), self.y_first, self.y_w, self.x_first, self.x_w)
+
+    def wave(self, raw_wave: torch.Tensor) -> torch.Tensor:
+        """raw_wave (n,) or (ch, n), fp32 or int16 PCM, device or host -> mono fp32 16 kHz (n16k,) on the device.  A mono fp32 wave at 16 kHz is returned as it is."""
+        if raw_wave.dim() not in (1, 2) or raw_wave.dtype not in (torch.float32, torch.int16) or (raw_wave.dim() == 2 and not 1 <= raw_wave.shape[0] <= 8):
+            raise ValueError(f'raw wave: expected fp32 or int16 (n,) or (ch <= 8, n), got {raw_wave.dtype} {tuple(raw_wave.shape)}')
+        x = raw_wave.to(self.dev, non_blocking=True)
+        if self.rate_in == 16000 and x.dtype == torch.float32 and (x.dim() == 1 or x.shape[0] == 1):
+            return x.reshape(-1)
+        from . import ops
+        return ops.resample_wave(x, self.kernel, self.o, self.width)

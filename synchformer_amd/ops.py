@@ -671,6 +671,60 @@ def track_decode(logits: torch.Tensor, lam: float):
     return cls_raw, conf_raw, cls_path, conf_path
 
 
+INGEST_OUT, INGEST_MAX_TAPS = 224, 35
+
+
+def ingest_video(raw: torch.Tensor, channels_last: bool, frame_table: torch.Tensor, y_first: torch.Tensor, y_w: torch.Tensor, x_first: torch.Tensor,
+                 x_w: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Frame pick + antialiased resize + crop in one launch (sf_ingest_video): raw uint8 on the device, (n_src, 3, H, W) or - channels_last - (n_src, H, W, 3),
+    any strides (a view is read in place); frame_table int32 (T_out,) of source frame indices inside [0, n_src); y_first / x_first int32 (224,) and
+    y_w / x_w fp32 (224, taps) contiguous: the filter tables already sliced to the crop -> uint8 (T_out, 3, 224, 224)."""
+    if raw.dim() != 4 or raw.dtype != torch.uint8 or raw.shape[3 if channels_last else 1] != 3:
+        raise ValueError(f'ingest_video: expected uint8 frames (n, 3, H, W) or channels_last (n, H, W, 3), got {raw.dtype} {tuple(raw.shape)}')
+    n_src = raw.shape[0]
+    (H, W), (sf, sc, sy, sx) = ((raw.shape[1], raw.shape[2]), (raw.stride(i) for i in (0, 3, 1, 2))) if channels_last else \
+        ((raw.shape[2], raw.shape[3]), raw.stride())
+    assert min(sf, sc, sy) >= 0 and sx >= 1, 'ingest_video: negative strides'
+    T_out = frame_table.numel()
+    assert frame_table.dtype == y_first.dtype == x_first.dtype == torch.int32 and y_w.dtype == x_w.dtype == torch.float32
+    assert y_first.shape == x_first.shape == (INGEST_OUT,) and y_w.dim() == x_w.dim() == 2 and y_w.shape[0] == x_w.shape[0] == INGEST_OUT
+    assert all(t.is_contiguous() for t in (frame_table, y_first, y_w, x_first, x_w))
+    if out is None:
+        out = torch.empty(T_out, 3, INGEST_OUT, INGEST_OUT, device=raw.device, dtype=torch.uint8)
+    assert out.dtype == torch.uint8 and out.shape == (T_out, 3, INGEST_OUT, INGEST_OUT) and out.is_contiguous()
+    for t0 in range(0, max(T_out, 1), 65535):                                    # the launcher takes 65535 output frames at a time
+        n = min(65535, T_out - t0)
+        rc = _lib.load().sf_ingest_video(_dev(raw, 'raw'), sf, sc, sy, sx, n_src, H, W, _dev(frame_table[t0:], 'frame_table'), _dev(y_first, 'y_first'),
+                                         _dev(y_w, 'y_w'), y_w.shape[1], _dev(x_first, 'x_first'), _dev(x_w, 'x_w'), x_w.shape[1], _dev(out[t0:], 'out'), n,
+                                         _stream())
+        _lib.check(rc, 'sf_ingest_video')
+    return out
+
+
+SF_I16 = 4
+
+
+def resample_wave(x: torch.Tensor, kernel: torch.Tensor, o: int, width: int, len_out: Optional[int] = None) -> torch.Tensor:
+    """Polyphase resampler (sf_resample_wave): x fp32 or int16 (scaled by 1 / 32768) on the device, (len,) or (ch, len) with ch <= 8 averaged to mono and a unit
+    sample stride; kernel fp32 (n, 2 width + o) contiguous (ingest.resample_kernel) -> fp32 (ceil(n len / o),), or its first len_out samples."""
+    if x.dim() == 1:
+        x = x[None]
+    if x.dim() != 2 or x.dtype not in (torch.float32, torch.int16):
+        raise ValueError(f'resample_wave: expected an fp32 or int16 wave (len,) or (ch, len), got {x.dtype} {tuple(x.shape)}')
+    if x.shape[1] > 1 and x.stride(1) != 1:
+        x = x.contiguous()
+    ch, n_in = x.shape
+    n, taps = kernel.shape
+    assert kernel.dtype == torch.float32 and kernel.is_contiguous() and taps == 2 * width + o
+    full = -(-n * n_in // o)
+    len_out = full if len_out is None else int(len_out)
+    y = torch.empty(len_out, device=x.device, dtype=torch.float32)
+    rc = _lib.load().sf_resample_wave(_dev(x, 'x'), SF_F32 if x.dtype == torch.float32 else SF_I16, ch, x.stride(0) if ch > 1 else max(n_in, 1), n_in,
+                                      _dev(kernel, 'kernel'), n, taps, o, width, _dev(y, 'y'), len_out, _stream())
+    _lib.check(rc, 'sf_resample_wave')
+    return y
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # PyTorch dispatcher registration (SURVEY §8b "custom-op contract"): the C-ABI launchers as `torch.ops.synchformer.*`
 # out-variant custom ops (device_types = "cuda", i.e. HIP on ROCm).  They mutate their `out` argument and return nothing,

@@ -8,6 +8,7 @@ under a cost on class changes).
 
     tracker = OffsetTracker(engine, MelFrontend(dev))
     track = tracker.track(frames, wave)           # frames (T, 3, 224, 224) uint8, wave (n,) fp32 16 kHz; device or host
+    track = tracker.track_raw(raw_frames, raw_wave, RecordingIngest(dev, (30000, 1001), (1080, 1920), 48000, channels_last=True))   # as decoded
     track.t_sec, track.offset_sec_path            # where in the recording, which offset
 
 Out of scope (one recording per call): batching several recordings, double-buffered host-to-device transfer of the chunks, de-duplicating the
@@ -75,3 +76,13 @@ class OffsetTracker:
         """frames (T, 3, 224, 224) uint8, wave (n,) fp32 16 kHz, on the device or in host memory -> OffsetTrack; ValueError below one window (120 frames,
         76800 samples)."""
         return self.track_features(*self.eng.extract_recording(frames, wave, self.mel, seg_chunk), win_chunk=win_chunk)
+
+    def track_raw(self, raw_frames: torch.Tensor, raw_wave: torch.Tensor, ingest, seg_chunk: Optional[int] = None, win_chunk: int = 256) -> OffsetTrack:
+        """The recording as a decoder hands it out: raw_frames uint8 (T, 3, H, W) or channels-last (T, H, W, 3) at the native frame rate and
+        size, raw_wave fp32 or int16 (n,) / (ch, n) at the native rate, device or host; `ingest` an ingest.RecordingIngest of that geometry -> OffsetTrack.
+        Each tower chunk's 25 fps, 224 x 224 frames are made from the raw ones right before the chunk runs; the resized recording is never materialised.
+        ValueError below one window after conversion, or when the frames do not have the ingest's size."""
+        ingest._check_frames(raw_frames)
+        wave = ingest.wave(raw_wave)
+        banks = self.eng.extract_recording_from(lambda f0, f1: ingest.frames(raw_frames, f0, f1), ingest.n_frames(raw_frames.shape[0]), wave, self.mel, seg_chunk)
+        return self.track_features(*banks, win_chunk=win_chunk)

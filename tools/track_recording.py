@@ -1,7 +1,11 @@
 """Offset tracking along a synthetic recording: the bank path (every segment through the towers once, windows as row-map views of the bank)
 beside the same windows through forward_clips on explicit 120-frame slices.  Prints one JSON line.
 
-    python tools/track_recording.py [--seconds 60] [--hop 1] [--seg-chunk 224] [--host] [--clip-windows 8]
+    python tools/track_recording.py [--seconds 60] [--hop 1] [--seg-chunk 224] [--host] [--clip-windows 8] [--fps 30000/1001 --size 1080x1920 --rate 48000]
+
+With --fps / --size / --rate the recording is synthesised RAW at that geometry (channels-last uint8 frames, stereo int16 PCM, in device memory) and goes through
+the ingest stage: the line then also carries the ingest time alone (the same chunks the bank asks for, plus the wave) and the bank from raw
+frames next to the bank from frames ingested beforehand.
 
 forward_clips is timed on at most --clip-windows windows (spread over the recording) and scaled to all W; both sides include the mel front-end and
 are timed by wall clock around a device synchronisation, after one warm-up pass each.  Synthetic weights and inputs: the numbers are throughput only."""
@@ -26,13 +30,26 @@ def main():
     ap.add_argument('--win-chunk', type=int, default=256)
     ap.add_argument('--clip-windows', type=int, default=8, help='windows timed through forward_clips (scaled to all of them)')
     ap.add_argument('--host', action='store_true', help='keep the recording in pinned host memory (uploaded chunk by chunk)')
+    ap.add_argument('--fps', default=None, help='raw frame rate, e.g. 30, 29.97 or 30000/1001 (default: 25, no ingest)')
+    ap.add_argument('--size', default=None, help='raw frame size HxW, e.g. 1080x1920')
+    ap.add_argument('--rate', type=int, default=None, help='raw sample rate in Hz, e.g. 48000')
     args = ap.parse_args()
     from synchformer_amd import synth
     from synchformer_amd.engine import SynchformerEngine
     from synchformer_amd.frontend import MelFrontend, recording_geometry
+    from synchformer_amd.ingest import RecordingIngest
     from synchformer_amd.track import OffsetTracker
     dev = torch.device('cuda:0')
-    T, n = int(args.seconds * 25), int(args.seconds * 16000)
+    raw_mode = args.fps is not None or args.size is not None or args.rate is not None
+    ing = None
+    if raw_mode:
+        fps = tuple(int(v) for v in args.fps.split('/')) if args.fps and '/' in args.fps else float(args.fps or 25)
+        RH, RW = (int(v) for v in (args.size or '256x256').lower().split('x'))
+        ing = RecordingIngest(dev, fps, (RH, RW), args.rate or 16000, channels_last=True)
+        T_raw, n_raw = int(args.seconds * ing.fps_in), int(args.seconds * ing.rate_in)
+        T, n = ing.n_frames(T_raw), ing.n_samples(n_raw)
+    else:
+        T, n = int(args.seconds * 25), int(args.seconds * 16000)
     g = recording_geometry(T, n, args.hop)
     N, W = g['n_segments'], g['n_windows']
     if W < 1:
@@ -40,10 +57,19 @@ def main():
     eng = SynchformerEngine(synth.make_state_dict(1337), dev, seg_chunk=args.seg_chunk)
     mel = MelFrontend(dev)
     gen = torch.Generator().manual_seed(7)
-    frames = torch.randint(0, 256, (T, 3, 224, 224), generator=gen, dtype=torch.uint8)
-    wave = torch.rand(n, generator=gen) * 2 - 1
-    fd, wd = frames.to(dev), wave.to(dev)
-    src = (frames.pin_memory(), wave.pin_memory()) if args.host else (fd, wd)
+    if raw_mode:
+        dgen = torch.Generator(device=dev).manual_seed(7)
+        raw = torch.randint(0, 256, (T_raw, RH, RW, 3), generator=dgen, dtype=torch.uint8, device=dev)
+        raw_wave = torch.randint(-32768, 32768, (2, n_raw), generator=gen, dtype=torch.int32).to(torch.int16).to(dev)
+        fd, wd = ing.frames(raw, 0, T), ing.wave(raw_wave)                      # materialised for the comparisons below only
+        if args.host:
+            raw, raw_wave = raw.cpu().pin_memory(), raw_wave.cpu().pin_memory()
+        src = (fd.cpu().pin_memory(), wd.cpu().pin_memory()) if args.host else (fd, wd)
+    else:
+        frames = torch.randint(0, 256, (T, 3, 224, 224), generator=gen, dtype=torch.uint8)
+        wave = torch.rand(n, generator=gen) * 2 - 1
+        fd, wd = frames.to(dev), wave.to(dev)
+        src = (frames.pin_memory(), wave.pin_memory()) if args.host else (fd, wd)
     tracker = OffsetTracker(eng, mel, hop_segments=args.hop)
 
     def timed(fn, reps=1):
@@ -56,6 +82,26 @@ def main():
         return (time.perf_counter() - t0) / reps, out
 
     t_bank, (vbank, abank) = timed(lambda: eng.extract_recording(*src, mel))
+    extra = {}
+    if raw_mode:
+        chunks = [(8 * s0, 8 * (min(args.seg_chunk, N - s0) + s0 - 1) + 16) for s0 in range(0, N, args.seg_chunk)]      # the bank's own frame slices
+
+        def ingest_only():
+            ing.wave(raw_wave)
+            for f0, f1 in chunks:
+                ing.frames(raw, f0, f1)
+
+        t_ing, _ = timed(ingest_only, reps=3)
+        t_one, _ = timed(lambda: ing.frames(raw, 0, T), reps=3)                  # the whole recording in one launch
+        t_wave, _ = timed(lambda: ing.wave(raw_wave), reps=3)
+        t_raw, (vb_raw, ab_raw) = timed(lambda: eng.extract_recording_from(lambda f0, f1: ing.frames(raw, f0, f1), T, ing.wave(raw_wave), mel))
+        table = ing.frame_table(T_raw)
+        src_frames = int(torch.unique(table).numel())
+        extra = {'raw_fps': float(ing.fps_in), 'raw_size': [RH, RW], 'raw_rate': ing.rate_in, 'raw_frames': T_raw, 'frames_25fps': T, 'taps': [ing.taps_y, ing.taps_x],
+                 'ingest_s': round(t_ing, 5), 'ingest_frames_per_s': round(sum(f1 - f0 for f0, f1 in chunks) / t_ing, 1),
+                 'ingest_video_one_launch_s': round(t_one, 5), 'ingest_video_one_launch_frames_per_s': round(T / t_one, 1),
+                 'ingest_video_one_launch_source_GBps': round(src_frames * RH * RW * 3 / t_one / 1e9, 1), 'resample_wave_s': round(t_wave, 6),
+                 'bank_from_raw_s': round(t_raw, 4), 'bank_from_raw_equals_bank': bool(torch.equal(vb_raw, vbank) and torch.equal(ab_raw, abank))}
     t_win, track = timed(lambda: tracker.track_features(vbank, abank, win_chunk=args.win_chunk), reps=3)
     k = min(W, max(1, args.clip_windows))
     picks = [round(i * (W - 1) / max(1, k - 1)) for i in range(k)]
@@ -73,7 +119,7 @@ def main():
         'windows_per_s': round(W / t_win, 1), 'track_total_s': round(t_bank + t_win, 4),
         'forward_clips_windows_timed': k, 'forward_clips_s_scaled': round(t_clips_all, 3), 'speedup_vs_forward_clips': round(t_clips_all / (t_bank + t_win), 2),
         'max_abs_logit_diff_vs_forward_clips': round(err, 6), 'path_changes': int((track.cls_path[1:] != track.cls_path[:-1]).sum().item()),
-        'raw_changes': int((track.cls_raw[1:] != track.cls_raw[:-1]).sum().item())}))
+        'raw_changes': int((track.cls_raw[1:] != track.cls_raw[:-1]).sum().item()), **extra}))
 
 
 if __name__ == '__main__':
