@@ -29,7 +29,7 @@ extern "C" {
 enum { SF_F32 = 0, SF_BF16 = 1, SF_F16 = 2, SF_U8 = 3, SF_I16 = 4 };   /* element types (SF_I16: PCM input of sf_resample_wave only) */
 enum { SF_EPI_NONE = 0, SF_EPI_GELU = 1 };                  /* GEMM epilogue activation */
 
-#define SF_ABI_VERSION 15
+#define SF_ABI_VERSION 16
 int sf_abi_version(void);
 const char* sf_last_error(void);
 /* "gfx950" + build flags; lets the host assert it loaded the library it built */
@@ -536,6 +536,26 @@ int sf_ingest_video(const uint8_t* raw, int64_t stride_frame, int64_t stride_cha
                     uint8_t* out, int T_out, void* stream);
 int sf_resample_wave(const void* x, int dtype, int ch, int64_t ld, int64_t len, const float* kernel, int n, int taps, int o, int width, float* y, int64_t len_out,
                      void* stream);
+
+/* sf_ingest_video for 8-bit YUV 4:2:0 frames as decoders hand them out (NV12 surfaces, I420 / yuv420p arrays): the planes are resized first and the colour
+ * conversion runs on the 224 x 224 result, the order of the reference's ffmpeg step (example.py:16-53 scales in YUV; RGB appears when the 256-side result is
+ * decoded).  A frame of even H x W has luma Y (H x W) and chroma U, V (H/2 x W/2 each); with base = raw + f * stride_frame,
+ *       Y[y, x] = base[y * stride_row + x],   U[y, x] = base[u_off + y * stride_crow + x * stride_ccol],   V[y, x] = base[v_off + y * stride_crow + x * stride_ccol]
+ *   (NV12 at row pitch P: u_off = P H, v_off = u_off + 1, stride_crow = P, stride_ccol = 2;  I420 with contiguous rows: u_off = H W, v_off = H W 5 / 4,
+ *   stride_crow = W / 2, stride_ccol = 1).  For output frame j < T_out (source frame frame_table[j], clamped into [0, n_src)) and r, x < 224:
+ *       Yr = sum_i y_w[r, i]  * sum_k x_w[x, k]  * Y[y_first[r] + i,  x_first[x] + k]          luma tables: those of sf_ingest_video (H -> Hr, W -> Wr)
+ *       Ur = sum_i cy_w[r, i] * sum_k cx_w[x, k] * U[cy_first[r] + i, cx_first[x] + k]         chroma tables: H/2 -> Hr, W/2 -> Wr, sliced at the SAME crop origin;
+ *       Vr = the same on V                                                                     chroma is an (H/2, W/2) image under align_corners=False (centre siting)
+ *       out[c, r, x] = clamp(round_half_even(M[c][0] (Yr - o[0]) + M[c][1] (Ur - o[1]) + M[c][2] (Vr - o[2])), 0, 255)
+ *   fp32, horizontal pass first, taps ascending, nothing rounded between the resize and the conversion; uint8 planar (T_out, 3, 224, 224), 4-byte aligned.
+ *   csc: 12 floats in HOST memory, M row-major (rows R, G, B; columns Y, U, V) then o; they travel as kernel arguments (synchformer_amd.ingest.csc_matrix).
+ *   When v_off == u_off + 1 and stride_ccol == 2 the interleaved chroma rows are fetched once and split in registers.  Taps outside a plane are skipped.
+ *   -1 on: odd H or W, taps outside 1 .. 35 in any of the four tables, stride_ccol < 1, negative strides or offsets, a row too wide to stage (W + taps_x above
+ *   ~5100 or W / 2 + taps_cx above ~2550), T_out outside 0 .. 65535, a null pointer, out not 4-byte aligned.  T_out == 0 launches nothing.  One launch. */
+int sf_ingest_video_yuv(const uint8_t* raw, int64_t stride_frame, int64_t stride_row, int64_t u_off, int64_t v_off, int64_t stride_crow, int64_t stride_ccol,
+                        int n_src, int H, int W, const int32_t* frame_table, const int32_t* y_first, const float* y_w, int taps_y, const int32_t* x_first,
+                        const float* x_w, int taps_x, const int32_t* cy_first, const float* cy_w, int taps_cy, const int32_t* cx_first, const float* cx_w,
+                        int taps_cx, const float* csc, uint8_t* out, int T_out, void* stream);
 
 /* Backward of sf_attention for tiny groups (n_tok <= 8, head_dim 64: Motionformer time attention, vit_helper.py:343-344): same
  * addressing as the forward; dq | dk | dv rows of the group's tokens are written (=), the CLS key's dk | dv of every (seq, group) goes to

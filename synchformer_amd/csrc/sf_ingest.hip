@@ -1,10 +1,11 @@
-// Ingest of a decoded recording at its native geometry (DESIGN 3.11): what the reference leaves to an ffmpeg subprocess before any of its code runs
+// Ingest of a decoded recording at its native geometry (DESIGN 3.11, 3.12): what the reference leaves to an ffmpeg subprocess before any of its code runs
 // (example.py:16-53: fps=25, short side 256, even dimensions, -ar 16000) plus the centre 224 crop of RGBSpatialCrop, as two launches.
 //   sf_ingest_video:   frame pick (frame_table) + antialiased bicubic resize + crop, uint8 -> uint8 planar (T_out, 3, 224, 224).  The resize is separable and the
 //                      two filter tables arrive already sliced to the crop, so only the 224 x 224 outputs are computed: a horizontal pass over the source rows a
 //                      tile of output rows needs (fp32, kept in LDS), then the vertical pass over those rows.
+//   sf_ingest_video_yuv: the same for 8-bit YUV 4:2:0 frames (NV12, I420): the three planes are resized, the colour matrix runs on the 224 x 224 result.
 //   sf_resample_wave:  zero-delay polyphase windowed-sinc resampler (the bank of ingest.resample_kernel), channels averaged on read, zero padding by bounds checks.
-// Both kernels bound every address they form by the sizes the launcher was given: a table with entries outside the source only changes the picture, never the
+// All kernels bound every address they form by the sizes the launcher was given: a table with entries outside the source only changes the picture, never the
 // addresses (frame index, first-tap row / column and every tap are clamped or skipped).
 #include "sf_common.h"
 #include "../../include/synchformer_hip.h"
@@ -216,6 +217,260 @@ extern "C" int sf_ingest_video(const uint8_t* raw, int64_t stride_frame, int64_t
   const int lds = fixed + R * (RP + ING_OUT * 4);
   hipLaunchKernelGGL(ingest_video_kernel, dim3(ING_OUT / ING_TY, 3, (unsigned)T_out), dim3(256), lds, (hipStream_t)stream, raw, stride_frame, stride_channel,
                      stride_row, stride_col, n_src, H, W, frame_table, y_first, y_w, taps_y, x_first, x_w, taps_x, out, R, RP, TW);
+  SF_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- YUV 4:2:0 -------------------------------------------------------------------------------------------------------------------------------------------
+struct IngCsc { float m[9], o[3]; };                                             // M row-major (rows R, G, B; columns Y, U, V), then the offsets
+
+// The pipeline of ingest_video_kernel over NP planes of one frame that share their geometry and tables (NP = 1: luma; NP = 2: U and V), on the LDS of the
+// workgroup:  xw [TW][224] | yw [8][taps_y] | mid [NP R][224] | rows [NP R][RP], plane p in staged rows [p R, (p + 1) R); R source rows of each plane per chunk,
+// R % 4 == 0 and NP R <= 8, so that a horizontal item (4 source rows, one output column) never straddles two planes.  Element (y, x) of plane p is
+// s[p][y * sy + x * sx].  INTER: s1 == s0 + 1 and sx == 2 (NV12) - the 8 bytes U V U V U V U V of four chroma columns are fetched once as two dwords and split
+// into the U and the V dword in registers.  Adds into a0[p] / a1[p]: this lane's 4 columns of output rows r0 + rg and r0 + rg + 4 (lanes < 224).
+template <int NP, bool INTER>
+__device__ __forceinline__ void ing_plane_pass(unsigned char* lds, const uint8_t* __restrict__ s0, const uint8_t* __restrict__ s1, int64_t sy, int64_t sx, int H, int W, const int32_t* __restrict__ y_first, const float* __restrict__ y_w, int taps_y,
+                                               const int32_t* __restrict__ x_first, const float* __restrict__ x_w, int taps_x, int R, int RP, int TW, int r0,
+                                               float (&a0)[NP][4], float (&a1)[NP][4]) {
+  float* xw = (float*)lds;
+  float* yw = xw + TW * ING_OUT;
+  float* mid = yw + ING_TY * taps_y;
+  uint32_t* rows = (uint32_t*)(mid + NP * R * ING_OUT);
+  const int tid = threadIdx.x;
+  __syncthreads();                                                             // every lane is past the LDS of the pass before this one
+
+  for (int i = tid; i < TW * ING_OUT; i += 256) {
+    const int row = i / ING_OUT;
+    if (row < 3 || row >= taps_x + 3) xw[i] = 0.f;
+  }
+  for (int i = tid; i < taps_x * ING_OUT; i += 256) {
+    const int x = i / taps_x, j = i - x * taps_x;
+    xw[(j + 3) * ING_OUT + x] = x_w[i];
+  }
+  for (int i = tid; i < ING_TY * taps_y; i += 256) yw[i] = y_w[(int64_t)r0 * taps_y + i];
+
+  int xlo = x_first[0];
+  xlo = xlo < 0 ? 0 : (xlo > W ? W : xlo);
+  int ys = y_first[r0], ye = y_first[r0 + ING_TY - 1] + taps_y;
+  ys = ys < 0 ? 0 : ys;
+  ye = ye > H ? H : ye;
+
+  const int q = tid % 56, rg = tid / 56;
+  const bool vert = tid < 224;
+  int yf0 = 0, yf1 = 0;
+  if (vert) { yf0 = y_first[r0 + rg]; yf1 = y_first[r0 + rg + 4]; }
+  const int Q4 = RP >> 2;
+  const int nd = (taps_x + 6) >> 2;
+  const int valid_x = W - xlo;
+  const int n_stage = R * Q4;                                                   // staging items: 4 columns of one row of every plane; NP n_stage <= 256 * ING_PF
+
+  const uint32_t* hp[2];
+  const float* hw[2];
+  float* hm[2];
+  bool hon[2];
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int it = tid + 256 * k;
+    hon[k] = it < (NP * R / 4) * ING_OUT;
+    const int g = it / ING_OUT, x = it - g * ING_OUT;
+    int off = hon[k] ? x_first[x] - xlo : 0;
+    off = off < 0 ? 0 : (off > RP - ING_ROW_SLACK - taps_x ? RP - ING_ROW_SLACK - taps_x : off);
+    hp[k] = rows + (g * 4) * Q4 + (off >> 2);
+    hw[k] = xw + (3 - (off & 3)) * ING_OUT + x;
+    hm[k] = mid + (g * 4) * ING_OUT + x;
+  }
+
+  uint32_t pf[ING_PF];
+  auto fetch = [&](int yc) {
+#pragma unroll
+    for (int k = 0; k < ING_PF / NP; ++k) {
+      const int it = tid + 256 * k;
+      uint32_t v[NP];
+#pragma unroll
+      for (int p = 0; p < NP; ++p) v[p] = 0;
+      if (it < n_stage) {
+        const int r = it / Q4, c = (it - r * Q4) * 4;
+        const int y = yc + r;
+        if (y < ye && c < valid_x) {
+          const int64_t o = (int64_t)y * sy + (int64_t)(xlo + c) * sx;
+          const bool full = c + 3 < valid_x;
+          const uint8_t* gi = s0 + o;
+          if (NP == 2 && INTER && full && ((uintptr_t)gi & 3) == 0) {
+            const uint32_t a = ((const uint32_t*)gi)[0], b = ((const uint32_t*)gi)[1];
+            v[0] = (a & 0xffu) | ((a >> 8) & 0xff00u) | ((b & 0xffu) << 16) | ((b << 8) & 0xff000000u);
+            v[NP - 1] = ((a >> 8) & 0xffu) | ((a >> 16) & 0xff00u) | ((b << 8) & 0xff0000u) | (b & 0xff000000u);
+          } else {
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+              const uint8_t* g = (p ? s1 : s0) + o;
+              if (!INTER && sx == 1 && full && ((uintptr_t)g & 3) == 0) {
+                v[p] = *(const uint32_t*)g;
+              } else {
+                uint32_t u = g[0];
+                if (c + 1 < valid_x) u |= (uint32_t)g[sx] << 8;
+                if (c + 2 < valid_x) u |= (uint32_t)g[2 * sx] << 16;
+                if (full) u |= (uint32_t)g[3 * sx] << 24;
+                v[p] = u;
+              }
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int p = 0; p < NP; ++p) pf[k * NP + p] = v[p];
+    }
+  };
+  auto commit = [&]() {
+#pragma unroll
+    for (int k = 0; k < ING_PF / NP; ++k) {
+      const int it = tid + 256 * k;
+      if (it < n_stage) {
+#pragma unroll
+        for (int p = 0; p < NP; ++p) rows[p * n_stage + it] = pf[k * NP + p];
+      }
+    }
+  };
+
+  if (ys < ye) {
+    fetch(ys);
+    commit();
+  }
+  __syncthreads();
+  for (int yc = ys; yc < ye; yc += R) {
+    const bool more = yc + R < ye;
+    if (more) fetch(yc + R);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      if (hon[k]) {
+        const uint32_t* p0 = hp[k];
+        const float* wp = hw[k];
+        float h0 = 0.f, h1 = 0.f, h2 = 0.f, h3 = 0.f;
+        for (int d = 0; d < nd; ++d) {
+          const uint32_t v0 = p0[d], v1 = p0[Q4 + d], v2 = p0[2 * Q4 + d], v3 = p0[3 * Q4 + d];
+#pragma unroll
+          for (int b = 0; b < 4; ++b) {
+            const float w = wp[(4 * d + b) * ING_OUT];
+            h0 = fmaf(w, (float)((v0 >> (8 * b)) & 255u), h0);
+            h1 = fmaf(w, (float)((v1 >> (8 * b)) & 255u), h1);
+            h2 = fmaf(w, (float)((v2 >> (8 * b)) & 255u), h2);
+            h3 = fmaf(w, (float)((v3 >> (8 * b)) & 255u), h3);
+          }
+        }
+        float* m = hm[k];
+        m[0] = h0; m[ING_OUT] = h1; m[2 * ING_OUT] = h2; m[3 * ING_OUT] = h3;
+      }
+    }
+    __syncthreads();
+    if (vert) {
+      const int n = ye - yc < R ? ye - yc : R;
+      for (int r = 0; r < n; ++r) {
+        const int j0 = yc + r - yf0, j1 = yc + r - yf1;
+        const bool in0 = j0 >= 0 && j0 < taps_y, in1 = j1 >= 0 && j1 < taps_y;
+        if (in0 || in1) {
+          const float w0 = in0 ? yw[rg * taps_y + j0] : 0.f, w1 = in1 ? yw[(rg + 4) * taps_y + j1] : 0.f;
+#pragma unroll
+          for (int p = 0; p < NP; ++p) {
+            const f32x4 v = *(const f32x4*)(mid + (p * R + r) * ING_OUT + 4 * q);
+            if (in0) { a0[p][0] = fmaf(w0, v.x, a0[p][0]); a0[p][1] = fmaf(w0, v.y, a0[p][1]); a0[p][2] = fmaf(w0, v.z, a0[p][2]); a0[p][3] = fmaf(w0, v.w, a0[p][3]); }
+            if (in1) { a1[p][0] = fmaf(w1, v.x, a1[p][0]); a1[p][1] = fmaf(w1, v.y, a1[p][1]); a1[p][2] = fmaf(w1, v.z, a1[p][2]); a1[p][3] = fmaf(w1, v.w, a1[p][3]); }
+          }
+        }
+      }
+    }
+    if (more) {
+      commit();
+      __syncthreads();
+    }
+  }
+}
+
+// One workgroup = output rows [r0, r0 + 8) of ALL THREE channels of one output frame: the luma plane through ing_plane_pass (chunks of R source rows), then U and
+// V together (chunks of 4 rows of each; their tables replace the luma ones in the same LDS), the three resized 8 x 224 fp32 tiles staying in registers (24 per
+// lane); then the colour matrix, round half to even, clamp and three full 224-byte lines per output row.
+template <bool INTER>
+__global__ __launch_bounds__(256) void ingest_video_yuv_kernel(const uint8_t* __restrict__ raw, int64_t sf, int64_t sy, int64_t u_off, int64_t v_off, int64_t csy,
+                                                                int64_t csx, int n_src, int H, int W, const int32_t* __restrict__ frame_table,
+                                                                const int32_t* __restrict__ y_first, const float* __restrict__ y_w, int taps_y,
+                                                                const int32_t* __restrict__ x_first, const float* __restrict__ x_w, int taps_x,
+                                                                const int32_t* __restrict__ cy_first, const float* __restrict__ cy_w, int taps_cy,
+                                                                const int32_t* __restrict__ cx_first, const float* __restrict__ cx_w, int taps_cx, IngCsc csc,
+                                                                uint8_t* __restrict__ out, int R, int RP, int TW, int RPc, int TWc) {
+  extern __shared__ __align__(16) unsigned char ing_yuv_lds[];
+  const int r0 = blockIdx.x * ING_TY, fo = blockIdx.y;
+  int fs = frame_table[fo];
+  fs = fs < 0 ? 0 : (fs >= n_src ? n_src - 1 : fs);
+  const uint8_t* src = raw + (int64_t)fs * sf;
+  float ya[1][4] = {}, yb[1][4] = {}, c0[2][4] = {}, c1[2][4] = {};
+  ing_plane_pass<1, false>(ing_yuv_lds, src, src, sy, 1, H, W, y_first, y_w, taps_y, x_first, x_w, taps_x, R, RP, TW, r0, ya, yb);
+  ing_plane_pass<2, INTER>(ing_yuv_lds, src + u_off, src + v_off, csy, csx, H >> 1, W >> 1, cy_first, cy_w, taps_cy, cx_first, cx_w,
+                           taps_cx, 4, RPc, TWc, r0, c0, c1);
+  const int tid = threadIdx.x;
+  if (tid < 224) {
+    const int q = tid % 56, rg = tid / 56;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      uint32_t w[3] = {0, 0, 0};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float y = (h ? yb[0][k] : ya[0][k]) - csc.o[0], u = (h ? c1[0][k] : c0[0][k]) - csc.o[1], v = (h ? c1[1][k] : c0[1][k]) - csc.o[2];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const float t = fmaf(csc.m[3 * c + 2], v, fmaf(csc.m[3 * c + 1], u, csc.m[3 * c] * y));
+          w[c] |= (uint32_t)fminf(fmaxf(rintf(t), 0.f), 255.f) << (8 * k);
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) *(uint32_t*)(out + (((int64_t)fo * 3 + c) * ING_OUT + r0 + rg + 4 * h) * ING_OUT + 4 * q) = w[c];
+    }
+  }
+}
+
+extern "C" int sf_ingest_video_yuv(const uint8_t* raw, int64_t stride_frame, int64_t stride_row, int64_t u_off, int64_t v_off, int64_t stride_crow,
+                                   int64_t stride_ccol, int n_src, int H, int W, const int32_t* frame_table, const int32_t* y_first, const float* y_w, int taps_y,
+                                   const int32_t* x_first, const float* x_w, int taps_x, const int32_t* cy_first, const float* cy_w, int taps_cy,
+                                   const int32_t* cx_first, const float* cx_w, int taps_cx, const float* csc, uint8_t* out, int T_out, void* stream) {
+  SF_CHECK_ARG(T_out >= 0 && T_out <= 65535, "sf_ingest_video_yuv: T_out = %d output frames per launch (0 .. 65535: grid y)", T_out);
+  SF_CHECK_ARG(n_src >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, "sf_ingest_video_yuv: source of %d frames %d x %d (4:2:0 takes even H and W)", n_src, H, W);
+  SF_CHECK_ARG(taps_y >= 1 && taps_y <= ING_MAX_TAPS && taps_x >= 1 && taps_x <= ING_MAX_TAPS && taps_cy >= 1 && taps_cy <= ING_MAX_TAPS && taps_cx >= 1 &&
+                   taps_cx <= ING_MAX_TAPS,
+               "sf_ingest_video_yuv: luma taps %d x %d, chroma taps %d x %d out of range (1 .. %d)", taps_y, taps_x, taps_cy, taps_cx, ING_MAX_TAPS);
+  SF_CHECK_ARG(stride_frame >= 0 && stride_row >= 0 && u_off >= 0 && v_off >= 0 && stride_crow >= 0 && stride_ccol >= 1,
+               "sf_ingest_video_yuv: negative byte stride or offset, or a chroma column stride below 1");
+  if (T_out == 0) return 0;
+  SF_CHECK_ARG(raw && frame_table && y_first && y_w && x_first && x_w && cy_first && cy_w && cx_first && cx_w && csc && out, "sf_ingest_video_yuv: null pointer");
+  SF_CHECK_ARG(((uintptr_t)out & 3) == 0, "sf_ingest_video_yuv: out must be 4-byte aligned");
+  SF_CHECK_ARG(W <= 1 << 20, "sf_ingest_video_yuv: W = %d is too wide for four staged source rows in LDS at taps_x = %d", W, taps_x);
+  // luma: as sf_ingest_video
+  const int RP = ((W + taps_x + 3) & ~3) + ING_ROW_SLACK;
+  const int TW = 4 * ((taps_x + 6) >> 2) + 3;
+  const int fixed = (TW * ING_OUT + ING_TY * taps_y) * 4;
+  int R = (ING_LDS_BYTES - fixed) / (RP + ING_OUT * 4);
+  R = R > ING_MAX_ROWS ? ING_MAX_ROWS : R;
+  if (R > 256 * ING_PF * 4 / RP) R = 256 * ING_PF * 4 / RP;
+  R &= ~3;
+  SF_CHECK_ARG(R >= 4, "sf_ingest_video_yuv: W = %d is too wide for four staged source rows in LDS at taps_x = %d", W, taps_x);
+  // chroma: four rows of U and four of V per chunk
+  const int RPc = ((W / 2 + taps_cx + 3) & ~3) + ING_ROW_SLACK;
+  const int TWc = 4 * ((taps_cx + 6) >> 2) + 3;
+  const int fixed_c = (TWc * ING_OUT + ING_TY * taps_cy) * 4;
+  const int lds_c = fixed_c + 8 * (RPc + ING_OUT * 4);
+  SF_CHECK_ARG(lds_c <= ING_LDS_BYTES && 2 * RPc <= 256 * ING_PF, "sf_ingest_video_yuv: W = %d is too wide for four staged rows of both chroma planes in LDS at taps_cx = %d",
+               W, taps_cx);
+  const int lds_y = fixed + R * (RP + ING_OUT * 4);
+  IngCsc k;
+  for (int i = 0; i < 9; ++i) k.m[i] = csc[i];
+  for (int i = 0; i < 3; ++i) k.o[i] = csc[9 + i];
+  const dim3 grid(ING_OUT / ING_TY, (unsigned)T_out);
+  const int lds = lds_y > lds_c ? lds_y : lds_c;
+  if (v_off == u_off + 1 && stride_ccol == 2)                                   // NV12: one fetch of the interleaved rows serves both planes
+    hipLaunchKernelGGL(ingest_video_yuv_kernel<true>, grid, dim3(256), lds, (hipStream_t)stream, raw, stride_frame, stride_row, u_off, v_off, stride_crow,
+                       stride_ccol, n_src, H, W, frame_table, y_first, y_w, taps_y, x_first, x_w, taps_x, cy_first, cy_w, taps_cy, cx_first, cx_w, taps_cx, k, out, R,
+                       RP, TW, RPc, TWc);
+  else
+    hipLaunchKernelGGL(ingest_video_yuv_kernel<false>, grid, dim3(256), lds, (hipStream_t)stream, raw, stride_frame, stride_row, u_off, v_off, stride_crow,
+                       stride_ccol, n_src, H, W, frame_table, y_first, y_w, taps_y, x_first, x_w, taps_x, cy_first, cy_w, taps_cy, cx_first, cx_w, taps_cx, k, out, R,
+                       RP, TW, RPc, TWc);
   SF_LAUNCH_CHECK();
   return 0;
 }

@@ -1,4 +1,4 @@
-"""Ingest a decoded recording at its native frame rate, size and sample rate.
+"""Ingest a decoded recording at its native frame rate, size, pixel format and sample rate.
 
 The reference re-encodes every input through an ffmpeg subprocess before any of its code runs (example.py:16-53: fps=25, short side scaled to 256, dimensions
 cropped to even, -ar 16000) and then takes the centre 224 crop of RGBSpatialCrop.  Here the same step is host geometry (this module: pure Python / torch,
@@ -9,8 +9,18 @@ no device needed) plus two launches (ops.ingest_video: frame pick + antialiased 
 
 What is pinned: the frame pick restates the documented "near" rounding of ffmpeg's fps filter; the resize is F.interpolate(mode='bicubic', antialias=True,
 align_corners=False) (NOT swscale's bicubic: no bit parity with an ffmpeg build is claimed or checkable here); the resampler is
-torchaudio.functional.resample at its defaults (sinc_interp_hann), not swresample.  Out of scope: decoding, YUV input, double-buffered uploads, several
-recordings per call.
+torchaudio.functional.resample at its defaults (sinc_interp_hann), not swresample.
+
+Frames may also arrive as the 8-bit YUV 4:2:0 a decoder produces, half the bytes of RGB:
+
+    ing = RecordingIngest(dev, (30000, 1001), (1080, 1920), 48000, pix_fmt='nv12')      # or 'yuv420p': PyAV's frame.to_ndarray(format='yuv420p')
+    track = tracker.track_raw(raw_frames, raw_wave, ing)        # raw_frames (T, 1620, 1920) uint8: H luma rows, then the chroma rows
+
+The planes are resized and the colour matrix (csc_matrix: bt601 or bt709, limited or full range) runs on the 224 x 224 result, in the reference's order (its
+ffmpeg step scales in YUV).  Chroma is taken centre-sited; the default, bt601 limited range, is what swscale assumes for an untagged stream - an assumption that
+cannot be checked without an ffmpeg build.
+
+Out of scope: decoding, 10-bit / 4:2:2 / 4:4:4 input, left chroma siting, double-buffered uploads, several recordings per call.
 """
 import math
 from fractions import Fraction
@@ -20,6 +30,8 @@ import torch
 
 CROP = 224
 MAX_TAPS = 35                    # sf_ingest_video's range: a short side up to 2160 at resize_side 256
+PIX_FMTS = ('rgb24', 'nv12', 'yuv420p')
+_KR_KB = {'bt601': (0.299, 0.114), 'bt709': (0.2126, 0.0722)}
 
 
 def _fraction(fps) -> Fraction:
@@ -104,6 +116,21 @@ def aa_bicubic_table(n_in: int, n_out: int, dtype=torch.float32):
     return first, w.to(dtype), taps
 
 
+def csc_matrix(colorspace: str = 'bt601', full_range: bool = False):
+    """(M (3, 3) float64, offsets (3,) float64) with (R, G, B) = M @ ((Y, U, V) - offsets) on the 8-bit scale.  With Kr, Kb of the colour space (bt601: 0.299,
+    0.114; bt709: 0.2126, 0.0722), Kg = 1 - Kr - Kb, luma gain gy and chroma gain gc (limited range: 255 / 219 and 255 / 224, offsets (16, 128, 128); full range:
+    1 and 1, offsets (0, 128, 128)):  R = gy Y' + 2 (1 - Kr) gc V',  B = gy Y' + 2 (1 - Kb) gc U',  G = gy Y' - 2 Kb (1 - Kb) / Kg gc U' - 2 Kr (1 - Kr) / Kg gc V'."""
+    if colorspace not in _KR_KB:
+        raise ValueError(f'colorspace = {colorspace!r}: one of {sorted(_KR_KB)}')
+    kr, kb = _KR_KB[colorspace]
+    kg = 1.0 - kr - kb
+    gy, gc, o0 = (1.0, 1.0, 0.0) if full_range else (255.0 / 219.0, 255.0 / 224.0, 16.0)
+    M = torch.tensor([[gy, 0.0, 2 * (1 - kr) * gc],
+                      [gy, -2 * kb * (1 - kb) / kg * gc, -2 * kr * (1 - kr) / kg * gc],
+                      [gy, 2 * (1 - kb) * gc, 0.0]], dtype=torch.float64)
+    return M, torch.tensor([o0, 128.0, 128.0], dtype=torch.float64)
+
+
 def resample_kernel(rate_in: int, rate_out: int = 16000, lowpass_filter_width: int = 6, rolloff: float = 0.99):
     """The polyphase windowed-sinc bank of torchaudio.functional.resample at its defaults (sinc_interp_hann): (kernel fp32 (n, 2 width + o), width, o, n) with
     o = rate_in / gcd, n = rate_out / gcd.  Output y[p + n q] = sum_i xpad[q o + i] * kernel[p, i] on x zero-padded by (width, width + o), cut to
@@ -128,10 +155,17 @@ class RecordingIngest:
     """The geometry of one kind of recording, tables on the device, built once.
     fps_in: int, float or (num, den); size_in = (H, W) of the raw frames; rate_in: Hz; channels_last: raw frames are (T, H, W, 3) as decoders hand them out,
     otherwise planar (T, 3, H, W); resize_side: what the short side is scaled to (256, the even cut of the other side as in example.py); crop stays 224, centred
-    with RGBSpatialCrop's origin int(round((Hr - 224) / 2.)).  ValueError on resize_side < crop, crop != 224, or a source so large that a filter row passes
-    35 taps (short side above ~2160 at resize_side 256)."""
+    with RGBSpatialCrop's origin int(round((Hr - 224) / 2.)).  pix_fmt: 'rgb24' (the layouts above), or 'nv12' / 'yuv420p': raw frames are (T, 3 H / 2, W), 8-bit
+    YUV 4:2:0 (ops.ingest_video_yuv), converted with csc_matrix(colorspace, full_range) after the resize.  ValueError on resize_side < crop, crop != 224, a source
+    so large that a filter row passes 35 taps (short side above ~2160 at resize_side 256), an unknown pix_fmt or colorspace, and for a YUV format odd H or W or
+    channels_last=True."""
 
-    def __init__(self, device, fps_in, size_in, rate_in: int, channels_last: bool = False, resize_side: int = 256, crop: int = CROP):
+    def __init__(self, device, fps_in, size_in, rate_in: int, channels_last: bool = False, resize_side: int = 256, crop: int = CROP, pix_fmt: str = 'rgb24',
+                 colorspace: str = 'bt601', full_range: bool = False):
+        if pix_fmt not in PIX_FMTS:
+            raise ValueError(f'pix_fmt = {pix_fmt!r}: one of {PIX_FMTS}')
+        if colorspace not in _KR_KB:
+            raise ValueError(f'colorspace = {colorspace!r}: one of {sorted(_KR_KB)}')
         if crop != CROP:
             raise ValueError(f'crop = {crop}: the model takes {CROP} x {CROP} frames')
         if resize_side < crop:
@@ -150,6 +184,20 @@ class RecordingIngest:
         self.taps_y, self.taps_x = ty, tx
         self.y_first, self.y_w = yf[self.y0:self.y0 + crop].contiguous().to(self.dev), yw[self.y0:self.y0 + crop].contiguous().to(self.dev)
         self.x_first, self.x_w = xf[self.x0:self.x0 + crop].contiguous().to(self.dev), xw[self.x0:self.x0 + crop].contiguous().to(self.dev)
+        self.pix_fmt = pix_fmt
+        if pix_fmt != 'rgb24':
+            if channels_last:
+                raise ValueError(f'channels_last=True with pix_fmt = {pix_fmt!r}: a YUV frame is (3 H / 2, W)')
+            if self.H % 2 or self.W % 2:
+                raise ValueError(f'{self.H} x {self.W} with pix_fmt = {pix_fmt!r}: 4:2:0 takes even H and W')
+            # chroma: an (H / 2, W / 2) image resized to the same (Hr, Wr), sliced at the same crop origin; never more taps than luma
+            cyf, cyw, self.taps_cy = aa_bicubic_table(self.H // 2, self.Hr)
+            cxf, cxw, self.taps_cx = aa_bicubic_table(self.W // 2, self.Wr)
+            self.cy_first, self.cy_w = cyf[self.y0:self.y0 + crop].contiguous().to(self.dev), cyw[self.y0:self.y0 + crop].contiguous().to(self.dev)
+            self.cx_first, self.cx_w = cxf[self.x0:self.x0 + crop].contiguous().to(self.dev), cxw[self.x0:self.x0 + crop].contiguous().to(self.dev)
+            self.colorspace, self.full_range = colorspace, bool(full_range)
+            M, off = csc_matrix(colorspace, full_range)
+            self.csc = torch.cat([M.reshape(9), off]).float()                        # host: the twelve floats travel as kernel arguments
         if self.rate_in == 16000:
             self.kernel, self.width, self.o, self.n = torch.ones(1, 1), 0, 1, 1   # down-mix / PCM scaling only
         else:
@@ -172,8 +220,8 @@ class RecordingIngest:
         return -(-self.n * int(n_in) // self.o)
 
     def _check_frames(self, raw: torch.Tensor):
-        want = (self.H, self.W, 3) if self.channels_last else (3, self.H, self.W)
-        if raw.dim() != 4 or raw.dtype != torch.uint8 or tuple(raw.shape[1:]) != want:
+        want = (self.H * 3 // 2, self.W) if self.pix_fmt != 'rgb24' else (self.H, self.W, 3) if self.channels_last else (3, self.H, self.W)
+        if raw.dim() != len(want) + 1 or raw.dtype != torch.uint8 or tuple(raw.shape[1:]) != want:
             raise ValueError(f'raw frames: expected uint8 (T, {", ".join(map(str, want))}), got {raw.dtype} {tuple(raw.shape)}')
 
     def frames(self, raw: torch.Tensor, j0: int, j1: int) -> torch.Tensor:
@@ -189,6 +237,9 @@ class RecordingIngest:
         t = table[j0:j1]
         lo, hi = int(t[0]), int(t[-1]) + 1                                       # the table is non-decreasing
         src = raw[lo:hi].to(self.dev, non_blocking=True)
+        if self.pix_fmt != 'rgb24':
+            return ops.ingest_video_yuv(src, self.pix_fmt, (t - lo).to(self.dev, non_blocking=True), self.y_first, self.y_w, self.x_first, self.x_w, self.cy_first,
+                                        self.cy_w, self.cx_first, self.cx_w, self.csc)
         return ops.ingest_video(src, self.channels_last, (t - lo).to(self.dev, non_blocking=True), self.y_first, self.y_w, self.x_first, self.x_w)
 
     def wave(self, raw_wave: torch.Tensor) -> torch.Tensor:

@@ -701,6 +701,44 @@ def ingest_video(raw: torch.Tensor, channels_last: bool, frame_table: torch.Tens
     return out
 
 
+def ingest_video_yuv(raw: torch.Tensor, pix_fmt: str, frame_table: torch.Tensor, y_first: torch.Tensor, y_w: torch.Tensor, x_first: torch.Tensor, x_w: torch.Tensor,
+                     cy_first: torch.Tensor, cy_w: torch.Tensor, cx_first: torch.Tensor, cx_w: torch.Tensor, csc, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ingest_video for 8-bit YUV 4:2:0 frames (sf_ingest_video_yuv): the three planes are resized, the colour matrix runs on the 224 x 224 result.  raw uint8
+    (n_src, 3 H / 2, W) on the device, H and W even, any frame stride; pix_fmt 'nv12' (H luma rows, then H / 2 rows of interleaved U V; any row stride >= W, so a
+    view into a pitched decoder surface is read in place) or 'yuv420p' (I420 as PyAV's to_ndarray gives it: H W luma bytes, then the U plane, then the V plane,
+    H / 2 x W / 2 each; contiguous rows).  y_* / x_*: the luma tables of ingest_video; cy_* / cx_*: the chroma tables (H / 2 -> Hr, W / 2 -> Wr), sliced at the
+    same crop origin; csc: 12 floats, the matrix row-major (rows R, G, B; columns Y, U, V) then the three offsets (ingest.csc_matrix) -> uint8 (T_out, 3, 224, 224)."""
+    if pix_fmt not in ('nv12', 'yuv420p'):
+        raise ValueError(f"ingest_video_yuv: pix_fmt = {pix_fmt!r} ('nv12' or 'yuv420p')")
+    if raw.dim() != 3 or raw.dtype != torch.uint8 or raw.shape[1] % 3 or raw.shape[2] % 2 or raw.shape[1] == 0 or raw.shape[2] == 0:
+        raise ValueError(f'ingest_video_yuv: expected uint8 frames (n, 3 H / 2, W) with even H and W, got {raw.dtype} {tuple(raw.shape)}')
+    n_src, H, W = raw.shape[0], raw.shape[1] // 3 * 2, raw.shape[2]
+    sf, sy, sx = raw.stride()
+    if sx != 1 or sf < 0 or (sy != W if pix_fmt == 'yuv420p' else sy < W):
+        raise ValueError(f'ingest_video_yuv: {pix_fmt} frames with strides {tuple(raw.stride())}: unit column stride and '
+                         f'{"contiguous rows" if pix_fmt == "yuv420p" else "a row stride of at least W"} expected')
+    u_off, v_off, csy, csx = (sy * H, sy * H + 1, sy, 2) if pix_fmt == 'nv12' else (H * W, H * W + (H // 2) * (W // 2), W // 2, 1)
+    csc = [float(v) for v in (csc.reshape(-1).tolist() if isinstance(csc, torch.Tensor) else csc)]
+    assert len(csc) == 12, 'ingest_video_yuv: csc is 9 matrix entries and 3 offsets'
+    csc_c = (C.c_float * 12)(*csc)
+    T_out = frame_table.numel()
+    firsts, weights = (y_first, x_first, cy_first, cx_first), (y_w, x_w, cy_w, cx_w)
+    assert frame_table.dtype == torch.int32 and all(t.dtype == torch.int32 and t.shape == (INGEST_OUT,) for t in firsts)
+    assert all(t.dtype == torch.float32 and t.dim() == 2 and t.shape[0] == INGEST_OUT for t in weights)
+    assert all(t.is_contiguous() for t in (frame_table, *firsts, *weights))
+    if out is None:
+        out = torch.empty(T_out, 3, INGEST_OUT, INGEST_OUT, device=raw.device, dtype=torch.uint8)
+    assert out.dtype == torch.uint8 and out.shape == (T_out, 3, INGEST_OUT, INGEST_OUT) and out.is_contiguous()
+    for t0 in range(0, max(T_out, 1), 65535):                                    # the launcher takes 65535 output frames at a time
+        n = min(65535, T_out - t0)
+        rc = _lib.load().sf_ingest_video_yuv(_dev(raw, 'raw'), sf, sy, u_off, v_off, csy, csx, n_src, H, W, _dev(frame_table[t0:], 'frame_table'),
+                                             _dev(y_first, 'y_first'), _dev(y_w, 'y_w'), y_w.shape[1], _dev(x_first, 'x_first'), _dev(x_w, 'x_w'), x_w.shape[1],
+                                             _dev(cy_first, 'cy_first'), _dev(cy_w, 'cy_w'), cy_w.shape[1], _dev(cx_first, 'cx_first'), _dev(cx_w, 'cx_w'),
+                                             cx_w.shape[1], C.addressof(csc_c), _dev(out[t0:], 'out'), n, _stream())
+        _lib.check(rc, 'sf_ingest_video_yuv')
+    return out
+
+
 SF_I16 = 4
 
 
