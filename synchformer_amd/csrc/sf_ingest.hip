@@ -5,46 +5,49 @@
 //                      tile of output rows needs (fp32, kept in LDS), then the vertical pass over those rows.
 //   sf_ingest_video_yuv: the same for 8-bit YUV 4:2:0 frames (NV12, I420): the three planes are resized, the colour matrix runs on the 224 x 224 result.
 //   sf_resample_wave:  zero-delay polyphase windowed-sinc resampler (the bank of ingest.resample_kernel), channels averaged on read, zero padding by bounds checks.
+// Both video kernels run ONE resize pipeline, ing_plane_pass: ingest_video_kernel once per workgroup (one channel), ingest_video_yuv_kernel twice (luma, then U and
+// V together); the launchers size its LDS with one formula, ing_geometry.
 // All kernels bound every address they form by the sizes the launcher was given: a table with entries outside the source only changes the picture, never the
 // addresses (frame index, first-tap row / column and every tap are clamped or skipped).
+#include <initializer_list>
+
 #include "sf_common.h"
 #include "../../include/synchformer_hip.h"
 
 #define ING_OUT 224            // output rows = columns (the model's input size)
-#define ING_TY 8               // output rows per workgroup: 28 row tiles x 3 channels x T_out workgroups
+#define ING_TY 8               // output rows per workgroup
 #define ING_MAX_TAPS 35        // 2 * ceil(2 * scale) + 1 at scale <= 8.5: a short side up to 2160 at resize_side 256
 #define ING_MAX_ROWS 8         // source rows per chunk (4 when the source is wide: the launcher sizes it so that everything fits 64 KiB of LDS)
 #define ING_LDS_BYTES 65536
-#define ING_PF 20              // staged dwords per lane per chunk at most: R * RP / 4 <= 5120
+#define ING_PF 20              // staged dwords per lane per chunk at most: NP * R * RP / 4 <= 5120
 #define ING_ROW_SLACK 8        // bytes behind a staged row that the horizontal pass may read (always against a zero weight)
 
-// One workgroup = output rows [r0, r0 + 8) of one channel of one output frame, 256 threads.
+// The resize of output rows [r0, r0 + 8) of NP planes of one frame that share their geometry and tables (NP = 1: one RGB channel, or luma; NP = 2: U and V), by the
+// 256 threads of a workgroup.  Element (y, x) of plane p is s[p][y * sy + x * sx].  Adds into a0[p] / a1[p]: this lane's 4 columns 4 q .. 4 q + 3 of output rows
+// r0 + rg and r0 + rg + 4 (q = tid % 56, rg = tid / 56, lanes < 224).  A caller that runs it twice on the same LDS puts a barrier between the two.
 //   LDS:  xw   [TW][224]     fp32   the horizontal table transposed (lane x reads xw[.][x]: no bank conflicts), tap j in row j + 3, zero rows around it
 //         yw   [8][taps_y]   fp32   this tile's vertical weights
-//         mid  [R][224]      fp32   the horizontal pass of the current chunk of R source rows
-//         rows [R][RP]       uint8  those source rows from column xlo on, zero beyond the picture (RP = W + taps_x rounded up to 4, + 8)
+//         mid  [NP R][224]   fp32   the horizontal pass of the current chunk of R source rows of each plane
+//         rows [NP R][RP]    uint8  those source rows from column xlo on, zero beyond the picture (RP = W + taps_x rounded up to 4, + 8); plane p in staged rows
+//                                   [p R, (p + 1) R).  R % 4 == 0 and NP R <= 8, so that a horizontal item (4 source rows, one output column) never straddles planes
 // Per chunk:
-//  (1) staging: a lane fetches 4 neighbouring source bytes (one dword where the layout allows it, else 4 byte loads at stride sx: 3 for channels-last) and writes
-//      one LDS dword; consecutive lanes cover consecutive bytes of the row.  The loads of chunk k + 1 are issued into registers before the horizontal pass of
-//      chunk k and written to LDS after its vertical pass: two barriers per chunk, no global latency between them;
+//  (1) staging: a lane fetches 4 neighbouring source bytes of each plane (one dword where the layout allows it, else 4 byte loads at stride sx: 3 for channels-last)
+//      and writes one LDS dword per plane; consecutive lanes cover consecutive bytes of the row.  INTER: s1 == s0 + 1 and sx == 2 (NV12) - the 8 bytes
+//      U V U V U V U V of four chroma columns are fetched once as two dwords and split into the U and the V dword in registers.  The loads of chunk k + 1 are issued
+//      into registers before the horizontal pass of chunk k and written to LDS after its vertical pass: two barriers per chunk, no global latency between them;
 //  (2) horizontal pass, lane = output column, four source rows at a time: the taps [off, off + taps_x) are read as the aligned dwords that cover them, and byte
 //      k of dword d meets weight row 4 d + k + 3 - (off & 3) - tap j = 4 d + k - (off & 3), or a zero row outside [0, taps_x): sums run in ascending j;
-//  (3) vertical pass, lane = four output columns of output rows ty and ty + 4: acc += yw[ty][row - first] * mid[row], rows ascending.
-// Then round half to even, clamp, one 4-byte store per lane: 56 lanes write one full 224-byte line.
-__global__ __launch_bounds__(256) void ingest_video_kernel(const uint8_t* __restrict__ raw, int64_t sf, int64_t sc, int64_t sy, int64_t sx, int n_src, int H, int W,
-                                                            const int32_t* __restrict__ frame_table, const int32_t* __restrict__ y_first,
-                                                            const float* __restrict__ y_w, int taps_y, const int32_t* __restrict__ x_first,
-                                                            const float* __restrict__ x_w, int taps_x, uint8_t* __restrict__ out, int R, int RP, int TW) {
-  extern __shared__ __align__(16) unsigned char ing_lds[];
-  float* xw = (float*)ing_lds;
+//  (3) vertical pass, lane = four output columns of output rows rg and rg + 4 of the tile: acc += yw[row][y - first] * mid[y], source rows y ascending.
+template <int NP, bool INTER>
+__device__ __forceinline__ void ing_plane_pass(unsigned char* lds, const uint8_t* __restrict__ s0, const uint8_t* __restrict__ s1, int64_t sy, int64_t sx, int H, int W,
+                                               const int32_t* __restrict__ y_first, const float* __restrict__ y_w, int taps_y,
+                                               const int32_t* __restrict__ x_first, const float* __restrict__ x_w, int taps_x, int R, int RP, int TW, int r0,
+                                               float (&a0)[NP][4], float (&a1)[NP][4]) {
+  float* xw = (float*)lds;
   float* yw = xw + TW * ING_OUT;
   float* mid = yw + ING_TY * taps_y;
-  uint32_t* rows = (uint32_t*)(mid + R * ING_OUT);
+  uint32_t* rows = (uint32_t*)(mid + NP * R * ING_OUT);
   const int tid = threadIdx.x;
-  const int r0 = blockIdx.x * ING_TY, ch = blockIdx.y, fo = blockIdx.z;
-  int fs = frame_table[fo];
-  fs = fs < 0 ? 0 : (fs >= n_src ? n_src - 1 : fs);
-  const uint8_t* src = raw + (int64_t)fs * sf + (int64_t)ch * sc;
 
   for (int i = tid; i < TW * ING_OUT; i += 256) {
     const int row = i / ING_OUT;
@@ -67,204 +70,13 @@ __global__ __launch_bounds__(256) void ingest_video_kernel(const uint8_t* __rest
   const bool vert = tid < 224;
   int yf0 = 0, yf1 = 0;
   if (vert) { yf0 = y_first[r0 + rg]; yf1 = y_first[r0 + rg + 4]; }
-  float acc0[4] = {0.f, 0.f, 0.f, 0.f}, acc1[4] = {0.f, 0.f, 0.f, 0.f};
   const int Q4 = RP >> 2;                                                       // dwords per staged row
   const int nd = (taps_x + 6) >> 2;                                             // aligned dwords that cover taps_x bytes at any byte offset (TW = 4 nd + 3)
   const int valid_x = W - xlo;
-  const int n_stage = R * Q4;                                                   // <= 256 * ING_PF (launcher)
-
-  // horizontal pass ownership: items (group of 4 source rows, output column) tid and tid + 256 of (R / 4) * 224 <= 448; their table entries are read here, so
-  // that the chunk loop issues no global load but the prefetch
-  const uint32_t* hp[2];
-  const float* hw[2];
-  float* hm[2];
-  bool hon[2];
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int it = tid + 256 * k;
-    hon[k] = it < (R / 4) * ING_OUT;
-    const int g = it / ING_OUT, x = it - g * ING_OUT;
-    int off = hon[k] ? x_first[x] - xlo : 0;
-    off = off < 0 ? 0 : (off > RP - ING_ROW_SLACK - taps_x ? RP - ING_ROW_SLACK - taps_x : off);
-    hp[k] = rows + (g * 4) * Q4 + (off >> 2);
-    hw[k] = xw + (3 - (off & 3)) * ING_OUT + x;
-    hm[k] = mid + (g * 4) * ING_OUT + x;
-  }
-
-  // staging of the R source rows from yc on, through registers: fetch() issues the loads (rows at or beyond ye and columns at or beyond W are zero), commit()
-  // writes them to LDS a phase later, so the loads of chunk k + 1 travel under the horizontal pass of chunk k
-  uint32_t pf[ING_PF];
-  auto fetch = [&](int yc) {
-#pragma unroll
-    for (int k = 0; k < ING_PF; ++k) {
-      const int it = tid + 256 * k;
-      uint32_t v = 0;
-      if (it < n_stage) {
-        const int r = it / Q4, p = (it - r * Q4) * 4;
-        const int y = yc + r;
-        if (y < ye && p < valid_x) {
-          const uint8_t* g = src + (int64_t)y * sy + (int64_t)(xlo + p) * sx;
-          if (sx == 1 && p + 3 < valid_x && ((uintptr_t)g & 3) == 0) {
-            v = *(const uint32_t*)g;
-          } else {
-            v = g[0];
-            if (p + 1 < valid_x) v |= (uint32_t)g[sx] << 8;
-            if (p + 2 < valid_x) v |= (uint32_t)g[2 * sx] << 16;
-            if (p + 3 < valid_x) v |= (uint32_t)g[3 * sx] << 24;
-          }
-        }
-      }
-      pf[k] = v;
-    }
-  };
-  auto commit = [&]() {
-#pragma unroll
-    for (int k = 0; k < ING_PF; ++k) {
-      const int it = tid + 256 * k;
-      if (it < n_stage) rows[it] = pf[k];
-    }
-  };
-
-  if (ys < ye) {
-    fetch(ys);
-    commit();
-  }
-  __syncthreads();                                                             // rows of the first chunk, xw, yw
-  for (int yc = ys; yc < ye; yc += R) {
-    const bool more = yc + R < ye;                                             // block-uniform
-    if (more) fetch(yc + R);
-    // horizontal pass: the taps as aligned dwords against the zero-padded table
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      if (hon[k]) {
-        const uint32_t* p0 = hp[k];
-        const float* wp = hw[k];
-        float h0 = 0.f, h1 = 0.f, h2 = 0.f, h3 = 0.f;
-        for (int d = 0; d < nd; ++d) {
-          const uint32_t v0 = p0[d], v1 = p0[Q4 + d], v2 = p0[2 * Q4 + d], v3 = p0[3 * Q4 + d];
-#pragma unroll
-          for (int b = 0; b < 4; ++b) {
-            const float w = wp[(4 * d + b) * ING_OUT];
-            h0 = fmaf(w, (float)((v0 >> (8 * b)) & 255u), h0);
-            h1 = fmaf(w, (float)((v1 >> (8 * b)) & 255u), h1);
-            h2 = fmaf(w, (float)((v2 >> (8 * b)) & 255u), h2);
-            h3 = fmaf(w, (float)((v3 >> (8 * b)) & 255u), h3);
-          }
-        }
-        float* m = hm[k];
-        m[0] = h0; m[ING_OUT] = h1; m[2 * ING_OUT] = h2; m[3 * ING_OUT] = h3;
-      }
-    }
-    __syncthreads();                                                           // mid complete; every lane is past its reads of rows
-    // vertical pass over the chunk's rows
-    if (vert) {
-      const int n = ye - yc < R ? ye - yc : R;
-      for (int r = 0; r < n; ++r) {
-        const int j0 = yc + r - yf0, j1 = yc + r - yf1;
-        const bool in0 = j0 >= 0 && j0 < taps_y, in1 = j1 >= 0 && j1 < taps_y;
-        if (in0 || in1) {
-          const f32x4 v = *(const f32x4*)(mid + r * ING_OUT + 4 * q);
-          if (in0) {
-            const float w = yw[rg * taps_y + j0];
-            acc0[0] = fmaf(w, v.x, acc0[0]); acc0[1] = fmaf(w, v.y, acc0[1]); acc0[2] = fmaf(w, v.z, acc0[2]); acc0[3] = fmaf(w, v.w, acc0[3]);
-          }
-          if (in1) {
-            const float w = yw[(rg + 4) * taps_y + j1];
-            acc1[0] = fmaf(w, v.x, acc1[0]); acc1[1] = fmaf(w, v.y, acc1[1]); acc1[2] = fmaf(w, v.z, acc1[2]); acc1[3] = fmaf(w, v.w, acc1[3]);
-          }
-        }
-      }
-    }
-    if (more) {
-      commit();
-      __syncthreads();                                                         // rows of the next chunk complete; every lane is past its reads of mid
-    }
-  }
-  if (vert) {
-    uint8_t* o = out + (((int64_t)fo * 3 + ch) * ING_OUT + r0 + rg) * ING_OUT + 4 * q;
-    uint32_t w0 = 0, w1 = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float a = fminf(fmaxf(rintf(acc0[k]), 0.f), 255.f), b = fminf(fmaxf(rintf(acc1[k]), 0.f), 255.f);
-      w0 |= (uint32_t)a << (8 * k);
-      w1 |= (uint32_t)b << (8 * k);
-    }
-    *(uint32_t*)o = w0;
-    *(uint32_t*)(o + 4 * ING_OUT) = w1;
-  }
-}
-
-extern "C" int sf_ingest_video(const uint8_t* raw, int64_t stride_frame, int64_t stride_channel, int64_t stride_row, int64_t stride_col, int n_src, int H, int W,
-                               const int32_t* frame_table, const int32_t* y_first, const float* y_w, int taps_y, const int32_t* x_first, const float* x_w,
-                               int taps_x, uint8_t* out, int T_out, void* stream) {
-  SF_CHECK_ARG(T_out >= 0 && T_out <= 65535, "sf_ingest_video: T_out = %d output frames per launch (0 .. 65535: grid z)", T_out);
-  SF_CHECK_ARG(n_src >= 1 && H >= 1 && W >= 1, "sf_ingest_video: source of %d frames %d x %d", n_src, H, W);
-  SF_CHECK_ARG(taps_y >= 1 && taps_y <= ING_MAX_TAPS && taps_x >= 1 && taps_x <= ING_MAX_TAPS,
-               "sf_ingest_video: taps_y = %d, taps_x = %d out of range (1 .. %d: a short side up to 2160 at resize side 256)", taps_y, taps_x, ING_MAX_TAPS);
-  SF_CHECK_ARG(stride_frame >= 0 && stride_channel >= 0 && stride_row >= 0 && stride_col >= 1, "sf_ingest_video: negative or zero byte stride");
-  if (T_out == 0) return 0;
-  SF_CHECK_ARG(raw && frame_table && y_first && y_w && x_first && x_w && out, "sf_ingest_video: null pointer");
-  SF_CHECK_ARG(((uintptr_t)out & 3) == 0, "sf_ingest_video: out must be 4-byte aligned");
-  SF_CHECK_ARG(W <= 1 << 20, "sf_ingest_video: W = %d is too wide for four staged source rows in LDS at taps_x = %d", W, taps_x);
-  const int RP = ((W + taps_x + 3) & ~3) + ING_ROW_SLACK;
-  const int TW = 4 * ((taps_x + 6) >> 2) + 3;
-  const int fixed = (TW * ING_OUT + ING_TY * taps_y) * 4;
-  int R = (ING_LDS_BYTES - fixed) / (RP + ING_OUT * 4);
-  R = R > ING_MAX_ROWS ? ING_MAX_ROWS : R;
-  if (R > 256 * ING_PF * 4 / RP) R = 256 * ING_PF * 4 / RP;                     // a chunk is staged through ING_PF registers per lane
-  R &= ~3;
-  SF_CHECK_ARG(R >= 4, "sf_ingest_video: W = %d is too wide for four staged source rows in LDS at taps_x = %d", W, taps_x);
-  const int lds = fixed + R * (RP + ING_OUT * 4);
-  hipLaunchKernelGGL(ingest_video_kernel, dim3(ING_OUT / ING_TY, 3, (unsigned)T_out), dim3(256), lds, (hipStream_t)stream, raw, stride_frame, stride_channel,
-                     stride_row, stride_col, n_src, H, W, frame_table, y_first, y_w, taps_y, x_first, x_w, taps_x, out, R, RP, TW);
-  SF_LAUNCH_CHECK();
-  return 0;
-}
-
-// ---- YUV 4:2:0 -------------------------------------------------------------------------------------------------------------------------------------------
-struct IngCsc { float m[9], o[3]; };                                             // M row-major (rows R, G, B; columns Y, U, V), then the offsets
-
-// The pipeline of ingest_video_kernel over NP planes of one frame that share their geometry and tables (NP = 1: luma; NP = 2: U and V), on the LDS of the
-// workgroup:  xw [TW][224] | yw [8][taps_y] | mid [NP R][224] | rows [NP R][RP], plane p in staged rows [p R, (p + 1) R); R source rows of each plane per chunk,
-// R % 4 == 0 and NP R <= 8, so that a horizontal item (4 source rows, one output column) never straddles two planes.  Element (y, x) of plane p is
-// s[p][y * sy + x * sx].  INTER: s1 == s0 + 1 and sx == 2 (NV12) - the 8 bytes U V U V U V U V of four chroma columns are fetched once as two dwords and split
-// into the U and the V dword in registers.  Adds into a0[p] / a1[p]: this lane's 4 columns of output rows r0 + rg and r0 + rg + 4 (lanes < 224).
-template <int NP, bool INTER>
-__device__ __forceinline__ void ing_plane_pass(unsigned char* lds, const uint8_t* __restrict__ s0, const uint8_t* __restrict__ s1, int64_t sy, int64_t sx, int H, int W, const int32_t* __restrict__ y_first, const float* __restrict__ y_w, int taps_y,
-                                               const int32_t* __restrict__ x_first, const float* __restrict__ x_w, int taps_x, int R, int RP, int TW, int r0,
-                                               float (&a0)[NP][4], float (&a1)[NP][4]) {
-  float* xw = (float*)lds;
-  float* yw = xw + TW * ING_OUT;
-  float* mid = yw + ING_TY * taps_y;
-  uint32_t* rows = (uint32_t*)(mid + NP * R * ING_OUT);
-  const int tid = threadIdx.x;
-  __syncthreads();                                                             // every lane is past the LDS of the pass before this one
-
-  for (int i = tid; i < TW * ING_OUT; i += 256) {
-    const int row = i / ING_OUT;
-    if (row < 3 || row >= taps_x + 3) xw[i] = 0.f;
-  }
-  for (int i = tid; i < taps_x * ING_OUT; i += 256) {
-    const int x = i / taps_x, j = i - x * taps_x;
-    xw[(j + 3) * ING_OUT + x] = x_w[i];
-  }
-  for (int i = tid; i < ING_TY * taps_y; i += 256) yw[i] = y_w[(int64_t)r0 * taps_y + i];
-
-  int xlo = x_first[0];
-  xlo = xlo < 0 ? 0 : (xlo > W ? W : xlo);
-  int ys = y_first[r0], ye = y_first[r0 + ING_TY - 1] + taps_y;
-  ys = ys < 0 ? 0 : ys;
-  ye = ye > H ? H : ye;
-
-  const int q = tid % 56, rg = tid / 56;
-  const bool vert = tid < 224;
-  int yf0 = 0, yf1 = 0;
-  if (vert) { yf0 = y_first[r0 + rg]; yf1 = y_first[r0 + rg + 4]; }
-  const int Q4 = RP >> 2;
-  const int nd = (taps_x + 6) >> 2;
-  const int valid_x = W - xlo;
   const int n_stage = R * Q4;                                                   // staging items: 4 columns of one row of every plane; NP n_stage <= 256 * ING_PF
 
+  // horizontal pass ownership: items (group of 4 source rows, output column) tid and tid + 256 of (NP R / 4) * 224 <= 448; their table entries are read here, so
+  // that the chunk loop issues no global load but the prefetch
   const uint32_t* hp[2];
   const float* hw[2];
   float* hm[2];
@@ -281,6 +93,8 @@ __device__ __forceinline__ void ing_plane_pass(unsigned char* lds, const uint8_t
     hm[k] = mid + (g * 4) * ING_OUT + x;
   }
 
+  // staging of the R source rows of each plane from yc on, through registers: fetch() issues the loads (rows at or beyond ye and columns at or beyond W are
+  // zero), commit() writes them to LDS a phase later, so the loads of chunk k + 1 travel under the horizontal pass of chunk k
   uint32_t pf[ING_PF];
   auto fetch = [&](int yc) {
 #pragma unroll
@@ -336,10 +150,11 @@ __device__ __forceinline__ void ing_plane_pass(unsigned char* lds, const uint8_t
     fetch(ys);
     commit();
   }
-  __syncthreads();
+  __syncthreads();                                                             // rows of the first chunk, xw, yw
   for (int yc = ys; yc < ye; yc += R) {
-    const bool more = yc + R < ye;
+    const bool more = yc + R < ye;                                             // block-uniform
     if (more) fetch(yc + R);
+    // horizontal pass: the taps as aligned dwords against the zero-padded table
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       if (hon[k]) {
@@ -361,7 +176,8 @@ __device__ __forceinline__ void ing_plane_pass(unsigned char* lds, const uint8_t
         m[0] = h0; m[ING_OUT] = h1; m[2 * ING_OUT] = h2; m[3 * ING_OUT] = h3;
       }
     }
-    __syncthreads();
+    __syncthreads();                                                           // mid complete; every lane is past its reads of rows
+    // vertical pass over the chunk's rows
     if (vert) {
       const int n = ye - yc < R ? ye - yc : R;
       for (int r = 0; r < n; ++r) {
@@ -380,14 +196,49 @@ __device__ __forceinline__ void ing_plane_pass(unsigned char* lds, const uint8_t
     }
     if (more) {
       commit();
-      __syncthreads();
+      __syncthreads();                                                         // rows of the next chunk complete; every lane is past its reads of mid
     }
   }
 }
 
+// The source frame of output frame fo, clamped into the recording.
+__device__ __forceinline__ int ing_pick_frame(const int32_t* __restrict__ frame_table, int fo, int n_src) {
+  const int fs = frame_table[fo];
+  return fs < 0 ? 0 : (fs >= n_src ? n_src - 1 : fs);
+}
+
+// Four fp32 levels -> round half to even, clamp to [0, 255], one byte each, column k in byte k.
+__device__ __forceinline__ uint32_t ing_pack4(const float (&v)[4]) {
+  uint32_t w = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) w |= (uint32_t)fminf(fmaxf(rintf(v[k]), 0.f), 255.f) << (8 * k);
+  return w;
+}
+
+// One workgroup = output rows [r0, r0 + 8) of one channel of one output frame (28 row tiles x 3 channels x T_out workgroups): one ing_plane_pass over that channel's
+// plane, then one 4-byte store per lane and row: 56 lanes write one full 224-byte line.
+__global__ __launch_bounds__(256) void ingest_video_kernel(const uint8_t* __restrict__ raw, int64_t sf, int64_t sc, int64_t sy, int64_t sx, int n_src, int H, int W,
+                                                            const int32_t* __restrict__ frame_table, const int32_t* __restrict__ y_first,
+                                                            const float* __restrict__ y_w, int taps_y, const int32_t* __restrict__ x_first,
+                                                            const float* __restrict__ x_w, int taps_x, uint8_t* __restrict__ out, int R, int RP, int TW) {
+  extern __shared__ __align__(16) unsigned char ing_lds[];
+  const int tid = threadIdx.x;
+  const int r0 = blockIdx.x * ING_TY, ch = blockIdx.y, fo = blockIdx.z;
+  const uint8_t* src = raw + (int64_t)ing_pick_frame(frame_table, fo, n_src) * sf + (int64_t)ch * sc;
+  float a0[1][4] = {}, a1[1][4] = {};
+  ing_plane_pass<1, false>(ing_lds, src, src, sy, sx, H, W, y_first, y_w, taps_y, x_first, x_w, taps_x, R, RP, TW, r0, a0, a1);
+  if (tid < 224) {
+    uint8_t* o = out + (((int64_t)fo * 3 + ch) * ING_OUT + r0 + tid / 56) * ING_OUT + 4 * (tid % 56);
+    *(uint32_t*)o = ing_pack4(a0[0]);
+    *(uint32_t*)(o + 4 * ING_OUT) = ing_pack4(a1[0]);
+  }
+}
+
+struct IngCsc { float m[9], o[3]; };                                             // M row-major (rows R, G, B; columns Y, U, V), then the offsets
+
 // One workgroup = output rows [r0, r0 + 8) of ALL THREE channels of one output frame: the luma plane through ing_plane_pass (chunks of R source rows), then U and
 // V together (chunks of 4 rows of each; their tables replace the luma ones in the same LDS), the three resized 8 x 224 fp32 tiles staying in registers (24 per
-// lane); then the colour matrix, round half to even, clamp and three full 224-byte lines per output row.
+// lane); then the colour matrix and three full 224-byte lines per output row.
 template <bool INTER>
 __global__ __launch_bounds__(256) void ingest_video_yuv_kernel(const uint8_t* __restrict__ raw, int64_t sf, int64_t sy, int64_t u_off, int64_t v_off, int64_t csy,
                                                                 int64_t csx, int n_src, int H, int W, const int32_t* __restrict__ frame_table,
@@ -396,81 +247,100 @@ __global__ __launch_bounds__(256) void ingest_video_yuv_kernel(const uint8_t* __
                                                                 const int32_t* __restrict__ cy_first, const float* __restrict__ cy_w, int taps_cy,
                                                                 const int32_t* __restrict__ cx_first, const float* __restrict__ cx_w, int taps_cx, IngCsc csc,
                                                                 uint8_t* __restrict__ out, int R, int RP, int TW, int RPc, int TWc) {
-  extern __shared__ __align__(16) unsigned char ing_yuv_lds[];
-  const int r0 = blockIdx.x * ING_TY, fo = blockIdx.y;
-  int fs = frame_table[fo];
-  fs = fs < 0 ? 0 : (fs >= n_src ? n_src - 1 : fs);
-  const uint8_t* src = raw + (int64_t)fs * sf;
-  float ya[1][4] = {}, yb[1][4] = {}, c0[2][4] = {}, c1[2][4] = {};
-  ing_plane_pass<1, false>(ing_yuv_lds, src, src, sy, 1, H, W, y_first, y_w, taps_y, x_first, x_w, taps_x, R, RP, TW, r0, ya, yb);
-  ing_plane_pass<2, INTER>(ing_yuv_lds, src + u_off, src + v_off, csy, csx, H >> 1, W >> 1, cy_first, cy_w, taps_cy, cx_first, cx_w,
-                           taps_cx, 4, RPc, TWc, r0, c0, c1);
+  extern __shared__ __align__(16) unsigned char ing_lds[];
   const int tid = threadIdx.x;
+  const int r0 = blockIdx.x * ING_TY, fo = blockIdx.y;
+  const uint8_t* src = raw + (int64_t)ing_pick_frame(frame_table, fo, n_src) * sf;
+  float ya[1][4] = {}, yb[1][4] = {}, c0[2][4] = {}, c1[2][4] = {};
+  ing_plane_pass<1, false>(ing_lds, src, src, sy, 1, H, W, y_first, y_w, taps_y, x_first, x_w, taps_x, R, RP, TW, r0, ya, yb);
+  __syncthreads();                                                             // every lane is past the LDS of the luma pass
+  ing_plane_pass<2, INTER>(ing_lds, src + u_off, src + v_off, csy, csx, H >> 1, W >> 1, cy_first, cy_w, taps_cy, cx_first, cx_w, taps_cx, 4, RPc, TWc, r0, c0, c1);
   if (tid < 224) {
-    const int q = tid % 56, rg = tid / 56;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      uint32_t w[3] = {0, 0, 0};
+      float t[3][4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const float y = (h ? yb[0][k] : ya[0][k]) - csc.o[0], u = (h ? c1[0][k] : c0[0][k]) - csc.o[1], v = (h ? c1[1][k] : c0[1][k]) - csc.o[2];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const float t = fmaf(csc.m[3 * c + 2], v, fmaf(csc.m[3 * c + 1], u, csc.m[3 * c] * y));
-          w[c] |= (uint32_t)fminf(fmaxf(rintf(t), 0.f), 255.f) << (8 * k);
-        }
+        for (int c = 0; c < 3; ++c) t[c][k] = fmaf(csc.m[3 * c + 2], v, fmaf(csc.m[3 * c + 1], u, csc.m[3 * c] * y));
       }
 #pragma unroll
-      for (int c = 0; c < 3; ++c) *(uint32_t*)(out + (((int64_t)fo * 3 + c) * ING_OUT + r0 + rg + 4 * h) * ING_OUT + 4 * q) = w[c];
+      for (int c = 0; c < 3; ++c) *(uint32_t*)(out + (((int64_t)fo * 3 + c) * ING_OUT + r0 + tid / 56 + 4 * h) * ING_OUT + 4 * (tid % 56)) = ing_pack4(t[c]);
     }
   }
+}
+
+// The LDS geometry of ing_plane_pass over `planes` planes of width W: the staged row RP, the padded table's rows TW, the chunk R - what ING_LDS_BYTES leave after
+// the padded horizontal table and the tile's vertical weights, over the bytes of one staged row plus one row of the horizontal pass of every plane, at most
+// max_rows and at most ING_PF staging registers per lane, rounded down to a multiple of 4 - and the bytes in all.  false: not even 4 rows fit.
+struct IngGeom { int RP, TW, R, lds; };
+static bool ing_geometry(int W, int taps_y, int taps_x, int planes, int max_rows, IngGeom* g) {
+  g->RP = ((W + taps_x + 3) & ~3) + ING_ROW_SLACK;
+  g->TW = 4 * ((taps_x + 6) >> 2) + 3;
+  const int fixed = (g->TW * ING_OUT + ING_TY * taps_y) * 4, per_row = planes * (g->RP + ING_OUT * 4);
+  int R = (ING_LDS_BYTES - fixed) / per_row;
+  R = R > max_rows ? max_rows : R;
+  if (R > 256 * ING_PF * 4 / (planes * g->RP)) R = 256 * ING_PF * 4 / (planes * g->RP);
+  g->R = R & ~3;
+  g->lds = fixed + g->R * per_row;
+  return g->R >= 4;
+}
+
+// The argument checks both launchers share (0, or -1 with sf_last_error set); out and W are looked at only when there is something to launch.
+static int ing_check_args(const char* who, int T_out, std::initializer_list<int> taps, const void* out, int W) {
+  SF_CHECK_ARG(T_out >= 0 && T_out <= 65535, "%s: T_out = %d output frames per launch (0 .. 65535: one grid dimension)", who, T_out);
+  for (const int t : taps)
+    SF_CHECK_ARG(t >= 1 && t <= ING_MAX_TAPS, "%s: %d filter taps out of range (1 .. %d: a short side up to 2160 at resize side 256)", who, t, ING_MAX_TAPS);
+  SF_CHECK_ARG(T_out == 0 || ((uintptr_t)out & 3) == 0, "%s: out must be 4-byte aligned", who);
+  SF_CHECK_ARG(T_out == 0 || W <= 1 << 20, "%s: W = %d is too wide for four staged source rows in LDS", who, W);
+  return 0;
+}
+
+extern "C" int sf_ingest_video(const uint8_t* raw, int64_t stride_frame, int64_t stride_channel, int64_t stride_row, int64_t stride_col, int n_src, int H, int W,
+                               const int32_t* frame_table, const int32_t* y_first, const float* y_w, int taps_y, const int32_t* x_first, const float* x_w,
+                               int taps_x, uint8_t* out, int T_out, void* stream) {
+  if (ing_check_args("sf_ingest_video", T_out, {taps_y, taps_x}, out, W)) return -1;
+  SF_CHECK_ARG(n_src >= 1 && H >= 1 && W >= 1, "sf_ingest_video: source of %d frames %d x %d", n_src, H, W);
+  SF_CHECK_ARG(stride_frame >= 0 && stride_channel >= 0 && stride_row >= 0 && stride_col >= 1, "sf_ingest_video: negative or zero byte stride");
+  if (T_out == 0) return 0;
+  SF_CHECK_ARG(raw && frame_table && y_first && y_w && x_first && x_w && out, "sf_ingest_video: null pointer");
+  IngGeom g;
+  SF_CHECK_ARG(ing_geometry(W, taps_y, taps_x, 1, ING_MAX_ROWS, &g), "sf_ingest_video: W = %d is too wide for four staged source rows in LDS at taps_x = %d", W,
+               taps_x);
+  hipLaunchKernelGGL(ingest_video_kernel, dim3(ING_OUT / ING_TY, 3, (unsigned)T_out), dim3(256), g.lds, (hipStream_t)stream, raw, stride_frame, stride_channel,
+                     stride_row, stride_col, n_src, H, W, frame_table, y_first, y_w, taps_y, x_first, x_w, taps_x, out, g.R, g.RP, g.TW);
+  SF_LAUNCH_CHECK();
+  return 0;
 }
 
 extern "C" int sf_ingest_video_yuv(const uint8_t* raw, int64_t stride_frame, int64_t stride_row, int64_t u_off, int64_t v_off, int64_t stride_crow,
                                    int64_t stride_ccol, int n_src, int H, int W, const int32_t* frame_table, const int32_t* y_first, const float* y_w, int taps_y,
                                    const int32_t* x_first, const float* x_w, int taps_x, const int32_t* cy_first, const float* cy_w, int taps_cy,
                                    const int32_t* cx_first, const float* cx_w, int taps_cx, const float* csc, uint8_t* out, int T_out, void* stream) {
-  SF_CHECK_ARG(T_out >= 0 && T_out <= 65535, "sf_ingest_video_yuv: T_out = %d output frames per launch (0 .. 65535: grid y)", T_out);
+  if (ing_check_args("sf_ingest_video_yuv", T_out, {taps_y, taps_x, taps_cy, taps_cx}, out, W)) return -1;
   SF_CHECK_ARG(n_src >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, "sf_ingest_video_yuv: source of %d frames %d x %d (4:2:0 takes even H and W)", n_src, H, W);
-  SF_CHECK_ARG(taps_y >= 1 && taps_y <= ING_MAX_TAPS && taps_x >= 1 && taps_x <= ING_MAX_TAPS && taps_cy >= 1 && taps_cy <= ING_MAX_TAPS && taps_cx >= 1 &&
-                   taps_cx <= ING_MAX_TAPS,
-               "sf_ingest_video_yuv: luma taps %d x %d, chroma taps %d x %d out of range (1 .. %d)", taps_y, taps_x, taps_cy, taps_cx, ING_MAX_TAPS);
   SF_CHECK_ARG(stride_frame >= 0 && stride_row >= 0 && u_off >= 0 && v_off >= 0 && stride_crow >= 0 && stride_ccol >= 1,
                "sf_ingest_video_yuv: negative byte stride or offset, or a chroma column stride below 1");
   if (T_out == 0) return 0;
   SF_CHECK_ARG(raw && frame_table && y_first && y_w && x_first && x_w && cy_first && cy_w && cx_first && cx_w && csc && out, "sf_ingest_video_yuv: null pointer");
-  SF_CHECK_ARG(((uintptr_t)out & 3) == 0, "sf_ingest_video_yuv: out must be 4-byte aligned");
-  SF_CHECK_ARG(W <= 1 << 20, "sf_ingest_video_yuv: W = %d is too wide for four staged source rows in LDS at taps_x = %d", W, taps_x);
-  // luma: as sf_ingest_video
-  const int RP = ((W + taps_x + 3) & ~3) + ING_ROW_SLACK;
-  const int TW = 4 * ((taps_x + 6) >> 2) + 3;
-  const int fixed = (TW * ING_OUT + ING_TY * taps_y) * 4;
-  int R = (ING_LDS_BYTES - fixed) / (RP + ING_OUT * 4);
-  R = R > ING_MAX_ROWS ? ING_MAX_ROWS : R;
-  if (R > 256 * ING_PF * 4 / RP) R = 256 * ING_PF * 4 / RP;
-  R &= ~3;
-  SF_CHECK_ARG(R >= 4, "sf_ingest_video_yuv: W = %d is too wide for four staged source rows in LDS at taps_x = %d", W, taps_x);
-  // chroma: four rows of U and four of V per chunk
-  const int RPc = ((W / 2 + taps_cx + 3) & ~3) + ING_ROW_SLACK;
-  const int TWc = 4 * ((taps_cx + 6) >> 2) + 3;
-  const int fixed_c = (TWc * ING_OUT + ING_TY * taps_cy) * 4;
-  const int lds_c = fixed_c + 8 * (RPc + ING_OUT * 4);
-  SF_CHECK_ARG(lds_c <= ING_LDS_BYTES && 2 * RPc <= 256 * ING_PF, "sf_ingest_video_yuv: W = %d is too wide for four staged rows of both chroma planes in LDS at taps_cx = %d",
-               W, taps_cx);
-  const int lds_y = fixed + R * (RP + ING_OUT * 4);
+  IngGeom gy, gc;                                                               // luma as sf_ingest_video; chroma: four rows of U and four of V per chunk
+  SF_CHECK_ARG(ing_geometry(W, taps_y, taps_x, 1, ING_MAX_ROWS, &gy), "sf_ingest_video_yuv: W = %d is too wide for four staged source rows in LDS at taps_x = %d", W,
+               taps_x);
+  SF_CHECK_ARG(ing_geometry(W / 2, taps_cy, taps_cx, 2, 4, &gc),
+               "sf_ingest_video_yuv: W = %d is too wide for four staged rows of both chroma planes in LDS at taps_cx = %d", W, taps_cx);
   IngCsc k;
   for (int i = 0; i < 9; ++i) k.m[i] = csc[i];
   for (int i = 0; i < 3; ++i) k.o[i] = csc[9 + i];
-  const dim3 grid(ING_OUT / ING_TY, (unsigned)T_out);
-  const int lds = lds_y > lds_c ? lds_y : lds_c;
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(ING_OUT / ING_TY, (unsigned)T_out), dim3(256), gy.lds > gc.lds ? gy.lds : gc.lds, (hipStream_t)stream, raw, stride_frame,
+                       stride_row, u_off, v_off, stride_crow, stride_ccol, n_src, H, W, frame_table, y_first, y_w, taps_y, x_first, x_w, taps_x, cy_first, cy_w,
+                       taps_cy, cx_first, cx_w, taps_cx, k, out, gy.R, gy.RP, gy.TW, gc.RP, gc.TW);
+  };
   if (v_off == u_off + 1 && stride_ccol == 2)                                   // NV12: one fetch of the interleaved rows serves both planes
-    hipLaunchKernelGGL(ingest_video_yuv_kernel<true>, grid, dim3(256), lds, (hipStream_t)stream, raw, stride_frame, stride_row, u_off, v_off, stride_crow,
-                       stride_ccol, n_src, H, W, frame_table, y_first, y_w, taps_y, x_first, x_w, taps_x, cy_first, cy_w, taps_cy, cx_first, cx_w, taps_cx, k, out, R,
-                       RP, TW, RPc, TWc);
+    launch(ingest_video_yuv_kernel<true>);
   else
-    hipLaunchKernelGGL(ingest_video_yuv_kernel<false>, grid, dim3(256), lds, (hipStream_t)stream, raw, stride_frame, stride_row, u_off, v_off, stride_crow,
-                       stride_ccol, n_src, H, W, frame_table, y_first, y_w, taps_y, x_first, x_w, taps_x, cy_first, cy_w, taps_cy, cx_first, cx_w, taps_cx, k, out, R,
-                       RP, TW, RPc, TWc);
+    launch(ingest_video_yuv_kernel<false>);
   SF_LAUNCH_CHECK();
   return 0;
 }

@@ -28,7 +28,7 @@ from typing import Tuple
 
 import torch
 
-CROP = 224
+CROP = 224                       # the model's input size; ops.INGEST_OUT and ops.INGEST_MAX_TAPS are these two
 MAX_TAPS = 35                    # sf_ingest_video's range: a short side up to 2160 at resize_side 256
 PIX_FMTS = ('rgb24', 'nv12', 'yuv420p')
 _KR_KB = {'bt601': (0.299, 0.114), 'bt709': (0.2126, 0.0722)}
@@ -116,6 +116,12 @@ def aa_bicubic_table(n_in: int, n_out: int, dtype=torch.float32):
     return first, w.to(dtype), taps
 
 
+def _crop_table(n_in: int, n_out: int, origin: int, crop: int, dev):
+    """aa_bicubic_table(n_in, n_out) cut to the output samples [origin, origin + crop), on the device: (first, weights, taps)."""
+    first, w, taps = aa_bicubic_table(n_in, n_out)
+    return first[origin:origin + crop].contiguous().to(dev), w[origin:origin + crop].contiguous().to(dev), taps
+
+
 def csc_matrix(colorspace: str = 'bt601', full_range: bool = False):
     """(M (3, 3) float64, offsets (3,) float64) with (R, G, B) = M @ ((Y, U, V) - offsets) on the 8-bit scale.  With Kr, Kb of the colour space (bt601: 0.299,
     0.114; bt709: 0.2126, 0.0722), Kg = 1 - Kr - Kb, luma gain gy and chroma gain gc (limited range: 255 / 219 and 255 / 224, offsets (16, 128, 128); full range:
@@ -177,13 +183,11 @@ class RecordingIngest:
         if self.Hr < crop or self.Wr < crop:
             raise ValueError(f'{self.H} x {self.W} resizes to {self.Hr} x {self.Wr}, below the {crop} crop')
         self.y0, self.x0 = int(round((self.Hr - crop) / 2.)), int(round((self.Wr - crop) / 2.))
-        yf, yw, ty = aa_bicubic_table(self.H, self.Hr)
-        xf, xw, tx = aa_bicubic_table(self.W, self.Wr)
-        if max(ty, tx) > MAX_TAPS:
-            raise ValueError(f'{self.H} x {self.W} -> {self.Hr} x {self.Wr} needs {ty} x {tx} filter taps, the kernel takes {MAX_TAPS} (a short side up to 2160 at 256)')
-        self.taps_y, self.taps_x = ty, tx
-        self.y_first, self.y_w = yf[self.y0:self.y0 + crop].contiguous().to(self.dev), yw[self.y0:self.y0 + crop].contiguous().to(self.dev)
-        self.x_first, self.x_w = xf[self.x0:self.x0 + crop].contiguous().to(self.dev), xw[self.x0:self.x0 + crop].contiguous().to(self.dev)
+        self.y_first, self.y_w, self.taps_y = _crop_table(self.H, self.Hr, self.y0, crop, self.dev)
+        self.x_first, self.x_w, self.taps_x = _crop_table(self.W, self.Wr, self.x0, crop, self.dev)
+        if max(self.taps_y, self.taps_x) > MAX_TAPS:
+            raise ValueError(f'{self.H} x {self.W} -> {self.Hr} x {self.Wr} needs {self.taps_y} x {self.taps_x} filter taps, the kernel takes {MAX_TAPS} '
+                             f'(a short side up to 2160 at 256)')
         self.pix_fmt = pix_fmt
         if pix_fmt != 'rgb24':
             if channels_last:
@@ -191,10 +195,8 @@ class RecordingIngest:
             if self.H % 2 or self.W % 2:
                 raise ValueError(f'{self.H} x {self.W} with pix_fmt = {pix_fmt!r}: 4:2:0 takes even H and W')
             # chroma: an (H / 2, W / 2) image resized to the same (Hr, Wr), sliced at the same crop origin; never more taps than luma
-            cyf, cyw, self.taps_cy = aa_bicubic_table(self.H // 2, self.Hr)
-            cxf, cxw, self.taps_cx = aa_bicubic_table(self.W // 2, self.Wr)
-            self.cy_first, self.cy_w = cyf[self.y0:self.y0 + crop].contiguous().to(self.dev), cyw[self.y0:self.y0 + crop].contiguous().to(self.dev)
-            self.cx_first, self.cx_w = cxf[self.x0:self.x0 + crop].contiguous().to(self.dev), cxw[self.x0:self.x0 + crop].contiguous().to(self.dev)
+            self.cy_first, self.cy_w, self.taps_cy = _crop_table(self.H // 2, self.Hr, self.y0, crop, self.dev)
+            self.cx_first, self.cx_w, self.taps_cx = _crop_table(self.W // 2, self.Wr, self.x0, crop, self.dev)
             self.colorspace, self.full_range = colorspace, bool(full_range)
             M, off = csc_matrix(colorspace, full_range)
             self.csc = torch.cat([M.reshape(9), off]).float()                        # host: the twelve floats travel as kernel arguments

@@ -14,6 +14,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
+from .ingest import CROP as INGEST_OUT, MAX_TAPS as INGEST_MAX_TAPS     # noqa: F401  the launchers' output size and tap range, stated once (ingest.py is host-only)
 
 SF_F32, SF_BF16, SF_F16, SF_U8 = 0, 1, 2, 3
 EPI_NONE, EPI_GELU = 0, 1
@@ -671,7 +672,29 @@ def track_decode(logits: torch.Tensor, lam: float):
     return cls_raw, conf_raw, cls_path, conf_path
 
 
-INGEST_OUT, INGEST_MAX_TAPS = 224, 35
+def _ingest_tables(frame_table: torch.Tensor, **tables):
+    """Checks frame_table (int32, contiguous) and the filter tables name=(first int32 (224,), weights fp32 (224, taps)), all contiguous; returns their launcher
+    arguments in order: (first, weights, taps) per table."""
+    firsts, weights = [f for f, _ in tables.values()], [w for _, w in tables.values()]
+    assert frame_table.dtype == torch.int32 and all(t.dtype == torch.int32 and t.shape == (INGEST_OUT,) for t in firsts)
+    assert all(t.dtype == torch.float32 and t.dim() == 2 and t.shape[0] == INGEST_OUT for t in weights)
+    assert all(t.is_contiguous() for t in (frame_table, *firsts, *weights))
+    return [a for k, (f, w) in tables.items() for a in (_dev(f, f'{k}_first'), _dev(w, f'{k}_w'), w.shape[1])]
+
+
+def _ingest_out(out: Optional[torch.Tensor], T_out: int, device) -> torch.Tensor:
+    if out is None:
+        out = torch.empty(T_out, 3, INGEST_OUT, INGEST_OUT, device=device, dtype=torch.uint8)
+    assert out.dtype == torch.uint8 and out.shape == (T_out, 3, INGEST_OUT, INGEST_OUT) and out.is_contiguous()
+    return out
+
+
+def _ingest_chunks(what: str, frame_table: torch.Tensor, out: torch.Tensor, launch):
+    """launch(frame_table pointer, out pointer, n) -> rc for every 65535 output frames: what one launch takes."""
+    T_out = frame_table.numel()
+    for t0 in range(0, max(T_out, 1), 65535):
+        _lib.check(launch(_dev(frame_table[t0:], 'frame_table'), _dev(out[t0:], 'out'), min(65535, T_out - t0)), what)
+    return out
 
 
 def ingest_video(raw: torch.Tensor, channels_last: bool, frame_table: torch.Tensor, y_first: torch.Tensor, y_w: torch.Tensor, x_first: torch.Tensor,
@@ -685,20 +708,9 @@ def ingest_video(raw: torch.Tensor, channels_last: bool, frame_table: torch.Tens
     (H, W), (sf, sc, sy, sx) = ((raw.shape[1], raw.shape[2]), (raw.stride(i) for i in (0, 3, 1, 2))) if channels_last else \
         ((raw.shape[2], raw.shape[3]), raw.stride())
     assert min(sf, sc, sy) >= 0 and sx >= 1, 'ingest_video: negative strides'
-    T_out = frame_table.numel()
-    assert frame_table.dtype == y_first.dtype == x_first.dtype == torch.int32 and y_w.dtype == x_w.dtype == torch.float32
-    assert y_first.shape == x_first.shape == (INGEST_OUT,) and y_w.dim() == x_w.dim() == 2 and y_w.shape[0] == x_w.shape[0] == INGEST_OUT
-    assert all(t.is_contiguous() for t in (frame_table, y_first, y_w, x_first, x_w))
-    if out is None:
-        out = torch.empty(T_out, 3, INGEST_OUT, INGEST_OUT, device=raw.device, dtype=torch.uint8)
-    assert out.dtype == torch.uint8 and out.shape == (T_out, 3, INGEST_OUT, INGEST_OUT) and out.is_contiguous()
-    for t0 in range(0, max(T_out, 1), 65535):                                    # the launcher takes 65535 output frames at a time
-        n = min(65535, T_out - t0)
-        rc = _lib.load().sf_ingest_video(_dev(raw, 'raw'), sf, sc, sy, sx, n_src, H, W, _dev(frame_table[t0:], 'frame_table'), _dev(y_first, 'y_first'),
-                                         _dev(y_w, 'y_w'), y_w.shape[1], _dev(x_first, 'x_first'), _dev(x_w, 'x_w'), x_w.shape[1], _dev(out[t0:], 'out'), n,
-                                         _stream())
-        _lib.check(rc, 'sf_ingest_video')
-    return out
+    src, tabs = _dev(raw, 'raw'), _ingest_tables(frame_table, y=(y_first, y_w), x=(x_first, x_w))
+    return _ingest_chunks('sf_ingest_video', frame_table, _ingest_out(out, frame_table.numel(), raw.device), lambda ft, o, n: _lib.load().sf_ingest_video(
+        src, sf, sc, sy, sx, n_src, H, W, ft, *tabs, o, n, _stream()))
 
 
 def ingest_video_yuv(raw: torch.Tensor, pix_fmt: str, frame_table: torch.Tensor, y_first: torch.Tensor, y_w: torch.Tensor, x_first: torch.Tensor, x_w: torch.Tensor,
@@ -721,22 +733,9 @@ def ingest_video_yuv(raw: torch.Tensor, pix_fmt: str, frame_table: torch.Tensor,
     csc = [float(v) for v in (csc.reshape(-1).tolist() if isinstance(csc, torch.Tensor) else csc)]
     assert len(csc) == 12, 'ingest_video_yuv: csc is 9 matrix entries and 3 offsets'
     csc_c = (C.c_float * 12)(*csc)
-    T_out = frame_table.numel()
-    firsts, weights = (y_first, x_first, cy_first, cx_first), (y_w, x_w, cy_w, cx_w)
-    assert frame_table.dtype == torch.int32 and all(t.dtype == torch.int32 and t.shape == (INGEST_OUT,) for t in firsts)
-    assert all(t.dtype == torch.float32 and t.dim() == 2 and t.shape[0] == INGEST_OUT for t in weights)
-    assert all(t.is_contiguous() for t in (frame_table, *firsts, *weights))
-    if out is None:
-        out = torch.empty(T_out, 3, INGEST_OUT, INGEST_OUT, device=raw.device, dtype=torch.uint8)
-    assert out.dtype == torch.uint8 and out.shape == (T_out, 3, INGEST_OUT, INGEST_OUT) and out.is_contiguous()
-    for t0 in range(0, max(T_out, 1), 65535):                                    # the launcher takes 65535 output frames at a time
-        n = min(65535, T_out - t0)
-        rc = _lib.load().sf_ingest_video_yuv(_dev(raw, 'raw'), sf, sy, u_off, v_off, csy, csx, n_src, H, W, _dev(frame_table[t0:], 'frame_table'),
-                                             _dev(y_first, 'y_first'), _dev(y_w, 'y_w'), y_w.shape[1], _dev(x_first, 'x_first'), _dev(x_w, 'x_w'), x_w.shape[1],
-                                             _dev(cy_first, 'cy_first'), _dev(cy_w, 'cy_w'), cy_w.shape[1], _dev(cx_first, 'cx_first'), _dev(cx_w, 'cx_w'),
-                                             cx_w.shape[1], C.addressof(csc_c), _dev(out[t0:], 'out'), n, _stream())
-        _lib.check(rc, 'sf_ingest_video_yuv')
-    return out
+    src, tabs = _dev(raw, 'raw'), _ingest_tables(frame_table, y=(y_first, y_w), x=(x_first, x_w), cy=(cy_first, cy_w), cx=(cx_first, cx_w))
+    return _ingest_chunks('sf_ingest_video_yuv', frame_table, _ingest_out(out, frame_table.numel(), raw.device), lambda ft, o, n: _lib.load().sf_ingest_video_yuv(
+        src, sf, sy, u_off, v_off, csy, csx, n_src, H, W, ft, *tabs, C.addressof(csc_c), o, n, _stream()))
 
 
 SF_I16 = 4

@@ -7,10 +7,9 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from ingest_oracle import resize64  # noqa: E402
+from ingest_oracle import TABLE, check_pixels, resize64  # noqa: E402,F401  (the frame pick and the pixel bar are shared with test_ingest_gpu.py)
 
 CROP = 224
-TABLE = [0, 0, 2, 4, 4]                                                          # a repeat and a skip
 # (H, W) -> (colorspace, full_range, luma taps (y, x), chroma taps (y, x))
 CASES = {(270, 480): ('bt601', False, (7, 7), (5, 5)), (360, 202): ('bt709', True, (5, 5), (5, 5)), (144, 176): ('bt601', False, (5, 5), (5, 5)),
          (540, 960): ('bt709', True, (11, 11), (7, 7)), (302, 518): ('bt601', False, (7, 7), (5, 5)), (1080, 608): ('bt709', True, (11, 11), (7, 7))}
@@ -72,12 +71,3 @@ def apply_tables32(plane: torch.Tensor, yf, yw, xf, xw) -> torch.Tensor:
         out = out + yw[:, i, None] * h[:, yf.long() + i]
     return out
 
-
-def check_pixels(got: torch.Tensor, ref: torch.Tensor, what: str):
-    """The standing bar of test_ingest_gpu.py: every pixel within 1 level of the float64 oracle, differing pixels at most 1e-3 of all."""
-    assert got.dtype == torch.uint8 and got.shape == ref.shape, (got.dtype, got.shape)
-    d = (got.cpu().int() - ref.int()).abs()
-    share = (d != 0).float().mean().item()
-    print(f'{what}: max |level difference| {int(d.max())}, share of differing pixels {share:.2e}')
-    assert int(d.max()) <= 1, int(d.max())
-    assert share <= 1e-3, share

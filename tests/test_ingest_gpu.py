@@ -1,6 +1,8 @@
 """GPU: the ingest stage.  sf_ingest_video against torch's own CPU F.interpolate on float64, sf_resample_wave against the float64 restatement of
-torchaudio's resampler (tests/ingest_oracle.py), and OffsetTracker.track_raw end to end on the identity case (bit-equal to track) and on a 50 fps / 48 kHz case."""
+torchaudio's resampler (tests/ingest_oracle.py), the output bytes of both video launchers against the digests recorded in tests/golden/ingest_digests.json, and
+OffsetTracker.track_raw end to end on the identity case (bit-equal to track) and on a 50 fps / 48 kHz case."""
 import functools
+import json
 import os
 import sys
 
@@ -8,11 +10,13 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden'))
 import ingest_oracle as R  # noqa: E402
+import make_ingest_digests as D  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-TABLE = [0, 0, 2, 4, 4]                                                          # a repeat and a skip
+TABLE = R.TABLE
 VIDEO_SIZES = [(270, 480), (360, 202), (144, 176), (540, 960), (301, 517), (1080, 608)]
 
 
@@ -20,23 +24,11 @@ VIDEO_SIZES = [(270, 480), (360, 202), (144, 176), (540, 960), (301, 517), (1080
 def _video_case(H, W, side=256):
     """(raw planar uint8 (5, 3, H, W), oracle uint8 (5, 3, 224, 224) of the 5 SOURCE frames, crop origin) - computed once per size, read-only."""
     from synchformer_amd.ingest import resized_dims
-    g = torch.Generator().manual_seed(H * 10000 + W + side)
-    raw = torch.randint(0, 256, (5, 3, H, W), generator=g, dtype=torch.uint8)
+    raw = R.random_frames(5, H, W, H * 10000 + W + side)
     Hr, Wr = resized_dims(H, W, side)
     y0, x0 = int(round((Hr - 224) / 2.)), int(round((Wr - 224) / 2.))
     ref = R.resize64(raw, (Hr, Wr))[..., y0:y0 + 224, x0:x0 + 224].round().clamp(0, 255).to(torch.uint8)
     return raw, ref
-
-
-def _check_pixels(got: torch.Tensor, ref: torch.Tensor, what: str):
-    """Every pixel within 1 level of the float64 oracle; pixels that differ at all are at most 1e-3 of all pixels (a pixel differs when fp32 and float64 land on
-    opposite sides of a rounding boundary; the fp32 evaluation of the same tables on the CPU does so on <= 2e-5 of the pixels at these sizes)."""
-    assert got.dtype == torch.uint8 and got.shape == ref.shape, (got.dtype, got.shape)
-    d = (got.cpu().int() - ref.int()).abs()
-    share = (d != 0).float().mean().item()
-    print(f'{what}: max |level difference| {int(d.max())}, share of differing pixels {share:.2e}')
-    assert int(d.max()) <= 1, int(d.max())
-    assert share <= 1e-3, share
 
 
 @pytest.mark.parametrize('channels_last', [False, True])
@@ -52,7 +44,7 @@ def test_ingest_video_matches_interpolate(gpu, H, W, channels_last):
     for where in (src.to(gpu), src):                                             # on the device, and uploaded from the host (only frames [0, 5) -> all of them)
         got = ing.frames(where, 0, 5)
         torch.cuda.synchronize()
-        _check_pixels(got, ref[TABLE], f'{H} x {W} taps {ing.taps_y} x {ing.taps_x} {"channels-last" if channels_last else "planar"}')
+        R.check_pixels(got, ref[TABLE], f'{H} x {W} taps {ing.taps_y} x {ing.taps_x} {"channels-last" if channels_last else "planar"}')
     # a slice of the output frames: [2, 5) reads source frames 2 .. 4 only
     part = ing.frames(src, 2, 5)
     assert torch.equal(part, got[2:5])
@@ -67,8 +59,7 @@ def test_ingest_video_many_taps(gpu, H, W, Wr, taps_y, taps_x, rows):
     staged row plus one row of the horizontal pass, at most 8 and at most 20 dwords per lane of staging registers, rounded down to a multiple of 4."""
     from synchformer_amd import ops
     from synchformer_amd.ingest import aa_bicubic_table
-    g = torch.Generator().manual_seed(H + W)
-    raw = torch.randint(0, 256, (3, 3, H, W), generator=g, dtype=torch.uint8)
+    raw = R.random_frames(3, H, W, H + W)
     x0 = (Wr - 224) // 2
     ref = R.resize64(raw, (256, Wr))[..., 16:240, x0:x0 + 224].round().clamp(0, 255).to(torch.uint8)
     yf, yw, ty = aa_bicubic_table(H, 256)
@@ -82,7 +73,7 @@ def test_ingest_video_many_taps(gpu, H, W, Wr, taps_y, taps_x, rows):
     pick = torch.tensor([2, 0, 1], dtype=torch.int32, device=gpu)
     got = ops.ingest_video(raw.to(gpu), False, pick, *tabs)
     torch.cuda.synchronize()
-    _check_pixels(got, ref[[2, 0, 1]], f'{H} x {W} taps {ty} x {tx}')
+    R.check_pixels(got, ref[[2, 0, 1]], f'{H} x {W} taps {ty} x {tx}')
     with pytest.raises(RuntimeError, match='out of range'):
         ops.ingest_video(raw.to(gpu), False, pick, tabs[0], torch.zeros(224, 36, device=gpu), tabs[2], tabs[3])
 
@@ -100,7 +91,7 @@ def test_ingest_video_strided_rows(gpu):
     ing._tables = {5: torch.tensor(TABLE, dtype=torch.int32)}
     got = ing.frames(view, 0, 5)
     torch.cuda.synchronize()
-    _check_pixels(got, ref[TABLE], 'strided rows')
+    R.check_pixels(got, ref[TABLE], 'strided rows')
 
 
 @pytest.mark.parametrize('H, W', [(270, 480), (360, 202)])
@@ -113,7 +104,7 @@ def test_ingest_video_border(gpu, H, W):
     ing._tables = {5: torch.tensor(TABLE, dtype=torch.int32)}
     got = ing.frames(raw.to(gpu), 0, 5)
     torch.cuda.synchronize()
-    _check_pixels(got, ref[TABLE], f'{H} x {W} resize_side 224')
+    R.check_pixels(got, ref[TABLE], f'{H} x {W} resize_side 224')
 
 
 @pytest.mark.parametrize('channels_last', [False, True])
@@ -125,6 +116,22 @@ def test_ingest_video_identity_is_the_centre_crop(gpu, channels_last):
     ing = RecordingIngest(gpu, 25, (256, 256), 16000, channels_last=channels_last)
     got = ing.frames(src.to(gpu), 0, 3)
     assert torch.equal(got.cpu(), raw[:, :, 16:240, 16:240])
+
+
+with open(D.OUT) as _f:
+    DIGESTS = json.load(_f)['cases']
+
+
+@pytest.mark.parametrize('name', list(D.CASES))
+def test_ingest_outputs_are_pinned(gpu, name):
+    """The pixel tests above allow one level against float64 and would pass a changed summation order; this one holds the output BYTES of the smallest inputs
+    that reach every branch of the resize pipeline (tests/golden/make_ingest_digests.py lists them) to the SHA-256 recorded once, on the commit the file names.
+    The input's own digest is checked first: a mismatch there is a changed random stream, not a changed kernel."""
+    assert set(DIGESTS) == set(D.CASES)
+    src, out = D.CASES[name](gpu)
+    torch.cuda.synchronize()
+    assert D.sha256(src) == DIGESTS[name]['input'], f'{name}: the generated INPUT differs from the recorded one'
+    assert D.sha256(out) == DIGESTS[name]['output'], f'{name}: output bytes differ from the recording'
 
 
 # ---- audio ----------------------------------------------------------------------------------------------------------------------------------------------------
