@@ -29,7 +29,7 @@ extern "C" {
 enum { SF_F32 = 0, SF_BF16 = 1, SF_F16 = 2, SF_U8 = 3, SF_I16 = 4 };   /* element types (SF_I16: PCM input of sf_resample_wave only) */
 enum { SF_EPI_NONE = 0, SF_EPI_GELU = 1 };                  /* GEMM epilogue activation */
 
-#define SF_ABI_VERSION 16
+#define SF_ABI_VERSION 17
 int sf_abi_version(void);
 const char* sf_last_error(void);
 /* "gfx950" + build flags; lets the host assert it loaded the library it built */
@@ -545,7 +545,8 @@ int sf_resample_wave(const void* x, int dtype, int ch, int64_t ld, int64_t len, 
  *   stride_crow = W / 2, stride_ccol = 1).  For output frame j < T_out (source frame frame_table[j], clamped into [0, n_src)) and r, x < 224:
  *       Yr = sum_i y_w[r, i]  * sum_k x_w[x, k]  * Y[y_first[r] + i,  x_first[x] + k]          luma tables: those of sf_ingest_video (H -> Hr, W -> Wr)
  *       Ur = sum_i cy_w[r, i] * sum_k cx_w[x, k] * U[cy_first[r] + i, cx_first[x] + k]         chroma tables: H/2 -> Hr, W/2 -> Wr, sliced at the SAME crop origin;
- *       Vr = the same on V                                                                     chroma is an (H/2, W/2) image under align_corners=False (centre siting)
+ *       Vr = the same on V                                                                     chroma is an (H/2, W/2) image under align_corners=False (centre siting;
+ *                                                                                              left / top-left siting: tables built with shift=0.25, see below)
  *       out[c, r, x] = clamp(round_half_even(M[c][0] (Yr - o[0]) + M[c][1] (Ur - o[1]) + M[c][2] (Vr - o[2])), 0, 255)
  *   fp32, horizontal pass first, taps ascending, nothing rounded between the resize and the conversion; uint8 planar (T_out, 3, 224, 224), 4-byte aligned.
  *   csc: 12 floats in HOST memory, M row-major (rows R, G, B; columns Y, U, V) then o; they travel as kernel arguments (synchformer_amd.ingest.csc_matrix).
@@ -556,6 +557,22 @@ int sf_ingest_video_yuv(const uint8_t* raw, int64_t stride_frame, int64_t stride
                         int n_src, int H, int W, const int32_t* frame_table, const int32_t* y_first, const float* y_w, int taps_y, const int32_t* x_first,
                         const float* x_w, int taps_x, const int32_t* cy_first, const float* cy_w, int taps_cy, const int32_t* cx_first, const float* cx_w,
                         int taps_cx, const float* csc, uint8_t* out, int T_out, void* stream);
+
+/* sf_ingest_video_yuv for 10-bit YUV 4:2:0 frames in 16-bit little-endian samples (P010 surfaces of hardware decoders, yuv420p10le arrays of libav / PyAV).
+ * raw is 2-byte aligned; stride_frame, stride_row, u_off, v_off, stride_crow and stride_ccol are in BYTES and even; the sample value is
+ *       v = (word >> shift) & 1023                  (P010: shift 6, the sample sits in the high ten bits; yuv420p10le: shift 0), so stray bits never leave the range;
+ *   (P010 at a row pitch of P bytes: u_off = P H, v_off = u_off + 2, stride_crow = P, stride_ccol = 4;  yuv420p10le with contiguous rows: u_off = 2 H W,
+ *   v_off = 2 H W 5 / 4, stride_crow = W, stride_ccol = 2).  Everything else is sf_ingest_video_yuv's definition on the 10-bit scale: the same tables, the same
+ *   order of operations (fp32, horizontal pass first, taps ascending, fused multiply-adds, nothing rounded before the matrix), csc = M and o on the 10-bit scale
+ *   (synchformer_amd.ingest.csc_matrix(bit_depth=10): limited range M = M8 / 4, o = (64, 512, 512)), output uint8 planar (T_out, 3, 224, 224).  Frames that hold
+ *   4 v8 give, bit for bit, what sf_ingest_video_yuv gives on v8.  Chroma siting is in the chroma tables (aa_bicubic_table(shift=0.25)), for this entry and for the
+ *   8-bit one alike.  When v_off == u_off + 2 and stride_ccol == 4 the interleaved chroma rows are fetched once (16 bytes per four columns) and split in registers.
+ *   Serves every width sf_ingest_video_yuv serves (four 16-bit rows of a 3840-wide plane at 35 taps take ~68 KiB of LDS: the kernel raises its dynamic-LDS limit).
+ *   -1 on: everything sf_ingest_video_yuv refuses, an odd stride or offset, raw not 2-byte aligned, stride_ccol < 2, shift outside 0 .. 6.  One launch. */
+int sf_ingest_video_yuv16(const uint16_t* raw, int64_t stride_frame, int64_t stride_row, int64_t u_off, int64_t v_off, int64_t stride_crow, int64_t stride_ccol,
+                          int shift, int n_src, int H, int W, const int32_t* frame_table, const int32_t* y_first, const float* y_w, int taps_y,
+                          const int32_t* x_first, const float* x_w, int taps_x, const int32_t* cy_first, const float* cy_w, int taps_cy, const int32_t* cx_first,
+                          const float* cx_w, int taps_cx, const float* csc, uint8_t* out, int T_out, void* stream);
 
 /* Backward of sf_attention for tiny groups (n_tok <= 8, head_dim 64: Motionformer time attention, vit_helper.py:343-344): same
  * addressing as the forward; dq | dk | dv rows of the group's tokens are written (=), the CLS key's dk | dv of every (seq, group) goes to

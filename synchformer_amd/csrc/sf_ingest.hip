@@ -4,9 +4,10 @@
 //                      two filter tables arrive already sliced to the crop, so only the 224 x 224 outputs are computed: a horizontal pass over the source rows a
 //                      tile of output rows needs (fp32, kept in LDS), then the vertical pass over those rows.
 //   sf_ingest_video_yuv: the same for 8-bit YUV 4:2:0 frames (NV12, I420): the three planes are resized, the colour matrix runs on the 224 x 224 result.
+//   sf_ingest_video_yuv16: the same for 10-bit YUV 4:2:0 frames in 16-bit samples (P010, yuv420p10le): the sample is (raw >> shift) & 1023.
 //   sf_resample_wave:  zero-delay polyphase windowed-sinc resampler (the bank of ingest.resample_kernel), channels averaged on read, zero padding by bounds checks.
-// Both video kernels run ONE resize pipeline, ing_plane_pass: ingest_video_kernel once per workgroup (one channel), ingest_video_yuv_kernel twice (luma, then U and
-// V together); the launchers size its LDS with one formula, ing_geometry.
+// All video kernels run ONE resize pipeline, ing_plane_pass, over 1-byte or 2-byte samples (BS): ingest_video_kernel once per workgroup (one channel), the YUV
+// kernels twice (luma, then U and V together); the launchers size its LDS with one formula, ing_geometry.
 // All kernels bound every address they form by the sizes the launcher was given: a table with entries outside the source only changes the picture, never the
 // addresses (frame index, first-tap row / column and every tap are clamped or skipped).
 #include <initializer_list>
@@ -14,13 +15,18 @@
 #include "sf_common.h"
 #include "../../include/synchformer_hip.h"
 
+typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
+typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+
 #define ING_OUT 224            // output rows = columns (the model's input size)
 #define ING_TY 8               // output rows per workgroup
 #define ING_MAX_TAPS 35        // 2 * ceil(2 * scale) + 1 at scale <= 8.5: a short side up to 2160 at resize_side 256
 #define ING_MAX_ROWS 8         // source rows per chunk (4 when the source is wide: the launcher sizes it so that everything fits 64 KiB of LDS)
 #define ING_LDS_BYTES 65536
 #define ING_PF 20              // staged dwords per lane per chunk at most: NP * R * RP / 4 <= 5120
-#define ING_ROW_SLACK 8        // bytes behind a staged row that the horizontal pass may read (always against a zero weight)
+#define ING_ROW_SLACK 8        // samples behind a staged row that the horizontal pass may read (always against a zero weight)
+#define ING_LDS_BYTES16 98304  // the same for 2-byte samples: four staged rows of a 3840-wide luma plane at 35 taps take ~68 KiB (gfx950: 160 KiB per workgroup)
+#define ING_PF16 40            // staged dwords per lane per chunk at most for 2-byte samples: NP * R * RP / 2 <= 10240, the row widths the 1-byte kernels serve
 
 // The resize of output rows [r0, r0 + 8) of NP planes of one frame that share their geometry and tables (NP = 1: one RGB channel, or luma; NP = 2: U and V), by the
 // 256 threads of a workgroup.  Element (y, x) of plane p is s[p][y * sy + x * sx].  Adds into a0[p] / a1[p]: this lane's 4 columns 4 q .. 4 q + 3 of output rows
@@ -38,11 +44,20 @@
 //  (2) horizontal pass, lane = output column, four source rows at a time: the taps [off, off + taps_x) are read as the aligned dwords that cover them, and byte
 //      k of dword d meets weight row 4 d + k + 3 - (off & 3) - tap j = 4 d + k - (off & 3), or a zero row outside [0, taps_x): sums run in ascending j;
 //  (3) vertical pass, lane = four output columns of output rows rg and rg + 4 of the tile: acc += yw[row][y - first] * mid[y], source rows y ascending.
-template <int NP, bool INTER>
+// BS = 2: the samples are 16-bit words that hold 10 bits, v = (word >> shift) & 1023; sy, sx and the planes' addresses stay in BYTES (all even).  What changes:
+//   rows [NP R][RP] uint16: two LDS dwords per staged item (one 8-byte store), at most ING_PF16 staged dwords per lane; the staged row starts at xlo rounded down
+//      to a multiple of 4 columns, so that rows of an aligned surface are fetched with wide loads at any crop origin: 8 bytes per plane (else two dwords, else
+//      2-byte loads); INTER (s1 == s0 + 2, sx == 4: P010) takes the 16 bytes U V U V U V U V of four chroma columns as one 16-byte load (else four dwords);
+//   xw: tap j in row j + 1, TW = 2 nd + 1; the horizontal pass reads the nd = (taps_x + 2) / 2 aligned dwords that cover the taps, two samples per dword, half k of
+//      dword d against weight row 2 d + k + 1 - (off & 1).  Zero rows only add exact zeros, so the sums - taps ascending, fmaf - are those of BS = 1 term by term.
+template <int NP, bool INTER, int BS>
 __device__ __forceinline__ void ing_plane_pass(unsigned char* lds, const uint8_t* __restrict__ s0, const uint8_t* __restrict__ s1, int64_t sy, int64_t sx, int H, int W,
                                                const int32_t* __restrict__ y_first, const float* __restrict__ y_w, int taps_y,
-                                               const int32_t* __restrict__ x_first, const float* __restrict__ x_w, int taps_x, int R, int RP, int TW, int r0,
+                                               const int32_t* __restrict__ x_first, const float* __restrict__ x_w, int taps_x, int R, int RP, int TW, int r0, int shift,
                                                float (&a0)[NP][4], float (&a1)[NP][4]) {
+  static_assert(BS == 1 || BS == 2, "samples of one or two bytes");
+  constexpr int PAD = BS == 1 ? 3 : 1;                                          // zero rows in front of the transposed table: samples per dword - 1
+  constexpr int PF = BS == 1 ? ING_PF : ING_PF16;
   float* xw = (float*)lds;
   float* yw = xw + TW * ING_OUT;
   float* mid = yw + ING_TY * taps_y;
@@ -51,16 +66,17 @@ __device__ __forceinline__ void ing_plane_pass(unsigned char* lds, const uint8_t
 
   for (int i = tid; i < TW * ING_OUT; i += 256) {
     const int row = i / ING_OUT;
-    if (row < 3 || row >= taps_x + 3) xw[i] = 0.f;
+    if (row < PAD || row >= taps_x + PAD) xw[i] = 0.f;
   }
   for (int i = tid; i < taps_x * ING_OUT; i += 256) {
     const int x = i / taps_x, j = i - x * taps_x;                               // coalesced read of the (224, taps_x) table
-    xw[(j + 3) * ING_OUT + x] = x_w[i];
+    xw[(j + PAD) * ING_OUT + x] = x_w[i];
   }
   for (int i = tid; i < ING_TY * taps_y; i += 256) yw[i] = y_w[(int64_t)r0 * taps_y + i];
 
   int xlo = x_first[0];
   xlo = xlo < 0 ? 0 : (xlo > W ? W : xlo);
+  if (BS == 2) xlo &= ~3;
   int ys = y_first[r0], ye = y_first[r0 + ING_TY - 1] + taps_y;
   ys = ys < 0 ? 0 : ys;
   ye = ye > H ? H : ye;                                                        // rows past the picture carry the tables' zero padding: never read
@@ -70,10 +86,11 @@ __device__ __forceinline__ void ing_plane_pass(unsigned char* lds, const uint8_t
   const bool vert = tid < 224;
   int yf0 = 0, yf1 = 0;
   if (vert) { yf0 = y_first[r0 + rg]; yf1 = y_first[r0 + rg + 4]; }
-  const int Q4 = RP >> 2;                                                       // dwords per staged row
-  const int nd = (taps_x + 6) >> 2;                                             // aligned dwords that cover taps_x bytes at any byte offset (TW = 4 nd + 3)
+  const int Q4 = RP >> 2;                                                       // staging items (4 columns) per staged row: BS dwords each
+  const int QD = Q4 * BS;                                                       // dwords per staged row
+  const int nd = BS == 1 ? (taps_x + 6) >> 2 : (taps_x + 2) >> 1;               // aligned dwords that cover taps_x samples at any offset (TW = 4 nd + 3, 2 nd + 1)
   const int valid_x = W - xlo;
-  const int n_stage = R * Q4;                                                   // staging items: 4 columns of one row of every plane; NP n_stage <= 256 * ING_PF
+  const int n_stage = R * Q4;                                                   // staging items: 4 columns of one row of every plane; NP BS n_stage <= 256 * PF
 
   // horizontal pass ownership: items (group of 4 source rows, output column) tid and tid + 256 of (NP R / 4) * 224 <= 448; their table entries are read here, so
   // that the chunk loop issues no global load but the prefetch
@@ -88,21 +105,21 @@ __device__ __forceinline__ void ing_plane_pass(unsigned char* lds, const uint8_t
     const int g = it / ING_OUT, x = it - g * ING_OUT;
     int off = hon[k] ? x_first[x] - xlo : 0;
     off = off < 0 ? 0 : (off > RP - ING_ROW_SLACK - taps_x ? RP - ING_ROW_SLACK - taps_x : off);
-    hp[k] = rows + (g * 4) * Q4 + (off >> 2);
-    hw[k] = xw + (3 - (off & 3)) * ING_OUT + x;
+    hp[k] = rows + (g * 4) * QD + (BS == 1 ? off >> 2 : off >> 1);
+    hw[k] = xw + (PAD - (off & PAD)) * ING_OUT + x;
     hm[k] = mid + (g * 4) * ING_OUT + x;
   }
 
   // staging of the R source rows of each plane from yc on, through registers: fetch() issues the loads (rows at or beyond ye and columns at or beyond W are
   // zero), commit() writes them to LDS a phase later, so the loads of chunk k + 1 travel under the horizontal pass of chunk k
-  uint32_t pf[ING_PF];
+  uint32_t pf[PF];
   auto fetch = [&](int yc) {
 #pragma unroll
-    for (int k = 0; k < ING_PF / NP; ++k) {
+    for (int k = 0; k < PF / (NP * BS); ++k) {
       const int it = tid + 256 * k;
-      uint32_t v[NP];
+      uint32_t v[NP * BS];
 #pragma unroll
-      for (int p = 0; p < NP; ++p) v[p] = 0;
+      for (int p = 0; p < NP * BS; ++p) v[p] = 0;
       if (it < n_stage) {
         const int r = it / Q4, c = (it - r * Q4) * 4;
         const int y = yc + r;
@@ -110,38 +127,82 @@ __device__ __forceinline__ void ing_plane_pass(unsigned char* lds, const uint8_t
           const int64_t o = (int64_t)y * sy + (int64_t)(xlo + c) * sx;
           const bool full = c + 3 < valid_x;
           const uint8_t* gi = s0 + o;
-          if (NP == 2 && INTER && full && ((uintptr_t)gi & 3) == 0) {
-            const uint32_t a = ((const uint32_t*)gi)[0], b = ((const uint32_t*)gi)[1];
-            v[0] = (a & 0xffu) | ((a >> 8) & 0xff00u) | ((b & 0xffu) << 16) | ((b << 8) & 0xff000000u);
-            v[NP - 1] = ((a >> 8) & 0xffu) | ((a >> 16) & 0xff00u) | ((b << 8) & 0xff0000u) | (b & 0xff000000u);
-          } else {
+          if constexpr (BS == 1) {
+            if (NP == 2 && INTER && full && ((uintptr_t)gi & 3) == 0) {
+              const uint32_t a = ((const uint32_t*)gi)[0], b = ((const uint32_t*)gi)[1];
+              v[0] = (a & 0xffu) | ((a >> 8) & 0xff00u) | ((b & 0xffu) << 16) | ((b << 8) & 0xff000000u);
+              v[NP - 1] = ((a >> 8) & 0xffu) | ((a >> 16) & 0xff00u) | ((b << 8) & 0xff0000u) | (b & 0xff000000u);
+            } else {
 #pragma unroll
-            for (int p = 0; p < NP; ++p) {
-              const uint8_t* g = (p ? s1 : s0) + o;
-              if (!INTER && sx == 1 && full && ((uintptr_t)g & 3) == 0) {
-                v[p] = *(const uint32_t*)g;
+              for (int p = 0; p < NP; ++p) {
+                const uint8_t* g = (p ? s1 : s0) + o;
+                if (!INTER && sx == 1 && full && ((uintptr_t)g & 3) == 0) {
+                  v[p] = *(const uint32_t*)g;
+                } else {
+                  uint32_t u = g[0];
+                  if (c + 1 < valid_x) u |= (uint32_t)g[sx] << 8;
+                  if (c + 2 < valid_x) u |= (uint32_t)g[2 * sx] << 16;
+                  if (full) u |= (uint32_t)g[3 * sx] << 24;
+                  v[p] = u;
+                }
+              }
+            }
+          } else {
+            if (NP == 2 && INTER && full && ((uintptr_t)gi & 3) == 0) {         // dword i = U | V << 16 of column c + i
+              uint32_t d[4];
+              if (((uintptr_t)gi & 15) == 0) {
+                const u32x4 w = *(const u32x4*)gi;
+                d[0] = w.x; d[1] = w.y; d[2] = w.z; d[3] = w.w;
               } else {
-                uint32_t u = g[0];
-                if (c + 1 < valid_x) u |= (uint32_t)g[sx] << 8;
-                if (c + 2 < valid_x) u |= (uint32_t)g[2 * sx] << 16;
-                if (full) u |= (uint32_t)g[3 * sx] << 24;
-                v[p] = u;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) d[i] = ((const uint32_t*)gi)[i];
+              }
+              v[0] = (d[0] & 0xffffu) | (d[1] << 16);
+              v[1] = (d[2] & 0xffffu) | (d[3] << 16);
+              v[2 * (NP - 1)] = (d[0] >> 16) | (d[1] & 0xffff0000u);
+              v[2 * (NP - 1) + 1] = (d[2] >> 16) | (d[3] & 0xffff0000u);
+            } else {
+#pragma unroll
+              for (int p = 0; p < NP; ++p) {
+                const uint8_t* g = (p ? s1 : s0) + o;
+                if (!INTER && sx == 2 && full && ((uintptr_t)g & 3) == 0) {
+                  if (((uintptr_t)g & 7) == 0) {
+                    const u32x2 w = *(const u32x2*)g;
+                    v[2 * p] = w.x; v[2 * p + 1] = w.y;
+                  } else {
+                    v[2 * p] = ((const uint32_t*)g)[0]; v[2 * p + 1] = ((const uint32_t*)g)[1];
+                  }
+                } else {
+                  uint32_t u = *(const uint16_t*)g, w = 0;
+                  if (c + 1 < valid_x) u |= (uint32_t)*(const uint16_t*)(g + sx) << 16;
+                  if (c + 2 < valid_x) w = *(const uint16_t*)(g + 2 * sx);
+                  if (full) w |= (uint32_t)*(const uint16_t*)(g + 3 * sx) << 16;
+                  v[2 * p] = u; v[2 * p + 1] = w;
+                }
               }
             }
           }
         }
       }
 #pragma unroll
-      for (int p = 0; p < NP; ++p) pf[k * NP + p] = v[p];
+      for (int p = 0; p < NP * BS; ++p) pf[k * NP * BS + p] = v[p];
     }
   };
   auto commit = [&]() {
 #pragma unroll
-    for (int k = 0; k < ING_PF / NP; ++k) {
+    for (int k = 0; k < PF / (NP * BS); ++k) {
       const int it = tid + 256 * k;
       if (it < n_stage) {
 #pragma unroll
-        for (int p = 0; p < NP; ++p) rows[p * n_stage + it] = pf[k * NP + p];
+        for (int p = 0; p < NP; ++p) {
+          if constexpr (BS == 1) {
+            rows[p * n_stage + it] = pf[k * NP + p];
+          } else {
+            u32x2 w;
+            w.x = pf[(k * NP + p) * 2]; w.y = pf[(k * NP + p) * 2 + 1];
+            *(u32x2*)(rows + 2 * (p * n_stage + it)) = w;
+          }
+        }
       }
     }
   };
@@ -162,14 +223,26 @@ __device__ __forceinline__ void ing_plane_pass(unsigned char* lds, const uint8_t
         const float* wp = hw[k];
         float h0 = 0.f, h1 = 0.f, h2 = 0.f, h3 = 0.f;
         for (int d = 0; d < nd; ++d) {
-          const uint32_t v0 = p0[d], v1 = p0[Q4 + d], v2 = p0[2 * Q4 + d], v3 = p0[3 * Q4 + d];
+          const uint32_t v0 = p0[d], v1 = p0[QD + d], v2 = p0[2 * QD + d], v3 = p0[3 * QD + d];
+          if constexpr (BS == 1) {
 #pragma unroll
-          for (int b = 0; b < 4; ++b) {
-            const float w = wp[(4 * d + b) * ING_OUT];
-            h0 = fmaf(w, (float)((v0 >> (8 * b)) & 255u), h0);
-            h1 = fmaf(w, (float)((v1 >> (8 * b)) & 255u), h1);
-            h2 = fmaf(w, (float)((v2 >> (8 * b)) & 255u), h2);
-            h3 = fmaf(w, (float)((v3 >> (8 * b)) & 255u), h3);
+            for (int b = 0; b < 4; ++b) {
+              const float w = wp[(4 * d + b) * ING_OUT];
+              h0 = fmaf(w, (float)((v0 >> (8 * b)) & 255u), h0);
+              h1 = fmaf(w, (float)((v1 >> (8 * b)) & 255u), h1);
+              h2 = fmaf(w, (float)((v2 >> (8 * b)) & 255u), h2);
+              h3 = fmaf(w, (float)((v3 >> (8 * b)) & 255u), h3);
+            }
+          } else {
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+              const float w = wp[(2 * d + b) * ING_OUT];
+              const int sh = 16 * b + shift;                                   // shift <= 6: the ten bits of half b
+              h0 = fmaf(w, (float)((v0 >> sh) & 1023u), h0);
+              h1 = fmaf(w, (float)((v1 >> sh) & 1023u), h1);
+              h2 = fmaf(w, (float)((v2 >> sh) & 1023u), h2);
+              h3 = fmaf(w, (float)((v3 >> sh) & 1023u), h3);
+            }
           }
         }
         float* m = hm[k];
@@ -226,7 +299,7 @@ __global__ __launch_bounds__(256) void ingest_video_kernel(const uint8_t* __rest
   const int r0 = blockIdx.x * ING_TY, ch = blockIdx.y, fo = blockIdx.z;
   const uint8_t* src = raw + (int64_t)ing_pick_frame(frame_table, fo, n_src) * sf + (int64_t)ch * sc;
   float a0[1][4] = {}, a1[1][4] = {};
-  ing_plane_pass<1, false>(ing_lds, src, src, sy, sx, H, W, y_first, y_w, taps_y, x_first, x_w, taps_x, R, RP, TW, r0, a0, a1);
+  ing_plane_pass<1, false, 1>(ing_lds, src, src, sy, sx, H, W, y_first, y_w, taps_y, x_first, x_w, taps_x, R, RP, TW, r0, 0, a0, a1);
   if (tid < 224) {
     uint8_t* o = out + (((int64_t)fo * 3 + ch) * ING_OUT + r0 + tid / 56) * ING_OUT + 4 * (tid % 56);
     *(uint32_t*)o = ing_pack4(a0[0]);
@@ -238,23 +311,26 @@ struct IngCsc { float m[9], o[3]; };                                            
 
 // One workgroup = output rows [r0, r0 + 8) of ALL THREE channels of one output frame: the luma plane through ing_plane_pass (chunks of R source rows), then U and
 // V together (chunks of 4 rows of each; their tables replace the luma ones in the same LDS), the three resized 8 x 224 fp32 tiles staying in registers (24 per
-// lane); then the colour matrix and three full 224-byte lines per output row.
-template <bool INTER>
+// lane); then the colour matrix and three full 224-byte lines per output row.  BS: bytes per sample.  BS = 2 (P010: INTER, shift 6; yuv420p10le: shift 0): csx in
+// bytes, v = (word >> shift) & 1023, up to ING_PF16 staging registers per lane - LDS holds two workgroups per CU at the widest rows anyway, so nothing is lost to
+// the larger register budget there.  BS = 1 ignores shift.
+template <bool INTER, int BS>
 __global__ __launch_bounds__(256) void ingest_video_yuv_kernel(const uint8_t* __restrict__ raw, int64_t sf, int64_t sy, int64_t u_off, int64_t v_off, int64_t csy,
                                                                 int64_t csx, int n_src, int H, int W, const int32_t* __restrict__ frame_table,
                                                                 const int32_t* __restrict__ y_first, const float* __restrict__ y_w, int taps_y,
                                                                 const int32_t* __restrict__ x_first, const float* __restrict__ x_w, int taps_x,
                                                                 const int32_t* __restrict__ cy_first, const float* __restrict__ cy_w, int taps_cy,
                                                                 const int32_t* __restrict__ cx_first, const float* __restrict__ cx_w, int taps_cx, IngCsc csc,
-                                                                uint8_t* __restrict__ out, int R, int RP, int TW, int RPc, int TWc) {
+                                                                uint8_t* __restrict__ out, int R, int RP, int TW, int RPc, int TWc, int shift) {
   extern __shared__ __align__(16) unsigned char ing_lds[];
   const int tid = threadIdx.x;
   const int r0 = blockIdx.x * ING_TY, fo = blockIdx.y;
   const uint8_t* src = raw + (int64_t)ing_pick_frame(frame_table, fo, n_src) * sf;
   float ya[1][4] = {}, yb[1][4] = {}, c0[2][4] = {}, c1[2][4] = {};
-  ing_plane_pass<1, false>(ing_lds, src, src, sy, 1, H, W, y_first, y_w, taps_y, x_first, x_w, taps_x, R, RP, TW, r0, ya, yb);
+  ing_plane_pass<1, false, BS>(ing_lds, src, src, sy, BS, H, W, y_first, y_w, taps_y, x_first, x_w, taps_x, R, RP, TW, r0, shift, ya, yb);
   __syncthreads();                                                             // every lane is past the LDS of the luma pass
-  ing_plane_pass<2, INTER>(ing_lds, src + u_off, src + v_off, csy, csx, H >> 1, W >> 1, cy_first, cy_w, taps_cy, cx_first, cx_w, taps_cx, 4, RPc, TWc, r0, c0, c1);
+  ing_plane_pass<2, INTER, BS>(ing_lds, src + u_off, src + v_off, csy, csx, H >> 1, W >> 1, cy_first, cy_w, taps_cy, cx_first, cx_w, taps_cx, 4, RPc, TWc, r0, shift, c0,
+                               c1);
   if (tid < 224) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -273,15 +349,17 @@ __global__ __launch_bounds__(256) void ingest_video_yuv_kernel(const uint8_t* __
 
 // The LDS geometry of ing_plane_pass over `planes` planes of width W: the staged row RP, the padded table's rows TW, the chunk R - what ING_LDS_BYTES leave after
 // the padded horizontal table and the tile's vertical weights, over the bytes of one staged row plus one row of the horizontal pass of every plane, at most
-// max_rows and at most ING_PF staging registers per lane, rounded down to a multiple of 4 - and the bytes in all.  false: not even 4 rows fit.
+// max_rows and at most ING_PF staging registers per lane, rounded down to a multiple of 4 - and the bytes in all.  false: not even 4 rows fit.  bs: bytes per
+// sample; 2 takes the padded table, the LDS cap and the register budget of the 16-bit instantiation (RP stays in samples).
 struct IngGeom { int RP, TW, R, lds; };
-static bool ing_geometry(int W, int taps_y, int taps_x, int planes, int max_rows, IngGeom* g) {
+static bool ing_geometry(int W, int taps_y, int taps_x, int planes, int max_rows, int bs, IngGeom* g) {
   g->RP = ((W + taps_x + 3) & ~3) + ING_ROW_SLACK;
-  g->TW = 4 * ((taps_x + 6) >> 2) + 3;
-  const int fixed = (g->TW * ING_OUT + ING_TY * taps_y) * 4, per_row = planes * (g->RP + ING_OUT * 4);
-  int R = (ING_LDS_BYTES - fixed) / per_row;
+  g->TW = bs == 1 ? 4 * ((taps_x + 6) >> 2) + 3 : 2 * ((taps_x + 2) >> 1) + 1;
+  const int fixed = (g->TW * ING_OUT + ING_TY * taps_y) * 4, per_row = planes * (g->RP * bs + ING_OUT * 4);
+  const int pf_bytes = 256 * (bs == 1 ? ING_PF : ING_PF16) * 4;
+  int R = ((bs == 1 ? ING_LDS_BYTES : ING_LDS_BYTES16) - fixed) / per_row;
   R = R > max_rows ? max_rows : R;
-  if (R > 256 * ING_PF * 4 / (planes * g->RP)) R = 256 * ING_PF * 4 / (planes * g->RP);
+  if (R > pf_bytes / (planes * g->RP * bs)) R = pf_bytes / (planes * g->RP * bs);
   g->R = R & ~3;
   g->lds = fixed + g->R * per_row;
   return g->R >= 4;
@@ -306,7 +384,7 @@ extern "C" int sf_ingest_video(const uint8_t* raw, int64_t stride_frame, int64_t
   if (T_out == 0) return 0;
   SF_CHECK_ARG(raw && frame_table && y_first && y_w && x_first && x_w && out, "sf_ingest_video: null pointer");
   IngGeom g;
-  SF_CHECK_ARG(ing_geometry(W, taps_y, taps_x, 1, ING_MAX_ROWS, &g), "sf_ingest_video: W = %d is too wide for four staged source rows in LDS at taps_x = %d", W,
+  SF_CHECK_ARG(ing_geometry(W, taps_y, taps_x, 1, ING_MAX_ROWS, 1, &g), "sf_ingest_video: W = %d is too wide for four staged source rows in LDS at taps_x = %d", W,
                taps_x);
   hipLaunchKernelGGL(ingest_video_kernel, dim3(ING_OUT / ING_TY, 3, (unsigned)T_out), dim3(256), g.lds, (hipStream_t)stream, raw, stride_frame, stride_channel,
                      stride_row, stride_col, n_src, H, W, frame_table, y_first, y_w, taps_y, x_first, x_w, taps_x, out, g.R, g.RP, g.TW);
@@ -325,9 +403,9 @@ extern "C" int sf_ingest_video_yuv(const uint8_t* raw, int64_t stride_frame, int
   if (T_out == 0) return 0;
   SF_CHECK_ARG(raw && frame_table && y_first && y_w && x_first && x_w && cy_first && cy_w && cx_first && cx_w && csc && out, "sf_ingest_video_yuv: null pointer");
   IngGeom gy, gc;                                                               // luma as sf_ingest_video; chroma: four rows of U and four of V per chunk
-  SF_CHECK_ARG(ing_geometry(W, taps_y, taps_x, 1, ING_MAX_ROWS, &gy), "sf_ingest_video_yuv: W = %d is too wide for four staged source rows in LDS at taps_x = %d", W,
+  SF_CHECK_ARG(ing_geometry(W, taps_y, taps_x, 1, ING_MAX_ROWS, 1, &gy), "sf_ingest_video_yuv: W = %d is too wide for four staged source rows in LDS at taps_x = %d", W,
                taps_x);
-  SF_CHECK_ARG(ing_geometry(W / 2, taps_cy, taps_cx, 2, 4, &gc),
+  SF_CHECK_ARG(ing_geometry(W / 2, taps_cy, taps_cx, 2, 4, 1, &gc),
                "sf_ingest_video_yuv: W = %d is too wide for four staged rows of both chroma planes in LDS at taps_cx = %d", W, taps_cx);
   IngCsc k;
   for (int i = 0; i < 9; ++i) k.m[i] = csc[i];
@@ -335,12 +413,51 @@ extern "C" int sf_ingest_video_yuv(const uint8_t* raw, int64_t stride_frame, int
   auto launch = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, dim3(ING_OUT / ING_TY, (unsigned)T_out), dim3(256), gy.lds > gc.lds ? gy.lds : gc.lds, (hipStream_t)stream, raw, stride_frame,
                        stride_row, u_off, v_off, stride_crow, stride_ccol, n_src, H, W, frame_table, y_first, y_w, taps_y, x_first, x_w, taps_x, cy_first, cy_w,
-                       taps_cy, cx_first, cx_w, taps_cx, k, out, gy.R, gy.RP, gy.TW, gc.RP, gc.TW);
+                       taps_cy, cx_first, cx_w, taps_cx, k, out, gy.R, gy.RP, gy.TW, gc.RP, gc.TW, 0);
   };
   if (v_off == u_off + 1 && stride_ccol == 2)                                   // NV12: one fetch of the interleaved rows serves both planes
-    launch(ingest_video_yuv_kernel<true>);
+    launch(ingest_video_yuv_kernel<true, 1>);
   else
-    launch(ingest_video_yuv_kernel<false>);
+    launch(ingest_video_yuv_kernel<false, 1>);
+  SF_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int sf_ingest_video_yuv16(const uint16_t* raw, int64_t stride_frame, int64_t stride_row, int64_t u_off, int64_t v_off, int64_t stride_crow,
+                                     int64_t stride_ccol, int shift, int n_src, int H, int W, const int32_t* frame_table, const int32_t* y_first, const float* y_w,
+                                     int taps_y, const int32_t* x_first, const float* x_w, int taps_x, const int32_t* cy_first, const float* cy_w, int taps_cy,
+                                     const int32_t* cx_first, const float* cx_w, int taps_cx, const float* csc, uint8_t* out, int T_out, void* stream) {
+  if (ing_check_args("sf_ingest_video_yuv16", T_out, {taps_y, taps_x, taps_cy, taps_cx}, out, W)) return -1;
+  SF_CHECK_ARG(n_src >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, "sf_ingest_video_yuv16: source of %d frames %d x %d (4:2:0 takes even H and W)", n_src, H,
+               W);
+  SF_CHECK_ARG(stride_frame >= 0 && stride_row >= 0 && u_off >= 0 && v_off >= 0 && stride_crow >= 0 && stride_ccol >= 2,
+               "sf_ingest_video_yuv16: negative byte stride or offset, or a chroma column stride below 2 bytes");
+  SF_CHECK_ARG(((stride_frame | stride_row | u_off | v_off | stride_crow | stride_ccol) & 1) == 0,
+               "sf_ingest_video_yuv16: odd byte stride or offset (16-bit samples are 2-byte aligned)");
+  SF_CHECK_ARG(shift >= 0 && shift <= 6, "sf_ingest_video_yuv16: shift = %d (0 .. 6: ten bits of a 16-bit word)", shift);
+  if (T_out == 0) return 0;
+  SF_CHECK_ARG(raw && frame_table && y_first && y_w && x_first && x_w && cy_first && cy_w && cx_first && cx_w && csc && out, "sf_ingest_video_yuv16: null pointer");
+  SF_CHECK_ARG(((uintptr_t)raw & 1) == 0, "sf_ingest_video_yuv16: raw must be 2-byte aligned");
+  IngGeom gy, gc;
+  SF_CHECK_ARG(ing_geometry(W, taps_y, taps_x, 1, ING_MAX_ROWS, 2, &gy), "sf_ingest_video_yuv16: W = %d is too wide for four staged source rows in LDS at taps_x = %d",
+               W, taps_x);
+  SF_CHECK_ARG(ing_geometry(W / 2, taps_cy, taps_cx, 2, 4, 2, &gc),
+               "sf_ingest_video_yuv16: W = %d is too wide for four staged rows of both chroma planes in LDS at taps_cx = %d", W, taps_cx);
+  IngCsc k;
+  for (int i = 0; i < 9; ++i) k.m[i] = csc[i];
+  for (int i = 0; i < 3; ++i) k.o[i] = csc[9 + i];
+  int rc = 0;
+  auto launch = [&](auto kernel) {
+    if ((rc = sf_prepare_kernel((const void*)kernel, ING_LDS_BYTES16, "sf_ingest_video_yuv16")) != 0) return;
+    hipLaunchKernelGGL(kernel, dim3(ING_OUT / ING_TY, (unsigned)T_out), dim3(256), gy.lds > gc.lds ? gy.lds : gc.lds, (hipStream_t)stream, (const uint8_t*)raw,
+                       stride_frame, stride_row, u_off, v_off, stride_crow, stride_ccol, n_src, H, W, frame_table, y_first, y_w, taps_y, x_first, x_w, taps_x, cy_first,
+                       cy_w, taps_cy, cx_first, cx_w, taps_cx, k, out, gy.R, gy.RP, gy.TW, gc.RP, gc.TW, shift);
+  };
+  if (v_off == u_off + 2 && stride_ccol == 4)                                   // P010: one fetch of the interleaved rows serves both planes
+    launch(ingest_video_yuv_kernel<true, 2>);
+  else
+    launch(ingest_video_yuv_kernel<false, 2>);
+  if (rc) return rc;
   SF_LAUNCH_CHECK();
   return 0;
 }

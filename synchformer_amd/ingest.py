@@ -1,4 +1,4 @@
-"""Ingest a decoded recording at its native frame rate, size, pixel format and sample rate (DESIGN 3.11, 3.12).
+"""Ingest a decoded recording at its native frame rate, size, pixel format and sample rate (DESIGN 3.11 - 3.13).
 
 The reference re-encodes every input through an ffmpeg subprocess before any of its code runs (example.py:16-53: fps=25, short side scaled to 256, dimensions
 cropped to even, -ar 16000) and then takes the centre 224 crop of RGBSpatialCrop.  Here the same step is host geometry (this module: pure Python / torch,
@@ -17,10 +17,19 @@ Frames may also arrive as the 8-bit YUV 4:2:0 a decoder produces, 
     track = tracker.track_raw(raw_frames, raw_wave, ing)        # raw_frames (T, 1620, 1920) uint8: H luma rows, then the chroma rows
 
 The planes are resized and the colour matrix (csc_matrix: bt601 or bt709, limited or full range) runs on the 224 x 224 result, in the reference's order (its
-ffmpeg step scales in YUV).  Chroma is taken centre-sited; the default, bt601 limited range, is what swscale assumes for an untagged stream - an assumption that
-cannot be checked without an ffmpeg build.
+ffmpeg step scales in YUV).  The default, bt601 limited range, is what swscale assumes for an untagged stream - an assumption that cannot be checked without an
+ffmpeg build.
 
-Out of scope: decoding, 10-bit / 4:2:2 / 4:4:4 input, left chroma siting, double-buffered uploads, several recordings per call.
+10-bit 4:2:0 (HEVC Main10, AV1, VP9 profile 2) arrives as uint16 (T, 3 H / 2, W) and takes the same path on 16-bit samples (ops.ingest_video_yuv16):
+
+    ing = RecordingIngest(dev, 25, (2160, 3840), 48000, pix_fmt='p010', colorspace='bt709', chroma_loc='left')     # or 'yuv420p10le' (libav / PyAV arrays)
+
+chroma_loc says where the chroma samples sit: 'center' (the default: chroma as an (H / 2, W / 2) image), 'left' (co-sited with the even luma columns: the default
+of H.264, HEVC and MPEG-2) or 'topleft' (the BT.2020 default) - a quarter of a chroma sample in the chroma tables (aa_bicubic_table(shift=0.25)), for every YUV
+format.  csc=(M, offsets) overrides colorspace / full_range with a matrix on the format's own sample scale: this is how BT.2020 coefficients are passed.
+
+Out of scope: decoding, 12-bit / 4:2:2 / 4:4:4 input, BT.2020 in csc_matrix, transfer functions (PQ, HLG: a 10-bit HDR stream is converted by the matrix alone,
+no tone mapping), double-buffered uploads, several recordings per call.
 """
 import math
 from fractions import Fraction
@@ -30,7 +39,9 @@ import torch
 
 CROP = 224                       # the model's input size; ops.INGEST_OUT and ops.INGEST_MAX_TAPS are these two
 MAX_TAPS = 35                    # sf_ingest_video's range: a short side up to 2160 at resize_side 256
-PIX_FMTS = ('rgb24', 'nv12', 'yuv420p')
+PIX_FMTS = ('rgb24', 'nv12', 'yuv420p', 'p010', 'yuv420p10le')
+PIX_FMTS_16 = ('p010', 'yuv420p10le')   # 10-bit samples in uint16: ops.ingest_video_yuv16
+CHROMA_LOCS = {'center': (0.0, 0.0), 'left': (0.0, 0.25), 'topleft': (0.25, 0.25)}       # (shift of the cy tables, of the cx tables)
 _KR_KB = {'bt601': (0.299, 0.114), 'bt709': (0.2126, 0.0722)}
 
 
@@ -90,12 +101,14 @@ def _cubic(x: torch.Tensor, a: float = -0.5) -> torch.Tensor:
     return torch.where(x < 1, near, torch.where(x < 2, far, torch.zeros_like(x)))
 
 
-def aa_bicubic_table(n_in: int, n_out: int, dtype=torch.float32):
+def aa_bicubic_table(n_in: int, n_out: int, dtype=torch.float32, shift: float = 0.0):
     """The separable filter of F.interpolate(mode='bicubic', antialias=True, align_corners=False) along one axis, n_in -> n_out samples (cubic a = -0.5):
     (first int32 (n_out,), weights fp32 (n_out, taps), taps) with out[i] = sum_j weights[i, j] * in[first[i] + j].  scale = n_in / n_out; when downscaling the
     kernel is stretched by scale (support 2 scale), otherwise support 2; taps = 2 ceil(support) + 1; rows are normalised to sum 1 in float64, stored fp32,
     zero-padded to `taps` (first[i] + j may then pass n_in - 1: those weights are zero).  At scale 1 it is the identity.  dtype=torch.float64 returns the weights
-    before the fp32 rounding (for checks of the formula itself)."""
+    before the fp32 rounding (for checks of the formula itself).  shift moves the filter centre, c = scale (i + 0.5) + shift in source samples: source sample j is
+    taken to sit at coordinate j + 0.5, so a chroma sample co-sited with luma sample 2 k (luma coordinate 2 k + 0.5 = chroma coordinate k + 0.25) asks for
+    shift=0.25; 0.0 is F.interpolate's own geometry."""
     n_in, n_out = int(n_in), int(n_out)
     if n_in < 1 or n_out < 1:
         raise ValueError(f'aa_bicubic_table: {n_in} -> {n_out}')
@@ -107,7 +120,7 @@ def aa_bicubic_table(n_in: int, n_out: int, dtype=torch.float32):
     w = torch.zeros(n_out, taps, dtype=torch.float64)
     j = torch.arange(taps, dtype=torch.float64)
     for i in range(n_out):
-        c = scale * (i + 0.5)
+        c = scale * (i + 0.5) + shift
         xmin = max(0, int(c - support + 0.5))
         xsize = min(n_in, int(c + support + 0.5)) - xmin
         row = _cubic((j[:xsize] + xmin - c + 0.5) * inv)
@@ -116,25 +129,34 @@ def aa_bicubic_table(n_in: int, n_out: int, dtype=torch.float32):
     return first, w.to(dtype), taps
 
 
-def _crop_table(n_in: int, n_out: int, origin: int, crop: int, dev):
-    """aa_bicubic_table(n_in, n_out) cut to the output samples [origin, origin + crop), on the device: (first, weights, taps)."""
-    first, w, taps = aa_bicubic_table(n_in, n_out)
+def _crop_table(n_in: int, n_out: int, origin: int, crop: int, dev, shift: float = 0.0):
+    """aa_bicubic_table(n_in, n_out, shift=shift) cut to the output samples [origin, origin + crop), on the device: (first, weights, taps)."""
+    first, w, taps = aa_bicubic_table(n_in, n_out, shift=shift)
     return first[origin:origin + crop].contiguous().to(dev), w[origin:origin + crop].contiguous().to(dev), taps
 
 
-def csc_matrix(colorspace: str = 'bt601', full_range: bool = False):
-    """(M (3, 3) float64, offsets (3,) float64) with (R, G, B) = M @ ((Y, U, V) - offsets) on the 8-bit scale.  With Kr, Kb of the colour space (bt601: 0.299,
+def csc_matrix(colorspace: str = 'bt601', full_range: bool = False, bit_depth: int = 8):
+    """(M (3, 3) float64, offsets (3,) float64) with (R, G, B) = M @ ((Y, U, V) - offsets): samples on the `bit_depth` scale (8 or 10), RGB on the 8-bit scale.
+    On the 8-bit scale, with Kr, Kb of the colour space (bt601: 0.299,
     0.114; bt709: 0.2126, 0.0722), Kg = 1 - Kr - Kb, luma gain gy and chroma gain gc (limited range: 255 / 219 and 255 / 224, offsets (16, 128, 128); full range:
-    1 and 1, offsets (0, 128, 128)):  R = gy Y' + 2 (1 - Kr) gc V',  B = gy Y' + 2 (1 - Kb) gc U',  G = gy Y' - 2 Kb (1 - Kb) / Kg gc U' - 2 Kr (1 - Kr) / Kg gc V'."""
+    1 and 1, offsets (0, 128, 128)):  R = gy Y' + 2 (1 - Kr) gc V',  B = gy Y' + 2 (1 - Kb) gc U',  G = gy Y' - 2 Kb (1 - Kb) / Kg gc U' - 2 Kr (1 - Kr) / Kg gc V'.
+    bit_depth=10: limited range has gains 255 / (219 * 4) and 255 / (224 * 4), offsets (64, 512, 512) - the 8-bit matrix divided by 4, exactly; full range has
+    gains 255 / 1023, offsets (0, 512, 512)."""
     if colorspace not in _KR_KB:
         raise ValueError(f'colorspace = {colorspace!r}: one of {sorted(_KR_KB)}')
+    if bit_depth not in (8, 10):
+        raise ValueError(f'bit_depth = {bit_depth}: 8 or 10')
     kr, kb = _KR_KB[colorspace]
     kg = 1.0 - kr - kb
     gy, gc, o0 = (1.0, 1.0, 0.0) if full_range else (255.0 / 219.0, 255.0 / 224.0, 16.0)
+    oc = 128.0
+    if bit_depth == 10:                                                          # a power of two: every entry of the limited-range matrix is the 8-bit one / 4
+        gy, gc = (255.0 / 1023.0, 255.0 / 1023.0) if full_range else (gy / 4.0, gc / 4.0)
+        o0, oc = 4.0 * o0, 512.0
     M = torch.tensor([[gy, 0.0, 2 * (1 - kr) * gc],
                       [gy, -2 * kb * (1 - kb) / kg * gc, -2 * kr * (1 - kr) / kg * gc],
                       [gy, 2 * (1 - kb) * gc, 0.0]], dtype=torch.float64)
-    return M, torch.tensor([o0, 128.0, 128.0], dtype=torch.float64)
+    return M, torch.tensor([o0, oc, oc], dtype=torch.float64)
 
 
 def resample_kernel(rate_in: int, rate_out: int = 16000, lowpass_filter_width: int = 6, rolloff: float = 0.99):
@@ -162,14 +184,20 @@ class RecordingIngest:
     fps_in: int, float or (num, den); size_in = (H, W) of the raw frames; rate_in: Hz; channels_last: raw frames are (T, H, W, 3) as decoders hand them out,
     otherwise planar (T, 3, H, W); resize_side: what the short side is scaled to (256, the even cut of the other side as in example.py); crop stays 224, centred
     with RGBSpatialCrop's origin int(round((Hr - 224) / 2.)).  pix_fmt: 'rgb24' (the layouts above), or 'nv12' / 'yuv420p': raw frames are (T, 3 H / 2, W), 8-bit
-    YUV 4:2:0 (ops.ingest_video_yuv), converted with csc_matrix(colorspace, full_range) after the resize.  ValueError on resize_side < crop, crop != 224, a source
-    so large that a filter row passes 35 taps (short side above ~2160 at resize_side 256), an unknown pix_fmt or colorspace, and for a YUV format odd H or W or
-    channels_last=True."""
+    YUV 4:2:0 (ops.ingest_video_yuv), or 'p010' / 'yuv420p10le': the same shape in uint16 (int16 is read as the same bits), 10-bit YUV 4:2:0
+    (ops.ingest_video_yuv16) - converted with csc_matrix(colorspace, full_range, bit_depth) after the resize, or with csc = (M (3, 3), offsets (3,)) on the format's
+    own sample scale when given (it overrides colorspace / full_range; e.g. BT.2020 coefficients).  chroma_loc: 'center', 'left' or 'topleft' (CHROMA_LOCS; YUV
+    formats only).  ValueError on resize_side < crop, crop != 224, a source so large that a filter row passes 35 taps (short side above ~2160 at resize_side 256),
+    an unknown pix_fmt, colorspace or chroma_loc, chroma_loc or csc with rgb24, and for a YUV format odd H or W or channels_last=True."""
 
     def __init__(self, device, fps_in, size_in, rate_in: int, channels_last: bool = False, resize_side: int = 256, crop: int = CROP, pix_fmt: str = 'rgb24',
-                 colorspace: str = 'bt601', full_range: bool = False):
+                 colorspace: str = 'bt601', full_range: bool = False, chroma_loc: str = 'center', csc=None):
         if pix_fmt not in PIX_FMTS:
             raise ValueError(f'pix_fmt = {pix_fmt!r}: one of {PIX_FMTS}')
+        if chroma_loc not in CHROMA_LOCS:
+            raise ValueError(f'chroma_loc = {chroma_loc!r}: one of {tuple(CHROMA_LOCS)}')
+        if pix_fmt == 'rgb24' and (chroma_loc != 'center' or csc is not None):
+            raise ValueError(f"chroma_loc = {chroma_loc!r} / csc with pix_fmt = 'rgb24': they describe YUV frames")
         if colorspace not in _KR_KB:
             raise ValueError(f'colorspace = {colorspace!r}: one of {sorted(_KR_KB)}')
         if crop != CROP:
@@ -195,10 +223,17 @@ class RecordingIngest:
             if self.H % 2 or self.W % 2:
                 raise ValueError(f'{self.H} x {self.W} with pix_fmt = {pix_fmt!r}: 4:2:0 takes even H and W')
             # chroma: an (H / 2, W / 2) image resized to the same (Hr, Wr), sliced at the same crop origin; never more taps than luma
-            self.cy_first, self.cy_w, self.taps_cy = _crop_table(self.H // 2, self.Hr, self.y0, crop, self.dev)
-            self.cx_first, self.cx_w, self.taps_cx = _crop_table(self.W // 2, self.Wr, self.x0, crop, self.dev)
+            # chroma_loc: the quarter-sample shift of sited chroma goes into these tables, the kernels never see it
+            self.chroma_loc = chroma_loc
+            self.cy_first, self.cy_w, self.taps_cy = _crop_table(self.H // 2, self.Hr, self.y0, crop, self.dev, CHROMA_LOCS[chroma_loc][0])
+            self.cx_first, self.cx_w, self.taps_cx = _crop_table(self.W // 2, self.Wr, self.x0, crop, self.dev, CHROMA_LOCS[chroma_loc][1])
             self.colorspace, self.full_range = colorspace, bool(full_range)
-            M, off = csc_matrix(colorspace, full_range)
+            if csc is None:
+                M, off = csc_matrix(colorspace, full_range, 10 if pix_fmt in PIX_FMTS_16 else 8)
+            else:
+                M, off = (torch.as_tensor(v, dtype=torch.float64).cpu() for v in csc)
+                if M.shape != (3, 3) or off.shape != (3,):
+                    raise ValueError(f'csc: expected (M (3, 3), offsets (3,)), got {tuple(M.shape)} and {tuple(off.shape)}')
             self.csc = torch.cat([M.reshape(9), off]).float()                        # host: the twelve floats travel as kernel arguments
         if self.rate_in == 16000:
             self.kernel, self.width, self.o, self.n = torch.ones(1, 1), 0, 1, 1   # down-mix / PCM scaling only
@@ -223,8 +258,9 @@ class RecordingIngest:
 
     def _check_frames(self, raw: torch.Tensor):
         want = (self.H * 3 // 2, self.W) if self.pix_fmt != 'rgb24' else (self.H, self.W, 3) if self.channels_last else (3, self.H, self.W)
-        if raw.dim() != len(want) + 1 or raw.dtype != torch.uint8 or tuple(raw.shape[1:]) != want:
-            raise ValueError(f'raw frames: expected uint8 (T, {", ".join(map(str, want))}), got {raw.dtype} {tuple(raw.shape)}')
+        dtypes = (torch.uint16, torch.int16) if self.pix_fmt in PIX_FMTS_16 else (torch.uint8,)
+        if raw.dim() != len(want) + 1 or raw.dtype not in dtypes or tuple(raw.shape[1:]) != want:
+            raise ValueError(f'raw frames: expected {str(dtypes[0])[6:]} (T, {", ".join(map(str, want))}), got {raw.dtype} {tuple(raw.shape)}')
 
     def frames(self, raw: torch.Tensor, j0: int, j1: int) -> torch.Tensor:
         """25 fps frames [j0, j1) of the recording, resized and cropped: uint8 (j1 - j0, 3, 224, 224) on the device.  raw: all the raw frames, device or host; from
@@ -240,8 +276,9 @@ class RecordingIngest:
         lo, hi = int(t[0]), int(t[-1]) + 1                                       # the table is non-decreasing
         src = raw[lo:hi].to(self.dev, non_blocking=True)
         if self.pix_fmt != 'rgb24':
-            return ops.ingest_video_yuv(src, self.pix_fmt, (t - lo).to(self.dev, non_blocking=True), self.y_first, self.y_w, self.x_first, self.x_w, self.cy_first,
-                                        self.cy_w, self.cx_first, self.cx_w, self.csc)
+            op = ops.ingest_video_yuv16 if self.pix_fmt in PIX_FMTS_16 else ops.ingest_video_yuv
+            return op(src, self.pix_fmt, (t - lo).to(self.dev, non_blocking=True), self.y_first, self.y_w, self.x_first, self.x_w, self.cy_first, self.cy_w,
+                      self.cx_first, self.cx_w, self.csc)
         return ops.ingest_video(src, self.channels_last, (t - lo).to(self.dev, non_blocking=True), self.y_first, self.y_w, self.x_first, self.x_w)
 
     def wave(self, raw_wave: torch.Tensor) -> torch.Tensor:

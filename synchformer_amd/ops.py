@@ -738,6 +738,35 @@ def ingest_video_yuv(raw: torch.Tensor, pix_fmt: str, frame_table: torch.Tensor,
         src, sf, sy, u_off, v_off, csy, csx, n_src, H, W, ft, *tabs, C.addressof(csc_c), o, n, _stream()))
 
 
+_YUV16_SHIFT = {'p010': 6, 'yuv420p10le': 0}
+
+
+def ingest_video_yuv16(raw: torch.Tensor, pix_fmt: str, frame_table: torch.Tensor, y_first: torch.Tensor, y_w: torch.Tensor, x_first: torch.Tensor, x_w: torch.Tensor,
+                       cy_first: torch.Tensor, cy_w: torch.Tensor, cx_first: torch.Tensor, cx_w: torch.Tensor, csc, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ingest_video_yuv for 10-bit YUV 4:2:0 frames in 16-bit samples (sf_ingest_video_yuv16).  raw uint16 (or int16, read as the same bits) (n_src, 3 H / 2, W) on
+    the device, H and W even, any frame stride; pix_fmt 'p010' (H luma rows, then H / 2 rows of interleaved U V, the sample in the high 10 bits; any row stride >= W
+    elements, so a view into a pitched decoder surface is read in place) or 'yuv420p10le' (I420 order, the sample in the low 10 bits; contiguous rows).  The sample is
+    (word >> shift) & 1023, so stray bits are dropped.  Tables as for ingest_video_yuv; csc: 12 floats on the 10-bit scale (ingest.csc_matrix(bit_depth=10)) ->
+    uint8 (T_out, 3, 224, 224)."""
+    if pix_fmt not in _YUV16_SHIFT:
+        raise ValueError(f"ingest_video_yuv16: pix_fmt = {pix_fmt!r} ('p010' or 'yuv420p10le')")
+    if raw.dim() != 3 or raw.dtype not in (torch.uint16, torch.int16) or raw.shape[1] % 3 or raw.shape[2] % 2 or raw.shape[1] == 0 or raw.shape[2] == 0:
+        raise ValueError(f'ingest_video_yuv16: expected uint16 frames (n, 3 H / 2, W) with even H and W, got {raw.dtype} {tuple(raw.shape)}')
+    n_src, H, W = raw.shape[0], raw.shape[1] // 3 * 2, raw.shape[2]
+    sf, sy, sx = raw.stride()
+    if sx != 1 or sf < 0 or (sy != W if pix_fmt == 'yuv420p10le' else sy < W):
+        raise ValueError(f'ingest_video_yuv16: {pix_fmt} frames with strides {tuple(raw.stride())}: unit column stride and '
+                         f'{"contiguous rows" if pix_fmt == "yuv420p10le" else "a row stride of at least W"} expected')
+    # the launcher takes byte strides and offsets
+    u_off, v_off, csy, csx = (2 * sy * H, 2 * sy * H + 2, 2 * sy, 4) if pix_fmt == 'p010' else (2 * H * W, 2 * (H * W + (H // 2) * (W // 2)), W, 2)
+    csc = [float(v) for v in (csc.reshape(-1).tolist() if isinstance(csc, torch.Tensor) else csc)]
+    assert len(csc) == 12, 'ingest_video_yuv16: csc is 9 matrix entries and 3 offsets'
+    csc_c = (C.c_float * 12)(*csc)
+    src, tabs = _dev(raw, 'raw'), _ingest_tables(frame_table, y=(y_first, y_w), x=(x_first, x_w), cy=(cy_first, cy_w), cx=(cx_first, cx_w))
+    return _ingest_chunks('sf_ingest_video_yuv16', frame_table, _ingest_out(out, frame_table.numel(), raw.device), lambda ft, o, n: _lib.load().sf_ingest_video_yuv16(
+        src, 2 * sf, 2 * sy, u_off, v_off, csy, csx, _YUV16_SHIFT[pix_fmt], n_src, H, W, ft, *tabs, C.addressof(csc_c), o, n, _stream()))
+
+
 SF_I16 = 4
 
 

@@ -2,12 +2,13 @@
 beside the same windows through forward_clips on explicit 120-frame slices.  Prints one JSON line.
 
     python tools/track_recording.py [--seconds 60] [--hop 1] [--seg-chunk 224] [--host] [--clip-windows 8] [--fps 30000/1001 --size 1080x1920 --rate 48000]
-                                    [--pix-fmt {rgb24,nv12,yuv420p}]
+                                    [--pix-fmt {rgb24,nv12,yuv420p,p010,yuv420p10le}] [--chroma-loc {center,left,topleft}]
 
 With --fps / --size / --rate the recording is synthesised RAW at that geometry (channels-last uint8 frames, stereo int16 PCM, in device memory) and goes through
 the ingest stage: the line then also carries the ingest time alone (the same chunks the bank asks for, plus the wave) and the bank from raw
 frames next to the bank from frames ingested beforehand.  With --pix-fmt nv12 / yuv420p the raw frames are 8-bit YUV 4:2:0 in that layout: half
-the bytes per frame, which the line reports next to the times (with --host they are what is uploaded).
+the bytes per frame, which the line reports next to the times (with --host they are what is uploaded).  With --pix-fmt p010 / yuv420p10le they are 10-bit
+4:2:0 in 16-bit samples: the bytes of RGB again.  --chroma-loc sites the chroma samples of a YUV layout (tables only: no cost on the device).
 
 forward_clips is timed on at most --clip-windows windows (spread over the recording) and scaled to all W; both sides include the mel front-end and
 are timed by wall clock around a device synchronisation, after one warm-up pass each.  Synthetic weights and inputs: the numbers are throughput only."""
@@ -35,7 +36,8 @@ def main():
     ap.add_argument('--fps', default=None, help='raw frame rate, e.g. 30, 29.97 or 30000/1001 (default: 25, no ingest)')
     ap.add_argument('--size', default=None, help='raw frame size HxW, e.g. 1080x1920')
     ap.add_argument('--rate', type=int, default=None, help='raw sample rate in Hz, e.g. 48000')
-    ap.add_argument('--pix-fmt', choices=['rgb24', 'nv12', 'yuv420p'], default=None, help='layout of the raw frames (default: rgb24, channels-last)')
+    ap.add_argument('--pix-fmt', choices=['rgb24', 'nv12', 'yuv420p', 'p010', 'yuv420p10le'], default=None, help='layout of the raw frames (default: rgb24, channels-last)')
+    ap.add_argument('--chroma-loc', choices=['center', 'left', 'topleft'], default='center', help='where the chroma samples of a YUV layout sit')
     args = ap.parse_args()
     from synchformer_amd import synth
     from synchformer_amd.engine import SynchformerEngine
@@ -49,9 +51,10 @@ def main():
         fps = tuple(int(v) for v in args.fps.split('/')) if args.fps and '/' in args.fps else float(args.fps or 25)
         RH, RW = (int(v) for v in (args.size or '256x256').lower().split('x'))
         pix_fmt = args.pix_fmt or 'rgb24'
-        ing = RecordingIngest(dev, fps, (RH, RW), args.rate or 16000, channels_last=pix_fmt == 'rgb24', pix_fmt=pix_fmt)
-        raw_shape = (RH, RW, 3) if pix_fmt == 'rgb24' else (RH * 3 // 2, RW)     # random bytes are a valid frame in every layout
-        frame_bytes = RH * RW * 3 if pix_fmt == 'rgb24' else RH * RW * 3 // 2
+        ing = RecordingIngest(dev, fps, (RH, RW), args.rate or 16000, channels_last=pix_fmt == 'rgb24', pix_fmt=pix_fmt, chroma_loc=args.chroma_loc)
+        deep = pix_fmt in ('p010', 'yuv420p10le')
+        raw_shape = (RH, RW, 3) if pix_fmt == 'rgb24' else (RH * 3 // 2, RW)     # random bits are a valid frame in every layout (stray bits of a 16-bit word are dropped)
+        frame_bytes = RH * RW * 3 if pix_fmt == 'rgb24' else RH * RW * 3 // 2 * (2 if deep else 1)
         T_raw, n_raw = int(args.seconds * ing.fps_in), int(args.seconds * ing.rate_in)
         T, n = ing.n_frames(T_raw), ing.n_samples(n_raw)
     else:
@@ -65,7 +68,10 @@ def main():
     gen = torch.Generator().manual_seed(7)
     if raw_mode:
         dgen = torch.Generator(device=dev).manual_seed(7)
-        raw = torch.randint(0, 256, (T_raw, *raw_shape), generator=dgen, dtype=torch.uint8, device=dev)
+        if deep:
+            raw = torch.randint(-32768, 32768, (T_raw, *raw_shape), generator=dgen, dtype=torch.int16, device=dev).view(torch.uint16)
+        else:
+            raw = torch.randint(0, 256, (T_raw, *raw_shape), generator=dgen, dtype=torch.uint8, device=dev)
         raw_wave = torch.randint(-32768, 32768, (2, n_raw), generator=gen, dtype=torch.int32).to(torch.int16).to(dev)
         fd, wd = ing.frames(raw, 0, T), ing.wave(raw_wave)                      # materialised for the comparisons below only
         if args.host:
@@ -103,7 +109,7 @@ def main():
         t_raw, (vb_raw, ab_raw) = timed(lambda: eng.extract_recording_from(lambda f0, f1: ing.frames(raw, f0, f1), T, ing.wave(raw_wave), mel))
         table = ing.frame_table(T_raw)
         src_frames = int(torch.unique(table).numel())
-        extra = {'raw_fps': float(ing.fps_in), 'raw_size': [RH, RW], 'raw_rate': ing.rate_in, 'pix_fmt': pix_fmt, 'raw_frames': T_raw, 'raw_bytes_per_frame': frame_bytes,
+        extra = {'raw_fps': float(ing.fps_in), 'raw_size': [RH, RW], 'raw_rate': ing.rate_in, 'pix_fmt': pix_fmt, 'chroma_loc': args.chroma_loc, 'raw_frames': T_raw, 'raw_bytes_per_frame': frame_bytes,
                  'raw_bytes': T_raw * frame_bytes, 'frames_25fps': T, 'taps': [ing.taps_y, ing.taps_x],
                  'ingest_s': round(t_ing, 5), 'ingest_frames_per_s': round(sum(f1 - f0 for f0, f1 in chunks) / t_ing, 1),
                  'ingest_video_one_launch_s': round(t_one, 5), 'ingest_video_one_launch_frames_per_s': round(T / t_one, 1),
