@@ -29,7 +29,7 @@ extern "C" {
 enum { SF_F32 = 0, SF_BF16 = 1, SF_F16 = 2, SF_U8 = 3, SF_I16 = 4 };   /* element types (SF_I16: PCM input of sf_resample_wave only) */
 enum { SF_EPI_NONE = 0, SF_EPI_GELU = 1 };                  /* GEMM epilogue activation */
 
-#define SF_ABI_VERSION 17
+#define SF_ABI_VERSION 18
 int sf_abi_version(void);
 const char* sf_last_error(void);
 /* "gfx950" + build flags; lets the host assert it loaded the library it built */
@@ -514,6 +514,26 @@ int sf_shift_window_preds(const float* G, int64_t ldg, int n_clips, int S, int W
  * (dataset/transforms.py:221-239); the reference itself has no recording-level read-out. */
 int sf_track_decode(const float* logits, int64_t ldl, int W, int C, float lam, int32_t* cls_raw, float* conf_raw, int32_t* cls_path, float* conf_path,
                     uint8_t* backptr, void* stream);
+
+/* Posterior (forward-backward) read-out of the same chain: the Viterbi path above is the mode of
+ *     p(c_0 .. c_{W-1})  ~  exp(sum_w e[w, c_w] - lam sum_{w >= 1} |c_w - c_{w-1}|),        e[w, c] = logits[w, c] - lse_c logits[w, .]   (the TRUE log-softmax),
+ * this entry gives its marginals.  logits (W, C) fp32, row stride ldl >= C, rows in time order, 2 <= C <= 64, lam finite and >= 0, grid (C) fp32 = the offsets
+ * (seconds) the classes stand for.  With lse = log sum exp:
+ *     a_0 = e[0];            a_w[c] = e[w, c] + lse_p (a_{w-1}[p] - lam |p - c|)
+ *     b_{W-1} = 0;           b_w[c] = lse_n (b_{w+1}[n] + e[w+1, n] - lam |n - c|)
+ *     post[w, c]     = exp(a_w[c] + b_w[c] - lse_c (a_w + b_w))              (W, C) fp32, row stride ldp >= C; rows sum to 1
+ *     cls_post[w]    = argmax_c post[w, c], lowest index on ties;            conf_post[w] = post[w, cls_post[w]]
+ *     offset_mean[w] = sum_c post[w, c] grid[c]                              ascending c, fp32
+ *     log_z[0]       = lse_c a_{W-1}[c]                                      <= 0; 0 at lam = 0 and at W = 1: the log of the probability mass that independent
+ *                                                                            per-window softmax draws keep under the smoothness penalty
+ * Log domain, fp32; every lse is a max pass and a sum-of-exp pass in ascending index.  After every step the maximum of a_w / b_w is subtracted (a per-row constant
+ * cancels in post), so the scores are bounded for any W; the amounts subtracted from a are summed in a double and carried into log_z.  At lam = 0 and at W = 1
+ * post[w] = softmax(logits[w]); reversing the rows reverses post and keeps log_z.  A -inf logit is a masked class: in a row with a finite entry it gives post == 0
+ * exactly there, finite values elsewhere and no NaN.  Rows with NaN or +inf give unspecified values; cls_post lies in [0, C) always (a NaN never wins `>`).
+ * workspace: caller-owned, 2 * W * C floats (a, then b; 8 W C bytes).  Two launches on the caller's stream (the two scans side by side in one launch of two
+ * one-wavefront workgroups, then one thread per window), no allocation, no host synchronisation; W == 0 launches nothing and writes nothing. */
+int sf_track_posterior(const float* logits, int64_t ldl, int W, int C, float lam, const float* grid, float* post, int64_t ldp, int32_t* cls_post,
+                       float* conf_post, float* offset_mean, float* log_z, float* workspace, void* stream);
 
 /* ---- Ingest of a decoded recording at its native frame rate, size and sample rate: the step the reference leaves to an ffmpeg subprocess in front of its code
  * (example.py:16-53: fps=25, short side 256, even dimensions, -ar 16000), plus the centre 224 crop of RGBSpatialCrop (dataset/transforms.py:68-95).  The host

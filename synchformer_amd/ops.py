@@ -672,6 +672,32 @@ def track_decode(logits: torch.Tensor, lam: float):
     return cls_raw, conf_raw, cls_path, conf_path
 
 
+def track_posterior(logits: torch.Tensor, lam: float, grid: torch.Tensor, post: Optional[torch.Tensor] = None):
+    """Posterior (forward-backward) read-out of a recording's window logits (sf_track_posterior): logits fp32 (W, C) on device with unit column stride (a row
+    stride above C is passed on), rows in time order, 2 <= C <= 64; grid fp32 (C,) on the same device: the offsets the classes stand for ->
+    (post fp32 (W, C), cls_post int32 (W,), conf_post fp32 (W,), offset_mean fp32 (W,), log_z fp32 (1,)): the marginals of the chain whose mode is
+    track_decode's path, their argmax and its value, the posterior mean of the grid, and the log partition sum over independent softmax draws (<= 0).
+    Allocates the outputs and the 2 W C floats of workspace (`post`, if given, is written instead of a fresh tensor: fp32 (W, C) with unit column stride, any
+    row stride >= C); nothing is read back: log_z stays on the device (0 for W = 0, the empty product)."""
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and grid.dtype == torch.float32 and grid.device == logits.device
+    W, C = logits.shape
+    assert grid.dim() == 1 and grid.numel() == C and grid.is_contiguous(), f'a grid of {tuple(grid.shape)} for {C} classes'
+    assert W == 0 or logits.stride(1) == 1, 'logits: unit column stride'
+    dev = logits.device
+    if post is None:
+        post = torch.empty(W, C, device=dev, dtype=torch.float32)
+    assert post.dtype == torch.float32 and post.shape == (W, C) and post.device == dev and (W == 0 or post.stride(1) == 1), 'post: fp32 (W, C), unit column stride'
+    cls_post = torch.empty(W, device=dev, dtype=torch.int32)
+    conf_post, offset_mean = torch.empty(W, device=dev, dtype=torch.float32), torch.empty(W, device=dev, dtype=torch.float32)
+    log_z = torch.empty(1, device=dev, dtype=torch.float32) if W else torch.zeros(1, device=dev, dtype=torch.float32)
+    ws = torch.empty(2 * max(W, 1) * C, device=dev, dtype=torch.float32)
+    rc = _lib.load().sf_track_posterior(_dev(logits, 'logits'), _ld(logits) if W else C, W, C, float(lam), _dev(grid, 'grid'), _dev(post, 'post'), _ld(post) if W else C,
+                                        _dev(cls_post, 'cls_post'), _dev(conf_post, 'conf_post'), _dev(offset_mean, 'offset_mean'), _dev(log_z, 'log_z'),
+                                        _dev(ws, 'workspace'), _stream())
+    _lib.check(rc, 'sf_track_posterior')
+    return post, cls_post, conf_post, offset_mean, log_z
+
+
 def _ingest_tables(frame_table: torch.Tensor, **tables):
     """Checks frame_table (int32, contiguous) and the filter tables name=(first int32 (224,), weights fp32 (224, taps)), all contiguous; returns their launcher
     arguments in order: (first, weights, taps) per table."""

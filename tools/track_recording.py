@@ -2,13 +2,16 @@
 beside the same windows through forward_clips on explicit 120-frame slices.  Prints one JSON line.
 
     python tools/track_recording.py [--seconds 60] [--hop 1] [--seg-chunk 224] [--host] [--clip-windows 8] [--fps 30000/1001 --size 1080x1920 --rate 48000]
-                                    [--pix-fmt {rgb24,nv12,yuv420p,p010,yuv420p10le}] [--chroma-loc {center,left,topleft}]
+                                    [--pix-fmt {rgb24,nv12,yuv420p,p010,yuv420p10le}] [--chroma-loc {center,left,topleft}] [--posterior]
 
 With --fps / --size / --rate the recording is synthesised RAW at that geometry (channels-last uint8 frames, stereo int16 PCM, in device memory) and goes through
 the ingest stage: the line then also carries the ingest time alone (the same chunks the bank asks for, plus the wave) and the bank from raw
 frames next to the bank from frames ingested beforehand.  With --pix-fmt nv12 / yuv420p the raw frames are 8-bit YUV 4:2:0 in that layout: half
 the bytes per frame, which the line reports next to the times (with --host they are what is uploaded).  With --pix-fmt p010 / yuv420p10le they are 10-bit
 4:2:0 in 16-bit samples: the bytes of RGB again.  --chroma-loc sites the chroma samples of a YUV layout (tables only: no cost on the device).
+
+With --posterior the windows are also read out as marginals: the line then carries the mean and minimum of conf_post, log_z per window step
+(log_z / max(W - 1, 1)), the largest |offset_sec_mean - offset_sec_path| and the time of the two extra launches (the read-out alone, on the track's logits).
 
 forward_clips is timed on at most --clip-windows windows (spread over the recording) and scaled to all W; both sides include the mel front-end and
 are timed by wall clock around a device synchronisation, after one warm-up pass each.  Synthetic weights and inputs: the numbers are throughput only."""
@@ -38,8 +41,9 @@ def main():
     ap.add_argument('--rate', type=int, default=None, help='raw sample rate in Hz, e.g. 48000')
     ap.add_argument('--pix-fmt', choices=['rgb24', 'nv12', 'yuv420p', 'p010', 'yuv420p10le'], default=None, help='layout of the raw frames (default: rgb24, channels-last)')
     ap.add_argument('--chroma-loc', choices=['center', 'left', 'topleft'], default='center', help='where the chroma samples of a YUV layout sit')
+    ap.add_argument('--posterior', action='store_true', help='also read the windows out as marginals (forward-backward)')
     args = ap.parse_args()
-    from synchformer_amd import synth
+    from synchformer_amd import ops, synth
     from synchformer_amd.engine import SynchformerEngine
     from synchformer_amd.frontend import MelFrontend, recording_geometry
     from synchformer_amd.ingest import RecordingIngest
@@ -82,7 +86,7 @@ def main():
         wave = torch.rand(n, generator=gen) * 2 - 1
         fd, wd = frames.to(dev), wave.to(dev)
         src = (frames.pin_memory(), wave.pin_memory()) if args.host else (fd, wd)
-    tracker = OffsetTracker(eng, mel, hop_segments=args.hop)
+    tracker = OffsetTracker(eng, mel, hop_segments=args.hop, posterior=args.posterior)
 
     def timed(fn, reps=1):
         fn()
@@ -116,6 +120,12 @@ def main():
                  'ingest_video_one_launch_source_GBps': round(src_frames * frame_bytes / t_one / 1e9, 1), 'resample_wave_s': round(t_wave, 6),
                  'bank_from_raw_s': round(t_raw, 4), 'bank_from_raw_equals_bank': bool(torch.equal(vb_raw, vbank) and torch.equal(ab_raw, abank))}
     t_win, track = timed(lambda: tracker.track_features(vbank, abank, win_chunk=args.win_chunk), reps=3)
+    if args.posterior:
+        t_post, _ = timed(lambda: ops.track_posterior(track.logits, tracker.lam, tracker.grid), reps=20)
+        extra.update({'conf_post_mean': round(track.conf_post.mean().item(), 4), 'conf_post_min': round(track.conf_post.min().item(), 4),
+                      'log_z_per_step': round(track.log_z.item() / max(W - 1, 1), 4),
+                      'max_abs_mean_minus_path_s': round((track.offset_sec_mean - track.offset_sec_path).abs().max().item(), 4),
+                      'posterior_s': round(t_post, 6)})
     k = min(W, max(1, args.clip_windows))
     picks = [round(i * (W - 1) / max(1, k - 1)) for i in range(k)]
 
