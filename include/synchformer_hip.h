@@ -37,6 +37,9 @@ const char* sf_build_info(void);
 /* C[cmap(m), n] = epi(sum_k A[m,k] * W[n,k] + bias[n]) (+ R[rmap(m), n]);  A: M x K bf16 (row stride lda),
  * W: N x K bf16 (an nn.Linear / flattened conv weight, row stride ldw), bias fp32 or NULL, C bf16|fp32,
  * R fp32 or NULL (may alias C for an in-place residual).  K % 64 == 0.  Exact-erf GELU when SF_EPI_GELU.
+ * Alignment: A and W 16 bytes, lda / ldw multiples of 8 elements (checked).  C and R need only their element's alignment, EXCEPT when N % 4 == 0 and ldc
+ * (and ldr, with a residual) are multiples of 4: the epilogue then moves four columns per access, so C must be 16-byte aligned for fp32 and 8-byte aligned
+ * for bf16, R 16-byte aligned (the caller's obligation: the launcher does not check it).  The GELU epilogue needs identity row maps and N % 64 == 0.
  * Replaces nn.Linear at vit_helper.py:103,155,392-396; modeling_ast.py:142-146,199,263,274;
  * modules/transformer.py:59-61,74,86-91; nn.MultiheadAttention in/out proj + linear1/2 at
  * motionformer.py:329; Conv3d vit_helper.py:436-443 and Conv2d modeling_ast.py:113-117 (after sf_im2col_*);
@@ -90,6 +93,8 @@ int sf_quantize_mxfp8(const uint16_t* x, int64_t ldx, uint8_t* q, int64_t ldq, u
 /* sf_gemm_bf16's contract (bias, exact-erf GELU, fp32 residual, bf16|fp32 output, identity row maps) on MXFP8 operands: A (M x K) / W (N x K)
  * e4m3 bytes with their stage-major scale planes sA / sW (K/128 planes, ldsa / ldsw bytes apart, 4 bytes per row, the rows of a plane PADDED to whole
  * 256-row tiles: ldsa >= ceil(M/256) * 1024, ldsw >= ceil(N/256) * 1024, 16-byte aligned - a tile's scales of one stage are fetched as one contiguous KiB); K % 128 == 0, N % 64 == 0.  v_mfma_scale_f32_32x32x64_f8f6f4, fp32 accumulate.
+ * (Accuracy: that instruction aligns the products of 8 consecutive k to the largest of them and drops what lies below 2^-13 of it before the fp32 accumulation -
+ * asserted by tests/test_gemm_gpu.py::test_mxfp8_mfma_group_alignment, bounded by tests/gemm_oracle.py mx_group_term; operands of narrow dynamic range inside a 32-block, the MX use case, are summed exactly.)
  * Replaces the nn.Linear calls at vit_helper.py:103,155,392-396 (qkv / proj / fc1 / fc2 of the DividedSpaceTimeBlocks) when the engine is built
  * with fp8 towers. */
 int sf_gemm_mxfp8(const uint8_t* A, int64_t lda, const uint8_t* sA, int64_t ldsa, const uint8_t* W, int64_t ldw, const uint8_t* sW, int64_t ldsw,
