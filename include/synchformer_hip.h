@@ -29,7 +29,7 @@ extern "C" {
 enum { SF_F32 = 0, SF_BF16 = 1, SF_F16 = 2, SF_U8 = 3, SF_I16 = 4 };   /* element types (SF_I16: PCM input of sf_resample_wave only) */
 enum { SF_EPI_NONE = 0, SF_EPI_GELU = 1 };                  /* GEMM epilogue activation */
 
-#define SF_ABI_VERSION 18
+#define SF_ABI_VERSION 19
 int sf_abi_version(void);
 const char* sf_last_error(void);
 /* "gfx950" + build flags; lets the host assert it loaded the library it built */
@@ -539,6 +539,33 @@ int sf_track_decode(const float* logits, int64_t ldl, int W, int C, float lam, i
  * one-wavefront workgroups, then one thread per window), no allocation, no host synchronisation; W == 0 launches nothing and writes nothing. */
 int sf_track_posterior(const float* logits, int64_t ldl, int W, int C, float lam, const float* grid, float* post, int64_t ldp, int32_t* cls_post,
                        float* conf_post, float* offset_mean, float* log_z, float* workspace, void* stream);
+
+/* Fixed-lag read-out of a STREAM of window logits: rows l_0, l_1, ... arrive in pushes, in order.  With path_t = sf_track_decode's cls_path and post_t =
+ * sf_track_posterior's post on rows 0 .. t (the same emission, renormalisation and tie rules), a push that brings the stream to t + 1 rows returns
+ *     cls_raw, conf_raw (n)                      per new row, as sf_track_decode gives them
+ *     cls_lag[w] = path_{w+lag}[w]               for every window w whose row w + lag arrived in this push (n_commit of them, from w0 = max(0, rows_done - lag));
+ *     conf_lag[w]                                the softmax probability of cls_lag[w] in row w.  Committed once, never revised
+ *     post_lag[w, :] = post_{w+lag}[w, :]        (posterior) with cls_post_lag, conf_post_lag, offset_mean_lag as sf_track_posterior defines them; row stride ldp >= C
+ *     cls_tail[j] = path_t[t - n_tail + 1 + j]   the path of the whole prefix on the n_tail = min(lag, t + 1) windows not yet committed, conf_tail likewise:
+ *                                                cls_tail[n_tail - 1] is the current offset; a later push may change it
+ *     log_z[0]                                   (posterior) that of the prefix 0 .. t
+ * final != 0 closes the stream: every window not yet committed is committed from the whole prefix (path_t / post_t) and the tail is empty; n may be 0 then.
+ * The counts are host arithmetic:  done(T) = max(0, T - lag);  n_commit = (final ? rows_done + n : done(rows_done + n)) - done(rows_done);
+ * n_tail = final ? 0 : min(lag, rows_done + n).  The outputs are caller-owned with at least those sizes (a block of size 0 may be null).
+ * state: one opaque device buffer per stream of sf_track_stream_bytes(C, lag, posterior) bytes, 16-byte aligned; it is read only when rows_done > 0, so a fresh
+ * stream needs no reset.  It holds the scan vectors after the last row (the Viterbi scores; posterior: the normalised forward vector and the double of subtracted
+ * maxima) and, of the last `lag` rows, the back pointers, the logits and (posterior) the forward vectors, as rings: its size does not depend on rows_done.
+ * rows_done: the rows pushed into this state so far (the caller counts; int64).  workspace: sf_track_stream_workspace_bytes(C, n, posterior) bytes, caller-owned,
+ * dead after the push.  2 <= C <= 64, 0 <= lag <= 255, n <= 2^20 rows per push, lam finite and >= 0; -1 and a message otherwise, before anything is launched.
+ * Up to four launches on the caller's stream (the row statistics, the two causal scans side by side, one wavefront per committed window plus one for the tail, the
+ * rings' update); nothing is read back, allocated or synchronised, so a push can be captured in a graph (rows_done is then part of the capture).  A push with
+ * posterior == 0 on a state sized with posterior != 0 (or the reverse) is an error of the caller: the three arguments C, lag, posterior are the state's.
+ * Non-finite rows follow the offline rules: every class written lies in [0, C). */
+int sf_track_stream_bytes(int C, int lag, int posterior);
+int sf_track_stream_workspace_bytes(int C, int n, int posterior);
+int sf_track_stream_push(void* state, int C, int lag, int posterior, int64_t rows_done, const float* logits, int64_t ldl, int n, float lam, const float* grid,
+                         int final, int32_t* cls_raw, float* conf_raw, int32_t* cls_lag, float* conf_lag, float* post_lag, int64_t ldp, int32_t* cls_post_lag,
+                         float* conf_post_lag, float* offset_mean_lag, int32_t* cls_tail, float* conf_tail, float* log_z, void* workspace, void* stream);
 
 /* ---- Ingest of a decoded recording at its native frame rate, size and sample rate: the step the reference leaves to an ffmpeg subprocess in front of its code
  * (example.py:16-53: fps=25, short side 256, even dimensions, -ar 16000), plus the centre 224 crop of RGBSpatialCrop (dataset/transforms.py:68-95).  The host

@@ -23,28 +23,53 @@
 
 // Per-window row statistics.  PATH = false: cls[w] = argmax (first maximum wins), conf[w] = its softmax probability = 1 / sum_c exp(l_c - max).
 // PATH = true: cls[w] is given (the Viterbi path), conf[w] = exp(l_cls - max) / sum.  A NaN never wins a `>` comparison, so the argmax of a row of NaNs is 0.
+// The statistics of one row, by one thread: the argmax (first maximum wins), the maximum and sum_c exp(l_c - max), in ascending c.
+__device__ __forceinline__ void track_row_stats(const float* __restrict__ row, int C, int& best, float& m, float& sum) {
+  best = 0;
+  m = row[0];
+  for (int c = 1; c < C; ++c) {
+    const float l = row[c];
+    if (l > m) { m = l; best = c; }
+  }
+  sum = 0.f;
+  for (int c = 0; c < C; ++c) sum += expf(row[c] - m);
+}
+// The softmax probability of class `c` (clamped into [0, C)) given the row's statistics.
+__device__ __forceinline__ float track_row_conf(const float* __restrict__ row, int C, int c, float m, float sum) {
+  c = c < 0 ? 0 : (c >= C ? C - 1 : c);
+  return expf(row[c] - m) / sum;
+}
+
 template <bool PATH>
 __global__ __launch_bounds__(256) void track_rows_kernel(const float* __restrict__ logits, int64_t ldl, int W, int C, int32_t* __restrict__ cls,
                                                           float* __restrict__ conf) {
   const int w = blockIdx.x * 256 + threadIdx.x;
   if (w >= W) return;
   const float* row = logits + (int64_t)w * ldl;
-  int best = 0;
-  float m = row[0];
-  for (int c = 1; c < C; ++c) {
-    const float l = row[c];
-    if (l > m) { m = l; best = c; }
-  }
-  float sum = 0.f;
-  for (int c = 0; c < C; ++c) sum += expf(row[c] - m);
+  int best;
+  float m, sum;
+  track_row_stats(row, C, best, m, sum);
   if (PATH) {
-    int c = cls[w];
-    c = c < 0 ? 0 : (c >= C ? C - 1 : c);
-    conf[w] = expf(row[c] - m) / sum;
+    conf[w] = track_row_conf(row, C, cls[w], m, sum);
   } else {
     cls[w] = best;
     conf[w] = 1.0f / sum;
   }
+}
+
+// One step of the Viterbi scan, by the whole wavefront: l = this row's logit of class c (-inf in the idle lanes), s_prev = the previous scores (LDS) ->
+// the new, renormalised score of class c; bp = the predecessor (lowest p on ties).
+__device__ __forceinline__ float track_viterbi_step(const float* s_prev, int C, int c, bool live, float lam, float l, int& bp) {
+  const float e = l - wave_max(l);
+  float best = s_prev[0] - lam * (float)c;
+  bp = 0;
+  for (int p = 1; p < C; ++p) {
+    const float cand = s_prev[p] - lam * fabsf((float)(p - c));
+    if (cand > best) { best = cand; bp = p; }
+  }
+  float s = live ? best + e : -INFINITY;
+  s -= wave_max(s);
+  return s;
 }
 
 // One wavefront.  Lane c < C owns class c; lanes >= C run along with -inf scores so that every cross-lane operation sees a full EXEC mask.
@@ -65,15 +90,8 @@ __global__ __launch_bounds__(64) void track_viterbi_kernel(const float* __restri
   for (int w = 1; w < W; ++w) {
     l = l_next;
     if (w + 1 < W) l_next = live ? logits[(int64_t)(w + 1) * ldl + c] : ninf;      // the next row's load travels under this step's scan
-    const float e = l - wave_max(l);
-    float best = s_prev[0] - lam * (float)c;
-    int bp = 0;
-    for (int p = 1; p < C; ++p) {
-      const float cand = s_prev[p] - lam * fabsf((float)(p - c));
-      if (cand > best) { best = cand; bp = p; }
-    }
-    s = live ? best + e : ninf;
-    s -= wave_max(s);
+    int bp;
+    s = track_viterbi_step(s_prev, C, c, live, lam, l, bp);
     if (live) backptr[(int64_t)w * C + c] = (uint8_t)bp;
     __syncthreads();                                               // every lane has read s_prev
     s_prev[c] = s;
@@ -156,6 +174,15 @@ __device__ __forceinline__ float fb_log_softmax(float l) {
   return l - (m + logf(wave_sum(expf(l - m))));
 }
 
+// One step of either scan, by the whole wavefront: u (LDS) = the vector the transition reads, e = this row's log-softmax (joins the lse in the forward scan only)
+// -> the new vector's entry of class c with the vector's maximum m (0 when that is not finite) subtracted.
+__device__ __forceinline__ float fb_scan_step(const float* u, int C4, int c, bool live, bool back, float lam, float e, float& m) {
+  const float r = fb_transition_lse(u, C4, c, lam);
+  float v = live ? (back ? r : r + e) : -INFINITY;
+  m = fb_finite_or_zero(wave_max(v));
+  return v - m;
+}
+
 // Block 0, the forward scan over rows 0 .. W-1:   a_0 = e[0];        a_w[c] = e[w, c] + lse_p (a_{w-1}[p] - lam |p - c|);
 // block 1, the backward scan over rows W-1 .. 0:  b_{W-1} = 0;       b_w[c] = lse_n (b_{w+1}[n] + e[w+1, n] - lam |n - c|).
 // One wavefront each, lane c = class c, the vector the transition reads (a_{w-1}, or b_{w+1} + e[w+1]) in LDS, the next row's load under the current step.
@@ -187,10 +214,7 @@ __global__ __launch_bounds__(64) void track_fb_scan_kernel(const float* __restri
     const float l = l_next;
     if (k + 1 < W) l_next = live ? logits[(row + step) * ldl + c] : ninf;
     e = fb_log_softmax(l);
-    const float r = fb_transition_lse(s_u, C4, c, lam);
-    v = live ? (back ? r : r + e) : ninf;
-    m = fb_finite_or_zero(wave_max(v));
-    v -= m;
+    v = fb_scan_step(s_u, C4, c, live, back, lam, e, m);
     shifted += (double)m;
     if (live) out[row * C + c] = v;
     __syncthreads();                                               // every lane has read s_u
@@ -203,6 +227,26 @@ __global__ __launch_bounds__(64) void track_fb_scan_kernel(const float* __restri
   }
 }
 
+// One window, by one thread: prow[c] = exp(a[c] + b[c] - lse_c (a + b)); best = its argmax (first maximum wins), pbest its value; mean = sum_c prow[c] grid[c].
+__device__ __forceinline__ void fb_combine_row(const float* a, const float* b, int C, const float* __restrict__ grid, float* __restrict__ prow, int& best,
+                                               float& pbest, float& mean) {
+  float m = -INFINITY;
+  for (int c = 0; c < C; ++c) m = fmaxf(m, a[c] + b[c]);
+  m = fb_finite_or_zero(m);
+  float sum = 0.f;
+  for (int c = 0; c < C; ++c) sum += expf(a[c] + b[c] - m);
+  const float lse = fb_finite_or_zero(m + logf(sum));
+  best = 0;
+  pbest = 0.f;
+  mean = 0.f;
+  for (int c = 0; c < C; ++c) {
+    const float p = expf(a[c] + b[c] - lse);
+    prow[c] = p;
+    mean += p * grid[c];
+    if (c == 0 || p > pbest) { pbest = p; best = c; }
+  }
+}
+
 // One thread per window:  s = a_w + b_w;  post[w, c] = exp(s[c] - lse_c s);  cls_post = argmax_c post (first maximum wins; a NaN never wins `>`), conf_post its
 // value;  offset_mean = sum_c post[w, c] grid[c] in ascending c.
 __global__ __launch_bounds__(256) void track_fb_combine_kernel(const float* __restrict__ ws, int W, int C, const float* __restrict__ grid, float* __restrict__ post,
@@ -211,22 +255,9 @@ __global__ __launch_bounds__(256) void track_fb_combine_kernel(const float* __re
   const int w = blockIdx.x * 256 + threadIdx.x;
   if (w >= W) return;
   const float* a = ws + (int64_t)w * C;
-  const float* b = a + (int64_t)W * C;
-  float m = -INFINITY;
-  for (int c = 0; c < C; ++c) m = fmaxf(m, a[c] + b[c]);
-  m = fb_finite_or_zero(m);
-  float sum = 0.f;
-  for (int c = 0; c < C; ++c) sum += expf(a[c] + b[c] - m);
-  const float lse = fb_finite_or_zero(m + logf(sum));
-  float* prow = post + (int64_t)w * ldp;
-  int best = 0;
-  float pbest = 0.f, mean = 0.f;
-  for (int c = 0; c < C; ++c) {
-    const float p = expf(a[c] + b[c] - lse);
-    prow[c] = p;
-    mean += p * grid[c];
-    if (c == 0 || p > pbest) { pbest = p; best = c; }
-  }
+  int best;
+  float pbest, mean;
+  fb_combine_row(a, a + (int64_t)W * C, C, grid, post + (int64_t)w * ldp, best, pbest, mean);
   cls_post[w] = best;
   conf_post[w] = pbest;
   offset_mean[w] = mean;
@@ -247,5 +278,315 @@ extern "C" int sf_track_posterior(const float* logits, int64_t ldl, int W, int C
   hipLaunchKernelGGL(track_fb_combine_kernel, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, s, (const float*)workspace, W, C, grid, post, ldp, cls_post,
                      conf_post, offset_mean);
   SF_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- fixed-lag read-out of a stream (sf_track_stream_push) -------------------------------------------------------------------------------------------------
+// Rows arrive in pushes; window w is committed by the push that delivers row w + lag, as path_{w+lag}[w] / post_{w+lag}[w] (the offline read-outs of the prefix
+// 0 .. w + lag), and never revised.  Both scans are causal, so what a push needs of the past is the scan vectors after the last row (s; with the posterior a and
+// the double of subtracted maxima) and, of the last `lag` rows, the back pointers, the logits (conf_lag, and the backward recursion's log-softmax, which is
+// recomputed from them as the offline scan does) and - posterior - the normalised a.  The state buffer holds exactly that, the per-row parts as rings (row r in
+// slot r % lag); its size does not depend on how many rows have passed.  A push of n rows is three or four launches on the caller's stream:
+//   1. track_rows_kernel<false>:     cls_raw / conf_raw of the new rows (the offline kernel);
+//   2. track_stream_scan_kernel:     one wavefront per scan, side by side (block 0 Viterbi, block 1 forward): loads the carried vector, runs the n rows with the next
+//                                    row's load under the current step, writes back pointers / a and every row's end state (argmax s_r) into the push's workspace,
+//                                    stores the carried vectors;
+//   3. track_stream_readout_kernel:  one wavefront per window that becomes committed: its own backtrace from the end state of row w + lag (eight rows of back
+//                                    pointers per round, wave-uniform shuffles), with the posterior its own backward recursion over rows w + lag .. w + 1 and the
+//                                    combine of row w; one more wavefront backtraces the tail from the last row.  The windows are independent: a catch-up push of
+//                                    1000 rows spreads over the chip instead of running n * lag dependent steps in one wavefront;
+//   4. track_stream_keep_kernel:     copies the last min(lag, n) new rows into the rings (after 3, which still reads the slots they replace).
+// Rows before the push live in the rings, rows of the push in the caller's logits and the workspace: TrackStreamRows resolves a row index to either.
+struct TrackStreamRows {
+  const float* lg_new;  int64_t ldl;      // the push's logits
+  const uint8_t* bp_new;                  // workspace: back pointers (n, C)
+  const float* a_new;                     // workspace: normalised a (n, C); posterior only
+  const int32_t* end_new;                 // workspace: argmax s_r per new row
+  const float* lg_ring;  const uint8_t* bp_ring;  const float* a_ring;      // state: (lag, C) each
+  const int32_t* end_last;                // state: argmax s of the last row pushed
+  int64_t t_old;                          // rows before this push
+  int lag, C;
+  __device__ __forceinline__ const float* logits(int64_t r) const { return r >= t_old ? lg_new + (r - t_old) * ldl : lg_ring + (r % lag) * C; }
+  __device__ __forceinline__ const uint8_t* backptr(int64_t r) const { return r >= t_old ? bp_new + (r - t_old) * C : bp_ring + (r % lag) * C; }
+  __device__ __forceinline__ const float* a(int64_t r) const { return r >= t_old ? a_new + (r - t_old) * C : a_ring + (r % lag) * C; }
+  __device__ __forceinline__ int end(int64_t r) const { return r >= t_old ? end_new[r - t_old] : end_last[0]; }
+};
+
+// the state buffer: [double shifted][int32 end_last, pad][s: 64 floats][posterior: a: 64 floats][logits ring][posterior: a ring][back pointer ring]
+struct TrackStreamLayout {
+  int64_t s, a, lg_ring, a_ring, bp_ring, total;
+  __host__ __device__ TrackStreamLayout(int C, int lag, bool posterior) {
+    s = 16;
+    a = s + TRACK_MAX_C * 4;
+    lg_ring = a + (posterior ? TRACK_MAX_C * 4 : 0);
+    a_ring = lg_ring + (int64_t)lag * C * 4;
+    bp_ring = a_ring + (posterior ? (int64_t)lag * C * 4 : 0);
+    total = (bp_ring + (int64_t)lag * C + 15) & ~(int64_t)15;
+  }
+};
+
+// The end state of a row: the lowest class whose renormalised score is the maximum, 0.  (No such lane - NaN scores - gives class 0, as a NaN never wins `>`.)
+__device__ __forceinline__ int track_wave_end_state(float s, bool live) {
+  const unsigned long long hit = __ballot(live && s == 0.f);
+  return hit ? __ffsll((long long)hit) - 1 : 0;
+}
+
+__global__ __launch_bounds__(64) void track_stream_scan_kernel(const float* __restrict__ logits, int64_t ldl, int n, int C, float lam, int64_t t_old,
+                                                                unsigned char* __restrict__ state, int lag, int posterior, uint8_t* __restrict__ bp_new,
+                                                                float* __restrict__ a_new, int32_t* __restrict__ end_new, float* __restrict__ log_z) {
+  __shared__ __attribute__((aligned(16))) float s_u[TRACK_MAX_C];
+  const TrackStreamLayout lay(C, lag, posterior != 0);
+  const int c = threadIdx.x;
+  const bool live = c < C;
+  const bool fwd = blockIdx.x == 1;                               // wave-uniform
+  const int C4 = (C + 3) & ~3;
+  const float ninf = -INFINITY;
+  float* carried = reinterpret_cast<float*>(state + (fwd ? lay.a : lay.s));
+  double* st_shifted = reinterpret_cast<double*>(state);
+  int32_t* st_end = reinterpret_cast<int32_t*>(state + 8);
+  double shifted = (fwd && t_old > 0) ? st_shifted[0] : 0.0;
+  float v = (t_old > 0 && live) ? carried[c] : ninf;
+  int k = 0;
+  float l_next = (live && n > 0) ? logits[c] : ninf;
+  if (t_old == 0 && n > 0) {                                       // the first row of the stream: s_0 = e[0] / a_0 = e[0], as the offline scans begin
+    const float l = l_next;
+    if (n > 1) l_next = live ? logits[ldl + c] : ninf;
+    if (fwd) {
+      v = fb_log_softmax(l);
+      const float m = fb_finite_or_zero(wave_max(v));
+      v -= m;
+      shifted += (double)m;
+      if (live) a_new[c] = v;
+    } else {
+      v = l - wave_max(l);
+      if (live) bp_new[c] = 0;                                     // never followed: the backtrace stops at row 1
+      const int end = track_wave_end_state(v, live);               // (the ballot needs the whole wavefront)
+      if (c == 0) end_new[0] = end;
+    }
+    k = 1;
+  }
+  s_u[c] = v;
+  __syncthreads();
+  for (; k < n; ++k) {
+    const float l = l_next;
+    if (k + 1 < n) l_next = live ? logits[(int64_t)(k + 1) * ldl + c] : ninf;       // the next row's load travels under this step
+    if (fwd) {
+      float m;
+      v = fb_scan_step(s_u, C4, c, live, false, lam, fb_log_softmax(l), m);
+      shifted += (double)m;
+      if (live) a_new[(int64_t)k * C + c] = v;
+    } else {
+      int bp;
+      v = track_viterbi_step(s_u, C, c, live, lam, l, bp);
+      if (live) bp_new[(int64_t)k * C + c] = (uint8_t)bp;
+      const int end = track_wave_end_state(v, live);
+      if (c == 0) end_new[k] = end;
+    }
+    __syncthreads();                                               // every lane has read s_u
+    s_u[c] = v;
+    __syncthreads();
+  }
+  if (n > 0) {
+    const int end = track_wave_end_state(v, live);
+    if (live) carried[c] = v;
+    if (c == 0) {
+      if (fwd) st_shifted[0] = shifted;
+      else st_end[0] = end;
+    }
+  }
+  if (fwd) {
+    const float z = logf(wave_sum(expf(v)));                       // the normalised a of the last row: maximum 0
+    if (c == 0) log_z[0] = (float)(shifted + (double)z);
+  }
+}
+
+// Follows the back pointers of rows R .. w + 1 from class `cur` (the class at row R) -> the class at row w.  Lane c loads backptr[r, c] of eight rows at a time, the
+// chain itself is eight wave-uniform shuffles.  KEEP: tail[r - w] = the class at row r, for every r in [w, R] (LDS, written by lane 0).
+template <bool KEEP>
+__device__ __forceinline__ int track_stream_backtrace(const TrackStreamRows& rows, int64_t R, int64_t w, int cur, int c, bool live, int* tail) {
+  const int C = rows.C;
+  for (int64_t r0 = R; r0 > w; r0 -= 8) {
+    int b[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) b[j] = (live && r0 - j > w) ? (int)rows.backptr(r0 - j)[c] : 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (r0 - j > w) {                                            // wave-uniform
+        if (KEEP && c == 0) tail[r0 - j - w] = cur;
+        const int p = __shfl(b[j], cur, 64);
+        cur = p < C ? p : C - 1;
+      }
+    }
+  }
+  if (KEEP && c == 0) tail[0] = cur;
+  return cur;
+}
+
+// Block i < n_commit: window w = w0 + i, read from the prefix that ends at row R = min(w + lag, t_last).  Block n_commit (if n_tail > 0): the tail, the path of the
+// whole prefix on the last n_tail rows.
+template <bool POST>
+__global__ __launch_bounds__(64) void track_stream_readout_kernel(TrackStreamRows rows, float lam, const float* __restrict__ grid, int64_t w0, int n_commit, int n_tail,
+                                                                   int64_t t_last, int32_t* __restrict__ cls_lag, float* __restrict__ conf_lag,
+                                                                   float* __restrict__ post_lag, int64_t ldp, int32_t* __restrict__ cls_post_lag,
+                                                                   float* __restrict__ conf_post_lag, float* __restrict__ offset_mean_lag,
+                                                                   int32_t* __restrict__ cls_tail, float* __restrict__ conf_tail) {
+  __shared__ __attribute__((aligned(16))) float s_u[TRACK_MAX_C];
+  __shared__ float s_b[TRACK_MAX_C];
+  __shared__ int s_tail[256];
+  const int c = threadIdx.x;
+  const int C = rows.C;
+  const bool live = c < C;
+  if ((int)blockIdx.x == n_commit) {                               // the tail
+    const int64_t w = t_last - (n_tail - 1);
+    int cur = rows.end(t_last);
+    cur = cur < 0 ? 0 : (cur >= C ? C - 1 : cur);
+    track_stream_backtrace<true>(rows, t_last, w, cur, c, live, s_tail);
+    __syncthreads();
+    for (int i = c; i < n_tail; i += 64) {
+      const float* row = rows.logits(w + i);
+      int best;
+      float m, sum;
+      track_row_stats(row, C, best, m, sum);
+      cls_tail[i] = s_tail[i];
+      conf_tail[i] = track_row_conf(row, C, s_tail[i], m, sum);
+    }
+    return;
+  }
+  const int i = blockIdx.x;
+  const int64_t w = w0 + i;
+  const int64_t R = w + rows.lag < t_last ? w + rows.lag : t_last;
+  int cur = rows.end(R);
+  cur = cur < 0 ? 0 : (cur >= C ? C - 1 : cur);
+  cur = track_stream_backtrace<false>(rows, R, w, cur, c, live, nullptr);
+  if (c == 0) {
+    const float* row = rows.logits(w);
+    int best;
+    float m, sum;
+    track_row_stats(row, C, best, m, sum);
+    cls_lag[i] = cur;
+    conf_lag[i] = track_row_conf(row, C, cur, m, sum);
+  }
+  if (POST) {
+    // the backward scan of the prefix 0 .. R, from its end down to row w:  b_R = 0;  b_r[c] = lse_n (b_{r+1}[n] + e[r+1, n] - lam |n - c|), renormalised per step
+    const int C4 = (C + 3) & ~3;
+    const float ninf = -INFINITY;
+    float v = live ? 0.f : ninf;
+    float l_next = live ? rows.logits(R)[c] : ninf;
+    for (int64_t r = R; r > w; --r) {                              // b_{r-1} from b_r and row r
+      const float l = l_next;
+      if (r - 1 > w) l_next = live ? rows.logits(r - 1)[c] : ninf;
+      const float e = fb_log_softmax(l);
+      __syncthreads();                                             // every lane has read s_u
+      s_u[c] = v + e;
+      __syncthreads();
+      float m;
+      v = fb_scan_step(s_u, C4, c, live, true, lam, 0.f, m);
+    }
+    s_b[c] = v;
+    __syncthreads();
+    if (c == 0) {
+      int best;
+      float pbest, mean;
+      fb_combine_row(rows.a(w), s_b, C, grid, post_lag + (int64_t)i * ldp, best, pbest, mean);
+      cls_post_lag[i] = best;
+      conf_post_lag[i] = pbest;
+      offset_mean_lag[i] = mean;
+    }
+  }
+}
+
+// Block j: new row k = k0 + j (row t_old + k of the stream) into slot (t_old + k) % lag of the rings.
+__global__ __launch_bounds__(64) void track_stream_keep_kernel(const float* __restrict__ logits, int64_t ldl, const uint8_t* __restrict__ bp_new,
+                                                                const float* __restrict__ a_new, int k0, int64_t t_old, int C, int lag, int posterior,
+                                                                unsigned char* __restrict__ state) {
+  const TrackStreamLayout lay(C, lag, posterior != 0);
+  const int c = threadIdx.x;
+  if (c >= C) return;
+  const int64_t k = k0 + (int64_t)blockIdx.x;
+  const int64_t slot = ((t_old + k) % lag) * C + c;
+  reinterpret_cast<float*>(state + lay.lg_ring)[slot] = logits[k * ldl + c];
+  (state + lay.bp_ring)[slot] = bp_new[k * C + c];
+  if (posterior) reinterpret_cast<float*>(state + lay.a_ring)[slot] = a_new[k * C + c];
+}
+
+static bool track_stream_shape_ok(const char* who, int C, int lag) {
+  if (C < 2 || C > TRACK_MAX_C) { sf_set_error("%s: C = %d classes out of range (2 .. %d: one lane per class)", who, C, TRACK_MAX_C); return false; }
+  if (lag < 0 || lag > 255) { sf_set_error("%s: lag = %d windows out of range (0 .. 255)", who, lag); return false; }
+  return true;
+}
+
+extern "C" int sf_track_stream_bytes(int C, int lag, int posterior) {
+  if (!track_stream_shape_ok("sf_track_stream_bytes", C, lag)) return -1;
+  return (int)TrackStreamLayout(C, lag, posterior != 0).total;     // at most 16 + 512 + 255 * 64 * 9
+}
+
+// the workspace of a push: [posterior: a (n, C) fp32][end (n) int32][back pointers (n, C) bytes]
+#define TRACK_STREAM_MAX_PUSH (1 << 20)
+extern "C" int sf_track_stream_workspace_bytes(int C, int n, int posterior) {
+  SF_CHECK_ARG(C >= 2 && C <= TRACK_MAX_C, "sf_track_stream_workspace_bytes: C = %d classes out of range (2 .. %d)", C, TRACK_MAX_C);
+  SF_CHECK_ARG(n >= 0 && n <= TRACK_STREAM_MAX_PUSH, "sf_track_stream_workspace_bytes: n = %d rows in one push (0 .. %d)", n, TRACK_STREAM_MAX_PUSH);
+  return (int)(((posterior ? (int64_t)n * C * 4 : 0) + (int64_t)n * 4 + (int64_t)n * C + 15) & ~(int64_t)15);      // at most 2^20 * 324
+}
+
+extern "C" int sf_track_stream_push(void* state, int C, int lag, int posterior, int64_t rows_done, const float* logits, int64_t ldl, int n, float lam,
+                                    const float* grid, int final, int32_t* cls_raw, float* conf_raw, int32_t* cls_lag, float* conf_lag, float* post_lag, int64_t ldp,
+                                    int32_t* cls_post_lag, float* conf_post_lag, float* offset_mean_lag, int32_t* cls_tail, float* conf_tail, float* log_z,
+                                    void* workspace, void* stream) {
+  if (!track_stream_shape_ok("sf_track_stream_push", C, lag)) return -1;
+  SF_CHECK_ARG(state, "sf_track_stream_push: null state");
+  SF_CHECK_ARG(n >= 0 && n <= TRACK_STREAM_MAX_PUSH, "sf_track_stream_push: n = %d rows in one push (0 .. %d: split a longer catch-up)", n, TRACK_STREAM_MAX_PUSH);
+  SF_CHECK_ARG(rows_done >= 0 && rows_done <= (INT64_MAX >> 1), "sf_track_stream_push: %lld rows pushed so far", (long long)rows_done);
+  SF_CHECK_ARG(std::isfinite(lam) && lam >= 0.f, "sf_track_stream_push: lam must be finite and >= 0 (the cost of a class change)");
+  SF_CHECK_ARG(n == 0 || ldl >= C, "sf_track_stream_push: row stride ldl = %lld below C = %d", (long long)ldl, C);
+  const int64_t t_old = rows_done, t_new = rows_done + n;
+  const int64_t done_old = t_old > lag ? t_old - lag : 0;                                   // windows committed before this push
+  const int64_t done_new = final ? t_new : (t_new > lag ? t_new - lag : 0);
+  const int64_t n_commit = done_new - done_old, n_tail = t_new - done_new;
+  if (t_new == 0) return 0;
+  SF_CHECK_ARG(n == 0 || (logits && cls_raw && conf_raw && workspace), "sf_track_stream_push: null pointer (new rows)");
+  SF_CHECK_ARG(n_commit == 0 || (cls_lag && conf_lag), "sf_track_stream_push: null pointer (committed block)");
+  SF_CHECK_ARG(n_tail == 0 || (cls_tail && conf_tail), "sf_track_stream_push: null pointer (tail)");
+  if (posterior) {
+    SF_CHECK_ARG(log_z, "sf_track_stream_push: null log_z");
+    SF_CHECK_ARG(n_commit == 0 || (grid && post_lag && cls_post_lag && conf_post_lag && offset_mean_lag && ldp >= C),
+                 "sf_track_stream_push: null pointer or post row stride ldp = %lld below C = %d (posterior block)", (long long)ldp, C);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const TrackStreamLayout lay(C, lag, posterior != 0);
+  unsigned char* st = static_cast<unsigned char*>(state);
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  float* a_new = reinterpret_cast<float*>(ws);
+  int32_t* end_new = reinterpret_cast<int32_t*>(ws + (posterior ? (int64_t)n * C * 4 : 0));
+  uint8_t* bp_new = reinterpret_cast<uint8_t*>(end_new + n);
+  if (n > 0) {
+    hipLaunchKernelGGL(track_rows_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, logits, ldl, n, C, cls_raw, conf_raw);
+    SF_LAUNCH_CHECK();
+  }
+  if (n > 0 || posterior) {                                        // (n == 0 with the posterior: log_z of the prefix so far, from the carried a)
+    hipLaunchKernelGGL(track_stream_scan_kernel, dim3(posterior ? 2 : 1), dim3(64), 0, s, logits, ldl, n, C, lam, t_old, st, lag, posterior, bp_new, a_new, end_new,
+                       log_z);
+    SF_LAUNCH_CHECK();
+  }
+  if (n_commit + n_tail > 0) {
+    TrackStreamRows rows;
+    rows.lg_new = logits;  rows.ldl = ldl;  rows.bp_new = bp_new;  rows.a_new = a_new;  rows.end_new = end_new;
+    rows.lg_ring = reinterpret_cast<const float*>(st + lay.lg_ring);  rows.bp_ring = st + lay.bp_ring;  rows.a_ring = reinterpret_cast<const float*>(st + lay.a_ring);
+    rows.end_last = reinterpret_cast<const int32_t*>(st + 8);
+    rows.t_old = t_old;  rows.lag = lag;  rows.C = C;
+    const dim3 g((unsigned)(n_commit + (n_tail > 0 ? 1 : 0)));
+    if (posterior)
+      hipLaunchKernelGGL(track_stream_readout_kernel<true>, g, dim3(64), 0, s, rows, lam, grid, done_old, (int)n_commit, (int)n_tail, t_new - 1, cls_lag, conf_lag, post_lag,
+                         ldp, cls_post_lag, conf_post_lag, offset_mean_lag, cls_tail, conf_tail);
+    else
+      hipLaunchKernelGGL(track_stream_readout_kernel<false>, g, dim3(64), 0, s, rows, lam, grid, done_old, (int)n_commit, (int)n_tail, t_new - 1, cls_lag, conf_lag, post_lag,
+                         ldp, cls_post_lag, conf_post_lag, offset_mean_lag, cls_tail, conf_tail);
+    SF_LAUNCH_CHECK();
+  }
+  const int keep = n < lag ? n : lag;
+  if (keep > 0) {
+    hipLaunchKernelGGL(track_stream_keep_kernel, dim3((unsigned)keep), dim3(64), 0, s, logits, ldl, (const uint8_t*)bp_new, (const float*)a_new, n - keep, t_old, C, lag,
+                       posterior, st);
+    SF_LAUNCH_CHECK();
+  }
   return 0;
 }

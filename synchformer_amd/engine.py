@@ -795,19 +795,30 @@ class SynchformerEngine:
         chunk = self.seg_chunk if seg_chunk is None else int(seg_chunk)
         if chunk < 1:
             raise ValueError(f'extract_recording: seg_chunk = {chunk}')
+        return self.extract_segments_from(frame_fn, wave, mel, 0, N, chunk)
+
+    def extract_segments_from(self, frame_fn, wave16k: torch.Tensor, mel, s_first: int, n_seg: int, seg_chunk: Optional[int] = None, sample0: int = 0):
+        """Segments [s_first, s_first + n_seg) of the anchored grid through both towers, at most `seg_chunk` per launch group -> (vfeat (n_seg, 8, 768), afeat
+        (n_seg, 6, 768)) fp32 on the device.  No minimum: a stream (track.OffsetStream) runs the few segments a push completes.  frame_fn(f0, f1) as in
+        extract_recording_from, in frames of the recording; wave16k[k] is sample sample0 + k of the recording (a stream holds only the samples later segments read)."""
+        from .frontend import recording_geometry
+        chunk = self.seg_chunk if seg_chunk is None else int(seg_chunk)
+        if chunk < 1 or n_seg < 1 or s_first < 0:
+            raise ValueError(f'extract_segments_from: seg_chunk = {chunk}, segments [{s_first}, {s_first + n_seg})')
+        g = recording_geometry(0, 0)
         vs, vz, as_, az = g['v_stride'], g['v_size'], g['a_stride'], g['a_size']
         vbank = abank = None
-        for s0 in range(0, N, chunk):
-            n = min(chunk, N - s0)
+        for s0 in range(s_first, s_first + n_seg, chunk):
+            n = min(chunk, s_first + n_seg - s0)
             f = frame_fn(vs * s0, vs * (s0 + n - 1) + vz)
-            w = wave[as_ * s0:as_ * (s0 + n - 1) + az].to(self.dev, torch.float32, non_blocking=True)
+            w = wave16k[as_ * s0 - sample0:as_ * (s0 + n - 1) + az - sample0].to(self.dev, torch.float32, non_blocking=True)
             aud = mel.segments(w[None], 0, as_, n, az)
             vf, af = self.both_towers(lambda: self.extract_vfeats_clips(f[None], 0, vs, n), aud)
             if vbank is None:
-                vbank = torch.empty(N, *vf.shape[2:], device=self.dev, dtype=torch.float32)
-                abank = torch.empty(N, *af.shape[2:], device=self.dev, dtype=torch.float32)
-            vbank[s0:s0 + n].copy_(vf[0])
-            abank[s0:s0 + n].copy_(af[0])
+                vbank = torch.empty(n_seg, *vf.shape[2:], device=self.dev, dtype=torch.float32)
+                abank = torch.empty(n_seg, *af.shape[2:], device=self.dev, dtype=torch.float32)
+            vbank[s0 - s_first:s0 - s_first + n].copy_(vf[0])
+            abank[s0 - s_first:s0 - s_first + n].copy_(af[0])
         return vbank, abank
 
     def sync_windows(self, vbank: torch.Tensor, abank: torch.Tensor, hop: int = 1, win_chunk: int = 256, n_window: int = 14) -> torch.Tensor:

@@ -63,6 +63,26 @@ def recording_geometry(v_len_frames: int, a_len_frames: int, hop_segments: int =
                 a_size=a_size)
 
 
+def stream_geometry(v_len_frames: int, a_len_frames: int, segments_done: int, hop_segments: int = 1, **segment_kw) -> dict:
+    """recording_geometry for a recording that is still arriving (track.OffsetStream): given the frames and samples pushed SO FAR and the segments already
+    through the towers, which segments and windows are new and which prefixes of the carried buffers nothing will read again.  Pure host arithmetic on the
+    same anchored grid, so the windows of a stream are the windows of the finished recording, whatever the pushes.
+        n_segments, n_windows          of the prefix (recording_geometry's)
+        new_segments = (s0, s1)        segments [s0, s1) = [segments_done, n_segments) can run now
+        new_windows  = (w0, w1)        windows whose last segment is among them: w0 = the windows `segments_done` segments held, w1 = n_windows
+        frames_from, samples_from      the first frame / sample a later segment reads: v_stride * n_segments, a_stride * n_segments
+        features_from                  the first segment a later window reads: hop * n_windows, at most n_segments (nothing is held for a window that starts
+                                       beyond the segments so far).  So at most n_window - 1 + hop - 1 segments (13 at hop 1) stay held, v_size - 1 = 15 frames of
+                                       a video that is not ahead of the audio, a_size - 1 samples of an audio that is not ahead of the video."""
+    g = recording_geometry(v_len_frames, a_len_frames, hop_segments, **segment_kw)
+    if not 0 <= segments_done <= g['n_segments']:
+        raise ValueError(f"stream_geometry: {segments_done} segments done, the prefix holds {g['n_segments']}")
+    n_seg, n_win, nw = g['n_segments'], g['n_windows'], g['n_window']
+    w_done = (segments_done - nw) // hop_segments + 1 if segments_done >= nw else 0
+    return dict(g, new_segments=(segments_done, n_seg), new_windows=(w_done, n_win), frames_from=g['v_stride'] * n_seg, samples_from=g['a_stride'] * n_seg,
+                features_from=min(hop_segments * n_win, n_seg))
+
+
 class MelFrontend:
     def __init__(self, device, sample_rate=16000, n_mels=128, pad_to=66, mean=AST_MEAN, std=AST_STD):
         self.dev = torch.device(device)

@@ -33,7 +33,7 @@ no tone mapping), double-buffered uploads, several recordings per call.
 """
 import math
 from fractions import Fraction
-from typing import Tuple
+from typing import Optional, Tuple
 
 import torch
 
@@ -269,17 +269,20 @@ class RecordingIngest:
         table = self.frame_table(raw.shape[0])
         if not 0 <= j0 <= j1 <= table.numel():
             raise ValueError(f'frames [{j0}, {j1}) of {table.numel()}')
-        from . import ops
         if j1 == j0:
             return torch.empty(0, 3, CROP, CROP, device=self.dev, dtype=torch.uint8)
         t = table[j0:j1]
         lo, hi = int(t[0]), int(t[-1]) + 1                                       # the table is non-decreasing
-        src = raw[lo:hi].to(self.dev, non_blocking=True)
+        return self._resize(raw[lo:hi].to(self.dev, non_blocking=True), t - lo)
+
+    def _resize(self, src: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+        """Output frame j = source frame src[t[j]] (src on the device, t int32 on the host), resized and cropped."""
+        from . import ops
         if self.pix_fmt != 'rgb24':
             op = ops.ingest_video_yuv16 if self.pix_fmt in PIX_FMTS_16 else ops.ingest_video_yuv
-            return op(src, self.pix_fmt, (t - lo).to(self.dev, non_blocking=True), self.y_first, self.y_w, self.x_first, self.x_w, self.cy_first, self.cy_w,
+            return op(src, self.pix_fmt, t.to(self.dev, non_blocking=True), self.y_first, self.y_w, self.x_first, self.x_w, self.cy_first, self.cy_w,
                       self.cx_first, self.cx_w, self.csc)
-        return ops.ingest_video(src, self.channels_last, (t - lo).to(self.dev, non_blocking=True), self.y_first, self.y_w, self.x_first, self.x_w)
+        return ops.ingest_video(src, self.channels_last, t.to(self.dev, non_blocking=True), self.y_first, self.y_w, self.x_first, self.x_w)
 
     def wave(self, raw_wave: torch.Tensor) -> torch.Tensor:
         """raw_wave (n,) or (ch, n), fp32 or int16 PCM, device or host -> mono fp32 16 kHz (n16k,) on the device.  A mono fp32 wave at 16 kHz is returned as it is."""
@@ -290,3 +293,114 @@ class RecordingIngest:
             return x.reshape(-1)
         from . import ops
         return ops.resample_wave(x, self.kernel, self.o, self.width)
+
+    def stream(self) -> 'IngestStream':
+        """The same conversion for a recording that is still arriving: see IngestStream."""
+        return IngestStream(self)
+
+
+def fps_final_slots(n_in: int, fps_in, fps_out=25) -> int:
+    """How many output slots of fps_frame_table are FINAL once n_in source frames have been seen: slot j is final when a source frame with p_i > j has arrived,
+    so slots [0, p_{n_in - 1}) are (the table of a prefix equals the table of the whole recording except in its last slot).  0 for n_in = 0."""
+    if n_in <= 0:
+        return 0
+    return math.floor((n_in - 1) * (_fraction(fps_out) / _fraction(fps_in)) + Fraction(1, 2))
+
+
+def fps_slot_source(j: int, fps_in, fps_out=25) -> int:
+    """The source frame of a final slot j: max{i : floor(i r + 1/2) <= j} = ceil((j + 1/2) / r) - 1, exact rational arithmetic (r = fps_out / fps_in)."""
+    return math.ceil((j + Fraction(1, 2)) / (_fraction(fps_out) / _fraction(fps_in))) - 1
+
+
+def resample_stream_plan(emitted: int, seen: int, o: int, width: int, n: int, final: bool = False):
+    """The resampler of a stream: `emitted` output samples are out (a multiple of n), `seen` raw samples have arrived.  -> (c0, k0, k1, hold): run the offline
+    resampler on raw[c0:seen] and take its outputs [k0, k1): they are the recording's outputs [emitted, emitted + k1 - k0); afterwards the raw samples before
+    `hold` are never read again.  Output p + n q reads raw samples [q o - width, q o + width + o): c0 is a multiple of o at most (emitted / n) o - width (0 while
+    the filter still reaches before the recording: the zero padding there is the offline one), so the chunk's polyphase grid is the recording's, and an output
+    is taken only when all its taps have arrived - or at the end (final), where the offline call zero-pads on the right and cuts at ceil(n seen / o)."""
+    q_next = emitted // n
+    c0 = max(0, (q_next * o - width) // o) * o
+    if final:
+        k1 = -(-n * seen // o) - n * (c0 // o)
+    else:
+        q_end = max(q_next, (seen - width - o) // o + 1 if seen >= width + o else 0)      # groups q < q_end have every tap inside [0, seen)
+        k1 = n * q_end - n * (c0 // o)
+    k0 = emitted - n * (c0 // o)
+    done = emitted + k1 - k0
+    return c0, k0, k1, max(0, ((done // n) * o - width) // o) * o
+
+
+class IngestStream:
+    """RecordingIngest for a feed: push(raw_frames, raw_wave) and flush() return the 25 fps frames (uint8 (t, 3, 224, 224)) and the 16 kHz samples (fp32 (m,)) that
+    have become FINAL, on the device; concatenated over all calls they are bit-equal to ingest.frames(raw_all, 0, n_frames) and ingest.wave(raw_all), for every
+    chunking.  Host logic over the same kernels: the last source frame is held until a later one shows which slots it fills (flush emits its slot), the raw
+    samples are held from the resampler's left context on (resample_stream_plan).  Either argument may be empty (or None)."""
+
+    def __init__(self, ingest: RecordingIngest):
+        self.ing = ingest
+        self.n_src = self.slots_out = 0          # source frames seen, 25 fps frames emitted
+        self._last = None                        # the last source frame, on the device (1, ...)
+        self.raw_seen = self.samples_out = 0     # raw samples seen, 16 kHz samples emitted
+        self._raw = None                         # raw samples [self._raw0, raw_seen) on the device, (ch, m)
+        self._raw0 = 0
+        self.closed = False
+
+    @property
+    def held(self) -> dict:
+        return dict(frames=0 if self._last is None else 1, samples=0 if self._raw is None else int(self._raw.shape[1]))
+
+    def _passthrough(self, x: torch.Tensor) -> bool:
+        return self.ing.rate_in == 16000 and x.dtype == torch.float32 and x.shape[0] == 1
+
+    def push(self, raw_frames: Optional[torch.Tensor] = None, raw_wave: Optional[torch.Tensor] = None):
+        if self.closed:
+            raise RuntimeError('IngestStream.push: the stream was closed by flush()')
+        return self._frames(raw_frames, False), self._wave(raw_wave, False)
+
+    def flush(self):
+        if self.closed:
+            raise RuntimeError('IngestStream.flush: the stream is closed')
+        self.closed = True
+        return self._frames(None, True), self._wave(None, True)
+
+    def _frames(self, raw: Optional[torch.Tensor], final: bool) -> torch.Tensor:
+        ing = self.ing
+        src, base = self._last, self.n_src - 1                                    # src[k] = source frame base + k
+        if raw is not None and raw.shape[0]:
+            ing._check_frames(raw)
+            new = raw.to(ing.dev, non_blocking=True)
+            new = new.view(torch.int16) if new.dtype == torch.uint16 else new     # (the same bits; the kernels read either)
+            src, base = (new, self.n_src) if src is None else (torch.cat([src, new]), base)
+            self.n_src += int(raw.shape[0])
+        j1 = fps_final_slots(self.n_src, ing.fps_in) + (1 if final and self.n_src else 0)
+        j0, self.slots_out = self.slots_out, max(j1, self.slots_out)
+        if src is not None:
+            self._last = src[-1:].clone() if not final else None
+        if j1 <= j0:
+            return torch.empty(0, 3, CROP, CROP, device=ing.dev, dtype=torch.uint8)
+        t = torch.tensor([min(fps_slot_source(j, ing.fps_in), self.n_src - 1) - base for j in range(j0, j1)], dtype=torch.int32)
+        return ing._resize(src, t)
+
+    def _wave(self, raw: Optional[torch.Tensor], final: bool) -> torch.Tensor:
+        ing = self.ing
+        if raw is not None and raw.shape[-1]:
+            if raw.dim() not in (1, 2) or raw.dtype not in (torch.float32, torch.int16) or (raw.dim() == 2 and not 1 <= raw.shape[0] <= 8):
+                raise ValueError(f'raw wave: expected fp32 or int16 (n,) or (ch <= 8, n), got {raw.dtype} {tuple(raw.shape)}')
+            x = raw.to(ing.dev, non_blocking=True)
+            x = x[None] if x.dim() == 1 else x
+            if self._passthrough(x):                                             # a mono fp32 wave at 16 kHz passes as it is
+                self.raw_seen += int(x.shape[1])
+                self.samples_out += int(x.shape[1])
+                return x.reshape(-1)
+            self._raw = x if self._raw is None else torch.cat([self._raw, x], 1)
+            self.raw_seen += int(x.shape[1])
+        if self._raw is None:
+            return torch.empty(0, device=ing.dev, dtype=torch.float32)
+        from . import ops
+        c0, k0, k1, hold = resample_stream_plan(self.samples_out, self.raw_seen, ing.o, ing.width, ing.n, final)
+        out = torch.empty(0, device=ing.dev, dtype=torch.float32)
+        if k1 > k0:
+            out = ops.resample_wave(self._raw[:, c0 - self._raw0:], ing.kernel, ing.o, ing.width, len_out=k1)[k0:]
+            self.samples_out += k1 - k0
+        self._raw, self._raw0 = self._raw[:, hold - self._raw0:], hold
+        return out

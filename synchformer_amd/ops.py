@@ -8,6 +8,7 @@ to the dispatcher, as the reference's callers would expect of a PyTorch-ROCm ext
 import ctypes as C
 import os
 import threading
+from collections import namedtuple
 from pathlib import Path
 from typing import Optional, Sequence
 
@@ -696,6 +697,75 @@ def track_posterior(logits: torch.Tensor, lam: float, grid: torch.Tensor, post: 
                                         _dev(ws, 'workspace'), _stream())
     _lib.check(rc, 'sf_track_posterior')
     return post, cls_post, conf_post, offset_mean, log_z
+
+
+class TrackStreamState:
+    """The carried state of one stream's fixed-lag read-out (sf_track_stream_push): `buf` the opaque device buffer, `rows` the rows pushed so far (host count),
+    `closed` after a final push.  Its size does not depend on `rows`."""
+
+    def __init__(self, buf: torch.Tensor, C: int, lag: int, posterior: bool):
+        self.buf, self.C, self.lag, self.posterior, self.rows, self.closed = buf, int(C), int(lag), bool(posterior), 0, False
+
+
+def track_stream_state(C: int, lag: int, posterior: bool, device) -> TrackStreamState:
+    """A fresh stream state for C classes (2 .. 64) and a decision lag of `lag` windows (0 .. 255): sf_track_stream_bytes(C, lag, posterior) zeroed bytes on `device`."""
+    nbytes = _lib.load().sf_track_stream_bytes(int(C), int(lag), int(bool(posterior)))
+    if nbytes < 0:
+        _lib.check(nbytes, 'sf_track_stream_bytes')
+    return TrackStreamState(torch.zeros(nbytes, device=device, dtype=torch.uint8), C, lag, posterior)
+
+
+TrackStreamOut = namedtuple('TrackStreamOut', 'w0 cls_raw conf_raw cls_lag conf_lag cls_tail conf_tail post_lag cls_post_lag conf_post_lag offset_mean_lag log_z')
+
+
+def track_stream_counts(rows: int, n: int, lag: int, final: bool = False):
+    """-> (w0, n_commit, n_tail) of a push of n rows onto `rows` rows: the first window it commits, how many it commits, the uncommitted tail after it."""
+    done_old = max(0, rows - lag)
+    done_new = rows + n if final else max(0, rows + n - lag)
+    return done_old, done_new - done_old, rows + n - done_new
+
+
+def track_stream_push(state: TrackStreamState, logits: torch.Tensor, lam: float, grid: Optional[torch.Tensor] = None, final: bool = False) -> TrackStreamOut:
+    """Fixed-lag read-out of the next n rows of a stream (sf_track_stream_push): logits fp32 (n, C) on the state's device with unit column stride (n = 0 allowed),
+    rows in time order after the state.rows pushed before; grid fp32 (C,) when the state was made with posterior ->
+    TrackStreamOut(w0, cls_raw (n,), conf_raw (n,), cls_lag (k,), conf_lag (k,), cls_tail (m,), conf_tail (m,), post_lag (k, C), cls_post_lag, conf_post_lag,
+    offset_mean_lag (k,), log_z (1,)): windows w0 .. w0 + k - 1 are committed by this push (those whose row w + lag arrived: cls_lag[i] is the class of window
+    w0 + i on the Viterbi path of rows 0 .. w0 + i + lag, never revised), the tail is the path of everything pushed so far on the m = min(lag, rows) windows not yet
+    committed (cls_tail[-1]: the current offset).  final=True commits the tail from the whole prefix and closes the state.  The posterior fields are None without
+    posterior.  Output sizes are host arithmetic; nothing is read back or synchronised, the state advances on the device in stream order."""
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.shape[1] == state.C, f'logits {tuple(logits.shape)} for a stream of {state.C} classes'
+    if state.closed:
+        raise RuntimeError('track_stream_push: the stream was closed by a final push')
+    n, C, dev = logits.shape[0], state.C, state.buf.device
+    assert n == 0 or (logits.device == dev and logits.stride(1) == 1), 'logits: on the state\'s device, unit column stride'
+    if state.posterior:
+        assert grid is not None and grid.dtype == torch.float32 and grid.device == dev and grid.shape == (C,) and grid.is_contiguous(), f'a grid for {C} classes'
+    w0, k, m = track_stream_counts(state.rows, n, state.lag, final)
+    i32 = dict(device=dev, dtype=torch.int32)
+    f32 = dict(device=dev, dtype=torch.float32)
+    cls_raw, conf_raw = torch.empty(n, **i32), torch.empty(n, **f32)
+    cls_lag, conf_lag = torch.empty(k, **i32), torch.empty(k, **f32)
+    cls_tail, conf_tail = torch.empty(m, **i32), torch.empty(m, **f32)
+    post = cls_post = conf_post = mean = log_z = None
+    if state.posterior:
+        post, cls_post, conf_post, mean = torch.empty(k, C, **f32), torch.empty(k, **i32), torch.empty(k, **f32), torch.empty(k, **f32)
+        log_z = torch.zeros(1, **f32)                                               # (stays 0 while the stream is empty: the empty product)
+    lib = _lib.load()
+    ws_bytes = lib.sf_track_stream_workspace_bytes(C, n, int(state.posterior))
+    if ws_bytes < 0:
+        _lib.check(ws_bytes, 'sf_track_stream_workspace_bytes')
+    ws = torch.empty(max(ws_bytes, 16), device=dev, dtype=torch.uint8)
+
+    def ptr(t):
+        return _dev(t, 'out') if t is not None and t.numel() else None
+
+    rc = lib.sf_track_stream_push(_dev(state.buf, 'state'), C, state.lag, int(state.posterior), state.rows, ptr(logits), _ld(logits) if n else C, n, float(lam),
+                                  _dev(grid, 'grid') if state.posterior else None, int(bool(final)), ptr(cls_raw), ptr(conf_raw), ptr(cls_lag), ptr(conf_lag), ptr(post),
+                                  C, ptr(cls_post), ptr(conf_post), ptr(mean), ptr(cls_tail), ptr(conf_tail), ptr(log_z), _dev(ws, 'workspace'), _stream())
+    _lib.check(rc, 'sf_track_stream_push')
+    state.rows += n
+    state.closed = bool(final)
+    return TrackStreamOut(w0, cls_raw, conf_raw, cls_lag, conf_lag, cls_tail, conf_tail, post, cls_post, conf_post, mean, log_z)
 
 
 def _ingest_tables(frame_table: torch.Tensor, **tables):

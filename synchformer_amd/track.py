@@ -14,6 +14,10 @@ confidence that carries the evidence of the whole recording, and an offset finer
     track = OffsetTracker(engine, mel, posterior=True).track(frames, wave)
     track.conf_post, track.offset_sec_mean        # how sure given every window, the posterior mean offset
 
+    stream = tracker.stream(lag=16)               # a live feed: push what arrived, get the windows that became final
+    upd = stream.push(frames_1s, wave_1s)         # upd.cls_lag / offset_sec_lag: committed, never revised; upd.offset_sec_tail[-1]: the offset now
+    upd = stream.flush()                          # end of the feed: the tail is committed
+
 Out of scope (one recording per call): batching several recordings, double-buffered host-to-device transfer of the chunks, de-duplicating the
 overlapped tubelets inside the patch embedding.
 """
@@ -23,16 +27,22 @@ from typing import Optional
 import torch
 
 from . import ops
-from .frontend import recording_geometry
+from .frontend import recording_geometry, stream_geometry
 from .postprocess import class_grid
+
+
+def window_times64(n_windows: int, hop_segments: int = 1, v_fps: float = 25.0, first_window: int = 0, **segment_kw) -> torch.Tensor:
+    """Centres (seconds, float64) of windows first_window .. first_window + n_windows - 1: window w covers frames [8 hop w, 8 hop w + 120) at 25 fps ->
+    (8 hop w + 60) / 25, computed at the absolute window index (a stream's day-old windows keep their milliseconds)."""
+    g = recording_geometry(0, 0, hop_segments, **segment_kw)
+    span = (g['n_window'] - 1) * g['v_stride'] + g['v_size']                    # frames of one window (120)
+    w = torch.arange(first_window, first_window + n_windows, dtype=torch.float64)
+    return (g['v_stride'] * hop_segments * w + span / 2) / v_fps
 
 
 def window_times(n_windows: int, hop_segments: int = 1, v_fps: float = 25.0, **segment_kw) -> torch.Tensor:
     """Centres (seconds, fp32) of the windows of a recording: window w covers frames [8 hop w, 8 hop w + 120) at 25 fps -> (8 hop w + 60) / 25."""
-    g = recording_geometry(0, 0, hop_segments, **segment_kw)
-    span = (g['n_window'] - 1) * g['v_stride'] + g['v_size']                    # frames of one window (120)
-    w = torch.arange(n_windows, dtype=torch.float64)
-    return ((g['v_stride'] * hop_segments * w + span / 2) / v_fps).float()
+    return window_times64(n_windows, hop_segments, v_fps, **segment_kw).float()
 
 
 @dataclass
@@ -102,3 +112,140 @@ class OffsetTracker:
         wave = ingest.wave(raw_wave)
         banks = self.eng.extract_recording_from(lambda f0, f1: ingest.frames(raw_frames, f0, f1), ingest.n_frames(raw_frames.shape[0]), wave, self.mel, seg_chunk)
         return self.track_features(*banks, win_chunk=win_chunk)
+
+    def stream(self, lag: int = 16, seg_chunk: Optional[int] = None, ingest=None) -> 'OffsetStream':
+        """A live feed: push frames and samples as they arrive, get per push the windows that became final.  lag: window w is committed once
+        `lag` more windows have arrived (0 .. 255), as the class of w on the Viterbi path of everything up to window w + lag - a decision delay of
+        lag * hop * 0.32 s.  lag = 16 is a DEFAULT, NOT A TUNED VALUE (as lam): how far back a later window still changes the decision depends on lam and on
+        the domain's logits; choose it on held-out recordings.  lag >= the number of windows gives the offline path at flush().  seg_chunk: as in track().
+        ingest: an ingest.RecordingIngest - push then takes frames and samples as decoded (native frame rate, size, sample rate; track_raw's layouts)."""
+        return OffsetStream(self, lag, seg_chunk, ingest)
+
+
+@dataclass
+class OffsetUpdate:
+    """What one push (or the flush) of an OffsetStream adds; tensors on the engine's device, times float64 on the host."""
+    # the windows this push completed (n of them, from window w_new)
+    w_new: int
+    logits: torch.Tensor             # (n, C) fp32
+    cls_raw: torch.Tensor            # (n,) int32: per-window argmax
+    conf_raw: torch.Tensor           # (n,) fp32
+    # the committed block: windows w0 .. w0 + k - 1, final - a later push never revises them
+    w0: int
+    t_sec: torch.Tensor              # (k,) float64: window centres at the absolute window index
+    cls_lag: torch.Tensor            # (k,) int32: the class of window w on the Viterbi path of windows 0 .. w + lag
+    conf_lag: torch.Tensor           # (k,) fp32: its softmax probability in window w
+    offset_sec_lag: torch.Tensor     # (k,) fp32: grid[cls_lag]
+    # the tail: the windows not yet committed, on the path of everything so far; [-1] is the current offset and may change with the next push
+    t_sec_tail: torch.Tensor         # (m,) float64
+    cls_tail: torch.Tensor           # (m,) int32
+    conf_tail: torch.Tensor          # (m,) fp32
+    offset_sec_tail: torch.Tensor    # (m,) fp32
+    # OffsetTracker(posterior=True): the marginals of the committed windows given windows 0 .. w + lag; None without it
+    post_lag: Optional[torch.Tensor] = None            # (k, C) fp32
+    cls_post_lag: Optional[torch.Tensor] = None        # (k,) int32
+    conf_post_lag: Optional[torch.Tensor] = None       # (k,) fp32
+    offset_sec_post_lag: Optional[torch.Tensor] = None  # (k,) fp32: grid[cls_post_lag]
+    offset_sec_mean_lag: Optional[torch.Tensor] = None  # (k,) fp32
+    log_z: Optional[torch.Tensor] = None               # (1,) fp32: that of all the windows so far
+
+
+class OffsetStream:
+    """OffsetTracker.stream(): the recording path for a feed that does not end.  push() takes what arrived - uint8 frames (t, 3, 224, 224) at 25 fps and fp32
+    samples (m,) at 16 kHz, device or host, either possibly empty, the two at their own pace (with `ingest`: as decoded) - runs the towers on the segments that
+    became complete, the sync transformer on the windows that became complete (engine.sync_windows on the held features: 13 old segments and n new ones give
+    exactly the n new windows) and the fixed-lag read-out (ops.track_stream_push).  What the stream carries is bounded, whatever has passed (`held`):
+        frames   from 8 N on (N = segments done): at most 15, plus what the video is ahead of the audio, plus one push
+        samples  from 5120 N on: at most 10239, plus what the audio is ahead of the video, plus one push
+        segment features from the next window's first segment on: at most 13 + hop - 1
+        the read-out state: ops.track_stream_state's bytes
+    The segment grid is the recording's (anchored at frame 0), so the windows, their logits (bit for bit where the tower schedule is position-independent: the
+    un-fused one) and t_sec are those track() gives for the finished recording."""
+
+    def __init__(self, tracker: OffsetTracker, lag: int = 16, seg_chunk: Optional[int] = None, ingest=None):
+        self.tracker, self.lag, self.seg_chunk = tracker, int(lag), seg_chunk
+        dev = tracker.eng.dev
+        self.state = ops.track_stream_state(tracker.eng.n_out, self.lag, tracker.posterior, dev)
+        self._ingest = None if ingest is None else ingest.stream()
+        self._frames = torch.empty(0, 3, 224, 224, device=dev, dtype=torch.uint8)
+        self._wave = torch.empty(0, device=dev, dtype=torch.float32)
+        self._vfeat = self._afeat = None
+        self.n_frames = self.n_samples = self.n_segments = self.n_windows = 0    # totals so far
+        self._f0 = self._a0 = self._s0 = 0                                       # the recording's index of the first held frame / sample / segment
+        self.closed = False
+
+    @property
+    def held(self) -> dict:
+        """The sizes of the carried buffers: frames, samples, segments (features) and state_bytes."""
+        return dict(frames=int(self._frames.shape[0]), samples=int(self._wave.shape[0]), segments=0 if self._vfeat is None else int(self._vfeat.shape[0]),
+                    state_bytes=int(self.state.buf.numel()))
+
+    @property
+    def held_bound(self) -> dict:
+        """The bound on `held` after a push, from the totals so far (see the class docstring; one push's own frames and samples pass through on top of it)."""
+        g = recording_geometry(self.n_frames, self.n_samples, self.tracker.hop)
+        nv = max(0, (self.n_frames - g['v_size']) // g['v_stride'] + 1)
+        na = max(0, (self.n_samples - g['a_size']) // g['a_stride'] + 1)
+        return dict(frames=g['v_size'] - 1 + g['v_stride'] * (nv - g['n_segments']), samples=g['a_size'] - 1 + g['a_stride'] * (na - g['n_segments']),
+                    segments=g['n_window'] - 1 + self.tracker.hop - 1, state_bytes=int(self.state.buf.numel()))
+
+    def push(self, frames: torch.Tensor, wave: torch.Tensor) -> OffsetUpdate:
+        if self.closed:
+            raise RuntimeError('OffsetStream.push: the stream was closed by flush()')
+        if self._ingest is not None:
+            frames, wave = self._ingest.push(frames, wave)
+        return self._advance(frames, wave, final=False)
+
+    def flush(self) -> OffsetUpdate:
+        """End of the feed: whatever the ingest still held becomes final, the tail is committed from everything pushed, the stream closes (a later push raises)."""
+        if self.closed:
+            raise RuntimeError('OffsetStream.flush: the stream is closed')
+        dev = self.tracker.eng.dev
+        frames, wave = torch.empty(0, 3, 224, 224, device=dev, dtype=torch.uint8), torch.empty(0, device=dev, dtype=torch.float32)
+        if self._ingest is not None:
+            frames, wave = self._ingest.flush()
+        upd = self._advance(frames, wave, final=True)
+        self.closed = True
+        return upd
+
+    def _advance(self, frames: torch.Tensor, wave: torch.Tensor, final: bool) -> OffsetUpdate:
+        tr, eng = self.tracker, self.tracker.eng
+        if frames.dim() != 4 or frames.dtype != torch.uint8 or tuple(frames.shape[1:]) != (3, 224, 224) or wave.dim() != 1:
+            raise ValueError(f'OffsetStream.push: expected uint8 frames (t, 3, 224, 224) and a 1-D wave, got {frames.dtype} {tuple(frames.shape)} / {tuple(wave.shape)}')
+        if frames.shape[0]:
+            self._frames = torch.cat([self._frames, frames.to(eng.dev, non_blocking=True)])
+        if wave.shape[0]:
+            self._wave = torch.cat([self._wave, wave.to(eng.dev, torch.float32, non_blocking=True)])
+        self.n_frames += int(frames.shape[0])
+        self.n_samples += int(wave.shape[0])
+        g = stream_geometry(self.n_frames, self.n_samples, self.n_segments, tr.hop)
+        (s0, s1), (w0, w1) = g['new_segments'], g['new_windows']
+        if s1 > s0:                                                              # the towers, on the segments this push completed
+            vf, af = eng.extract_segments_from(lambda f0, f1: self._frames[f0 - self._f0:f1 - self._f0], self._wave, tr.mel, s0, s1 - s0, self.seg_chunk,
+                                               sample0=self._a0)
+            self._vfeat = vf if self._vfeat is None else torch.cat([self._vfeat, vf])
+            self._afeat = af if self._afeat is None else torch.cat([self._afeat, af])
+        if w1 > w0:                                                              # the windows whose last segment arrived: the held features hold exactly these
+            lo = tr.hop * w0 - self._s0
+            logits = eng.sync_windows(self._vfeat[lo:], self._afeat[lo:], hop=tr.hop)
+            assert logits.shape[0] == w1 - w0, (logits.shape, w0, w1)
+        else:
+            logits = torch.empty(0, eng.n_out, device=eng.dev, dtype=torch.float32)
+        out = ops.track_stream_push(self.state, logits, tr.lam, tr.grid if tr.posterior else None, final=final)
+        # drop what no later segment / window reads
+        self._frames, self._f0 = self._frames[g['frames_from'] - self._f0:], g['frames_from']
+        self._wave, self._a0 = self._wave[g['samples_from'] - self._a0:], g['samples_from']
+        if self._vfeat is not None:
+            k = g['features_from'] - self._s0
+            self._vfeat, self._afeat, self._s0 = self._vfeat[k:], self._afeat[k:], g['features_from']
+        self.n_segments, self.n_windows = s1, w1
+        k, m = out.cls_lag.shape[0], out.cls_tail.shape[0]
+        upd = OffsetUpdate(w_new=w0, logits=logits, cls_raw=out.cls_raw, conf_raw=out.conf_raw, w0=out.w0, t_sec=window_times64(k, tr.hop, first_window=out.w0),
+                           cls_lag=out.cls_lag, conf_lag=out.conf_lag, offset_sec_lag=tr.grid[out.cls_lag.long()],
+                           t_sec_tail=window_times64(m, tr.hop, first_window=w1 - m), cls_tail=out.cls_tail, conf_tail=out.conf_tail,
+                           offset_sec_tail=tr.grid[out.cls_tail.long()])
+        if tr.posterior:
+            upd.post_lag, upd.cls_post_lag, upd.conf_post_lag, upd.offset_sec_mean_lag, upd.log_z = (out.post_lag, out.cls_post_lag, out.conf_post_lag,
+                                                                                                       out.offset_mean_lag, out.log_z)
+            upd.offset_sec_post_lag = tr.grid[out.cls_post_lag.long()]
+        return upd

@@ -3,6 +3,7 @@ beside the same windows through forward_clips on explicit 120-frame slices.  Pri
 
     python tools/track_recording.py [--seconds 60] [--hop 1] [--seg-chunk 224] [--host] [--clip-windows 8] [--fps 30000/1001 --size 1080x1920 --rate 48000]
                                     [--pix-fmt {rgb24,nv12,yuv420p,p010,yuv420p10le}] [--chroma-loc {center,left,topleft}] [--posterior]
+                                    [--stream SECONDS [--lag N]]
 
 With --fps / --size / --rate the recording is synthesised RAW at that geometry (channels-last uint8 frames, stereo int16 PCM, in device memory) and goes through
 the ingest stage: the line then also carries the ingest time alone (the same chunks the bank asks for, plus the wave) and the bank from raw
@@ -12,6 +13,11 @@ the bytes per frame, which the line reports next to the times (with --host they 
 
 With --posterior the windows are also read out as marginals: the line then carries the mean and minimum of conf_post, log_z per window step
 (log_z / max(W - 1, 1)), the largest |offset_sec_mean - offset_sec_path| and the time of the two extra launches (the read-out alone, on the track's logits).
+
+With --stream SECONDS the recording is also pushed through OffsetTracker.stream(lag) in pieces of that many seconds (from raw input when --fps /
+--size / --rate are given): the line then carries, per push, the milliseconds of the bank (the towers on the segments the push completed), the windows (the sync
+transformer on the windows it completed) and the read-out (ops.track_stream_push) - each timed by wall clock between device synchronisations, which a
+production stream would not place - their sum over the recording against the offline track_total_s, and whether the streamed logits equal the offline ones.
 
 forward_clips is timed on at most --clip-windows windows (spread over the recording) and scaled to all W; both sides include the mel front-end and
 are timed by wall clock around a device synchronisation, after one warm-up pass each.  Synthetic weights and inputs: the numbers are throughput only."""
@@ -42,6 +48,8 @@ def main():
     ap.add_argument('--pix-fmt', choices=['rgb24', 'nv12', 'yuv420p', 'p010', 'yuv420p10le'], default=None, help='layout of the raw frames (default: rgb24, channels-last)')
     ap.add_argument('--chroma-loc', choices=['center', 'left', 'topleft'], default='center', help='where the chroma samples of a YUV layout sit')
     ap.add_argument('--posterior', action='store_true', help='also read the windows out as marginals (forward-backward)')
+    ap.add_argument('--stream', type=float, default=None, metavar='SECONDS', help='also push the recording through OffsetTracker.stream in pieces of this length')
+    ap.add_argument('--lag', type=int, default=16, help='decision lag of the stream, in windows')
     args = ap.parse_args()
     from synchformer_amd import ops, synth
     from synchformer_amd.engine import SynchformerEngine
@@ -126,6 +134,8 @@ def main():
                       'log_z_per_step': round(track.log_z.item() / max(W - 1, 1), 4),
                       'max_abs_mean_minus_path_s': round((track.offset_sec_mean - track.offset_sec_path).abs().max().item(), 4),
                       'posterior_s': round(t_post, 6)})
+    if args.stream is not None:
+        extra['stream'] = stream_timing(args, tracker, eng, ops, (raw, raw_wave, ing) if raw_mode else (src[0], src[1], None), track)
     k = min(W, max(1, args.clip_windows))
     picks = [round(i * (W - 1) / max(1, k - 1)) for i in range(k)]
 
@@ -143,6 +153,65 @@ def main():
         'forward_clips_windows_timed': k, 'forward_clips_s_scaled': round(t_clips_all, 3), 'speedup_vs_forward_clips': round(t_clips_all / (t_bank + t_win), 2),
         'max_abs_logit_diff_vs_forward_clips': round(err, 6), 'path_changes': int((track.cls_path[1:] != track.cls_path[:-1]).sum().item()),
         'raw_changes': int((track.cls_raw[1:] != track.cls_raw[:-1]).sum().item()), **extra}))
+
+
+def stream_timing(args, tracker, eng, ops, source, track):
+    """Pushes the recording through tracker.stream(lag) in pieces of args.stream seconds, twice (the first pass warms up); the three stages are timed by wrapping
+    the calls OffsetStream makes (engine.extract_segments_from, engine.sync_windows, ops.track_stream_push) between device synchronisations."""
+    frames, wave, ing = source
+    fps, rate = (float(ing.fps_in), ing.rate_in) if ing is not None else (25.0, 16000)
+    ms = {}
+
+    def staged(obj, name, key):
+        fn = getattr(obj, name)
+
+        def wrapped(*a, **kw):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn(*a, **kw)
+            torch.cuda.synchronize()
+            ms[key] = ms.get(key, 0.0) + (time.perf_counter() - t0) * 1e3
+            return out
+        setattr(obj, name, wrapped)
+        return fn
+
+    saved = [(eng, 'extract_segments_from', staged(eng, 'extract_segments_from', 'bank')), (eng, 'sync_windows', staged(eng, 'sync_windows', 'windows')),
+             (ops, 'track_stream_push', staged(ops, 'track_stream_push', 'readout'))]
+    try:
+        for _ in range(2):
+            stream = tracker.stream(lag=args.lag, ingest=ing)
+            rows, logits, f, a, i = [], [], 0, 0, 1
+            t_start = time.perf_counter()
+            while f < frames.shape[0] or a < wave.shape[-1]:
+                f1, a1 = min(frames.shape[0], round(i * args.stream * fps)), min(wave.shape[-1], round(i * args.stream * rate))
+                ms.clear()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                upd = stream.push(frames[f:f1], wave[..., a:a1])
+                torch.cuda.synchronize()
+                rows.append(dict(ms, push=(time.perf_counter() - t0) * 1e3, windows_new=int(upd.logits.shape[0]), committed=int(upd.cls_lag.shape[0])))
+                logits.append(upd.logits)
+                f, a, i = f1, a1, i + 1
+            upd = stream.flush()
+            logits.append(upd.logits)
+            torch.cuda.synchronize()
+            total = time.perf_counter() - t_start
+    finally:
+        for obj, name, fn in saved:
+            setattr(obj, name, fn)
+    for r in rows:
+        print('push ' + '  '.join(f'{k} {v:.2f} ms' if isinstance(v, float) else f'{k} {v}' for k, v in r.items()), file=sys.stderr)
+    busy = [r for r in rows if r['windows_new']]
+
+    def stat(key):
+        v = [r.get(key, 0.0) for r in busy]
+        return {'mean_ms': round(sum(v) / max(len(v), 1), 3), 'max_ms': round(max(v, default=0.0), 3)}
+
+    got = torch.cat(logits)
+    return {'piece_s': args.stream, 'lag': args.lag, 'pushes': len(rows), 'pushes_with_windows': len(busy), 'bank': stat('bank'), 'windows': stat('windows'),
+            'readout': stat('readout'), 'push': stat('push'), 'held_after': stream.held, 'total_s': round(total, 4),
+            'logits_equal_offline': bool(got.shape == track.logits.shape and torch.equal(got, track.logits)),
+            'max_abs_logit_diff_vs_offline': round((got - track.logits).abs().max().item(), 6) if got.shape == track.logits.shape else None}
 
 
 if __name__ == '__main__':
