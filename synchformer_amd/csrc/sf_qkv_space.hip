@@ -7,12 +7,9 @@
 //     q | k | v of two heads (384 features) = 6 x 12 = 72 blocks of 32 x 32, nine per wave (2 x 4 waves of 96 rows x 96 features) - no padded rows, the operand
 //     bytes per MAC of the 256 x 256 tile.  The four left-over tokens of every frame and the CLS row are projected up front by a small GEMM of the caller
 //     (`side`: 33 rows per sequence); they join as queries 192-195 / keys 193-196 / key 0 in the epilogue.
-//   * Main loop: 64-deep k-tiles in two 72-KiB stages (A 24 KiB | W0 | W1 | W2 of 16 KiB, W part j = feature block j of each of the four wave columns), THREE phases per
-//     k-tile - one feature block each, 12 MFMAs of 32x32x16 per wave and phase with the wave's 12 A fragments held in registers - accumulators transposed
-//     (C^T = W X^T: a lane ends with one token's features).  LDS-DMA pieces (9 per wave and k-tile) run about one stage ahead behind COUNTED waits, the wm = 1
-//     waves one barrier behind the wm = 0 waves - the schedule of sf_qkv_time.hip / sf_gemm_pp.hip:
-//         phase 0 of k-tile kt: issue W1, A1, A2 of kt+1 (no wait) | phase 1: issue W2 of kt+1, vmcnt(9): W2 of kt landed | phase 2: issue W0, A0 of kt+2,
-//         vmcnt(5): A, W0, W1 of kt+1 landed;   every part is refilled two phases after its last fragment read, data is read one phase after its wait.
+//   * Main loop: the 192 x 384 x 64 two-stage, three-phase loop of sf_qkv_tile.h (stages, pieces, the phase / vmcnt table and the work-item schedule are described
+//     there, once, for this kernel and sf_qkv_time2.hip), on one contiguous run of 192 rows of X.  This kernel's side loads in front of it: the bias (waves 0-5) and
+//     the 240 chunks of the side rows (waves 0-3).
 //   * Epilogue: accumulators (+ bias) -> bf16 -> LDS as K | V | Q of both heads in the row-major, XOR-swizzled layout of attn_mfma_kernel (sf_attention.hip); the side rows
 //     arrive by LDS-DMA during the main loop; then the arithmetic of that kernel (S^T = K Q^T on v_mfma_f32_16x16x32_bf16, in-lane base-2 softmax, P V with
 //     ds_read_b64_tr_b16 V fragments) on PAIRS of 16-query tiles - every K / V fragment read from LDS feeds two MFMAs: 14 pair units (2 heads x 7) over the 8 waves -, the
@@ -21,24 +18,17 @@
 //   * Measured (M = 351,456, profiles/r04_qkv_space.md): 1330 us against 1050 (sf_gemm_bf16 qkv) + 483 (attention) un-fused; the main loop + accumulator hand-over
 //     alone run at 1.31 PFLOP/s (947 us), the attention epilogue costs ~9 us per work item (softmax VALU + LDS fragment reads + MFMAs of ONE workgroup per CU).
 //   * persistent, one workgroup per CU; every XCD owns a contiguous range of frames and sweeps it once per chunk of head pairs (pair fastest inside a chunk).
-#include "sf_common.h"
-#include <type_traits>
-#include <stdlib.h>
+#include "sf_qkv_tile.h"
 #include "../../include/synchformer_hip.h"
 
 #define QS_TOK 196                     // tokens of a space group (one frame)
-#define QS_ROWS 192                    // ... of which the GEMM tile computes the first 192
-#define QS_D 768
-#define QS_A_BYTES (QS_ROWS * 128)     // 24 KiB: 192 rows x 64 k (bf16)
-#define QS_W_PART (128 * 128)          // 16 KiB: 4 wave columns x 32 features x 64 k
-#define QS_STAGE (QS_A_BYTES + 3 * QS_W_PART)   // 72 KiB
-#define QS_SIDE_OFF (2 * QS_STAGE)     // 144 KiB: landing area of the side rows (240 x 16 B) during the main loop
+#define QS_ROWS QKT_ROWS               // ... of which the GEMM tile computes the first 192
+#define QS_SIDE_OFF (2 * QKT_STAGE)    // 144 KiB: landing area of the side rows (240 x 16 B) during the main loop
 #define QS_ARR (208 * 128)             // one K / V / Q array of the attention: 208 rows of 128 B
-#define QS_BIAS_OFF (6 * QS_ARR)       // 156 KiB: the tile's 384 bias floats (behind the attention arrays: lives through main loop AND epilogue)
-#define QS_MASK_OFF (QS_BIAS_OFF + 1536) // MASK variant: one float per key of the frame's group (0 = kept, -inf = masked), 208 floats; key 0 = the CLS key
-#define QS_LDS (160 * 1024)
+static_assert(6 * QS_ARR == QKT_BIAS_OFF, "the bias sits right behind the six attention arrays");
+#define QS_MASK_OFF (QKT_BIAS_OFF + 1536) // MASK variant: one float per key of the frame's group (0 = kept, -inf = masked), 208 floats; key 0 = the CLS key
 #ifndef QS_ABL
-#define QS_ABL 0                       // measurement builds: 1 no attention (epilogue part 2 skipped), 2 no MFMAs in the main loop, 4 no softmax arithmetic, 8 no S phase, 16 one of the seven P V steps
+#define QS_ABL 0                       // measurement builds: 1 no attention (epilogue part 2 skipped), 2 no MFMAs in the main loop, 4 no softmax arithmetic, 8 no S phase, 16 one of the seven P V steps, 32 no wait in the main loop's prologue
 #endif
 
 struct QsArgs {
@@ -49,7 +39,7 @@ struct QsArgs {
   bf16_t* out; int64_t ldo;
   float* cls_part;                     // [n_seq][12][8][66]
   int64_t seq_rows;
-  uint32_t n_frames;                   // n_seq * 8
+  uint32_t n_rt;                       // row tiles = frames: n_seq * 8
   uint32_t pair_chunk;                 // head pairs per sweep over an XCD's frames (divides 6)
   float scale;
   // MX (template parameter): X / W are e4m3 BYTES (ldx / ldw in bytes) with stage-major E8M0 scale planes (one dword per row per 128 k, ldsx / ldsw bytes between planes)
@@ -60,263 +50,47 @@ struct QsArgs {
   // MASK (template parameter): token flags, one byte per row of X; a row with flag 0 is a masked KEY (score -inf) for every query of its frame and for the CLS query
   const uint8_t* key_keep = nullptr;
 };
-#define QS_SC_OFF (148 * 1024)         // MX: the k-tile's scale dwords, two parities x (192 token rows | 3 x 128 part rows of W) = 2 x 2304 B
-#define QS_SC_BYTES 2304
+#define QS_SC_OFF (148 * 1024)         // MX: where the k-tile's scale dwords land (two parities of QKT_SC_BYTES)
 #ifndef QS_MXOUT
 #define QS_MXOUT 1
 #endif
-typedef __attribute__((ext_vector_type(8))) int qs_i32x8;
-
-typedef short qs_s4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) qs_s4 qs_lds_s4;
-
-__device__ __forceinline__ void qs_dma1(uint32_t voff, const void* sbase, uint32_t lds) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds) : "memory");
-}
-__device__ __forceinline__ void qs_dma_dword_addr(const void* gaddr, uint32_t lds) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gaddr), "s"(lds) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void qs_wait_vmcnt() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_waitcnt((N & 0xF) | (0x7 << 4) | (0xF << 8) | ((N >> 4) << 14));
-}
-__device__ __forceinline__ void qs_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-__device__ __forceinline__ uint32_t qs_lds_addr(const void* p) { return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char*)p; }
 __device__ __forceinline__ int qs_arr_off(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }   // = k_lds_off<64> of sf_attention.hip
-
-template <int V> using qs_ic = std::integral_constant<int, V>;
 
 template <bool MX, bool MASK = false>
 __device__ __forceinline__ void qkv_space_attn_body(const QsArgs& p) {
-  constexpr int ESZ = MX ? 1 : 2;                                 // bytes per operand element
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;                         // 2 x 4 waves, wave tile 96 token rows x 96 features
-  const int hi = lane >> 5;
 
-  // persistent schedule: block b sits on XCD b % 8; every XCD owns a contiguous range of frames and walks (frame, head pair) in chunks of `hc` pairs
-  const uint32_t xcd = blockIdx.x & 7u, li = blockIdx.x >> 3, per_xcd_blocks = gridDim.x >> 3;
-  const uint32_t f8 = (p.n_frames + 7u) >> 3;
-  const uint32_t fr0 = min(xcd * f8, p.n_frames), fr1 = min(fr0 + f8, p.n_frames);
-  const uint32_t hc = p.pair_chunk, chunk_tiles = (fr1 - fr0) * hc, t_end = (fr1 - fr0) * 6u;
-  uint32_t t = li;
-  if (t >= t_end) return;
+  const QktSchedule sched(p.n_rt, p.pair_chunk);               // row tile = frame
+  uint32_t t = sched.li;
+  if (t >= sched.t_end) return;
 
-  // ---- tile-invariant lane offsets of the LDS-DMA pieces -----------------------------------------------------------------------------
-  // A piece pc of this wave = tile rows (3 wave + pc) * 8 .. + 7; lane (r = lane >> 3, chunk slot = lane & 7) -> LDS row-linear, source chunk XOR-swizzled
-  uint32_t voff_a = 0, voff_w[3] = {0, 0, 0}, sc_voff = 0;         // lane offsets of the LDS-DMA pieces: re-derived at the top of every tile (not kept live across the attention)
-  const uint32_t a8 = (uint32_t)(8 * p.ldx * ESZ), w8 = (uint32_t)(8 * p.ldw * ESZ);
-  const uint32_t lds0 = __builtin_amdgcn_readfirstlane(qs_lds_addr(smem));
-  const uint32_t lds_a_w = __builtin_amdgcn_readfirstlane(lds0 + wave * 3072);
-  const uint32_t lds_w_w = __builtin_amdgcn_readfirstlane(lds0 + QS_A_BYTES + wave * 2048);
-
-  const char* xbase; const char* wbase;
-  uint32_t fr; int hp; int64_t xrow0;
-  auto set_tile = [&](uint32_t tt) {
-    const uint32_t c = tt / chunk_tiles, r = tt - c * chunk_tiles;
-    fr = fr0 + r / hc; hp = (int)(c * hc + r % hc);
-    const int64_t seq = fr >> 3; const int f = (int)(fr & 7u);
-    xrow0 = seq * p.seq_rows + 1 + (int64_t)f * QS_TOK;
-    xbase = reinterpret_cast<const char*>(p.X) + xrow0 * p.ldx * ESZ;
-    wbase = reinterpret_cast<const char*>(p.W) + (int64_t)hp * 128 * p.ldw * ESZ;
-  };
-  // MX: the scale dwords of a k-tile - 192 token rows (768 contiguous bytes of plane kt of sX) and the tile's 384 W rows (12 runs of 32 rows of plane kt of sW, in
-  // part order: area index j * 128 + 32 wn' + rr) - as 16-byte LDS-DMA lanes: 48 + 96 lanes = three pieces.  EVERY wave issues exactly one of them (wave % 3; the
-  // copies land the same bytes on the same addresses), so that all waves count the same number of vector-memory operations per k-tile
-  const int sc_seg = wave % 3;
-  const int sc_lanes = sc_seg == 0 ? 48 : (sc_seg == 1 ? 64 : 32);
-  // tile-invariant lane offsets (row strides are multiples of 128 bytes - launcher check -, so the low 7 bits of an offset are its chunk slot: the piece 8 rows
-  // further down is (offset ^ 64) + 8 rows, computed at issue time instead of held in a register per piece).
-  // A piece pc of this wave = tile rows (3 wave + pc) * 8 .. + 7; lane (r = lane >> 3, chunk slot = lane & 7) -> LDS row-linear, source chunk XOR-swizzled.
-  // W part j, piece pc of this wave = part rows (2 wave + pc) * 8 .. + 7; part row pr = 32 wn' + rr <-> tile column wn' * 96 + 32 j + rr <-> row
-  // which * 768 + hd * 64 + feat of W (the head pair's offset rides in the SGPR base)
-  auto derive_offsets = [&]() {
-    int dtid = threadIdx.x;
-    asm volatile("" : "+v"(dtid));
-    const int dl = dtid & 63;
-    {
-      const int r = wave * 3 * 8 + (dl >> 3);
-      voff_a = (uint32_t)((int64_t)r * p.ldx * ESZ + ((((dl & 7) ^ ((r >> 1) & 7))) << 4));
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const int pr = wave * 2 * 8 + (dl >> 3);
-      const int c = (pr >> 5) * 96 + j * 32 + (pr & 31);
-      const int hd = c / 192, within = c - hd * 192;
-      const int grow = (within >> 6) * QS_D + hd * 64 + (within & 63);
-      voff_w[j] = (uint32_t)((int64_t)grow * p.ldw * ESZ + ((((dl & 7) ^ ((pr >> 1) & 7))) << 4));
-    }
-    if (MX) {
-      if (sc_seg == 0) sc_voff = (uint32_t)dl * 16u;
-      else {
-        const int L = (sc_seg == 1 ? 0 : 64) + dl, run = L >> 3, j = run >> 2, wnp = run & 3;
-        const int c = wnp * 96 + j * 32 + (L & 7) * 4;
-        const int hd = c / 192, within = c - hd * 192;
-        sc_voff = (uint32_t)(((within >> 6) * QS_D + hd * 64 + (within & 63)) * 4);
-      }
-    }
-  };
-  const uint32_t sc_lds = __builtin_amdgcn_readfirstlane(lds0 + QS_SC_OFF + (sc_seg == 0 ? 0 : (sc_seg == 1 ? 768 : 768 + 1024)));
-  auto issue_sc = [&](int kt) {
-    const char* base = sc_seg == 0 ? reinterpret_cast<const char*>(p.sX) + (int64_t)kt * p.ldsx + xrow0 * 4
-                                   : reinterpret_cast<const char*>(p.sW) + (int64_t)kt * p.ldsw + (int64_t)hp * 512;
-    if (lane < sc_lanes) qs_dma1(sc_voff, base, sc_lds + (kt & 1) * QS_SC_BYTES);
-  };
-  auto issue_a = [&](int pc, int S, int kt) {                       // piece pc: 8 pc rows further down; the chunk swizzle flips bit 2 with every 8 rows
-    qs_dma1(((pc & 1) ? (voff_a ^ 64u) : voff_a) + (uint32_t)pc * a8, xbase + kt * 128, lds_a_w + S * QS_STAGE + pc * 1024);
-  };
-  auto issue_w = [&](int j, int S, int kt) {
-    qs_dma1(voff_w[j], wbase + kt * 128, lds_w_w + S * QS_STAGE + j * QS_W_PART);
-    qs_dma1((voff_w[j] ^ 64u) + w8, wbase + kt * 128, lds_w_w + S * QS_STAGE + j * QS_W_PART + 1024);
-  };
-
-  constexpr int nk = MX ? QS_D / 128 : QS_D / 64;                   // 12 k-tiles of 64 bf16 / 6 of 128 fp8: 128 bytes per row either way
+  // the tile's 192 rows are one contiguous run of X (XRUN = 24)
+  QktTile<MX, 24, QS_SC_OFF, (QS_ABL & 2) != 0, (QS_ABL & 32) != 0> tile(smem, QktOperands{p.X, p.ldx, p.W, p.ldw, p.sX, p.ldsx, p.sW, p.ldsw, p.bias}, wave, lane);
+  const uint32_t lds0 = tile.lds0;
   const float sc2 = p.scale * 1.44269504088896f;                   // softmax in base 2
   uint32_t tcount = 0;
 
   for (;;) {
-    set_tile(t);
-    derive_offsets();
+    uint32_t fr; int hp;
+    sched.item(t, fr, hp);
     const int64_t seq = fr >> 3; const int f = (int)(fr & 7u);
-    // ---- prologue: bias, side rows, k-tile 0 and W0 | A0 of k-tile 1 (the previous tile's attention is over: barrier at the bottom of the loop) ----------
-    if (wave < 6) {                                                 // 6 x 64 bias floats: tile columns 64 wave .. + 63 = (head hd = wave / 3, q | k | v = wave % 3)
-      if (p.bias) qs_dma_dword_addr(p.bias + (wave % 3) * QS_D + (hp * 2 + wave / 3) * 64 + lane, lds0 + QS_BIAS_OFF + wave * 256);
-    }
+    const int64_t xrow0 = seq * p.seq_rows + 1 + (int64_t)f * QS_TOK;
+    tile.begin_item(xrow0, hp);
+    // ---- side loads, in front of the main loop's own pieces (the previous tile's attention is over: barrier at the bottom of the loop): bias, side rows ----------
+    tile.issue_bias();
     if (wave < 4) {                                                 // side rows: chunk x = ((hd * 5 + srow) * 3 + which) * 8 + ch, 240 chunks of 16 B
       const int x = wave * 64 + lane;
       if (x < 240) {
         const int ch = x & 7, w3 = (x >> 3) % 3, hs = (x >> 3) / 3, srow = hs % 5, hd = hs / 5;
-        const uint32_t voff = (uint32_t)(((srow == 0 ? 0 : 1 + f * 4 + (srow - 1)) * p.lds_ + w3 * QS_D + hd * 64 + ch * 8) * 2);
-        qs_dma1(voff, reinterpret_cast<const char*>(p.side + seq * 33 * p.lds_ + hp * 128), lds0 + QS_SIDE_OFF + wave * 1024);
+        const uint32_t voff = (uint32_t)(((srow == 0 ? 0 : 1 + f * 4 + (srow - 1)) * p.lds_ + w3 * QKT_D + hd * 64 + ch * 8) * 2);
+        qkt_dma1(voff, reinterpret_cast<const char*>(p.side + seq * 33 * p.lds_ + hp * 128), lds0 + QS_SIDE_OFF + wave * 1024);
       }
     }
-    if (MX) issue_sc(0);
-    issue_w(0, 0, 0); issue_a(0, 0, 0);
-    issue_w(1, 0, 0); issue_a(1, 0, 0); issue_a(2, 0, 0);
-    issue_w(2, 0, 0);
-    issue_w(0, 1, 1); issue_a(0, 1, 1);
-    if (!(QS_ABL & 32)) qs_wait_vmcnt<5>();                         // bias, side rows, A | W0 | W1 of k-tile 0 (this wave's pieces) have landed   (ABL 32: WRONG results - what does this wait cost?)
-    qs_barrier();
-
-    // accumulators start at the bias: block (j, i) = features 96 wn + 32 j + 8 g + 4 hi + r of the tile, tokens 96 wm + 32 i + l31
     f32x16 acc[3][3];
-    {
-      const float* bs = reinterpret_cast<const float*>(smem + QS_BIAS_OFF);
-#pragma unroll
-      for (int j = 0; j < 3; ++j)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const float4 b4 = p.bias ? *reinterpret_cast<const float4*>(bs + wn * 96 + j * 32 + g * 8 + hi * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-          for (int i = 0; i < 3; ++i) { acc[j][i][g * 4 + 0] = b4.x; acc[j][i][g * 4 + 1] = b4.y; acc[j][i][g * 4 + 2] = b4.z; acc[j][i][g * 4 + 3] = b4.w; }
-        }
-    }
-    {
-      int fo[4], fs_x = 0, fs_w = 0, shi = 0;                       // (MX: addresses of this lane's scale dwords - its token row of block 0, row l31 of its W part 0 - and 8 * (lane >> 5))
-      {
-        int ptid = threadIdx.x;
-        asm volatile("" : "+v"(ptid));
-        const int pl31 = ptid & 31, phi = (ptid & 63) >> 5;
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) fo[kk] = pl31 * 128 + (((kk * 2 + phi) ^ ((pl31 >> 1) & 7)) << 4);
-        if (MX) { fs_x = QS_SC_OFF + (wm * 96 + pl31) * 4; fs_w = QS_SC_OFF + 768 + (wn * 32 + pl31) * 4; shi = phi * 8; }
-      }
-      const int a_base = wm * 96 * 128, w_base = QS_A_BYTES + wn * 32 * 128;
-      // fragments as 32-byte pairs (kk = 2 k2, 2 k2 + 1): the two 16-byte reads a lane supplies to ONE 64-deep scaled MFMA sit in eight consecutive registers, no copies
-      union QsFrag { bf16x8 h[2]; qs_i32x8 v; };
-      QsFrag xf[3][2], wf[2];
-      uint32_t sx[3] = {0u, 0u, 0u}, sw = 0u;                        // MX: this lane's scale dwords of the k-tile (token row of block i; W row of the current part), >> shi
-      auto read_w = [&](const char* st, int j, int par) {
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) wf[kk >> 1].h[kk & 1] = *reinterpret_cast<const bf16x8*>(st + w_base + j * QS_W_PART + fo[kk]);
-        if (MX) sw = *reinterpret_cast<const uint32_t*>(smem + fs_w + j * 512 + par * QS_SC_BYTES) >> shi;
-      };
-      auto mma = [&](auto Jc) {
-        constexpr int J = decltype(Jc)::value;
-        __builtin_amdgcn_s_setprio(1);
-        if constexpr (MX) {
-          // a 128-byte LDS row = 128 fp8 k: fragments 2 k2 and 2 k2 + 1 are the 2 x 16 bytes a lane supplies to ONE 64-deep scaled MFMA (as qkv_time_attn_kernel<true, true>)
-#pragma unroll
-          // scale operands: the k-tile's dword of the row, shifted by 8 * (lane >> 5) so that BYTE 2 k2 is this half-wave's 32-k block of MFMA k2 - selected by the
-          // instruction's op_sel (byte index of the scale register), no extraction arithmetic inside the matrix segment
-          for (int k2 = 0; k2 < 2; ++k2) {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-              if (k2 == 0) acc[J][i] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wf[0].v, xf[i][0].v, acc[J][i], 0 /* e4m3 */, 0 /* e4m3 */, 0, (int)sw, 0, (int)sx[i]);
-              else acc[J][i] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wf[1].v, xf[i][1].v, acc[J][i], 0, 0, 2, (int)sw, 2, (int)sx[i]);
-            }
-          }
-        } else
-        if (!(QS_ABL & 2)) {
-#pragma unroll
-          for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-            for (int i = 0; i < 3; ++i) acc[J][i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[kk >> 1].h[kk & 1], xf[i][kk >> 1].h[kk & 1], acc[J][i], 0, 0, 0);
-        } else asm volatile("" :: "v"(wf[0].v), "v"(wf[1].v), "v"(xf[0][0].v), "v"(xf[2][1].v));
-        asm volatile("" : "+v"(acc[J][0]), "+v"(acc[J][1]), "+v"(acc[J][2]));   // pins the (pure) MFMAs inside their matrix segment
-        __builtin_amdgcn_s_setprio(0);
-      };
-      // one k-tile held in stage S; ld1 / ld2: k-tiles kt+1 / kt+2 exist
-      auto ktile = [&](auto Sc, int kt, bool ld1, bool ld2) {
-        constexpr int S = decltype(Sc)::value;
-        const char* st = smem + S * QS_STAGE;
-        // ---- phase 0: feature block 0 ----
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-          for (int kk = 0; kk < 4; ++kk) xf[i][kk >> 1].h[kk & 1] = *reinterpret_cast<const bf16x8*>(st + a_base + i * 4096 + fo[kk]);
-        read_w(st, 0, S);                                            // (nk is even: the parity of k-tile kt is the stage S)
-        if (MX) {
-#pragma unroll
-          for (int i = 0; i < 3; ++i) sx[i] = *reinterpret_cast<const uint32_t*>(smem + fs_x + i * 128 + S * QS_SC_BYTES) >> shi;
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (ld1) { issue_w(1, S ^ 1, kt + 1); issue_a(1, S ^ 1, kt + 1); issue_a(2, S ^ 1, kt + 1); }      // W1, A1, A2 of k-tile kt+1
-        qs_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        mma(qs_ic<0>{});
-        __builtin_amdgcn_sched_barrier(0);
-        qs_barrier();
-        // ---- phase 1: feature block 1 ----
-        read_w(st, 1, S);
-        __builtin_amdgcn_sched_barrier(0);
-        // (MX: the scale piece of k-tile kt+1 goes in FRONT of W2 - the phase-2 wait below then retires it with A | W0 | W1 - into the other parity's area, last read in phase 0 of kt-1)
-        if (ld1) { if (MX) issue_sc(kt + 1); issue_w(2, S ^ 1, kt + 1); if (MX) qs_wait_vmcnt<10>(); else qs_wait_vmcnt<9>(); } else qs_wait_vmcnt<0>();   // W2 of k-tile kt+1 issued; W2 of this k-tile has landed
-        qs_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        mma(qs_ic<1>{});
-        __builtin_amdgcn_sched_barrier(0);
-        qs_barrier();
-        // ---- phase 2: feature block 2 ----
-        read_w(st, 2, S);
-        __builtin_amdgcn_sched_barrier(0);
-        if (ld2) { issue_w(0, S, kt + 2); issue_a(0, S, kt + 2); qs_wait_vmcnt<5>(); }                     // W0, A0 of k-tile kt+2; A | W0 | W1 of k-tile kt+1 have landed
-        else if (ld1) qs_wait_vmcnt<2>();
-        else qs_wait_vmcnt<0>();
-        qs_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        mma(qs_ic<2>{});
-        __builtin_amdgcn_sched_barrier(0);
-        qs_barrier();
-      };
-      if (wm == 1) qs_barrier();                                    // waves 4-7 run one barrier behind waves 0-3
-#pragma unroll 1
-      for (int kt = 0; kt < nk; kt += 2) {
-        ktile(qs_ic<0>{}, kt, true, kt + 2 < nk);
-        ktile(qs_ic<1>{}, kt + 1, kt + 2 < nk, kt + 3 < nk);
-      }
-      if (wm == 0) qs_barrier();                                    // re-align; every wave is done with both stages
-    }
+    tile.project(acc);
 
     // ---- epilogue (1): accumulators -> bf16 -> the attention's K | V | Q arrays (they overlay the operand stages) ---------------------------------------
     {
@@ -329,7 +103,7 @@ __device__ __forceinline__ void qkv_space_attn_body(const QsArgs& p) {
       // MASK: the group's key flags -> additive score terms (the S accumulators START at them: 0 or -inf, no arithmetic in the softmax); the byte loads fly under the hand-over
       uint8_t kflag = 1;
       if (MASK && etid >= 256 && etid < 256 + QS_TOK + 1) { const int k = etid - 256; kflag = k == 0 ? p.key_keep[seq * p.seq_rows] : p.key_keep[xrow0 + k - 1]; }
-      qs_barrier();
+      qkt_barrier();
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
         const int cb = (wn * 3 + j) * 32;                           // first tile column of the block (wave-uniform)
@@ -361,7 +135,7 @@ __device__ __forceinline__ void qkv_space_attn_body(const QsArgs& p) {
         const int x = etid - 256, ch = x & 7, rr = (x >> 3) % 11, hd = (x >> 3) / 11;
         *reinterpret_cast<uint4*>(smem + hd * 3 * QS_ARR + QS_ARR + qs_arr_off(QS_TOK + 1 + rr, ch)) = make_uint4(0u, 0u, 0u, 0u);
       }
-      qs_barrier();
+      qkt_barrier();
     }
 
     // ---- epilogue (2): the space attention of (frame, head), the arithmetic of attn_mfma_kernel<64, 13> -----------------------------------------------------
@@ -474,10 +248,10 @@ __device__ __forceinline__ void qkv_space_attn_body(const QsArgs& p) {
           }
 #pragma unroll
           for (int dt = 0; dt < 4; ++dt) {
-            union { bf16x8 v; qs_s4 hh[2]; } vb;
-            vb.hh[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((qs_lds_s4*)(v_lds + v_off[dt] + kk * 32 * 128));
-            vb.hh[1] = qs_s4{0, 0, 0, 0};
-            if (2 * kk + 1 < NKT) vb.hh[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((qs_lds_s4*)(v_lds + v_off[dt] + (kk * 32 + 16) * 128));
+            union { bf16x8 v; qkt_s4 hh[2]; } vb;
+            vb.hh[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((qkt_lds_s4*)(v_lds + v_off[dt] + kk * 32 * 128));
+            vb.hh[1] = qkt_s4{0, 0, 0, 0};
+            if (2 * kk + 1 < NKT) vb.hh[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((qkt_lds_s4*)(v_lds + v_off[dt] + (kk * 32 + 16) * 128));
             o[0][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vb.v, pa[0].v, o[0][dt], 0, 0, 0);
             if (NT == 2) o[1][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vb.v, pa[1].v, o[1][dt], 0, 0, 0);
           }
@@ -577,14 +351,14 @@ __device__ __forceinline__ void qkv_space_attn_body(const QsArgs& p) {
         // four units u, u + 4, u + 8, u + 12 share a SIMD (waves w, w + 4), so the two SIMDs with four units are the ones that hold a single: 7 | 7 | 6 | 6 tiles
         const int u = ((wave + (int)tcount) & 7) + 8 * uu;         // wave-uniform
         if (u >= 14) break;
-        if (u < 12) { const int h = u >= 6 ? 1 : 0, pu = u - 6 * h; unit(qs_ic<2>{}, h, 2 * pu, 2 * pu + 1); }
-        else unit(qs_ic<1>{}, u - 12, 12, 12);
+        if (u < 12) { const int h = u >= 6 ? 1 : 0, pu = u - 6 * h; unit(qkt_ic<2>{}, h, 2 * pu, 2 * pu + 1); }
+        else unit(qkt_ic<1>{}, u - 12, 12, 12);
       }
     }
-    qs_barrier();                                                   // every wave is out of the attention arrays: the next tile's operands may land
-    t += per_xcd_blocks;
+    qkt_barrier();                                                   // every wave is out of the attention arrays: the next tile's operands may land
+    t += sched.step;
     ++tcount;
-    if (t >= t_end) break;
+    if (t >= sched.t_end) break;
   }
 }
 
@@ -597,41 +371,21 @@ __global__ __launch_bounds__(512, 2) void qkv_space_attn_masked_kernel(QsArgs p)
 // caller with sf_gemm_bf16 on a gathered copy of those rows; out (rows as X, 768) bf16: the PATCH rows are written (row 0 of every sequence comes from
 // sf_attention_cls_combine on cls_partial [n_seq][12][8][66] fp32, one record per frame as sf_attention_cls_partial writes them).  out must not alias X (other workgroups
 // still read X).  Reference: vit_helper.py:97-150 with the '(b f) n d' groups of :341-342, heads = 12, head dim 64, q scaled by `scale` (vit_helper.py:113).
-static int qs_launch(const uint16_t* X, int64_t ldx, const uint16_t* W, int64_t ldw, const float* bias, const uint16_t* side, int64_t lds_,
-                     uint16_t* out, int64_t ldo, float* cls_partial, int64_t n_seq, int n_tok, float scale, const uint8_t* key_keep, void* stream) {
-  SF_CHECK_ARG(X && W && side && out && cls_partial, "sf_qkv_space_attention: null pointer");
-  SF_CHECK_ARG(n_tok == QS_TOK, "sf_qkv_space_attention: built for 196-token frames (8 frames per sequence), got %d", n_tok);
-  SF_CHECK_ARG((ldx % 64) == 0 && (ldw % 64) == 0 && (lds_ % 8) == 0 && (ldo % 8) == 0 && ldx >= QS_D && ldw >= QS_D && lds_ >= 3 * QS_D && ldo >= QS_D,
-               "sf_qkv_space_attention: bad row strides (ldx / ldw multiples of 64 elements: the chunk slot lives in the low 7 bits of a piece's byte offset)");
-  SF_CHECK_ARG(((uintptr_t)X % 16) == 0 && ((uintptr_t)W % 16) == 0 && ((uintptr_t)side % 16) == 0 && ((uintptr_t)out % 16) == 0 && (!bias || ((uintptr_t)bias % 16) == 0) &&
-                   ((uintptr_t)cls_partial % 8) == 0, "sf_qkv_space_attention: operands must be 16-byte aligned");
-  SF_CHECK_ARG((const void*)X != (const void*)out, "sf_qkv_space_attention: out must not alias X");
-  if (n_seq <= 0) return 0;
-  const int64_t seq_rows = 1 + 8 * (int64_t)QS_TOK;
-  SF_CHECK_ARG((int64_t)QS_TOK * ldx * 2 < ((int64_t)1 << 32) && (int64_t)3 * QS_D * ldw * 2 < ((int64_t)1 << 32) && (int64_t)33 * lds_ * 2 < ((int64_t)1 << 32),
-               "sf_qkv_space_attention: a frame of X, W and a sequence's side rows must stay below 4 GiB (32-bit lane offsets)");
-  SF_CHECK_ARG(n_seq * 8 * 6 < ((int64_t)1 << 31), "sf_qkv_space_attention: too many tiles");
-  if (int rc = sf_prepare_kernel(key_keep ? (const void*)qkv_space_attn_masked_kernel : (const void*)qkv_space_attn_kernel, QS_LDS, "sf_qkv_space_attention")) return rc;
-  const int n_cu = sf_cu_count("sf_qkv_space_attention");
-  if (n_cu <= 0) return -1;
+static const QktLaunch QS_BF16 = {"sf_qkv_space_attention", "196-token frames", "a frame", QS_TOK, 8, false};
+static const QktLaunch QS_MX = {"sf_qkv_space_attention_mx", "196-token frames", "a frame", QS_TOK, 8, true};
+
+static int qs_launch_bf16(const uint16_t* X, int64_t ldx, const uint16_t* W, int64_t ldw, const float* bias, const uint16_t* side, int64_t lds_,
+                          uint16_t* out, int64_t ldo, float* cls_partial, int64_t n_seq, int n_tok, float scale, const uint8_t* key_keep, void* stream) {
   QsArgs a;
   a.X = X; a.ldx = ldx; a.W = W; a.ldw = ldw; a.bias = bias; a.side = side; a.lds_ = lds_; a.out = out; a.ldo = ldo; a.cls_part = cls_partial;
-  a.seq_rows = seq_rows; a.n_frames = (uint32_t)(n_seq * 8); a.scale = scale; a.key_keep = key_keep;
-  static int env_hc = -1;
-  if (env_hc < 0) { const char* e = getenv("SF_QS_PAIR_CHUNK"); env_hc = e ? atoi(e) : 6; if (env_hc < 1 || 6 % env_hc) env_hc = 6; }
+  a.scale = scale; a.key_keep = key_keep;
+  static const int env_hc = qkt_env_pair_chunk("SF_QS_PAIR_CHUNK");
   a.pair_chunk = (uint32_t)env_hc;
-  int64_t blocks = (n_cu / 8) * 8;                               // one workgroup per CU, a multiple of the 8 XCD slots of the tile schedule (blockIdx % 8) ...
-  if (blocks < 8) blocks = 8;                                    // ... and never an empty grid on a device / partition with fewer than 8 CUs
-  const int64_t need = ((n_seq * 8 * 6 + 7) / 8) * 8;
-  if (blocks > need) blocks = need;
-  if (key_keep) hipLaunchKernelGGL(qkv_space_attn_masked_kernel, dim3((unsigned)blocks), dim3(512), QS_LDS, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(qkv_space_attn_kernel, dim3((unsigned)blocks), dim3(512), QS_LDS, (hipStream_t)stream, a);
-  SF_LAUNCH_CHECK();
-  return 0;
+  return qkt_launch(QS_BF16, key_keep ? qkv_space_attn_masked_kernel : qkv_space_attn_kernel, a, n_seq, n_tok, stream);
 }
 extern "C" int sf_qkv_space_attention(const uint16_t* X, int64_t ldx, const uint16_t* W, int64_t ldw, const float* bias, const uint16_t* side, int64_t lds_,
                                       uint16_t* out, int64_t ldo, float* cls_partial, int64_t n_seq, int n_tok, float scale, void* stream) {
-  return qs_launch(X, ldx, W, ldw, bias, side, lds_, out, ldo, cls_partial, n_seq, n_tok, scale, nullptr, stream);
+  return qs_launch_bf16(X, ldx, W, ldw, bias, side, lds_, out, ldo, cls_partial, n_seq, n_tok, scale, nullptr, stream);
 }
 // The same launch with TOKEN MASKS (Synchformer.forward(vis_mask=...), sync_model.py:72-80 -> the -inf key masks of vit_helper.py:107-141): key_keep holds one byte per
 // row of X; a row with flag 0 is a masked KEY for every query of its frame's group and for the CLS query (its own output row is still computed, as in the reference).
@@ -639,7 +393,7 @@ extern "C" int sf_qkv_space_attention(const uint16_t* X, int64_t ldx, const uint
 extern "C" int sf_qkv_space_attention_masked(const uint16_t* X, int64_t ldx, const uint16_t* W, int64_t ldw, const float* bias, const uint16_t* side, int64_t lds_,
                                              uint16_t* out, int64_t ldo, float* cls_partial, int64_t n_seq, int n_tok, float scale, const uint8_t* key_keep, void* stream) {
   SF_CHECK_ARG(key_keep, "sf_qkv_space_attention_masked: null key_keep (call sf_qkv_space_attention for an unmasked forward)");
-  return qs_launch(X, ldx, W, ldw, bias, side, lds_, out, ldo, cls_partial, n_seq, n_tok, scale, key_keep, stream);
+  return qs_launch_bf16(X, ldx, W, ldw, bias, side, lds_, out, ldo, cls_partial, n_seq, n_tok, scale, key_keep, stream);
 }
 
 // The same launch on MXFP8 operands (fp8 towers of the synchronizability fine-tune): X (rows, 768) e4m3 bytes with its stage-major scale planes sX (6 planes, ldsx bytes
@@ -651,33 +405,9 @@ extern "C" int sf_qkv_space_attention_masked(const uint16_t* X, int64_t ldx, con
 extern "C" int sf_qkv_space_attention_mx(const uint8_t* X, int64_t ldx, const uint8_t* sX, int64_t ldsx, const uint8_t* W, int64_t ldw, const uint8_t* sW, int64_t ldsw,
                                          const float* bias, const uint16_t* side, int64_t lds_, uint16_t* out, int64_t ldo, uint8_t* out_q, int64_t ldq, uint8_t* out_s,
                                          int64_t splane, float* cls_partial, int64_t n_seq, int n_tok, float scale, void* stream) {
-  SF_CHECK_ARG(X && sX && W && sW && side && cls_partial && ((out != nullptr) != (out_q != nullptr)), "sf_qkv_space_attention_mx: null pointer (exactly one of out / out_q)");
-  SF_CHECK_ARG(n_tok == QS_TOK, "sf_qkv_space_attention_mx: built for 196-token frames (8 frames per sequence), got %d", n_tok);
-  SF_CHECK_ARG((ldx % 128) == 0 && (ldw % 128) == 0 && ldx >= QS_D && ldw >= QS_D && (lds_ % 8) == 0 && lds_ >= 3 * QS_D, "sf_qkv_space_attention_mx: bad row strides (ldx / ldw multiples of 128 bytes)");
-  SF_CHECK_ARG(((uintptr_t)X % 16) == 0 && ((uintptr_t)W % 16) == 0 && ((uintptr_t)sX % 16) == 0 && ((uintptr_t)sW % 16) == 0 && ((uintptr_t)side % 16) == 0 &&
-                   (!bias || ((uintptr_t)bias % 16) == 0) && ((uintptr_t)cls_partial % 8) == 0, "sf_qkv_space_attention_mx: operands must be 16-byte aligned");
-  if (out) SF_CHECK_ARG(((uintptr_t)out % 16) == 0 && (ldo % 8) == 0 && ldo >= QS_D, "sf_qkv_space_attention_mx: out must be a 16-byte aligned bf16 buffer");
-  if (out_q) SF_CHECK_ARG(out_s && ((uintptr_t)out_q % 8) == 0 && ((uintptr_t)out_s % 2) == 0 && (ldq % 8) == 0 && ldq >= QS_D && out_q != X && out_s != sX,
-                          "sf_qkv_space_attention_mx: out_q (8-byte aligned, ldq %% 8 == 0) / out_s must be buffers of their own");
-  if (n_seq <= 0) return 0;
-  const int64_t seq_rows = 1 + 8 * (int64_t)QS_TOK;
-  if (out_q) SF_CHECK_ARG(splane >= n_seq * seq_rows * 4, "sf_qkv_space_attention_mx: a scale plane holds 4 bytes per row");
-  SF_CHECK_ARG((ldsx % 16) == 0 && (ldsw % 16) == 0 && ldsx >= n_seq * seq_rows * 4 && ldsw >= 3 * QS_D * 4, "sf_qkv_space_attention_mx: scale planes must hold one dword per row of X / W");
-  SF_CHECK_ARG((int64_t)QS_TOK * ldx < ((int64_t)1 << 32) && (int64_t)3 * QS_D * ldw < ((int64_t)1 << 32) && (int64_t)33 * lds_ * 2 < ((int64_t)1 << 32),
-               "sf_qkv_space_attention_mx: a frame of X, W and a sequence's side rows must stay below 4 GiB (32-bit lane offsets)");
-  SF_CHECK_ARG(n_seq * 8 * 6 < ((int64_t)1 << 31), "sf_qkv_space_attention_mx: too many tiles");
-  if (int rc = sf_prepare_kernel((const void*)qkv_space_attn_mx_kernel, QS_LDS, "sf_qkv_space_attention_mx")) return rc;
-  const int n_cu = sf_cu_count("sf_qkv_space_attention_mx");
-  if (n_cu <= 0) return -1;
   QsArgs a;
   a.X = reinterpret_cast<const bf16_t*>(X); a.ldx = ldx; a.W = reinterpret_cast<const bf16_t*>(W); a.ldw = ldw; a.bias = bias; a.side = side; a.lds_ = lds_;
-  a.out = out; a.ldo = ldo; a.cls_part = cls_partial; a.seq_rows = seq_rows; a.n_frames = (uint32_t)(n_seq * 8); a.scale = scale; a.pair_chunk = 6;
+  a.out = out; a.ldo = ldo; a.cls_part = cls_partial; a.scale = scale; a.pair_chunk = 6;
   a.sX = sX; a.ldsx = ldsx; a.sW = sW; a.ldsw = ldsw; a.out_q = out_q; a.ldq = ldq; a.out_s = out_s; a.splane = splane;
-  int64_t blocks = (n_cu / 8) * 8;                               // one workgroup per CU, a multiple of the 8 XCD slots of the tile schedule (blockIdx % 8) ...
-  if (blocks < 8) blocks = 8;                                    // ... and never an empty grid on a device / partition with fewer than 8 CUs
-  const int64_t need = ((n_seq * 8 * 6 + 7) / 8) * 8;
-  if (blocks > need) blocks = need;
-  hipLaunchKernelGGL(qkv_space_attn_mx_kernel, dim3((unsigned)blocks), dim3(512), QS_LDS, (hipStream_t)stream, a);
-  SF_LAUNCH_CHECK();
-  return 0;
+  return qkt_launch(QS_MX, qkv_space_attn_mx_kernel, a, n_seq, n_tok, stream);
 }

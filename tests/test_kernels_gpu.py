@@ -1,10 +1,16 @@
 """Per-kernel parity on the GPU: each `sf_*` entry point (called through the C ABI via synchformer_amd.ops)
 against a plain fp32 torch evaluation of the same op on the same (bf16-rounded) operands.
 Tolerances: outputs are bf16 (rel 2^-8) or fp32 sums of bf16 products; stated per test."""
+import json
 import math
+import os
+import sys
 
 import pytest
 import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden'))
+import make_qkv_fused_digests as QD  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -1379,3 +1385,23 @@ def test_qkv_space_attention_mx(gpu, n_seq):
     patch = torch.ones(n_seq, L, dtype=torch.bool, device=gpu); patch[:, 0] = False
     patch = patch.reshape(-1)
     assert torch.equal(oq[patch], wq_[patch]) and torch.equal(os_[:, :rows][:, patch], ws_[:, :rows][:, patch]) and torch.equal(part2, part)
+
+
+@pytest.fixture(scope='module')
+def qkv_fused_digests():
+    with open(QD.OUT) as f:
+        return json.load(f)['cases']
+
+
+@pytest.mark.parametrize('name', list(QD.CASES))
+def test_qkv_fused_outputs_are_pinned(gpu, qkv_fused_digests, name):
+    """The parity tests above allow a bf16 ulp against other kernels and would pass a changed order of the k sum, and a race that a wrong wait count of the shared main loop
+    (csrc/sf_qkv_tile.h) opens need not move a value past it; this one holds the output BYTES of every launch form of sf_qkv_space_attention / sf_qkv_time_attention2
+    (plain, key_keep, _mx to bf16, _mx to MXFP8; without bias; on strided operands; with fewer items than workgroups and with several items per workgroup -
+    tests/golden/make_qkv_fused_digests.py lists the cases) to the SHA-256 recorded once from the library of the commit the file names.  The input's own digest is checked
+    first: a mismatch there is a changed random stream, not a changed kernel."""
+    assert set(qkv_fused_digests) == set(QD.CASES)
+    src, out = QD.CASES[name](gpu)
+    torch.cuda.synchronize()
+    assert QD.sha256(*src) == qkv_fused_digests[name]['input'], f'{name}: the generated INPUT differs from the recorded one'
+    assert QD.sha256(*out) == qkv_fused_digests[name]['output'], f'{name}: output bytes differ from the recording'
