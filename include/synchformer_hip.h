@@ -29,7 +29,7 @@ extern "C" {
 enum { SF_F32 = 0, SF_BF16 = 1, SF_F16 = 2, SF_U8 = 3, SF_I16 = 4 };   /* element types (SF_I16: PCM input of sf_resample_wave only) */
 enum { SF_EPI_NONE = 0, SF_EPI_GELU = 1 };                  /* GEMM epilogue activation */
 
-#define SF_ABI_VERSION 19
+#define SF_ABI_VERSION 20
 int sf_abi_version(void);
 const char* sf_last_error(void);
 /* "gfx950" + build flags; lets the host assert it loaded the library it built */
@@ -566,6 +566,32 @@ int sf_track_stream_workspace_bytes(int C, int n, int posterior);
 int sf_track_stream_push(void* state, int C, int lag, int posterior, int64_t rows_done, const float* logits, int64_t ldl, int n, float lam, const float* grid,
                          int final, int32_t* cls_raw, float* conf_raw, int32_t* cls_lag, float* conf_lag, float* post_lag, int64_t ldp, int32_t* cls_post_lag,
                          float* conf_post_lag, float* offset_mean_lag, int32_t* cls_tail, float* conf_tail, float* log_z, void* workspace, void* stream);
+
+/* The same read-out for MANY streams in one call (ABI v20): sf_track_pool_push advances the states of n_active streams that share C, lag and posterior.  For every
+ * stream the outputs and the state bytes are those of sf_track_stream_push on that stream alone, bit for bit (the kernels call the same device functions); the number
+ * of launches does not depend on n_active: the same at-most-four kinds (row statistics, scans, read-out, rings).
+ * states: one caller-owned device buffer of n_slots states, state i at byte i * state_stride; state_stride a multiple of 16 and at least
+ *   sf_track_stream_bytes(C, lag, posterior); the layout of one state is sf_track_stream_push's.  A state is read only when its rows_done > 0.
+ * table: n_active rows of 8 int64, one per stream of this push:
+ *     [0] slot       which state (distinct, < n_slots)            [4] final     != 0 closes the stream (as sf_track_stream_push's final)
+ *     [1] rows_done  rows pushed into that state so far           [5] commit0   where its committed block starts in cls_lag .. offset_mean_lag (post_lag: row commit0)
+ *     [2] n          its new rows in this push (0 allowed)        [6] tail0     where its tail starts in cls_tail / conf_tail
+ *     [3] row0       its rows are rows [row0, row0 + n) of logits [7] unused, 0
+ *   passed twice: table_host (the launcher validates it and sizes its grids from it) and table_dev (a device copy the caller has uploaded, in stream order before
+ *   this call; the kernels read it).  commit0 / tail0 are the running sums of sf_track_stream_push's n_commit / n_tail in table order: the blocks lie back to back.
+ * logits (total_rows, C) fp32 with row stride ldl >= C: the new rows of all streams; the row ranges are disjoint and inside total_rows (gaps are allowed: their
+ *   cls_raw / conf_raw are written from whatever the rows hold).  cls_raw / conf_raw (total_rows) are indexed like logits.  log_z (posterior): one float per table row,
+ *   written for every stream that holds at least one row after the push.  workspace: sf_track_pool_workspace_bytes(C, total_rows, posterior) bytes, caller-owned,
+ *   dead after the push; stream e's part is addressed by its row0.
+ * 1 <= n_active <= 4096, total_rows <= 2^20; C, lag, lam as sf_track_stream_push.  -1 and a message, before anything is launched, for: a bad C / lag / lam / stride,
+ * n_active out of range, a slot twice or >= n_slots, overlapping or outlying row ranges, commit0 / tail0 that are not the running sums, a null pointer for a block
+ * that is not empty.  The launcher reads nothing back, allocates nothing on the device and synchronises nothing.  Block-to-work mapping: blockIdx.y = table row,
+ * blockIdx.x = the stream's own work item (scan / committed window or tail / ring row), blocks beyond a stream's count exit at once. */
+int sf_track_pool_workspace_bytes(int C, int total_rows, int posterior);
+int sf_track_pool_push(void* states, int64_t state_stride, int n_slots, int C, int lag, int posterior, const int64_t* table_host, const int64_t* table_dev,
+                       int n_active, const float* logits, int64_t ldl, int total_rows, float lam, const float* grid, int32_t* cls_raw, float* conf_raw,
+                       int32_t* cls_lag, float* conf_lag, float* post_lag, int64_t ldp, int32_t* cls_post_lag, float* conf_post_lag, float* offset_mean_lag,
+                       int32_t* cls_tail, float* conf_tail, float* log_z, void* workspace, void* stream);
 
 /* ---- Ingest of a decoded recording at its native frame rate, size and sample rate: the step the reference leaves to an ffmpeg subprocess in front of its code
  * (example.py:16-53: fps=25, short side 256, even dimensions, -ar 16000), plus the centre 224 crop of RGBSpatialCrop (dataset/transforms.py:68-95).  The host

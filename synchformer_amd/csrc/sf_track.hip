@@ -15,8 +15,12 @@
 // and the forward-backward algorithm gives post[w, c] = p(c_w = c) and log_z = log of the sum over all paths.  Two launches:
 //   1. track_fb_scan_kernel:     TWO workgroups of one wavefront each, side by side: block 0 the forward scan (a, and log_z), block 1 the backward scan (b);
 //   2. track_fb_combine_kernel:  one thread per window: post = softmax_c (a + b), its argmax and value, the posterior mean of the grid.
+//
+// sf_track_stream_push (further below) reads a stream of rows out at a fixed lag with carried state; sf_track_pool_push (at the end) does that for many streams
+// in one call: the same launches over a descriptor table, blockIdx.y = the stream, every block running the single-stream device functions on its stream's context.
 #include "sf_common.h"
 #include "../../include/synchformer_hip.h"
+#include <algorithm>
 #include <cmath>
 
 #define TRACK_MAX_C 64
@@ -331,14 +335,14 @@ __device__ __forceinline__ int track_wave_end_state(float s, bool live) {
   return hit ? __ffsll((long long)hit) - 1 : 0;
 }
 
-__global__ __launch_bounds__(64) void track_stream_scan_kernel(const float* __restrict__ logits, int64_t ldl, int n, int C, float lam, int64_t t_old,
-                                                                unsigned char* __restrict__ state, int lag, int posterior, uint8_t* __restrict__ bp_new,
-                                                                float* __restrict__ a_new, int32_t* __restrict__ end_new, float* __restrict__ log_z) {
-  __shared__ __attribute__((aligned(16))) float s_u[TRACK_MAX_C];
+// The scan of one stream's push, by one wavefront: fwd = false the Viterbi scan, fwd = true the forward scan (wave-uniform).  s_u: TRACK_MAX_C floats of LDS, 16-byte
+// aligned.  The single-stream kernel and the pool's kernel (sf_track_pool_push) both run this body: one stream's arithmetic is the same in either.
+__device__ __forceinline__ void track_stream_scan_body(const float* __restrict__ logits, int64_t ldl, int n, int C, float lam, int64_t t_old,
+                                                       unsigned char* __restrict__ state, int lag, int posterior, uint8_t* __restrict__ bp_new,
+                                                       float* __restrict__ a_new, int32_t* __restrict__ end_new, float* __restrict__ log_z, bool fwd, float* s_u) {
   const TrackStreamLayout lay(C, lag, posterior != 0);
   const int c = threadIdx.x;
   const bool live = c < C;
-  const bool fwd = blockIdx.x == 1;                               // wave-uniform
   const int C4 = (C + 3) & ~3;
   const float ninf = -INFINITY;
   float* carried = reinterpret_cast<float*>(state + (fwd ? lay.a : lay.s));
@@ -400,6 +404,13 @@ __global__ __launch_bounds__(64) void track_stream_scan_kernel(const float* __re
   }
 }
 
+__global__ __launch_bounds__(64) void track_stream_scan_kernel(const float* __restrict__ logits, int64_t ldl, int n, int C, float lam, int64_t t_old,
+                                                                unsigned char* __restrict__ state, int lag, int posterior, uint8_t* __restrict__ bp_new,
+                                                                float* __restrict__ a_new, int32_t* __restrict__ end_new, float* __restrict__ log_z) {
+  __shared__ __attribute__((aligned(16))) float s_u[TRACK_MAX_C];
+  track_stream_scan_body(logits, ldl, n, C, lam, t_old, state, lag, posterior, bp_new, a_new, end_new, log_z, blockIdx.x == 1, s_u);      // block 1: the forward scan
+}
+
 // Follows the back pointers of rows R .. w + 1 from class `cur` (the class at row R) -> the class at row w.  Lane c loads backptr[r, c] of eight rows at a time, the
 // chain itself is eight wave-uniform shuffles.  KEEP: tail[r - w] = the class at row r, for every r in [w, R] (LDS, written by lane 0).
 template <bool KEEP>
@@ -424,19 +435,17 @@ __device__ __forceinline__ int track_stream_backtrace(const TrackStreamRows& row
 
 // Block i < n_commit: window w = w0 + i, read from the prefix that ends at row R = min(w + lag, t_last).  Block n_commit (if n_tail > 0): the tail, the path of the
 // whole prefix on the last n_tail rows.
+// bx = the block's index among the stream's n_commit + (n_tail > 0) blocks; s_u (16-byte aligned) / s_b: TRACK_MAX_C floats of LDS each, s_tail: 256 ints.
 template <bool POST>
-__global__ __launch_bounds__(64) void track_stream_readout_kernel(TrackStreamRows rows, float lam, const float* __restrict__ grid, int64_t w0, int n_commit, int n_tail,
-                                                                   int64_t t_last, int32_t* __restrict__ cls_lag, float* __restrict__ conf_lag,
-                                                                   float* __restrict__ post_lag, int64_t ldp, int32_t* __restrict__ cls_post_lag,
-                                                                   float* __restrict__ conf_post_lag, float* __restrict__ offset_mean_lag,
-                                                                   int32_t* __restrict__ cls_tail, float* __restrict__ conf_tail) {
-  __shared__ __attribute__((aligned(16))) float s_u[TRACK_MAX_C];
-  __shared__ float s_b[TRACK_MAX_C];
-  __shared__ int s_tail[256];
+__device__ __forceinline__ void track_stream_readout_body(const TrackStreamRows& rows, float lam, const float* __restrict__ grid, int64_t w0, int n_commit, int n_tail,
+                                                          int64_t t_last, int32_t* __restrict__ cls_lag, float* __restrict__ conf_lag,
+                                                          float* __restrict__ post_lag, int64_t ldp, int32_t* __restrict__ cls_post_lag,
+                                                          float* __restrict__ conf_post_lag, float* __restrict__ offset_mean_lag,
+                                                          int32_t* __restrict__ cls_tail, float* __restrict__ conf_tail, int bx, float* s_u, float* s_b, int* s_tail) {
   const int c = threadIdx.x;
   const int C = rows.C;
   const bool live = c < C;
-  if ((int)blockIdx.x == n_commit) {                               // the tail
+  if (bx == n_commit) {                                            // the tail
     const int64_t w = t_last - (n_tail - 1);
     int cur = rows.end(t_last);
     cur = cur < 0 ? 0 : (cur >= C ? C - 1 : cur);
@@ -452,7 +461,7 @@ __global__ __launch_bounds__(64) void track_stream_readout_kernel(TrackStreamRow
     }
     return;
   }
-  const int i = blockIdx.x;
+  const int i = bx;
   const int64_t w = w0 + i;
   const int64_t R = w + rows.lag < t_last ? w + rows.lag : t_last;
   int cur = rows.end(R);
@@ -495,18 +504,37 @@ __global__ __launch_bounds__(64) void track_stream_readout_kernel(TrackStreamRow
   }
 }
 
-// Block j: new row k = k0 + j (row t_old + k of the stream) into slot (t_old + k) % lag of the rings.
-__global__ __launch_bounds__(64) void track_stream_keep_kernel(const float* __restrict__ logits, int64_t ldl, const uint8_t* __restrict__ bp_new,
-                                                                const float* __restrict__ a_new, int k0, int64_t t_old, int C, int lag, int posterior,
-                                                                unsigned char* __restrict__ state) {
+template <bool POST>
+__global__ __launch_bounds__(64) void track_stream_readout_kernel(TrackStreamRows rows, float lam, const float* __restrict__ grid, int64_t w0, int n_commit, int n_tail,
+                                                                   int64_t t_last, int32_t* __restrict__ cls_lag, float* __restrict__ conf_lag,
+                                                                   float* __restrict__ post_lag, int64_t ldp, int32_t* __restrict__ cls_post_lag,
+                                                                   float* __restrict__ conf_post_lag, float* __restrict__ offset_mean_lag,
+                                                                   int32_t* __restrict__ cls_tail, float* __restrict__ conf_tail) {
+  __shared__ __attribute__((aligned(16))) float s_u[TRACK_MAX_C];
+  __shared__ float s_b[TRACK_MAX_C];
+  __shared__ int s_tail[256];
+  track_stream_readout_body<POST>(rows, lam, grid, w0, n_commit, n_tail, t_last, cls_lag, conf_lag, post_lag, ldp, cls_post_lag, conf_post_lag, offset_mean_lag, cls_tail,
+                                  conf_tail, (int)blockIdx.x, s_u, s_b, s_tail);
+}
+
+// Ring row j of a push: new row k = k0 + j (row t_old + k of the stream) into slot (t_old + k) % lag of the rings.
+__device__ __forceinline__ void track_stream_keep_body(const float* __restrict__ logits, int64_t ldl, const uint8_t* __restrict__ bp_new, const float* __restrict__ a_new,
+                                                       int k0, int64_t t_old, int C, int lag, int posterior, unsigned char* __restrict__ state, int j) {
   const TrackStreamLayout lay(C, lag, posterior != 0);
   const int c = threadIdx.x;
   if (c >= C) return;
-  const int64_t k = k0 + (int64_t)blockIdx.x;
+  const int64_t k = k0 + (int64_t)j;
   const int64_t slot = ((t_old + k) % lag) * C + c;
   reinterpret_cast<float*>(state + lay.lg_ring)[slot] = logits[k * ldl + c];
   (state + lay.bp_ring)[slot] = bp_new[k * C + c];
   if (posterior) reinterpret_cast<float*>(state + lay.a_ring)[slot] = a_new[k * C + c];
+}
+
+// Block j: ring row j.
+__global__ __launch_bounds__(64) void track_stream_keep_kernel(const float* __restrict__ logits, int64_t ldl, const uint8_t* __restrict__ bp_new,
+                                                                const float* __restrict__ a_new, int k0, int64_t t_old, int C, int lag, int posterior,
+                                                                unsigned char* __restrict__ state) {
+  track_stream_keep_body(logits, ldl, bp_new, a_new, k0, t_old, C, lag, posterior, state, (int)blockIdx.x);
 }
 
 static bool track_stream_shape_ok(const char* who, int C, int lag) {
@@ -586,6 +614,185 @@ extern "C" int sf_track_stream_push(void* state, int C, int lag, int posterior, 
   if (keep > 0) {
     hipLaunchKernelGGL(track_stream_keep_kernel, dim3((unsigned)keep), dim3(64), 0, s, logits, ldl, (const uint8_t*)bp_new, (const float*)a_new, n - keep, t_old, C, lag,
                        posterior, st);
+    SF_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+// ---- the same read-out for many streams in one call (sf_track_pool_push) ---------------------------------------------------------------------------------------
+// n_active streams that share C, lag and posterior, named by a descriptor table of 8 int64 per stream (slot, rows_done, n, row0, final, commit0, tail0, unused): the
+// states lie state_stride bytes apart in one buffer, the new rows of all streams in one logits matrix (stream e: rows [row0, row0 + n)), the committed blocks and
+// the tails back to back in table order.  The same four kinds of launch as one stream's push, each over all streams: blockIdx.y = the table row, blockIdx.x = that
+// stream's own work item (its scan / committed window or tail / ring row); the grid's x extent is the largest count in the table and a block beyond its stream's
+// count exits at once (a stream brings 0 .. n rows and commits 0 .. k windows: the mapping is ragged, an idle block costs one table read).  Every block builds its
+// stream's context from the table's DEVICE copy and runs the single-stream bodies above: one stream's bits do not depend on who shares the push.
+#define TRACK_POOL_MAX_ACTIVE 4096
+#define TRACK_POOL_ROW 8
+
+// One table row and sf_track_stream_push's counts for it (host and device: the launcher sizes the grids from the same arithmetic).
+struct TrackPoolEntry {
+  int64_t slot, t_old, n, row0, final, commit0, tail0;
+  int64_t t_new, done_old, n_commit, n_tail;
+  __host__ __device__ TrackPoolEntry(const int64_t* table, int64_t e, int lag) {
+    const int64_t* r = table + e * TRACK_POOL_ROW;
+    slot = r[0];  t_old = r[1];  n = r[2];  row0 = r[3];  final = r[4];  commit0 = r[5];  tail0 = r[6];
+    t_new = t_old + n;
+    done_old = t_old > lag ? t_old - lag : 0;
+    const int64_t done_new = final ? t_new : (t_new > lag ? t_new - lag : 0);
+    n_commit = done_new - done_old;
+    n_tail = t_new - done_new;
+  }
+  __host__ __device__ int64_t readout_blocks() const { return t_new == 0 ? 0 : n_commit + (n_tail > 0 ? 1 : 0); }
+  __host__ __device__ int64_t keep(int lag) const { return n < lag ? n : lag; }
+};
+
+// the workspace of a pool push: sf_track_stream_push's three arrays over total_rows rows; stream e's part starts at its row0
+struct TrackPoolWorkspace {
+  float* a;  int32_t* end;  uint8_t* bp;
+  __host__ __device__ TrackPoolWorkspace(unsigned char* ws, int C, int total_rows, bool posterior) {
+    a = reinterpret_cast<float*>(ws);
+    end = reinterpret_cast<int32_t*>(ws + (posterior ? (int64_t)total_rows * C * 4 : 0));
+    bp = reinterpret_cast<uint8_t*>(end + total_rows);
+  }
+};
+
+// grid (posterior ? 2 : 1, n_active): block (0, e) the Viterbi scan of stream e, block (1, e) its forward scan
+__global__ __launch_bounds__(64) void track_pool_scan_kernel(const int64_t* __restrict__ table, unsigned char* __restrict__ states, int64_t state_stride,
+                                                              const float* __restrict__ logits, int64_t ldl, int C, float lam, int lag, int posterior,
+                                                              unsigned char* __restrict__ workspace, int total_rows, float* __restrict__ log_z) {
+  __shared__ __attribute__((aligned(16))) float s_u[TRACK_MAX_C];
+  const TrackPoolEntry e(table, blockIdx.y, lag);
+  const bool fwd = blockIdx.x == 1;
+  if (e.t_new == 0 || (e.n == 0 && !fwd)) return;                  // an empty stream; nothing to scan (n == 0 with the posterior: log_z from the carried a)
+  const TrackPoolWorkspace ws(workspace, C, total_rows, posterior != 0);
+  track_stream_scan_body(logits + e.row0 * ldl, ldl, (int)e.n, C, lam, e.t_old, states + e.slot * state_stride, lag, posterior, ws.bp + e.row0 * C, ws.a + e.row0 * C,
+                         ws.end + e.row0, log_z + blockIdx.y, fwd, s_u);
+}
+
+// grid (the largest n_commit + (n_tail > 0) of the table, n_active)
+template <bool POST>
+__global__ __launch_bounds__(64) void track_pool_readout_kernel(const int64_t* __restrict__ table, const unsigned char* __restrict__ states, int64_t state_stride,
+                                                                 const float* __restrict__ logits, int64_t ldl, int C, float lam, int lag,
+                                                                 const float* __restrict__ grid, const unsigned char* __restrict__ workspace, int total_rows,
+                                                                 int32_t* __restrict__ cls_lag, float* __restrict__ conf_lag, float* __restrict__ post_lag, int64_t ldp,
+                                                                 int32_t* __restrict__ cls_post_lag, float* __restrict__ conf_post_lag,
+                                                                 float* __restrict__ offset_mean_lag, int32_t* __restrict__ cls_tail, float* __restrict__ conf_tail) {
+  __shared__ __attribute__((aligned(16))) float s_u[TRACK_MAX_C];
+  __shared__ float s_b[TRACK_MAX_C];
+  __shared__ int s_tail[256];
+  const TrackPoolEntry e(table, blockIdx.y, lag);
+  if ((int64_t)blockIdx.x >= e.readout_blocks()) return;
+  const TrackStreamLayout lay(C, lag, POST);
+  const TrackPoolWorkspace ws(const_cast<unsigned char*>(workspace), C, total_rows, POST);
+  const unsigned char* st = states + e.slot * state_stride;
+  TrackStreamRows rows;
+  rows.lg_new = logits + e.row0 * ldl;  rows.ldl = ldl;  rows.bp_new = ws.bp + e.row0 * C;  rows.a_new = ws.a + e.row0 * C;  rows.end_new = ws.end + e.row0;
+  rows.lg_ring = reinterpret_cast<const float*>(st + lay.lg_ring);  rows.bp_ring = st + lay.bp_ring;  rows.a_ring = reinterpret_cast<const float*>(st + lay.a_ring);
+  rows.end_last = reinterpret_cast<const int32_t*>(st + 8);
+  rows.t_old = e.t_old;  rows.lag = lag;  rows.C = C;
+  track_stream_readout_body<POST>(rows, lam, grid, e.done_old, (int)e.n_commit, (int)e.n_tail, e.t_new - 1, cls_lag + e.commit0, conf_lag + e.commit0,
+                                  post_lag + e.commit0 * ldp, ldp, cls_post_lag + e.commit0, conf_post_lag + e.commit0, offset_mean_lag + e.commit0,
+                                  cls_tail + e.tail0, conf_tail + e.tail0, (int)blockIdx.x, s_u, s_b, s_tail);
+}
+
+// grid (the largest min(n, lag) of the table, n_active)
+__global__ __launch_bounds__(64) void track_pool_keep_kernel(const int64_t* __restrict__ table, unsigned char* __restrict__ states, int64_t state_stride,
+                                                              const float* __restrict__ logits, int64_t ldl, int C, int lag, int posterior,
+                                                              const unsigned char* __restrict__ workspace, int total_rows) {
+  const TrackPoolEntry e(table, blockIdx.y, lag);
+  const int64_t keep = e.keep(lag);
+  if ((int64_t)blockIdx.x >= keep) return;
+  const TrackPoolWorkspace ws(const_cast<unsigned char*>(workspace), C, total_rows, posterior != 0);
+  track_stream_keep_body(logits + e.row0 * ldl, ldl, ws.bp + e.row0 * C, ws.a + e.row0 * C, (int)(e.n - keep), e.t_old, C, lag, posterior,
+                         states + e.slot * state_stride, (int)blockIdx.x);
+}
+
+extern "C" int sf_track_pool_workspace_bytes(int C, int total_rows, int posterior) {
+  SF_CHECK_ARG(C >= 2 && C <= TRACK_MAX_C, "sf_track_pool_workspace_bytes: C = %d classes out of range (2 .. %d)", C, TRACK_MAX_C);
+  SF_CHECK_ARG(total_rows >= 0 && total_rows <= TRACK_STREAM_MAX_PUSH, "sf_track_pool_workspace_bytes: %d rows in one push (0 .. %d)", total_rows, TRACK_STREAM_MAX_PUSH);
+  return sf_track_stream_workspace_bytes(C, total_rows, posterior);
+}
+
+extern "C" int sf_track_pool_push(void* states, int64_t state_stride, int n_slots, int C, int lag, int posterior, const int64_t* table_host, const int64_t* table_dev,
+                                  int n_active, const float* logits, int64_t ldl, int total_rows, float lam, const float* grid, int32_t* cls_raw, float* conf_raw,
+                                  int32_t* cls_lag, float* conf_lag, float* post_lag, int64_t ldp, int32_t* cls_post_lag, float* conf_post_lag,
+                                  float* offset_mean_lag, int32_t* cls_tail, float* conf_tail, float* log_z, void* workspace, void* stream) {
+  if (!track_stream_shape_ok("sf_track_pool_push", C, lag)) return -1;
+  SF_CHECK_ARG(std::isfinite(lam) && lam >= 0.f, "sf_track_pool_push: lam must be finite and >= 0 (the cost of a class change)");
+  SF_CHECK_ARG(n_active >= 1 && n_active <= TRACK_POOL_MAX_ACTIVE, "sf_track_pool_push: n_active = %d streams in one push (1 .. %d)", n_active, TRACK_POOL_MAX_ACTIVE);
+  SF_CHECK_ARG(n_slots >= 1, "sf_track_pool_push: n_slots = %d", n_slots);
+  SF_CHECK_ARG(states && table_host && table_dev, "sf_track_pool_push: null pointer (states or table)");
+  const TrackStreamLayout lay(C, lag, posterior != 0);
+  SF_CHECK_ARG(state_stride >= lay.total && state_stride % 16 == 0, "sf_track_pool_push: state stride %lld: a multiple of 16, at least %lld bytes", (long long)state_stride,
+               (long long)lay.total);
+  SF_CHECK_ARG(total_rows >= 0 && total_rows <= TRACK_STREAM_MAX_PUSH, "sf_track_pool_push: total_rows = %d rows in one push (0 .. %d)", total_rows, TRACK_STREAM_MAX_PUSH);
+  struct Span { int64_t row0, n; };
+  static thread_local int64_t slots[TRACK_POOL_MAX_ACTIVE];
+  static thread_local Span spans[TRACK_POOL_MAX_ACTIVE];
+  int64_t sum_n = 0, sum_commit = 0, sum_tail = 0, max_read = 0, max_keep = 0;
+  int n_spans = 0;
+  bool scan = false;
+  for (int i = 0; i < n_active; ++i) {
+    const int64_t* r = table_host + (int64_t)i * TRACK_POOL_ROW;
+    SF_CHECK_ARG(r[0] >= 0 && r[0] < n_slots, "sf_track_pool_push: table row %d: slot %lld outside the %d slots", i, (long long)r[0], n_slots);
+    SF_CHECK_ARG(r[1] >= 0 && r[1] <= (INT64_MAX >> 1), "sf_track_pool_push: table row %d: %lld rows pushed so far", i, (long long)r[1]);
+    SF_CHECK_ARG(r[2] >= 0 && r[3] >= 0 && r[2] <= total_rows && r[3] <= total_rows - r[2],
+                 "sf_track_pool_push: table row %d: rows [%lld, %lld + %lld) outside the %d rows of the push", i, (long long)r[3], (long long)r[3], (long long)r[2], total_rows);
+    const TrackPoolEntry e(table_host, i, lag);
+    SF_CHECK_ARG(e.commit0 == sum_commit && e.tail0 == sum_tail,
+                 "sf_track_pool_push: table row %d: commit0 = %lld, tail0 = %lld, the counts of the rows before it give %lld, %lld", i, (long long)e.commit0,
+                 (long long)e.tail0, (long long)sum_commit, (long long)sum_tail);
+    slots[i] = e.slot;
+    if (e.n > 0) spans[n_spans++] = Span{e.row0, e.n};
+    if (e.t_new > 0) {
+      sum_commit += e.n_commit;
+      sum_tail += e.n_tail;
+      if (e.readout_blocks() > max_read) max_read = e.readout_blocks();
+      if (e.keep(lag) > max_keep) max_keep = e.keep(lag);
+      scan = scan || e.n > 0 || posterior;
+    }
+    sum_n += e.n;
+  }
+  std::sort(slots, slots + n_active);
+  for (int i = 1; i < n_active; ++i) SF_CHECK_ARG(slots[i] != slots[i - 1], "sf_track_pool_push: slot %lld named twice in one push", (long long)slots[i]);
+  std::sort(spans, spans + n_spans, [](const Span& a, const Span& b) { return a.row0 < b.row0; });
+  for (int i = 1; i < n_spans; ++i)
+    SF_CHECK_ARG(spans[i - 1].row0 + spans[i - 1].n <= spans[i].row0, "sf_track_pool_push: the rows [%lld, +%lld) and [%lld, +%lld) of two streams overlap",
+                 (long long)spans[i - 1].row0, (long long)spans[i - 1].n, (long long)spans[i].row0, (long long)spans[i].n);
+  SF_CHECK_ARG(sum_n == 0 || ldl >= C, "sf_track_pool_push: row stride ldl = %lld below C = %d", (long long)ldl, C);
+  SF_CHECK_ARG(sum_n == 0 || (logits && cls_raw && conf_raw && workspace), "sf_track_pool_push: null pointer (new rows)");
+  SF_CHECK_ARG(sum_commit == 0 || (cls_lag && conf_lag), "sf_track_pool_push: null pointer (committed block)");
+  SF_CHECK_ARG(sum_tail == 0 || (cls_tail && conf_tail), "sf_track_pool_push: null pointer (tail)");
+  if (posterior) {
+    SF_CHECK_ARG(!scan || log_z, "sf_track_pool_push: null log_z");
+    SF_CHECK_ARG(sum_commit == 0 || (grid && post_lag && cls_post_lag && conf_post_lag && offset_mean_lag && ldp >= C),
+                 "sf_track_pool_push: null pointer or post row stride ldp = %lld below C = %d (posterior block)", (long long)ldp, C);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  unsigned char* st = static_cast<unsigned char*>(states);
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  if (sum_n > 0) {                                                 // one thread per row of the packed matrix (rows between two streams' ranges: their own argmax, unread)
+    hipLaunchKernelGGL(track_rows_kernel<false>, dim3((unsigned)((total_rows + 255) / 256)), dim3(256), 0, s, logits, ldl, total_rows, C, cls_raw, conf_raw);
+    SF_LAUNCH_CHECK();
+  }
+  if (scan) {
+    hipLaunchKernelGGL(track_pool_scan_kernel, dim3(posterior ? 2 : 1, (unsigned)n_active), dim3(64), 0, s, table_dev, st, state_stride, logits, ldl, C, lam, lag, posterior,
+                       ws, total_rows, log_z);
+    SF_LAUNCH_CHECK();
+  }
+  if (max_read > 0) {
+    const dim3 g((unsigned)max_read, (unsigned)n_active);
+    if (posterior)
+      hipLaunchKernelGGL(track_pool_readout_kernel<true>, g, dim3(64), 0, s, table_dev, (const unsigned char*)st, state_stride, logits, ldl, C, lam, lag, grid,
+                         (const unsigned char*)ws, total_rows, cls_lag, conf_lag, post_lag, ldp, cls_post_lag, conf_post_lag, offset_mean_lag, cls_tail, conf_tail);
+    else
+      hipLaunchKernelGGL(track_pool_readout_kernel<false>, g, dim3(64), 0, s, table_dev, (const unsigned char*)st, state_stride, logits, ldl, C, lam, lag, grid,
+                         (const unsigned char*)ws, total_rows, cls_lag, conf_lag, post_lag, ldp, cls_post_lag, conf_post_lag, offset_mean_lag, cls_tail, conf_tail);
+    SF_LAUNCH_CHECK();
+  }
+  if (max_keep > 0) {
+    hipLaunchKernelGGL(track_pool_keep_kernel, dim3((unsigned)max_keep, (unsigned)n_active), dim3(64), 0, s, table_dev, st, state_stride, logits, ldl, C, lag, posterior,
+                       (const unsigned char*)ws, total_rows);
     SF_LAUNCH_CHECK();
   }
   return 0;

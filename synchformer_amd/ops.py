@@ -768,6 +768,125 @@ def track_stream_push(state: TrackStreamState, logits: torch.Tensor, lam: float,
     return TrackStreamOut(w0, cls_raw, conf_raw, cls_lag, conf_lag, cls_tail, conf_tail, post, cls_post, conf_post, mean, log_z)
 
 
+TRACK_POOL_ROW = 8                       # int64 per descriptor row: slot, rows_done, n, row0, final, commit0, tail0, unused
+TRACK_POOL_MAX_ACTIVE = 4096
+TrackPoolPlan = namedtuple('TrackPoolPlan', 'table total_rows total_commit total_tail blocks')
+
+
+def track_pool_plan(rows, counts, lag: int, final, slots=None) -> TrackPoolPlan:
+    """The descriptor table of one pool push (sf_track_pool_push), pure host arithmetic: entry i pushes counts[i] rows onto a stream that holds rows[i], final[i]
+    truthy closes it, slots[i] (default i) names its state -> TrackPoolPlan(table int64 (n, 8) on the host: slot, rows_done, n, row0, final, commit0, tail0, 0;
+    total_rows, total_commit, total_tail: the sizes of the packed blocks; blocks: per entry (w0, n_commit, n_tail) = track_stream_counts).  The rows, the
+    committed blocks and the tails of the entries lie back to back in table order: row0 / commit0 / tail0 are the running sums."""
+    rows, counts, final = [int(r) for r in rows], [int(c) for c in counts], [bool(f) for f in final]
+    slots = list(range(len(rows))) if slots is None else [int(x) for x in slots]
+    if not (len(rows) == len(counts) == len(final) == len(slots)):
+        raise ValueError(f'track_pool_plan: {len(rows)} row counts, {len(counts)} push sizes, {len(final)} final flags, {len(slots)} slots')
+    if min(rows + counts + [int(lag)], default=0) < 0:
+        raise ValueError('track_pool_plan: negative rows, counts or lag')
+    row0 = commit0 = tail0 = 0
+    table, blocks = [], []
+    for slot, r, n, f in zip(slots, rows, counts, final):
+        w0, k, m = track_stream_counts(r, n, lag, f)
+        table.append((slot, r, n, row0, int(f), commit0, tail0, 0))
+        blocks.append((w0, k, m))
+        row0, commit0, tail0 = row0 + n, commit0 + k, tail0 + m
+    table = torch.tensor(table, dtype=torch.int64).reshape(len(rows), TRACK_POOL_ROW)
+    return TrackPoolPlan(table, row0, commit0, tail0, blocks)
+
+
+class TrackPoolState:
+    """The carried states of a pool of streams (sf_track_pool_push): `buf` uint8 (n_slots, bytes) on the device, slot i the state of one stream
+    (sf_track_stream_push's layout); `rows[i]` the rows pushed into slot i so far and `closed[i]` after its final push (host counts)."""
+
+    def __init__(self, buf: torch.Tensor, C: int, lag: int, posterior: bool):
+        self.buf, self.C, self.lag, self.posterior = buf, int(C), int(lag), bool(posterior)
+        self.n_slots = int(buf.shape[0])
+        self.rows, self.closed = [0] * self.n_slots, [False] * self.n_slots
+
+    def reopen(self, slot: int):
+        """Slot `slot` starts a new stream: only the host count is reset - the device state is read only when rows_done > 0."""
+        self.rows[slot], self.closed[slot] = 0, False
+
+
+def track_pool_state(n_slots: int, C: int, lag: int, posterior: bool, device) -> TrackPoolState:
+    """n_slots fresh stream states in one zeroed (n_slots, sf_track_stream_bytes(C, lag, posterior)) buffer on `device` (the size is a multiple of 16: the stride)."""
+    if n_slots < 1:
+        raise ValueError(f'track_pool_state: n_slots = {n_slots}')
+    nbytes = _lib.load().sf_track_stream_bytes(int(C), int(lag), int(bool(posterior)))
+    if nbytes < 0:
+        _lib.check(nbytes, 'sf_track_stream_bytes')
+    return TrackPoolState(torch.zeros(int(n_slots), nbytes, device=device, dtype=torch.uint8), C, lag, posterior)
+
+
+def track_pool_push(state: TrackPoolState, slots, logits: torch.Tensor, counts, lam: float, grid: Optional[torch.Tensor] = None, final=(),
+                    post: Optional[torch.Tensor] = None) -> list:
+    """One push for many streams (sf_track_pool_push): logits fp32 (total, C) on the state's device with unit column stride, the new rows of all named streams
+    packed in the order of `slots` - counts[i] rows (0 allowed) belong to the stream in slots[i]; `final`: the slots this push closes -> one TrackStreamOut per
+    slot, views into the packed outputs, each equal bit for bit to track_stream_push on that stream alone (log_z: its own (1,) view).  The number of launches and
+    of allocations does not depend on len(slots).  The descriptor table is built on the host (track_pool_plan), copied into a FRESH PINNED tensor and uploaded
+    with one non-blocking copy on the current stream: no buffer is shared between two pushes, so a later push cannot race the upload (torch's pinned-memory
+    allocator keeps the block until the copy has run).  Nothing is read back or synchronised.  `post` (posterior only), if given, is written instead of a fresh
+    tensor: fp32 (total_commit, C) - track_pool_plan's count - with unit column stride and any row stride >= C."""
+    C, dev = state.C, state.buf.device
+    slots, counts, final = [int(x) for x in slots], [int(x) for x in counts], {int(x) for x in final}
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.shape[1] == C, f'logits {tuple(logits.shape)} for streams of {C} classes'
+    if len(slots) != len(counts) or not 1 <= len(slots) <= TRACK_POOL_MAX_ACTIVE:
+        raise ValueError(f'track_pool_push: {len(slots)} slots, {len(counts)} counts (1 .. {TRACK_POOL_MAX_ACTIVE} streams in one push)')
+    if len(set(slots)) != len(slots) or not all(0 <= x < state.n_slots for x in slots) or not final <= set(slots):
+        raise ValueError(f'track_pool_push: slots {slots} (final {sorted(final)}): distinct, below {state.n_slots}, the final ones among them')
+    if any(state.closed[x] for x in slots):
+        raise RuntimeError(f'track_pool_push: slots {[x for x in slots if state.closed[x]]} were closed by a final push (reopen them)')
+    total = logits.shape[0]
+    if min(counts) < 0 or sum(counts) != total:
+        raise ValueError(f'track_pool_push: counts {counts} for {total} rows of logits')
+    assert total == 0 or (logits.device == dev and logits.stride(1) == 1), 'logits: on the state\'s device, unit column stride'
+    if state.posterior:
+        assert grid is not None and grid.dtype == torch.float32 and grid.device == dev and grid.shape == (C,) and grid.is_contiguous(), f'a grid for {C} classes'
+    plan = track_pool_plan([state.rows[x] for x in slots], counts, state.lag, [x in final for x in slots], slots)
+    K, M, n_act = plan.total_commit, plan.total_tail, len(slots)
+    host = torch.empty(n_act, TRACK_POOL_ROW, dtype=torch.int64, pin_memory=True)
+    host.copy_(plan.table)
+    table = host.to(dev, non_blocking=True)
+    i32 = dict(device=dev, dtype=torch.int32)
+    f32 = dict(device=dev, dtype=torch.float32)
+    cls_raw, conf_raw = torch.empty(total, **i32), torch.empty(total, **f32)
+    cls_lag, conf_lag = torch.empty(K, **i32), torch.empty(K, **f32)
+    cls_tail, conf_tail = torch.empty(M, **i32), torch.empty(M, **f32)
+    assert post is None or state.posterior, 'post: only with the posterior'
+    cls_post = conf_post = mean = log_z = None
+    if state.posterior:
+        if post is None:
+            post = torch.empty(K, C, **f32)
+        assert post.dtype == torch.float32 and post.shape == (K, C) and post.device == dev and (K == 0 or post.stride(1) == 1), f'post: fp32 ({K}, {C}), unit column stride'
+        cls_post, conf_post, mean = torch.empty(K, **i32), torch.empty(K, **f32), torch.empty(K, **f32)
+        log_z = torch.zeros(n_act, **f32)                                           # (stays 0 for a stream that is still empty: the empty product)
+    lib = _lib.load()
+    ws_bytes = lib.sf_track_pool_workspace_bytes(C, total, int(state.posterior))
+    if ws_bytes < 0:
+        _lib.check(ws_bytes, 'sf_track_pool_workspace_bytes')
+    ws = torch.empty(max(ws_bytes, 16), device=dev, dtype=torch.uint8)
+
+    def ptr(t):
+        return _dev(t, 'out') if t is not None and t.numel() else None
+
+    rc = lib.sf_track_pool_push(_dev(state.buf, 'states'), state.buf.stride(0), state.n_slots, C, state.lag, int(state.posterior), host.data_ptr(), _dev(table, 'table'),
+                                n_act, ptr(logits), _ld(logits) if total else C, total, float(lam), _dev(grid, 'grid') if state.posterior else None, ptr(cls_raw),
+                                ptr(conf_raw), ptr(cls_lag), ptr(conf_lag), ptr(post), _ld(post) if state.posterior and K else C, ptr(cls_post), ptr(conf_post), ptr(mean),
+                                ptr(cls_tail), ptr(conf_tail), ptr(log_z), _dev(ws, 'workspace'), _stream())
+    _lib.check(rc, 'sf_track_pool_push')
+    # one TrackStreamOut per slot: views into the packed outputs (one split per field, not one slice per slot and field)
+    ns, ks, ms = counts, [b[1] for b in plan.blocks], [b[2] for b in plan.blocks]
+    none = [None] * n_act
+    fields = [cls_raw.split(ns), conf_raw.split(ns), cls_lag.split(ks), conf_lag.split(ks), cls_tail.split(ms), conf_tail.split(ms)]
+    fields += [post.split(ks), cls_post.split(ks), conf_post.split(ks), mean.split(ks), log_z.split(1)] if state.posterior else [none] * 5
+    outs = [TrackStreamOut(b[0], *views) for b, views in zip(plan.blocks, zip(*fields))]
+    for slot, n in zip(slots, ns):
+        state.rows[slot] += n
+        state.closed[slot] = slot in final
+    return outs
+
+
 def _ingest_tables(frame_table: torch.Tensor, **tables):
     """Checks frame_table (int32, contiguous) and the filter tables name=(first int32 (224,), weights fp32 (224, taps)), all contiguous; returns their launcher
     arguments in order: (first, weights, taps) per table."""

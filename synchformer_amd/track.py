@@ -18,7 +18,12 @@ confidence that carries the evidence of the whole recording, and an offset finer
     upd = stream.push(frames_1s, wave_1s)         # upd.cls_lag / offset_sec_lag: committed, never revised; upd.offset_sec_tail[-1]: the offset now
     upd = stream.flush()                          # end of the feed: the tail is committed
 
-Out of scope (one recording per call): batching several recordings, double-buffered host-to-device transfer of the chunks, de-duplicating the
+    pool = tracker.pool(n_feeds=64, lag=16)       # many live feeds on one device: one tick = one batched pass for all of them
+    a, b = pool.open(), pool.open()
+    upds = pool.push({a: (frames_a, wave_a), b: (frames_b, wave_b)})     # {feed: OffsetUpdate}, each what the feed's own stream would return
+    upds = pool.push({a: (frames_a2, wave_a2)}, flush=[b])               # b's final push; its slot is free again
+
+Out of scope (one recording per call): batching several recordings offline, double-buffered host-to-device transfer of the chunks, de-duplicating the
 overlapped tubelets inside the patch embedding.
 """
 from dataclasses import dataclass
@@ -121,6 +126,11 @@ class OffsetTracker:
         ingest: an ingest.RecordingIngest - push then takes frames and samples as decoded (native frame rate, size, sample rate; track_raw's layouts)."""
         return OffsetStream(self, lag, seg_chunk, ingest)
 
+    def pool(self, n_feeds: int, lag: int = 16, seg_chunk: Optional[int] = None) -> 'OffsetStreamPool':
+        """Up to `n_feeds` live feeds at once: each feed is what stream(lag, seg_chunk) is, but one push() advances all named feeds together - their
+        new segments share the towers' launch groups, their new windows the sync transformer's passes, their read-outs one ops.track_pool_push."""
+        return OffsetStreamPool(self, n_feeds, lag, seg_chunk)
+
 
 @dataclass
 class OffsetUpdate:
@@ -150,7 +160,112 @@ class OffsetUpdate:
     log_z: Optional[torch.Tensor] = None               # (1,) fp32: that of all the windows so far
 
 
-class OffsetStream:
+def pool_schedule(feeds, hop: int = 1, seg_chunk: int = 224, win_chunk: int = 256) -> dict:
+    """The host schedule of one pool tick (OffsetStreamPool.push), pure arithmetic.  feeds: one dict per feed taking part, in feed order, AFTER its new frames and
+    samples were accepted: n_frames, n_samples (totals so far), n_segments (segments already through the towers), f0, a0, s0 (the recording's index of the first held
+    frame / sample / segment feature) ->
+        geometry   per feed: stream_geometry(n_frames, n_samples, n_segments, hop) - each feed's own, nothing is shared
+        segments   the staging order of the towers: (feed, s, frame_lo, sample_lo) for every new segment of every feed, feeds in order, s ascending; frame_lo /
+                   sample_lo index the feed's HELD buffers (v_stride s - f0, a_stride s - a0)
+        groups     (i0, i1) ranges of `segments`: launch groups of at most seg_chunk segments, whatever feed they come from
+        windows    the gather order of the sync transformer: (feed, w, feat_lo) for every new window, feat_lo = hop w - s0 indexing the held features (after the new
+                   segments were appended); passes = (i0, i1) ranges of at most win_chunk windows
+        counts     per feed: its new windows (the rows it brings to ops.track_pool_push)
+        trims      per feed: (frames_from, samples_from, features_from) of its geometry"""
+    if seg_chunk < 1 or win_chunk < 1:
+        raise ValueError(f'pool_schedule: seg_chunk = {seg_chunk}, win_chunk = {win_chunk}')
+    geometry, segments, windows, counts, trims = [], [], [], [], []
+    for i, f in enumerate(feeds):
+        g = stream_geometry(f['n_frames'], f['n_samples'], f['n_segments'], hop)
+        (s0, s1), (w0, w1) = g['new_segments'], g['new_windows']
+        geometry.append(g)
+        segments += [(i, s, g['v_stride'] * s - f['f0'], g['a_stride'] * s - f['a0']) for s in range(s0, s1)]
+        windows += [(i, w, hop * w - f['s0']) for w in range(w0, w1)]
+        counts.append(w1 - w0)
+        trims.append((g['frames_from'], g['samples_from'], g['features_from']))
+    groups = [(i0, min(i0 + seg_chunk, len(segments))) for i0 in range(0, len(segments), seg_chunk)]
+    passes = [(i0, min(i0 + win_chunk, len(windows))) for i0 in range(0, len(windows), win_chunk)]
+    return dict(geometry=geometry, segments=segments, groups=groups, windows=windows, passes=passes, counts=counts, trims=trims)
+
+
+class _Feed:
+    """What one live feed carries on the host and the steps of one advance - accept, (towers), (windows), (read-out), trim, update - shared by OffsetStream (one feed,
+    its own launches) and OffsetStreamPool (many feeds, the three device steps batched across them)."""
+
+    def __init__(self, tracker: 'OffsetTracker', ingest=None):
+        self.tracker = tracker
+        dev = tracker.eng.dev
+        self._ingest = None if ingest is None else ingest.stream()
+        self._frames = torch.empty(0, 3, 224, 224, device=dev, dtype=torch.uint8)
+        self._wave = torch.empty(0, device=dev, dtype=torch.float32)
+        self._vfeat = self._afeat = None
+        self.n_frames = self.n_samples = self.n_segments = self.n_windows = 0    # totals so far
+        self._f0 = self._a0 = self._s0 = 0                                       # the recording's index of the first held frame / sample / segment
+        self.closed = False
+
+    def _state_bytes(self) -> int:
+        raise NotImplementedError
+
+    @property
+    def held(self) -> dict:
+        """The sizes of the carried buffers: frames, samples, segments (features) and state_bytes."""
+        return dict(frames=int(self._frames.shape[0]), samples=int(self._wave.shape[0]), segments=0 if self._vfeat is None else int(self._vfeat.shape[0]),
+                    state_bytes=self._state_bytes())
+
+    @property
+    def held_bound(self) -> dict:
+        """The bound on `held` after a push, from the totals so far (see the class docstring; one push's own frames and samples pass through on top of it)."""
+        g = recording_geometry(self.n_frames, self.n_samples, self.tracker.hop)
+        nv = max(0, (self.n_frames - g['v_size']) // g['v_stride'] + 1)
+        na = max(0, (self.n_samples - g['a_size']) // g['a_stride'] + 1)
+        return dict(frames=g['v_size'] - 1 + g['v_stride'] * (nv - g['n_segments']), samples=g['a_size'] - 1 + g['a_stride'] * (na - g['n_segments']),
+                    segments=g['n_window'] - 1 + self.tracker.hop - 1, state_bytes=self._state_bytes())
+
+    def _empty_input(self):
+        dev = self.tracker.eng.dev
+        return torch.empty(0, 3, 224, 224, device=dev, dtype=torch.uint8), torch.empty(0, device=dev, dtype=torch.float32)
+
+    def _accept(self, frames: torch.Tensor, wave: torch.Tensor, who: str = 'OffsetStream.push'):
+        """Appends what arrived (25 fps, 224 x 224, 16 kHz: after the ingest) to the held frames and samples and counts it."""
+        eng = self.tracker.eng
+        if frames.dim() != 4 or frames.dtype != torch.uint8 or tuple(frames.shape[1:]) != (3, 224, 224) or wave.dim() != 1:
+            raise ValueError(f'{who}: expected uint8 frames (t, 3, 224, 224) and a 1-D wave, got {frames.dtype} {tuple(frames.shape)} / {tuple(wave.shape)}')
+        if frames.shape[0]:
+            self._frames = torch.cat([self._frames, frames.to(eng.dev, non_blocking=True)])
+        if wave.shape[0]:
+            self._wave = torch.cat([self._wave, wave.to(eng.dev, torch.float32, non_blocking=True)])
+        self.n_frames += int(frames.shape[0])
+        self.n_samples += int(wave.shape[0])
+
+    def _add_features(self, vf: torch.Tensor, af: torch.Tensor):
+        self._vfeat = vf if self._vfeat is None else torch.cat([self._vfeat, vf])
+        self._afeat = af if self._afeat is None else torch.cat([self._afeat, af])
+
+    def _trim(self, g: dict):
+        """Drops what no later segment / window reads and moves the totals on (g: this advance's stream_geometry)."""
+        self._frames, self._f0 = self._frames[g['frames_from'] - self._f0:], g['frames_from']
+        self._wave, self._a0 = self._wave[g['samples_from'] - self._a0:], g['samples_from']
+        if self._vfeat is not None:
+            k = g['features_from'] - self._s0
+            self._vfeat, self._afeat, self._s0 = self._vfeat[k:], self._afeat[k:], g['features_from']
+        self.n_segments, self.n_windows = g['new_segments'][1], g['new_windows'][1]
+
+    def _update(self, out, logits: torch.Tensor, w0: int, w1: int) -> 'OffsetUpdate':
+        """The read-out of this advance (an ops.TrackStreamOut) and its logits (windows w0 .. w1 - 1) -> OffsetUpdate."""
+        tr = self.tracker
+        k, m = out.cls_lag.shape[0], out.cls_tail.shape[0]
+        upd = OffsetUpdate(w_new=w0, logits=logits, cls_raw=out.cls_raw, conf_raw=out.conf_raw, w0=out.w0, t_sec=window_times64(k, tr.hop, first_window=out.w0),
+                           cls_lag=out.cls_lag, conf_lag=out.conf_lag, offset_sec_lag=tr.grid[out.cls_lag.long()],
+                           t_sec_tail=window_times64(m, tr.hop, first_window=w1 - m), cls_tail=out.cls_tail, conf_tail=out.conf_tail,
+                           offset_sec_tail=tr.grid[out.cls_tail.long()])
+        if tr.posterior:
+            upd.post_lag, upd.cls_post_lag, upd.conf_post_lag, upd.offset_sec_mean_lag, upd.log_z = (out.post_lag, out.cls_post_lag, out.conf_post_lag,
+                                                                                                       out.offset_mean_lag, out.log_z)
+            upd.offset_sec_post_lag = tr.grid[out.cls_post_lag.long()]
+        return upd
+
+
+class OffsetStream(_Feed):
     """OffsetTracker.stream(): the recording path for a feed that does not end.  push() takes what arrived - uint8 frames (t, 3, 224, 224) at 25 fps and fp32
     samples (m,) at 16 kHz, device or host, either possibly empty, the two at their own pace (with `ingest`: as decoded) - runs the towers on the segments that
     became complete, the sync transformer on the windows that became complete (engine.sync_windows on the held features: 13 old segments and n new ones give
@@ -163,31 +278,12 @@ class OffsetStream:
     un-fused one) and t_sec are those track() gives for the finished recording."""
 
     def __init__(self, tracker: OffsetTracker, lag: int = 16, seg_chunk: Optional[int] = None, ingest=None):
-        self.tracker, self.lag, self.seg_chunk = tracker, int(lag), seg_chunk
-        dev = tracker.eng.dev
-        self.state = ops.track_stream_state(tracker.eng.n_out, self.lag, tracker.posterior, dev)
-        self._ingest = None if ingest is None else ingest.stream()
-        self._frames = torch.empty(0, 3, 224, 224, device=dev, dtype=torch.uint8)
-        self._wave = torch.empty(0, device=dev, dtype=torch.float32)
-        self._vfeat = self._afeat = None
-        self.n_frames = self.n_samples = self.n_segments = self.n_windows = 0    # totals so far
-        self._f0 = self._a0 = self._s0 = 0                                       # the recording's index of the first held frame / sample / segment
-        self.closed = False
+        super().__init__(tracker, ingest)
+        self.lag, self.seg_chunk = int(lag), seg_chunk
+        self.state = ops.track_stream_state(tracker.eng.n_out, self.lag, tracker.posterior, tracker.eng.dev)
 
-    @property
-    def held(self) -> dict:
-        """The sizes of the carried buffers: frames, samples, segments (features) and state_bytes."""
-        return dict(frames=int(self._frames.shape[0]), samples=int(self._wave.shape[0]), segments=0 if self._vfeat is None else int(self._vfeat.shape[0]),
-                    state_bytes=int(self.state.buf.numel()))
-
-    @property
-    def held_bound(self) -> dict:
-        """The bound on `held` after a push, from the totals so far (see the class docstring; one push's own frames and samples pass through on top of it)."""
-        g = recording_geometry(self.n_frames, self.n_samples, self.tracker.hop)
-        nv = max(0, (self.n_frames - g['v_size']) // g['v_stride'] + 1)
-        na = max(0, (self.n_samples - g['a_size']) // g['a_stride'] + 1)
-        return dict(frames=g['v_size'] - 1 + g['v_stride'] * (nv - g['n_segments']), samples=g['a_size'] - 1 + g['a_stride'] * (na - g['n_segments']),
-                    segments=g['n_window'] - 1 + self.tracker.hop - 1, state_bytes=int(self.state.buf.numel()))
+    def _state_bytes(self) -> int:
+        return int(self.state.buf.numel())
 
     def push(self, frames: torch.Tensor, wave: torch.Tensor) -> OffsetUpdate:
         if self.closed:
@@ -200,8 +296,7 @@ class OffsetStream:
         """End of the feed: whatever the ingest still held becomes final, the tail is committed from everything pushed, the stream closes (a later push raises)."""
         if self.closed:
             raise RuntimeError('OffsetStream.flush: the stream is closed')
-        dev = self.tracker.eng.dev
-        frames, wave = torch.empty(0, 3, 224, 224, device=dev, dtype=torch.uint8), torch.empty(0, device=dev, dtype=torch.float32)
+        frames, wave = self._empty_input()
         if self._ingest is not None:
             frames, wave = self._ingest.flush()
         upd = self._advance(frames, wave, final=True)
@@ -210,21 +305,12 @@ class OffsetStream:
 
     def _advance(self, frames: torch.Tensor, wave: torch.Tensor, final: bool) -> OffsetUpdate:
         tr, eng = self.tracker, self.tracker.eng
-        if frames.dim() != 4 or frames.dtype != torch.uint8 or tuple(frames.shape[1:]) != (3, 224, 224) or wave.dim() != 1:
-            raise ValueError(f'OffsetStream.push: expected uint8 frames (t, 3, 224, 224) and a 1-D wave, got {frames.dtype} {tuple(frames.shape)} / {tuple(wave.shape)}')
-        if frames.shape[0]:
-            self._frames = torch.cat([self._frames, frames.to(eng.dev, non_blocking=True)])
-        if wave.shape[0]:
-            self._wave = torch.cat([self._wave, wave.to(eng.dev, torch.float32, non_blocking=True)])
-        self.n_frames += int(frames.shape[0])
-        self.n_samples += int(wave.shape[0])
+        self._accept(frames, wave)
         g = stream_geometry(self.n_frames, self.n_samples, self.n_segments, tr.hop)
         (s0, s1), (w0, w1) = g['new_segments'], g['new_windows']
         if s1 > s0:                                                              # the towers, on the segments this push completed
-            vf, af = eng.extract_segments_from(lambda f0, f1: self._frames[f0 - self._f0:f1 - self._f0], self._wave, tr.mel, s0, s1 - s0, self.seg_chunk,
-                                               sample0=self._a0)
-            self._vfeat = vf if self._vfeat is None else torch.cat([self._vfeat, vf])
-            self._afeat = af if self._afeat is None else torch.cat([self._afeat, af])
+            self._add_features(*eng.extract_segments_from(lambda f0, f1: self._frames[f0 - self._f0:f1 - self._f0], self._wave, tr.mel, s0, s1 - s0, self.seg_chunk,
+                                                          sample0=self._a0))
         if w1 > w0:                                                              # the windows whose last segment arrived: the held features hold exactly these
             lo = tr.hop * w0 - self._s0
             logits = eng.sync_windows(self._vfeat[lo:], self._afeat[lo:], hop=tr.hop)
@@ -232,20 +318,114 @@ class OffsetStream:
         else:
             logits = torch.empty(0, eng.n_out, device=eng.dev, dtype=torch.float32)
         out = ops.track_stream_push(self.state, logits, tr.lam, tr.grid if tr.posterior else None, final=final)
-        # drop what no later segment / window reads
-        self._frames, self._f0 = self._frames[g['frames_from'] - self._f0:], g['frames_from']
-        self._wave, self._a0 = self._wave[g['samples_from'] - self._a0:], g['samples_from']
-        if self._vfeat is not None:
-            k = g['features_from'] - self._s0
-            self._vfeat, self._afeat, self._s0 = self._vfeat[k:], self._afeat[k:], g['features_from']
-        self.n_segments, self.n_windows = s1, w1
-        k, m = out.cls_lag.shape[0], out.cls_tail.shape[0]
-        upd = OffsetUpdate(w_new=w0, logits=logits, cls_raw=out.cls_raw, conf_raw=out.conf_raw, w0=out.w0, t_sec=window_times64(k, tr.hop, first_window=out.w0),
-                           cls_lag=out.cls_lag, conf_lag=out.conf_lag, offset_sec_lag=tr.grid[out.cls_lag.long()],
-                           t_sec_tail=window_times64(m, tr.hop, first_window=w1 - m), cls_tail=out.cls_tail, conf_tail=out.conf_tail,
-                           offset_sec_tail=tr.grid[out.cls_tail.long()])
-        if tr.posterior:
-            upd.post_lag, upd.cls_post_lag, upd.conf_post_lag, upd.offset_sec_mean_lag, upd.log_z = (out.post_lag, out.cls_post_lag, out.conf_post_lag,
-                                                                                                       out.offset_mean_lag, out.log_z)
-            upd.offset_sec_post_lag = tr.grid[out.cls_post_lag.long()]
-        return upd
+        self._trim(g)
+        return self._update(out, logits, w0, w1)
+
+
+class PoolFeed(_Feed):
+    """One feed of an OffsetStreamPool (pool.open()): the handle push() is keyed by.  `held` / `held_bound` / the totals as an OffsetStream's."""
+
+    def __init__(self, pool: 'OffsetStreamPool', slot: int, ingest=None):
+        super().__init__(pool.tracker, ingest)
+        self.pool, self.slot = pool, slot
+
+    def _state_bytes(self) -> int:
+        return int(self.pool.state.buf.shape[1])
+
+
+class OffsetStreamPool:
+    """OffsetTracker.pool(): many live feeds on one device, advanced together.  open() takes a free slot and returns the feed's handle; one push() is
+    one tick: every feed named in it accepts what arrived for it (through its own ingest, if it has one), then
+        towers    the new segments of all feeds, in feed order, are gathered into staging tensors (n, 16, 3, 224, 224) / (n, 10240) and cross the towers as n
+                  one-segment clips, in launch groups of at most seg_chunk segments, whatever feed they come from;
+        windows   the new windows of all feeds are gathered from the held features into (nw, 14, t, 768) and cross the sync transformer in passes of at most
+                  win_chunk = 256;
+        read-out  one ops.track_pool_push for all feeds;
+    and every feed trims its buffers as its own stream would.  Per feed the host arithmetic is OffsetStream's (the same code), `held <= held_bound` holds per
+    feed, and on the un-fused tower schedule (the engine's seg_chunk < 6) every field of every update equals the same feed through its own OffsetStream bit for
+    bit.  A feed named in `flush` gets its final push in that tick (with or without data) and its slot becomes free; feeds not named are untouched."""
+
+    def __init__(self, tracker: OffsetTracker, n_feeds: int, lag: int = 16, seg_chunk: Optional[int] = None, win_chunk: int = 256):
+        if n_feeds < 1:
+            raise ValueError(f'OffsetStreamPool: n_feeds = {n_feeds}')
+        self.tracker, self.n_feeds, self.lag, self.seg_chunk, self.win_chunk = tracker, int(n_feeds), int(lag), seg_chunk, int(win_chunk)
+        self.state = ops.track_pool_state(self.n_feeds, tracker.eng.n_out, self.lag, tracker.posterior, tracker.eng.dev)
+        self._free = list(range(self.n_feeds - 1, -1, -1))                       # slot 0 first
+        self.feeds = {}                                                          # slot -> the open feed
+
+    def open(self, ingest=None) -> PoolFeed:
+        """A new feed in a free slot (ingest: an ingest.RecordingIngest, as OffsetTracker.stream's); RuntimeError when every slot is taken."""
+        if not self._free:
+            raise RuntimeError(f'OffsetStreamPool.open: all {self.n_feeds} slots are taken (flush a feed first)')
+        slot = self._free.pop()
+        self.state.reopen(slot)
+        feed = self.feeds[slot] = PoolFeed(self, slot, ingest)
+        return feed
+
+    def push(self, data: dict, flush=()) -> dict:
+        """One tick.  data: {feed: (frames, wave)} - what arrived for each feed since its last push (OffsetStream.push's inputs); flush: feeds that end in this
+        tick -> {feed: OffsetUpdate}, for every feed named in either."""
+        tr, eng = self.tracker, self.tracker.eng
+        flush = list(flush)
+        feeds = list(data) + [f for f in flush if f not in data]
+        if len(set(feeds)) != len(feeds) or len(set(flush)) != len(flush):
+            raise ValueError('OffsetStreamPool.push: a feed named twice')
+        for f in feeds:
+            if not isinstance(f, PoolFeed) or f.pool is not self:
+                raise ValueError('OffsetStreamPool.push: not a feed of this pool')
+            if f.closed:
+                raise RuntimeError(f'OffsetStreamPool.push: the feed in slot {f.slot} was closed by a flush')
+        if not feeds:
+            return {}
+        # accept: per feed, through its own ingest
+        for f in feeds:
+            frames, wave = data[f] if f in data else f._empty_input()
+            if f._ingest is not None:
+                parts = ([f._ingest.push(frames, wave)] if f in data else []) + ([f._ingest.flush()] if f in flush else [])
+                frames, wave = (parts[0] if len(parts) == 1 else (torch.cat([p[0].to(eng.dev) for p in parts]), torch.cat([p[1].to(eng.dev) for p in parts])))
+            f._accept(frames, wave, 'OffsetStreamPool.push')
+        chunk = eng.seg_chunk if self.seg_chunk is None else int(self.seg_chunk)
+        plan = pool_schedule([dict(n_frames=f.n_frames, n_samples=f.n_samples, n_segments=f.n_segments, f0=f._f0, a0=f._a0, s0=f._s0) for f in feeds], tr.hop, chunk,
+                             self.win_chunk)
+        # towers: launch groups over the new segments of all feeds
+        if plan['segments']:
+            g0 = plan['geometry'][0]
+            vz, vs, az, as_ = g0['v_size'], g0['v_stride'], g0['a_size'], g0['a_stride']
+            new_v, new_a = [[] for _ in feeds], [[] for _ in feeds]
+            for i0, i1 in plan['groups']:
+                n = i1 - i0
+                fst = torch.empty(n, vz, 3, 224, 224, device=eng.dev, dtype=torch.uint8)
+                wst = torch.empty(n, az, device=eng.dev, dtype=torch.float32)
+                for j, (i, _, flo, alo) in enumerate(plan['segments'][i0:i1]):
+                    fst[j].copy_(feeds[i]._frames[flo:flo + vz])
+                    wst[j].copy_(feeds[i]._wave[alo:alo + az])
+                aud = tr.mel.segments(wst, 0, as_, 1, az)
+                vf, af = eng.both_towers(lambda: eng.extract_vfeats_clips(fst, 0, vs, 1), aud)
+                for j, (i, _, _, _) in enumerate(plan['segments'][i0:i1]):
+                    new_v[i].append(vf[j])
+                    new_a[i].append(af[j])
+            for f, v, a in zip(feeds, new_v, new_a):
+                if v:
+                    f._add_features(torch.cat(v), torch.cat(a))
+        # windows: gathered from the held features of all feeds
+        nw = len(plan['windows'])
+        logits = torch.empty(nw, eng.n_out, device=eng.dev, dtype=torch.float32)
+        if nw:
+            nwin = plan['geometry'][0]['n_window']
+            for i0, i1 in plan['passes']:
+                vwin = torch.stack([feeds[i]._vfeat[lo:lo + nwin] for i, _, lo in plan['windows'][i0:i1]])
+                awin = torch.stack([feeds[i]._afeat[lo:lo + nwin] for i, _, lo in plan['windows'][i0:i1]])
+                logits[i0:i1].copy_(eng.sync_transformer(vwin, awin))
+        # read-out: one call for all feeds
+        outs = ops.track_pool_push(self.state, [f.slot for f in feeds], logits, plan['counts'], tr.lam, tr.grid if tr.posterior else None,
+                                   final=[f.slot for f in flush])
+        res, row = {}, 0
+        for f, g, n, out in zip(feeds, plan['geometry'], plan['counts'], outs):
+            f._trim(g)
+            res[f] = f._update(out, logits[row:row + n], g['new_windows'][0], g['new_windows'][1])
+            row += n
+        for f in flush:
+            f.closed = True
+            del self.feeds[f.slot]
+            self._free.append(f.slot)
+        return res
