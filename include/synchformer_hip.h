@@ -29,7 +29,7 @@ extern "C" {
 enum { SF_F32 = 0, SF_BF16 = 1, SF_F16 = 2, SF_U8 = 3, SF_I16 = 4 };   /* element types (SF_I16: PCM input of sf_resample_wave only) */
 enum { SF_EPI_NONE = 0, SF_EPI_GELU = 1 };                  /* GEMM epilogue activation */
 
-#define SF_ABI_VERSION 20
+#define SF_ABI_VERSION 21
 int sf_abi_version(void);
 const char* sf_last_error(void);
 /* "gfx950" + build flags; lets the host assert it loaded the library it built */
@@ -651,6 +651,36 @@ int sf_ingest_video_yuv16(const uint16_t* raw, int64_t stride_frame, int64_t str
                           int shift, int n_src, int H, int W, const int32_t* frame_table, const int32_t* y_first, const float* y_w, int taps_y,
                           const int32_t* x_first, const float* x_w, int taps_x, const int32_t* cy_first, const float* cy_w, int taps_cy, const int32_t* cx_first,
                           const float* cx_w, int taps_cx, const float* csc, uint8_t* out, int T_out, void* stream);
+
+/* The general form of sf_ingest_video_yuv and sf_ingest_video_yuv16 (ABI v21): three planes of 1-byte or 2-byte samples at any offsets and strides,
+ * chroma planes of Hc x Wc - 4:2:2 as capture cards, mezzanine codecs and hardware surfaces hand it out (uyvy422, yuyv422, yuv422p, nv16, yuv422p10le, p210, y210),
+ * the four 4:2:0 layouts of the two entries above, 4:4:4 planar.  With base = raw + f * stride_frame (all strides and offsets in BYTES),
+ *       Y[y, x] = base[y_off + y * stride_row  + x * stride_col]       y < H,  x < W
+ *       U[y, x] = base[u_off + y * stride_crow + x * stride_ccol]      y < Hc, x < Wc       (V: v_off)
+ *       sample  = bytes_per_sample == 1 ? byte : (word >> shift) & 1023
+ *   and from there sf_ingest_video_yuv's definition unchanged: the luma tables map H -> Hr and W -> Wr, the chroma tables Hc -> Hr and Wc -> Wr, sliced at the same
+ *   crop origin; fp32, horizontal pass first, taps ascending, fused multiply-adds, nothing rounded before the matrix; out = clamp(round_half_even(M (yuv - o)), 0,
+ *   255), uint8 planar (T_out, 3, 224, 224).  On a layout the two entries above serve, the output is theirs bit for bit.  With P the row pitch in bytes:
+ *       format       bytes  y_off  stride_col  u_off  v_off     stride_crow  stride_ccol  Hc x Wc    shift
+ *       uyvy422      1      1      2           0      2         P            4            H x W/2    -
+ *       yuyv422      1      0      2           1      3         P            4            H x W/2    -
+ *       yuv422p      1      0      1           H W    H W 3/2   W/2          1            H x W/2    -         (contiguous)
+ *       nv16         1      0      1           P H    P H + 1   P            2            H x W/2    -
+ *       yuv422p10le  2      0      2           2 H W  3 H W     W            2            H x W/2    0         (contiguous)
+ *       p210         2      0      2           P H    P H + 2   P            4            H x W/2    6
+ *       y210         2      0      4           2      6         P            8            H x W/2    6         (words Y0 U Y1 V)
+ *   Staging: interleaved chroma (v_off == u_off + bytes, stride_ccol == 2 bytes: NV12, NV16, P010, P210) is fetched once and split in registers, as in the entries
+ *   above.  A packed row (stride_col == 2 bytes, stride_ccol == 4 bytes, v_off == u_off + 2 bytes, |y_off - u_off| == bytes, stride_crow == stride_row, Hc == H, W even,
+ *   Wc == W / 2) is fetched as whole 4-sample macropixels with dword or 16-byte loads where the row is 4-byte aligned, once by the luma pass and once by the chroma
+ *   pass.  Every other layout, unaligned rows and row ends take one load per sample.  Even H and W are NOT required: the caller's format decides.
+ *   -1 before anything is launched on: everything the two entries above refuse (on the given Hc, Wc), bytes_per_sample outside {1, 2}, Hc outside 1 .. H, Wc outside
+ *   1 .. W, stride_col or stride_ccol below bytes_per_sample, for 2-byte samples an odd stride or offset or raw not 2-byte aligned, shift outside 0 .. 6, a luma row or
+ *   a pair of chroma rows too wide to stage (8-bit 4:4:4 at 3840 columns is).  T_out == 0 launches nothing.  One launch. */
+int sf_ingest_video_yuv_planes(const void* raw, int bytes_per_sample, int64_t stride_frame, int64_t y_off, int64_t stride_row, int64_t stride_col, int64_t u_off,
+                               int64_t v_off, int64_t stride_crow, int64_t stride_ccol, int shift, int n_src, int H, int W, int Hc, int Wc,
+                               const int32_t* frame_table, const int32_t* y_first, const float* y_w, int taps_y, const int32_t* x_first, const float* x_w, int taps_x,
+                               const int32_t* cy_first, const float* cy_w, int taps_cy, const int32_t* cx_first, const float* cx_w, int taps_cx, const float* csc,
+                               uint8_t* out, int T_out, void* stream);
 
 /* Backward of sf_attention for tiny groups (n_tok <= 8, head_dim 64: Motionformer time attention, vit_helper.py:343-344): same
  * addressing as the forward; dq | dk | dv rows of the group's tokens are written (=), the CLS key's dk | dv of every (seq, group) goes to

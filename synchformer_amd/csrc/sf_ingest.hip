@@ -1,10 +1,12 @@
-// Ingest of a decoded recording at its native geometry (DESIGN 3.11, 3.12): what the reference leaves to an ffmpeg subprocess before any of its code runs
+// Ingest of a decoded recording at its native geometry (DESIGN 3.11 - 3.13, 3.17): what the reference leaves to an ffmpeg subprocess before any of its code runs
 // (example.py:16-53: fps=25, short side 256, even dimensions, -ar 16000) plus the centre 224 crop of RGBSpatialCrop, as two launches.
 //   sf_ingest_video:   frame pick (frame_table) + antialiased bicubic resize + crop, uint8 -> uint8 planar (T_out, 3, 224, 224).  The resize is separable and the
 //                      two filter tables arrive already sliced to the crop, so only the 224 x 224 outputs are computed: a horizontal pass over the source rows a
 //                      tile of output rows needs (fp32, kept in LDS), then the vertical pass over those rows.
 //   sf_ingest_video_yuv: the same for 8-bit YUV 4:2:0 frames (NV12, I420): the three planes are resized, the colour matrix runs on the 224 x 224 result.
 //   sf_ingest_video_yuv16: the same for 10-bit YUV 4:2:0 frames in 16-bit samples (P010, yuv420p10le): the sample is (raw >> shift) & 1023.
+//   sf_ingest_video_yuv_planes: the general form of the two: three planes of 1- or 2-byte samples at any offsets and strides, chroma of Hc x Wc -
+//                      4:2:2 packed (uyvy422, yuyv422, y210), semi-planar (nv16, p210) and planar (yuv422p, yuv422p10le), the 4:2:0 layouts, 4:4:4 planar.
 //   sf_resample_wave:  zero-delay polyphase windowed-sinc resampler (the bank of ingest.resample_kernel), channels averaged on read, zero padding by bounds checks.
 // All video kernels run ONE resize pipeline, ing_plane_pass, over 1-byte or 2-byte samples (BS): ingest_video_kernel once per workgroup (one channel), the YUV
 // kernels twice (luma, then U and V together); the launchers size its LDS with one formula, ing_geometry.
@@ -50,14 +52,23 @@ typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 //      2-byte loads); INTER (s1 == s0 + 2, sx == 4: P010) takes the 16 bytes U V U V U V U V of four chroma columns as one 16-byte load (else four dwords);
 //   xw: tap j in row j + 1, TW = 2 nd + 1; the horizontal pass reads the nd = (taps_x + 2) / 2 aligned dwords that cover the taps, two samples per dword, half k of
 //      dword d against weight row 2 d + k + 1 - (off & 1).  Zero rows only add exact zeros, so the sums - taps ascending, fmaf - are those of BS = 1 term by term.
-template <int NP, bool INTER, int BS>
+// FORM = 2: the planes are PACKED into macropixels of 4 BS bytes, Y0 U Y1 V in some order (uyvy422, yuyv422, y210); pk is the byte of plane 0's first
+//   sample inside its macropixel, and the launcher has checked that every byte of macropixels [0, W / 2) of a row belongs to the frame.  NP = 1 (luma, sx == 2 BS):
+//   the staged row starts at xlo rounded down to 4 columns, a lane's 4 samples lie in two macropixels - 8 or 16 bytes fetched as dwords (one 16-byte load where
+//   aligned), every other sample picked with v_perm_b32.  NP = 2 (chroma, s1 == s0 + 2 BS, sx == 4 BS): four chroma columns are four macropixels - 16 or 32 bytes
+//   fetched once and split into the U and the V dwords.  Rows that are not 4-byte aligned and row ends take the strided loads.  What reaches LDS is the same either way.
+//   BS = 2 fetches twice the dwords it stages, so it stages at most ING_PF16 / 2 per lane and chunk (the launcher sizes R for that): the fetched words of a chunk then
+//   fit the registers of the plain form, all loads stay in flight together, and the kernel keeps three workgroups per CU instead of one (12.9 -> 5.0 us per frame).
+template <int NP, int FORM, int BS>
 __device__ __forceinline__ void ing_plane_pass(unsigned char* lds, const uint8_t* __restrict__ s0, const uint8_t* __restrict__ s1, int64_t sy, int64_t sx, int H, int W,
                                                const int32_t* __restrict__ y_first, const float* __restrict__ y_w, int taps_y,
                                                const int32_t* __restrict__ x_first, const float* __restrict__ x_w, int taps_x, int R, int RP, int TW, int r0, int shift,
-                                               float (&a0)[NP][4], float (&a1)[NP][4]) {
+                                               int pk, float (&a0)[NP][4], float (&a1)[NP][4]) {
   static_assert(BS == 1 || BS == 2, "samples of one or two bytes");
+  static_assert(FORM >= 0 && FORM <= 2, "plain, interleaved or packed");
+  constexpr bool INTER = FORM == 1;
   constexpr int PAD = BS == 1 ? 3 : 1;                                          // zero rows in front of the transposed table: samples per dword - 1
-  constexpr int PF = BS == 1 ? ING_PF : ING_PF16;
+  constexpr int PF = BS == 1 ? ING_PF : FORM == 2 ? ING_PF16 / 2 : ING_PF16;      // packed words: twice the staged dwords are fetched, so half are staged
   float* xw = (float*)lds;
   float* yw = xw + TW * ING_OUT;
   float* mid = yw + ING_TY * taps_y;
@@ -76,7 +87,7 @@ __device__ __forceinline__ void ing_plane_pass(unsigned char* lds, const uint8_t
 
   int xlo = x_first[0];
   xlo = xlo < 0 ? 0 : (xlo > W ? W : xlo);
-  if (BS == 2) xlo &= ~3;
+  if (BS == 2 || (FORM == 2 && NP == 1)) xlo &= ~3;
   int ys = y_first[r0], ye = y_first[r0 + ING_TY - 1] + taps_y;
   ys = ys < 0 ? 0 : ys;
   ye = ye > H ? H : ye;                                                        // rows past the picture carry the tables' zero padding: never read
@@ -127,7 +138,54 @@ __device__ __forceinline__ void ing_plane_pass(unsigned char* lds, const uint8_t
           const int64_t o = (int64_t)y * sy + (int64_t)(xlo + c) * sx;
           const bool full = c + 3 < valid_x;
           const uint8_t* gi = s0 + o;
-          if constexpr (BS == 1) {
+          bool packed = false;
+          if constexpr (FORM == 2) {
+            const uint8_t* gm = gi - pk;                                        // the first of the item's macropixels
+            packed = full && ((uintptr_t)gm & 3) == 0;
+            if (packed) {
+              const uint32_t sel = 0x01010101u * (uint32_t)(pk / BS);
+              if constexpr (BS == 1 && NP == 1) {                               // Y0 . Y1 . | Y2 . Y3 .
+                v[0] = __builtin_amdgcn_perm(((const uint32_t*)gm)[1], ((const uint32_t*)gm)[0], 0x06040200u + sel);
+              } else if constexpr (BS == 1) {                                   // U . V . of four columns
+                uint32_t d[4];
+                if (((uintptr_t)gm & 15) == 0) {
+                  const u32x4 w = *(const u32x4*)gm;
+                  d[0] = w.x; d[1] = w.y; d[2] = w.z; d[3] = w.w;
+                } else {
+#pragma unroll
+                  for (int i = 0; i < 4; ++i) d[i] = ((const uint32_t*)gm)[i];
+                }
+                const uint32_t lo = __builtin_amdgcn_perm(d[1], d[0], 0x06020400u + sel), hi = __builtin_amdgcn_perm(d[3], d[2], 0x06020400u + sel);   // U U V V
+                v[0] = __builtin_amdgcn_perm(hi, lo, 0x05040100u);
+                v[NP - 1] = __builtin_amdgcn_perm(hi, lo, 0x07060302u);
+              } else {                                                          // 16-bit words: half pk / 2 of every other dword
+                constexpr int ND = 4 * NP;
+                uint32_t d[ND];
+                if (((uintptr_t)gm & 15) == 0) {
+#pragma unroll
+                  for (int i = 0; i < NP; ++i) {
+                    const u32x4 w = ((const u32x4*)gm)[i];
+                    d[4 * i] = w.x; d[4 * i + 1] = w.y; d[4 * i + 2] = w.z; d[4 * i + 3] = w.w;
+                  }
+                } else {
+#pragma unroll
+                  for (int i = 0; i < ND; ++i) d[i] = ((const uint32_t*)gm)[i];
+                }
+                const uint32_t s16 = 0x05040100u + 2u * sel;
+                if constexpr (NP == 1) {                                        // Y0 . Y1 . Y2 . Y3 .
+                  v[0] = __builtin_amdgcn_perm(d[1], d[0], s16);
+                  v[1] = __builtin_amdgcn_perm(d[3], d[2], s16);
+                } else {                                                        // U . V . of four columns
+                  v[0] = __builtin_amdgcn_perm(d[2], d[0], s16);
+                  v[1] = __builtin_amdgcn_perm(d[ND - 2], d[ND - 4], s16);
+                  v[2 * (NP - 1)] = __builtin_amdgcn_perm(d[3], d[1], s16);
+                  v[2 * (NP - 1) + 1] = __builtin_amdgcn_perm(d[ND - 1], d[ND - 3], s16);
+                }
+              }
+            }
+          }
+          if (packed) {
+          } else if constexpr (BS == 1) {
             if (NP == 2 && INTER && full && ((uintptr_t)gi & 3) == 0) {
               const uint32_t a = ((const uint32_t*)gi)[0], b = ((const uint32_t*)gi)[1];
               v[0] = (a & 0xffu) | ((a >> 8) & 0xff00u) | ((b & 0xffu) << 16) | ((b << 8) & 0xff000000u);
@@ -299,7 +357,7 @@ __global__ __launch_bounds__(256) void ingest_video_kernel(const uint8_t* __rest
   const int r0 = blockIdx.x * ING_TY, ch = blockIdx.y, fo = blockIdx.z;
   const uint8_t* src = raw + (int64_t)ing_pick_frame(frame_table, fo, n_src) * sf + (int64_t)ch * sc;
   float a0[1][4] = {}, a1[1][4] = {};
-  ing_plane_pass<1, false, 1>(ing_lds, src, src, sy, sx, H, W, y_first, y_w, taps_y, x_first, x_w, taps_x, R, RP, TW, r0, 0, a0, a1);
+  ing_plane_pass<1, 0, 1>(ing_lds, src, src, sy, sx, H, W, y_first, y_w, taps_y, x_first, x_w, taps_x, R, RP, TW, r0, 0, 0, a0, a1);
   if (tid < 224) {
     uint8_t* o = out + (((int64_t)fo * 3 + ch) * ING_OUT + r0 + tid / 56) * ING_OUT + 4 * (tid % 56);
     *(uint32_t*)o = ing_pack4(a0[0]);
@@ -314,23 +372,33 @@ struct IngCsc { float m[9], o[3]; };                                            
 // lane); then the colour matrix and three full 224-byte lines per output row.  BS: bytes per sample.  BS = 2 (P010: INTER, shift 6; yuv420p10le: shift 0): csx in
 // bytes, v = (word >> shift) & 1023, up to ING_PF16 staging registers per lane - LDS holds two workgroups per CU at the widest rows anyway, so nothing is lost to
 // the larger register budget there.  BS = 1 ignores shift.
-template <bool INTER, int BS>
+// GEN = 0: the 4:2:0 entries - luma at the frame base with unit column stride, chroma planes of H / 2 x W / 2; the trailing arguments from y_off on are ignored, so
+// these instantiations are what they were before the general entry.  GEN = 1: sf_ingest_video_yuv_planes - luma at y_off with column stride sxl,
+// chroma planes of Hc x Wc; CF = 0 (separate planes: any strides) or 1 (interleaved U V: NV12, NV16, P010, P210).  GEN = 2, CF = 2: a packed 4:2:2 row (uyvy422,
+// yuyv422, y210), both passes on the packed staging of ing_plane_pass; pky / pkc: the byte of Y0 / of U inside the macropixel.
+template <int CF, int BS, int GEN = 0>
 __global__ __launch_bounds__(256) void ingest_video_yuv_kernel(const uint8_t* __restrict__ raw, int64_t sf, int64_t sy, int64_t u_off, int64_t v_off, int64_t csy,
                                                                 int64_t csx, int n_src, int H, int W, const int32_t* __restrict__ frame_table,
                                                                 const int32_t* __restrict__ y_first, const float* __restrict__ y_w, int taps_y,
                                                                 const int32_t* __restrict__ x_first, const float* __restrict__ x_w, int taps_x,
                                                                 const int32_t* __restrict__ cy_first, const float* __restrict__ cy_w, int taps_cy,
                                                                 const int32_t* __restrict__ cx_first, const float* __restrict__ cx_w, int taps_cx, IngCsc csc,
-                                                                uint8_t* __restrict__ out, int R, int RP, int TW, int RPc, int TWc, int shift) {
+                                                                uint8_t* __restrict__ out, int R, int RP, int TW, int RPc, int TWc, int shift, int64_t y_off,
+                                                                int64_t sxl, int Hc, int Wc, int pky, int pkc) {
+  static_assert((GEN == 2) == (CF == 2), "the packed luma and chroma forms come together");
   extern __shared__ __align__(16) unsigned char ing_lds[];
   const int tid = threadIdx.x;
   const int r0 = blockIdx.x * ING_TY, fo = blockIdx.y;
   const uint8_t* src = raw + (int64_t)ing_pick_frame(frame_table, fo, n_src) * sf;
   float ya[1][4] = {}, yb[1][4] = {}, c0[2][4] = {}, c1[2][4] = {};
-  ing_plane_pass<1, false, BS>(ing_lds, src, src, sy, BS, H, W, y_first, y_w, taps_y, x_first, x_w, taps_x, R, RP, TW, r0, shift, ya, yb);
+  if constexpr (GEN == 0)
+    ing_plane_pass<1, 0, BS>(ing_lds, src, src, sy, BS, H, W, y_first, y_w, taps_y, x_first, x_w, taps_x, R, RP, TW, r0, shift, 0, ya, yb);
+  else
+    ing_plane_pass<1, GEN == 2 ? 2 : 0, BS>(ing_lds, src + y_off, src + y_off, sy, sxl, H, W, y_first, y_w, taps_y, x_first, x_w, taps_x, R, RP, TW, r0, shift, pky, ya,
+                                            yb);
   __syncthreads();                                                             // every lane is past the LDS of the luma pass
-  ing_plane_pass<2, INTER, BS>(ing_lds, src + u_off, src + v_off, csy, csx, H >> 1, W >> 1, cy_first, cy_w, taps_cy, cx_first, cx_w, taps_cx, 4, RPc, TWc, r0, shift, c0,
-                               c1);
+  ing_plane_pass<2, CF, BS>(ing_lds, src + u_off, src + v_off, csy, csx, GEN ? Hc : H >> 1, GEN ? Wc : W >> 1, cy_first, cy_w, taps_cy, cx_first, cx_w, taps_cx, 4, RPc,
+                            TWc, r0, shift, GEN == 2 ? pkc : 0, c0, c1);
   if (tid < 224) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -352,11 +420,11 @@ __global__ __launch_bounds__(256) void ingest_video_yuv_kernel(const uint8_t* __
 // max_rows and at most ING_PF staging registers per lane, rounded down to a multiple of 4 - and the bytes in all.  false: not even 4 rows fit.  bs: bytes per
 // sample; 2 takes the padded table, the LDS cap and the register budget of the 16-bit instantiation (RP stays in samples).
 struct IngGeom { int RP, TW, R, lds; };
-static bool ing_geometry(int W, int taps_y, int taps_x, int planes, int max_rows, int bs, IngGeom* g) {
+static bool ing_geometry(int W, int taps_y, int taps_x, int planes, int max_rows, int bs, IngGeom* g, int pf = 0) {
   g->RP = ((W + taps_x + 3) & ~3) + ING_ROW_SLACK;
   g->TW = bs == 1 ? 4 * ((taps_x + 6) >> 2) + 3 : 2 * ((taps_x + 2) >> 1) + 1;
   const int fixed = (g->TW * ING_OUT + ING_TY * taps_y) * 4, per_row = planes * (g->RP * bs + ING_OUT * 4);
-  const int pf_bytes = 256 * (bs == 1 ? ING_PF : ING_PF16) * 4;
+  const int pf_bytes = 256 * (pf ? pf : bs == 1 ? ING_PF : ING_PF16) * 4;
   int R = ((bs == 1 ? ING_LDS_BYTES : ING_LDS_BYTES16) - fixed) / per_row;
   R = R > max_rows ? max_rows : R;
   if (R > pf_bytes / (planes * g->RP * bs)) R = pf_bytes / (planes * g->RP * bs);
@@ -413,12 +481,12 @@ extern "C" int sf_ingest_video_yuv(const uint8_t* raw, int64_t stride_frame, int
   auto launch = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, dim3(ING_OUT / ING_TY, (unsigned)T_out), dim3(256), gy.lds > gc.lds ? gy.lds : gc.lds, (hipStream_t)stream, raw, stride_frame,
                        stride_row, u_off, v_off, stride_crow, stride_ccol, n_src, H, W, frame_table, y_first, y_w, taps_y, x_first, x_w, taps_x, cy_first, cy_w,
-                       taps_cy, cx_first, cx_w, taps_cx, k, out, gy.R, gy.RP, gy.TW, gc.RP, gc.TW, 0);
+                       taps_cy, cx_first, cx_w, taps_cx, k, out, gy.R, gy.RP, gy.TW, gc.RP, gc.TW, 0, (int64_t)0, (int64_t)1, H / 2, W / 2, 0, 0);
   };
   if (v_off == u_off + 1 && stride_ccol == 2)                                   // NV12: one fetch of the interleaved rows serves both planes
-    launch(ingest_video_yuv_kernel<true, 1>);
+    launch(ingest_video_yuv_kernel<1, 1>);
   else
-    launch(ingest_video_yuv_kernel<false, 1>);
+    launch(ingest_video_yuv_kernel<0, 1>);
   SF_LAUNCH_CHECK();
   return 0;
 }
@@ -451,12 +519,71 @@ extern "C" int sf_ingest_video_yuv16(const uint16_t* raw, int64_t stride_frame, 
     if ((rc = sf_prepare_kernel((const void*)kernel, ING_LDS_BYTES16, "sf_ingest_video_yuv16")) != 0) return;
     hipLaunchKernelGGL(kernel, dim3(ING_OUT / ING_TY, (unsigned)T_out), dim3(256), gy.lds > gc.lds ? gy.lds : gc.lds, (hipStream_t)stream, (const uint8_t*)raw,
                        stride_frame, stride_row, u_off, v_off, stride_crow, stride_ccol, n_src, H, W, frame_table, y_first, y_w, taps_y, x_first, x_w, taps_x, cy_first,
-                       cy_w, taps_cy, cx_first, cx_w, taps_cx, k, out, gy.R, gy.RP, gy.TW, gc.RP, gc.TW, shift);
+                       cy_w, taps_cy, cx_first, cx_w, taps_cx, k, out, gy.R, gy.RP, gy.TW, gc.RP, gc.TW, shift, (int64_t)0, (int64_t)2, H / 2, W / 2, 0, 0);
   };
   if (v_off == u_off + 2 && stride_ccol == 4)                                   // P010: one fetch of the interleaved rows serves both planes
-    launch(ingest_video_yuv_kernel<true, 2>);
+    launch(ingest_video_yuv_kernel<1, 2>);
   else
-    launch(ingest_video_yuv_kernel<false, 2>);
+    launch(ingest_video_yuv_kernel<0, 2>);
+  if (rc) return rc;
+  SF_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int sf_ingest_video_yuv_planes(const void* raw, int bytes_per_sample, int64_t stride_frame, int64_t y_off, int64_t stride_row, int64_t stride_col,
+                                          int64_t u_off, int64_t v_off, int64_t stride_crow, int64_t stride_ccol, int shift, int n_src, int H, int W, int Hc, int Wc,
+                                          const int32_t* frame_table, const int32_t* y_first, const float* y_w, int taps_y, const int32_t* x_first, const float* x_w,
+                                          int taps_x, const int32_t* cy_first, const float* cy_w, int taps_cy, const int32_t* cx_first, const float* cx_w, int taps_cx,
+                                          const float* csc, uint8_t* out, int T_out, void* stream) {
+  const char* who = "sf_ingest_video_yuv_planes";
+  if (ing_check_args(who, T_out, {taps_y, taps_x, taps_cy, taps_cx}, out, W)) return -1;
+  const int bs = bytes_per_sample;
+  SF_CHECK_ARG(bs == 1 || bs == 2, "%s: bytes_per_sample = %d (1 or 2)", who, bs);
+  SF_CHECK_ARG(n_src >= 1 && H >= 1 && W >= 1, "%s: source of %d frames %d x %d", who, n_src, H, W);
+  SF_CHECK_ARG(Hc >= 1 && Hc <= H && Wc >= 1 && Wc <= W, "%s: chroma planes of %d x %d beside a luma plane of %d x %d (1 .. H by 1 .. W)", who, Hc, Wc, H, W);
+  SF_CHECK_ARG(stride_frame >= 0 && y_off >= 0 && stride_row >= 0 && u_off >= 0 && v_off >= 0 && stride_crow >= 0 && stride_col >= bs && stride_ccol >= bs,
+               "%s: negative byte stride or offset, or a column stride below the %d bytes of a sample", who, bs);
+  SF_CHECK_ARG(bs == 1 || ((stride_frame | y_off | stride_row | stride_col | u_off | v_off | stride_crow | stride_ccol) & 1) == 0,
+               "%s: odd byte stride or offset (16-bit samples are 2-byte aligned)", who);
+  SF_CHECK_ARG(shift >= 0 && shift <= 6, "%s: shift = %d (0 .. 6: ten bits of a 16-bit word)", who, shift);
+  if (T_out == 0) return 0;
+  SF_CHECK_ARG(raw && frame_table && y_first && y_w && x_first && x_w && cy_first && cy_w && cx_first && cx_w && csc && out, "%s: null pointer", who);
+  SF_CHECK_ARG(bs == 1 || ((uintptr_t)raw & 1) == 0, "%s: raw must be 2-byte aligned", who);
+  IngGeom gy, gc;
+  SF_CHECK_ARG(ing_geometry(W, taps_y, taps_x, 1, ING_MAX_ROWS, bs, &gy), "%s: W = %d is too wide for four staged source rows in LDS at taps_x = %d", who, W, taps_x);
+  SF_CHECK_ARG(ing_geometry(Wc, taps_cy, taps_cx, 2, 4, bs, &gc), "%s: Wc = %d is too wide for four staged rows of both chroma planes in LDS at taps_cx = %d", who, Wc,
+               taps_cx);
+  IngCsc k;
+  for (int i = 0; i < 9; ++i) k.m[i] = csc[i];
+  for (int i = 0; i < 3; ++i) k.o[i] = csc[9 + i];
+  // packed 4:2:2: macropixels of 4 samples, Y0 and U in the first two, Y1 = Y0 + 2 samples, V = U + 2 samples, one row pitch, every byte of the W / 2 macropixels of a
+  // row a sample of the frame - so whole macropixels may be fetched
+  const int64_t m = y_off < u_off ? y_off : u_off;
+  bool packed = stride_col == 2 * bs && stride_ccol == 4 * bs && v_off == u_off + 2 * bs && stride_crow == stride_row && Hc == H && W % 2 == 0 && Wc == W / 2 &&
+                      (y_off < u_off ? u_off - y_off : y_off - u_off) == bs;
+  const bool inter = v_off == u_off + bs && stride_ccol == 2 * bs;
+  if (packed && bs == 2) {                                                      // the packed 16-bit form stages half as much per chunk; rows too wide for that take the strided loads
+    IngGeom py, pc;
+    packed = ing_geometry(W, taps_y, taps_x, 1, ING_MAX_ROWS, 2, &py, ING_PF16 / 2) && ing_geometry(Wc, taps_cy, taps_cx, 2, 4, 2, &pc, ING_PF16 / 2);
+    if (packed) { gy = py; gc = pc; }
+  }
+  int rc = 0;
+  auto launch = [&](auto kernel) {
+    if (bs == 2 && (rc = sf_prepare_kernel((const void*)kernel, ING_LDS_BYTES16, who)) != 0) return;
+    hipLaunchKernelGGL(kernel, dim3(ING_OUT / ING_TY, (unsigned)T_out), dim3(256), gy.lds > gc.lds ? gy.lds : gc.lds, (hipStream_t)stream, (const uint8_t*)raw,
+                       stride_frame, stride_row, u_off, v_off, stride_crow, stride_ccol, n_src, H, W, frame_table, y_first, y_w, taps_y, x_first, x_w, taps_x, cy_first,
+                       cy_w, taps_cy, cx_first, cx_w, taps_cx, k, out, gy.R, gy.RP, gy.TW, gc.RP, gc.TW, shift, y_off, stride_col, Hc, Wc, (int)(y_off - m),
+                       (int)(u_off - m));
+  };
+  if (bs == 1) {
+    if (packed) launch(ingest_video_yuv_kernel<2, 1, 2>);
+    else if (inter) launch(ingest_video_yuv_kernel<1, 1, 1>);
+    else launch(ingest_video_yuv_kernel<0, 1, 1>);
+  } else {
+    if (packed) launch(ingest_video_yuv_kernel<2, 2, 2>);
+    else if (inter) launch(ingest_video_yuv_kernel<1, 2, 1>);
+    else launch(ingest_video_yuv_kernel<0, 2, 1>);
+  }
   if (rc) return rc;
   SF_LAUNCH_CHECK();
   return 0;

@@ -1,4 +1,4 @@
-"""Ingest a decoded recording at its native frame rate, size, pixel format and sample rate (DESIGN 3.11 - 3.13).
+"""Ingest a decoded recording at its native frame rate, size, pixel format and sample rate (DESIGN 3.11 - 3.13, 3.17).
 
 The reference re-encodes every input through an ffmpeg subprocess before any of its code runs (example.py:16-53: fps=25, short side scaled to 256, dimensions
 cropped to even, -ar 16000) and then takes the centre 224 crop of RGBSpatialCrop.  Here the same step is host geometry (this module: pure Python / torch,
@@ -28,12 +28,18 @@ chroma_loc says where the chroma samples sit: 'center' (the default: chroma as a
 of H.264, HEVC and MPEG-2) or 'topleft' (the BT.2020 default) - a quarter of a chroma sample in the chroma tables (aa_bicubic_table(shift=0.25)), for every YUV
 format.  csc=(M, offsets) overrides colorspace / full_range with a matrix on the format's own sample scale: this is how BT.2020 coefficients are passed.
 
-Out of scope: decoding, 12-bit / 4:2:2 / 4:4:4 input, BT.2020 in csc_matrix, transfer functions (PQ, HLG: a 10-bit HDR stream is converted by the matrix alone,
+4:2:2 is what a live feed delivers - capture cards hand out packed 'uyvy422' / 'yuyv422', contribution codecs decode to 'yuv422p' / 'yuv422p10le',
+hardware surfaces are 'nv16' / 'p210' / 'y210' - and goes through the general entry (ops.ingest_video_planes over plane_layout):
+
+    ing = RecordingIngest(dev, 50, (1080, 1920), 48000, pix_fmt='uyvy422', colorspace='bt709', chroma_loc='left')
+    feed = tracker.stream(ingest=ing)                           # raw frames (T, 1080, 1920, 2) uint8; y210: uint16; the others (T, 2 H, W)
+
+Out of scope: decoding, 12-bit / 4:4:4 input through RecordingIngest (ops.ingest_video_planes takes a 4:4:4 planar layout), v210, interlaced fields, BT.2020 in csc_matrix, transfer functions (PQ, HLG: a 10-bit HDR stream is converted by the matrix alone,
 no tone mapping), double-buffered uploads, several recordings per call.
 """
 import math
 from fractions import Fraction
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
@@ -41,8 +47,67 @@ CROP = 224                       # the model's input size; ops.INGEST_OUT and op
 MAX_TAPS = 35                    # sf_ingest_video's range: a short side up to 2160 at resize_side 256
 PIX_FMTS = ('rgb24', 'nv12', 'yuv420p', 'p010', 'yuv420p10le')
 PIX_FMTS_16 = ('p010', 'yuv420p10le')   # 10-bit samples in uint16: ops.ingest_video_yuv16
+PIX_FMTS_422 = ('uyvy422', 'yuyv422', 'yuv422p', 'nv16', 'yuv422p10le', 'p210', 'y210')     # 4:2:2: ops.ingest_video_planes
+PIX_FMTS_422_16 = ('yuv422p10le', 'p210', 'y210')                                           # of those, 10-bit samples in uint16
+PIX_FMTS_PACKED = ('uyvy422', 'yuyv422', 'y210')                                            # raw frames (T, H, W, 2): a macropixel Y0 U Y1 V (in some order) per two columns
 CHROMA_LOCS = {'center': (0.0, 0.0), 'left': (0.0, 0.25), 'topleft': (0.25, 0.25)}       # (shift of the cy tables, of the cx tables)
 _KR_KB = {'bt601': (0.299, 0.114), 'bt709': (0.2126, 0.0722)}
+
+
+class PlaneLayout(NamedTuple):
+    """Where the three planes of one frame lie: the arguments of sf_ingest_video_yuv_planes.  Strides and offsets in BYTES; the sample is a byte, or
+    (word >> shift) & 1023 of a 16-bit word."""
+    bytes_per_sample: int
+    H: int
+    W: int
+    Hc: int
+    Wc: int
+    stride_frame: int
+    y_off: int
+    stride_row: int
+    stride_col: int
+    u_off: int
+    v_off: int
+    stride_crow: int
+    stride_ccol: int
+    shift: int
+
+
+def plane_layout(pix_fmt: str, H: int, W: int, strides=None) -> PlaneLayout:
+    """The PlaneLayout of raw frames of H x W in a named format: the seven 4:2:2 formats (PIX_FMTS_422) and the four 4:2:0 ones.  strides: the raw tensor's own
+    strides in ELEMENTS (frame, row, column - or frame, row, column, 2 for the packed formats); None: contiguous.  A row pitch above W is taken where the format has
+    one (packed, nv12 / nv16, p010 / p210); the planar formats are contiguous.  ValueError on an unknown name, odd W, odd H for 4:2:0, or strides the format cannot
+    have.  The raw shapes: 4:2:0 (T, 3 H / 2, W); uyvy422 / yuyv422 / y210 (T, H, W, 2); the other 4:2:2 formats (T, 2 H, W)."""
+    H, W = int(H), int(W)
+    fmts = PIX_FMTS[1:] + PIX_FMTS_422
+    if pix_fmt not in fmts:
+        raise ValueError(f'plane_layout: pix_fmt = {pix_fmt!r}: one of {fmts}')
+    is422 = pix_fmt in PIX_FMTS_422
+    if H < 1 or W < 2 or W % 2 or (H % 2 and not is422):
+        raise ValueError(f'plane_layout: {H} x {W} with pix_fmt = {pix_fmt!r}: {"4:2:2 takes even W" if is422 else "4:2:0 takes even H and W"}')
+    b = 2 if pix_fmt in PIX_FMTS_16 + PIX_FMTS_422_16 else 1
+    packed = pix_fmt in PIX_FMTS_PACKED
+    rows = H if packed else 2 * H if is422 else 3 * H // 2
+    if strides is None:
+        strides = (rows * W * 2, W * 2, 2, 1) if packed else (rows * W, W, 1)
+    strides = tuple(int(v) for v in strides)
+    if len(strides) != (4 if packed else 3) or strides[0] < 0:
+        raise ValueError(f'plane_layout: {pix_fmt} frames with strides {strides}')
+    sf, sy = strides[0], strides[1]
+    pitched = packed or pix_fmt in ('nv12', 'nv16', 'p010', 'p210')
+    if strides[2:] != ((2, 1) if packed else (1,)) or (sy < (2 * W if packed else W) if pitched else sy != W):
+        raise ValueError(f'plane_layout: {pix_fmt} frames with strides {strides}: '
+                         + ('inner strides (2, 1) and a row stride of at least 2 W expected' if packed else
+                            'unit column stride and ' + ('a row stride of at least W' if pitched else 'contiguous rows') + ' expected'))
+    P = sy * b                                                                    # the row pitch in bytes
+    Hc = H if is422 else H // 2
+    shift = 6 if pix_fmt in ('p010', 'p210', 'y210') else 0
+    if packed:                                                                    # y_off, u_off, v_off inside the macropixel, in samples
+        yo, uo, vo = (1, 0, 2) if pix_fmt == 'uyvy422' else (0, 1, 3)
+        return PlaneLayout(b, H, W, Hc, W // 2, sf * b, yo * b, P, 2 * b, uo * b, vo * b, P, 4 * b, shift)
+    if pitched:                                                                   # H luma rows, then the rows of interleaved U V
+        return PlaneLayout(b, H, W, Hc, W // 2, sf * b, 0, P, b, P * H, P * H + b, P, 2 * b, shift)
+    return PlaneLayout(b, H, W, Hc, W // 2, sf * b, 0, P, b, H * W * b, (H * W + Hc * (W // 2)) * b, (W // 2) * b, b, shift)
 
 
 def _fraction(fps) -> Fraction:
@@ -185,15 +250,17 @@ class RecordingIngest:
     otherwise planar (T, 3, H, W); resize_side: what the short side is scaled to (256, the even cut of the other side as in example.py); crop stays 224, centred
     with RGBSpatialCrop's origin int(round((Hr - 224) / 2.)).  pix_fmt: 'rgb24' (the layouts above), or 'nv12' / 'yuv420p': raw frames are (T, 3 H / 2, W), 8-bit
     YUV 4:2:0 (ops.ingest_video_yuv), or 'p010' / 'yuv420p10le': the same shape in uint16 (int16 is read as the same bits), 10-bit YUV 4:2:0
-    (ops.ingest_video_yuv16) - converted with csc_matrix(colorspace, full_range, bit_depth) after the resize, or with csc = (M (3, 3), offsets (3,)) on the format's
+    (ops.ingest_video_yuv16), or one of PIX_FMTS_422: 4:2:2 (ops.ingest_video_planes) - 'uyvy422' / 'yuyv422' uint8 (T, H, W, 2), a pitched view read in place
+    (inner strides 2, 1); 'y210' the same in uint16; 'nv16' uint8 / 'p210' uint16 (T, 2 H, W) at any row pitch; 'yuv422p' uint8 / 'yuv422p10le' uint16 (T, 2 H, W)
+    contiguous; even W only, an odd H is legal; the chroma rows take the luma tables, so 'topleft' is 'left' - converted with csc_matrix(colorspace, full_range, bit_depth) after the resize, or with csc = (M (3, 3), offsets (3,)) on the format's
     own sample scale when given (it overrides colorspace / full_range; e.g. BT.2020 coefficients).  chroma_loc: 'center', 'left' or 'topleft' (CHROMA_LOCS; YUV
     formats only).  ValueError on resize_side < crop, crop != 224, a source so large that a filter row passes 35 taps (short side above ~2160 at resize_side 256),
     an unknown pix_fmt, colorspace or chroma_loc, chroma_loc or csc with rgb24, and for a YUV format odd H or W or channels_last=True."""
 
     def __init__(self, device, fps_in, size_in, rate_in: int, channels_last: bool = False, resize_side: int = 256, crop: int = CROP, pix_fmt: str = 'rgb24',
                  colorspace: str = 'bt601', full_range: bool = False, chroma_loc: str = 'center', csc=None):
-        if pix_fmt not in PIX_FMTS:
-            raise ValueError(f'pix_fmt = {pix_fmt!r}: one of {PIX_FMTS}')
+        if pix_fmt not in PIX_FMTS + PIX_FMTS_422:
+            raise ValueError(f'pix_fmt = {pix_fmt!r}: one of {PIX_FMTS + PIX_FMTS_422}')
         if chroma_loc not in CHROMA_LOCS:
             raise ValueError(f'chroma_loc = {chroma_loc!r}: one of {tuple(CHROMA_LOCS)}')
         if pix_fmt == 'rgb24' and (chroma_loc != 'center' or csc is not None):
@@ -218,18 +285,22 @@ class RecordingIngest:
                              f'(a short side up to 2160 at 256)')
         self.pix_fmt = pix_fmt
         if pix_fmt != 'rgb24':
+            is422 = pix_fmt in PIX_FMTS_422
             if channels_last:
-                raise ValueError(f'channels_last=True with pix_fmt = {pix_fmt!r}: a YUV frame is (3 H / 2, W)')
-            if self.H % 2 or self.W % 2:
-                raise ValueError(f'{self.H} x {self.W} with pix_fmt = {pix_fmt!r}: 4:2:0 takes even H and W')
+                raise ValueError(f'channels_last=True with pix_fmt = {pix_fmt!r}: a YUV frame is '
+                                 f'{"(H, W, 2)" if pix_fmt in PIX_FMTS_PACKED else "(2 H, W)" if is422 else "(3 H / 2, W)"}')
+            if self.W % 2 or (self.H % 2 and not is422):
+                raise ValueError(f'{self.H} x {self.W} with pix_fmt = {pix_fmt!r}: {"4:2:2 takes even W" if is422 else "4:2:0 takes even H and W"}')
             # chroma: an (H / 2, W / 2) image resized to the same (Hr, Wr), sliced at the same crop origin; never more taps than luma
             # chroma_loc: the quarter-sample shift of sited chroma goes into these tables, the kernels never see it
             self.chroma_loc = chroma_loc
-            self.cy_first, self.cy_w, self.taps_cy = _crop_table(self.H // 2, self.Hr, self.y0, crop, self.dev, CHROMA_LOCS[chroma_loc][0])
+            # 4:2:2 has no vertical subsampling: the chroma rows are the luma rows, the luma tables serve them and 'topleft' is 'left'
+            self.cy_first, self.cy_w, self.taps_cy = (self.y_first, self.y_w, self.taps_y) if is422 else \
+                _crop_table(self.H // 2, self.Hr, self.y0, crop, self.dev, CHROMA_LOCS[chroma_loc][0])
             self.cx_first, self.cx_w, self.taps_cx = _crop_table(self.W // 2, self.Wr, self.x0, crop, self.dev, CHROMA_LOCS[chroma_loc][1])
             self.colorspace, self.full_range = colorspace, bool(full_range)
             if csc is None:
-                M, off = csc_matrix(colorspace, full_range, 10 if pix_fmt in PIX_FMTS_16 else 8)
+                M, off = csc_matrix(colorspace, full_range, 10 if pix_fmt in PIX_FMTS_16 + PIX_FMTS_422_16 else 8)
             else:
                 M, off = (torch.as_tensor(v, dtype=torch.float64).cpu() for v in csc)
                 if M.shape != (3, 3) or off.shape != (3,):
@@ -257,8 +328,9 @@ class RecordingIngest:
         return -(-self.n * int(n_in) // self.o)
 
     def _check_frames(self, raw: torch.Tensor):
-        want = (self.H * 3 // 2, self.W) if self.pix_fmt != 'rgb24' else (self.H, self.W, 3) if self.channels_last else (3, self.H, self.W)
-        dtypes = (torch.uint16, torch.int16) if self.pix_fmt in PIX_FMTS_16 else (torch.uint8,)
+        want = (self.H, self.W, 2) if self.pix_fmt in PIX_FMTS_PACKED else (2 * self.H, self.W) if self.pix_fmt in PIX_FMTS_422 else \
+            (self.H * 3 // 2, self.W) if self.pix_fmt != 'rgb24' else (self.H, self.W, 3) if self.channels_last else (3, self.H, self.W)
+        dtypes = (torch.uint16, torch.int16) if self.pix_fmt in PIX_FMTS_16 + PIX_FMTS_422_16 else (torch.uint8,)
         if raw.dim() != len(want) + 1 or raw.dtype not in dtypes or tuple(raw.shape[1:]) != want:
             raise ValueError(f'raw frames: expected {str(dtypes[0])[6:]} (T, {", ".join(map(str, want))}), got {raw.dtype} {tuple(raw.shape)}')
 
@@ -278,6 +350,9 @@ class RecordingIngest:
     def _resize(self, src: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
         """Output frame j = source frame src[t[j]] (src on the device, t int32 on the host), resized and cropped."""
         from . import ops
+        if self.pix_fmt in PIX_FMTS_422:
+            return ops.ingest_video_planes(src, plane_layout(self.pix_fmt, self.H, self.W, src.stride()), t.to(self.dev, non_blocking=True), self.y_first, self.y_w,
+                                           self.x_first, self.x_w, self.cy_first, self.cy_w, self.cx_first, self.cx_w, self.csc)
         if self.pix_fmt != 'rgb24':
             op = ops.ingest_video_yuv16 if self.pix_fmt in PIX_FMTS_16 else ops.ingest_video_yuv
             return op(src, self.pix_fmt, t.to(self.dev, non_blocking=True), self.y_first, self.y_w, self.x_first, self.x_w, self.cy_first, self.cy_w,

@@ -982,6 +982,40 @@ def ingest_video_yuv16(raw: torch.Tensor, pix_fmt: str, frame_table: torch.Tenso
         src, 2 * sf, 2 * sy, u_off, v_off, csy, csx, _YUV16_SHIFT[pix_fmt], n_src, H, W, ft, *tabs, C.addressof(csc_c), o, n, _stream()))
 
 
+def ingest_video_planes(raw: torch.Tensor, layout, frame_table: torch.Tensor, y_first: torch.Tensor, y_w: torch.Tensor, x_first: torch.Tensor, x_w: torch.Tensor,
+                        cy_first: torch.Tensor, cy_w: torch.Tensor, cx_first: torch.Tensor, cx_w: torch.Tensor, csc, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The general YUV ingest (sf_ingest_video_yuv_planes): raw uint8, or uint16 / int16 (the same bits), on the device, frames along dim 0, any shape
+    behind it; layout: an ingest.PlaneLayout (ingest.plane_layout for the named formats, or written out: 4:4:4 planar is Hc = H, Wc = W with the luma tables for
+    chroma) saying in BYTES where the three planes of a frame lie and how many bytes a sample has.  y_* / x_*: the luma tables (H -> Hr, W -> Wr); cy_* / cx_*: the
+    chroma tables (Hc -> Hr, Wc -> Wr), sliced at the same crop origin; csc: 12 floats on the samples' own scale -> uint8 (T_out, 3, 224, 224).  ValueError when the
+    dtype does not hold layout.bytes_per_sample bytes or when a plane of the layout reaches outside the tensor; what the launcher refuses is a RuntimeError."""
+    L = layout
+    if raw.dim() < 2 or raw.dtype not in ((torch.uint8,) if L.bytes_per_sample == 1 else (torch.uint16, torch.int16)):
+        raise ValueError(f'ingest_video_planes: expected {"uint8" if L.bytes_per_sample == 1 else "uint16"} frames (n, ...) for samples of {L.bytes_per_sample} '
+                         f'byte(s), got {raw.dtype} {tuple(raw.shape)}')
+    n_src, b = raw.shape[0], L.bytes_per_sample
+    if min(L) < 0 or min(L.H, L.W, L.Hc, L.Wc) < 1 or min(L.stride_col, L.stride_ccol) < b:
+        raise ValueError(f'ingest_video_planes: {L}: negative entries, an empty plane or a column stride below a sample')
+    # the last byte any plane reaches against the bytes the tensor spans from its first element (strides >= 0 for a frame tensor; a negative one is refused)
+    if any(s < 0 for s in raw.stride()):
+        raise ValueError(f'ingest_video_planes: frames with strides {tuple(raw.stride())}')
+    span = (1 + sum((n - 1) * s for n, s in zip(raw.shape, raw.stride()))) * raw.element_size() if raw.numel() else 0
+    ends = [off + (h - 1) * sr + (w - 1) * sc + b for off, h, sr, w, sc in ((L.y_off, L.H, L.stride_row, L.W, L.stride_col),
+                                                                              (L.u_off, L.Hc, L.stride_crow, L.Wc, L.stride_ccol),
+                                                                              (L.v_off, L.Hc, L.stride_crow, L.Wc, L.stride_ccol))]
+    if n_src < 1 or (n_src - 1) * L.stride_frame + max(ends) > span:
+        raise ValueError(f'ingest_video_planes: {L} reaches byte {(n_src - 1) * L.stride_frame + max(ends)} of {n_src} frames that span {span} bytes '
+                         f'({raw.dtype} {tuple(raw.shape)}, strides {tuple(raw.stride())})')
+    csc = [float(v) for v in (csc.reshape(-1).tolist() if isinstance(csc, torch.Tensor) else csc)]
+    assert len(csc) == 12, 'ingest_video_planes: csc is 9 matrix entries and 3 offsets'
+    csc_c = (C.c_float * 12)(*csc)
+    src, tabs = _dev(raw, 'raw'), _ingest_tables(frame_table, y=(y_first, y_w), x=(x_first, x_w), cy=(cy_first, cy_w), cx=(cx_first, cx_w))
+    return _ingest_chunks('sf_ingest_video_yuv_planes', frame_table, _ingest_out(out, frame_table.numel(), raw.device),
+                          lambda ft, o, n: _lib.load().sf_ingest_video_yuv_planes(src, b, L.stride_frame, L.y_off, L.stride_row, L.stride_col, L.u_off, L.v_off,
+                                                                                  L.stride_crow, L.stride_ccol, L.shift, n_src, L.H, L.W, L.Hc, L.Wc, ft, *tabs,
+                                                                                  C.addressof(csc_c), o, n, _stream()))
+
+
 SF_I16 = 4
 
 

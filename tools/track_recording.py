@@ -2,14 +2,16 @@
 beside the same windows through forward_clips on explicit 120-frame slices.  Prints one JSON line.
 
     python tools/track_recording.py [--seconds 60] [--hop 1] [--seg-chunk 224] [--host] [--clip-windows 8] [--fps 30000/1001 --size 1080x1920 --rate 48000]
-                                    [--pix-fmt {rgb24,nv12,yuv420p,p010,yuv420p10le}] [--chroma-loc {center,left,topleft}] [--posterior]
+                                    [--pix-fmt {rgb24,nv12,yuv420p,p010,yuv420p10le,uyvy422,yuyv422,yuv422p,nv16,yuv422p10le,p210,y210}]
+                                    [--chroma-loc {center,left,topleft}] [--posterior]
                                     [--stream SECONDS [--lag N]]
 
 With --fps / --size / --rate the recording is synthesised RAW at that geometry (channels-last uint8 frames, stereo int16 PCM, in device memory) and goes through
 the ingest stage: the line then also carries the ingest time alone (the same chunks the bank asks for, plus the wave) and the bank from raw
 frames next to the bank from frames ingested beforehand.  With --pix-fmt nv12 / yuv420p the raw frames are 8-bit YUV 4:2:0 in that layout: half
 the bytes per frame, which the line reports next to the times (with --host they are what is uploaded).  With --pix-fmt p010 / yuv420p10le they are 10-bit
-4:2:0 in 16-bit samples: the bytes of RGB again.  --chroma-loc sites the chroma samples of a YUV layout (tables only: no cost on the device).
+4:2:0 in 16-bit samples: the bytes of RGB again.  With a 4:2:2 layout the raw frames are (H, W, 2) for the packed uyvy422 / yuyv422
+(uint8) and y210 (uint16), (2 H, W) for yuv422p / nv16 (uint8) and yuv422p10le / p210 (uint16): 2 H W bytes per frame in 8 bits, 4 H W in 16.  --chroma-loc sites the chroma samples of a YUV layout (tables only: no cost on the device).
 
 With --posterior the windows are also read out as marginals: the line then carries the mean and minimum of conf_post, log_z per window step
 (log_z / max(W - 1, 1)), the largest |offset_sec_mean - offset_sec_path| and the time of the two extra launches (the read-out alone, on the track's logits).
@@ -45,7 +47,8 @@ def main():
     ap.add_argument('--fps', default=None, help='raw frame rate, e.g. 30, 29.97 or 30000/1001 (default: 25, no ingest)')
     ap.add_argument('--size', default=None, help='raw frame size HxW, e.g. 1080x1920')
     ap.add_argument('--rate', type=int, default=None, help='raw sample rate in Hz, e.g. 48000')
-    ap.add_argument('--pix-fmt', choices=['rgb24', 'nv12', 'yuv420p', 'p010', 'yuv420p10le'], default=None, help='layout of the raw frames (default: rgb24, channels-last)')
+    ap.add_argument('--pix-fmt', choices=['rgb24', 'nv12', 'yuv420p', 'p010', 'yuv420p10le', 'uyvy422', 'yuyv422', 'yuv422p', 'nv16', 'yuv422p10le', 'p210', 'y210'],
+                    default=None, help='layout of the raw frames (default: rgb24, channels-last); 4:2:2: uyvy422 / yuyv422 / y210 frames are (H, W, 2), the others (2 H, W)')
     ap.add_argument('--chroma-loc', choices=['center', 'left', 'topleft'], default='center', help='where the chroma samples of a YUV layout sit')
     ap.add_argument('--posterior', action='store_true', help='also read the windows out as marginals (forward-backward)')
     ap.add_argument('--stream', type=float, default=None, metavar='SECONDS', help='also push the recording through OffsetTracker.stream in pieces of this length')
@@ -54,7 +57,7 @@ def main():
     from synchformer_amd import ops, synth
     from synchformer_amd.engine import SynchformerEngine
     from synchformer_amd.frontend import MelFrontend, recording_geometry
-    from synchformer_amd.ingest import RecordingIngest
+    from synchformer_amd.ingest import PIX_FMTS_422, PIX_FMTS_422_16, PIX_FMTS_PACKED, RecordingIngest
     from synchformer_amd.track import OffsetTracker
     dev = torch.device('cuda:0')
     raw_mode = args.fps is not None or args.size is not None or args.rate is not None or args.pix_fmt is not None
@@ -64,9 +67,10 @@ def main():
         RH, RW = (int(v) for v in (args.size or '256x256').lower().split('x'))
         pix_fmt = args.pix_fmt or 'rgb24'
         ing = RecordingIngest(dev, fps, (RH, RW), args.rate or 16000, channels_last=pix_fmt == 'rgb24', pix_fmt=pix_fmt, chroma_loc=args.chroma_loc)
-        deep = pix_fmt in ('p010', 'yuv420p10le')
-        raw_shape = (RH, RW, 3) if pix_fmt == 'rgb24' else (RH * 3 // 2, RW)     # random bits are a valid frame in every layout (stray bits of a 16-bit word are dropped)
-        frame_bytes = RH * RW * 3 if pix_fmt == 'rgb24' else RH * RW * 3 // 2 * (2 if deep else 1)
+        deep = pix_fmt in ('p010', 'yuv420p10le') + PIX_FMTS_422_16
+        # random bits are a valid frame in every layout (stray bits of a 16-bit word are dropped)
+        raw_shape = (RH, RW, 3) if pix_fmt == 'rgb24' else (RH, RW, 2) if pix_fmt in PIX_FMTS_PACKED else (2 * RH, RW) if pix_fmt in PIX_FMTS_422 else (RH * 3 // 2, RW)
+        frame_bytes = RH * RW * 3 if pix_fmt == 'rgb24' else RH * RW * (2 if pix_fmt in PIX_FMTS_422 else 3) // (1 if pix_fmt in PIX_FMTS_422 else 2) * (2 if deep else 1)
         T_raw, n_raw = int(args.seconds * ing.fps_in), int(args.seconds * ing.rate_in)
         T, n = ing.n_frames(T_raw), ing.n_samples(n_raw)
     else:
