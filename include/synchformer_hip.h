@@ -29,7 +29,7 @@ extern "C" {
 enum { SF_F32 = 0, SF_BF16 = 1, SF_F16 = 2, SF_U8 = 3, SF_I16 = 4 };   /* element types (SF_I16: PCM input of sf_resample_wave only) */
 enum { SF_EPI_NONE = 0, SF_EPI_GELU = 1 };                  /* GEMM epilogue activation */
 
-#define SF_ABI_VERSION 21
+#define SF_ABI_VERSION 22
 int sf_abi_version(void);
 const char* sf_last_error(void);
 /* "gfx950" + build flags; lets the host assert it loaded the library it built */
@@ -681,6 +681,27 @@ int sf_ingest_video_yuv_planes(const void* raw, int bytes_per_sample, int64_t st
                                const int32_t* frame_table, const int32_t* y_first, const float* y_w, int taps_y, const int32_t* x_first, const float* x_w, int taps_x,
                                const int32_t* cy_first, const float* cy_w, int taps_cy, const int32_t* cx_first, const float* cx_w, int taps_cx, const float* csc,
                                uint8_t* out, int T_out, void* stream);
+
+/* Interlaced recordings (ABI v22): n_src frames of even H x W ARE 2 n_src fields of H / 2 x W.  Field f is rows p, p + 2, .. of frame f >> 1 in every
+ * plane, p = (f & 1) ^ bottom_first (bottom_first 0: top field first, 1: bottom field first).  The two entries are sf_ingest_video and sf_ingest_video_yuv_planes on
+ * that field recording, with these changes: field_table holds FIELD indices (int32, clamped into [0, 2 n_src)); there are two vertical tables, y_first0 / y_w0 for
+ * the fields of parity 0 and y_first1 / y_w1 for parity 1 (cy_*0 / cy_*1 likewise), of one tap count, mapping H / 2 field rows -> Hr with the field's rows placed where
+ * they sit in the frame: aa_bicubic_table(H / 2, Hr, shift = 0.25 - p / 2) sliced to the crop (frame row 2 k + p has its centre at frame coordinate 2 k + p + 0.5,
+ * which is field coordinate k + 0.5 + 0.25 - p / 2).  Per workgroup the kernel picks the field, moves every plane's base by p stride_row (chroma: p stride_crow) and
+ * runs the progressive resize with doubled row strides, H / 2 rows and the tables of parity p: every address is bounded by the field's geometry, and packed rows
+ * that the parity offset takes off the 4-byte grid take the per-sample loads.  No deinterlacing filter: one field is resized to the frame's target size.
+ * sf_ingest_video_yuv_planes_fields takes layouts with full vertical chroma resolution (Hc == H: the 4:2:2 formats, 4:4:4 planar); interlaced 4:2:0 is out of scope.
+ * -1 before anything is launched on: everything the progressive entry refuses, H odd or below 2, Hc != H, bottom_first outside {0, 1}, a null table of either
+ * parity, n_src above 2^30 - 1; the LDS geometry is the progressive one at the field's tap counts.  T_out == 0 launches nothing.  One launch. */
+int sf_ingest_video_fields(const uint8_t* raw, int64_t stride_frame, int64_t stride_channel, int64_t stride_row, int64_t stride_col, int n_src, int H, int W,
+                           const int32_t* field_table, const int32_t* y_first0, const float* y_w0, const int32_t* y_first1, const float* y_w1, int taps_y,
+                           const int32_t* x_first, const float* x_w, int taps_x, int bottom_first, uint8_t* out, int T_out, void* stream);
+int sf_ingest_video_yuv_planes_fields(const void* raw, int bytes_per_sample, int64_t stride_frame, int64_t y_off, int64_t stride_row, int64_t stride_col, int64_t u_off,
+                                      int64_t v_off, int64_t stride_crow, int64_t stride_ccol, int shift, int n_src, int H, int W, int Hc, int Wc,
+                                      const int32_t* field_table, const int32_t* y_first0, const float* y_w0, const int32_t* y_first1, const float* y_w1, int taps_y,
+                                      const int32_t* x_first, const float* x_w, int taps_x, const int32_t* cy_first0, const float* cy_w0, const int32_t* cy_first1,
+                                      const float* cy_w1, int taps_cy, const int32_t* cx_first, const float* cx_w, int taps_cx, const float* csc, int bottom_first,
+                                      uint8_t* out, int T_out, void* stream);
 
 /* Backward of sf_attention for tiny groups (n_tok <= 8, head_dim 64: Motionformer time attention, vit_helper.py:343-344): same
  * addressing as the forward; dq | dk | dv rows of the group's tokens are written (=), the CLS key's dk | dv of every (seq, group) goes to

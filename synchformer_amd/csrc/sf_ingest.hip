@@ -1,4 +1,4 @@
-// Ingest of a decoded recording at its native geometry (DESIGN 3.11 - 3.13, 3.17): what the reference leaves to an ffmpeg subprocess before any of its code runs
+// Ingest of a decoded recording at its native geometry (DESIGN 3.11 - 3.13, 3.17, 3.18): what the reference leaves to an ffmpeg subprocess before any of its code runs
 // (example.py:16-53: fps=25, short side 256, even dimensions, -ar 16000) plus the centre 224 crop of RGBSpatialCrop, as two launches.
 //   sf_ingest_video:   frame pick (frame_table) + antialiased bicubic resize + crop, uint8 -> uint8 planar (T_out, 3, 224, 224).  The resize is separable and the
 //                      two filter tables arrive already sliced to the crop, so only the 224 x 224 outputs are computed: a horizontal pass over the source rows a
@@ -7,6 +7,9 @@
 //   sf_ingest_video_yuv16: the same for 10-bit YUV 4:2:0 frames in 16-bit samples (P010, yuv420p10le): the sample is (raw >> shift) & 1023.
 //   sf_ingest_video_yuv_planes: the general form of the two: three planes of 1- or 2-byte samples at any offsets and strides, chroma of Hc x Wc -
 //                      4:2:2 packed (uyvy422, yuyv422, y210), semi-planar (nv16, p210) and planar (yuv422p, yuv422p10le), the 4:2:0 layouts, 4:4:4 planar.
+//   sf_ingest_video_fields, sf_ingest_video_yuv_planes_fields: sf_ingest_video and the general entry on an INTERLACED recording: the table names fields,
+//                      each workgroup resizes the rows p, p + 2, .. of its frame with the vertical table of that parity - kernels of their own beside the
+//                      progressive ones, which stay the code they were.
 //   sf_resample_wave:  zero-delay polyphase windowed-sinc resampler (the bank of ingest.resample_kernel), channels averaged on read, zero padding by bounds checks.
 // All video kernels run ONE resize pipeline, ing_plane_pass, over 1-byte or 2-byte samples (BS): ingest_video_kernel once per workgroup (one channel), the YUV
 // kernels twice (luma, then U and V together); the launchers size its LDS with one formula, ing_geometry.
@@ -338,6 +341,15 @@ __device__ __forceinline__ int ing_pick_frame(const int32_t* __restrict__ frame_
   return fs < 0 ? 0 : (fs >= n_src ? n_src - 1 : fs);
 }
 
+// Interlaced frames: n_src frames of H rows are 2 n_src fields of H / 2 rows; field f is rows p, p + 2, .. of frame f >> 1, p = (f & 1) ^ bottom_first.
+// The field of output frame fo, clamped into the recording as ing_pick_frame clamps frames (2 n_src fits an int: the launchers check n_src).
+struct IngField { int frame, parity; };
+__device__ __forceinline__ IngField ing_pick_field(const int32_t* __restrict__ field_table, int fo, int n_src, int bottom_first) {
+  int f = field_table[fo];
+  f = f < 0 ? 0 : (f >= 2 * n_src ? 2 * n_src - 1 : f);
+  return {f >> 1, (f & 1) ^ (bottom_first & 1)};
+}
+
 // Four fp32 levels -> round half to even, clamp to [0, 255], one byte each, column k in byte k.
 __device__ __forceinline__ uint32_t ing_pack4(const float (&v)[4]) {
   uint32_t w = 0;
@@ -358,6 +370,28 @@ __global__ __launch_bounds__(256) void ingest_video_kernel(const uint8_t* __rest
   const uint8_t* src = raw + (int64_t)ing_pick_frame(frame_table, fo, n_src) * sf + (int64_t)ch * sc;
   float a0[1][4] = {}, a1[1][4] = {};
   ing_plane_pass<1, 0, 1>(ing_lds, src, src, sy, sx, H, W, y_first, y_w, taps_y, x_first, x_w, taps_x, R, RP, TW, r0, 0, 0, a0, a1);
+  if (tid < 224) {
+    uint8_t* o = out + (((int64_t)fo * 3 + ch) * ING_OUT + r0 + tid / 56) * ING_OUT + 4 * (tid % 56);
+    *(uint32_t*)o = ing_pack4(a0[0]);
+    *(uint32_t*)(o + 4 * ING_OUT) = ing_pack4(a1[0]);
+  }
+}
+
+// ingest_video_kernel on the field that field_table names: the plane starts `parity` rows into the frame, its rows are two frame rows apart, it has H / 2 of them (the
+// last one is frame row H - 2 + parity <= H - 1) and the vertical tables are those of its parity (y_first0 / y_w0: the rows 0, 2, ..; y_first1 / y_w1: 1, 3, ..).
+__global__ __launch_bounds__(256) void ingest_video_fields_kernel(const uint8_t* __restrict__ raw, int64_t sf, int64_t sc, int64_t sy, int64_t sx, int n_src, int H, int W,
+                                                                   const int32_t* __restrict__ field_table, const int32_t* __restrict__ y_first0,
+                                                                   const float* __restrict__ y_w0, const int32_t* __restrict__ y_first1, const float* __restrict__ y_w1,
+                                                                   int taps_y, const int32_t* __restrict__ x_first, const float* __restrict__ x_w, int taps_x,
+                                                                   uint8_t* __restrict__ out, int R, int RP, int TW, int bottom_first) {
+  extern __shared__ __align__(16) unsigned char ing_lds[];
+  const int tid = threadIdx.x;
+  const int r0 = blockIdx.x * ING_TY, ch = blockIdx.y, fo = blockIdx.z;
+  const IngField fl = ing_pick_field(field_table, fo, n_src, bottom_first);
+  const uint8_t* src = raw + (int64_t)fl.frame * sf + (int64_t)ch * sc + (int64_t)fl.parity * sy;
+  float a0[1][4] = {}, a1[1][4] = {};
+  ing_plane_pass<1, 0, 1>(ing_lds, src, src, 2 * sy, sx, H >> 1, W, fl.parity ? y_first1 : y_first0, fl.parity ? y_w1 : y_w0, taps_y, x_first, x_w, taps_x, R, RP, TW, r0,
+                          0, 0, a0, a1);
   if (tid < 224) {
     uint8_t* o = out + (((int64_t)fo * 3 + ch) * ING_OUT + r0 + tid / 56) * ING_OUT + 4 * (tid % 56);
     *(uint32_t*)o = ing_pack4(a0[0]);
@@ -415,6 +449,57 @@ __global__ __launch_bounds__(256) void ingest_video_yuv_kernel(const uint8_t* __
   }
 }
 
+// The end of a YUV workgroup: the colour matrix on the three resized 8 x 224 tiles in registers, three full 224-byte lines per output row.
+__device__ __forceinline__ void ing_csc_store(const IngCsc& csc, const float (&ya)[1][4], const float (&yb)[1][4], const float (&c0)[2][4], const float (&c1)[2][4],
+                                              uint8_t* __restrict__ out, int fo, int r0, int tid) {
+  if (tid < 224) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      float t[3][4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float y = (h ? yb[0][k] : ya[0][k]) - csc.o[0], u = (h ? c1[0][k] : c0[0][k]) - csc.o[1], v = (h ? c1[1][k] : c0[1][k]) - csc.o[2];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) t[c][k] = fmaf(csc.m[3 * c + 2], v, fmaf(csc.m[3 * c + 1], u, csc.m[3 * c] * y));
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) *(uint32_t*)(out + (((int64_t)fo * 3 + c) * ING_OUT + r0 + tid / 56 + 4 * h) * ING_OUT + 4 * (tid % 56)) = ing_pack4(t[c]);
+    }
+  }
+}
+
+// ingest_video_yuv_kernel's general forms (GEN = 1, 2) on the field that field_table names, Hc == H (full vertical chroma resolution): every plane starts `parity`
+// rows in - luma by parity sy, chroma by parity csy - with doubled row strides and H / 2 rows; index 0 / 1 of the vertical tables is the parity.  A packed row that the
+// parity offset takes off the 4-byte grid goes through the strided loads: ing_plane_pass looks at each pointer it forms.  A kernel of its own, not a flag of
+// ingest_video_yuv_kernel: that one's instantiations stay the code they were (sharing its body as an inlined function changed their register allocation).
+template <int CF, int BS, int GEN>
+__global__ __launch_bounds__(256) void ingest_video_yuv_fields_kernel(const uint8_t* __restrict__ raw, int64_t sf, int64_t sy, int64_t u_off, int64_t v_off, int64_t csy,
+                                                                       int64_t csx, int n_src, int H, int W, const int32_t* __restrict__ field_table,
+                                                                       const int32_t* __restrict__ y_first0, const float* __restrict__ y_w0,
+                                                                       const int32_t* __restrict__ y_first1, const float* __restrict__ y_w1, int taps_y,
+                                                                       const int32_t* __restrict__ x_first, const float* __restrict__ x_w, int taps_x,
+                                                                       const int32_t* __restrict__ cy_first0, const float* __restrict__ cy_w0,
+                                                                       const int32_t* __restrict__ cy_first1, const float* __restrict__ cy_w1, int taps_cy,
+                                                                       const int32_t* __restrict__ cx_first, const float* __restrict__ cx_w, int taps_cx, IngCsc csc,
+                                                                       uint8_t* __restrict__ out, int R, int RP, int TW, int RPc, int TWc, int shift, int64_t y_off,
+                                                                       int64_t sxl, int Wc, int pky, int pkc, int bottom_first) {
+  static_assert(GEN != 0, "fields go through the general entry");
+  extern __shared__ __align__(16) unsigned char ing_lds[];
+  const int fo = blockIdx.y;
+  const IngField fl = ing_pick_field(field_table, fo, n_src, bottom_first);
+  const uint8_t* src = raw + (int64_t)fl.frame * sf;
+  const int64_t py = fl.parity ? sy : 0, pc = fl.parity ? csy : 0;
+  const uint8_t* yp = src + y_off + py;
+  const int tid = threadIdx.x, r0 = blockIdx.x * ING_TY, Hf = H >> 1;
+  float ya[1][4] = {}, yb[1][4] = {}, c0[2][4] = {}, c1[2][4] = {};
+  ing_plane_pass<1, GEN == 2 ? 2 : 0, BS>(ing_lds, yp, yp, 2 * sy, sxl, Hf, W, fl.parity ? y_first1 : y_first0, fl.parity ? y_w1 : y_w0, taps_y, x_first, x_w, taps_x, R, RP,
+                                          TW, r0, shift, pky, ya, yb);
+  __syncthreads();                                                             // every lane is past the LDS of the luma pass
+  ing_plane_pass<2, CF, BS>(ing_lds, src + u_off + pc, src + v_off + pc, 2 * csy, csx, Hf, Wc, fl.parity ? cy_first1 : cy_first0, fl.parity ? cy_w1 : cy_w0, taps_cy,
+                            cx_first, cx_w, taps_cx, 4, RPc, TWc, r0, shift, GEN == 2 ? pkc : 0, c0, c1);
+  ing_csc_store(csc, ya, yb, c0, c1, out, fo, r0, tid);
+}
+
 // The LDS geometry of ing_plane_pass over `planes` planes of width W: the staged row RP, the padded table's rows TW, the chunk R - what ING_LDS_BYTES leave after
 // the padded horizontal table and the tile's vertical weights, over the bytes of one staged row plus one row of the horizontal pass of every plane, at most
 // max_rows and at most ING_PF staging registers per lane, rounded down to a multiple of 4 - and the bytes in all.  false: not even 4 rows fit.  bs: bytes per
@@ -456,6 +541,25 @@ extern "C" int sf_ingest_video(const uint8_t* raw, int64_t stride_frame, int64_t
                taps_x);
   hipLaunchKernelGGL(ingest_video_kernel, dim3(ING_OUT / ING_TY, 3, (unsigned)T_out), dim3(256), g.lds, (hipStream_t)stream, raw, stride_frame, stride_channel,
                      stride_row, stride_col, n_src, H, W, frame_table, y_first, y_w, taps_y, x_first, x_w, taps_x, out, g.R, g.RP, g.TW);
+  SF_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int sf_ingest_video_fields(const uint8_t* raw, int64_t stride_frame, int64_t stride_channel, int64_t stride_row, int64_t stride_col, int n_src, int H, int W,
+                                      const int32_t* field_table, const int32_t* y_first0, const float* y_w0, const int32_t* y_first1, const float* y_w1, int taps_y,
+                                      const int32_t* x_first, const float* x_w, int taps_x, int bottom_first, uint8_t* out, int T_out, void* stream) {
+  if (ing_check_args("sf_ingest_video_fields", T_out, {taps_y, taps_x}, out, W)) return -1;
+  SF_CHECK_ARG(n_src >= 1 && n_src <= 0x3fffffff && H >= 1 && W >= 1, "sf_ingest_video_fields: source of %d frames %d x %d", n_src, H, W);
+  SF_CHECK_ARG(H >= 2 && H % 2 == 0, "sf_ingest_video_fields: H = %d (two fields take an even H of at least 2)", H);
+  SF_CHECK_ARG(stride_frame >= 0 && stride_channel >= 0 && stride_row >= 0 && stride_col >= 1, "sf_ingest_video_fields: negative or zero byte stride");
+  SF_CHECK_ARG(bottom_first == 0 || bottom_first == 1, "sf_ingest_video_fields: bottom_first = %d (0: top field first, 1: bottom field first)", bottom_first);
+  if (T_out == 0) return 0;
+  SF_CHECK_ARG(raw && field_table && y_first0 && y_w0 && y_first1 && y_w1 && x_first && x_w && out, "sf_ingest_video_fields: null pointer");
+  IngGeom g;                                                                    // the field's tap count sizes the LDS
+  SF_CHECK_ARG(ing_geometry(W, taps_y, taps_x, 1, ING_MAX_ROWS, 1, &g), "sf_ingest_video_fields: W = %d is too wide for four staged source rows in LDS at taps_x = %d",
+               W, taps_x);
+  hipLaunchKernelGGL(ingest_video_fields_kernel, dim3(ING_OUT / ING_TY, 3, (unsigned)T_out), dim3(256), g.lds, (hipStream_t)stream, raw, stride_frame, stride_channel,
+                     stride_row, stride_col, n_src, H, W, field_table, y_first0, y_w0, y_first1, y_w1, taps_y, x_first, x_w, taps_x, out, g.R, g.RP, g.TW, bottom_first);
   SF_LAUNCH_CHECK();
   return 0;
 }
@@ -530,12 +634,13 @@ extern "C" int sf_ingest_video_yuv16(const uint16_t* raw, int64_t stride_frame, 
   return 0;
 }
 
-extern "C" int sf_ingest_video_yuv_planes(const void* raw, int bytes_per_sample, int64_t stride_frame, int64_t y_off, int64_t stride_row, int64_t stride_col,
-                                          int64_t u_off, int64_t v_off, int64_t stride_crow, int64_t stride_ccol, int shift, int n_src, int H, int W, int Hc, int Wc,
-                                          const int32_t* frame_table, const int32_t* y_first, const float* y_w, int taps_y, const int32_t* x_first, const float* x_w,
-                                          int taps_x, const int32_t* cy_first, const float* cy_w, int taps_cy, const int32_t* cx_first, const float* cx_w, int taps_cx,
-                                          const float* csc, uint8_t* out, int T_out, void* stream) {
-  const char* who = "sf_ingest_video_yuv_planes";
+// The two general entries.  fields: frame_table holds field indices, y_first / y_w / cy_first / cy_w are the tables of parity 0, y_first1 / y_w1 / cy_first1 / cy_w1
+// those of parity 1, bottom_first the field order; otherwise those five are unused.
+static int ing_planes(const char* who, bool fields, const void* raw, int bytes_per_sample, int64_t stride_frame, int64_t y_off, int64_t stride_row, int64_t stride_col,
+                      int64_t u_off, int64_t v_off, int64_t stride_crow, int64_t stride_ccol, int shift, int n_src, int H, int W, int Hc, int Wc,
+                      const int32_t* frame_table, const int32_t* y_first, const float* y_w, const int32_t* y_first1, const float* y_w1, int taps_y,
+                      const int32_t* x_first, const float* x_w, int taps_x, const int32_t* cy_first, const float* cy_w, const int32_t* cy_first1, const float* cy_w1,
+                      int taps_cy, const int32_t* cx_first, const float* cx_w, int taps_cx, const float* csc, int bottom_first, uint8_t* out, int T_out, void* stream) {
   if (ing_check_args(who, T_out, {taps_y, taps_x, taps_cy, taps_cx}, out, W)) return -1;
   const int bs = bytes_per_sample;
   SF_CHECK_ARG(bs == 1 || bs == 2, "%s: bytes_per_sample = %d (1 or 2)", who, bs);
@@ -546,10 +651,17 @@ extern "C" int sf_ingest_video_yuv_planes(const void* raw, int bytes_per_sample,
   SF_CHECK_ARG(bs == 1 || ((stride_frame | y_off | stride_row | stride_col | u_off | v_off | stride_crow | stride_ccol) & 1) == 0,
                "%s: odd byte stride or offset (16-bit samples are 2-byte aligned)", who);
   SF_CHECK_ARG(shift >= 0 && shift <= 6, "%s: shift = %d (0 .. 6: ten bits of a 16-bit word)", who, shift);
+  if (fields) {
+    SF_CHECK_ARG(H >= 2 && H % 2 == 0, "%s: H = %d (two fields take an even H of at least 2)", who, H);
+    SF_CHECK_ARG(Hc == H, "%s: chroma planes of %d rows beside %d luma rows (fields take full vertical chroma resolution: 4:2:2, 4:4:4)", who, Hc, H);
+    SF_CHECK_ARG(n_src <= 0x3fffffff, "%s: source of %d frames", who, n_src);
+    SF_CHECK_ARG(bottom_first == 0 || bottom_first == 1, "%s: bottom_first = %d (0: top field first, 1: bottom field first)", who, bottom_first);
+  }
   if (T_out == 0) return 0;
   SF_CHECK_ARG(raw && frame_table && y_first && y_w && x_first && x_w && cy_first && cy_w && cx_first && cx_w && csc && out, "%s: null pointer", who);
+  SF_CHECK_ARG(!fields || (y_first1 && y_w1 && cy_first1 && cy_w1), "%s: null pointer", who);
   SF_CHECK_ARG(bs == 1 || ((uintptr_t)raw & 1) == 0, "%s: raw must be 2-byte aligned", who);
-  IngGeom gy, gc;
+  IngGeom gy, gc;                                                               // fields: the field's tap counts size the LDS
   SF_CHECK_ARG(ing_geometry(W, taps_y, taps_x, 1, ING_MAX_ROWS, bs, &gy), "%s: W = %d is too wide for four staged source rows in LDS at taps_x = %d", who, W, taps_x);
   SF_CHECK_ARG(ing_geometry(Wc, taps_cy, taps_cx, 2, 4, bs, &gc), "%s: Wc = %d is too wide for four staged rows of both chroma planes in LDS at taps_cx = %d", who, Wc,
                taps_cx);
@@ -575,7 +687,24 @@ extern "C" int sf_ingest_video_yuv_planes(const void* raw, int bytes_per_sample,
                        cy_w, taps_cy, cx_first, cx_w, taps_cx, k, out, gy.R, gy.RP, gy.TW, gc.RP, gc.TW, shift, y_off, stride_col, Hc, Wc, (int)(y_off - m),
                        (int)(u_off - m));
   };
-  if (bs == 1) {
+  auto launch_fields = [&](auto kernel) {
+    if (bs == 2 && (rc = sf_prepare_kernel((const void*)kernel, ING_LDS_BYTES16, who)) != 0) return;
+    hipLaunchKernelGGL(kernel, dim3(ING_OUT / ING_TY, (unsigned)T_out), dim3(256), gy.lds > gc.lds ? gy.lds : gc.lds, (hipStream_t)stream, (const uint8_t*)raw,
+                       stride_frame, stride_row, u_off, v_off, stride_crow, stride_ccol, n_src, H, W, frame_table, y_first, y_w, y_first1, y_w1, taps_y, x_first, x_w,
+                       taps_x, cy_first, cy_w, cy_first1, cy_w1, taps_cy, cx_first, cx_w, taps_cx, k, out, gy.R, gy.RP, gy.TW, gc.RP, gc.TW, shift, y_off, stride_col, Wc,
+                       (int)(y_off - m), (int)(u_off - m), bottom_first);
+  };
+  if (fields) {
+    if (bs == 1) {
+      if (packed) launch_fields(ingest_video_yuv_fields_kernel<2, 1, 2>);
+      else if (inter) launch_fields(ingest_video_yuv_fields_kernel<1, 1, 1>);
+      else launch_fields(ingest_video_yuv_fields_kernel<0, 1, 1>);
+    } else {
+      if (packed) launch_fields(ingest_video_yuv_fields_kernel<2, 2, 2>);
+      else if (inter) launch_fields(ingest_video_yuv_fields_kernel<1, 2, 1>);
+      else launch_fields(ingest_video_yuv_fields_kernel<0, 2, 1>);
+    }
+  } else if (bs == 1) {
     if (packed) launch(ingest_video_yuv_kernel<2, 1, 2>);
     else if (inter) launch(ingest_video_yuv_kernel<1, 1, 1>);
     else launch(ingest_video_yuv_kernel<0, 1, 1>);
@@ -587,6 +716,27 @@ extern "C" int sf_ingest_video_yuv_planes(const void* raw, int bytes_per_sample,
   if (rc) return rc;
   SF_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int sf_ingest_video_yuv_planes(const void* raw, int bytes_per_sample, int64_t stride_frame, int64_t y_off, int64_t stride_row, int64_t stride_col,
+                                          int64_t u_off, int64_t v_off, int64_t stride_crow, int64_t stride_ccol, int shift, int n_src, int H, int W, int Hc, int Wc,
+                                          const int32_t* frame_table, const int32_t* y_first, const float* y_w, int taps_y, const int32_t* x_first, const float* x_w,
+                                          int taps_x, const int32_t* cy_first, const float* cy_w, int taps_cy, const int32_t* cx_first, const float* cx_w, int taps_cx,
+                                          const float* csc, uint8_t* out, int T_out, void* stream) {
+  return ing_planes("sf_ingest_video_yuv_planes", false, raw, bytes_per_sample, stride_frame, y_off, stride_row, stride_col, u_off, v_off, stride_crow, stride_ccol, shift,
+                    n_src, H, W, Hc, Wc, frame_table, y_first, y_w, nullptr, nullptr, taps_y, x_first, x_w, taps_x, cy_first, cy_w, nullptr, nullptr, taps_cy, cx_first, cx_w,
+                    taps_cx, csc, 0, out, T_out, stream);
+}
+
+extern "C" int sf_ingest_video_yuv_planes_fields(const void* raw, int bytes_per_sample, int64_t stride_frame, int64_t y_off, int64_t stride_row, int64_t stride_col,
+                                                 int64_t u_off, int64_t v_off, int64_t stride_crow, int64_t stride_ccol, int shift, int n_src, int H, int W, int Hc,
+                                                 int Wc, const int32_t* field_table, const int32_t* y_first0, const float* y_w0, const int32_t* y_first1,
+                                                 const float* y_w1, int taps_y, const int32_t* x_first, const float* x_w, int taps_x, const int32_t* cy_first0,
+                                                 const float* cy_w0, const int32_t* cy_first1, const float* cy_w1, int taps_cy, const int32_t* cx_first,
+                                                 const float* cx_w, int taps_cx, const float* csc, int bottom_first, uint8_t* out, int T_out, void* stream) {
+  return ing_planes("sf_ingest_video_yuv_planes_fields", true, raw, bytes_per_sample, stride_frame, y_off, stride_row, stride_col, u_off, v_off, stride_crow, stride_ccol,
+                    shift, n_src, H, W, Hc, Wc, field_table, y_first0, y_w0, y_first1, y_w1, taps_y, x_first, x_w, taps_x, cy_first0, cy_w0, cy_first1, cy_w1, taps_cy,
+                    cx_first, cx_w, taps_cx, csc, bottom_first, out, T_out, stream);
 }
 
 // ---- audio ---------------------------------------------------------------------------------------------------------------------------------------------------

@@ -34,7 +34,14 @@ hardware surfaces are 'nv16' / 'p210' / 'y210' - and goes through the general en
     ing = RecordingIngest(dev, 50, (1080, 1920), 48000, pix_fmt='uyvy422', colorspace='bt709', chroma_loc='left')
     feed = tracker.stream(ingest=ing)                           # raw frames (T, 1080, 1920, 2) uint8; y210: uint16; the others (T, 2 H, W)
 
-Out of scope: decoding, 12-bit / 4:4:4 input through RecordingIngest (ops.ingest_video_planes takes a 4:4:4 planar layout), v210, interlaced fields, BT.2020 in csc_matrix, transfer functions (PQ, HLG: a 10-bit HDR stream is converted by the matrix alone,
+Interlaced recordings (1080i50 / 1080i59.94 / 576i / 480i contribution feeds) are recordings of fields: field_order='tff' or 'bff' picks the one
+field nearest each 25 fps slot and resizes it on its own to the frame's target size, its rows placed where they sit in the frame - no weave of two instants, no
+deinterlacing filter (ops.ingest_video_fields, ops.ingest_video_planes_fields); fps_in stays the FRAME rate as ffprobe reports it; rgb24 and the 4:2:2 formats:
+
+    ing = RecordingIngest(dev, (30000, 1001), (1080, 1920), 48000, pix_fmt='uyvy422', field_order='tff')
+
+Out of scope: decoding, 12-bit / 4:4:4 input through RecordingIngest (ops.ingest_video_planes takes a 4:4:4 planar layout), v210, deinterlacing filters, interlaced
+4:2:0, a field order that changes mid-stream, telecine, BT.2020 in csc_matrix, transfer functions (PQ, HLG: a 10-bit HDR stream is converted by the matrix alone,
 no tone mapping), double-buffered uploads, several recordings per call.
 """
 import math
@@ -50,6 +57,7 @@ PIX_FMTS_16 = ('p010', 'yuv420p10le')   # 10-bit samples in uint16: ops.ingest_v
 PIX_FMTS_422 = ('uyvy422', 'yuyv422', 'yuv422p', 'nv16', 'yuv422p10le', 'p210', 'y210')     # 4:2:2: ops.ingest_video_planes
 PIX_FMTS_422_16 = ('yuv422p10le', 'p210', 'y210')                                           # of those, 10-bit samples in uint16
 PIX_FMTS_PACKED = ('uyvy422', 'yuyv422', 'y210')                                            # raw frames (T, H, W, 2): a macropixel Y0 U Y1 V (in some order) per two columns
+FIELD_ORDERS = ('progressive', 'tff', 'bff')                                                   # frames; interlaced, top / bottom field first
 CHROMA_LOCS = {'center': (0.0, 0.0), 'left': (0.0, 0.25), 'topleft': (0.25, 0.25)}       # (shift of the cy tables, of the cx tables)
 _KR_KB = {'bt601': (0.299, 0.114), 'bt709': (0.2126, 0.0722)}
 
@@ -147,6 +155,13 @@ def fps_frame_table(n_in: int, fps_in, fps_out=25) -> torch.Tensor:
             i += 1
         src[j] = i
     return torch.tensor(src, dtype=torch.int32)
+
+
+def fps_field_table(n_frames: int, fps_in, fps_out=25) -> torch.Tensor:
+    """Which FIELD each output frame shows when n_frames interlaced frames at frame rate fps_in are converted to fps_out: an interlaced recording is a progressive
+    one of 2 n_frames fields at 2 fps_in, so this is fps_frame_table(2 n_frames, 2 fps_in, fps_out) - the same "near" rule.  Field f is temporal: the first field
+    of frame f >> 1 when f is even, whichever rows the field order gives it.  At 25i: 0, 2, 4, .. and the end-of-stream slot; at 30000/1001 the parities alternate."""
+    return fps_frame_table(2 * int(n_frames), 2 * _fraction(fps_in), fps_out)
 
 
 def resized_dims(H: int, W: int, side: int = 256) -> Tuple[int, int]:
@@ -255,10 +270,19 @@ class RecordingIngest:
     contiguous; even W only, an odd H is legal; the chroma rows take the luma tables, so 'topleft' is 'left' - converted with csc_matrix(colorspace, full_range, bit_depth) after the resize, or with csc = (M (3, 3), offsets (3,)) on the format's
     own sample scale when given (it overrides colorspace / full_range; e.g. BT.2020 coefficients).  chroma_loc: 'center', 'left' or 'topleft' (CHROMA_LOCS; YUV
     formats only).  ValueError on resize_side < crop, crop != 224, a source so large that a filter row passes 35 taps (short side above ~2160 at resize_side 256),
-    an unknown pix_fmt, colorspace or chroma_loc, chroma_loc or csc with rgb24, and for a YUV format odd H or W or channels_last=True."""
+    an unknown pix_fmt, colorspace or chroma_loc, chroma_loc or csc with rgb24, and for a YUV format odd H or W or channels_last=True.
+    field_order: 'progressive' (the default: frames), or 'tff' / 'bff' (DESIGN 3.18): the raw frames are interlaced, top / bottom field first, fps_in is still the
+    frame rate.  The recording is then its 2 n fields at 2 fps_in: frame_table / n_frames come from fps_field_table, every output frame is ONE field resized to the
+    frame's (Hr, Wr) with the vertical table of its parity p, aa_bicubic_table(H / 2, Hr, shift = 0.25 - p / 2) (y_tables; 4:2:2 chroma rows take the same two), and
+    the 35-tap limit applies to the field's taps.  ValueError on an unknown field_order, an odd H with an interlaced order, or an interlaced order with a 4:2:0 format
+    (field-sited chroma is another geometry)."""
+
+    field_order, interlaced = 'progressive', False
 
     def __init__(self, device, fps_in, size_in, rate_in: int, channels_last: bool = False, resize_side: int = 256, crop: int = CROP, pix_fmt: str = 'rgb24',
-                 colorspace: str = 'bt601', full_range: bool = False, chroma_loc: str = 'center', csc=None):
+                 colorspace: str = 'bt601', full_range: bool = False, chroma_loc: str = 'center', csc=None, field_order: str = 'progressive'):
+        if field_order not in FIELD_ORDERS:
+            raise ValueError(f'field_order = {field_order!r}: one of {FIELD_ORDERS}')
         if pix_fmt not in PIX_FMTS + PIX_FMTS_422:
             raise ValueError(f'pix_fmt = {pix_fmt!r}: one of {PIX_FMTS + PIX_FMTS_422}')
         if chroma_loc not in CHROMA_LOCS:
@@ -274,11 +298,24 @@ class RecordingIngest:
         self.dev = torch.device(device)
         self.fps_in, self.rate_in, self.channels_last = _fraction(fps_in), int(rate_in), bool(channels_last)
         self.H, self.W = int(size_in[0]), int(size_in[1])
+        if field_order != 'progressive':                                          # (a progressive object keeps the attributes it had: the class holds the defaults)
+            self.field_order, self.interlaced = field_order, True
+        if self.interlaced and pix_fmt != 'rgb24' and pix_fmt not in PIX_FMTS_422:
+            raise ValueError(f'field_order = {field_order!r} with pix_fmt = {pix_fmt!r}: interlaced 4:2:0 (field-sited chroma) is out of scope; rgb24 or one of '
+                             f'{PIX_FMTS_422}')
+        if self.interlaced and (self.H % 2 or self.H < 2):
+            raise ValueError(f'field_order = {field_order!r} with H = {self.H}: two fields take an even H')
         self.Hr, self.Wr = resized_dims(self.H, self.W, resize_side)
         if self.Hr < crop or self.Wr < crop:
             raise ValueError(f'{self.H} x {self.W} resizes to {self.Hr} x {self.Wr}, below the {crop} crop')
         self.y0, self.x0 = int(round((self.Hr - crop) / 2.)), int(round((self.Wr - crop) / 2.))
-        self.y_first, self.y_w, self.taps_y = _crop_table(self.H, self.Hr, self.y0, crop, self.dev)
+        if self.interlaced:
+            # a field's H / 2 rows to the FRAME's Hr: row k of the field of parity p is frame row 2 k + p, centre 2 k + p + 0.5 = 2 (k + 0.5 + 0.25 - p / 2)
+            tabs = [_crop_table(self.H // 2, self.Hr, self.y0, crop, self.dev, 0.25 - p / 2) for p in (0, 1)]
+            self.y_tables, self.taps_y = tuple(t[:2] for t in tabs), tabs[0][2]       # one tap count: the scale is the same
+            self.y_first, self.y_w = self.y_tables[0]
+        else:
+            self.y_first, self.y_w, self.taps_y = _crop_table(self.H, self.Hr, self.y0, crop, self.dev)
         self.x_first, self.x_w, self.taps_x = _crop_table(self.W, self.Wr, self.x0, crop, self.dev)
         if max(self.taps_y, self.taps_x) > MAX_TAPS:
             raise ValueError(f'{self.H} x {self.W} -> {self.Hr} x {self.Wr} needs {self.taps_y} x {self.taps_x} filter taps, the kernel takes {MAX_TAPS} '
@@ -314,9 +351,9 @@ class RecordingIngest:
         self._tables = {}
 
     def frame_table(self, n_in: int) -> torch.Tensor:
-        """fps_frame_table(n_in, fps_in) (host, cached per n_in)."""
+        """fps_frame_table(n_in, fps_in) (host, cached per n_in); interlaced: fps_field_table(n_in, fps_in), FIELD indices."""
         if n_in not in self._tables:
-            self._tables = {n_in: fps_frame_table(n_in, self.fps_in)}
+            self._tables = {n_in: (fps_field_table if self.interlaced else fps_frame_table)(n_in, self.fps_in)}
         return self._tables[n_in]
 
     def n_frames(self, n_in: int) -> int:
@@ -336,7 +373,7 @@ class RecordingIngest:
 
     def frames(self, raw: torch.Tensor, j0: int, j1: int) -> torch.Tensor:
         """25 fps frames [j0, j1) of the recording, resized and cropped: uint8 (j1 - j0, 3, 224, 224) on the device.  raw: all the raw frames, device or host; from
-        a host tensor only the source frames frame_table[j0:j1] spans are uploaded."""
+        a host tensor only the source frames frame_table[j0:j1] spans are uploaded (interlaced: the frames that hold the fields it spans)."""
         self._check_frames(raw)
         table = self.frame_table(raw.shape[0])
         if not 0 <= j0 <= j1 <= table.numel():
@@ -344,12 +381,19 @@ class RecordingIngest:
         if j1 == j0:
             return torch.empty(0, 3, CROP, CROP, device=self.dev, dtype=torch.uint8)
         t = table[j0:j1]
-        lo, hi = int(t[0]), int(t[-1]) + 1                                       # the table is non-decreasing
-        return self._resize(raw[lo:hi].to(self.dev, non_blocking=True), t - lo)
+        u = 2 if self.interlaced else 1                                          # table entries per source frame
+        lo, hi = int(t[0]) // u, int(t[-1]) // u + 1                             # the table is non-decreasing
+        return self._resize(raw[lo:hi].to(self.dev, non_blocking=True), t - u * lo)
 
     def _resize(self, src: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
-        """Output frame j = source frame src[t[j]] (src on the device, t int32 on the host), resized and cropped."""
+        """Output frame j = source frame src[t[j]] (src on the device, t int32 on the host), resized and cropped; interlaced: field t[j] of src's 2 len(src) fields."""
         from . import ops
+        if self.interlaced:
+            bff = self.field_order == 'bff'
+            if self.pix_fmt == 'rgb24':
+                return ops.ingest_video_fields(src, self.channels_last, t.to(self.dev, non_blocking=True), self.y_tables, self.x_first, self.x_w, bff)
+            return ops.ingest_video_planes_fields(src, plane_layout(self.pix_fmt, self.H, self.W, src.stride()), t.to(self.dev, non_blocking=True), self.y_tables,
+                                                  self.x_first, self.x_w, self.y_tables, self.cx_first, self.cx_w, self.csc, bff)
         if self.pix_fmt in PIX_FMTS_422:
             return ops.ingest_video_planes(src, plane_layout(self.pix_fmt, self.H, self.W, src.stride()), t.to(self.dev, non_blocking=True), self.y_first, self.y_w,
                                            self.x_first, self.x_w, self.cy_first, self.cy_w, self.cx_first, self.cx_w, self.csc)
@@ -408,7 +452,7 @@ def resample_stream_plan(emitted: int, seen: int, o: int, width: int, n: int, fi
 class IngestStream:
     """RecordingIngest for a feed: push(raw_frames, raw_wave) and flush() return the 25 fps frames (uint8 (t, 3, 224, 224)) and the 16 kHz samples (fp32 (m,)) that
     have become FINAL, on the device; concatenated over all calls they are bit-equal to ingest.frames(raw_all, 0, n_frames) and ingest.wave(raw_all), for every
-    chunking.  Host logic over the same kernels: the last source frame is held until a later one shows which slots it fills (flush emits its slot), the raw
+    chunking.  An interlaced ingest counts fields (two per frame seen) and still holds one source FRAME.  Host logic over the same kernels: the last source frame is held until a later one shows which slots it fills (flush emits its slot), the raw
     samples are held from the resampler's left context on (resample_stream_plan).  Either argument may be empty (or None)."""
 
     def __init__(self, ingest: RecordingIngest):
@@ -447,13 +491,14 @@ class IngestStream:
             new = new.view(torch.int16) if new.dtype == torch.uint16 else new     # (the same bits; the kernels read either)
             src, base = (new, self.n_src) if src is None else (torch.cat([src, new]), base)
             self.n_src += int(raw.shape[0])
-        j1 = fps_final_slots(self.n_src, ing.fps_in) + (1 if final and self.n_src else 0)
+        u = 2 if ing.interlaced else 1                                            # an interlaced frame is two fields at twice the rate: the slots are the fields'
+        j1 = fps_final_slots(u * self.n_src, u * ing.fps_in) + (1 if final and self.n_src else 0)
         j0, self.slots_out = self.slots_out, max(j1, self.slots_out)
         if src is not None:
             self._last = src[-1:].clone() if not final else None
         if j1 <= j0:
             return torch.empty(0, 3, CROP, CROP, device=ing.dev, dtype=torch.uint8)
-        t = torch.tensor([min(fps_slot_source(j, ing.fps_in), self.n_src - 1) - base for j in range(j0, j1)], dtype=torch.int32)
+        t = torch.tensor([min(fps_slot_source(j, u * ing.fps_in), u * self.n_src - 1) - u * base for j in range(j0, j1)], dtype=torch.int32)
         return ing._resize(src, t)
 
     def _wave(self, raw: Optional[torch.Tensor], final: bool) -> torch.Tensor:

@@ -1016,6 +1016,81 @@ def ingest_video_planes(raw: torch.Tensor, layout, frame_table: torch.Tensor, y_
                                                                                   C.addressof(csc_c), o, n, _stream()))
 
 
+def _field_pairs(what: str, **pairs):
+    """name=((first0, w0), (first1, w1)): the vertical tables of the fields of parity 0 and parity 1 share one tap count (ValueError otherwise)."""
+    for k, (t0, t1) in pairs.items():
+        if t0[1].shape != t1[1].shape:
+            raise ValueError(f'{what}: the {k} tables of the two parities have {t0[1].shape[-1]} and {t1[1].shape[-1]} taps; one tap count serves both')
+
+
+def _field_tables(field_table: torch.Tensor, **pairs):
+    """The launcher arguments of the field entries' vertical tables, name=((first0, w0), (first1, w1)) -> (first0, w0, first1, w1, taps) per name, after
+    _ingest_tables' checks on all of them."""
+    args = []
+    for k, (t0, t1) in pairs.items():
+        a = _ingest_tables(field_table, **{f'{k}0': t0, f'{k}1': t1})
+        args += [a[0], a[1], a[3], a[4], a[2]]
+    return args
+
+
+def ingest_video_fields(raw: torch.Tensor, channels_last: bool, field_table: torch.Tensor, y_tables, x_first: torch.Tensor, x_w: torch.Tensor, bottom_first: bool,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ingest_video on an interlaced recording (sf_ingest_video_fields): raw as for ingest_video, H even; field_table int32 (T_out,) of FIELD indices
+    inside [0, 2 n_src) - field f is rows p, p + 2, .. of frame f >> 1, p = (f & 1) ^ bottom_first; y_tables = ((first0, w0), (first1, w1)): the vertical tables of
+    the fields of parity 0 and 1 (H / 2 rows -> Hr, shift 0.25 - p / 2, sliced to the crop), one tap count; x_first / x_w as for ingest_video -> uint8
+    (T_out, 3, 224, 224): every output frame is one field, resized on its own."""
+    if raw.dim() != 4 or raw.dtype != torch.uint8 or raw.shape[3 if channels_last else 1] != 3:
+        raise ValueError(f'ingest_video_fields: expected uint8 frames (n, 3, H, W) or channels_last (n, H, W, 3), got {raw.dtype} {tuple(raw.shape)}')
+    n_src = raw.shape[0]
+    (H, W), (sf, sc, sy, sx) = ((raw.shape[1], raw.shape[2]), (raw.stride(i) for i in (0, 3, 1, 2))) if channels_last else \
+        ((raw.shape[2], raw.shape[3]), raw.stride())
+    if H < 2 or H % 2:
+        raise ValueError(f'ingest_video_fields: H = {H}: two fields take an even H')
+    assert min(sf, sc, sy) >= 0 and sx >= 1, 'ingest_video_fields: negative strides'
+    _field_pairs('ingest_video_fields', y=y_tables)
+    src = _dev(raw, 'raw')
+    ytabs, xtabs = _field_tables(field_table, y=y_tables), _ingest_tables(field_table, x=(x_first, x_w))
+    return _ingest_chunks('sf_ingest_video_fields', field_table, _ingest_out(out, field_table.numel(), raw.device),
+                          lambda ft, o, n: _lib.load().sf_ingest_video_fields(src, sf, sc, sy, sx, n_src, H, W, ft, *ytabs, *xtabs, int(bool(bottom_first)), o, n, _stream()))
+
+
+def ingest_video_planes_fields(raw: torch.Tensor, layout, field_table: torch.Tensor, y_tables, x_first: torch.Tensor, x_w: torch.Tensor, cy_tables,
+                               cx_first: torch.Tensor, cx_w: torch.Tensor, csc, bottom_first: bool, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ingest_video_planes on an interlaced recording (sf_ingest_video_yuv_planes_fields): raw and layout as there, with layout.Hc == layout.H even (4:2:2,
+    4:4:4: full vertical chroma resolution); field_table, y_tables and bottom_first as for ingest_video_fields; cy_tables: the chroma planes' pair of vertical tables
+    (for 4:2:2 the luma pair); the horizontal tables and csc as for ingest_video_planes -> uint8 (T_out, 3, 224, 224)."""
+    L = layout
+    if raw.dim() < 2 or raw.dtype not in ((torch.uint8,) if L.bytes_per_sample == 1 else (torch.uint16, torch.int16)):
+        raise ValueError(f'ingest_video_planes_fields: expected {"uint8" if L.bytes_per_sample == 1 else "uint16"} frames (n, ...) for samples of {L.bytes_per_sample} '
+                         f'byte(s), got {raw.dtype} {tuple(raw.shape)}')
+    n_src, b = raw.shape[0], L.bytes_per_sample
+    if min(L) < 0 or min(L.H, L.W, L.Hc, L.Wc) < 1 or min(L.stride_col, L.stride_ccol) < b:
+        raise ValueError(f'ingest_video_planes_fields: {L}: negative entries, an empty plane or a column stride below a sample')
+    if L.H % 2 or L.Hc != L.H:
+        raise ValueError(f'ingest_video_planes_fields: {L}: two fields take an even H and chroma planes of H rows (4:2:2, 4:4:4)')
+    if any(s < 0 for s in raw.stride()):
+        raise ValueError(f'ingest_video_planes_fields: frames with strides {tuple(raw.stride())}')
+    span = (1 + sum((n - 1) * s for n, s in zip(raw.shape, raw.stride()))) * raw.element_size() if raw.numel() else 0
+    ends = [off + (h - 1) * sr + (w - 1) * sc + b for off, h, sr, w, sc in ((L.y_off, L.H, L.stride_row, L.W, L.stride_col),
+                                                                              (L.u_off, L.Hc, L.stride_crow, L.Wc, L.stride_ccol),
+                                                                              (L.v_off, L.Hc, L.stride_crow, L.Wc, L.stride_ccol))]
+    if n_src < 1 or (n_src - 1) * L.stride_frame + max(ends) > span:
+        raise ValueError(f'ingest_video_planes_fields: {L} reaches byte {(n_src - 1) * L.stride_frame + max(ends)} of {n_src} frames that span {span} bytes '
+                         f'({raw.dtype} {tuple(raw.shape)}, strides {tuple(raw.stride())})')
+    csc = [float(v) for v in (csc.reshape(-1).tolist() if isinstance(csc, torch.Tensor) else csc)]
+    assert len(csc) == 12, 'ingest_video_planes_fields: csc is 9 matrix entries and 3 offsets'
+    csc_c = (C.c_float * 12)(*csc)
+    _field_pairs('ingest_video_planes_fields', y=y_tables, cy=cy_tables)
+    src = _dev(raw, 'raw')
+    ytabs, cytabs = _field_tables(field_table, y=y_tables), _field_tables(field_table, cy=cy_tables)
+    xtabs, cxtabs = _ingest_tables(field_table, x=(x_first, x_w)), _ingest_tables(field_table, cx=(cx_first, cx_w))
+    return _ingest_chunks('sf_ingest_video_yuv_planes_fields', field_table, _ingest_out(out, field_table.numel(), raw.device),
+                          lambda ft, o, n: _lib.load().sf_ingest_video_yuv_planes_fields(src, b, L.stride_frame, L.y_off, L.stride_row, L.stride_col, L.u_off, L.v_off,
+                                                                                         L.stride_crow, L.stride_ccol, L.shift, n_src, L.H, L.W, L.Hc, L.Wc, ft, *ytabs,
+                                                                                         *xtabs, *cytabs, *cxtabs, C.addressof(csc_c), int(bool(bottom_first)), o, n,
+                                                                                         _stream()))
+
+
 SF_I16 = 4
 
 

@@ -3,7 +3,7 @@ beside the same windows through forward_clips on explicit 120-frame slices.  Pri
 
     python tools/track_recording.py [--seconds 60] [--hop 1] [--seg-chunk 224] [--host] [--clip-windows 8] [--fps 30000/1001 --size 1080x1920 --rate 48000]
                                     [--pix-fmt {rgb24,nv12,yuv420p,p010,yuv420p10le,uyvy422,yuyv422,yuv422p,nv16,yuv422p10le,p210,y210}]
-                                    [--chroma-loc {center,left,topleft}] [--posterior]
+                                    [--chroma-loc {center,left,topleft}] [--field-order {progressive,tff,bff}] [--posterior]
                                     [--stream SECONDS [--lag N]]
 
 With --fps / --size / --rate the recording is synthesised RAW at that geometry (channels-last uint8 frames, stereo int16 PCM, in device memory) and goes through
@@ -12,6 +12,8 @@ frames next to the bank from frames ingested beforehand.  With --pix-fmt nv12 / 
 the bytes per frame, which the line reports next to the times (with --host they are what is uploaded).  With --pix-fmt p010 / yuv420p10le they are 10-bit
 4:2:0 in 16-bit samples: the bytes of RGB again.  With a 4:2:2 layout the raw frames are (H, W, 2) for the packed uyvy422 / yuyv422
 (uint8) and y210 (uint16), (2 H, W) for yuv422p / nv16 (uint8) and yuv422p10le / p210 (uint16): 2 H W bytes per frame in 8 bits, 4 H W in 16.  --chroma-loc sites the chroma samples of a YUV layout (tables only: no cost on the device).
+With --field-order tff / bff the raw frames are interlaced (rgb24 and the 4:2:2 layouts): --fps stays the frame rate, every 25 fps frame is the one field
+nearest its slot resized on its own, and the line reports the field order, the fields shown and the field's vertical taps (half the source rows are read).
 
 With --posterior the windows are also read out as marginals: the line then carries the mean and minimum of conf_post, log_z per window step
 (log_z / max(W - 1, 1)), the largest |offset_sec_mean - offset_sec_path| and the time of the two extra launches (the read-out alone, on the track's logits).
@@ -50,6 +52,8 @@ def main():
     ap.add_argument('--pix-fmt', choices=['rgb24', 'nv12', 'yuv420p', 'p010', 'yuv420p10le', 'uyvy422', 'yuyv422', 'yuv422p', 'nv16', 'yuv422p10le', 'p210', 'y210'],
                     default=None, help='layout of the raw frames (default: rgb24, channels-last); 4:2:2: uyvy422 / yuyv422 / y210 frames are (H, W, 2), the others (2 H, W)')
     ap.add_argument('--chroma-loc', choices=['center', 'left', 'topleft'], default='center', help='where the chroma samples of a YUV layout sit')
+    ap.add_argument('--field-order', choices=['progressive', 'tff', 'bff'], default='progressive',
+                    help='interlaced raw frames, top / bottom field first: the field nearest each 25 fps slot is ingested on its own (rgb24 and 4:2:2 layouts)')
     ap.add_argument('--posterior', action='store_true', help='also read the windows out as marginals (forward-backward)')
     ap.add_argument('--stream', type=float, default=None, metavar='SECONDS', help='also push the recording through OffsetTracker.stream in pieces of this length')
     ap.add_argument('--lag', type=int, default=16, help='decision lag of the stream, in windows')
@@ -60,13 +64,14 @@ def main():
     from synchformer_amd.ingest import PIX_FMTS_422, PIX_FMTS_422_16, PIX_FMTS_PACKED, RecordingIngest
     from synchformer_amd.track import OffsetTracker
     dev = torch.device('cuda:0')
-    raw_mode = args.fps is not None or args.size is not None or args.rate is not None or args.pix_fmt is not None
+    raw_mode = args.fps is not None or args.size is not None or args.rate is not None or args.pix_fmt is not None or args.field_order != 'progressive'
     ing = None
     if raw_mode:
         fps = tuple(int(v) for v in args.fps.split('/')) if args.fps and '/' in args.fps else float(args.fps or 25)
         RH, RW = (int(v) for v in (args.size or '256x256').lower().split('x'))
         pix_fmt = args.pix_fmt or 'rgb24'
-        ing = RecordingIngest(dev, fps, (RH, RW), args.rate or 16000, channels_last=pix_fmt == 'rgb24', pix_fmt=pix_fmt, chroma_loc=args.chroma_loc)
+        ing = RecordingIngest(dev, fps, (RH, RW), args.rate or 16000, channels_last=pix_fmt == 'rgb24', pix_fmt=pix_fmt, chroma_loc=args.chroma_loc,
+                              field_order=args.field_order)
         deep = pix_fmt in ('p010', 'yuv420p10le') + PIX_FMTS_422_16
         # random bits are a valid frame in every layout (stray bits of a 16-bit word are dropped)
         raw_shape = (RH, RW, 3) if pix_fmt == 'rgb24' else (RH, RW, 2) if pix_fmt in PIX_FMTS_PACKED else (2 * RH, RW) if pix_fmt in PIX_FMTS_422 else (RH * 3 // 2, RW)
@@ -124,8 +129,9 @@ def main():
         t_wave, _ = timed(lambda: ing.wave(raw_wave), reps=3)
         t_raw, (vb_raw, ab_raw) = timed(lambda: eng.extract_recording_from(lambda f0, f1: ing.frames(raw, f0, f1), T, ing.wave(raw_wave), mel))
         table = ing.frame_table(T_raw)
-        src_frames = int(torch.unique(table).numel())
-        extra = {'raw_fps': float(ing.fps_in), 'raw_size': [RH, RW], 'raw_rate': ing.rate_in, 'pix_fmt': pix_fmt, 'chroma_loc': args.chroma_loc, 'raw_frames': T_raw, 'raw_bytes_per_frame': frame_bytes,
+        src_frames = int(torch.unique(table).numel()) / (2 if ing.interlaced else 1)          # interlaced: the table holds fields, half a frame's bytes each
+        extra = {'raw_fps': float(ing.fps_in), 'raw_size': [RH, RW], 'raw_rate': ing.rate_in, 'pix_fmt': pix_fmt, 'chroma_loc': args.chroma_loc,
+                 'field_order': ing.field_order, 'raw_frames': T_raw, 'raw_bytes_per_frame': frame_bytes,
                  'raw_bytes': T_raw * frame_bytes, 'frames_25fps': T, 'taps': [ing.taps_y, ing.taps_x],
                  'ingest_s': round(t_ing, 5), 'ingest_frames_per_s': round(sum(f1 - f0 for f0, f1 in chunks) / t_ing, 1),
                  'ingest_video_one_launch_s': round(t_one, 5), 'ingest_video_one_launch_frames_per_s': round(T / t_one, 1),
