@@ -26,10 +26,10 @@
 extern "C" {
 #endif
 
-enum { SF_F32 = 0, SF_BF16 = 1, SF_F16 = 2, SF_U8 = 3, SF_I16 = 4 };   /* element types (SF_I16: PCM input of sf_resample_wave only) */
+enum { SF_F32 = 0, SF_BF16 = 1, SF_F16 = 2, SF_U8 = 3, SF_I16 = 4, SF_I32 = 5 };   /* element types (SF_I16: PCM input of sf_resample_wave / _mix only; SF_I32: of sf_resample_wave_mix only) */
 enum { SF_EPI_NONE = 0, SF_EPI_GELU = 1 };                  /* GEMM epilogue activation */
 
-#define SF_ABI_VERSION 22
+#define SF_ABI_VERSION 23
 int sf_abi_version(void);
 const char* sf_last_error(void);
 /* "gfx950" + build flags; lets the host assert it loaded the library it built */
@@ -614,6 +614,21 @@ int sf_ingest_video(const uint8_t* raw, int64_t stride_frame, int64_t stride_cha
                     uint8_t* out, int T_out, void* stream);
 int sf_resample_wave(const void* x, int dtype, int ch, int64_t ld, int64_t len, const float* kernel, int n, int taps, int o, int width, float* y, int64_t len_out,
                      void* stream);
+
+/* sf_resample_wave for several audio PROGRAMMES of one multi-channel wave (an SDI / contribution feed: up to 16 embedded channels, organised as a stereo main mix,
+ * a second language, audio description, .. - each checked against the picture on its own).  Input element (channel c, sample s) at x + c * stride_ch + s * stride_s,
+ * in elements, both strides >= 1 (planar (ch, len): stride_ch = ld, stride_s = 1; interleaved (len, ch): stride_ch = 1, stride_s = the frame stride >= ch); dtype
+ * SF_F32, SF_I16 (scaled by 2^-15) or SF_I32 (the C cast to fp32, times 2^-31: 24-bit audio left-justified in 32 bits, ffmpeg's s32); 1 <= ch <= 16.  mix fp32
+ * (P, ch) row-major in DEVICE memory, 1 <= P <= 8 per launch; y fp32 (P, len_out) at row stride ldy >= len_out, len_out <= ceil(n len / o):
+ *       m_p[s] = fmaf(mix[p, ch - 1], xf[ch - 1, s], .. fmaf(mix[p, 0], xf[0, s], 0))     (c ascending; xf the scaled fp32 sample; 0 outside [0, len))
+ *       y[p, r + n q] = sum_{i < taps} mpad_p[q o + i] * kernel[r, i],  mpad_p[m] = m_p[m - width]      (i ascending, fmaf: sf_resample_wave's rule, the same bank,
+ *   centring and zero padding).  Zero weights are multiplied like any other: no skipping.  One workgroup makes 256 consecutive outputs of all P programmes: the
+ *   tile's input span is read from memory once, mixed into P fp32 rows in LDS, and each lane walks its phase's taps P times.  The rows take
+ *   P (((255 / n) + 1) o + taps) <= 16384 floats (64 KiB of LDS): P = 8 at 8, 16, 22.05, 32, 44.1, 48 and 96 kHz -> 16 kHz; a caller with more programmes, or a
+ *   longer span, launches several times.  -1 with a message, before any launch: an unknown dtype, ch or P out of range, strides below 1, len_out above
+ *   ceil(n len / o), ldy < len_out, the LDS limit, null pointers with len_out > 0.  The launcher cannot see the buffers' extents: the caller owns them. */
+int sf_resample_wave_mix(const void* x, int dtype, int ch, int64_t stride_ch, int64_t stride_s, int64_t len, const float* mix, int P, const float* kernel, int n,
+                         int taps, int o, int width, float* y, int64_t ldy, int64_t len_out, void* stream);
 
 /* sf_ingest_video for 8-bit YUV 4:2:0 frames as decoders hand them out (NV12 surfaces, I420 / yuv420p arrays): the planes are resized first and the colour
  * conversion runs on the 224 x 224 result, the order of the reference's ffmpeg step (example.py:16-53 scales in YUV; RGB appears when the 256-side result is

@@ -11,6 +11,8 @@
 //                      each workgroup resizes the rows p, p + 2, .. of its frame with the vertical table of that parity - kernels of their own beside the
 //                      progressive ones, which stay the code they were.
 //   sf_resample_wave:  zero-delay polyphase windowed-sinc resampler (the bank of ingest.resample_kernel), channels averaged on read, zero padding by bounds checks.
+//   sf_resample_wave_mix: the same resampler for P programmes of one multi-channel wave: planar or interleaved fp32 / int16 / int32 input read once
+//                      per tile, mixed by a (P, ch) matrix into P fp32 rows in LDS, each row filtered by sf_resample_wave's rule - a kernel of its own.
 // All video kernels run ONE resize pipeline, ing_plane_pass, over 1-byte or 2-byte samples (BS): ingest_video_kernel once per workgroup (one channel), the YUV
 // kernels twice (luma, then U and V together); the launchers size its LDS with one formula, ing_geometry.
 // All kernels bound every address they form by the sizes the launcher was given: a table with entries outside the source only changes the picture, never the
@@ -800,6 +802,115 @@ extern "C" int sf_resample_wave(const void* x, int dtype, int ch, int64_t ld, in
   else
     hipLaunchKernelGGL(resample_wave_kernel<int16_t>, grid, dim3(RES_TILE), lds, (hipStream_t)stream, (const int16_t*)x, ch, ld, len, kernel, n, taps, o, width, y,
                        len_out);
+  SF_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- audio, several programmes -----------------------------------------------------------------------------------------------------------------
+#define MIX_MAX_CH 16          // channels of the input
+#define MIX_MAX_P 8            // programmes (output rows) per launch
+#define MIX_MAX_FLOATS 16384   // P * span: the mixed rows of one tile (64 KiB of LDS)
+#define MIX_CHUNK RES_TILE     // input samples staged at a time
+#define MIX_PITCH (MIX_CHUNK + 1)   // floats between two channels of the staged chunk: lane = sample reads without bank conflicts, c-fastest writes spread over the banks
+#define MIX_LDS_BYTES (MIX_MAX_FLOATS * 4 + MIX_MAX_CH * MIX_PITCH * 4)
+
+__device__ __forceinline__ float mix_sample(float v) { return v; }
+__device__ __forceinline__ float mix_sample(int16_t v) { return (float)v * (1.0f / 32768.0f); }
+__device__ __forceinline__ float mix_sample(int32_t v) { return (float)v * (1.0f / 2147483648.0f); }
+
+// m_p[s] = sum_c mix[p][c] * xf[c][s] (fmaf, c ascending, from 0; 0 outside [0, len)),  y[p][r + n q] = sum_i mpad_p[q o + i] * k[r][i]: sf_resample_wave's rule per
+// programme.  Element (c, s) of the input is x[c * stride_ch + s * stride_s].  One workgroup = 256 consecutive outputs of ALL P programmes:
+//   (1) the tile's input span is read once, 256 samples at a time, into stage[ch][MIX_PITCH] (fp32, scaled): item i of a chunk is (sample i / ch, channel i % ch) when
+//       the channels of a sample lie closer than the samples of a channel (interleaved) and (channel i / 256, sample i % 256) otherwise (planar), so neighbouring
+//       lanes touch neighbouring addresses in either layout;
+//   (2) lane t mixes sample t of the chunk into the P rows rows[p][span_ld];
+//   (3) after the last chunk lane t walks the taps of its phase once per programme, ascending.
+// T = float, int16_t (scaled by 2^-15) or int32_t (cast to fp32, scaled by 2^-31).
+template <typename T>
+__global__ __launch_bounds__(RES_TILE) void resample_wave_mix_kernel(const T* __restrict__ x, int ch, int64_t stride_ch, int64_t stride_s, int64_t len,
+                                                                      const float* __restrict__ mix, int P, const float* __restrict__ kern, int n, int taps, int o,
+                                                                      int width, float* __restrict__ y, int64_t ldy, int64_t len_out, int span_ld) {
+  extern __shared__ __align__(16) float mix_lds[];
+  float* rows = mix_lds;                                                          // [P][span_ld]
+  float* stage = mix_lds + P * span_ld;                                           // [ch][MIX_PITCH]
+  const int tid = threadIdx.x;
+  const int64_t j0 = (int64_t)blockIdx.x * RES_TILE;
+  int64_t j1 = j0 + RES_TILE;
+  j1 = j1 > len_out ? len_out : j1;
+  const int64_t q0 = j0 / n, q1 = (j1 - 1) / n;
+  int span = (int)(q1 - q0) * o + taps;
+  span = span > span_ld ? span_ld : span;                                         // (the launcher's bound: never in force)
+  const int64_t s0 = q0 * o - width;
+  const bool c_fast = stride_ch < stride_s;
+  for (int m0 = 0; m0 < span; m0 += MIX_CHUNK) {
+    const int cnt = span - m0 < MIX_CHUNK ? span - m0 : MIX_CHUNK;
+    const int items = c_fast ? cnt * ch : MIX_CHUNK * ch;
+    for (int i = tid; i < items; i += RES_TILE) {
+      int c, m;
+      if (c_fast) { m = i / ch; c = i - m * ch; } else { c = i / MIX_CHUNK; m = i - c * MIX_CHUNK; }
+      const int64_t s = s0 + m0 + m;
+      float v = 0.f;
+      if (m < cnt && s >= 0 && s < len) v = mix_sample(x[(int64_t)c * stride_ch + s * stride_s]);
+      stage[c * MIX_PITCH + m] = v;
+    }
+    __syncthreads();
+    if (tid < cnt) {
+      const int64_t s = s0 + m0 + tid;
+      const bool inside = s >= 0 && s < len;
+      for (int p = 0; p < P; ++p) {
+        const float* mp = mix + p * ch;
+        float acc = 0.f;
+        for (int c = 0; c < ch; ++c) acc = fmaf(mp[c], stage[c * MIX_PITCH + tid], acc);
+        rows[p * span_ld + m0 + tid] = inside ? acc : 0.f;
+      }
+    }
+    __syncthreads();
+  }
+  const int64_t j = j0 + tid;
+  if (j >= j1) return;
+  const int64_t qq = j / n;
+  const int r = (int)(j - qq * n);
+  const float* kp = kern + (int64_t)r * taps;
+  const int off = (int)(qq - q0) * o;
+  for (int p = 0; p < P; ++p) {
+    const float* xs = rows + p * span_ld + off;
+    float acc = 0.f;
+    for (int i = 0; i < taps; ++i) acc = fmaf(xs[i], kp[i], acc);
+    y[(int64_t)p * ldy + j] = acc;
+  }
+}
+
+extern "C" int sf_resample_wave_mix(const void* x, int dtype, int ch, int64_t stride_ch, int64_t stride_s, int64_t len, const float* mix, int P, const float* kernel,
+                                    int n, int taps, int o, int width, float* y, int64_t ldy, int64_t len_out, void* stream) {
+  SF_CHECK_ARG(dtype == SF_F32 || dtype == SF_I16 || dtype == SF_I32, "sf_resample_wave_mix: dtype %d (fp32 = %d, int16 = %d or int32 = %d)", dtype, SF_F32, SF_I16,
+               SF_I32);
+  SF_CHECK_ARG(ch >= 1 && ch <= MIX_MAX_CH, "sf_resample_wave_mix: %d channels out of range (1 .. %d)", ch, MIX_MAX_CH);
+  SF_CHECK_ARG(P >= 1 && P <= MIX_MAX_P, "sf_resample_wave_mix: %d programmes out of range (1 .. %d per launch)", P, MIX_MAX_P);
+  SF_CHECK_ARG(len >= 0 && len_out >= 0 && stride_ch >= 1 && stride_s >= 1, "sf_resample_wave_mix: len = %lld, len_out = %lld, strides %lld (channel) and %lld (sample)",
+               (long long)len, (long long)len_out, (long long)stride_ch, (long long)stride_s);
+  SF_CHECK_ARG(n >= 1 && o >= 1 && taps >= 1 && width >= 0, "sf_resample_wave_mix: n = %d phases, o = %d, taps = %d, width = %d", n, o, taps, width);
+  SF_CHECK_ARG(len_out <= (len * n + o - 1) / o, "sf_resample_wave_mix: len_out = %lld above ceil(n len / o) = %lld", (long long)len_out,
+               (long long)((len * n + o - 1) / o));
+  SF_CHECK_ARG(ldy >= len_out, "sf_resample_wave_mix: row stride ldy = %lld below len_out = %lld", (long long)ldy, (long long)len_out);
+  const int64_t span = (int64_t)((RES_TILE - 1) / n + 1) * o + taps;            // q_last - q_first <= (255 / n) + 1
+  SF_CHECK_ARG((int64_t)P * span <= MIX_MAX_FLOATS, "sf_resample_wave_mix: a tile of %d outputs spans %lld input samples (o = %d, n = %d, taps = %d); %d programmes "
+               "of them are above the %d floats of LDS: at most %lld programmes per launch", RES_TILE, (long long)span, o, n, taps, P, MIX_MAX_FLOATS,
+               (long long)(MIX_MAX_FLOATS / span));
+  SF_CHECK_ARG((len_out + RES_TILE - 1) / RES_TILE <= 0x7fffffffLL, "sf_resample_wave_mix: len_out = %lld is too long for one launch", (long long)len_out);
+  if (len_out == 0) return 0;
+  SF_CHECK_ARG(x && mix && kernel && y, "sf_resample_wave_mix: null pointer");
+  const dim3 grid((unsigned)((len_out + RES_TILE - 1) / RES_TILE));
+  const int lds = ((int)(P * span) + ch * MIX_PITCH) * 4;
+  int rc = 0;
+  auto launch = [&](auto kern, auto* xs) {
+    if ((rc = sf_prepare_kernel((const void*)kern, MIX_LDS_BYTES, "sf_resample_wave_mix")) != 0) return;
+    hipLaunchKernelGGL(kern, grid, dim3(RES_TILE), lds, (hipStream_t)stream, xs, ch, stride_ch, stride_s, len, mix, P, kernel, n, taps, o, width, y, ldy, len_out,
+                       (int)span);
+  };
+  if (dtype == SF_F32) launch(resample_wave_mix_kernel<float>, (const float*)x);
+  else if (dtype == SF_I16) launch(resample_wave_mix_kernel<int16_t>, (const int16_t*)x);
+  else launch(resample_wave_mix_kernel<int32_t>, (const int32_t*)x);
+  if (rc != 0) return rc;
   SF_LAUNCH_CHECK();
   return 0;
 }

@@ -821,6 +821,73 @@ class SynchformerEngine:
             abank[s0 - s_first:s0 - s_first + n].copy_(af[0])
         return vbank, abank
 
+    # several audio programmes against one picture: the visual tower - 96 % of the towers' work - runs once, the audio tower once per programme
+    def extract_recording_programmes_from(self, frame_fn, n_frames: int, waves16k: torch.Tensor, mel, seg_chunk: Optional[int] = None):
+        """extract_recording_from for P audio programmes of one recording: waves16k (P, n) fp32 16 kHz (ingest.RecordingIngest.waves), device or host ->
+        (vbank (N, 8, 768), abanks (P, N, 6, 768)).  ValueError below one window."""
+        from .frontend import recording_geometry
+        if waves16k.dim() != 2 or waves16k.shape[0] < 1:
+            raise ValueError(f'extract_recording_programmes: expected waves (P, n), got {tuple(waves16k.shape)}')
+        g = recording_geometry(n_frames, waves16k.shape[1])
+        N = g['n_segments']
+        if N < g['n_window']:
+            raise ValueError(f"extract_recording_programmes: {n_frames} frames / {waves16k.shape[1]} samples hold {N} segments, one window needs {g['n_window']}")
+        chunk = self.seg_chunk if seg_chunk is None else int(seg_chunk)
+        if chunk < 1:
+            raise ValueError(f'extract_recording_programmes: seg_chunk = {chunk}')
+        return self.extract_segments_programmes_from(frame_fn, waves16k, mel, 0, N, chunk)
+
+    def extract_segments_programmes_from(self, frame_fn, waves16k: torch.Tensor, mel, s_first: int, n_seg: int, seg_chunk: Optional[int] = None, sample0: int = 0):
+        """extract_segments_from for P programmes: waves16k (P, n) -> (vfeat (n_seg, 8, 768), afeats (P, n_seg, 6, 768)).  Per chunk of at most seg_chunk segments the
+        visual tower runs once, exactly as in extract_segments_from; the audio tower runs over the chunk's segments of all P programmes (programme-major) in groups
+        of at most seg_chunk segments, so its workspaces do not grow with P: the first group beside the visual tower (both_towers), the rest after it."""
+        from .frontend import recording_geometry
+        chunk = self.seg_chunk if seg_chunk is None else int(seg_chunk)
+        if chunk < 1 or n_seg < 1 or s_first < 0 or waves16k.dim() != 2 or waves16k.shape[0] < 1:
+            raise ValueError(f'extract_segments_programmes_from: seg_chunk = {chunk}, segments [{s_first}, {s_first + n_seg}), waves {tuple(waves16k.shape)}')
+        g = recording_geometry(0, 0)
+        vs, vz, as_, az = g['v_stride'], g['v_size'], g['a_stride'], g['a_size']
+        P = waves16k.shape[0]
+        vbank = abanks = None
+        for s0 in range(s_first, s_first + n_seg, chunk):
+            n = min(chunk, s_first + n_seg - s0)
+            f = frame_fn(vs * s0, vs * (s0 + n - 1) + vz)
+            w = waves16k[:, as_ * s0 - sample0:as_ * (s0 + n - 1) + az - sample0].to(self.dev, torch.float32, non_blocking=True)
+            aud = mel.segments(w, 0, as_, n, az)                                 # (P, n, 1, F, Ta)
+            aud = aud.reshape(1, P * n, *aud.shape[2:])
+            vf, af0 = self.both_towers(lambda: self.extract_vfeats_clips(f[None], 0, vs, n), aud[:, :chunk])
+            afs = [af0[0]] + [self.extract_afeats(aud[:, i0:i0 + chunk])[0] for i0 in range(chunk, P * n, chunk)]
+            af = (afs[0] if len(afs) == 1 else torch.cat(afs)).view(P, n, *af0.shape[2:])
+            if vbank is None:
+                vbank = torch.empty(n_seg, *vf.shape[2:], device=self.dev, dtype=torch.float32)
+                abanks = torch.empty(P, n_seg, *af.shape[2:], device=self.dev, dtype=torch.float32)
+            vbank[s0 - s_first:s0 - s_first + n].copy_(vf[0])
+            abanks[:, s0 - s_first:s0 - s_first + n].copy_(af)
+        return vbank, abanks
+
+    def sync_windows_programmes(self, vbank: torch.Tensor, abanks: torch.Tensor, hop: int = 1, win_chunk: int = 256, n_window: int = 14) -> torch.Tensor:
+        """sync_windows for P audio banks against one visual bank: vbank (N, tv, 768), abanks (P, N, ta, 768) -> logits (P, W, n_out).  vproj runs over the visual
+        bank once; each programme's bank is projected and crosses the sync transformer through sync_windows' row maps."""
+        if vbank.dim() != 3 or abanks.dim() != 4 or abanks.shape[0] < 1 or vbank.shape[0] != abanks.shape[1] or vbank.shape[2] != D or abanks.shape[3] != D:
+            raise ValueError(f'sync_windows_programmes: expected banks (N, tv, {D}) / (P, N, ta, {D}), got {tuple(vbank.shape)} / {tuple(abanks.shape)}')
+        if hop < 1 or win_chunk < 1:
+            raise ValueError(f'sync_windows_programmes: hop = {hop}, win_chunk = {win_chunk}')
+        P, N, tv, ta = abanks.shape[0], vbank.shape[0], vbank.shape[1], abanks.shape[2]
+        if N < n_window:
+            raise ValueError(f'sync_windows_programmes: a bank of {N} segments holds no window of {n_window}')
+        Sv, Sa = n_window * tv, n_window * ta
+        self._sync_table(Sv, Sa)
+        W = (N - n_window) // hop + 1
+        v2 = self.project(vbank.to(self.dev, torch.float32).unsqueeze(0), 'v')[0]
+        logits = torch.empty(P, W, self.n_out, device=self.dev, dtype=torch.float32)
+        for p in range(P):
+            a2 = self.project(abanks[p].to(self.dev, torch.float32).unsqueeze(0), 'a')[0]
+            for w0 in range(0, W, win_chunk):
+                nw = min(win_chunk, W - w0)
+                maps = (ops.rowmap(Sv, Sv, hop * tv, 0, 1, w0 * hop * tv), ops.rowmap(Sa, Sa, hop * ta, 0, 1, w0 * hop * ta))
+                logits[p, w0:w0 + nw].copy_(self._sync_stack(v2, a2, nw, Sv, Sa, src_maps=maps))
+        return logits
+
     def sync_windows(self, vbank: torch.Tensor, abank: torch.Tensor, hop: int = 1, win_chunk: int = 256, n_window: int = 14) -> torch.Tensor:
         """Segment feature banks (N, tv, 768) / (N, ta, 768) fp32 on the device -> logits (W, n_out) of the W = (N - 14) // hop + 1 windows of 14 segments, window w =
         segments [w hop, w hop + 14).  vproj / aproj run once over the whole bank; the sync transformer's input LayerNorms then read window w's 14 tv / 14 ta rows

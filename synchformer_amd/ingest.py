@@ -40,13 +40,20 @@ deinterlacing filter (ops.ingest_video_fields, ops.ingest_video_planes_fields); 
 
     ing = RecordingIngest(dev, (30000, 1001), (1080, 1920), 48000, pix_fmt='uyvy422', field_order='tff')
 
+Several audio programmes of one feed (an SDI / contribution feed carries up to 16 embedded channels - a stereo main mix, a second language, audio
+description - each of which can be out of sync on its own) are tracked against ONE pass of the picture:
+
+    ing = RecordingIngest(dev, 25, (1080, 1920), 48000, pix_fmt='uyvy422', audio_channels=8, audio_interleaved=True, programmes=[(0, 1), (2, 3), 4])
+    tracks = tracker.track_raw_programmes(raw_frames, raw_wave, ing)      # raw_wave (n, 8) int16 / int32 (s24 left-justified) / fp32 -> one OffsetTrack per programme
+
 Out of scope: decoding, 12-bit / 4:4:4 input through RecordingIngest (ops.ingest_video_planes takes a 4:4:4 planar layout), v210, deinterlacing filters, interlaced
 4:2:0, a field order that changes mid-stream, telecine, BT.2020 in csc_matrix, transfer functions (PQ, HLG: a 10-bit HDR stream is converted by the matrix alone,
-no tone mapping), double-buffered uploads, several recordings per call.
+no tone mapping), double-buffered uploads, several recordings per call; for programmes: de-embedding, channel-layout metadata, loudness normalisation, more than
+16 channels, u8 / packed s24 / float64 samples, per-programme sample rates or known delays.
 """
 import math
 from fractions import Fraction
-from typing import NamedTuple, Optional, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -58,6 +65,8 @@ PIX_FMTS_422 = ('uyvy422', 'yuyv422', 'yuv422p', 'nv16', 'yuv422p10le', 'p210', 
 PIX_FMTS_422_16 = ('yuv422p10le', 'p210', 'y210')                                           # of those, 10-bit samples in uint16
 PIX_FMTS_PACKED = ('uyvy422', 'yuyv422', 'y210')                                            # raw frames (T, H, W, 2): a macropixel Y0 U Y1 V (in some order) per two columns
 FIELD_ORDERS = ('progressive', 'tff', 'bff')                                                   # frames; interlaced, top / bottom field first
+MAX_AUDIO_CHANNELS = 16          # sf_resample_wave_mix's range (ops.MIX_MAX_CH)
+WAVE_DTYPES = (torch.float32, torch.int16, torch.int32)                                        # of an ingest with programmes: flt, s16, s32 (s24 left-justified)
 CHROMA_LOCS = {'center': (0.0, 0.0), 'left': (0.0, 0.25), 'topleft': (0.25, 0.25)}       # (shift of the cy tables, of the cx tables)
 _KR_KB = {'bt601': (0.299, 0.114), 'bt709': (0.2126, 0.0722)}
 
@@ -239,6 +248,41 @@ def csc_matrix(colorspace: str = 'bt601', full_range: bool = False, bit_depth: i
     return M, torch.tensor([o0, oc, oc], dtype=torch.float64)
 
 
+def programme_matrix(programmes: Sequence, n_channels: int) -> torch.Tensor:
+    """The down-mix of a multi-channel wave into audio programmes: fp32 (P, n_channels), row p the weights of programme p.  A programme is an int (that
+    channel, weight 1), a tuple / list of ints (those channels at equal weights 1 / k: a stereo pair averaged as sf_resample_wave averages) or a dict
+    {channel: weight}.  ValueError on an empty list, an empty programme, a channel outside [0, n_channels), a channel named twice in one programme, a non-finite
+    weight."""
+    n_channels = int(n_channels)
+    if isinstance(programmes, (int, dict)) or programmes is None or len(programmes) == 0:
+        raise ValueError(f'programme_matrix: programmes = {programmes!r}: a non-empty list of programmes')
+    if n_channels < 1:
+        raise ValueError(f'programme_matrix: n_channels = {n_channels}')
+    M = torch.zeros(len(programmes), n_channels, dtype=torch.float32)
+    for p, prog in enumerate(programmes):
+        if isinstance(prog, dict):
+            items = list(prog.items())
+        elif isinstance(prog, (tuple, list)):
+            items = [(c, 1.0 / len(prog)) for c in prog]
+        elif isinstance(prog, int) and not isinstance(prog, bool):
+            items = [(prog, 1.0)]
+        else:
+            raise ValueError(f'programme_matrix: programme {p} = {prog!r}: an int, a tuple of ints or a dict {{channel: weight}}')
+        if not items:
+            raise ValueError(f'programme_matrix: programme {p} is empty')
+        seen = set()
+        for c, w in items:
+            if isinstance(c, bool) or not isinstance(c, int) or not 0 <= c < n_channels:
+                raise ValueError(f'programme_matrix: programme {p} names channel {c!r}, the wave has channels 0 .. {n_channels - 1}')
+            if c in seen:
+                raise ValueError(f'programme_matrix: programme {p} names channel {c} twice')
+            if isinstance(w, bool) or not isinstance(w, (int, float)) or not math.isfinite(w):
+                raise ValueError(f'programme_matrix: programme {p}, channel {c}: weight {w!r} is not a finite number')
+            seen.add(c)
+            M[p, c] = float(w)
+    return M
+
+
 def resample_kernel(rate_in: int, rate_out: int = 16000, lowpass_filter_width: int = 6, rolloff: float = 0.99):
     """The polyphase windowed-sinc bank of torchaudio.functional.resample at its defaults (sinc_interp_hann): (kernel fp32 (n, 2 width + o), width, o, n) with
     o = rate_in / gcd, n = rate_out / gcd.  Output y[p + n q] = sum_i xpad[q o + i] * kernel[p, i] on x zero-padded by (width, width + o), cut to
@@ -275,12 +319,25 @@ class RecordingIngest:
     frame rate.  The recording is then its 2 n fields at 2 fps_in: frame_table / n_frames come from fps_field_table, every output frame is ONE field resized to the
     frame's (Hr, Wr) with the vertical table of its parity p, aa_bicubic_table(H / 2, Hr, shift = 0.25 - p / 2) (y_tables; 4:2:2 chroma rows take the same two), and
     the 35-tap limit applies to the field's taps.  ValueError on an unknown field_order, an odd H with an interlaced order, or an interlaced order with a 4:2:0 format
-    (field-sited chroma is another geometry)."""
+    (field-sited chroma is another geometry).
+    programmes: a list for programme_matrix - the wave then has audio_channels channels (1 .. 16), planar (ch, n) or, with audio_interleaved, (n, ch),
+    fp32, int16 or int32 (s24 left-justified), and .waves() gives one 16 kHz wave per programme from one read of the input (ops.resample_wave_mix); .wave() raises.
+    programmes=None (the default) is the object without them: no attribute changes.  ValueError on audio_channels / audio_interleaved without programmes,
+    audio_channels outside 1 .. 16, and whatever programme_matrix refuses."""
 
     field_order, interlaced = 'progressive', False
+    programmes = None
 
     def __init__(self, device, fps_in, size_in, rate_in: int, channels_last: bool = False, resize_side: int = 256, crop: int = CROP, pix_fmt: str = 'rgb24',
-                 colorspace: str = 'bt601', full_range: bool = False, chroma_loc: str = 'center', csc=None, field_order: str = 'progressive'):
+                 colorspace: str = 'bt601', full_range: bool = False, chroma_loc: str = 'center', csc=None, field_order: str = 'progressive',
+                 audio_channels: Optional[int] = None, audio_interleaved: bool = False, programmes=None):
+        if programmes is None:
+            if audio_channels is not None or audio_interleaved:
+                raise ValueError('audio_channels / audio_interleaved describe the wave of an ingest with programmes: pass programmes=[...]')
+        else:
+            if audio_channels is None or isinstance(audio_channels, bool) or not 1 <= int(audio_channels) <= MAX_AUDIO_CHANNELS:
+                raise ValueError(f'audio_channels = {audio_channels!r} with programmes: the channels of the wave, 1 .. {MAX_AUDIO_CHANNELS}')
+            mix = programme_matrix(programmes, int(audio_channels))
         if field_order not in FIELD_ORDERS:
             raise ValueError(f'field_order = {field_order!r}: one of {FIELD_ORDERS}')
         if pix_fmt not in PIX_FMTS + PIX_FMTS_422:
@@ -349,6 +406,9 @@ class RecordingIngest:
             self.kernel, self.width, self.o, self.n = resample_kernel(self.rate_in)
         self.kernel = self.kernel.contiguous().to(self.dev)
         self._tables = {}
+        if programmes is not None:                                               # (an object without programmes keeps the attributes it had)
+            self.programmes, self.audio_channels, self.audio_interleaved = list(programmes), int(audio_channels), bool(audio_interleaved)
+            self.mix = mix.to(self.dev)
 
     def frame_table(self, n_in: int) -> torch.Tensor:
         """fps_frame_table(n_in, fps_in) (host, cached per n_in); interlaced: fps_field_table(n_in, fps_in), FIELD indices."""
@@ -405,6 +465,8 @@ class RecordingIngest:
 
     def wave(self, raw_wave: torch.Tensor) -> torch.Tensor:
         """raw_wave (n,) or (ch, n), fp32 or int16 PCM, device or host -> mono fp32 16 kHz (n16k,) on the device.  A mono fp32 wave at 16 kHz is returned as it is."""
+        if self.programmes is not None:
+            raise ValueError(f'RecordingIngest.wave: this ingest has {len(self.programmes)} programmes, there is no single wave: use .waves()')
         if raw_wave.dim() not in (1, 2) or raw_wave.dtype not in (torch.float32, torch.int16) or (raw_wave.dim() == 2 and not 1 <= raw_wave.shape[0] <= 8):
             raise ValueError(f'raw wave: expected fp32 or int16 (n,) or (ch <= 8, n), got {raw_wave.dtype} {tuple(raw_wave.shape)}')
         x = raw_wave.to(self.dev, non_blocking=True)
@@ -412,6 +474,22 @@ class RecordingIngest:
             return x.reshape(-1)
         from . import ops
         return ops.resample_wave(x, self.kernel, self.o, self.width)
+
+    def _check_wave(self, raw_wave: torch.Tensor):
+        ch = self.audio_channels
+        want = ('n', ch) if self.audio_interleaved else (ch, 'n')
+        if raw_wave.dim() != 2 or raw_wave.dtype not in WAVE_DTYPES or raw_wave.shape[0 if not self.audio_interleaved else 1] != ch:
+            raise ValueError(f'raw wave: expected fp32, int16 or int32 ({want[0]}, {want[1]}), got {raw_wave.dtype} {tuple(raw_wave.shape)}')
+
+    def waves(self, raw_wave: torch.Tensor, len_out: Optional[int] = None) -> torch.Tensor:
+        """The programmes of a multi-channel wave: raw_wave fp32, int16 or int32 (s24 left-justified), (audio_channels, n), or (n, audio_channels) when
+        audio_interleaved, device or host -> fp32 16 kHz (P, n16k) on the device, row p the programme programmes[p].  One read of the input.  At 16 kHz the identity
+        bank goes through the same kernel: the rows are the mix itself, to the last bit."""
+        if self.programmes is None:
+            raise ValueError('RecordingIngest.waves: this ingest has no programmes: use .wave()')
+        self._check_wave(raw_wave)
+        from . import ops
+        return ops.resample_wave_mix(raw_wave.to(self.dev, non_blocking=True), self.mix, self.kernel, self.o, self.width, self.audio_interleaved, len_out)
 
     def stream(self) -> 'IngestStream':
         """The same conversion for a recording that is still arriving: see IngestStream."""
@@ -453,7 +531,9 @@ class IngestStream:
     """RecordingIngest for a feed: push(raw_frames, raw_wave) and flush() return the 25 fps frames (uint8 (t, 3, 224, 224)) and the 16 kHz samples (fp32 (m,)) that
     have become FINAL, on the device; concatenated over all calls they are bit-equal to ingest.frames(raw_all, 0, n_frames) and ingest.wave(raw_all), for every
     chunking.  An interlaced ingest counts fields (two per frame seen) and still holds one source FRAME.  Host logic over the same kernels: the last source frame is held until a later one shows which slots it fills (flush emits its slot), the raw
-    samples are held from the resampler's left context on (resample_stream_plan).  Either argument may be empty (or None)."""
+    samples are held from the resampler's left context on (resample_stream_plan).  Either argument may be empty (or None).  An ingest with programmes
+    holds the raw samples in the layout they arrive in, (ch, m) or (m, ch), returns fp32 (P, m) per call, and the concatenation along the samples is bit-equal to
+    ingest.waves(raw_all); the plan, and so the bound on the held samples, is the same."""
 
     def __init__(self, ingest: RecordingIngest):
         self.ing = ingest
@@ -462,11 +542,12 @@ class IngestStream:
         self.raw_seen = self.samples_out = 0     # raw samples seen, 16 kHz samples emitted
         self._raw = None                         # raw samples [self._raw0, raw_seen) on the device, (ch, m)
         self._raw0 = 0
+        self._t = 0 if ingest.programmes is not None and ingest.audio_interleaved else 1      # the sample axis of the held raw wave
         self.closed = False
 
     @property
     def held(self) -> dict:
-        return dict(frames=0 if self._last is None else 1, samples=0 if self._raw is None else int(self._raw.shape[1]))
+        return dict(frames=0 if self._last is None else 1, samples=0 if self._raw is None else int(self._raw.shape[self._t]))
 
     def _passthrough(self, x: torch.Tensor) -> bool:
         return self.ing.rate_in == 16000 and x.dtype == torch.float32 and x.shape[0] == 1
@@ -501,8 +582,29 @@ class IngestStream:
         t = torch.tensor([min(fps_slot_source(j, u * ing.fps_in), u * self.n_src - 1) - u * base for j in range(j0, j1)], dtype=torch.int32)
         return ing._resize(src, t)
 
+    def _waves(self, raw: Optional[torch.Tensor], final: bool) -> torch.Tensor:
+        """_wave for an ingest with programmes: the same plan over the raw samples as they arrive, P rows out."""
+        ing, t = self.ing, self._t
+        if raw is not None and raw.shape[t if raw.dim() == 2 else 0]:
+            ing._check_wave(raw)
+            x = raw.to(ing.dev, non_blocking=True)
+            self._raw = x if self._raw is None else torch.cat([self._raw, x], t)
+            self.raw_seen += int(x.shape[t])
+        P = len(ing.programmes)
+        if self._raw is None:
+            return torch.empty(P, 0, device=ing.dev, dtype=torch.float32)
+        c0, k0, k1, hold = resample_stream_plan(self.samples_out, self.raw_seen, ing.o, ing.width, ing.n, final)
+        out = torch.empty(P, 0, device=ing.dev, dtype=torch.float32)
+        if k1 > k0:
+            out = ing.waves(self._raw.narrow(t, c0 - self._raw0, self.raw_seen - c0), len_out=k1)[:, k0:]
+            self.samples_out += k1 - k0
+        self._raw, self._raw0 = self._raw.narrow(t, hold - self._raw0, self.raw_seen - hold), hold
+        return out
+
     def _wave(self, raw: Optional[torch.Tensor], final: bool) -> torch.Tensor:
         ing = self.ing
+        if ing.programmes is not None:
+            return self._waves(raw, final)
         if raw is not None and raw.shape[-1]:
             if raw.dim() not in (1, 2) or raw.dtype not in (torch.float32, torch.int16) or (raw.dim() == 2 and not 1 <= raw.shape[0] <= 8):
                 raise ValueError(f'raw wave: expected fp32 or int16 (n,) or (ch <= 8, n), got {raw.dtype} {tuple(raw.shape)}')

@@ -1115,6 +1115,55 @@ def resample_wave(x: torch.Tensor, kernel: torch.Tensor, o: int, width: int, len
     return y
 
 
+SF_I32 = 5
+MIX_MAX_CH, MIX_MAX_P, MIX_MAX_FLOATS, MIX_TILE = 16, 8, 16384, 256      # sf_resample_wave_mix: channels, programmes per launch, floats of LDS for the mixed rows
+_MIX_DT = {torch.float32: SF_F32, torch.int16: SF_I16, torch.int32: SF_I32}
+
+
+def resample_mix_span(n: int, o: int, taps: int) -> int:
+    """Input samples one tile of 256 outputs may span (sf_resample_wave_mix stages them per programme): ((255 // n) + 1) o + taps."""
+    return ((MIX_TILE - 1) // n + 1) * o + taps
+
+
+def resample_wave_mix(x: torch.Tensor, mix: torch.Tensor, kernel: torch.Tensor, o: int, width: int, interleaved: bool = False,
+                      len_out: Optional[int] = None) -> torch.Tensor:
+    """The polyphase resampler for several programmes of one multi-channel wave (sf_resample_wave_mix): x fp32, int16 (scaled by 2^-15) or int32 (2^-31)
+    on the device, (ch, len), or (len, ch) when `interleaved`, ch <= 16, any strided 2-D view with positive strides (anything else is copied once); mix fp32 (P, ch):
+    programme p is sum_c mix[p, c] x[c]; kernel fp32 (n, 2 width + o) contiguous (ingest.resample_kernel) -> fp32 (P, ceil(n len / o)), or its first len_out
+    columns.  More than 8 programmes, or more than the LDS limit holds (P * resample_mix_span <= 16384), go in several launches."""
+    if x.dim() != 2 or x.dtype not in _MIX_DT or mix.dim() != 2 or mix.dtype != torch.float32:
+        raise ValueError(f'resample_wave_mix: expected an fp32, int16 or int32 wave (ch, len) / (len, ch) and an fp32 mix (P, ch), got {x.dtype} {tuple(x.shape)} and '
+                         f'{mix.dtype} {tuple(mix.shape)}')
+    if interleaved:
+        x = x.t()
+    ch, n_in = x.shape
+    P = mix.shape[0]
+    if not 1 <= ch <= MIX_MAX_CH or mix.shape[1] != ch or P < 1:
+        raise ValueError(f'resample_wave_mix: {ch} channels (1 .. {MIX_MAX_CH}) with a mix of {tuple(mix.shape)}')
+    xp, mp, kp = _dev(x, 'x'), _dev(mix, 'mix'), _dev(kernel, 'kernel')
+    if (ch > 1 and x.stride(0) < 1) or (n_in > 1 and x.stride(1) < 1):           # a layout two positive strides cannot express: one contiguous copy
+        x = x.contiguous()
+        xp = x.data_ptr()
+    if not mix.is_contiguous():
+        mix = mix.contiguous()
+        mp = mix.data_ptr()
+    n, taps = kernel.shape
+    assert kernel.dtype == torch.float32 and kernel.is_contiguous() and taps == 2 * width + o
+    per = min(MIX_MAX_P, MIX_MAX_FLOATS // resample_mix_span(n, o, taps))
+    if per < 1:
+        raise ValueError(f'resample_wave_mix: a tile spans {resample_mix_span(n, o, taps)} input samples (o = {o}, n = {n}, taps = {taps}), above {MIX_MAX_FLOATS}')
+    full = -(-n * n_in // o)
+    len_out = full if len_out is None else int(len_out)
+    y = torch.empty(P, len_out, device=x.device, dtype=torch.float32)
+    lib = _lib.load()
+    for p0 in range(0, P, per):
+        pn = min(per, P - p0)
+        rc = lib.sf_resample_wave_mix(xp, _MIX_DT[x.dtype], ch, x.stride(0) if ch > 1 else 1, x.stride(1) if n_in > 1 else 1, n_in, mp + 4 * ch * p0, pn, kp, n, taps,
+                                      o, width, _dev(y, 'y') + 4 * len_out * p0, max(len_out, 1), len_out, _stream())
+        _lib.check(rc, 'sf_resample_wave_mix')
+    return y
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # PyTorch dispatcher registration (SURVEY §8b "custom-op contract"): the C-ABI launchers as `torch.ops.synchformer.*`
 # out-variant custom ops (device_types = "cuda", i.e. HIP on ROCm).  They mutate their `out` argument and return nothing,

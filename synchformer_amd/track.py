@@ -23,11 +23,15 @@ confidence that carries the evidence of the whole recording, and an offset finer
     upds = pool.push({a: (frames_a, wave_a), b: (frames_b, wave_b)})     # {feed: OffsetUpdate}, each what the feed's own stream would return
     upds = pool.push({a: (frames_a2, wave_a2)}, flush=[b])               # b's final push; its slot is free again
 
+    ing = RecordingIngest(dev, 25, (1080, 1920), 48000, audio_channels=8, audio_interleaved=True, programmes=[(0, 1), (2, 3), 4])
+    tracks = tracker.track_raw_programmes(raw_frames, raw_wave, ing)     # one OffsetTrack per audio programme; the picture crosses its tower once
+    upds = tracker.stream(ingest=ing).push(raw_frames_1s, raw_wave_1s)   # a ProgrammeStream: one OffsetUpdate per programme
+
 Out of scope (one recording per call): batching several recordings offline, double-buffered host-to-device transfer of the chunks, de-duplicating the
 overlapped tubelets inside the patch embedding.
 """
 from dataclasses import dataclass
-from typing import Optional
+from typing import List, Optional
 
 import torch
 
@@ -93,15 +97,36 @@ class OffsetTracker:
 
     def track_features(self, vbank: torch.Tensor, abank: torch.Tensor, win_chunk: int = 256) -> OffsetTrack:
         """Segment feature banks (N, 8, 768) / (N, 6, 768) (engine.extract_recording, or features the caller already holds) -> OffsetTrack."""
-        logits = self.eng.sync_windows(vbank, abank, hop=self.hop, win_chunk=win_chunk)
+        return self._track_of(self.eng.sync_windows(vbank, abank, hop=self.hop, win_chunk=win_chunk), int(vbank.shape[0]))
+
+    def _track_of(self, logits: torch.Tensor, n_segments: int) -> OffsetTrack:
+        """The read-out of one recording's window logits (W, C)."""
         cls_raw, conf_raw, cls_path, conf_path = ops.track_decode(logits, self.lam)
         track = OffsetTrack(t_sec=window_times(logits.shape[0], self.hop).to(self.eng.dev), logits=logits, cls_raw=cls_raw, conf_raw=conf_raw,
                             cls_path=cls_path, conf_path=conf_path, offset_sec_raw=self.grid[cls_raw.long()], offset_sec_path=self.grid[cls_path.long()],
-                            n_segments=int(vbank.shape[0]))
+                            n_segments=n_segments)
         if self.posterior:
             track.post, track.cls_post, track.conf_post, track.offset_sec_mean, track.log_z = ops.track_posterior(logits, self.lam, self.grid)
             track.offset_sec_post = self.grid[track.cls_post.long()]
         return track
+
+    def track_features_programmes(self, vbank: torch.Tensor, abanks: torch.Tensor, win_chunk: int = 256) -> List[OffsetTrack]:
+        """One visual bank (N, 8, 768) and the audio banks of P programmes (P, N, 6, 768) (engine.extract_recording_programmes_from) -> one OffsetTrack per
+        programme, each what track_features gives for (vbank, abanks[p]); vproj runs over the visual bank once (engine.sync_windows_programmes)."""
+        logits = self.eng.sync_windows_programmes(vbank, abanks, hop=self.hop, win_chunk=win_chunk)
+        return [self._track_of(logits[p], int(vbank.shape[0])) for p in range(logits.shape[0])]
+
+    def track_raw_programmes(self, raw_frames: torch.Tensor, raw_wave: torch.Tensor, ingest, seg_chunk: Optional[int] = None, win_chunk: int = 256) -> List[OffsetTrack]:
+        """track_raw for the audio programmes of one recording: `ingest` an ingest.RecordingIngest with programmes, raw_wave its multi-channel wave
+        ((ch, n), or (n, ch) interleaved; fp32, int16 or int32) -> one OffsetTrack per programme, in the order of ingest.programmes, each identical in every field
+        to track_raw on that programme alone.  The frames are resized once and cross the visual tower once; the audio tower runs once per programme."""
+        if getattr(ingest, 'programmes', None) is None:
+            raise ValueError('track_raw_programmes: the ingest has no programmes (RecordingIngest(..., audio_channels=, programmes=[...])): use track_raw')
+        ingest._check_frames(raw_frames)
+        waves = ingest.waves(raw_wave)
+        banks = self.eng.extract_recording_programmes_from(lambda f0, f1: ingest.frames(raw_frames, f0, f1), ingest.n_frames(raw_frames.shape[0]), waves, self.mel,
+                                                           seg_chunk)
+        return self.track_features_programmes(*banks, win_chunk=win_chunk)
 
     def track(self, frames: torch.Tensor, wave: torch.Tensor, seg_chunk: Optional[int] = None, win_chunk: int = 256) -> OffsetTrack:
         """frames (T, 3, 224, 224) uint8, wave (n,) fp32 16 kHz, on the device or in host memory -> OffsetTrack; ValueError below one window (120 frames,
@@ -112,18 +137,23 @@ class OffsetTracker:
         """The recording as a decoder hands it out: raw_frames uint8 (T, 3, H, W) or channels-last (T, H, W, 3) at the native frame rate and
         size, raw_wave fp32 or int16 (n,) / (ch, n) at the native rate, device or host; `ingest` an ingest.RecordingIngest of that geometry -> OffsetTrack.
         Each tower chunk's 25 fps, 224 x 224 frames are made from the raw ones right before the chunk runs; the resized recording is never materialised.
-        ValueError below one window after conversion, or when the frames do not have the ingest's size."""
+        ValueError below one window after conversion, or when the frames do not have the ingest's size, or for an ingest with programmes (track_raw_programmes)."""
+        if getattr(ingest, 'programmes', None) is not None:
+            raise ValueError(f'track_raw: the ingest has {len(ingest.programmes)} audio programmes, one track cannot hold them: use track_raw_programmes')
         ingest._check_frames(raw_frames)
         wave = ingest.wave(raw_wave)
         banks = self.eng.extract_recording_from(lambda f0, f1: ingest.frames(raw_frames, f0, f1), ingest.n_frames(raw_frames.shape[0]), wave, self.mel, seg_chunk)
         return self.track_features(*banks, win_chunk=win_chunk)
 
-    def stream(self, lag: int = 16, seg_chunk: Optional[int] = None, ingest=None) -> 'OffsetStream':
+    def stream(self, lag: int = 16, seg_chunk: Optional[int] = None, ingest=None):
         """A live feed: push frames and samples as they arrive, get per push the windows that became final.  lag: window w is committed once
         `lag` more windows have arrived (0 .. 255), as the class of w on the Viterbi path of everything up to window w + lag - a decision delay of
         lag * hop * 0.32 s.  lag = 16 is a DEFAULT, NOT A TUNED VALUE (as lam): how far back a later window still changes the decision depends on lam and on
         the domain's logits; choose it on held-out recordings.  lag >= the number of windows gives the offline path at flush().  seg_chunk: as in track().
-        ingest: an ingest.RecordingIngest - push then takes frames and samples as decoded (native frame rate, size, sample rate; track_raw's layouts)."""
+        ingest: an ingest.RecordingIngest - push then takes frames and samples as decoded (native frame rate, size, sample rate; track_raw's layouts).  An ingest
+        with programmes gives a ProgrammeStream: push / flush return one OffsetUpdate per programme."""
+        if getattr(ingest, 'programmes', None) is not None:
+            return ProgrammeStream(self, lag, seg_chunk, ingest)
         return OffsetStream(self, lag, seg_chunk, ingest)
 
     def pool(self, n_feeds: int, lag: int = 16, seg_chunk: Optional[int] = None) -> 'OffsetStreamPool':
@@ -209,7 +239,7 @@ class _Feed:
     @property
     def held(self) -> dict:
         """The sizes of the carried buffers: frames, samples, segments (features) and state_bytes."""
-        return dict(frames=int(self._frames.shape[0]), samples=int(self._wave.shape[0]), segments=0 if self._vfeat is None else int(self._vfeat.shape[0]),
+        return dict(frames=int(self._frames.shape[0]), samples=int(self._wave.numel()), segments=0 if self._vfeat is None else int(self._vfeat.shape[0]),
                     state_bytes=self._state_bytes())
 
     @property
@@ -228,14 +258,15 @@ class _Feed:
     def _accept(self, frames: torch.Tensor, wave: torch.Tensor, who: str = 'OffsetStream.push'):
         """Appends what arrived (25 fps, 224 x 224, 16 kHz: after the ingest) to the held frames and samples and counts it."""
         eng = self.tracker.eng
-        if frames.dim() != 4 or frames.dtype != torch.uint8 or tuple(frames.shape[1:]) != (3, 224, 224) or wave.dim() != 1:
-            raise ValueError(f'{who}: expected uint8 frames (t, 3, 224, 224) and a 1-D wave, got {frames.dtype} {tuple(frames.shape)} / {tuple(wave.shape)}')
+        if frames.dim() != 4 or frames.dtype != torch.uint8 or tuple(frames.shape[1:]) != (3, 224, 224) or wave.shape[:-1] != self._wave.shape[:-1]:
+            raise ValueError(f'{who}: expected uint8 frames (t, 3, 224, 224) and a {"1-D wave" if self._wave.dim() == 1 else f"wave ({self._wave.shape[0]}, m)"}, got '
+                             f'{frames.dtype} {tuple(frames.shape)} / {tuple(wave.shape)}')
         if frames.shape[0]:
             self._frames = torch.cat([self._frames, frames.to(eng.dev, non_blocking=True)])
-        if wave.shape[0]:
-            self._wave = torch.cat([self._wave, wave.to(eng.dev, torch.float32, non_blocking=True)])
+        if wave.shape[-1]:                                                       # (the samples are the last axis: a ProgrammeStream holds P rows of them)
+            self._wave = torch.cat([self._wave, wave.to(eng.dev, torch.float32, non_blocking=True)], -1)
         self.n_frames += int(frames.shape[0])
-        self.n_samples += int(wave.shape[0])
+        self.n_samples += int(wave.shape[-1])
 
     def _add_features(self, vf: torch.Tensor, af: torch.Tensor):
         self._vfeat = vf if self._vfeat is None else torch.cat([self._vfeat, vf])
@@ -244,7 +275,7 @@ class _Feed:
     def _trim(self, g: dict):
         """Drops what no later segment / window reads and moves the totals on (g: this advance's stream_geometry)."""
         self._frames, self._f0 = self._frames[g['frames_from'] - self._f0:], g['frames_from']
-        self._wave, self._a0 = self._wave[g['samples_from'] - self._a0:], g['samples_from']
+        self._wave, self._a0 = self._wave[..., g['samples_from'] - self._a0:], g['samples_from']
         if self._vfeat is not None:
             k = g['features_from'] - self._s0
             self._vfeat, self._afeat, self._s0 = self._vfeat[k:], self._afeat[k:], g['features_from']
@@ -322,6 +353,77 @@ class OffsetStream(_Feed):
         return self._update(out, logits, w0, w1)
 
 
+class ProgrammeStream(_Feed):
+    """OffsetTracker.stream(ingest=<an ingest with programmes>): OffsetStream for the P audio programmes of one feed.  push(raw_frames, raw_wave) and
+    flush() return one OffsetUpdate per programme, in the order of ingest.programmes; each is what a plain OffsetStream fed that programme's channels returns,
+    field for field (bit for bit on the un-fused tower schedule).  The picture is resized once and crosses the visual tower once per segment; the stream holds ONE
+    set of frames and ONE visual feature buffer, P wave rows and P audio feature buffers, and one ops.track_pool_state(P, ..) advanced by one ops.track_pool_push
+    per push.  The host arithmetic is _Feed's.  The bound on `held` is OffsetStream's with the audio entries scaled by P:
+        frames          at most 15, plus what the video is ahead of the audio, plus one push
+        samples         P x (at most 10239, plus what the audio is ahead of the video, plus one push)
+        segments        visual features: at most 13 + hop - 1
+        audio_segments  P x segments
+        state_bytes     P x ops.track_stream_state's bytes"""
+
+    def __init__(self, tracker: OffsetTracker, lag: int = 16, seg_chunk: Optional[int] = None, ingest=None):
+        if getattr(ingest, 'programmes', None) is None:
+            raise ValueError('ProgrammeStream: an ingest with programmes is required (RecordingIngest(..., audio_channels=, programmes=[...]))')
+        super().__init__(tracker, ingest)
+        self.P = len(ingest.programmes)
+        self.lag, self.seg_chunk = int(lag), seg_chunk
+        self._wave = torch.empty(self.P, 0, device=tracker.eng.dev, dtype=torch.float32)
+        self.state = ops.track_pool_state(self.P, tracker.eng.n_out, self.lag, tracker.posterior, tracker.eng.dev)
+
+    def _state_bytes(self) -> int:
+        return int(self.state.buf.numel())
+
+    @property
+    def held(self) -> dict:
+        h = super().held                                                         # (samples: the elements of the (P, m) wave rows)
+        h['audio_segments'] = self.P * h['segments']
+        return h
+
+    @property
+    def held_bound(self) -> dict:
+        b = super().held_bound
+        b['samples'], b['audio_segments'] = self.P * b['samples'], self.P * b['segments']
+        return b
+
+    def push(self, frames: torch.Tensor, wave: torch.Tensor) -> List[OffsetUpdate]:
+        if self.closed:
+            raise RuntimeError('ProgrammeStream.push: the stream was closed by flush()')
+        return self._advance(*self._ingest.push(frames, wave), final=False)
+
+    def flush(self) -> List[OffsetUpdate]:
+        """End of the feed: what the ingest still held becomes final, every programme's tail is committed, the stream closes (a later push raises)."""
+        if self.closed:
+            raise RuntimeError('ProgrammeStream.flush: the stream is closed')
+        upds = self._advance(*self._ingest.flush(), final=True)
+        self.closed = True
+        return upds
+
+    def _advance(self, frames: torch.Tensor, waves: torch.Tensor, final: bool) -> List[OffsetUpdate]:
+        tr, eng, P = self.tracker, self.tracker.eng, self.P
+        self._accept(frames, waves, 'ProgrammeStream.push')
+        g = stream_geometry(self.n_frames, self.n_samples, self.n_segments, tr.hop)
+        (s0, s1), (w0, w1) = g['new_segments'], g['new_windows']
+        if s1 > s0:                                                              # the towers: the picture once, the audio once per programme
+            vf, af = eng.extract_segments_programmes_from(lambda f0, f1: self._frames[f0 - self._f0:f1 - self._f0], self._wave, tr.mel, s0, s1 - s0, self.seg_chunk,
+                                                          sample0=self._a0)
+            self._add_features(vf, af.transpose(0, 1))                           # held audio features: (segments, P, 6, 768), trimmed along the segments
+        if w1 > w0:
+            lo = tr.hop * w0 - self._s0
+            logits = eng.sync_windows_programmes(self._vfeat[lo:], self._afeat[lo:].transpose(0, 1), hop=tr.hop)
+            assert logits.shape[:2] == (P, w1 - w0), (logits.shape, w0, w1)
+        else:
+            logits = torch.empty(P, 0, eng.n_out, device=eng.dev, dtype=torch.float32)
+        slots = list(range(P))
+        outs = ops.track_pool_push(self.state, slots, logits.reshape(P * (w1 - w0), eng.n_out), [w1 - w0] * P, tr.lam, tr.grid if tr.posterior else None,
+                                   final=slots if final else ())
+        self._trim(g)
+        return [self._update(out, logits[p], w0, w1) for p, out in enumerate(outs)]
+
+
 class PoolFeed(_Feed):
     """One feed of an OffsetStreamPool (pool.open()): the handle push() is keyed by.  `held` / `held_bound` / the totals as an OffsetStream's."""
 
@@ -354,7 +456,11 @@ class OffsetStreamPool:
         self.feeds = {}                                                          # slot -> the open feed
 
     def open(self, ingest=None) -> PoolFeed:
-        """A new feed in a free slot (ingest: an ingest.RecordingIngest, as OffsetTracker.stream's); RuntimeError when every slot is taken."""
+        """A new feed in a free slot (ingest: an ingest.RecordingIngest, as OffsetTracker.stream's); RuntimeError when every slot is taken; ValueError for an ingest
+        with programmes."""
+        if getattr(ingest, 'programmes', None) is not None:
+            raise ValueError('OffsetStreamPool.open: an ingest with audio programmes is not served by a pool (one feed with several read-out slots is out of '
+                             'scope): use OffsetTracker.stream(ingest=...) for that feed')
         if not self._free:
             raise RuntimeError(f'OffsetStreamPool.open: all {self.n_feeds} slots are taken (flush a feed first)')
         slot = self._free.pop()

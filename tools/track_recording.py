@@ -5,6 +5,7 @@ beside the same windows through forward_clips on explicit 120-frame slices.  Pri
                                     [--pix-fmt {rgb24,nv12,yuv420p,p010,yuv420p10le,uyvy422,yuyv422,yuv422p,nv16,yuv422p10le,p210,y210}]
                                     [--chroma-loc {center,left,topleft}] [--field-order {progressive,tff,bff}] [--posterior]
                                     [--stream SECONDS [--lag N]]
+                                    [--audio-channels N [--audio-interleaved] [--sample-fmt {flt,s16,s32}] --programmes 0+1,2+3,4]
 
 With --fps / --size / --rate the recording is synthesised RAW at that geometry (channels-last uint8 frames, stereo int16 PCM, in device memory) and goes through
 the ingest stage: the line then also carries the ingest time alone (the same chunks the bank asks for, plus the wave) and the bank from raw
@@ -22,6 +23,13 @@ With --stream SECONDS the recording is also pushed through OffsetTracker.stream(
 --size / --rate are given): the line then carries, per push, the milliseconds of the bank (the towers on the segments the push completed), the windows (the sync
 transformer on the windows it completed) and the read-out (ops.track_stream_push) - each timed by wall clock between device synchronisations, which a
 production stream would not place - their sum over the recording against the offline track_total_s, and whether the streamed logits equal the offline ones.
+
+With --programmes (implies the raw path) the wave has --audio-channels channels, every channel a differently seeded synth.make_wave so that the
+programmes differ, planar (ch, n) or with --audio-interleaved (n, ch), as --sample-fmt flt (fp32), s16 or s32 (the s16 values << 16).  `0+1,2+3,4` are three
+programmes: two averaged pairs and a single channel.  The recording goes through OffsetTracker.track_raw_programmes - the picture once, the audio tower once per
+programme - and ONE JSON LINE PER PROGRAMME is printed: its channels, the time of the whole call and of P separate track_raw calls on the programme's channels
+alone, whether the programme's logits equal that separate call's, and its path.  With --stream the recording is also pushed through the ProgrammeStream and each
+line says whether the streamed logits equal the offline ones.  Nothing else of the tool runs in this mode.
 
 forward_clips is timed on at most --clip-windows windows (spread over the recording) and scaled to all W; both sides include the mel front-end and
 are timed by wall clock around a device synchronisation, after one warm-up pass each.  Synthetic weights and inputs: the numbers are throughput only."""
@@ -57,6 +65,10 @@ def main():
     ap.add_argument('--posterior', action='store_true', help='also read the windows out as marginals (forward-backward)')
     ap.add_argument('--stream', type=float, default=None, metavar='SECONDS', help='also push the recording through OffsetTracker.stream in pieces of this length')
     ap.add_argument('--lag', type=int, default=16, help='decision lag of the stream, in windows')
+    ap.add_argument('--programmes', default=None, help="audio programmes of the wave's channels, e.g. 0+1,2+3,4: one offset track per programme against one pass of the picture")
+    ap.add_argument('--audio-channels', type=int, default=None, help='channels of the raw wave (with --programmes; default: the highest channel named + 1)')
+    ap.add_argument('--audio-interleaved', action='store_true', help='the raw wave is (n, ch), as a feed delivers it (with --programmes)')
+    ap.add_argument('--sample-fmt', choices=['flt', 's16', 's32'], default='s16', help='sample type of the raw wave (with --programmes)')
     args = ap.parse_args()
     from synchformer_amd import ops, synth
     from synchformer_amd.engine import SynchformerEngine
@@ -64,6 +76,10 @@ def main():
     from synchformer_amd.ingest import PIX_FMTS_422, PIX_FMTS_422_16, PIX_FMTS_PACKED, RecordingIngest
     from synchformer_amd.track import OffsetTracker
     dev = torch.device('cuda:0')
+    if args.programmes is not None:
+        return programmes_main(args, dev)
+    if args.audio_channels is not None or args.audio_interleaved:
+        raise SystemExit('--audio-channels / --audio-interleaved describe the wave of --programmes')
     raw_mode = args.fps is not None or args.size is not None or args.rate is not None or args.pix_fmt is not None or args.field_order != 'progressive'
     ing = None
     if raw_mode:
@@ -163,6 +179,76 @@ def main():
         'forward_clips_windows_timed': k, 'forward_clips_s_scaled': round(t_clips_all, 3), 'speedup_vs_forward_clips': round(t_clips_all / (t_bank + t_win), 2),
         'max_abs_logit_diff_vs_forward_clips': round(err, 6), 'path_changes': int((track.cls_path[1:] != track.cls_path[:-1]).sum().item()),
         'raw_changes': int((track.cls_raw[1:] != track.cls_raw[:-1]).sum().item()), **extra}))
+
+
+def programmes_main(args, dev):
+    """--programmes: one recording, P audio programmes, one line per programme."""
+    from synchformer_amd import synth
+    from synchformer_amd.engine import SynchformerEngine
+    from synchformer_amd.frontend import MelFrontend
+    from synchformer_amd.ingest import PIX_FMTS_422, PIX_FMTS_422_16, PIX_FMTS_PACKED, RecordingIngest
+    from synchformer_amd.track import OffsetTracker
+    progs = [tuple(int(c) for c in part.split('+')) for part in args.programmes.split(',')]
+    progs = [p[0] if len(p) == 1 else p for p in progs]
+    ch = args.audio_channels or 1 + max(c for p in progs for c in ((p,) if isinstance(p, int) else p))
+    fps = tuple(int(v) for v in args.fps.split('/')) if args.fps and '/' in args.fps else float(args.fps or 25)
+    RH, RW = (int(v) for v in (args.size or '256x256').lower().split('x'))
+    pix_fmt = args.pix_fmt or 'rgb24'
+    geo = dict(channels_last=pix_fmt == 'rgb24', pix_fmt=pix_fmt, chroma_loc=args.chroma_loc, field_order=args.field_order)
+    ing = RecordingIngest(dev, fps, (RH, RW), args.rate or 16000, audio_channels=ch, audio_interleaved=args.audio_interleaved, programmes=progs, **geo)
+    plain = RecordingIngest(dev, fps, (RH, RW), args.rate or 16000, **geo)
+    deep = pix_fmt in ('p010', 'yuv420p10le') + PIX_FMTS_422_16
+    raw_shape = (RH, RW, 3) if pix_fmt == 'rgb24' else (RH, RW, 2) if pix_fmt in PIX_FMTS_PACKED else (2 * RH, RW) if pix_fmt in PIX_FMTS_422 else (RH * 3 // 2, RW)
+    T_raw, n_raw = int(args.seconds * ing.fps_in), int(args.seconds * ing.rate_in)
+    dgen = torch.Generator(device=dev).manual_seed(7)
+    if deep:
+        raw = torch.randint(-32768, 32768, (T_raw, *raw_shape), generator=dgen, dtype=torch.int16, device=dev).view(torch.uint16)
+    else:
+        raw = torch.randint(0, 256, (T_raw, *raw_shape), generator=dgen, dtype=torch.uint8, device=dev)
+    wave = torch.stack([synth.make_wave(1, 1, 100 + c, n=n_raw).reshape(n_raw) for c in range(ch)])      # every channel its own signal: the programmes differ
+    wave = wave / wave.abs().max()
+    pcm = (wave * 30000).round().to(torch.int16)
+    planar = wave if args.sample_fmt == 'flt' else pcm if args.sample_fmt == 's16' else pcm.to(torch.int32) << 16
+    single = planar if args.sample_fmt != 's32' else pcm                         # track_raw takes fp32 or int16: the same samples
+    raw_wave = planar.t().contiguous() if args.audio_interleaved else planar
+    if args.host:
+        raw, raw_wave, single = raw.cpu().pin_memory(), raw_wave.pin_memory(), single.pin_memory()
+    else:
+        raw_wave, single = raw_wave.to(dev), single.to(dev)
+    eng = SynchformerEngine(synth.make_state_dict(1337), dev, seg_chunk=args.seg_chunk)
+    tracker = OffsetTracker(eng, MelFrontend(dev), hop_segments=args.hop, posterior=args.posterior)
+
+    def timed(fn):
+        fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    t_all, tracks = timed(lambda: tracker.track_raw_programmes(raw, raw_wave, ing, win_chunk=args.win_chunk))
+    rows = [[p] if isinstance(p, int) else list(p) for p in progs]
+    t_sep, refs = timed(lambda: [tracker.track_raw(raw, single[r], plain, win_chunk=args.win_chunk) for r in rows])
+    streamed = None
+    if args.stream is not None:
+        stream = tracker.stream(lag=args.lag, ingest=ing)
+        ups, f, a, i, t = [], 0, 0, 1, 0 if args.audio_interleaved else 1
+        while f < raw.shape[0] or a < raw_wave.shape[t]:
+            f1, a1 = min(raw.shape[0], round(i * args.stream * float(ing.fps_in))), min(raw_wave.shape[t], round(i * args.stream * ing.rate_in))
+            ups.append(stream.push(raw[f:f1], raw_wave.narrow(t, a, a1 - a)))
+            f, a, i = f1, a1, i + 1
+        ups.append(stream.flush())
+        streamed = [torch.cat([u[p].logits for u in ups]) for p in range(len(progs))]
+    for p, (prog, tr, ref) in enumerate(zip(progs, tracks, refs)):
+        line = {'tool': 'track_recording', 'programme': p, 'channels': rows[p], 'programmes': len(progs), 'audio_channels': ch, 'sample_fmt': args.sample_fmt,
+                'audio_interleaved': bool(args.audio_interleaved), 'seconds': args.seconds, 'segments': tr.n_segments, 'windows': int(tr.logits.shape[0]),
+                'track_raw_programmes_s': round(t_all, 4), 'track_raw_per_programme_s': round(t_sep, 4), 'ratio': round(t_all / t_sep, 3),
+                'logits_equal_track_raw': bool(torch.equal(tr.logits, ref.logits)), 'max_abs_logit_diff_vs_track_raw': round((tr.logits - ref.logits).abs().max().item(), 6),
+                'path_changes': int((tr.cls_path[1:] != tr.cls_path[:-1]).sum().item()), 'offset_sec_path_first': round(tr.offset_sec_path[0].item(), 3)}
+        if streamed is not None:
+            line['stream'] = {'piece_s': args.stream, 'lag': args.lag, 'held_after': stream.held,
+                              'logits_equal_offline': bool(streamed[p].shape == tr.logits.shape and torch.equal(streamed[p], tr.logits))}
+        print(json.dumps(line))
 
 
 def stream_timing(args, tracker, eng, ops, source, track):
