@@ -15,6 +15,9 @@
 //                      per tile, mixed by a (P, ch) matrix into P fp32 rows in LDS, each row filtered by sf_resample_wave's rule - a kernel of its own.
 // All video kernels run ONE resize pipeline, ing_plane_pass, over 1-byte or 2-byte samples (BS): ingest_video_kernel once per workgroup (one channel), the YUV
 // kernels twice (luma, then U and V together); the launchers size its LDS with one formula, ing_geometry.
+// Host side: the six video entries are argument conversions onto two bodies - ing_rgb (sf_ingest_video, sf_ingest_video_fields) and ing_planes (the four YUV
+// entries) - which hold every check, the LDS sizing, the colour matrix and the kernel pick once.  The two 4:2:0 entries reach ing_planes in ING_LEGACY420 mode: it
+// keeps their messages, their GEN = 0 instantiations and the trailing kernel arguments they always passed.
 // All kernels bound every address they form by the sizes the launcher was given: a table with entries outside the source only changes the picture, never the
 // addresses (frame index, first-tap row / column and every tap are clamped or skipped).
 #include <initializer_list>
@@ -520,7 +523,7 @@ static bool ing_geometry(int W, int taps_y, int taps_x, int planes, int max_rows
   return g->R >= 4;
 }
 
-// The argument checks both launchers share (0, or -1 with sf_last_error set); out and W are looked at only when there is something to launch.
+// The argument checks all launchers share (0, or -1 with sf_last_error set); out and W are looked at only when there is something to launch.
 static int ing_check_args(const char* who, int T_out, std::initializer_list<int> taps, const void* out, int W) {
   SF_CHECK_ARG(T_out >= 0 && T_out <= 65535, "%s: T_out = %d output frames per launch (0 .. 65535: one grid dimension)", who, T_out);
   for (const int t : taps)
@@ -530,126 +533,95 @@ static int ing_check_args(const char* who, int T_out, std::initializer_list<int>
   return 0;
 }
 
+// SF_LAUNCH_CHECK under the name each entry has always reported a failed launch with (the macro takes __func__, which is now a shared body).
+static int ing_launched(const char* who) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { sf_set_error("%s: %s", who, hipGetErrorString(e)); return (int)e; }
+  return 0;
+}
+
+// What the table of an entry names: frames; the fields of an interlaced recording; or frames in the argument form of the two 4:2:0 entries, which
+// keep their own kernel instantiations, checks and messages.
+enum IngMode { ING_FRAMES, ING_FIELDS, ING_LEGACY420 };
+
+// The two RGB entries.  ING_FIELDS: table holds field indices, y_first / y_w are the tables of parity 0, y_first1 / y_w1 those of parity 1, bottom_first the field
+// order; otherwise those three are unused.
+static int ing_rgb(const char* who, IngMode mode, const uint8_t* raw, int64_t stride_frame, int64_t stride_channel, int64_t stride_row, int64_t stride_col, int n_src, int H,
+                   int W, const int32_t* table, const int32_t* y_first, const float* y_w, const int32_t* y_first1, const float* y_w1, int taps_y, const int32_t* x_first,
+                   const float* x_w, int taps_x, int bottom_first, uint8_t* out, int T_out, void* stream) {
+  const bool fields = mode == ING_FIELDS;
+  if (ing_check_args(who, T_out, {taps_y, taps_x}, out, W)) return -1;
+  SF_CHECK_ARG(n_src >= 1 && (!fields || n_src <= 0x3fffffff) && H >= 1 && W >= 1, "%s: source of %d frames %d x %d", who, n_src, H, W);
+  SF_CHECK_ARG(!fields || (H >= 2 && H % 2 == 0), "%s: H = %d (two fields take an even H of at least 2)", who, H);
+  SF_CHECK_ARG(stride_frame >= 0 && stride_channel >= 0 && stride_row >= 0 && stride_col >= 1, "%s: negative or zero byte stride", who);
+  SF_CHECK_ARG(!fields || bottom_first == 0 || bottom_first == 1, "%s: bottom_first = %d (0: top field first, 1: bottom field first)", who, bottom_first);
+  if (T_out == 0) return 0;
+  SF_CHECK_ARG(raw && table && y_first && y_w && (!fields || (y_first1 && y_w1)) && x_first && x_w && out, "%s: null pointer", who);
+  IngGeom g;                                                                    // fields: the field's tap count sizes the LDS
+  SF_CHECK_ARG(ing_geometry(W, taps_y, taps_x, 1, ING_MAX_ROWS, 1, &g), "%s: W = %d is too wide for four staged source rows in LDS at taps_x = %d", who, W, taps_x);
+  const dim3 grid(ING_OUT / ING_TY, 3, (unsigned)T_out);
+  if (fields)
+    hipLaunchKernelGGL(ingest_video_fields_kernel, grid, dim3(256), g.lds, (hipStream_t)stream, raw, stride_frame, stride_channel, stride_row, stride_col, n_src, H, W,
+                       table, y_first, y_w, y_first1, y_w1, taps_y, x_first, x_w, taps_x, out, g.R, g.RP, g.TW, bottom_first);
+  else
+    hipLaunchKernelGGL(ingest_video_kernel, grid, dim3(256), g.lds, (hipStream_t)stream, raw, stride_frame, stride_channel, stride_row, stride_col, n_src, H, W, table,
+                       y_first, y_w, taps_y, x_first, x_w, taps_x, out, g.R, g.RP, g.TW);
+  return ing_launched(who);
+}
+
 extern "C" int sf_ingest_video(const uint8_t* raw, int64_t stride_frame, int64_t stride_channel, int64_t stride_row, int64_t stride_col, int n_src, int H, int W,
                                const int32_t* frame_table, const int32_t* y_first, const float* y_w, int taps_y, const int32_t* x_first, const float* x_w,
                                int taps_x, uint8_t* out, int T_out, void* stream) {
-  if (ing_check_args("sf_ingest_video", T_out, {taps_y, taps_x}, out, W)) return -1;
-  SF_CHECK_ARG(n_src >= 1 && H >= 1 && W >= 1, "sf_ingest_video: source of %d frames %d x %d", n_src, H, W);
-  SF_CHECK_ARG(stride_frame >= 0 && stride_channel >= 0 && stride_row >= 0 && stride_col >= 1, "sf_ingest_video: negative or zero byte stride");
-  if (T_out == 0) return 0;
-  SF_CHECK_ARG(raw && frame_table && y_first && y_w && x_first && x_w && out, "sf_ingest_video: null pointer");
-  IngGeom g;
-  SF_CHECK_ARG(ing_geometry(W, taps_y, taps_x, 1, ING_MAX_ROWS, 1, &g), "sf_ingest_video: W = %d is too wide for four staged source rows in LDS at taps_x = %d", W,
-               taps_x);
-  hipLaunchKernelGGL(ingest_video_kernel, dim3(ING_OUT / ING_TY, 3, (unsigned)T_out), dim3(256), g.lds, (hipStream_t)stream, raw, stride_frame, stride_channel,
-                     stride_row, stride_col, n_src, H, W, frame_table, y_first, y_w, taps_y, x_first, x_w, taps_x, out, g.R, g.RP, g.TW);
-  SF_LAUNCH_CHECK();
-  return 0;
+  return ing_rgb("sf_ingest_video", ING_FRAMES, raw, stride_frame, stride_channel, stride_row, stride_col, n_src, H, W, frame_table, y_first, y_w, nullptr, nullptr, taps_y,
+                 x_first, x_w, taps_x, 0, out, T_out, stream);
 }
 
 extern "C" int sf_ingest_video_fields(const uint8_t* raw, int64_t stride_frame, int64_t stride_channel, int64_t stride_row, int64_t stride_col, int n_src, int H, int W,
                                       const int32_t* field_table, const int32_t* y_first0, const float* y_w0, const int32_t* y_first1, const float* y_w1, int taps_y,
                                       const int32_t* x_first, const float* x_w, int taps_x, int bottom_first, uint8_t* out, int T_out, void* stream) {
-  if (ing_check_args("sf_ingest_video_fields", T_out, {taps_y, taps_x}, out, W)) return -1;
-  SF_CHECK_ARG(n_src >= 1 && n_src <= 0x3fffffff && H >= 1 && W >= 1, "sf_ingest_video_fields: source of %d frames %d x %d", n_src, H, W);
-  SF_CHECK_ARG(H >= 2 && H % 2 == 0, "sf_ingest_video_fields: H = %d (two fields take an even H of at least 2)", H);
-  SF_CHECK_ARG(stride_frame >= 0 && stride_channel >= 0 && stride_row >= 0 && stride_col >= 1, "sf_ingest_video_fields: negative or zero byte stride");
-  SF_CHECK_ARG(bottom_first == 0 || bottom_first == 1, "sf_ingest_video_fields: bottom_first = %d (0: top field first, 1: bottom field first)", bottom_first);
-  if (T_out == 0) return 0;
-  SF_CHECK_ARG(raw && field_table && y_first0 && y_w0 && y_first1 && y_w1 && x_first && x_w && out, "sf_ingest_video_fields: null pointer");
-  IngGeom g;                                                                    // the field's tap count sizes the LDS
-  SF_CHECK_ARG(ing_geometry(W, taps_y, taps_x, 1, ING_MAX_ROWS, 1, &g), "sf_ingest_video_fields: W = %d is too wide for four staged source rows in LDS at taps_x = %d",
-               W, taps_x);
-  hipLaunchKernelGGL(ingest_video_fields_kernel, dim3(ING_OUT / ING_TY, 3, (unsigned)T_out), dim3(256), g.lds, (hipStream_t)stream, raw, stride_frame, stride_channel,
-                     stride_row, stride_col, n_src, H, W, field_table, y_first0, y_w0, y_first1, y_w1, taps_y, x_first, x_w, taps_x, out, g.R, g.RP, g.TW, bottom_first);
-  SF_LAUNCH_CHECK();
-  return 0;
+  return ing_rgb("sf_ingest_video_fields", ING_FIELDS, raw, stride_frame, stride_channel, stride_row, stride_col, n_src, H, W, field_table, y_first0, y_w0, y_first1, y_w1,
+                 taps_y, x_first, x_w, taps_x, bottom_first, out, T_out, stream);
 }
 
-extern "C" int sf_ingest_video_yuv(const uint8_t* raw, int64_t stride_frame, int64_t stride_row, int64_t u_off, int64_t v_off, int64_t stride_crow,
-                                   int64_t stride_ccol, int n_src, int H, int W, const int32_t* frame_table, const int32_t* y_first, const float* y_w, int taps_y,
-                                   const int32_t* x_first, const float* x_w, int taps_x, const int32_t* cy_first, const float* cy_w, int taps_cy,
-                                   const int32_t* cx_first, const float* cx_w, int taps_cx, const float* csc, uint8_t* out, int T_out, void* stream) {
-  if (ing_check_args("sf_ingest_video_yuv", T_out, {taps_y, taps_x, taps_cy, taps_cx}, out, W)) return -1;
-  SF_CHECK_ARG(n_src >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, "sf_ingest_video_yuv: source of %d frames %d x %d (4:2:0 takes even H and W)", n_src, H, W);
-  SF_CHECK_ARG(stride_frame >= 0 && stride_row >= 0 && u_off >= 0 && v_off >= 0 && stride_crow >= 0 && stride_ccol >= 1,
-               "sf_ingest_video_yuv: negative byte stride or offset, or a chroma column stride below 1");
-  if (T_out == 0) return 0;
-  SF_CHECK_ARG(raw && frame_table && y_first && y_w && x_first && x_w && cy_first && cy_w && cx_first && cx_w && csc && out, "sf_ingest_video_yuv: null pointer");
-  IngGeom gy, gc;                                                               // luma as sf_ingest_video; chroma: four rows of U and four of V per chunk
-  SF_CHECK_ARG(ing_geometry(W, taps_y, taps_x, 1, ING_MAX_ROWS, 1, &gy), "sf_ingest_video_yuv: W = %d is too wide for four staged source rows in LDS at taps_x = %d", W,
-               taps_x);
-  SF_CHECK_ARG(ing_geometry(W / 2, taps_cy, taps_cx, 2, 4, 1, &gc),
-               "sf_ingest_video_yuv: W = %d is too wide for four staged rows of both chroma planes in LDS at taps_cx = %d", W, taps_cx);
-  IngCsc k;
-  for (int i = 0; i < 9; ++i) k.m[i] = csc[i];
-  for (int i = 0; i < 3; ++i) k.o[i] = csc[9 + i];
-  auto launch = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, dim3(ING_OUT / ING_TY, (unsigned)T_out), dim3(256), gy.lds > gc.lds ? gy.lds : gc.lds, (hipStream_t)stream, raw, stride_frame,
-                       stride_row, u_off, v_off, stride_crow, stride_ccol, n_src, H, W, frame_table, y_first, y_w, taps_y, x_first, x_w, taps_x, cy_first, cy_w,
-                       taps_cy, cx_first, cx_w, taps_cx, k, out, gy.R, gy.RP, gy.TW, gc.RP, gc.TW, 0, (int64_t)0, (int64_t)1, H / 2, W / 2, 0, 0);
-  };
-  if (v_off == u_off + 1 && stride_ccol == 2)                                   // NV12: one fetch of the interleaved rows serves both planes
-    launch(ingest_video_yuv_kernel<1, 1>);
-  else
-    launch(ingest_video_yuv_kernel<0, 1>);
-  SF_LAUNCH_CHECK();
-  return 0;
+// ing_geometry for the luma pass and for the chroma pass (four rows of U and four of V per chunk) of a YUV workgroup: 0, or the pass that does not fit (1, 2).
+static int ing_geometry_yuv(int W, int Wc, int taps_y, int taps_x, int taps_cy, int taps_cx, int bs, int pf, IngGeom* gy, IngGeom* gc) {
+  if (!ing_geometry(W, taps_y, taps_x, 1, ING_MAX_ROWS, bs, gy, pf)) return 1;
+  return ing_geometry(Wc, taps_cy, taps_cx, 2, 4, bs, gc, pf) ? 0 : 2;
 }
 
-extern "C" int sf_ingest_video_yuv16(const uint16_t* raw, int64_t stride_frame, int64_t stride_row, int64_t u_off, int64_t v_off, int64_t stride_crow,
-                                     int64_t stride_ccol, int shift, int n_src, int H, int W, const int32_t* frame_table, const int32_t* y_first, const float* y_w,
-                                     int taps_y, const int32_t* x_first, const float* x_w, int taps_x, const int32_t* cy_first, const float* cy_w, int taps_cy,
-                                     const int32_t* cx_first, const float* cx_w, int taps_cx, const float* csc, uint8_t* out, int T_out, void* stream) {
-  if (ing_check_args("sf_ingest_video_yuv16", T_out, {taps_y, taps_x, taps_cy, taps_cx}, out, W)) return -1;
-  SF_CHECK_ARG(n_src >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, "sf_ingest_video_yuv16: source of %d frames %d x %d (4:2:0 takes even H and W)", n_src, H,
-               W);
-  SF_CHECK_ARG(stride_frame >= 0 && stride_row >= 0 && u_off >= 0 && v_off >= 0 && stride_crow >= 0 && stride_ccol >= 2,
-               "sf_ingest_video_yuv16: negative byte stride or offset, or a chroma column stride below 2 bytes");
-  SF_CHECK_ARG(((stride_frame | stride_row | u_off | v_off | stride_crow | stride_ccol) & 1) == 0,
-               "sf_ingest_video_yuv16: odd byte stride or offset (16-bit samples are 2-byte aligned)");
-  SF_CHECK_ARG(shift >= 0 && shift <= 6, "sf_ingest_video_yuv16: shift = %d (0 .. 6: ten bits of a 16-bit word)", shift);
-  if (T_out == 0) return 0;
-  SF_CHECK_ARG(raw && frame_table && y_first && y_w && x_first && x_w && cy_first && cy_w && cx_first && cx_w && csc && out, "sf_ingest_video_yuv16: null pointer");
-  SF_CHECK_ARG(((uintptr_t)raw & 1) == 0, "sf_ingest_video_yuv16: raw must be 2-byte aligned");
-  IngGeom gy, gc;
-  SF_CHECK_ARG(ing_geometry(W, taps_y, taps_x, 1, ING_MAX_ROWS, 2, &gy), "sf_ingest_video_yuv16: W = %d is too wide for four staged source rows in LDS at taps_x = %d",
-               W, taps_x);
-  SF_CHECK_ARG(ing_geometry(W / 2, taps_cy, taps_cx, 2, 4, 2, &gc),
-               "sf_ingest_video_yuv16: W = %d is too wide for four staged rows of both chroma planes in LDS at taps_cx = %d", W, taps_cx);
-  IngCsc k;
-  for (int i = 0; i < 9; ++i) k.m[i] = csc[i];
-  for (int i = 0; i < 3; ++i) k.o[i] = csc[9 + i];
-  int rc = 0;
-  auto launch = [&](auto kernel) {
-    if ((rc = sf_prepare_kernel((const void*)kernel, ING_LDS_BYTES16, "sf_ingest_video_yuv16")) != 0) return;
-    hipLaunchKernelGGL(kernel, dim3(ING_OUT / ING_TY, (unsigned)T_out), dim3(256), gy.lds > gc.lds ? gy.lds : gc.lds, (hipStream_t)stream, (const uint8_t*)raw,
-                       stride_frame, stride_row, u_off, v_off, stride_crow, stride_ccol, n_src, H, W, frame_table, y_first, y_w, taps_y, x_first, x_w, taps_x, cy_first,
-                       cy_w, taps_cy, cx_first, cx_w, taps_cx, k, out, gy.R, gy.RP, gy.TW, gc.RP, gc.TW, shift, (int64_t)0, (int64_t)2, H / 2, W / 2, 0, 0);
-  };
-  if (v_off == u_off + 2 && stride_ccol == 4)                                   // P010: one fetch of the interleaved rows serves both planes
-    launch(ingest_video_yuv_kernel<1, 2>);
-  else
-    launch(ingest_video_yuv_kernel<0, 2>);
-  if (rc) return rc;
-  SF_LAUNCH_CHECK();
-  return 0;
-}
+// The YUV kernels by [bytes per sample - 1][form]; form: 0 separate chroma planes, 1 interleaved U V, 2 packed - and for frames, before those three, the two forms of
+// the 4:2:0 entries (GEN = 0).
+using IngYuvKernel = decltype(&ingest_video_yuv_kernel<0, 1, 0>);
+using IngYuvFieldsKernel = decltype(&ingest_video_yuv_fields_kernel<0, 1, 1>);
+static const IngYuvKernel ing_yuv_kernels[2][5] = {
+    {ingest_video_yuv_kernel<0, 1, 0>, ingest_video_yuv_kernel<1, 1, 0>, ingest_video_yuv_kernel<0, 1, 1>, ingest_video_yuv_kernel<1, 1, 1>, ingest_video_yuv_kernel<2, 1, 2>},
+    {ingest_video_yuv_kernel<0, 2, 0>, ingest_video_yuv_kernel<1, 2, 0>, ingest_video_yuv_kernel<0, 2, 1>, ingest_video_yuv_kernel<1, 2, 1>, ingest_video_yuv_kernel<2, 2, 2>}};
+static const IngYuvFieldsKernel ing_yuv_fields_kernels[2][3] = {
+    {ingest_video_yuv_fields_kernel<0, 1, 1>, ingest_video_yuv_fields_kernel<1, 1, 1>, ingest_video_yuv_fields_kernel<2, 1, 2>},
+    {ingest_video_yuv_fields_kernel<0, 2, 1>, ingest_video_yuv_fields_kernel<1, 2, 1>, ingest_video_yuv_fields_kernel<2, 2, 2>}};
 
-// The two general entries.  fields: frame_table holds field indices, y_first / y_w / cy_first / cy_w are the tables of parity 0, y_first1 / y_w1 / cy_first1 / cy_w1
-// those of parity 1, bottom_first the field order; otherwise those five are unused.
-static int ing_planes(const char* who, bool fields, const void* raw, int bytes_per_sample, int64_t stride_frame, int64_t y_off, int64_t stride_row, int64_t stride_col,
+// The four YUV entries.  ING_FIELDS: frame_table holds field indices, y_first / y_w / cy_first / cy_w are the tables of parity 0, y_first1 / y_w1 / cy_first1 /
+// cy_w1 those of parity 1, bottom_first the field order; otherwise those five are unused.  ING_LEGACY420: the two 4:2:0 entries, whose arguments leave y_off = 0,
+// stride_col = one sample and chroma planes of H / 2 x W / 2 implied.
+static int ing_planes(const char* who, IngMode mode, const void* raw, int bytes_per_sample, int64_t stride_frame, int64_t y_off, int64_t stride_row, int64_t stride_col,
                       int64_t u_off, int64_t v_off, int64_t stride_crow, int64_t stride_ccol, int shift, int n_src, int H, int W, int Hc, int Wc,
                       const int32_t* frame_table, const int32_t* y_first, const float* y_w, const int32_t* y_first1, const float* y_w1, int taps_y,
                       const int32_t* x_first, const float* x_w, int taps_x, const int32_t* cy_first, const float* cy_w, const int32_t* cy_first1, const float* cy_w1,
                       int taps_cy, const int32_t* cx_first, const float* cx_w, int taps_cx, const float* csc, int bottom_first, uint8_t* out, int T_out, void* stream) {
+  const bool fields = mode == ING_FIELDS, legacy = mode == ING_LEGACY420;
   if (ing_check_args(who, T_out, {taps_y, taps_x, taps_cy, taps_cx}, out, W)) return -1;
   const int bs = bytes_per_sample;
   SF_CHECK_ARG(bs == 1 || bs == 2, "%s: bytes_per_sample = %d (1 or 2)", who, bs);
-  SF_CHECK_ARG(n_src >= 1 && H >= 1 && W >= 1, "%s: source of %d frames %d x %d", who, n_src, H, W);
+  if (legacy)
+    SF_CHECK_ARG(n_src >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, "%s: source of %d frames %d x %d (4:2:0 takes even H and W)", who, n_src, H, W);
+  else
+    SF_CHECK_ARG(n_src >= 1 && H >= 1 && W >= 1, "%s: source of %d frames %d x %d", who, n_src, H, W);
   SF_CHECK_ARG(Hc >= 1 && Hc <= H && Wc >= 1 && Wc <= W, "%s: chroma planes of %d x %d beside a luma plane of %d x %d (1 .. H by 1 .. W)", who, Hc, Wc, H, W);
-  SF_CHECK_ARG(stride_frame >= 0 && y_off >= 0 && stride_row >= 0 && u_off >= 0 && v_off >= 0 && stride_crow >= 0 && stride_col >= bs && stride_ccol >= bs,
-               "%s: negative byte stride or offset, or a column stride below the %d bytes of a sample", who, bs);
+  const bool strides_ok = stride_frame >= 0 && y_off >= 0 && stride_row >= 0 && u_off >= 0 && v_off >= 0 && stride_crow >= 0 && stride_col >= bs && stride_ccol >= bs;
+  if (legacy)
+    SF_CHECK_ARG(strides_ok, "%s: negative byte stride or offset, or a chroma column stride below %s", who, bs == 1 ? "1" : "2 bytes");
+  else
+    SF_CHECK_ARG(strides_ok, "%s: negative byte stride or offset, or a column stride below the %d bytes of a sample", who, bs);
   SF_CHECK_ARG(bs == 1 || ((stride_frame | y_off | stride_row | stride_col | u_off | v_off | stride_crow | stride_ccol) & 1) == 0,
                "%s: odd byte stride or offset (16-bit samples are 2-byte aligned)", who);
   SF_CHECK_ARG(shift >= 0 && shift <= 6, "%s: shift = %d (0 .. 6: ten bits of a 16-bit word)", who, shift);
@@ -663,61 +635,63 @@ static int ing_planes(const char* who, bool fields, const void* raw, int bytes_p
   SF_CHECK_ARG(raw && frame_table && y_first && y_w && x_first && x_w && cy_first && cy_w && cx_first && cx_w && csc && out, "%s: null pointer", who);
   SF_CHECK_ARG(!fields || (y_first1 && y_w1 && cy_first1 && cy_w1), "%s: null pointer", who);
   SF_CHECK_ARG(bs == 1 || ((uintptr_t)raw & 1) == 0, "%s: raw must be 2-byte aligned", who);
-  IngGeom gy, gc;                                                               // fields: the field's tap counts size the LDS
-  SF_CHECK_ARG(ing_geometry(W, taps_y, taps_x, 1, ING_MAX_ROWS, bs, &gy), "%s: W = %d is too wide for four staged source rows in LDS at taps_x = %d", who, W, taps_x);
-  SF_CHECK_ARG(ing_geometry(Wc, taps_cy, taps_cx, 2, 4, bs, &gc), "%s: Wc = %d is too wide for four staged rows of both chroma planes in LDS at taps_cx = %d", who, Wc,
-               taps_cx);
-  IngCsc k;
-  for (int i = 0; i < 9; ++i) k.m[i] = csc[i];
-  for (int i = 0; i < 3; ++i) k.o[i] = csc[9 + i];
   // packed 4:2:2: macropixels of 4 samples, Y0 and U in the first two, Y1 = Y0 + 2 samples, V = U + 2 samples, one row pitch, every byte of the W / 2 macropixels of a
   // row a sample of the frame - so whole macropixels may be fetched
   const int64_t m = y_off < u_off ? y_off : u_off;
   bool packed = stride_col == 2 * bs && stride_ccol == 4 * bs && v_off == u_off + 2 * bs && stride_crow == stride_row && Hc == H && W % 2 == 0 && Wc == W / 2 &&
-                      (y_off < u_off ? u_off - y_off : y_off - u_off) == bs;
-  const bool inter = v_off == u_off + bs && stride_ccol == 2 * bs;
-  if (packed && bs == 2) {                                                      // the packed 16-bit form stages half as much per chunk; rows too wide for that take the strided loads
-    IngGeom py, pc;
-    packed = ing_geometry(W, taps_y, taps_x, 1, ING_MAX_ROWS, 2, &py, ING_PF16 / 2) && ing_geometry(Wc, taps_cy, taps_cx, 2, 4, 2, &pc, ING_PF16 / 2);
-    if (packed) { gy = py; gc = pc; }
+                (y_off < u_off ? u_off - y_off : y_off - u_off) == bs;
+  const bool inter = v_off == u_off + bs && stride_ccol == 2 * bs;               // NV12, NV16, P010, P210: one fetch of the interleaved rows serves both planes
+  IngGeom gy, gc;                                                               // fields: the field's tap counts size the LDS
+  // the packed 16-bit form stages half as much per chunk; rows too wide for that take the strided loads.  A smaller staging budget never gives ing_geometry a larger
+  // R, so a layout that fits at half the budget fits at the whole one: the checks below have nothing to refuse then
+  if (packed && bs == 2) packed = ing_geometry_yuv(W, Wc, taps_y, taps_x, taps_cy, taps_cx, bs, ING_PF16 / 2, &gy, &gc) == 0;
+  if (!(packed && bs == 2)) {
+    const int wide = ing_geometry_yuv(W, Wc, taps_y, taps_x, taps_cy, taps_cx, bs, 0, &gy, &gc);
+    SF_CHECK_ARG(wide != 1, "%s: W = %d is too wide for four staged source rows in LDS at taps_x = %d", who, W, taps_x);
+    if (legacy)
+      SF_CHECK_ARG(wide != 2, "%s: W = %d is too wide for four staged rows of both chroma planes in LDS at taps_cx = %d", who, W, taps_cx);
+    else
+      SF_CHECK_ARG(wide != 2, "%s: Wc = %d is too wide for four staged rows of both chroma planes in LDS at taps_cx = %d", who, Wc, taps_cx);
   }
-  int rc = 0;
-  auto launch = [&](auto kernel) {
-    if (bs == 2 && (rc = sf_prepare_kernel((const void*)kernel, ING_LDS_BYTES16, who)) != 0) return;
-    hipLaunchKernelGGL(kernel, dim3(ING_OUT / ING_TY, (unsigned)T_out), dim3(256), gy.lds > gc.lds ? gy.lds : gc.lds, (hipStream_t)stream, (const uint8_t*)raw,
-                       stride_frame, stride_row, u_off, v_off, stride_crow, stride_ccol, n_src, H, W, frame_table, y_first, y_w, taps_y, x_first, x_w, taps_x, cy_first,
-                       cy_w, taps_cy, cx_first, cx_w, taps_cx, k, out, gy.R, gy.RP, gy.TW, gc.RP, gc.TW, shift, y_off, stride_col, Hc, Wc, (int)(y_off - m),
-                       (int)(u_off - m));
-  };
-  auto launch_fields = [&](auto kernel) {
-    if (bs == 2 && (rc = sf_prepare_kernel((const void*)kernel, ING_LDS_BYTES16, who)) != 0) return;
-    hipLaunchKernelGGL(kernel, dim3(ING_OUT / ING_TY, (unsigned)T_out), dim3(256), gy.lds > gc.lds ? gy.lds : gc.lds, (hipStream_t)stream, (const uint8_t*)raw,
-                       stride_frame, stride_row, u_off, v_off, stride_crow, stride_ccol, n_src, H, W, frame_table, y_first, y_w, y_first1, y_w1, taps_y, x_first, x_w,
-                       taps_x, cy_first, cy_w, cy_first1, cy_w1, taps_cy, cx_first, cx_w, taps_cx, k, out, gy.R, gy.RP, gy.TW, gc.RP, gc.TW, shift, y_off, stride_col, Wc,
-                       (int)(y_off - m), (int)(u_off - m), bottom_first);
-  };
-  if (fields) {
-    if (bs == 1) {
-      if (packed) launch_fields(ingest_video_yuv_fields_kernel<2, 1, 2>);
-      else if (inter) launch_fields(ingest_video_yuv_fields_kernel<1, 1, 1>);
-      else launch_fields(ingest_video_yuv_fields_kernel<0, 1, 1>);
-    } else {
-      if (packed) launch_fields(ingest_video_yuv_fields_kernel<2, 2, 2>);
-      else if (inter) launch_fields(ingest_video_yuv_fields_kernel<1, 2, 1>);
-      else launch_fields(ingest_video_yuv_fields_kernel<0, 2, 1>);
-    }
-  } else if (bs == 1) {
-    if (packed) launch(ingest_video_yuv_kernel<2, 1, 2>);
-    else if (inter) launch(ingest_video_yuv_kernel<1, 1, 1>);
-    else launch(ingest_video_yuv_kernel<0, 1, 1>);
-  } else {
-    if (packed) launch(ingest_video_yuv_kernel<2, 2, 2>);
-    else if (inter) launch(ingest_video_yuv_kernel<1, 2, 1>);
-    else launch(ingest_video_yuv_kernel<0, 2, 1>);
+  IngCsc k;
+  for (int i = 0; i < 9; ++i) k.m[i] = csc[i];
+  for (int i = 0; i < 3; ++i) k.o[i] = csc[9 + i];
+  const int form = packed ? 2 : inter ? 1 : 0, pky = legacy ? 0 : (int)(y_off - m), pkc = legacy ? 0 : (int)(u_off - m);
+  const IngYuvKernel frames_kernel = ing_yuv_kernels[bs - 1][legacy ? form : 2 + form];
+  const IngYuvFieldsKernel fields_kernel = ing_yuv_fields_kernels[bs - 1][form];
+  if (bs == 2) {                                                                // more LDS than a kernel gets unasked
+    const int rc = sf_prepare_kernel(fields ? (const void*)fields_kernel : (const void*)frames_kernel, ING_LDS_BYTES16, who);
+    if (rc) return rc;
   }
-  if (rc) return rc;
-  SF_LAUNCH_CHECK();
-  return 0;
+  const dim3 grid(ING_OUT / ING_TY, (unsigned)T_out);
+  const int lds = gy.lds > gc.lds ? gy.lds : gc.lds;
+  if (fields)
+    hipLaunchKernelGGL(fields_kernel, grid, dim3(256), lds, (hipStream_t)stream, (const uint8_t*)raw, stride_frame, stride_row, u_off, v_off, stride_crow, stride_ccol, n_src,
+                       H, W, frame_table, y_first, y_w, y_first1, y_w1, taps_y, x_first, x_w, taps_x, cy_first, cy_w, cy_first1, cy_w1, taps_cy, cx_first, cx_w, taps_cx, k,
+                       out, gy.R, gy.RP, gy.TW, gc.RP, gc.TW, shift, y_off, stride_col, Wc, pky, pkc, bottom_first);
+  else
+    hipLaunchKernelGGL(frames_kernel, grid, dim3(256), lds, (hipStream_t)stream, (const uint8_t*)raw, stride_frame, stride_row, u_off, v_off, stride_crow, stride_ccol, n_src,
+                       H, W, frame_table, y_first, y_w, taps_y, x_first, x_w, taps_x, cy_first, cy_w, taps_cy, cx_first, cx_w, taps_cx, k, out, gy.R, gy.RP, gy.TW, gc.RP,
+                       gc.TW, shift, y_off, stride_col, Hc, Wc, pky, pkc);
+  return ing_launched(legacy ? who : __func__);                                 // (the two general entries have always reported a failed launch under this body's name)
+}
+
+extern "C" int sf_ingest_video_yuv(const uint8_t* raw, int64_t stride_frame, int64_t stride_row, int64_t u_off, int64_t v_off, int64_t stride_crow,
+                                   int64_t stride_ccol, int n_src, int H, int W, const int32_t* frame_table, const int32_t* y_first, const float* y_w, int taps_y,
+                                   const int32_t* x_first, const float* x_w, int taps_x, const int32_t* cy_first, const float* cy_w, int taps_cy,
+                                   const int32_t* cx_first, const float* cx_w, int taps_cx, const float* csc, uint8_t* out, int T_out, void* stream) {
+  return ing_planes("sf_ingest_video_yuv", ING_LEGACY420, raw, 1, stride_frame, 0, stride_row, 1, u_off, v_off, stride_crow, stride_ccol, 0, n_src, H, W, H / 2, W / 2,
+                    frame_table, y_first, y_w, nullptr, nullptr, taps_y, x_first, x_w, taps_x, cy_first, cy_w, nullptr, nullptr, taps_cy, cx_first, cx_w, taps_cx, csc, 0, out,
+                    T_out, stream);
+}
+
+extern "C" int sf_ingest_video_yuv16(const uint16_t* raw, int64_t stride_frame, int64_t stride_row, int64_t u_off, int64_t v_off, int64_t stride_crow,
+                                     int64_t stride_ccol, int shift, int n_src, int H, int W, const int32_t* frame_table, const int32_t* y_first, const float* y_w,
+                                     int taps_y, const int32_t* x_first, const float* x_w, int taps_x, const int32_t* cy_first, const float* cy_w, int taps_cy,
+                                     const int32_t* cx_first, const float* cx_w, int taps_cx, const float* csc, uint8_t* out, int T_out, void* stream) {
+  return ing_planes("sf_ingest_video_yuv16", ING_LEGACY420, raw, 2, stride_frame, 0, stride_row, 2, u_off, v_off, stride_crow, stride_ccol, shift, n_src, H, W, H / 2, W / 2,
+                    frame_table, y_first, y_w, nullptr, nullptr, taps_y, x_first, x_w, taps_x, cy_first, cy_w, nullptr, nullptr, taps_cy, cx_first, cx_w, taps_cx, csc, 0, out,
+                    T_out, stream);
 }
 
 extern "C" int sf_ingest_video_yuv_planes(const void* raw, int bytes_per_sample, int64_t stride_frame, int64_t y_off, int64_t stride_row, int64_t stride_col,
@@ -725,9 +699,9 @@ extern "C" int sf_ingest_video_yuv_planes(const void* raw, int bytes_per_sample,
                                           const int32_t* frame_table, const int32_t* y_first, const float* y_w, int taps_y, const int32_t* x_first, const float* x_w,
                                           int taps_x, const int32_t* cy_first, const float* cy_w, int taps_cy, const int32_t* cx_first, const float* cx_w, int taps_cx,
                                           const float* csc, uint8_t* out, int T_out, void* stream) {
-  return ing_planes("sf_ingest_video_yuv_planes", false, raw, bytes_per_sample, stride_frame, y_off, stride_row, stride_col, u_off, v_off, stride_crow, stride_ccol, shift,
-                    n_src, H, W, Hc, Wc, frame_table, y_first, y_w, nullptr, nullptr, taps_y, x_first, x_w, taps_x, cy_first, cy_w, nullptr, nullptr, taps_cy, cx_first, cx_w,
-                    taps_cx, csc, 0, out, T_out, stream);
+  return ing_planes("sf_ingest_video_yuv_planes", ING_FRAMES, raw, bytes_per_sample, stride_frame, y_off, stride_row, stride_col, u_off, v_off, stride_crow, stride_ccol,
+                    shift, n_src, H, W, Hc, Wc, frame_table, y_first, y_w, nullptr, nullptr, taps_y, x_first, x_w, taps_x, cy_first, cy_w, nullptr, nullptr, taps_cy, cx_first,
+                    cx_w, taps_cx, csc, 0, out, T_out, stream);
 }
 
 extern "C" int sf_ingest_video_yuv_planes_fields(const void* raw, int bytes_per_sample, int64_t stride_frame, int64_t y_off, int64_t stride_row, int64_t stride_col,
@@ -736,9 +710,9 @@ extern "C" int sf_ingest_video_yuv_planes_fields(const void* raw, int bytes_per_
                                                  const float* y_w1, int taps_y, const int32_t* x_first, const float* x_w, int taps_x, const int32_t* cy_first0,
                                                  const float* cy_w0, const int32_t* cy_first1, const float* cy_w1, int taps_cy, const int32_t* cx_first,
                                                  const float* cx_w, int taps_cx, const float* csc, int bottom_first, uint8_t* out, int T_out, void* stream) {
-  return ing_planes("sf_ingest_video_yuv_planes_fields", true, raw, bytes_per_sample, stride_frame, y_off, stride_row, stride_col, u_off, v_off, stride_crow, stride_ccol,
-                    shift, n_src, H, W, Hc, Wc, field_table, y_first0, y_w0, y_first1, y_w1, taps_y, x_first, x_w, taps_x, cy_first0, cy_w0, cy_first1, cy_w1, taps_cy,
-                    cx_first, cx_w, taps_cx, csc, bottom_first, out, T_out, stream);
+  return ing_planes("sf_ingest_video_yuv_planes_fields", ING_FIELDS, raw, bytes_per_sample, stride_frame, y_off, stride_row, stride_col, u_off, v_off, stride_crow,
+                    stride_ccol, shift, n_src, H, W, Hc, Wc, field_table, y_first0, y_w0, y_first1, y_w1, taps_y, x_first, x_w, taps_x, cy_first0, cy_w0, cy_first1, cy_w1,
+                    taps_cy, cx_first, cx_w, taps_cx, csc, bottom_first, out, T_out, stream);
 }
 
 // ---- audio ---------------------------------------------------------------------------------------------------------------------------------------------------

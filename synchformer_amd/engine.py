@@ -779,72 +779,60 @@ class SynchformerEngine:
             raise ValueError(f'extract_recording: expected uint8 frames (T, 3, H, W) and a 1-D wave, got {frames.dtype} {tuple(frames.shape)} / {tuple(wave.shape)}')
         return self.extract_recording_from(lambda f0, f1: frames[f0:f1].to(self.dev, non_blocking=True), frames.shape[0], wave, mel, seg_chunk)
 
+    def _recording_segments(self, who: str, n_frames: int, n_samples: int, seg_chunk: Optional[int]):
+        """(the whole segments N that n_frames frames and n_samples samples hold, the segments per chunk); ValueError in `who`'s name below one window."""
+        from .frontend import recording_geometry
+        g = recording_geometry(n_frames, n_samples)
+        N = g['n_segments']
+        if N < g['n_window']:
+            raise ValueError(f"{who}: {n_frames} frames / {n_samples} samples hold {N} segments, one window needs {g['n_window']}")
+        chunk = self.seg_chunk if seg_chunk is None else int(seg_chunk)
+        if chunk < 1:
+            raise ValueError(f'{who}: seg_chunk = {chunk}')
+        return N, chunk
+
     def extract_recording_from(self, frame_fn, n_frames: int, wave16k: torch.Tensor, mel, seg_chunk: Optional[int] = None):
         """The chunk loop of extract_recording with the frames supplied by a callable: frame_fn(f0, f1) -> uint8 (f1 - f0, 3, 224, 224) on the device, the 25 fps
         frames [f0, f1) of a recording of `n_frames` (0 <= f0 < f1 <= n_frames; consecutive chunks overlap by 8 frames); wave16k (n,) fp32 16 kHz on the device or
         in host memory.  ingest.RecordingIngest.frames is such a callable for a recording at its native frame rate and size: the resized recording is
         never materialised, device memory holds one chunk of it."""
-        from .frontend import recording_geometry
         if wave16k.dim() != 1:
             raise ValueError(f'extract_recording: expected a 1-D wave, got {tuple(wave16k.shape)}')
-        wave = wave16k
-        g = recording_geometry(n_frames, wave.shape[0])
-        N = g['n_segments']
-        if N < g['n_window']:
-            raise ValueError(f"extract_recording: {n_frames} frames / {wave.shape[0]} samples hold {N} segments, one window needs {g['n_window']}")
-        chunk = self.seg_chunk if seg_chunk is None else int(seg_chunk)
-        if chunk < 1:
-            raise ValueError(f'extract_recording: seg_chunk = {chunk}')
-        return self.extract_segments_from(frame_fn, wave, mel, 0, N, chunk)
+        N, chunk = self._recording_segments('extract_recording', n_frames, wave16k.shape[0], seg_chunk)
+        return self.extract_segments_from(frame_fn, wave16k, mel, 0, N, chunk)
 
     def extract_segments_from(self, frame_fn, wave16k: torch.Tensor, mel, s_first: int, n_seg: int, seg_chunk: Optional[int] = None, sample0: int = 0):
         """Segments [s_first, s_first + n_seg) of the anchored grid through both towers, at most `seg_chunk` per launch group -> (vfeat (n_seg, 8, 768), afeat
         (n_seg, 6, 768)) fp32 on the device.  No minimum: a stream (track.OffsetStream) runs the few segments a push completes.  frame_fn(f0, f1) as in
         extract_recording_from, in frames of the recording; wave16k[k] is sample sample0 + k of the recording (a stream holds only the samples later segments read)."""
-        from .frontend import recording_geometry
         chunk = self.seg_chunk if seg_chunk is None else int(seg_chunk)
         if chunk < 1 or n_seg < 1 or s_first < 0:
             raise ValueError(f'extract_segments_from: seg_chunk = {chunk}, segments [{s_first}, {s_first + n_seg})')
-        g = recording_geometry(0, 0)
-        vs, vz, as_, az = g['v_stride'], g['v_size'], g['a_stride'], g['a_size']
-        vbank = abank = None
-        for s0 in range(s_first, s_first + n_seg, chunk):
-            n = min(chunk, s_first + n_seg - s0)
-            f = frame_fn(vs * s0, vs * (s0 + n - 1) + vz)
-            w = wave16k[as_ * s0 - sample0:as_ * (s0 + n - 1) + az - sample0].to(self.dev, torch.float32, non_blocking=True)
-            aud = mel.segments(w[None], 0, as_, n, az)
-            vf, af = self.both_towers(lambda: self.extract_vfeats_clips(f[None], 0, vs, n), aud)
-            if vbank is None:
-                vbank = torch.empty(n_seg, *vf.shape[2:], device=self.dev, dtype=torch.float32)
-                abank = torch.empty(n_seg, *af.shape[2:], device=self.dev, dtype=torch.float32)
-            vbank[s0 - s_first:s0 - s_first + n].copy_(vf[0])
-            abank[s0 - s_first:s0 - s_first + n].copy_(af[0])
-        return vbank, abank
+        vbank, abanks = self._extract_segments(frame_fn, wave16k[None], mel, s_first, n_seg, chunk, sample0)
+        return vbank, abanks[0]
 
     # several audio programmes against one picture (DESIGN 3.19): the visual tower - 96 % of the towers' work - runs once, the audio tower once per programme
     def extract_recording_programmes_from(self, frame_fn, n_frames: int, waves16k: torch.Tensor, mel, seg_chunk: Optional[int] = None):
         """extract_recording_from for P audio programmes of one recording: waves16k (P, n) fp32 16 kHz (ingest.RecordingIngest.waves), device or host ->
         (vbank (N, 8, 768), abanks (P, N, 6, 768)).  ValueError below one window."""
-        from .frontend import recording_geometry
         if waves16k.dim() != 2 or waves16k.shape[0] < 1:
             raise ValueError(f'extract_recording_programmes: expected waves (P, n), got {tuple(waves16k.shape)}')
-        g = recording_geometry(n_frames, waves16k.shape[1])
-        N = g['n_segments']
-        if N < g['n_window']:
-            raise ValueError(f"extract_recording_programmes: {n_frames} frames / {waves16k.shape[1]} samples hold {N} segments, one window needs {g['n_window']}")
-        chunk = self.seg_chunk if seg_chunk is None else int(seg_chunk)
-        if chunk < 1:
-            raise ValueError(f'extract_recording_programmes: seg_chunk = {chunk}')
+        N, chunk = self._recording_segments('extract_recording_programmes', n_frames, waves16k.shape[1], seg_chunk)
         return self.extract_segments_programmes_from(frame_fn, waves16k, mel, 0, N, chunk)
 
     def extract_segments_programmes_from(self, frame_fn, waves16k: torch.Tensor, mel, s_first: int, n_seg: int, seg_chunk: Optional[int] = None, sample0: int = 0):
         """extract_segments_from for P programmes: waves16k (P, n) -> (vfeat (n_seg, 8, 768), afeats (P, n_seg, 6, 768)).  Per chunk of at most seg_chunk segments the
         visual tower runs once, exactly as in extract_segments_from; the audio tower runs over the chunk's segments of all P programmes (programme-major) in groups
         of at most seg_chunk segments, so its workspaces do not grow with P: the first group beside the visual tower (both_towers), the rest after it."""
-        from .frontend import recording_geometry
         chunk = self.seg_chunk if seg_chunk is None else int(seg_chunk)
         if chunk < 1 or n_seg < 1 or s_first < 0 or waves16k.dim() != 2 or waves16k.shape[0] < 1:
             raise ValueError(f'extract_segments_programmes_from: seg_chunk = {chunk}, segments [{s_first}, {s_first + n_seg}), waves {tuple(waves16k.shape)}')
+        return self._extract_segments(frame_fn, waves16k, mel, s_first, n_seg, chunk, sample0)
+
+    def _extract_segments(self, frame_fn, waves16k: torch.Tensor, mel, s_first: int, n_seg: int, chunk: int, sample0: int):
+        """The segment loop of extract_segments_from and extract_segments_programmes_from, arguments checked: waves16k (P, n) -> (vfeat, afeats (P, n_seg, 6, 768)).
+        With one programme the only audio group is the one beside the visual tower: the work of the plain call, which hands out afeats[0]."""
+        from .frontend import recording_geometry
         g = recording_geometry(0, 0)
         vs, vz, as_, az = g['v_stride'], g['v_size'], g['a_stride'], g['a_size']
         P = waves16k.shape[0]
@@ -870,13 +858,25 @@ class SynchformerEngine:
         bank once; each programme's bank is projected and crosses the sync transformer through sync_windows' row maps."""
         if vbank.dim() != 3 or abanks.dim() != 4 or abanks.shape[0] < 1 or vbank.shape[0] != abanks.shape[1] or vbank.shape[2] != D or abanks.shape[3] != D:
             raise ValueError(f'sync_windows_programmes: expected banks (N, tv, {D}) / (P, N, ta, {D}), got {tuple(vbank.shape)} / {tuple(abanks.shape)}')
+        return self._sync_windows('sync_windows_programmes', vbank, abanks, hop, win_chunk, n_window)
+
+    def sync_windows(self, vbank: torch.Tensor, abank: torch.Tensor, hop: int = 1, win_chunk: int = 256, n_window: int = 14) -> torch.Tensor:
+        """Segment feature banks (N, tv, 768) / (N, ta, 768) fp32 on the device -> logits (W, n_out) of the W = (N - 14) // hop + 1 windows of 14 segments, window w =
+        segments [w hop, w hop + 14).  vproj / aproj run once over the whole bank; the sync transformer's input LayerNorms then read window w's 14 tv / 14 ta rows
+        through a row map whose sequence stride is hop tv / hop ta: the overlapping windows are never materialised.  `win_chunk` windows per pass bound the workspace."""
+        if vbank.dim() != 3 or abank.dim() != 3 or vbank.shape[0] != abank.shape[0] or vbank.shape[2] != D or abank.shape[2] != D:
+            raise ValueError(f'sync_windows: expected banks (N, tv, {D}) / (N, ta, {D}), got {tuple(vbank.shape)} / {tuple(abank.shape)}')
+        return self._sync_windows('sync_windows', vbank, abank[None], hop, win_chunk, n_window)[0]
+
+    def _sync_windows(self, who: str, vbank: torch.Tensor, abanks: torch.Tensor, hop: int, win_chunk: int, n_window: int) -> torch.Tensor:
+        """The window loop of sync_windows and sync_windows_programmes, bank shapes checked: abanks (P, N, ta, 768) -> logits (P, W, n_out)."""
         if hop < 1 or win_chunk < 1:
-            raise ValueError(f'sync_windows_programmes: hop = {hop}, win_chunk = {win_chunk}')
+            raise ValueError(f'{who}: hop = {hop}, win_chunk = {win_chunk}')
         P, N, tv, ta = abanks.shape[0], vbank.shape[0], vbank.shape[1], abanks.shape[2]
         if N < n_window:
-            raise ValueError(f'sync_windows_programmes: a bank of {N} segments holds no window of {n_window}')
+            raise ValueError(f'{who}: a bank of {N} segments holds no window of {n_window}')
         Sv, Sa = n_window * tv, n_window * ta
-        self._sync_table(Sv, Sa)
+        self._sync_table(Sv, Sa)                                                # ValueError when pos_emb is too short for one window
         W = (N - n_window) // hop + 1
         v2 = self.project(vbank.to(self.dev, torch.float32).unsqueeze(0), 'v')[0]
         logits = torch.empty(P, W, self.n_out, device=self.dev, dtype=torch.float32)
@@ -886,29 +886,6 @@ class SynchformerEngine:
                 nw = min(win_chunk, W - w0)
                 maps = (ops.rowmap(Sv, Sv, hop * tv, 0, 1, w0 * hop * tv), ops.rowmap(Sa, Sa, hop * ta, 0, 1, w0 * hop * ta))
                 logits[p, w0:w0 + nw].copy_(self._sync_stack(v2, a2, nw, Sv, Sa, src_maps=maps))
-        return logits
-
-    def sync_windows(self, vbank: torch.Tensor, abank: torch.Tensor, hop: int = 1, win_chunk: int = 256, n_window: int = 14) -> torch.Tensor:
-        """Segment feature banks (N, tv, 768) / (N, ta, 768) fp32 on the device -> logits (W, n_out) of the W = (N - 14) // hop + 1 windows of 14 segments, window w =
-        segments [w hop, w hop + 14).  vproj / aproj run once over the whole bank; the sync transformer's input LayerNorms then read window w's 14 tv / 14 ta rows
-        through a row map whose sequence stride is hop tv / hop ta: the overlapping windows are never materialised.  `win_chunk` windows per pass bound the workspace."""
-        if vbank.dim() != 3 or abank.dim() != 3 or vbank.shape[0] != abank.shape[0] or vbank.shape[2] != D or abank.shape[2] != D:
-            raise ValueError(f'sync_windows: expected banks (N, tv, {D}) / (N, ta, {D}), got {tuple(vbank.shape)} / {tuple(abank.shape)}')
-        if hop < 1 or win_chunk < 1:
-            raise ValueError(f'sync_windows: hop = {hop}, win_chunk = {win_chunk}')
-        N, tv, ta = vbank.shape[0], vbank.shape[1], abank.shape[1]
-        if N < n_window:
-            raise ValueError(f'sync_windows: a bank of {N} segments holds no window of {n_window}')
-        Sv, Sa = n_window * tv, n_window * ta
-        self._sync_table(Sv, Sa)                                                # ValueError when pos_emb is too short for one window
-        W = (N - n_window) // hop + 1
-        v2 = self.project(vbank.to(self.dev, torch.float32).unsqueeze(0), 'v')[0]
-        a2 = self.project(abank.to(self.dev, torch.float32).unsqueeze(0), 'a')[0]
-        logits = torch.empty(W, self.n_out, device=self.dev, dtype=torch.float32)
-        for w0 in range(0, W, win_chunk):
-            nw = min(win_chunk, W - w0)
-            maps = (ops.rowmap(Sv, Sv, hop * tv, 0, 1, w0 * hop * tv), ops.rowmap(Sa, Sa, hop * ta, 0, 1, w0 * hop * ta))
-            logits[w0:w0 + nw].copy_(self._sync_stack(v2, a2, nw, Sv, Sa, src_maps=maps))
         return logits
 
     def sync_transformer(self, vfeat: torch.Tensor, afeat: torch.Tensor) -> torch.Tensor:

@@ -448,20 +448,20 @@ class RecordingIngest:
     def _resize(self, src: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
         """Output frame j = source frame src[t[j]] (src on the device, t int32 on the host), resized and cropped; interlaced: field t[j] of src's 2 len(src) fields."""
         from . import ops
-        if self.interlaced:
-            bff = self.field_order == 'bff'
-            if self.pix_fmt == 'rgb24':
-                return ops.ingest_video_fields(src, self.channels_last, t.to(self.dev, non_blocking=True), self.y_tables, self.x_first, self.x_w, bff)
-            return ops.ingest_video_planes_fields(src, plane_layout(self.pix_fmt, self.H, self.W, src.stride()), t.to(self.dev, non_blocking=True), self.y_tables,
-                                                  self.x_first, self.x_w, self.y_tables, self.cx_first, self.cx_w, self.csc, bff)
-        if self.pix_fmt in PIX_FMTS_422:
-            return ops.ingest_video_planes(src, plane_layout(self.pix_fmt, self.H, self.W, src.stride()), t.to(self.dev, non_blocking=True), self.y_first, self.y_w,
-                                           self.x_first, self.x_w, self.cy_first, self.cy_w, self.cx_first, self.cx_w, self.csc)
-        if self.pix_fmt != 'rgb24':
-            op = ops.ingest_video_yuv16 if self.pix_fmt in PIX_FMTS_16 else ops.ingest_video_yuv
-            return op(src, self.pix_fmt, t.to(self.dev, non_blocking=True), self.y_first, self.y_w, self.x_first, self.x_w, self.cy_first, self.cy_w,
-                      self.cx_first, self.cx_w, self.csc)
-        return ops.ingest_video(src, self.channels_last, t.to(self.dev, non_blocking=True), self.y_first, self.y_w, self.x_first, self.x_w)
+        table, bff = t.to(self.dev, non_blocking=True), self.field_order == 'bff'
+        y, x = (self.y_first, self.y_w), (self.x_first, self.x_w)
+        if self.pix_fmt == 'rgb24':
+            if self.interlaced:
+                return ops.ingest_video_fields(src, self.channels_last, table, self.y_tables, *x, bff)
+            return ops.ingest_video(src, self.channels_last, table, *y, *x)
+        cy, cx = (self.cy_first, self.cy_w), (self.cx_first, self.cx_w)
+        if self.pix_fmt in PIX_FMTS_422:                                         # (the only YUV formats an interlaced ingest takes)
+            layout = plane_layout(self.pix_fmt, self.H, self.W, src.stride())
+            if self.interlaced:
+                return ops.ingest_video_planes_fields(src, layout, table, self.y_tables, *x, self.y_tables, *cx, self.csc, bff)
+            return ops.ingest_video_planes(src, layout, table, *y, *x, *cy, *cx, self.csc)
+        op = ops.ingest_video_yuv16 if self.pix_fmt in PIX_FMTS_16 else ops.ingest_video_yuv
+        return op(src, self.pix_fmt, table, *y, *x, *cy, *cx, self.csc)
 
     def wave(self, raw_wave: torch.Tensor) -> torch.Tensor:
         """raw_wave (n,) or (ch, n), fp32 or int16 PCM, device or host -> mono fp32 16 kHz (n16k,) on the device.  A mono fp32 wave at 16 kHz is returned as it is."""

@@ -904,12 +904,73 @@ def _ingest_out(out: Optional[torch.Tensor], T_out: int, device) -> torch.Tensor
     return out
 
 
-def _ingest_chunks(what: str, frame_table: torch.Tensor, out: torch.Tensor, launch):
-    """launch(frame_table pointer, out pointer, n) -> rc for every 65535 output frames: what one launch takes."""
+def _ingest_chunks(entry: str, head, frame_table: torch.Tensor, tail, out: Optional[torch.Tensor], device) -> torch.Tensor:
+    """The library's `entry`(*head, frame_table, *tail, out, n, stream) for every 65535 output frames: what one launch takes."""
     T_out = frame_table.numel()
+    out = _ingest_out(out, T_out, device)
     for t0 in range(0, max(T_out, 1), 65535):
-        _lib.check(launch(_dev(frame_table[t0:], 'frame_table'), _dev(out[t0:], 'out'), min(65535, T_out - t0)), what)
+        _lib.check(getattr(_lib.load(), entry)(*head, _dev(frame_table[t0:], 'frame_table'), *tail, _dev(out[t0:], 'out'), min(65535, T_out - t0), _stream()), entry)
     return out
+
+
+def _ingest_rgb_source(who: str, raw: torch.Tensor, channels_last: bool, fields: bool = False):
+    """The RGB frames of `who` -> the launcher's (frame, channel, row, column strides, n_src, H, W); fields: H has to hold two of them."""
+    if raw.dim() != 4 or raw.dtype != torch.uint8 or raw.shape[3 if channels_last else 1] != 3:
+        raise ValueError(f'{who}: expected uint8 frames (n, 3, H, W) or channels_last (n, H, W, 3), got {raw.dtype} {tuple(raw.shape)}')
+    (H, W), (sf, sc, sy, sx) = ((raw.shape[1], raw.shape[2]), (raw.stride(i) for i in (0, 3, 1, 2))) if channels_last else \
+        ((raw.shape[2], raw.shape[3]), raw.stride())
+    if fields and (H < 2 or H % 2):
+        raise ValueError(f'{who}: H = {H}: two fields take an even H')
+    assert min(sf, sc, sy) >= 0 and sx >= 1, f'{who}: negative strides'
+    return sf, sc, sy, sx, raw.shape[0], H, W
+
+
+def _ingest_420_source(who: str, raw: torch.Tensor, pix_fmt: str, semi: str, planar: str, dtypes):
+    """The 4:2:0 frames (n_src, 3 H / 2, W) of `who`, in its semi-planar format (H luma rows, then H / 2 rows of interleaved U V) or its planar one (I420 order) ->
+    the launcher's (frame stride, row stride, U offset, V offset, chroma row stride, chroma column stride) in BYTES, then (n_src, H, W)."""
+    b = dtypes[0].itemsize
+    if pix_fmt not in (semi, planar):
+        raise ValueError(f"{who}: pix_fmt = {pix_fmt!r} ('{semi}' or '{planar}')")
+    if raw.dim() != 3 or raw.dtype not in dtypes or raw.shape[1] % 3 or raw.shape[2] % 2 or raw.shape[1] == 0 or raw.shape[2] == 0:
+        raise ValueError(f'{who}: expected uint{8 * b} frames (n, 3 H / 2, W) with even H and W, got {raw.dtype} {tuple(raw.shape)}')
+    n_src, H, W = raw.shape[0], raw.shape[1] // 3 * 2, raw.shape[2]
+    sf, sy, sx = raw.stride()
+    if sx != 1 or sf < 0 or (sy != W if pix_fmt == planar else sy < W):
+        raise ValueError(f'{who}: {pix_fmt} frames with strides {tuple(raw.stride())}: unit column stride and '
+                         f'{"contiguous rows" if pix_fmt == planar else "a row stride of at least W"} expected')
+    u_off, v_off, csy, csx = (sy * H, sy * H + 1, sy, 2) if pix_fmt == semi else (H * W, H * W + (H // 2) * (W // 2), W // 2, 1)
+    return [b * v for v in (sf, sy, u_off, v_off, csy, csx)], (n_src, H, W)
+
+
+def _ingest_plane_source(who: str, raw: torch.Tensor, L, fields: bool = False):
+    """The frames of `who` against the ingest.PlaneLayout L (ValueError: a dtype that does not hold L.bytes_per_sample bytes, a plane that reaches outside the tensor;
+    fields: a layout that does not hold two of them) -> the launcher's arguments between raw and the table."""
+    if raw.dim() < 2 or raw.dtype not in ((torch.uint8,) if L.bytes_per_sample == 1 else (torch.uint16, torch.int16)):
+        raise ValueError(f'{who}: expected {"uint8" if L.bytes_per_sample == 1 else "uint16"} frames (n, ...) for samples of {L.bytes_per_sample} '
+                         f'byte(s), got {raw.dtype} {tuple(raw.shape)}')
+    n_src, b = raw.shape[0], L.bytes_per_sample
+    if min(L) < 0 or min(L.H, L.W, L.Hc, L.Wc) < 1 or min(L.stride_col, L.stride_ccol) < b:
+        raise ValueError(f'{who}: {L}: negative entries, an empty plane or a column stride below a sample')
+    if fields and (L.H % 2 or L.Hc != L.H):
+        raise ValueError(f'{who}: {L}: two fields take an even H and chroma planes of H rows (4:2:2, 4:4:4)')
+    # the last byte any plane reaches against the bytes the tensor spans from its first element (strides >= 0 for a frame tensor; a negative one is refused)
+    if any(s < 0 for s in raw.stride()):
+        raise ValueError(f'{who}: frames with strides {tuple(raw.stride())}')
+    span = (1 + sum((n - 1) * s for n, s in zip(raw.shape, raw.stride()))) * raw.element_size() if raw.numel() else 0
+    ends = [off + (h - 1) * sr + (w - 1) * sc + b for off, h, sr, w, sc in ((L.y_off, L.H, L.stride_row, L.W, L.stride_col),
+                                                                              (L.u_off, L.Hc, L.stride_crow, L.Wc, L.stride_ccol),
+                                                                              (L.v_off, L.Hc, L.stride_crow, L.Wc, L.stride_ccol))]
+    if n_src < 1 or (n_src - 1) * L.stride_frame + max(ends) > span:
+        raise ValueError(f'{who}: {L} reaches byte {(n_src - 1) * L.stride_frame + max(ends)} of {n_src} frames that span {span} bytes '
+                         f'({raw.dtype} {tuple(raw.shape)}, strides {tuple(raw.stride())})')
+    return (b, L.stride_frame, L.y_off, L.stride_row, L.stride_col, L.u_off, L.v_off, L.stride_crow, L.stride_ccol, L.shift, n_src, L.H, L.W, L.Hc, L.Wc)
+
+
+def _ingest_csc(who: str, csc):
+    """csc, a tensor or a sequence of 12 floats -> the float[12] the launchers read (their argument is its address: the caller holds it over the call)."""
+    csc = [float(v) for v in (csc.reshape(-1).tolist() if isinstance(csc, torch.Tensor) else csc)]
+    assert len(csc) == 12, f'{who}: csc is 9 matrix entries and 3 offsets'
+    return (C.c_float * 12)(*csc)
 
 
 def ingest_video(raw: torch.Tensor, channels_last: bool, frame_table: torch.Tensor, y_first: torch.Tensor, y_w: torch.Tensor, x_first: torch.Tensor,
@@ -917,15 +978,9 @@ def ingest_video(raw: torch.Tensor, channels_last: bool, frame_table: torch.Tens
     """Frame pick + antialiased resize + crop in one launch (sf_ingest_video): raw uint8 on the device, (n_src, 3, H, W) or - channels_last - (n_src, H, W, 3),
     any strides (a view is read in place); frame_table int32 (T_out,) of source frame indices inside [0, n_src); y_first / x_first int32 (224,) and
     y_w / x_w fp32 (224, taps) contiguous: the filter tables already sliced to the crop -> uint8 (T_out, 3, 224, 224)."""
-    if raw.dim() != 4 or raw.dtype != torch.uint8 or raw.shape[3 if channels_last else 1] != 3:
-        raise ValueError(f'ingest_video: expected uint8 frames (n, 3, H, W) or channels_last (n, H, W, 3), got {raw.dtype} {tuple(raw.shape)}')
-    n_src = raw.shape[0]
-    (H, W), (sf, sc, sy, sx) = ((raw.shape[1], raw.shape[2]), (raw.stride(i) for i in (0, 3, 1, 2))) if channels_last else \
-        ((raw.shape[2], raw.shape[3]), raw.stride())
-    assert min(sf, sc, sy) >= 0 and sx >= 1, 'ingest_video: negative strides'
-    src, tabs = _dev(raw, 'raw'), _ingest_tables(frame_table, y=(y_first, y_w), x=(x_first, x_w))
-    return _ingest_chunks('sf_ingest_video', frame_table, _ingest_out(out, frame_table.numel(), raw.device), lambda ft, o, n: _lib.load().sf_ingest_video(
-        src, sf, sc, sy, sx, n_src, H, W, ft, *tabs, o, n, _stream()))
+    geom = _ingest_rgb_source('ingest_video', raw, channels_last)
+    head, tabs = (_dev(raw, 'raw'), *geom), _ingest_tables(frame_table, y=(y_first, y_w), x=(x_first, x_w))
+    return _ingest_chunks('sf_ingest_video', head, frame_table, tabs, out, raw.device)
 
 
 def ingest_video_yuv(raw: torch.Tensor, pix_fmt: str, frame_table: torch.Tensor, y_first: torch.Tensor, y_w: torch.Tensor, x_first: torch.Tensor, x_w: torch.Tensor,
@@ -935,22 +990,10 @@ def ingest_video_yuv(raw: torch.Tensor, pix_fmt: str, frame_table: torch.Tensor,
     view into a pitched decoder surface is read in place) or 'yuv420p' (I420 as PyAV's to_ndarray gives it: H W luma bytes, then the U plane, then the V plane,
     H / 2 x W / 2 each; contiguous rows).  y_* / x_*: the luma tables of ingest_video; cy_* / cx_*: the chroma tables (H / 2 -> Hr, W / 2 -> Wr), sliced at the
     same crop origin; csc: 12 floats, the matrix row-major (rows R, G, B; columns Y, U, V) then the three offsets (ingest.csc_matrix) -> uint8 (T_out, 3, 224, 224)."""
-    if pix_fmt not in ('nv12', 'yuv420p'):
-        raise ValueError(f"ingest_video_yuv: pix_fmt = {pix_fmt!r} ('nv12' or 'yuv420p')")
-    if raw.dim() != 3 or raw.dtype != torch.uint8 or raw.shape[1] % 3 or raw.shape[2] % 2 or raw.shape[1] == 0 or raw.shape[2] == 0:
-        raise ValueError(f'ingest_video_yuv: expected uint8 frames (n, 3 H / 2, W) with even H and W, got {raw.dtype} {tuple(raw.shape)}')
-    n_src, H, W = raw.shape[0], raw.shape[1] // 3 * 2, raw.shape[2]
-    sf, sy, sx = raw.stride()
-    if sx != 1 or sf < 0 or (sy != W if pix_fmt == 'yuv420p' else sy < W):
-        raise ValueError(f'ingest_video_yuv: {pix_fmt} frames with strides {tuple(raw.stride())}: unit column stride and '
-                         f'{"contiguous rows" if pix_fmt == "yuv420p" else "a row stride of at least W"} expected')
-    u_off, v_off, csy, csx = (sy * H, sy * H + 1, sy, 2) if pix_fmt == 'nv12' else (H * W, H * W + (H // 2) * (W // 2), W // 2, 1)
-    csc = [float(v) for v in (csc.reshape(-1).tolist() if isinstance(csc, torch.Tensor) else csc)]
-    assert len(csc) == 12, 'ingest_video_yuv: csc is 9 matrix entries and 3 offsets'
-    csc_c = (C.c_float * 12)(*csc)
-    src, tabs = _dev(raw, 'raw'), _ingest_tables(frame_table, y=(y_first, y_w), x=(x_first, x_w), cy=(cy_first, cy_w), cx=(cx_first, cx_w))
-    return _ingest_chunks('sf_ingest_video_yuv', frame_table, _ingest_out(out, frame_table.numel(), raw.device), lambda ft, o, n: _lib.load().sf_ingest_video_yuv(
-        src, sf, sy, u_off, v_off, csy, csx, n_src, H, W, ft, *tabs, C.addressof(csc_c), o, n, _stream()))
+    strides, size = _ingest_420_source('ingest_video_yuv', raw, pix_fmt, 'nv12', 'yuv420p', (torch.uint8,))
+    csc_c = _ingest_csc('ingest_video_yuv', csc)
+    head, tabs = (_dev(raw, 'raw'), *strides, *size), _ingest_tables(frame_table, y=(y_first, y_w), x=(x_first, x_w), cy=(cy_first, cy_w), cx=(cx_first, cx_w))
+    return _ingest_chunks('sf_ingest_video_yuv', head, frame_table, (*tabs, C.addressof(csc_c)), out, raw.device)
 
 
 _YUV16_SHIFT = {'p010': 6, 'yuv420p10le': 0}
@@ -963,23 +1006,11 @@ def ingest_video_yuv16(raw: torch.Tensor, pix_fmt: str, frame_table: torch.Tenso
     elements, so a view into a pitched decoder surface is read in place) or 'yuv420p10le' (I420 order, the sample in the low 10 bits; contiguous rows).  The sample is
     (word >> shift) & 1023, so stray bits are dropped.  Tables as for ingest_video_yuv; csc: 12 floats on the 10-bit scale (ingest.csc_matrix(bit_depth=10)) ->
     uint8 (T_out, 3, 224, 224)."""
-    if pix_fmt not in _YUV16_SHIFT:
-        raise ValueError(f"ingest_video_yuv16: pix_fmt = {pix_fmt!r} ('p010' or 'yuv420p10le')")
-    if raw.dim() != 3 or raw.dtype not in (torch.uint16, torch.int16) or raw.shape[1] % 3 or raw.shape[2] % 2 or raw.shape[1] == 0 or raw.shape[2] == 0:
-        raise ValueError(f'ingest_video_yuv16: expected uint16 frames (n, 3 H / 2, W) with even H and W, got {raw.dtype} {tuple(raw.shape)}')
-    n_src, H, W = raw.shape[0], raw.shape[1] // 3 * 2, raw.shape[2]
-    sf, sy, sx = raw.stride()
-    if sx != 1 or sf < 0 or (sy != W if pix_fmt == 'yuv420p10le' else sy < W):
-        raise ValueError(f'ingest_video_yuv16: {pix_fmt} frames with strides {tuple(raw.stride())}: unit column stride and '
-                         f'{"contiguous rows" if pix_fmt == "yuv420p10le" else "a row stride of at least W"} expected')
-    # the launcher takes byte strides and offsets
-    u_off, v_off, csy, csx = (2 * sy * H, 2 * sy * H + 2, 2 * sy, 4) if pix_fmt == 'p010' else (2 * H * W, 2 * (H * W + (H // 2) * (W // 2)), W, 2)
-    csc = [float(v) for v in (csc.reshape(-1).tolist() if isinstance(csc, torch.Tensor) else csc)]
-    assert len(csc) == 12, 'ingest_video_yuv16: csc is 9 matrix entries and 3 offsets'
-    csc_c = (C.c_float * 12)(*csc)
-    src, tabs = _dev(raw, 'raw'), _ingest_tables(frame_table, y=(y_first, y_w), x=(x_first, x_w), cy=(cy_first, cy_w), cx=(cx_first, cx_w))
-    return _ingest_chunks('sf_ingest_video_yuv16', frame_table, _ingest_out(out, frame_table.numel(), raw.device), lambda ft, o, n: _lib.load().sf_ingest_video_yuv16(
-        src, 2 * sf, 2 * sy, u_off, v_off, csy, csx, _YUV16_SHIFT[pix_fmt], n_src, H, W, ft, *tabs, C.addressof(csc_c), o, n, _stream()))
+    strides, size = _ingest_420_source('ingest_video_yuv16', raw, pix_fmt, 'p010', 'yuv420p10le', (torch.uint16, torch.int16))
+    csc_c = _ingest_csc('ingest_video_yuv16', csc)
+    head = (_dev(raw, 'raw'), *strides, _YUV16_SHIFT[pix_fmt], *size)
+    tabs = _ingest_tables(frame_table, y=(y_first, y_w), x=(x_first, x_w), cy=(cy_first, cy_w), cx=(cx_first, cx_w))
+    return _ingest_chunks('sf_ingest_video_yuv16', head, frame_table, (*tabs, C.addressof(csc_c)), out, raw.device)
 
 
 def ingest_video_planes(raw: torch.Tensor, layout, frame_table: torch.Tensor, y_first: torch.Tensor, y_w: torch.Tensor, x_first: torch.Tensor, x_w: torch.Tensor,
@@ -989,31 +1020,10 @@ def ingest_video_planes(raw: torch.Tensor, layout, frame_table: torch.Tensor, y_
     chroma) saying in BYTES where the three planes of a frame lie and how many bytes a sample has.  y_* / x_*: the luma tables (H -> Hr, W -> Wr); cy_* / cx_*: the
     chroma tables (Hc -> Hr, Wc -> Wr), sliced at the same crop origin; csc: 12 floats on the samples' own scale -> uint8 (T_out, 3, 224, 224).  ValueError when the
     dtype does not hold layout.bytes_per_sample bytes or when a plane of the layout reaches outside the tensor; what the launcher refuses is a RuntimeError."""
-    L = layout
-    if raw.dim() < 2 or raw.dtype not in ((torch.uint8,) if L.bytes_per_sample == 1 else (torch.uint16, torch.int16)):
-        raise ValueError(f'ingest_video_planes: expected {"uint8" if L.bytes_per_sample == 1 else "uint16"} frames (n, ...) for samples of {L.bytes_per_sample} '
-                         f'byte(s), got {raw.dtype} {tuple(raw.shape)}')
-    n_src, b = raw.shape[0], L.bytes_per_sample
-    if min(L) < 0 or min(L.H, L.W, L.Hc, L.Wc) < 1 or min(L.stride_col, L.stride_ccol) < b:
-        raise ValueError(f'ingest_video_planes: {L}: negative entries, an empty plane or a column stride below a sample')
-    # the last byte any plane reaches against the bytes the tensor spans from its first element (strides >= 0 for a frame tensor; a negative one is refused)
-    if any(s < 0 for s in raw.stride()):
-        raise ValueError(f'ingest_video_planes: frames with strides {tuple(raw.stride())}')
-    span = (1 + sum((n - 1) * s for n, s in zip(raw.shape, raw.stride()))) * raw.element_size() if raw.numel() else 0
-    ends = [off + (h - 1) * sr + (w - 1) * sc + b for off, h, sr, w, sc in ((L.y_off, L.H, L.stride_row, L.W, L.stride_col),
-                                                                              (L.u_off, L.Hc, L.stride_crow, L.Wc, L.stride_ccol),
-                                                                              (L.v_off, L.Hc, L.stride_crow, L.Wc, L.stride_ccol))]
-    if n_src < 1 or (n_src - 1) * L.stride_frame + max(ends) > span:
-        raise ValueError(f'ingest_video_planes: {L} reaches byte {(n_src - 1) * L.stride_frame + max(ends)} of {n_src} frames that span {span} bytes '
-                         f'({raw.dtype} {tuple(raw.shape)}, strides {tuple(raw.stride())})')
-    csc = [float(v) for v in (csc.reshape(-1).tolist() if isinstance(csc, torch.Tensor) else csc)]
-    assert len(csc) == 12, 'ingest_video_planes: csc is 9 matrix entries and 3 offsets'
-    csc_c = (C.c_float * 12)(*csc)
-    src, tabs = _dev(raw, 'raw'), _ingest_tables(frame_table, y=(y_first, y_w), x=(x_first, x_w), cy=(cy_first, cy_w), cx=(cx_first, cx_w))
-    return _ingest_chunks('sf_ingest_video_yuv_planes', frame_table, _ingest_out(out, frame_table.numel(), raw.device),
-                          lambda ft, o, n: _lib.load().sf_ingest_video_yuv_planes(src, b, L.stride_frame, L.y_off, L.stride_row, L.stride_col, L.u_off, L.v_off,
-                                                                                  L.stride_crow, L.stride_ccol, L.shift, n_src, L.H, L.W, L.Hc, L.Wc, ft, *tabs,
-                                                                                  C.addressof(csc_c), o, n, _stream()))
+    geom = _ingest_plane_source('ingest_video_planes', raw, layout)
+    csc_c = _ingest_csc('ingest_video_planes', csc)
+    head, tabs = (_dev(raw, 'raw'), *geom), _ingest_tables(frame_table, y=(y_first, y_w), x=(x_first, x_w), cy=(cy_first, cy_w), cx=(cx_first, cx_w))
+    return _ingest_chunks('sf_ingest_video_yuv_planes', head, frame_table, (*tabs, C.addressof(csc_c)), out, raw.device)
 
 
 def _field_pairs(what: str, **pairs):
@@ -1039,19 +1049,11 @@ def ingest_video_fields(raw: torch.Tensor, channels_last: bool, field_table: tor
     inside [0, 2 n_src) - field f is rows p, p + 2, .. of frame f >> 1, p = (f & 1) ^ bottom_first; y_tables = ((first0, w0), (first1, w1)): the vertical tables of
     the fields of parity 0 and 1 (H / 2 rows -> Hr, shift 0.25 - p / 2, sliced to the crop), one tap count; x_first / x_w as for ingest_video -> uint8
     (T_out, 3, 224, 224): every output frame is one field, resized on its own."""
-    if raw.dim() != 4 or raw.dtype != torch.uint8 or raw.shape[3 if channels_last else 1] != 3:
-        raise ValueError(f'ingest_video_fields: expected uint8 frames (n, 3, H, W) or channels_last (n, H, W, 3), got {raw.dtype} {tuple(raw.shape)}')
-    n_src = raw.shape[0]
-    (H, W), (sf, sc, sy, sx) = ((raw.shape[1], raw.shape[2]), (raw.stride(i) for i in (0, 3, 1, 2))) if channels_last else \
-        ((raw.shape[2], raw.shape[3]), raw.stride())
-    if H < 2 or H % 2:
-        raise ValueError(f'ingest_video_fields: H = {H}: two fields take an even H')
-    assert min(sf, sc, sy) >= 0 and sx >= 1, 'ingest_video_fields: negative strides'
+    geom = _ingest_rgb_source('ingest_video_fields', raw, channels_last, fields=True)
     _field_pairs('ingest_video_fields', y=y_tables)
-    src = _dev(raw, 'raw')
-    ytabs, xtabs = _field_tables(field_table, y=y_tables), _ingest_tables(field_table, x=(x_first, x_w))
-    return _ingest_chunks('sf_ingest_video_fields', field_table, _ingest_out(out, field_table.numel(), raw.device),
-                          lambda ft, o, n: _lib.load().sf_ingest_video_fields(src, sf, sc, sy, sx, n_src, H, W, ft, *ytabs, *xtabs, int(bool(bottom_first)), o, n, _stream()))
+    head = (_dev(raw, 'raw'), *geom)
+    tabs = _field_tables(field_table, y=y_tables) + _ingest_tables(field_table, x=(x_first, x_w))
+    return _ingest_chunks('sf_ingest_video_fields', head, field_table, (*tabs, int(bool(bottom_first))), out, raw.device)
 
 
 def ingest_video_planes_fields(raw: torch.Tensor, layout, field_table: torch.Tensor, y_tables, x_first: torch.Tensor, x_w: torch.Tensor, cy_tables,
@@ -1059,36 +1061,14 @@ def ingest_video_planes_fields(raw: torch.Tensor, layout, field_table: torch.Ten
     """ingest_video_planes on an interlaced recording (sf_ingest_video_yuv_planes_fields): raw and layout as there, with layout.Hc == layout.H even (4:2:2,
     4:4:4: full vertical chroma resolution); field_table, y_tables and bottom_first as for ingest_video_fields; cy_tables: the chroma planes' pair of vertical tables
     (for 4:2:2 the luma pair); the horizontal tables and csc as for ingest_video_planes -> uint8 (T_out, 3, 224, 224)."""
-    L = layout
-    if raw.dim() < 2 or raw.dtype not in ((torch.uint8,) if L.bytes_per_sample == 1 else (torch.uint16, torch.int16)):
-        raise ValueError(f'ingest_video_planes_fields: expected {"uint8" if L.bytes_per_sample == 1 else "uint16"} frames (n, ...) for samples of {L.bytes_per_sample} '
-                         f'byte(s), got {raw.dtype} {tuple(raw.shape)}')
-    n_src, b = raw.shape[0], L.bytes_per_sample
-    if min(L) < 0 or min(L.H, L.W, L.Hc, L.Wc) < 1 or min(L.stride_col, L.stride_ccol) < b:
-        raise ValueError(f'ingest_video_planes_fields: {L}: negative entries, an empty plane or a column stride below a sample')
-    if L.H % 2 or L.Hc != L.H:
-        raise ValueError(f'ingest_video_planes_fields: {L}: two fields take an even H and chroma planes of H rows (4:2:2, 4:4:4)')
-    if any(s < 0 for s in raw.stride()):
-        raise ValueError(f'ingest_video_planes_fields: frames with strides {tuple(raw.stride())}')
-    span = (1 + sum((n - 1) * s for n, s in zip(raw.shape, raw.stride()))) * raw.element_size() if raw.numel() else 0
-    ends = [off + (h - 1) * sr + (w - 1) * sc + b for off, h, sr, w, sc in ((L.y_off, L.H, L.stride_row, L.W, L.stride_col),
-                                                                              (L.u_off, L.Hc, L.stride_crow, L.Wc, L.stride_ccol),
-                                                                              (L.v_off, L.Hc, L.stride_crow, L.Wc, L.stride_ccol))]
-    if n_src < 1 or (n_src - 1) * L.stride_frame + max(ends) > span:
-        raise ValueError(f'ingest_video_planes_fields: {L} reaches byte {(n_src - 1) * L.stride_frame + max(ends)} of {n_src} frames that span {span} bytes '
-                         f'({raw.dtype} {tuple(raw.shape)}, strides {tuple(raw.stride())})')
-    csc = [float(v) for v in (csc.reshape(-1).tolist() if isinstance(csc, torch.Tensor) else csc)]
-    assert len(csc) == 12, 'ingest_video_planes_fields: csc is 9 matrix entries and 3 offsets'
-    csc_c = (C.c_float * 12)(*csc)
+    geom = _ingest_plane_source('ingest_video_planes_fields', raw, layout, fields=True)
+    csc_c = _ingest_csc('ingest_video_planes_fields', csc)
     _field_pairs('ingest_video_planes_fields', y=y_tables, cy=cy_tables)
-    src = _dev(raw, 'raw')
+    head = (_dev(raw, 'raw'), *geom)
     ytabs, cytabs = _field_tables(field_table, y=y_tables), _field_tables(field_table, cy=cy_tables)
     xtabs, cxtabs = _ingest_tables(field_table, x=(x_first, x_w)), _ingest_tables(field_table, cx=(cx_first, cx_w))
-    return _ingest_chunks('sf_ingest_video_yuv_planes_fields', field_table, _ingest_out(out, field_table.numel(), raw.device),
-                          lambda ft, o, n: _lib.load().sf_ingest_video_yuv_planes_fields(src, b, L.stride_frame, L.y_off, L.stride_row, L.stride_col, L.u_off, L.v_off,
-                                                                                         L.stride_crow, L.stride_ccol, L.shift, n_src, L.H, L.W, L.Hc, L.Wc, ft, *ytabs,
-                                                                                         *xtabs, *cytabs, *cxtabs, C.addressof(csc_c), int(bool(bottom_first)), o, n,
-                                                                                         _stream()))
+    tail = (*ytabs, *xtabs, *cytabs, *cxtabs, C.addressof(csc_c), int(bool(bottom_first)))
+    return _ingest_chunks('sf_ingest_video_yuv_planes_fields', head, field_table, tail, out, raw.device)
 
 
 SF_I16 = 4

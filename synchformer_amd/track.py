@@ -296,7 +296,26 @@ class _Feed:
         return upd
 
 
-class OffsetStream(_Feed):
+class _Stream(_Feed):
+    """A feed with launches of its own: the bodies of push() and flush() around the subclass's _advance(frames, wave, final); `who` is the class named in the
+    messages.  (A PoolFeed has neither: its pool advances it.)"""
+
+    def _push(self, who: str, frames: torch.Tensor, wave: torch.Tensor):
+        if self.closed:
+            raise RuntimeError(f'{who}.push: the stream was closed by flush()')
+        if self._ingest is not None:
+            frames, wave = self._ingest.push(frames, wave)
+        return self._advance(frames, wave, final=False)
+
+    def _flush(self, who: str):
+        if self.closed:
+            raise RuntimeError(f'{who}.flush: the stream is closed')
+        upd = self._advance(*(self._empty_input() if self._ingest is None else self._ingest.flush()), final=True)
+        self.closed = True
+        return upd
+
+
+class OffsetStream(_Stream):
     """OffsetTracker.stream(): the recording path for a feed that does not end.  push() takes what arrived - uint8 frames (t, 3, 224, 224) at 25 fps and fp32
     samples (m,) at 16 kHz, device or host, either possibly empty, the two at their own pace (with `ingest`: as decoded) - runs the towers on the segments that
     became complete, the sync transformer on the windows that became complete (engine.sync_windows on the held features: 13 old segments and n new ones give
@@ -317,22 +336,11 @@ class OffsetStream(_Feed):
         return int(self.state.buf.numel())
 
     def push(self, frames: torch.Tensor, wave: torch.Tensor) -> OffsetUpdate:
-        if self.closed:
-            raise RuntimeError('OffsetStream.push: the stream was closed by flush()')
-        if self._ingest is not None:
-            frames, wave = self._ingest.push(frames, wave)
-        return self._advance(frames, wave, final=False)
+        return self._push('OffsetStream', frames, wave)
 
     def flush(self) -> OffsetUpdate:
         """End of the feed: whatever the ingest still held becomes final, the tail is committed from everything pushed, the stream closes (a later push raises)."""
-        if self.closed:
-            raise RuntimeError('OffsetStream.flush: the stream is closed')
-        frames, wave = self._empty_input()
-        if self._ingest is not None:
-            frames, wave = self._ingest.flush()
-        upd = self._advance(frames, wave, final=True)
-        self.closed = True
-        return upd
+        return self._flush('OffsetStream')
 
     def _advance(self, frames: torch.Tensor, wave: torch.Tensor, final: bool) -> OffsetUpdate:
         tr, eng = self.tracker, self.tracker.eng
@@ -353,7 +361,7 @@ class OffsetStream(_Feed):
         return self._update(out, logits, w0, w1)
 
 
-class ProgrammeStream(_Feed):
+class ProgrammeStream(_Stream):
     """OffsetTracker.stream(ingest=<an ingest with programmes>): OffsetStream for the P audio programmes of one feed.  push(raw_frames, raw_wave) and
     flush() return one OffsetUpdate per programme, in the order of ingest.programmes; each is what a plain OffsetStream fed that programme's channels returns,
     field for field (bit for bit on the un-fused tower schedule).  The picture is resized once and crosses the visual tower once per segment; the stream holds ONE
@@ -390,17 +398,11 @@ class ProgrammeStream(_Feed):
         return b
 
     def push(self, frames: torch.Tensor, wave: torch.Tensor) -> List[OffsetUpdate]:
-        if self.closed:
-            raise RuntimeError('ProgrammeStream.push: the stream was closed by flush()')
-        return self._advance(*self._ingest.push(frames, wave), final=False)
+        return self._push('ProgrammeStream', frames, wave)
 
     def flush(self) -> List[OffsetUpdate]:
         """End of the feed: what the ingest still held becomes final, every programme's tail is committed, the stream closes (a later push raises)."""
-        if self.closed:
-            raise RuntimeError('ProgrammeStream.flush: the stream is closed')
-        upds = self._advance(*self._ingest.flush(), final=True)
-        self.closed = True
-        return upds
+        return self._flush('ProgrammeStream')
 
     def _advance(self, frames: torch.Tensor, waves: torch.Tensor, final: bool) -> List[OffsetUpdate]:
         tr, eng, P = self.tracker, self.tracker.eng, self.P
