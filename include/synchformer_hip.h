@@ -29,7 +29,7 @@ extern "C" {
 enum { SF_F32 = 0, SF_BF16 = 1, SF_F16 = 2, SF_U8 = 3, SF_I16 = 4, SF_I32 = 5 };   /* element types (SF_I16: PCM input of sf_resample_wave / _mix only; SF_I32: of sf_resample_wave_mix only) */
 enum { SF_EPI_NONE = 0, SF_EPI_GELU = 1 };                  /* GEMM epilogue activation */
 
-#define SF_ABI_VERSION 23
+#define SF_ABI_VERSION 24
 int sf_abi_version(void);
 const char* sf_last_error(void);
 /* "gfx950" + build flags; lets the host assert it loaded the library it built */
@@ -592,6 +592,31 @@ int sf_track_pool_push(void* states, int64_t state_stride, int n_slots, int C, i
                        int n_active, const float* logits, int64_t ldl, int total_rows, float lam, const float* grid, int32_t* cls_raw, float* conf_raw,
                        int32_t* cls_lag, float* conf_lag, float* post_lag, int64_t ldp, int32_t* cls_post_lag, float* conf_post_lag, float* offset_mean_lag,
                        int32_t* cls_tail, float* conf_tail, float* log_z, void* workspace, void* stream);
+
+/* The two offline read-outs GATED by synchronizability (ABI v24).  A second, 2-way head (GlobalTransformerWithSyncabilityHead, sync_model.py:176-190;
+ * class 1 = synchronizable) reads the same windows: gate_logits (W, 2) fp32, row stride ldg >= 2, beside logits (W, C), row stride ldl >= C.  One chain over the 2C
+ * states j = m * C + c (c the offset class, m = 1 synchronizable) joins them:
+ *     d = z[w, 1] - z[w, 0];    ls = -softplus(-d);    lu = -softplus(d);    softplus(x) = max(x, 0) + log1p(exp(-|x|))                                  (fp32)
+ *     E[w, c, 1] = ls + l[w, c] - lse_c l[w, .];       E[w, c, 0] = lu - log C          (true log-probabilities: every row sums to 1 over the 2C states)
+ *     T((p, m') -> (c, m)) = -lam |p - c| - mu [m' != m]                                 lam, mu finite and >= 0
+ * A window judged not synchronizable is flat over the offset classes: the chain carries the class across it on the smoothness prior; mu is the flag's hysteresis; a
+ * caller's prior on the flag is a constant added to z[:, 1].  2 <= C <= 32 (one lane per state).
+ * sf_track_decode_gated: cls_raw / conf_raw as sf_track_decode gives them (from logits alone), sync_raw[w] = sigmoid(d), and the mode of the chain:
+ *     S_0 = E[0];   S_w[j] = E[w, j] + max_j' (S_{w-1}[j'] + T(j', j)), the LOWEST predecessor state j' on ties -> backptr[w, j] (one byte);   S_w -= max_j S_w[j];
+ *     end state = the lowest state of maximal S_{W-1};   cls_path = j % C, sync_path = j / C (int32) along the backtrace;   conf_path = the softmax probability of
+ *     cls_path in the offset row.  backptr: W * 2C bytes, caller-owned.  Three launches.
+ * sf_track_posterior_gated: the marginals of the same chain.  With a, b the scans of sf_track_posterior over the 2C states (E, T as above) and post2 = the normalised
+ * exp(a + b):
+ *     post[w, c] = post2[w, c, 0] + post2[w, c, 1]    (row stride ldp >= C; rows sum to 1);      p_sync[w] = sum_c post2[w, c, 1]    in [0, 1]
+ *     cls_post, conf_post, offset_mean from post and log_z[0] = lse_j a_{W-1}[j] <= 0 exactly as sf_track_posterior defines them
+ *     reversing the rows reverses post and p_sync and keeps log_z.  workspace: 4 * W * C floats (a, then b, (W, 2C) each), caller-owned.  Two launches.
+ * Both: -1 and a message, before anything is launched, for a bad C, stride, lam, mu or a null pointer; W == 0 launches nothing and needs no buffers.  The launchers read
+ * nothing back, allocate nothing and synchronise nothing.  Rows with non-finite values give unspecified results, every index inside [0, C) / {0, 1}.  Masked (-inf)
+ * classes are not served here. */
+int sf_track_decode_gated(const float* logits, int64_t ldl, const float* gate_logits, int64_t ldg, int W, int C, float lam, float mu, int32_t* cls_raw, float* conf_raw,
+                          float* sync_raw, int32_t* cls_path, int32_t* sync_path, float* conf_path, uint8_t* backptr, void* stream);
+int sf_track_posterior_gated(const float* logits, int64_t ldl, const float* gate_logits, int64_t ldg, int W, int C, float lam, float mu, const float* grid, float* post,
+                             int64_t ldp, float* p_sync, int32_t* cls_post, float* conf_post, float* offset_mean, float* log_z, float* workspace, void* stream);
 
 /* ---- Ingest of a decoded recording at its native frame rate, size and sample rate: the step the reference leaves to an ffmpeg subprocess in front of its code
  * (example.py:16-53: fps=25, short side 256, even dimensions, -ar 16000), plus the centre 224 crop of RGBSpatialCrop (dataset/transforms.py:68-95).  The host

@@ -40,6 +40,22 @@ def synchformer_state(ckpt: Mapping) -> Dict[str, torch.Tensor]:
     return _strip_module(sd)
 
 
+TOWER_PREFIXES = ('vfeat_extractor.', 'afeat_extractor.')
+
+
+def same_towers(sd_a: Mapping[str, torch.Tensor], sd_b: Mapping[str, torch.Tensor]) -> bool:
+    """True when two Synchformer state dicts hold the same feature extractors: the same `vfeat_extractor.` / `afeat_extractor.` keys (at least one) with equal
+    shapes, dtypes and values.  Host only.  THE check a caller makes before pairing two checkpoints on one segment feature bank - an offset model and a
+    syncability head as OffsetTracker(engine, mel, gate=...) pairs them: the syncability fine-tune keeps both extractors frozen
+    (configs/ft_synchability.yaml: is_trainable False), so its checkpoint carries the offset model's towers unchanged; a gate trained on other towers would read
+    features it has never seen, and nothing downstream could tell."""
+    ta = {k: v for k, v in sd_a.items() if k.startswith(TOWER_PREFIXES)}
+    tb = {k: v for k, v in sd_b.items() if k.startswith(TOWER_PREFIXES)}
+    if not ta or ta.keys() != tb.keys():
+        return False
+    return all(ta[k].shape == tb[k].shape and ta[k].dtype == tb[k].dtype and torch.equal(ta[k].detach().cpu(), tb[k].detach().cpu()) for k in ta)
+
+
 def stage1_tower_state(ckpt: Mapping, which: str) -> Dict[str, torch.Tensor]:
     """Keys of one tower out of a Stage-1 AVCLIP checkpoint: which = 'v_encoder' | 'a_encoder' (motionformer.py:156-163)."""
     sd = ckpt['state_dict'] if 'state_dict' in ckpt else ckpt

@@ -18,6 +18,7 @@
 //
 // sf_track_stream_push (further below) reads a stream of rows out at a fixed lag with carried state; sf_track_pool_push (at the end) does that for many streams
 // in one call: the same launches over a descriptor table, blockIdx.y = the stream, every block running the single-stream device functions on its stream's context.
+// sf_track_decode_gated / sf_track_posterior_gated (last) are the two offline read-outs of one chain over (offset class, synchronizable flag), fed by a second head.
 #include "sf_common.h"
 #include "../../include/synchformer_hip.h"
 #include <algorithm>
@@ -795,5 +796,256 @@ extern "C" int sf_track_pool_push(void* states, int64_t state_stride, int n_slot
                        (const unsigned char*)ws, total_rows);
     SF_LAUNCH_CHECK();
   }
+  return 0;
+}
+
+// ---- the read-outs gated by synchronizability (sf_track_decode_gated, sf_track_posterior_gated) ----------------------------------------------------
+// A second, 2-way head (class 1 = synchronizable) reads the same windows; one chain over the 2C states j = m * C + c (c the offset class, m the flag) joins the two:
+//     d = z[w, 1] - z[w, 0];   ls = -softplus(-d) = log sigmoid(d);   lu = -softplus(d);   softplus(x) = max(x, 0) + log1p(exp(-|x|))
+//     E[w, c, 1] = ls + l[w, c] - lse_c l[w, .];     E[w, c, 0] = lu - log C          (a true log-probability: every row sums to 1 over the 2C states)
+//     T((p, m') -> (c, m)) = -lam |p - c| - mu [m' != m]
+// A window judged not synchronizable says nothing about the offset (plane 0 is flat) and the chain carries the class across it on the smoothness prior.
+// One wavefront per scan as above, lane j = state j, lanes >= 2C idle with -inf.  A lane scans the C predecessors of its OWN plane and takes the other plane's best
+// (Viterbi) / lse (forward-backward) from its partner lane (m, c) <-> (1 - m, c), which has just computed exactly that: max_p (s[p, 1-m] - lam |p - c|) - mu.
+#define TRACK_GATE_MAX_C 32
+
+__device__ __forceinline__ float gate_softplus(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
+
+// What a lane of the gated scans is: its state's plane m and class c, its partner's lane.  Idle lanes (j >= 2C) act as state 0 and are their own partner.
+struct TrackGatedLane {
+  int j, m, c, partner;
+  bool live;
+  __device__ __forceinline__ TrackGatedLane(int C) {
+    j = threadIdx.x;
+    live = j < 2 * C;
+    m = (live && j >= C) ? 1 : 0;
+    c = live ? j - m * C : 0;
+    partner = live ? (m ? j - C : j + C) : j;
+  }
+};
+
+// E[w, c, m] of the lane's state, by the whole wavefront: l1 = the row's offset logit of class c in the lanes of plane 1 and -inf in every other lane, z0 / z1 the
+// row's gate logits (wave-uniform).  -inf in the idle lanes.
+__device__ __forceinline__ float track_gated_emission(const TrackGatedLane& ln, float l1, float z0, float z1, float log_c) {
+  const float d = z1 - z0;
+  const float e1 = fb_log_softmax(l1);
+  const float e = ln.m ? -gate_softplus(-d) + e1 : -gate_softplus(d) - log_c;
+  return ln.live ? e : -INFINITY;
+}
+
+// One thread per window: cls_raw / conf_raw as track_rows_kernel<false> gives them, sync_raw = sigmoid(z1 - z0).
+__global__ __launch_bounds__(256) void track_gated_rows_kernel(const float* __restrict__ logits, int64_t ldl, const float* __restrict__ gate, int64_t ldg, int W, int C,
+                                                                int32_t* __restrict__ cls_raw, float* __restrict__ conf_raw, float* __restrict__ sync_raw) {
+  const int w = blockIdx.x * 256 + threadIdx.x;
+  if (w >= W) return;
+  int best;
+  float m, sum;
+  track_row_stats(logits + (int64_t)w * ldl, C, best, m, sum);
+  cls_raw[w] = best;
+  conf_raw[w] = 1.0f / sum;
+  const float d = gate[(int64_t)w * ldg + 1] - gate[(int64_t)w * ldg];
+  sync_raw[w] = 1.0f / (1.0f + expf(-d));
+}
+
+// One wavefront, lane j = state j = m * C + c.   S_0 = E[0];   S_w[j] = E[w, j] + max_j' (S_{w-1}[j'] + T(j', j)), the LOWEST predecessor state on ties -> backptr[w, j]
+// (one byte);   S_w -= max_j S_w[j].  Inside a plane the lowest p wins (strict `>` in ascending p); between the planes m' = 0 wins: a lane of plane 0 takes the other
+// plane's candidate only when it is strictly larger, a lane of plane 1 also when it is equal.  (The partner picks its p BEFORE mu is subtracted, a scan over all 2C
+// predecessors would pick after: the two differ only where fp32 rounds two different candidates of the other plane to one value by subtracting mu - the partner then
+// keeps the truly larger one.  With exact arithmetic, e.g. dyadic inputs, they are the same rule.)  The end state is the lowest state whose score is the maximum; the
+// backtrace is track_viterbi_kernel's (eight rows of back pointers per load) and writes cls_path = j % C, sync_path = j / C.  NaN scores never win a comparison, and
+// the backtrace clamps what it reads: every byte and every index written lies in [0, 2C) / [0, C) / {0, 1}.
+__global__ __launch_bounds__(64) void track_gated_viterbi_kernel(const float* __restrict__ logits, int64_t ldl, const float* __restrict__ gate, int64_t ldg, int W, int C,
+                                                                  float lam, float mu, int32_t* __restrict__ cls_path, int32_t* __restrict__ sync_path,
+                                                                  uint8_t* __restrict__ backptr) {
+  __shared__ float s_prev[64];
+  const TrackGatedLane ln(C);
+  const int S = 2 * C;
+  const float ninf = -INFINITY;
+  const float log_c = logf((float)C);
+  const bool loads = ln.live && ln.m;                              // the lanes of plane 1 carry the offset logits
+  float s = track_gated_emission(ln, loads ? logits[ln.c] : ninf, gate[0], gate[1], log_c);
+  s -= wave_max(s);
+  s_prev[ln.j] = s;
+  __syncthreads();
+  float l_next = (loads && W > 1) ? logits[ldl + ln.c] : ninf;
+  float z0_next = W > 1 ? gate[ldg] : 0.f, z1_next = W > 1 ? gate[ldg + 1] : 0.f;
+  for (int w = 1; w < W; ++w) {
+    const float l = l_next, z0 = z0_next, z1 = z1_next;
+    if (w + 1 < W) {                                               // the next row's loads travel under this step's scan
+      l_next = loads ? logits[(int64_t)(w + 1) * ldl + ln.c] : ninf;
+      z0_next = gate[(int64_t)(w + 1) * ldg];
+      z1_next = gate[(int64_t)(w + 1) * ldg + 1];
+    }
+    const float e = track_gated_emission(ln, l, z0, z1, log_c);
+    const float* sp = s_prev + ln.m * C;                           // the lane's own plane
+    float best = sp[0] - lam * (float)ln.c;
+    int bp = 0;
+    for (int p = 1; p < C; ++p) {
+      const float cand = sp[p] - lam * fabsf((float)(p - ln.c));
+      if (cand > best) { best = cand; bp = p; }
+    }
+    const float other = __shfl(best, ln.partner, 64) - mu;         // max_p (S[p, 1 - m] - lam |p - c|) - mu, and the p that gave it
+    const int other_bp = __shfl(bp, ln.partner, 64);
+    const bool cross = ln.m ? other >= best : other > best;        // ties between the planes: m' = 0 wins
+    bp = cross ? (1 - ln.m) * C + other_bp : ln.m * C + bp;
+    s = ln.live ? (cross ? other : best) + e : ninf;
+    s -= wave_max(s);
+    if (ln.live) backptr[(int64_t)w * S + ln.j] = (uint8_t)bp;
+    __syncthreads();                                               // every lane has read s_prev
+    s_prev[ln.j] = s;
+    __syncthreads();
+  }
+  // (the barriers above order this wave's backptr stores before its loads below)
+  int cur = track_wave_end_state(s, ln.live);
+  for (int w0 = W - 1; w0 >= 1; w0 -= 8) {
+    int b[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) b[i] = (ln.live && w0 - i >= 1) ? (int)backptr[(int64_t)(w0 - i) * S + ln.j] : 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      if (w0 - i >= 1) {                                           // wave-uniform
+        if (ln.j == 0) { cls_path[w0 - i] = cur % C;  sync_path[w0 - i] = cur / C; }
+        const int p = __shfl(b[i], cur, 64);
+        cur = p < S ? p : S - 1;
+      }
+    }
+  }
+  if (ln.j == 0) { cls_path[0] = cur % C;  sync_path[0] = cur / C; }
+}
+
+static bool track_gated_args_ok(const char* who, int W, int C, int64_t ldl, int64_t ldg, float lam, float mu) {
+  if (W < 0) { sf_set_error("%s: W = %d windows", who, W); return false; }
+  if (C < 2 || C > TRACK_GATE_MAX_C) { sf_set_error("%s: C = %d classes out of range (2 .. %d: one lane per (class, flag) state)", who, C, TRACK_GATE_MAX_C); return false; }
+  if (ldl < C) { sf_set_error("%s: row stride ldl = %lld below C = %d", who, (long long)ldl, C); return false; }
+  if (ldg < 2) { sf_set_error("%s: gate row stride ldg = %lld below 2", who, (long long)ldg); return false; }
+  if (!(std::isfinite(lam) && lam >= 0.f)) { sf_set_error("%s: lam must be finite and >= 0 (the cost of a class change)", who); return false; }
+  if (!(std::isfinite(mu) && mu >= 0.f)) { sf_set_error("%s: mu must be finite and >= 0 (the cost of a change of the synchronizable flag)", who); return false; }
+  return true;
+}
+
+extern "C" int sf_track_decode_gated(const float* logits, int64_t ldl, const float* gate_logits, int64_t ldg, int W, int C, float lam, float mu, int32_t* cls_raw,
+                                     float* conf_raw, float* sync_raw, int32_t* cls_path, int32_t* sync_path, float* conf_path, uint8_t* backptr, void* stream) {
+  if (!track_gated_args_ok("sf_track_decode_gated", W, C, ldl, ldg, lam, mu)) return -1;
+  if (W == 0) return 0;
+  SF_CHECK_ARG(logits && gate_logits && cls_raw && conf_raw && sync_raw && cls_path && sync_path && conf_path && backptr, "sf_track_decode_gated: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)((W + 255) / 256));
+  hipLaunchKernelGGL(track_gated_rows_kernel, grid, dim3(256), 0, s, logits, ldl, gate_logits, ldg, W, C, cls_raw, conf_raw, sync_raw);
+  SF_LAUNCH_CHECK();
+  hipLaunchKernelGGL(track_gated_viterbi_kernel, dim3(1), dim3(64), 0, s, logits, ldl, gate_logits, ldg, W, C, lam, mu, cls_path, sync_path, backptr);
+  SF_LAUNCH_CHECK();
+  hipLaunchKernelGGL(track_rows_kernel<true>, grid, dim3(256), 0, s, logits, ldl, W, C, cls_path, conf_path);
+  SF_LAUNCH_CHECK();
+  return 0;
+}
+
+// The two scans of 3.14 over the 2C states: block 0 forward (a, and log_z), block 1 backward (b), one wavefront each.
+//     a_0 = E[0];        a_w[j] = E[w, j] + lse_j' (a_{w-1}[j'] + T(j', j));        b_{W-1} = 0;        b_w[j] = lse_n (b_{w+1}[n] + E[w+1, n] + T(j, n))
+// The vector the transition reads lies in LDS as two planes of 32 floats (entries >= C hold -inf, so fb_transition_lse's float4 reads stay aligned and add +0);
+// lse over the 2C predecessors = logaddexp(lse over the own plane, the partner's lse over its own plane - mu).  The maximum is subtracted after every step and, in the
+// forward block, summed in a double.  ws = a (W, 2C) then b (W, 2C), fp32, state-major rows j = m * C + c.
+__global__ __launch_bounds__(64) void track_gated_fb_scan_kernel(const float* __restrict__ logits, int64_t ldl, const float* __restrict__ gate, int64_t ldg, int W, int C,
+                                                                  float lam, float mu, float* __restrict__ ws, float* __restrict__ log_z) {
+  __shared__ __attribute__((aligned(16))) float s_u[64];
+  const TrackGatedLane ln(C);
+  const int S = 2 * C;
+  const bool back = blockIdx.x == 1;                              // wave-uniform
+  const int C4 = (C + 3) & ~3;
+  const float ninf = -INFINITY;
+  const float log_c = logf((float)C);
+  const bool loads = ln.live && ln.m;
+  const int slot = ln.m * 32 + ln.c;
+  float* out = ws + (back ? (int64_t)W * S : 0);
+  const int64_t row0 = back ? W - 1 : 0, step = back ? -1 : 1;     // scan position k reads row row0 + step * k
+  double shifted = 0.0;
+
+  s_u[threadIdx.x] = ninf;
+  __syncthreads();
+  float e = track_gated_emission(ln, loads ? logits[row0 * ldl + ln.c] : ninf, gate[row0 * ldg], gate[row0 * ldg + 1], log_c);
+  float v = back ? (ln.live ? 0.f : ninf) : e;
+  float m = fb_finite_or_zero(wave_max(v));
+  v -= m;
+  shifted += (double)m;
+  if (ln.live) {
+    out[row0 * S + ln.j] = v;
+    s_u[slot] = back ? v + e : v;
+  }
+  __syncthreads();
+  float l_next = (loads && W > 1) ? logits[(row0 + step) * ldl + ln.c] : ninf;
+  float z0_next = W > 1 ? gate[(row0 + step) * ldg] : 0.f, z1_next = W > 1 ? gate[(row0 + step) * ldg + 1] : 0.f;
+  for (int k = 1; k < W; ++k) {
+    const int64_t row = row0 + step * k;
+    const float l = l_next, z0 = z0_next, z1 = z1_next;
+    if (k + 1 < W) {
+      l_next = loads ? logits[(row + step) * ldl + ln.c] : ninf;
+      z0_next = gate[(row + step) * ldg];
+      z1_next = gate[(row + step) * ldg + 1];
+    }
+    e = track_gated_emission(ln, l, z0, z1, log_c);
+    const float own = fb_transition_lse(s_u + ln.m * 32, C4, ln.c, lam);
+    const float other = __shfl(own, ln.partner, 64) - mu;
+    const float mx = fb_finite_or_zero(fmaxf(own, other));
+    const float r = mx + logf(expf(own - mx) + expf(other - mx));
+    v = ln.live ? (back ? r : r + e) : ninf;
+    m = fb_finite_or_zero(wave_max(v));
+    v -= m;
+    shifted += (double)m;
+    if (ln.live) out[row * S + ln.j] = v;
+    __syncthreads();                                               // every lane has read s_u
+    if (ln.live) s_u[slot] = back ? v + e : v;
+    __syncthreads();
+  }
+  if (!back) {
+    const float z = logf(wave_sum(expf(v)));                       // the normalised a_{W-1}: maximum 0 (idle lanes add exp(-inf) = 0)
+    if (ln.j == 0) log_z[0] = (float)(shifted + (double)z);
+  }
+}
+
+// One thread per window:  s = a_w + b_w over the 2C states;  post2 = exp(s - lse_j s);  post[w, c] = post2[c, 0] + post2[c, 1];  p_sync[w] = sum_c post2[c, 1] (at most
+// 1);  cls_post = argmax_c post (first maximum wins; a NaN never wins `>`), conf_post its value;  offset_mean = sum_c post[w, c] grid[c] in ascending c.
+__global__ __launch_bounds__(256) void track_gated_fb_combine_kernel(const float* __restrict__ ws, int W, int C, const float* __restrict__ grid, float* __restrict__ post,
+                                                                      int64_t ldp, float* __restrict__ p_sync, int32_t* __restrict__ cls_post,
+                                                                      float* __restrict__ conf_post, float* __restrict__ offset_mean) {
+  const int w = blockIdx.x * 256 + threadIdx.x;
+  if (w >= W) return;
+  const int S = 2 * C;
+  const float* a = ws + (int64_t)w * S;
+  const float* b = a + (int64_t)W * S;
+  float* prow = post + (int64_t)w * ldp;
+  float m = -INFINITY;
+  for (int j = 0; j < S; ++j) m = fmaxf(m, a[j] + b[j]);
+  m = fb_finite_or_zero(m);
+  float sum = 0.f;
+  for (int j = 0; j < S; ++j) sum += expf(a[j] + b[j] - m);
+  const float lse = fb_finite_or_zero(m + logf(sum));
+  int best = 0;
+  float pbest = 0.f, mean = 0.f, ps = 0.f;
+  for (int c = 0; c < C; ++c) {
+    const float p1 = expf(a[C + c] + b[C + c] - lse);
+    const float p = expf(a[c] + b[c] - lse) + p1;
+    prow[c] = p;
+    ps += p1;
+    mean += p * grid[c];
+    if (c == 0 || p > pbest) { pbest = p; best = c; }
+  }
+  p_sync[w] = fminf(ps, 1.f);
+  cls_post[w] = best;
+  conf_post[w] = pbest;
+  offset_mean[w] = mean;
+}
+
+extern "C" int sf_track_posterior_gated(const float* logits, int64_t ldl, const float* gate_logits, int64_t ldg, int W, int C, float lam, float mu, const float* grid,
+                                        float* post, int64_t ldp, float* p_sync, int32_t* cls_post, float* conf_post, float* offset_mean, float* log_z,
+                                        float* workspace, void* stream) {
+  if (!track_gated_args_ok("sf_track_posterior_gated", W, C, ldl, ldg, lam, mu)) return -1;
+  SF_CHECK_ARG(ldp >= C, "sf_track_posterior_gated: post row stride ldp = %lld below C = %d", (long long)ldp, C);
+  if (W == 0) return 0;
+  SF_CHECK_ARG(logits && gate_logits && grid && post && p_sync && cls_post && conf_post && offset_mean && log_z && workspace, "sf_track_posterior_gated: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(track_gated_fb_scan_kernel, dim3(2), dim3(64), 0, s, logits, ldl, gate_logits, ldg, W, C, lam, mu, workspace, log_z);
+  SF_LAUNCH_CHECK();
+  hipLaunchKernelGGL(track_gated_fb_combine_kernel, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, s, (const float*)workspace, W, C, grid, post, ldp, p_sync, cls_post,
+                     conf_post, offset_mean);
+  SF_LAUNCH_CHECK();
   return 0;
 }

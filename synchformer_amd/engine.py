@@ -96,10 +96,16 @@ def agg_cls_operands(cls_token, g1, b1, w_in, b_in, w_o, b_o, heads: int = 12, e
 
 
 class SynchformerEngine:
-    def __init__(self, state_dict: Dict[str, torch.Tensor], device='cuda:0', seg_chunk: int = 224, fp8_towers: bool = False):
+    def __init__(self, state_dict: Dict[str, torch.Tensor], device='cuda:0', seg_chunk: int = 224, fp8_towers: bool = False, towers: bool = True):
         self.dev = torch.device(device)
         if self.dev.type != 'cuda':
             raise RuntimeError('SynchformerEngine needs a HIP device; there is no CPU path in the product')
+        # towers=False: a sync-module-only engine (vproj / aproj / sync transformer / head) - the state dict need not hold tower keys and the tower methods raise.  It
+        # reads segment features another engine's towers made: the 2-way syncability head is fine-tuned with both feature extractors frozen
+        # (configs/ft_synchability.yaml: is_trainable False), so it pairs with the offset model of the same towers (checkpoint.same_towers).
+        self.towers = bool(towers)
+        if fp8_towers and not self.towers:
+            raise ValueError('SynchformerEngine: fp8_towers asks for towers, towers=False loads none')
         self.seg_chunk = seg_chunk
         # fp8_towers: the six big Linears of every visual block run on MXFP8 operands (sf_gemm_mxfp8) - the frozen-extractor mode of the
         # synchronizability fine-tune (BASELINE configs[4]).  Off (bf16) for every other workload: inference parity bars are stated for bf16.
@@ -140,11 +146,18 @@ class SynchformerEngine:
     # weight preparation (one-off; not on the hot path)
     # ------------------------------------------------------------------------------------------------
     def load_weights(self, sd: Dict[str, torch.Tensor]):
-        self.load_tower_weights(sd)
+        if self.towers:
+            self.load_tower_weights(sd)
         self.load_sync_weights(sd)
+
+    def _need_towers(self, who: str):
+        if not self.towers:
+            raise RuntimeError(f'SynchformerEngine.{who}: this engine was built with towers=False (sync module only): it reads segment features, it cannot make them - '
+                               'run the towers on an engine that has them')
 
     def load_tower_weights(self, sd: Dict[str, torch.Tensor]):
         """The two feature extractors (214.8M parameters; frozen in Stage-2 training, train_utils.py:199-204)."""
+        self._need_towers('load_tower_weights')
         dev = self.dev
         f32 = lambda k: sd[k].detach().to(dev, torch.float32)
         lin = lambda k: _Lin(sd[k + '.weight'], sd[k + '.bias'], dev)
@@ -226,6 +239,8 @@ class SynchformerEngine:
         head = 'off_head' if f'{t}.off_head.weight' in sd else 'sync_head'
         self.s_head = lin(f'{t}.{head}')
         self.n_out = self.s_head.w.shape[0]
+        # the segments of one window: 2 + 14 n tokens fill the position table (198 -> 14: the offset model; 184 -> 13: the reference's syncability fine-tune)
+        self.n_window = (self.s_pos.shape[0] - 2) // 14
 
     def _agg(self, sd, p):
         """Aggregator layer (BaseEncoderLayer, motionformer.py:301-334): its attention is prepared once per weight load for sf_agg_cls_pool, see agg_cls_operands
@@ -299,6 +314,7 @@ class SynchformerEngine:
         """vid (n, 16, 3, 224, 224) u8|f16|bf16|f32 on device -> out fp32 (n*8, 768).  a3-a9 of SURVEY §8a.
         With clip_seg = (frame0, seg_stride, n_seg), vid is (clips, T, 3, 224, 224) and the segments are read in place; with clip_seg = (table, seg_stride, n_seg)
         (table an int32 device tensor of (frame0, y0, x0, flip) rows, one per clip) vid is uint8 (clips, T, 3, H, W) and every clip is cropped / flipped on the fly."""
+        self._need_towers('the visual tower')
         crops = clip_seg is not None and torch.is_tensor(clip_seg[0])
         n = vid.shape[0] if clip_seg is None else vid.shape[0] * clip_seg[2]
         rows = n * VIS_L
@@ -639,6 +655,7 @@ class SynchformerEngine:
     def extract_afeats(self, aud: torch.Tensor, aud_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """aud (B, S, 1, F=128, Ta=66) fp32 -> (B, S, 6, 768) fp32 (sync_model.py:82-89, ast.py:137-201).
         aud_mask: optional bool tensor shaped like aud, False = masked content (sync_model.py:85-86)."""
+        self._need_towers('extract_afeats')
         B, S, _, Fa, Ta = aud.shape
         n = B * S
         spec = aud.reshape(n, Fa, Ta).to(torch.float32)

@@ -699,6 +699,60 @@ def track_posterior(logits: torch.Tensor, lam: float, grid: torch.Tensor, post: 
     return post, cls_post, conf_post, offset_mean, log_z
 
 
+def _gated_inputs(logits: torch.Tensor, gate_logits: torch.Tensor):
+    """The shape checks the two gated read-outs share -> (W, C): logits fp32 (W, C), gate_logits fp32 (W, 2), same device, unit column stride, any row stride."""
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and gate_logits.dtype == torch.float32 and gate_logits.device == logits.device
+    W, C = logits.shape
+    assert gate_logits.shape == (W, 2), f'gate logits of {tuple(gate_logits.shape)} for {W} windows'
+    assert W == 0 or (logits.stride(1) == 1 and gate_logits.stride(1) == 1), 'logits, gate_logits: unit column stride'
+    return W, C
+
+
+def track_decode_gated(logits: torch.Tensor, gate_logits: torch.Tensor, lam: float, mu: float):
+    """Track read-out gated by synchronizability (sf_track_decode_gated): logits fp32 (W, C) of the offset head and gate_logits fp32 (W, 2) of the 2-way
+    syncability head (class 1 = synchronizable) for the same windows, on one device, rows in time order, unit column stride (a row stride above the width is passed
+    on), 2 <= C <= 32 -> (cls_raw int32, conf_raw fp32, sync_raw fp32, cls_path int32, sync_path int32, conf_path fp32), (W,) each: the per-window argmax and its
+    softmax probability as track_decode gives them, sigmoid(z1 - z0), and the Viterbi path of the chain over (offset class, synchronizable flag) under a cost `lam`
+    per class step and `mu` per change of the flag, with the softmax probability of the path's class.  Allocates the outputs and the W * 2C bytes of back pointers."""
+    W, C = _gated_inputs(logits, gate_logits)
+    dev = logits.device
+    i32 = lambda: torch.empty(W, device=dev, dtype=torch.int32)
+    f32 = lambda: torch.empty(W, device=dev, dtype=torch.float32)
+    cls_raw, cls_path, sync_path = i32(), i32(), i32()
+    conf_raw, sync_raw, conf_path = f32(), f32(), f32()
+    back = torch.empty(max(W, 1) * 2 * C, device=dev, dtype=torch.uint8)
+    rc = _lib.load().sf_track_decode_gated(_dev(logits, 'logits'), _ld(logits) if W else C, _dev(gate_logits, 'gate_logits'), _ld(gate_logits) if W else 2, W, C,
+                                           float(lam), float(mu), _dev(cls_raw, 'cls_raw'), _dev(conf_raw, 'conf_raw'), _dev(sync_raw, 'sync_raw'),
+                                           _dev(cls_path, 'cls_path'), _dev(sync_path, 'sync_path'), _dev(conf_path, 'conf_path'), _dev(back, 'backptr'), _stream())
+    _lib.check(rc, 'sf_track_decode_gated')
+    return cls_raw, conf_raw, sync_raw, cls_path, sync_path, conf_path
+
+
+def track_posterior_gated(logits: torch.Tensor, gate_logits: torch.Tensor, lam: float, mu: float, grid: torch.Tensor, post: Optional[torch.Tensor] = None):
+    """Posterior read-out gated by synchronizability (sf_track_posterior_gated): inputs as track_decode_gated, grid fp32 (C,) on the same device ->
+    (post fp32 (W, C), p_sync fp32 (W,), cls_post int32 (W,), conf_post fp32 (W,), offset_mean fp32 (W,), log_z fp32 (1,)): the marginals of the offset class under
+    the chain over (offset class, synchronizable flag), the marginal of the flag, and cls_post / conf_post / offset_mean / log_z from `post` as track_posterior
+    defines them.  Allocates the outputs and the 4 W C floats of workspace (`post`, if given, is written instead of a fresh tensor: fp32 (W, C) with unit column
+    stride, any row stride >= C); nothing is read back: log_z stays on the device (0 for W = 0)."""
+    W, C = _gated_inputs(logits, gate_logits)
+    assert grid.dtype == torch.float32 and grid.device == logits.device
+    assert grid.dim() == 1 and grid.numel() == C and grid.is_contiguous(), f'a grid of {tuple(grid.shape)} for {C} classes'
+    dev = logits.device
+    if post is None:
+        post = torch.empty(W, C, device=dev, dtype=torch.float32)
+    assert post.dtype == torch.float32 and post.shape == (W, C) and post.device == dev and (W == 0 or post.stride(1) == 1), 'post: fp32 (W, C), unit column stride'
+    cls_post = torch.empty(W, device=dev, dtype=torch.int32)
+    p_sync, conf_post, offset_mean = (torch.empty(W, device=dev, dtype=torch.float32) for _ in range(3))
+    log_z = torch.empty(1, device=dev, dtype=torch.float32) if W else torch.zeros(1, device=dev, dtype=torch.float32)
+    ws = torch.empty(4 * max(W, 1) * C, device=dev, dtype=torch.float32)
+    rc = _lib.load().sf_track_posterior_gated(_dev(logits, 'logits'), _ld(logits) if W else C, _dev(gate_logits, 'gate_logits'), _ld(gate_logits) if W else 2, W, C,
+                                              float(lam), float(mu), _dev(grid, 'grid'), _dev(post, 'post'), _ld(post) if W else C, _dev(p_sync, 'p_sync'),
+                                              _dev(cls_post, 'cls_post'), _dev(conf_post, 'conf_post'), _dev(offset_mean, 'offset_mean'), _dev(log_z, 'log_z'),
+                                              _dev(ws, 'workspace'), _stream())
+    _lib.check(rc, 'sf_track_posterior_gated')
+    return post, p_sync, cls_post, conf_post, offset_mean, log_z
+
+
 class TrackStreamState:
     """The carried state of one stream's fixed-lag read-out (sf_track_stream_push): `buf` the opaque device buffer, `rows` the rows pushed so far (host count),
     `closed` after a final push.  Its size does not depend on `rows`."""

@@ -14,6 +14,10 @@ confidence that carries the evidence of the whole recording, and an offset finer
     track = OffsetTracker(engine, mel, posterior=True).track(frames, wave)
     track.conf_post, track.offset_sec_mean        # how sure given every window, the posterior mean offset
 
+    gate = SynchformerEngine(syncability_sd, dev, towers=False)        # the 2-way syncability head of the same towers (checkpoint.same_towers)
+    track = OffsetTracker(engine, mel, gate=gate).track(frames, wave)  # the read-outs run over (offset class, synchronizable flag): silence, music beds and
+    track.sync_path, track.p_sync, track.spans()                       # cutaways are flagged instead of being read as an offset
+
     stream = tracker.stream(lag=16)               # a live feed: push what arrived, get the windows that became final
     upd = stream.push(frames_1s, wave_1s)         # upd.cls_lag / offset_sec_lag: committed, never revised; upd.offset_sec_tail[-1]: the offset now
     upd = stream.flush()                          # end of the feed: the tail is committed
@@ -73,6 +77,29 @@ class OffsetTrack:
     offset_sec_post: Optional[torch.Tensor] = None   # (W,) fp32: grid[cls_post]
     offset_sec_mean: Optional[torch.Tensor] = None   # (W,) fp32: sum_c post[w, c] grid[c]
     log_z: Optional[torch.Tensor] = None             # (1,) fp32: log partition sum against independent softmax draws, <= 0 (0: the windows agree)
+    # the gate (OffsetTracker(gate=...), ops.track_decode_gated / track_posterior_gated); None without it.  Optional attributes, set by the tracker and
+    # deliberately NOT dataclass fields: the field list and the positional constructor above stay what they were
+    gate_logits = None               # (W, 2) fp32: the syncability head on the windows' first gate.n_window segments, class 1 = synchronizable
+    sync_raw = None                  # (W,) fp32: sigmoid(z1 - z0), the gate's own per-window probability
+    sync_path = None                 # (W,) int32: the flag along the joint Viterbi path (cls_path is that path's class), 1 = synchronizable
+    p_sync = None                    # (W,) fp32: the flag's marginal given all windows (with posterior=True)
+
+    def spans(self):
+        """Host side: the runs of constant (sync_path, cls_path) as a list of (t0_sec, t1_sec, offset_sec or None), in time order - None where the path says 'not
+        synchronizable'.  Neighbouring spans meet half-way between their windows' centres; the first starts at t_sec[0], the last ends at t_sec[-1].  Without a
+        gate every window counts as synchronizable.  Synchronises (the path is copied to the host)."""
+        t = self.t_sec.detach().cpu().double().tolist()
+        cls = self.cls_path.detach().cpu().tolist()
+        off = self.offset_sec_path.detach().cpu().tolist()
+        sync = [1] * len(cls) if self.sync_path is None else self.sync_path.detach().cpu().tolist()
+        out, a = [], 0
+        for w in range(1, len(cls) + 1):
+            if w == len(cls) or (sync[w], cls[w]) != (sync[a], cls[a]):
+                t0 = t[a] if a == 0 else 0.5 * (t[a - 1] + t[a])
+                t1 = t[w - 1] if w == len(cls) else 0.5 * (t[w - 1] + t[w])
+                out.append((t0, t1, float(off[a]) if sync[a] else None))
+                a = w
+        return out
 
 
 class OffsetTracker:
@@ -81,9 +108,16 @@ class OffsetTracker:
     whole recording).  lam = 1.0 is a DEFAULT, NOT A TUNED VALUE: nobody has measured it on real recordings (no trained checkpoint ships with this
     repository) - choose it on held-out recordings of the domain.  grid: the offsets (seconds) the classes stand for, default class_grid(-2, 2, 21); its
     length must be the engine's n_out (an engine with the 2-way syncability head takes a 2-element grid, e.g. torch.tensor([0., 1.])).  posterior: also
-    read the windows out as marginals under the same lam (two more launches; fills OffsetTrack.post .. log_z)."""
+    read the windows out as marginals under the same lam (two more launches; fills OffsetTrack.post .. log_z).
+    gate: an engine with the 2-way syncability head (n_out == 2, class 1 = synchronizable; SynchformerEngine(sd, dev, towers=False) suffices) on the
+    same device, of the SAME towers as `engine` (checkpoint.same_towers - nothing here can check it).  Gate window w is segments [w hop, w hop + gate.n_window) of
+    the same banks, start-aligned with offset window w; cls_path, conf_path, offset_sec_path and the posterior fields then come from the chain over (offset class,
+    synchronizable flag), and gate_logits, sync_raw, sync_path, p_sync are filled.  mu: the cost of one change of the flag between neighbouring windows, in logit
+    units.  mu = 2.0 is a DEFAULT, NOT A TUNED VALUE, as lam: choose both on held-out recordings of the domain.  A prior on the flag is a constant added to
+    gate_logits[:, 1] by the caller.  stream() and pool() do not take a gate yet."""
 
-    def __init__(self, engine, mel, hop_segments: int = 1, lam: float = 1.0, grid: Optional[torch.Tensor] = None, posterior: bool = False):
+    def __init__(self, engine, mel, hop_segments: int = 1, lam: float = 1.0, grid: Optional[torch.Tensor] = None, posterior: bool = False, gate=None,
+                 mu: float = 2.0):
         if hop_segments < 1:
             raise ValueError(f'hop_segments = {hop_segments}')
         if not (lam >= 0 and lam != float('inf')):
@@ -94,19 +128,44 @@ class OffsetTracker:
         self.eng, self.mel, self.hop, self.lam = engine, mel, int(hop_segments), float(lam)
         self.grid = grid.to(engine.dev)
         self.posterior = bool(posterior)
+        if not (mu >= 0 and mu != float('inf')):
+            raise ValueError(f'mu = {mu}: the cost of a change of the synchronizable flag is finite and >= 0')
+        if gate is not None:
+            if gate.n_out != 2:
+                raise ValueError(f'gate: an engine with {gate.n_out} outputs, the syncability head has 2 (class 1 = synchronizable)')
+            if torch.device(gate.dev) != torch.device(engine.dev):
+                raise ValueError(f'gate: on {gate.dev}, the engine on {engine.dev}')
+            if engine.n_out > 32:
+                raise ValueError(f'gate: the gated read-outs serve at most 32 classes, the engine has {engine.n_out}')
+            if not 1 <= gate.n_window <= engine.n_window:
+                raise ValueError(f'gate: its window of {gate.n_window} segments does not fit the offset window of {engine.n_window} it is start-aligned with')
+        self.gate, self.mu = gate, float(mu)
 
     def track_features(self, vbank: torch.Tensor, abank: torch.Tensor, win_chunk: int = 256) -> OffsetTrack:
         """Segment feature banks (N, 8, 768) / (N, 6, 768) (engine.extract_recording, or features the caller already holds) -> OffsetTrack."""
-        return self._track_of(self.eng.sync_windows(vbank, abank, hop=self.hop, win_chunk=win_chunk), int(vbank.shape[0]))
+        logits = self.eng.sync_windows(vbank, abank, hop=self.hop, win_chunk=win_chunk)
+        gate_logits = None
+        if self.gate is not None:                                                # the same banks, start-aligned windows of the gate's own length: exactly W rows
+            gate_logits = self.gate.sync_windows(vbank, abank, hop=self.hop, win_chunk=win_chunk, n_window=self.gate.n_window)[:logits.shape[0]]
+        return self._track_of(logits, int(vbank.shape[0]), gate_logits)
 
-    def _track_of(self, logits: torch.Tensor, n_segments: int) -> OffsetTrack:
-        """The read-out of one recording's window logits (W, C)."""
-        cls_raw, conf_raw, cls_path, conf_path = ops.track_decode(logits, self.lam)
+    def _track_of(self, logits: torch.Tensor, n_segments: int, gate_logits: Optional[torch.Tensor] = None) -> OffsetTrack:
+        """The read-out of one recording's window logits (W, C); with a gate, over (offset class, synchronizable flag) with its logits (W, 2) of the same windows."""
+        sync_raw = sync_path = None
+        if gate_logits is None:
+            cls_raw, conf_raw, cls_path, conf_path = ops.track_decode(logits, self.lam)
+        else:
+            cls_raw, conf_raw, sync_raw, cls_path, sync_path, conf_path = ops.track_decode_gated(logits, gate_logits, self.lam, self.mu)
         track = OffsetTrack(t_sec=window_times(logits.shape[0], self.hop).to(self.eng.dev), logits=logits, cls_raw=cls_raw, conf_raw=conf_raw,
                             cls_path=cls_path, conf_path=conf_path, offset_sec_raw=self.grid[cls_raw.long()], offset_sec_path=self.grid[cls_path.long()],
                             n_segments=n_segments)
-        if self.posterior:
+        track.gate_logits, track.sync_raw, track.sync_path = gate_logits, sync_raw, sync_path
+        if self.posterior and gate_logits is None:
             track.post, track.cls_post, track.conf_post, track.offset_sec_mean, track.log_z = ops.track_posterior(logits, self.lam, self.grid)
+        elif self.posterior:
+            track.post, track.p_sync, track.cls_post, track.conf_post, track.offset_sec_mean, track.log_z = ops.track_posterior_gated(logits, gate_logits, self.lam,
+                                                                                                                                       self.mu, self.grid)
+        if self.posterior:
             track.offset_sec_post = self.grid[track.cls_post.long()]
         return track
 
@@ -114,7 +173,10 @@ class OffsetTracker:
         """One visual bank (N, 8, 768) and the audio banks of P programmes (P, N, 6, 768) (engine.extract_recording_programmes_from) -> one OffsetTrack per
         programme, each what track_features gives for (vbank, abanks[p]); vproj runs over the visual bank once (engine.sync_windows_programmes)."""
         logits = self.eng.sync_windows_programmes(vbank, abanks, hop=self.hop, win_chunk=win_chunk)
-        return [self._track_of(logits[p], int(vbank.shape[0])) for p in range(logits.shape[0])]
+        gate_logits = [None] * logits.shape[0]
+        if self.gate is not None:
+            gate_logits = self.gate.sync_windows_programmes(vbank, abanks, hop=self.hop, win_chunk=win_chunk, n_window=self.gate.n_window)[:, :logits.shape[1]]
+        return [self._track_of(logits[p], int(vbank.shape[0]), gate_logits[p]) for p in range(logits.shape[0])]
 
     def track_raw_programmes(self, raw_frames: torch.Tensor, raw_wave: torch.Tensor, ingest, seg_chunk: Optional[int] = None, win_chunk: int = 256) -> List[OffsetTrack]:
         """track_raw for the audio programmes of one recording: `ingest` an ingest.RecordingIngest with programmes, raw_wave its multi-channel wave
@@ -152,6 +214,7 @@ class OffsetTracker:
         the domain's logits; choose it on held-out recordings.  lag >= the number of windows gives the offline path at flush().  seg_chunk: as in track().
         ingest: an ingest.RecordingIngest - push then takes frames and samples as decoded (native frame rate, size, sample rate; track_raw's layouts).  An ingest
         with programmes gives a ProgrammeStream: push / flush return one OffsetUpdate per programme."""
+        self._no_gate('stream')
         if getattr(ingest, 'programmes', None) is not None:
             return ProgrammeStream(self, lag, seg_chunk, ingest)
         return OffsetStream(self, lag, seg_chunk, ingest)
@@ -159,7 +222,13 @@ class OffsetTracker:
     def pool(self, n_feeds: int, lag: int = 16, seg_chunk: Optional[int] = None) -> 'OffsetStreamPool':
         """Up to `n_feeds` live feeds at once: each feed is what stream(lag, seg_chunk) is, but one push() advances all named feeds together - their
         new segments share the towers' launch groups, their new windows the sync transformer's passes, their read-outs one ops.track_pool_push."""
+        self._no_gate('pool')
         return OffsetStreamPool(self, n_feeds, lag, seg_chunk)
+
+    def _no_gate(self, who: str):
+        if self.gate is not None:
+            raise NotImplementedError(f'OffsetTracker.{who}: the fixed-lag read-outs carry a state C wide, a gate needs 2C (DESIGN 3.20, out of scope there): build the '
+                                      'tracker without a gate for live feeds')
 
 
 @dataclass

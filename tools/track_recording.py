@@ -4,7 +4,7 @@ beside the same windows through forward_clips on explicit 120-frame slices.  Pri
     python tools/track_recording.py [--seconds 60] [--hop 1] [--seg-chunk 224] [--host] [--clip-windows 8] [--fps 30000/1001 --size 1080x1920 --rate 48000]
                                     [--pix-fmt {rgb24,nv12,yuv420p,p010,yuv420p10le,uyvy422,yuyv422,yuv422p,nv16,yuv422p10le,p210,y210}]
                                     [--chroma-loc {center,left,topleft}] [--field-order {progressive,tff,bff}] [--posterior]
-                                    [--stream SECONDS [--lag N]]
+                                    [--stream SECONDS [--lag N]] [--gate [--mu X]]
                                     [--audio-channels N [--audio-interleaved] [--sample-fmt {flt,s16,s32}] --programmes 0+1,2+3,4]
 
 With --fps / --size / --rate the recording is synthesised RAW at that geometry (channels-last uint8 frames, stereo int16 PCM, in device memory) and goes through
@@ -18,6 +18,11 @@ nearest its slot resized on its own, and the line reports the field order, the f
 
 With --posterior the windows are also read out as marginals: the line then carries the mean and minimum of conf_post, log_z per window step
 (log_z / max(W - 1, 1)), the largest |offset_sec_mean - offset_sec_path| and the time of the two extra launches (the read-out alone, on the track's logits).
+
+With --gate a synthetic 2-way syncability engine without towers (184 position rows: windows of 13 segments) reads the same bank and the windows are
+read out over (offset class, synchronizable flag) at --mu: the line then carries, of this same run, the time of the offset windows and of the ungated read-out beside
+the time of the gate's windows and of the gated read-out (with --posterior both read-outs include their posterior launches), what the gate adds to track_total_s, the
+windows flagged not synchronizable, and the spans (start s, end s, offset s or null) of OffsetTrack.spans().  --stream keeps using the tracker without a gate.
 
 With --stream SECONDS the recording is also pushed through OffsetTracker.stream(lag) in pieces of that many seconds (from raw input when --fps /
 --size / --rate are given): the line then carries, per push, the milliseconds of the bank (the towers on the segments the push completed), the windows (the sync
@@ -65,6 +70,8 @@ def main():
     ap.add_argument('--posterior', action='store_true', help='also read the windows out as marginals (forward-backward)')
     ap.add_argument('--stream', type=float, default=None, metavar='SECONDS', help='also push the recording through OffsetTracker.stream in pieces of this length')
     ap.add_argument('--lag', type=int, default=16, help='decision lag of the stream, in windows')
+    ap.add_argument('--gate', action='store_true', help='also gate the track by a synthetic 2-way syncability engine (towers=False) on the same bank')
+    ap.add_argument('--mu', type=float, default=2.0, help='cost of one change of the synchronizable flag (with --gate)')
     ap.add_argument('--programmes', default=None, help="audio programmes of the wave's channels, e.g. 0+1,2+3,4: one offset track per programme against one pass of the picture")
     ap.add_argument('--audio-channels', type=int, default=None, help='channels of the raw wave (with --programmes; default: the highest channel named + 1)')
     ap.add_argument('--audio-interleaved', action='store_true', help='the raw wave is (n, ch), as a feed delivers it (with --programmes)')
@@ -160,6 +167,37 @@ def main():
                       'log_z_per_step': round(track.log_z.item() / max(W - 1, 1), 4),
                       'max_abs_mean_minus_path_s': round((track.offset_sec_mean - track.offset_sec_path).abs().max().item(), 4),
                       'posterior_s': round(t_post, 6)})
+    if args.gate:
+        gate = SynchformerEngine(synth.make_state_dict(4242, head='sync_head', n_pos=184, n_out=2), dev, towers=False)
+        gated = OffsetTracker(eng, mel, hop_segments=args.hop, posterior=args.posterior, gate=gate, mu=args.mu)
+        gtrack = gated.track_features(vbank, abank, win_chunk=args.win_chunk)
+        grid = gated.grid
+
+        def plain_readout():
+            ops.track_decode(track.logits, gated.lam)
+            if args.posterior:
+                ops.track_posterior(track.logits, gated.lam, grid)
+
+        def gated_readout():
+            ops.track_decode_gated(gtrack.logits, gtrack.gate_logits, gated.lam, gated.mu)
+            if args.posterior:
+                ops.track_posterior_gated(gtrack.logits, gtrack.gate_logits, gated.lam, gated.mu, grid)
+
+        t_ow, _ = timed(lambda: eng.sync_windows(vbank, abank, hop=args.hop, win_chunk=args.win_chunk), reps=5)
+        t_gw, _ = timed(lambda: gate.sync_windows(vbank, abank, hop=args.hop, win_chunk=args.win_chunk, n_window=gate.n_window), reps=5)
+        t_pr, _ = timed(plain_readout, reps=20)
+        t_gr, _ = timed(gated_readout, reps=20)
+        spans = gtrack.spans()
+        extra['gate'] = {'mu': args.mu, 'gate_n_window': gate.n_window, 'offset_windows_s': round(t_ow, 6), 'ungated_readout_s': round(t_pr, 6),
+                         'gate_windows_s': round(t_gw, 6), 'gated_readout_s': round(t_gr, 6),
+                         'gate_adds_fraction_of_track_total': round((t_gw + t_gr - t_pr) / (t_bank + t_win), 5),
+                         'logits_equal_ungated': bool(torch.equal(gtrack.logits, track.logits)),
+                         'windows_not_synchronizable': int((gtrack.sync_path == 0).sum().item()), 'sync_raw_mean': round(gtrack.sync_raw.mean().item(), 4),
+                         'spans': [[round(t0, 2), round(t1, 2), None if off is None else round(off, 3)] for t0, t1, off in spans]}
+        if args.posterior:
+            extra['gate']['p_sync_mean'] = round(gtrack.p_sync.mean().item(), 4)
+        for t0, t1, off in spans:
+            print(f'span {t0:8.2f} s .. {t1:8.2f} s  ' + ('not synchronizable' if off is None else f'offset {off:+.2f} s'), file=sys.stderr)
     if args.stream is not None:
         extra['stream'] = stream_timing(args, tracker, eng, ops, (raw, raw_wave, ing) if raw_mode else (src[0], src[1], None), track)
     k = min(W, max(1, args.clip_windows))
