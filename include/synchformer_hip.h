@@ -123,7 +123,8 @@ int sf_gemm_mx_res_ln768(const uint8_t* A, int64_t lda, const uint8_t* sA, int64
                          uint8_t* Y, int64_t ldy, uint8_t* sY, int64_t ldsy, int64_t M, int64_t K, void* stream);
 /* sf_qkv_time_attention on MXFP8 operands (the temporal qkv projection of the fp8 towers with the 8-frame time attention in its epilogue): X (rows, 768) / W (2304, 768)
  * e4m3 bytes with stage-major scale planes (6 planes, one dword per row, ldsx / ldsw bytes apart); qkv_cls / out bf16 and cls_partial fp32 as in
- * sf_qkv_time_attention.  Replaces sf_gemm_mxfp8 (bf16 output) + sf_attention (time groups) + sf_attention_cls on the MX path. */
+ * sf_qkv_time_attention.  n_groups % 4 == 0, and n_groups >= 28 unless n_seq <= 2 (a 32-patch tile may touch two sequences at the most: fewer patches per sequence
+ * are refused; the bf16 form serves them).  Replaces sf_gemm_mxfp8 (bf16 output) + sf_attention (time groups) + sf_attention_cls on the MX path. */
 int sf_qkv_time_attention_mx(const uint8_t* X, int64_t ldx, const uint8_t* sX, int64_t ldsx, const uint8_t* W, int64_t ldw, const uint8_t* sW, int64_t ldsw,
                              const float* bias, const uint16_t* qkv_cls, int64_t ldc, uint16_t* out, int64_t ldo, float* cls_partial, int64_t n_seq, int n_groups,
                              float scale, void* stream);

@@ -41,7 +41,8 @@
 #define QT_LDS (QT_CLS_OFF + 8 * 384)            // 160 KiB: slot 0 | slot 1 = the first 56 KiB of the slab area | bias | CLS
 // MXFP8 variant (template parameter MX): the same 4 KiB behind the slabs hold bias (768 B) | the k-tile's scale dwords (8 waves x 224 B: this wave's 32 token
 // rows | 24 of the head's 192 W rows) | FOUR shared CLS landing slots (tile parity x the at most two sequences a 32-patch tile touches; the bf16 variant's eight
-// private slots do not leave the 1792 B the scales need)
+// private slots do not leave the 1792 B the scales need).  Two sequences per tile holds from n_groups = 28 on; the launcher refuses fewer patches per sequence
+// when there are more than two sequences.
 #define QT_SC_OFF (QT_BIAS_OFF + 768)
 #define QT_SC_WAVE 224
 #define QT_CLSX_OFF (QT_SC_OFF + 8 * QT_SC_WAVE)  // + 4 x 384 B = QT_LDS exactly
@@ -778,6 +779,10 @@ static int qkv_time_mx_impl(const uint8_t* X, int64_t ldx, const uint8_t* sX, in
                "sf_qkv_time_attention_mx: operands must be 16-byte aligned (scale planes 4-byte)");
   if (n_seq <= 0) return 0;
   const int64_t seq_rows = 1 + 8 * (int64_t)n_groups;
+  // the CLS landing slots (QT_CLSX_OFF) hold the at most TWO sequences a 32-patch tile touches: true from n_groups = 28 on (tiles start at multiples of 4 patches:
+  // the first sequence of a tile gives it at least 4 patches, the second n_groups), or when there are no more than two sequences.  Below that the waves of a third
+  // sequence would land their CLS row in the other tile parity's slots or behind the LDS allocation: refused (the bf16 form has a private slot per wave and serves it).
+  SF_CHECK_ARG(n_groups >= 28 || n_seq <= 2, "sf_qkv_time_attention_mx: n_groups < 28 with more than two sequences is not served (a 32-patch tile would touch more than the two sequences its CLS landing slots hold); got n_groups %d, n_seq %lld", n_groups, (long long)n_seq);
   SF_CHECK_ARG(n_seq * seq_rows * ldx < ((int64_t)1 << 32) && (int64_t)3 * QT_D * ldw < ((int64_t)1 << 32), "sf_qkv_time_attention_mx: X and W must stay below 4 GiB");
   SF_CHECK_ARG((ldsx % 4) == 0 && (ldsw % 4) == 0 && ldsx >= n_seq * seq_rows * 4 && ldsw >= 3 * QT_D * 4 && ldsx < ((int64_t)1 << 32) && ldsw < ((int64_t)1 << 32),
                "sf_qkv_time_attention_mx: scale planes must hold one dword per row of X / W");

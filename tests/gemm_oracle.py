@@ -8,6 +8,9 @@ GELU, R an fp32 residual, out fp32 or bf16 (round-to-nearest-even).
 Operand families
   exact  integer-valued operands (A in [-4, 4], W in [-8, 8], integer bias / residual): every partial sum is an integer below 2^24 for K <= 3072, so the fp32
          result does not depend on the summation order, the tiling or a k rotation - outputs are compared BIT FOR BIT with the int64 result.
+  sparse the raw material of the fused qkv tests (tests/qkv_fused_oracle.py, which adds the powers of two and the marks): A rows with at most 16 entries +-1 at random
+         columns, W integers in [-8, 8], bias integers in [-64, 64] (MXFP8: at most 12 bytes +-1 per row of A, W bytes 0 / +-1, scale bytes 126 .. 128), so that
+         every sum stays below 2^8 units and is a bf16 number.
   wide   Gaussian operands whose magnitude changes per 32-deep k-block and per row (factors 2^-6 .. 2^5 on A, 2^-4 .. 2^3 on W, sigma 0.05), Gaussian
          bias, residual of sigma 2 plus an offset.  Two criteria, both against float64 computed from the very values the kernel reads:
            elementwise  |got - ref| <= MARGIN * (u_out |ref| + F),  F = (d + c) 2^-24 S,  S = sum_k |a_k w_k| + |bias| + |residual|,
@@ -59,6 +62,11 @@ def operands(family, M, N, K, seed, a_rows=None):
         w = torch.randint(-8, 9, (N, K), generator=g).float()
         bias = torch.randint(-50, 51, (N,), generator=g).float()
         res = torch.randint(-2000, 2001, (M, N), generator=g).float()
+    elif family == 'sparse':
+        a = torch.zeros(a_rows, K).scatter_(1, torch.randint(0, K, (a_rows, 16), generator=g), torch.randint(0, 2, (a_rows, 16), generator=g).float() * 2 - 1)
+        w = torch.randint(-8, 9, (N, K), generator=g).float()
+        bias = torch.randint(-64, 65, (N,), generator=g).float()
+        res = torch.zeros(M, N)
     elif family == 'wide':
         a = torch.randn(a_rows, K, generator=g) * torch.exp2(torch.randint(-6, 6, (a_rows, K // 32), generator=g).float()).repeat_interleave(32, 1)
         w = torch.randn(N, K, generator=g) * 0.05 * torch.exp2(torch.randint(-4, 4, (N, K // 32), generator=g).float()).repeat_interleave(32, 1)
@@ -74,7 +82,7 @@ def operands(family, M, N, K, seed, a_rows=None):
 def mx_operands(family, M, N, K, seed):
     """MXFP8 operands built directly as bytes: aq (M, K) / wq (N, K) e4m3 bytes (never 0x7F / 0xFF) and per-32-block E8M0 scale bytes asc (M, K / 32),
     wsc (N, K / 32); exact: bytes encoding integers in [-4, 4] / [-8, 8] and scale bytes 126 .. 128 (every product a multiple of 2^-2, every partial sum below
-    2^24 of them); wide: any finite byte, scale bytes 120 .. 134.  Plus bias / res as in operands()."""
+    2^24 of them); sparse: at most 12 bytes +-1 per row of A, W bytes 0 / +-1, scale bytes 126 .. 128 (every sum at most 12 * 16 + 64 quarter units); wide: any finite byte, scale bytes 120 .. 134.  Plus bias / res as in operands()."""
     g = gen(seed)
     if family == 'exact':
         aq = torch.randint(-4, 5, (M, K), generator=g).float().to(torch.float8_e4m3fn).view(torch.uint8)
@@ -83,7 +91,16 @@ def mx_operands(family, M, N, K, seed):
         wsc = torch.randint(126, 129, (N, K // 32), generator=g).to(torch.uint8)
         bias = torch.randint(-50, 51, (N,), generator=g).float()
         res = torch.randint(-2000, 2001, (M, N), generator=g).float()
+    elif family == 'sparse':
+        aq = torch.zeros(M, K).scatter_(1, torch.randint(0, K, (M, 12), generator=g), torch.randint(0, 2, (M, 12), generator=g).float() * 2 - 1)
+        aq = aq.to(torch.float8_e4m3fn).view(torch.uint8)
+        wq = torch.randint(-1, 2, (N, K), generator=g).float().to(torch.float8_e4m3fn).view(torch.uint8)
+        asc = torch.randint(126, 129, (M, K // 32), generator=g).to(torch.uint8)
+        wsc = torch.randint(126, 129, (N, K // 32), generator=g).to(torch.uint8)
+        bias = torch.randint(-64, 65, (N,), generator=g).float()
+        res = torch.zeros(M, N)
     else:
+        assert family == 'wide', family
         def bytes_(r):
             b = torch.randint(0, 256, (r, K), generator=g)
             b = torch.where((b & 0x7F) == 0x7F, b - 0x40, b)            # 0x7F / 0xFF (NaN) -> 0x3F / 0xBF
