@@ -1146,8 +1146,8 @@ extern "C" int sf_gemm_tn_splitk(const bf16_t* dY, int64_t ldy, const bf16_t* X,
                (long long)N, (long long)K);
   SF_CHECK_ARG(split >= 1 && split < 65536 && kc >= 64 && (kc % 64) == 0 && kc < ((int64_t)1 << 30) && (int64_t)split * kc >= M,
                "sf_gemm_tn_splitk: split * kc must cover M, kc %% 64 == 0");
-  SF_CHECK_ARG((ldy % 8) == 0 && (ldx % 8) == 0 && ((uintptr_t)dY % 16) == 0 && ((uintptr_t)X % 16) == 0 && ((uintptr_t)part % 16) == 0,
-               "sf_gemm_tn_splitk: operands must be 16-byte aligned with row strides %% 8 == 0");
+  SF_CHECK_ARG((ldy % 8) == 0 && (ldx % 8) == 0 && ldy >= N && ldx >= K && ((uintptr_t)dY % 16) == 0 && ((uintptr_t)X % 16) == 0 && ((uintptr_t)part % 16) == 0,
+               "sf_gemm_tn_splitk: operands must be 16-byte aligned with row strides %% 8 == 0, ldy >= N, ldx >= K");
   if (int rc = sf_prepare_kernel((const void*)gemm_tn_splitk_kernel, TN_LDS, "sf_gemm_tn_splitk")) return rc;
   TnArgs a;
   a.A = dY; a.lda = ldy; a.B = X; a.ldb = ldx; a.C = part; a.ldc = K; a.sC = N * K; a.M = M; a.kc = (int)kc;
