@@ -29,7 +29,7 @@ extern "C" {
 enum { SF_F32 = 0, SF_BF16 = 1, SF_F16 = 2, SF_U8 = 3, SF_I16 = 4, SF_I32 = 5 };   /* element types (SF_I16: PCM input of sf_resample_wave / _mix only; SF_I32: of sf_resample_wave_mix only) */
 enum { SF_EPI_NONE = 0, SF_EPI_GELU = 1 };                  /* GEMM epilogue activation */
 
-#define SF_ABI_VERSION 24
+#define SF_ABI_VERSION 25
 int sf_abi_version(void);
 const char* sf_last_error(void);
 /* "gfx950" + build flags; lets the host assert it loaded the library it built */
@@ -619,6 +619,42 @@ int sf_track_decode_gated(const float* logits, int64_t ldl, const float* gate_lo
                           float* sync_raw, int32_t* cls_path, int32_t* sync_path, float* conf_path, uint8_t* backptr, void* stream);
 int sf_track_posterior_gated(const float* logits, int64_t ldl, const float* gate_logits, int64_t ldg, int W, int C, float lam, float mu, const float* grid, float* post,
                              int64_t ldp, float* p_sync, int32_t* cls_post, float* conf_post, float* offset_mean, float* log_z, float* workspace, void* stream);
+
+/* The gated read-outs of a STREAM at a fixed lag (ABI v25): sf_track_stream_push and sf_track_pool_push with the chain over (offset class, synchronizable
+ * flag) of sf_track_decode_gated / sf_track_posterior_gated.  Rows (l_t, z_t) arrive in order: l_t the offset logits (C), z_t the gate logits (2) of the start-aligned
+ * gate window; E, T, lam, mu and the tie rules are those of the gated offline read-outs.  With path_t = sf_track_decode_gated's (cls_path, sync_path) and post_t, psync_t =
+ * sf_track_posterior_gated's post and p_sync on rows 0 .. t, a push that brings the stream to t + 1 rows returns
+ *     cls_raw, conf_raw, sync_raw (n)                         per new row, as sf_track_decode_gated gives them
+ *     (cls_lag[w], sync_lag[w]) = path_{w+lag}[w]             for every window w whose row w + lag arrived in this push; conf_lag[w] the softmax probability of cls_lag[w]
+ *                                                             in offset row w.  Committed once, never revised
+ *     post_lag[w, :] = post_{w+lag}[w, :], p_sync_lag[w] = psync_{w+lag}[w]      (posterior) with cls_post_lag, conf_post_lag, offset_mean_lag from post_lag
+ *     cls_tail, sync_tail, conf_tail (n_tail)                 path_t on the windows not yet committed
+ *     log_z[0]                                                (posterior) that of the prefix 0 .. t
+ * final, the counts n_commit / n_tail, rows_done, the block-of-size-0 rule and the launches (row statistics, the two causal scans side by side, one wavefront per
+ * committed window plus one for the tail, the rings' update) are sf_track_stream_push's; lag >= t gives the gated offline read-outs bit for bit at the final push.
+ * state: one opaque device buffer per stream of sf_track_stream_gated_bytes(C, lag, posterior) bytes (a multiple of 16, independent of rows_done), read only when
+ * rows_done > 0.  Layout (TrackGatedStreamLayout in sf_track.hip): [double: subtracted maxima][int32: end state, pad][Viterbi scores: 64 floats][posterior: forward
+ * vector: 64 floats][offset logits ring (lag, C) fp32][gate logits ring (lag, 2) fp32][posterior: a ring (lag, 2C) fp32][back pointer ring (lag, 2C) bytes]; row r lies
+ * in slot r % lag.  The emission is recomputed from the two logit rings as the offline scans compute it; no emission ring is kept.  A gated state is not an ungated one:
+ * the two kinds of push do not mix on one buffer.  workspace: sf_track_stream_gated_workspace_bytes(C, n, posterior) bytes, dead after the push.
+ * sf_track_pool_push_gated: the same for n_active streams in one call; the table, its validation, the packed outputs and the block-to-work mapping are
+ * sf_track_pool_push's, unchanged; the gate rows of a stream are rows [row0, row0 + n) of gate_logits (total_rows, 2), row stride ldg >= 2; sync_raw is indexed like
+ * cls_raw, sync_lag / p_sync_lag like cls_lag, sync_tail like cls_tail.  workspace: sf_track_pool_gated_workspace_bytes(C, total_rows, posterior).
+ * 2 <= C <= 32, 0 <= lag <= 255, n (total_rows) <= 2^20, lam and mu finite and >= 0, ldl >= C, ldg >= 2, ldp >= C; -1 and a message before anything is launched for
+ * everything sf_track_stream_push / sf_track_pool_push and the gated offline launchers refuse.  Nothing is read back, allocated or synchronised: a single-stream push
+ * can be captured in a graph (rows_done is part of the capture).  Non-finite rows: values unspecified, every index written inside [0, C) / {0, 1}. */
+int sf_track_stream_gated_bytes(int C, int lag, int posterior);
+int sf_track_stream_gated_workspace_bytes(int C, int n, int posterior);
+int sf_track_stream_push_gated(void* state, int C, int lag, int posterior, int64_t rows_done, const float* logits, int64_t ldl, const float* gate_logits, int64_t ldg,
+                               int n, float lam, float mu, const float* grid, int final, int32_t* cls_raw, float* conf_raw, float* sync_raw, int32_t* cls_lag,
+                               int32_t* sync_lag, float* conf_lag, float* post_lag, int64_t ldp, float* p_sync_lag, int32_t* cls_post_lag, float* conf_post_lag,
+                               float* offset_mean_lag, int32_t* cls_tail, int32_t* sync_tail, float* conf_tail, float* log_z, void* workspace, void* stream);
+int sf_track_pool_gated_workspace_bytes(int C, int total_rows, int posterior);
+int sf_track_pool_push_gated(void* states, int64_t state_stride, int n_slots, int C, int lag, int posterior, const int64_t* table_host, const int64_t* table_dev,
+                             int n_active, const float* logits, int64_t ldl, const float* gate_logits, int64_t ldg, int total_rows, float lam, float mu,
+                             const float* grid, int32_t* cls_raw, float* conf_raw, float* sync_raw, int32_t* cls_lag, int32_t* sync_lag, float* conf_lag, float* post_lag,
+                             int64_t ldp, float* p_sync_lag, int32_t* cls_post_lag, float* conf_post_lag, float* offset_mean_lag, int32_t* cls_tail, int32_t* sync_tail,
+                             float* conf_tail, float* log_z, void* workspace, void* stream);
 
 /* ---- Ingest of a decoded recording at its native frame rate, size and sample rate: the step the reference leaves to an ffmpeg subprocess in front of its code
  * (example.py:16-53: fps=25, short side 256, even dimensions, -ar 16000), plus the centre 224 crop of RGBSpatialCrop (dataset/transforms.py:68-95).  The host

@@ -18,7 +18,9 @@
 //
 // sf_track_stream_push (further below) reads a stream of rows out at a fixed lag with carried state; sf_track_pool_push (at the end) does that for many streams
 // in one call: the same launches over a descriptor table, blockIdx.y = the stream, every block running the single-stream device functions on its stream's context.
-// sf_track_decode_gated / sf_track_posterior_gated (last) are the two offline read-outs of one chain over (offset class, synchronizable flag), fed by a second head.
+// sf_track_decode_gated / sf_track_posterior_gated (after the pool) are the two offline read-outs of one chain over (offset class, synchronizable flag), fed by a
+// second head; sf_track_stream_push_gated / sf_track_pool_push_gated (last) read that chain out of a stream at a fixed lag, from a carried state 2C wide: the stream's
+// four kinds of launch around the gated kernels' own step functions.
 #include "sf_common.h"
 #include "../../include/synchformer_hip.h"
 #include <algorithm>
@@ -315,6 +317,7 @@ struct TrackStreamRows {
   __device__ __forceinline__ const uint8_t* backptr(int64_t r) const { return r >= t_old ? bp_new + (r - t_old) * C : bp_ring + (r % lag) * C; }
   __device__ __forceinline__ const float* a(int64_t r) const { return r >= t_old ? a_new + (r - t_old) * C : a_ring + (r % lag) * C; }
   __device__ __forceinline__ int end(int64_t r) const { return r >= t_old ? end_new[r - t_old] : end_last[0]; }
+  __device__ __forceinline__ int width() const { return C; }
 };
 
 // the state buffer: [double shifted][int32 end_last, pad][s: 64 floats][posterior: a: 64 floats][logits ring][posterior: a ring][back pointer ring]
@@ -414,9 +417,9 @@ __global__ __launch_bounds__(64) void track_stream_scan_kernel(const float* __re
 
 // Follows the back pointers of rows R .. w + 1 from class `cur` (the class at row R) -> the class at row w.  Lane c loads backptr[r, c] of eight rows at a time, the
 // chain itself is eight wave-uniform shuffles.  KEEP: tail[r - w] = the class at row r, for every r in [w, R] (LDS, written by lane 0).
-template <bool KEEP>
-__device__ __forceinline__ int track_stream_backtrace(const TrackStreamRows& rows, int64_t R, int64_t w, int cur, int c, bool live, int* tail) {
-  const int C = rows.C;
+template <bool KEEP, class Rows>
+__device__ __forceinline__ int track_stream_backtrace(const Rows& rows, int64_t R, int64_t w, int cur, int c, bool live, int* tail) {
+  const int C = rows.width();                                      // entries of one row of back pointers (the gated chain: 2C states)
   for (int64_t r0 = R; r0 > w; r0 -= 8) {
     int b[8];
 #pragma unroll
@@ -708,6 +711,47 @@ __global__ __launch_bounds__(64) void track_pool_keep_kernel(const int64_t* __re
                          states + e.slot * state_stride, (int)blockIdx.x);
 }
 
+// What a pool push's table adds up to; track_pool_table_check validates the HOST copy of the table (slots, row ranges, running sums) before anything is launched and
+// fills this in.  Shared by sf_track_pool_push and sf_track_pool_push_gated: the table is the same.
+struct TrackPoolTotals { int64_t sum_n, sum_commit, sum_tail, max_read, max_keep;  bool scan; };
+static int track_pool_table_check(const char* who, const int64_t* table_host, int n_active, int n_slots, int total_rows, int lag, int posterior, TrackPoolTotals& tot) {
+  struct Span { int64_t row0, n; };
+  static thread_local int64_t slots[TRACK_POOL_MAX_ACTIVE];
+  static thread_local Span spans[TRACK_POOL_MAX_ACTIVE];
+  int64_t sum_n = 0, sum_commit = 0, sum_tail = 0, max_read = 0, max_keep = 0;
+  int n_spans = 0;
+  bool scan = false;
+  for (int i = 0; i < n_active; ++i) {
+    const int64_t* r = table_host + (int64_t)i * TRACK_POOL_ROW;
+    SF_CHECK_ARG(r[0] >= 0 && r[0] < n_slots, "%s: table row %d: slot %lld outside the %d slots", who, i, (long long)r[0], n_slots);
+    SF_CHECK_ARG(r[1] >= 0 && r[1] <= (INT64_MAX >> 1), "%s: table row %d: %lld rows pushed so far", who, i, (long long)r[1]);
+    SF_CHECK_ARG(r[2] >= 0 && r[3] >= 0 && r[2] <= total_rows && r[3] <= total_rows - r[2],
+                 "%s: table row %d: rows [%lld, %lld + %lld) outside the %d rows of the push", who, i, (long long)r[3], (long long)r[3], (long long)r[2], total_rows);
+    const TrackPoolEntry e(table_host, i, lag);
+    SF_CHECK_ARG(e.commit0 == sum_commit && e.tail0 == sum_tail,
+                 "%s: table row %d: commit0 = %lld, tail0 = %lld, the counts of the rows before it give %lld, %lld", who, i, (long long)e.commit0,
+                 (long long)e.tail0, (long long)sum_commit, (long long)sum_tail);
+    slots[i] = e.slot;
+    if (e.n > 0) spans[n_spans++] = Span{e.row0, e.n};
+    if (e.t_new > 0) {
+      sum_commit += e.n_commit;
+      sum_tail += e.n_tail;
+      if (e.readout_blocks() > max_read) max_read = e.readout_blocks();
+      if (e.keep(lag) > max_keep) max_keep = e.keep(lag);
+      scan = scan || e.n > 0 || posterior;
+    }
+    sum_n += e.n;
+  }
+  std::sort(slots, slots + n_active);
+  for (int i = 1; i < n_active; ++i) SF_CHECK_ARG(slots[i] != slots[i - 1], "%s: slot %lld named twice in one push", who, (long long)slots[i]);
+  std::sort(spans, spans + n_spans, [](const Span& a, const Span& b) { return a.row0 < b.row0; });
+  for (int i = 1; i < n_spans; ++i)
+    SF_CHECK_ARG(spans[i - 1].row0 + spans[i - 1].n <= spans[i].row0, "%s: the rows [%lld, +%lld) and [%lld, +%lld) of two streams overlap", who,
+                 (long long)spans[i - 1].row0, (long long)spans[i - 1].n, (long long)spans[i].row0, (long long)spans[i].n);
+  tot = TrackPoolTotals{sum_n, sum_commit, sum_tail, max_read, max_keep, scan};
+  return 0;
+}
+
 extern "C" int sf_track_pool_workspace_bytes(int C, int total_rows, int posterior) {
   SF_CHECK_ARG(C >= 2 && C <= TRACK_MAX_C, "sf_track_pool_workspace_bytes: C = %d classes out of range (2 .. %d)", C, TRACK_MAX_C);
   SF_CHECK_ARG(total_rows >= 0 && total_rows <= TRACK_STREAM_MAX_PUSH, "sf_track_pool_workspace_bytes: %d rows in one push (0 .. %d)", total_rows, TRACK_STREAM_MAX_PUSH);
@@ -727,39 +771,10 @@ extern "C" int sf_track_pool_push(void* states, int64_t state_stride, int n_slot
   SF_CHECK_ARG(state_stride >= lay.total && state_stride % 16 == 0, "sf_track_pool_push: state stride %lld: a multiple of 16, at least %lld bytes", (long long)state_stride,
                (long long)lay.total);
   SF_CHECK_ARG(total_rows >= 0 && total_rows <= TRACK_STREAM_MAX_PUSH, "sf_track_pool_push: total_rows = %d rows in one push (0 .. %d)", total_rows, TRACK_STREAM_MAX_PUSH);
-  struct Span { int64_t row0, n; };
-  static thread_local int64_t slots[TRACK_POOL_MAX_ACTIVE];
-  static thread_local Span spans[TRACK_POOL_MAX_ACTIVE];
-  int64_t sum_n = 0, sum_commit = 0, sum_tail = 0, max_read = 0, max_keep = 0;
-  int n_spans = 0;
-  bool scan = false;
-  for (int i = 0; i < n_active; ++i) {
-    const int64_t* r = table_host + (int64_t)i * TRACK_POOL_ROW;
-    SF_CHECK_ARG(r[0] >= 0 && r[0] < n_slots, "sf_track_pool_push: table row %d: slot %lld outside the %d slots", i, (long long)r[0], n_slots);
-    SF_CHECK_ARG(r[1] >= 0 && r[1] <= (INT64_MAX >> 1), "sf_track_pool_push: table row %d: %lld rows pushed so far", i, (long long)r[1]);
-    SF_CHECK_ARG(r[2] >= 0 && r[3] >= 0 && r[2] <= total_rows && r[3] <= total_rows - r[2],
-                 "sf_track_pool_push: table row %d: rows [%lld, %lld + %lld) outside the %d rows of the push", i, (long long)r[3], (long long)r[3], (long long)r[2], total_rows);
-    const TrackPoolEntry e(table_host, i, lag);
-    SF_CHECK_ARG(e.commit0 == sum_commit && e.tail0 == sum_tail,
-                 "sf_track_pool_push: table row %d: commit0 = %lld, tail0 = %lld, the counts of the rows before it give %lld, %lld", i, (long long)e.commit0,
-                 (long long)e.tail0, (long long)sum_commit, (long long)sum_tail);
-    slots[i] = e.slot;
-    if (e.n > 0) spans[n_spans++] = Span{e.row0, e.n};
-    if (e.t_new > 0) {
-      sum_commit += e.n_commit;
-      sum_tail += e.n_tail;
-      if (e.readout_blocks() > max_read) max_read = e.readout_blocks();
-      if (e.keep(lag) > max_keep) max_keep = e.keep(lag);
-      scan = scan || e.n > 0 || posterior;
-    }
-    sum_n += e.n;
-  }
-  std::sort(slots, slots + n_active);
-  for (int i = 1; i < n_active; ++i) SF_CHECK_ARG(slots[i] != slots[i - 1], "sf_track_pool_push: slot %lld named twice in one push", (long long)slots[i]);
-  std::sort(spans, spans + n_spans, [](const Span& a, const Span& b) { return a.row0 < b.row0; });
-  for (int i = 1; i < n_spans; ++i)
-    SF_CHECK_ARG(spans[i - 1].row0 + spans[i - 1].n <= spans[i].row0, "sf_track_pool_push: the rows [%lld, +%lld) and [%lld, +%lld) of two streams overlap",
-                 (long long)spans[i - 1].row0, (long long)spans[i - 1].n, (long long)spans[i].row0, (long long)spans[i].n);
+  TrackPoolTotals tot;
+  if (track_pool_table_check("sf_track_pool_push", table_host, n_active, n_slots, total_rows, lag, posterior, tot)) return -1;
+  const int64_t sum_n = tot.sum_n, sum_commit = tot.sum_commit, sum_tail = tot.sum_tail, max_read = tot.max_read, max_keep = tot.max_keep;
+  const bool scan = tot.scan;
   SF_CHECK_ARG(sum_n == 0 || ldl >= C, "sf_track_pool_push: row stride ldl = %lld below C = %d", (long long)ldl, C);
   SF_CHECK_ARG(sum_n == 0 || (logits && cls_raw && conf_raw && workspace), "sf_track_pool_push: null pointer (new rows)");
   SF_CHECK_ARG(sum_commit == 0 || (cls_lag && conf_lag), "sf_track_pool_push: null pointer (committed block)");
@@ -833,6 +848,40 @@ __device__ __forceinline__ float track_gated_emission(const TrackGatedLane& ln, 
   return ln.live ? e : -INFINITY;
 }
 
+// One step of the gated Viterbi scan, by the whole wavefront: s_prev (LDS, 2C floats, state-major) = the previous, renormalised scores, e = this row's emission of
+// the lane's state -> the new renormalised score; bp = the predecessor STATE (one byte).  The lane scans the C predecessors of its own plane (lowest p on ties), takes
+// the other plane's best from its partner, subtracts mu, and settles the tie between the planes (m' = 0 wins).  The offline kernel and the stream's scan both call
+// this: the arithmetic is shared, not copied.
+__device__ __forceinline__ float track_gated_viterbi_step(const TrackGatedLane& ln, const float* s_prev, int C, float lam, float mu, float e, int& bp) {
+  const float* sp = s_prev + ln.m * C;                             // the lane's own plane
+  float best = sp[0] - lam * (float)ln.c;
+  bp = 0;
+  for (int p = 1; p < C; ++p) {
+    const float cand = sp[p] - lam * fabsf((float)(p - ln.c));
+    if (cand > best) { best = cand; bp = p; }
+  }
+  const float other = __shfl(best, ln.partner, 64) - mu;           // max_p (S[p, 1 - m] - lam |p - c|) - mu, and the p that gave it
+  const int other_bp = __shfl(bp, ln.partner, 64);
+  const bool cross = ln.m ? other >= best : other > best;          // ties between the planes: m' = 0 wins
+  bp = cross ? (1 - ln.m) * C + other_bp : ln.m * C + bp;
+  float s = ln.live ? (cross ? other : best) + e : -INFINITY;
+  s -= wave_max(s);
+  return s;
+}
+
+// One step of either gated forward-backward scan, by the whole wavefront: s_u (LDS, two planes of 32 floats, entries >= C hold -inf) = the vector the transition
+// reads, e = this row's emission (joins the lse in the forward scan only) -> the new vector's entry of the lane's state with the vector's maximum m (0 when that is
+// not finite) subtracted.  lse over the 2C predecessors = logaddexp(lse over the own plane, the partner's lse over its own plane - mu).
+__device__ __forceinline__ float track_gated_fb_step(const TrackGatedLane& ln, const float* s_u, int C4, bool back, float lam, float mu, float e, float& m) {
+  const float own = fb_transition_lse(s_u + ln.m * 32, C4, ln.c, lam);
+  const float other = __shfl(own, ln.partner, 64) - mu;
+  const float mx = fb_finite_or_zero(fmaxf(own, other));
+  const float r = mx + logf(expf(own - mx) + expf(other - mx));
+  const float v = ln.live ? (back ? r : r + e) : -INFINITY;
+  m = fb_finite_or_zero(wave_max(v));
+  return v - m;
+}
+
 // One thread per window: cls_raw / conf_raw as track_rows_kernel<false> gives them, sync_raw = sigmoid(z1 - z0).
 __global__ __launch_bounds__(256) void track_gated_rows_kernel(const float* __restrict__ logits, int64_t ldl, const float* __restrict__ gate, int64_t ldg, int W, int C,
                                                                 int32_t* __restrict__ cls_raw, float* __restrict__ conf_raw, float* __restrict__ sync_raw) {
@@ -876,20 +925,8 @@ __global__ __launch_bounds__(64) void track_gated_viterbi_kernel(const float* __
       z0_next = gate[(int64_t)(w + 1) * ldg];
       z1_next = gate[(int64_t)(w + 1) * ldg + 1];
     }
-    const float e = track_gated_emission(ln, l, z0, z1, log_c);
-    const float* sp = s_prev + ln.m * C;                           // the lane's own plane
-    float best = sp[0] - lam * (float)ln.c;
-    int bp = 0;
-    for (int p = 1; p < C; ++p) {
-      const float cand = sp[p] - lam * fabsf((float)(p - ln.c));
-      if (cand > best) { best = cand; bp = p; }
-    }
-    const float other = __shfl(best, ln.partner, 64) - mu;         // max_p (S[p, 1 - m] - lam |p - c|) - mu, and the p that gave it
-    const int other_bp = __shfl(bp, ln.partner, 64);
-    const bool cross = ln.m ? other >= best : other > best;        // ties between the planes: m' = 0 wins
-    bp = cross ? (1 - ln.m) * C + other_bp : ln.m * C + bp;
-    s = ln.live ? (cross ? other : best) + e : ninf;
-    s -= wave_max(s);
+    int bp;
+    s = track_gated_viterbi_step(ln, s_prev, C, lam, mu, track_gated_emission(ln, l, z0, z1, log_c), bp);
     if (ln.live) backptr[(int64_t)w * S + ln.j] = (uint8_t)bp;
     __syncthreads();                                               // every lane has read s_prev
     s_prev[ln.j] = s;
@@ -982,13 +1019,7 @@ __global__ __launch_bounds__(64) void track_gated_fb_scan_kernel(const float* __
       z1_next = gate[(row + step) * ldg + 1];
     }
     e = track_gated_emission(ln, l, z0, z1, log_c);
-    const float own = fb_transition_lse(s_u + ln.m * 32, C4, ln.c, lam);
-    const float other = __shfl(own, ln.partner, 64) - mu;
-    const float mx = fb_finite_or_zero(fmaxf(own, other));
-    const float r = mx + logf(expf(own - mx) + expf(other - mx));
-    v = ln.live ? (back ? r : r + e) : ninf;
-    m = fb_finite_or_zero(wave_max(v));
-    v -= m;
+    v = track_gated_fb_step(ln, s_u, C4, back, lam, mu, e, m);
     shifted += (double)m;
     if (ln.live) out[row * S + ln.j] = v;
     __syncthreads();                                               // every lane has read s_u
@@ -1001,6 +1032,32 @@ __global__ __launch_bounds__(64) void track_gated_fb_scan_kernel(const float* __
   }
 }
 
+// One window, by one thread: a, b (2C floats each, state-major) -> prow[c] = post2[c, 0] + post2[c, 1] with post2 = exp(a + b - lse_j (a + b)); ps = sum_c post2[c, 1]
+// clamped at 1; best = argmax_c prow (first maximum wins), pbest its value; mean = sum_c prow[c] grid[c] in ascending c.
+__device__ __forceinline__ void track_gated_combine_row(const float* a, const float* b, int C, const float* __restrict__ grid, float* __restrict__ prow, int& best,
+                                                        float& pbest, float& mean, float& ps) {
+  const int S = 2 * C;
+  float m = -INFINITY;
+  for (int j = 0; j < S; ++j) m = fmaxf(m, a[j] + b[j]);
+  m = fb_finite_or_zero(m);
+  float sum = 0.f;
+  for (int j = 0; j < S; ++j) sum += expf(a[j] + b[j] - m);
+  const float lse = fb_finite_or_zero(m + logf(sum));
+  best = 0;
+  pbest = 0.f;
+  mean = 0.f;
+  ps = 0.f;
+  for (int c = 0; c < C; ++c) {
+    const float p1 = expf(a[C + c] + b[C + c] - lse);
+    const float p = expf(a[c] + b[c] - lse) + p1;
+    prow[c] = p;
+    ps += p1;
+    mean += p * grid[c];
+    if (c == 0 || p > pbest) { pbest = p; best = c; }
+  }
+  ps = fminf(ps, 1.f);
+}
+
 // One thread per window:  s = a_w + b_w over the 2C states;  post2 = exp(s - lse_j s);  post[w, c] = post2[c, 0] + post2[c, 1];  p_sync[w] = sum_c post2[c, 1] (at most
 // 1);  cls_post = argmax_c post (first maximum wins; a NaN never wins `>`), conf_post its value;  offset_mean = sum_c post[w, c] grid[c] in ascending c.
 __global__ __launch_bounds__(256) void track_gated_fb_combine_kernel(const float* __restrict__ ws, int W, int C, const float* __restrict__ grid, float* __restrict__ post,
@@ -1010,25 +1067,10 @@ __global__ __launch_bounds__(256) void track_gated_fb_combine_kernel(const float
   if (w >= W) return;
   const int S = 2 * C;
   const float* a = ws + (int64_t)w * S;
-  const float* b = a + (int64_t)W * S;
-  float* prow = post + (int64_t)w * ldp;
-  float m = -INFINITY;
-  for (int j = 0; j < S; ++j) m = fmaxf(m, a[j] + b[j]);
-  m = fb_finite_or_zero(m);
-  float sum = 0.f;
-  for (int j = 0; j < S; ++j) sum += expf(a[j] + b[j] - m);
-  const float lse = fb_finite_or_zero(m + logf(sum));
-  int best = 0;
-  float pbest = 0.f, mean = 0.f, ps = 0.f;
-  for (int c = 0; c < C; ++c) {
-    const float p1 = expf(a[C + c] + b[C + c] - lse);
-    const float p = expf(a[c] + b[c] - lse) + p1;
-    prow[c] = p;
-    ps += p1;
-    mean += p * grid[c];
-    if (c == 0 || p > pbest) { pbest = p; best = c; }
-  }
-  p_sync[w] = fminf(ps, 1.f);
+  int best;
+  float pbest, mean, ps;
+  track_gated_combine_row(a, a + (int64_t)W * S, C, grid, post + (int64_t)w * ldp, best, pbest, mean, ps);
+  p_sync[w] = ps;
   cls_post[w] = best;
   conf_post[w] = pbest;
   offset_mean[w] = mean;
@@ -1047,5 +1089,458 @@ extern "C" int sf_track_posterior_gated(const float* logits, int64_t ldl, const 
   hipLaunchKernelGGL(track_gated_fb_combine_kernel, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, s, (const float*)workspace, W, C, grid, post, ldp, p_sync, cls_post,
                      conf_post, offset_mean);
   SF_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- the gated read-outs of a stream at a fixed lag (sf_track_stream_push_gated, sf_track_pool_push_gated) -----------------------------------------
+// sf_track_stream_push's definition with the gated offline read-outs in place of the ungated ones: window w is committed by the push that delivers row w + lag as
+// path_{w+lag}[w] / post_{w+lag}[w] of sf_track_decode_gated / sf_track_posterior_gated on the prefix 0 .. w + lag.  The carried state is 2C wide: the scan vectors
+// over the states j = m * C + c, rings of back pointers (2C bytes a row) and of a (2C floats a row), and rings of BOTH inputs - the offset logits (C) and the gate
+// logits (2) - from which the emission is recomputed exactly as the offline scans compute it (no emission ring).  The same four kinds of launch, the per-step
+// arithmetic that of the offline kernels (track_gated_viterbi_step, track_gated_fb_step, track_gated_emission, track_gated_combine_row).
+struct TrackGatedStreamRows {
+  const float* lg_new;  int64_t ldl;      // the push's offset logits
+  const float* gz_new;  int64_t ldg;      // the push's gate logits
+  const uint8_t* bp_new;                  // workspace: back pointers (n, 2C)
+  const float* a_new;                     // workspace: normalised a (n, 2C); posterior only
+  const int32_t* end_new;                 // workspace: the end state per new row
+  const float* lg_ring;  const float* gz_ring;  const uint8_t* bp_ring;  const float* a_ring;      // state: (lag, C), (lag, 2), (lag, 2C), (lag, 2C)
+  const int32_t* end_last;                // state: the end state of the last row pushed
+  int64_t t_old;                          // rows before this push
+  int lag, C;
+  __device__ __forceinline__ const float* logits(int64_t r) const { return r >= t_old ? lg_new + (r - t_old) * ldl : lg_ring + (r % lag) * C; }
+  __device__ __forceinline__ const float* gate(int64_t r) const { return r >= t_old ? gz_new + (r - t_old) * ldg : gz_ring + (r % lag) * 2; }
+  __device__ __forceinline__ const uint8_t* backptr(int64_t r) const { return r >= t_old ? bp_new + (r - t_old) * 2 * C : bp_ring + (r % lag) * 2 * C; }
+  __device__ __forceinline__ const float* a(int64_t r) const { return r >= t_old ? a_new + (r - t_old) * 2 * C : a_ring + (r % lag) * 2 * C; }
+  __device__ __forceinline__ int end(int64_t r) const { return r >= t_old ? end_new[r - t_old] : end_last[0]; }
+  __device__ __forceinline__ int width() const { return 2 * C; }
+};
+
+// the gated state buffer:
+//   [double shifted][int32 end_last, pad][s: 64 floats][posterior: a: 64 floats][offset logits ring (lag, C) fp32][gate logits ring (lag, 2) fp32]
+//   [posterior: a ring (lag, 2C) fp32][back pointer ring (lag, 2C) bytes], rounded up to 16 bytes.  Row r of the stream lies in slot r % lag of every ring.
+struct TrackGatedStreamLayout {
+  int64_t s, a, lg_ring, gz_ring, a_ring, bp_ring, total;
+  __host__ __device__ TrackGatedStreamLayout(int C, int lag, bool posterior) {
+    s = 16;
+    a = s + 64 * 4;
+    lg_ring = a + (posterior ? 64 * 4 : 0);
+    gz_ring = lg_ring + (int64_t)lag * C * 4;
+    a_ring = gz_ring + (int64_t)lag * 2 * 4;
+    bp_ring = a_ring + (posterior ? (int64_t)lag * 2 * C * 4 : 0);
+    total = (bp_ring + (int64_t)lag * 2 * C + 15) & ~(int64_t)15;
+  }
+};
+
+// One stream's view of its rows: the rings of its state and its part of the push (host and device: the single-stream launcher and the pool's kernels build it).
+__host__ __device__ __forceinline__ void track_gated_rows_fill(TrackGatedStreamRows& rows, const TrackGatedStreamLayout& lay, const unsigned char* st, const float* logits,
+                                                               int64_t ldl, const float* gate, int64_t ldg, const uint8_t* bp, const float* a, const int32_t* end,
+                                                               int64_t t_old, int lag, int C) {
+  rows.lg_new = logits;  rows.ldl = ldl;  rows.gz_new = gate;  rows.ldg = ldg;  rows.bp_new = bp;  rows.a_new = a;  rows.end_new = end;
+  rows.lg_ring = reinterpret_cast<const float*>(st + lay.lg_ring);  rows.gz_ring = reinterpret_cast<const float*>(st + lay.gz_ring);
+  rows.bp_ring = st + lay.bp_ring;  rows.a_ring = reinterpret_cast<const float*>(st + lay.a_ring);
+  rows.end_last = reinterpret_cast<const int32_t*>(st + 8);
+  rows.t_old = t_old;  rows.lag = lag;  rows.C = C;
+}
+
+// The scan of one stream's push, by one wavefront: fwd = false the Viterbi scan, fwd = true the forward scan (wave-uniform).  s_u: 64 floats of LDS, 16-byte aligned:
+// the Viterbi scores state-major, the forward vector as two planes of 32 (entries >= C hold -inf), as the offline kernels keep them.
+__device__ __forceinline__ void track_gated_stream_scan_body(const float* __restrict__ logits, int64_t ldl, const float* __restrict__ gate, int64_t ldg, int n, int C,
+                                                             float lam, float mu, int64_t t_old, unsigned char* __restrict__ state, int lag, int posterior,
+                                                             uint8_t* __restrict__ bp_new, float* __restrict__ a_new, int32_t* __restrict__ end_new,
+                                                             float* __restrict__ log_z, bool fwd, float* s_u) {
+  const TrackGatedStreamLayout lay(C, lag, posterior != 0);
+  const TrackGatedLane ln(C);
+  const int S = 2 * C;
+  const int C4 = (C + 3) & ~3;
+  const float ninf = -INFINITY;
+  const float log_c = logf((float)C);
+  const bool loads = ln.live && ln.m;                              // the lanes of plane 1 carry the offset logits
+  const int slot = fwd ? ln.m * 32 + ln.c : ln.j;
+  float* carried = reinterpret_cast<float*>(state + (fwd ? lay.a : lay.s));
+  double* st_shifted = reinterpret_cast<double*>(state);
+  int32_t* st_end = reinterpret_cast<int32_t*>(state + 8);
+  double shifted = (fwd && t_old > 0) ? st_shifted[0] : 0.0;
+  float v = (t_old > 0 && ln.live) ? carried[ln.j] : ninf;
+  int k = 0;
+  float l_next = (loads && n > 0) ? logits[ln.c] : ninf;
+  float z0_next = n > 0 ? gate[0] : 0.f, z1_next = n > 0 ? gate[1] : 0.f;
+  s_u[threadIdx.x] = ninf;
+  __syncthreads();
+  if (t_old == 0 && n > 0) {                                       // the first row of the stream: S_0 = E[0] / a_0 = E[0], as the offline scans begin
+    const float l = l_next, z0 = z0_next, z1 = z1_next;
+    if (n > 1) {
+      l_next = loads ? logits[ldl + ln.c] : ninf;
+      z0_next = gate[ldg];
+      z1_next = gate[ldg + 1];
+    }
+    const float e = track_gated_emission(ln, l, z0, z1, log_c);
+    if (fwd) {
+      v = e;
+      const float m = fb_finite_or_zero(wave_max(v));
+      v -= m;
+      shifted += (double)m;
+      if (ln.live) a_new[ln.j] = v;
+    } else {
+      v = e;
+      v -= wave_max(v);
+      if (ln.live) bp_new[ln.j] = 0;                               // never followed: the backtrace stops at row 1
+      const int end = track_wave_end_state(v, ln.live);            // (the ballot needs the whole wavefront)
+      if (ln.j == 0) end_new[0] = end;
+    }
+    k = 1;
+  }
+  if (ln.live) s_u[slot] = v;
+  __syncthreads();
+  for (; k < n; ++k) {
+    const float l = l_next, z0 = z0_next, z1 = z1_next;
+    if (k + 1 < n) {                                               // the next row's loads travel under this step
+      l_next = loads ? logits[(int64_t)(k + 1) * ldl + ln.c] : ninf;
+      z0_next = gate[(int64_t)(k + 1) * ldg];
+      z1_next = gate[(int64_t)(k + 1) * ldg + 1];
+    }
+    const float e = track_gated_emission(ln, l, z0, z1, log_c);
+    if (fwd) {
+      float m;
+      v = track_gated_fb_step(ln, s_u, C4, false, lam, mu, e, m);
+      shifted += (double)m;
+      if (ln.live) a_new[(int64_t)k * S + ln.j] = v;
+    } else {
+      int bp;
+      v = track_gated_viterbi_step(ln, s_u, C, lam, mu, e, bp);
+      if (ln.live) bp_new[(int64_t)k * S + ln.j] = (uint8_t)bp;
+      const int end = track_wave_end_state(v, ln.live);
+      if (ln.j == 0) end_new[k] = end;
+    }
+    __syncthreads();                                               // every lane has read s_u
+    if (ln.live) s_u[slot] = v;
+    __syncthreads();
+  }
+  if (n > 0) {
+    const int end = track_wave_end_state(v, ln.live);
+    if (ln.live) carried[ln.j] = v;
+    if (ln.j == 0) {
+      if (fwd) st_shifted[0] = shifted;
+      else st_end[0] = end;
+    }
+  }
+  if (fwd) {
+    const float z = logf(wave_sum(expf(v)));                       // the normalised a of the last row: maximum 0
+    if (ln.j == 0) log_z[0] = (float)(shifted + (double)z);
+  }
+}
+
+__global__ __launch_bounds__(64) void track_gated_stream_scan_kernel(const float* __restrict__ logits, int64_t ldl, const float* __restrict__ gate, int64_t ldg, int n,
+                                                                      int C, float lam, float mu, int64_t t_old, unsigned char* __restrict__ state, int lag,
+                                                                      int posterior, uint8_t* __restrict__ bp_new, float* __restrict__ a_new,
+                                                                      int32_t* __restrict__ end_new, float* __restrict__ log_z) {
+  __shared__ __attribute__((aligned(16))) float s_u[64];
+  track_gated_stream_scan_body(logits, ldl, gate, ldg, n, C, lam, mu, t_old, state, lag, posterior, bp_new, a_new, end_new, log_z, blockIdx.x == 1, s_u);
+}
+
+// Every pointer of the committed block and the tail of one stream's read-out.
+struct TrackGatedStreamOut {
+  int32_t* cls_lag;  int32_t* sync_lag;  float* conf_lag;
+  float* post_lag;  int64_t ldp;  float* p_sync_lag;  int32_t* cls_post_lag;  float* conf_post_lag;  float* offset_mean_lag;
+  int32_t* cls_tail;  int32_t* sync_tail;  float* conf_tail;
+  // the same block `commit0` committed windows / `tail0` tail entries further on (a pool's packed outputs)
+  __host__ __device__ TrackGatedStreamOut at(int64_t commit0, int64_t tail0) const {
+    TrackGatedStreamOut o = *this;
+    o.cls_lag += commit0;  o.sync_lag += commit0;  o.conf_lag += commit0;
+    o.post_lag += commit0 * ldp;  o.p_sync_lag += commit0;  o.cls_post_lag += commit0;  o.conf_post_lag += commit0;  o.offset_mean_lag += commit0;
+    o.cls_tail += tail0;  o.sync_tail += tail0;  o.conf_tail += tail0;
+    return o;
+  }
+};
+
+// Block i < n_commit: window w = w0 + i, read from the prefix that ends at row R = min(w + lag, t_last); block n_commit (if n_tail > 0): the tail.  The backtrace is
+// track_stream_backtrace over rows of 2C back pointers (every index read clamped below 2C); the state j it arrives at is written as cls = j % C, sync = j / C.
+// s_u (16-byte aligned) / s_b: 64 floats of LDS each, s_tail: 256 ints.
+template <bool POST>
+__device__ __forceinline__ void track_gated_stream_readout_body(const TrackGatedStreamRows& rows, float lam, float mu, const float* __restrict__ grid, int64_t w0,
+                                                                int n_commit, int n_tail, int64_t t_last, const TrackGatedStreamOut& out, int bx, float* s_u, float* s_b,
+                                                                int* s_tail) {
+  const int C = rows.C, S = 2 * C;
+  const TrackGatedLane ln(C);
+  if (bx == n_commit) {                                            // the tail
+    const int64_t w = t_last - (n_tail - 1);
+    int cur = rows.end(t_last);
+    cur = cur < 0 ? 0 : (cur >= S ? S - 1 : cur);
+    track_stream_backtrace<true>(rows, t_last, w, cur, ln.j, ln.live, s_tail);
+    __syncthreads();
+    for (int i = threadIdx.x; i < n_tail; i += 64) {
+      const float* row = rows.logits(w + i);
+      int best;
+      float m, sum;
+      track_row_stats(row, C, best, m, sum);
+      const int cls = s_tail[i] % C;
+      out.cls_tail[i] = cls;
+      out.sync_tail[i] = s_tail[i] / C;
+      out.conf_tail[i] = track_row_conf(row, C, cls, m, sum);
+    }
+    return;
+  }
+  const int i = bx;
+  const int64_t w = w0 + i;
+  const int64_t R = w + rows.lag < t_last ? w + rows.lag : t_last;
+  int cur = rows.end(R);
+  cur = cur < 0 ? 0 : (cur >= S ? S - 1 : cur);
+  cur = track_stream_backtrace<false>(rows, R, w, cur, ln.j, ln.live, nullptr);
+  if (ln.j == 0) {
+    const float* row = rows.logits(w);
+    int best;
+    float m, sum;
+    track_row_stats(row, C, best, m, sum);
+    out.cls_lag[i] = cur % C;
+    out.sync_lag[i] = cur / C;
+    out.conf_lag[i] = track_row_conf(row, C, cur % C, m, sum);
+  }
+  if (POST) {
+    // the backward scan of the prefix 0 .. R, from its end down to row w:  b_R = 0;  b_r[j] = lse_n (b_{r+1}[n] + E[r+1, n] + T(j, n)), renormalised per step
+    const int C4 = (C + 3) & ~3;
+    const float ninf = -INFINITY;
+    const float log_c = logf((float)C);
+    const bool loads = ln.live && ln.m;
+    const int slot = ln.m * 32 + ln.c;
+    s_u[threadIdx.x] = ninf;                                       // (ordered before the planes' stores by the loop's first barrier)
+    float v = ln.live ? 0.f : ninf;
+    float l_next = loads ? rows.logits(R)[ln.c] : ninf;
+    float z0_next = rows.gate(R)[0], z1_next = rows.gate(R)[1];
+    for (int64_t r = R; r > w; --r) {                              // b_{r-1} from b_r and row r
+      const float l = l_next, z0 = z0_next, z1 = z1_next;
+      if (r - 1 > w) {
+        l_next = loads ? rows.logits(r - 1)[ln.c] : ninf;
+        z0_next = rows.gate(r - 1)[0];
+        z1_next = rows.gate(r - 1)[1];
+      }
+      const float e = track_gated_emission(ln, l, z0, z1, log_c);
+      __syncthreads();                                             // every lane has read s_u
+      if (ln.live) s_u[slot] = v + e;
+      __syncthreads();
+      float m;
+      v = track_gated_fb_step(ln, s_u, C4, true, lam, mu, 0.f, m);
+    }
+    if (ln.live) s_b[ln.j] = v;
+    __syncthreads();
+    if (ln.j == 0) {
+      int best;
+      float pbest, mean, ps;
+      track_gated_combine_row(rows.a(w), s_b, C, grid, out.post_lag + (int64_t)i * out.ldp, best, pbest, mean, ps);
+      out.p_sync_lag[i] = ps;
+      out.cls_post_lag[i] = best;
+      out.conf_post_lag[i] = pbest;
+      out.offset_mean_lag[i] = mean;
+    }
+  }
+}
+
+template <bool POST>
+__global__ __launch_bounds__(64) void track_gated_stream_readout_kernel(TrackGatedStreamRows rows, float lam, float mu, const float* __restrict__ grid, int64_t w0,
+                                                                         int n_commit, int n_tail, int64_t t_last, TrackGatedStreamOut out) {
+  __shared__ __attribute__((aligned(16))) float s_u[64];
+  __shared__ float s_b[64];
+  __shared__ int s_tail[256];
+  track_gated_stream_readout_body<POST>(rows, lam, mu, grid, w0, n_commit, n_tail, t_last, out, (int)blockIdx.x, s_u, s_b, s_tail);
+}
+
+// Ring row j of a push: new row k = k0 + j (row t_old + k of the stream) into slot (t_old + k) % lag of the rings: C offset logits, 2 gate logits, 2C back pointers
+// and (posterior) 2C entries of a, one lane per entry.
+__device__ __forceinline__ void track_gated_stream_keep_body(const float* __restrict__ logits, int64_t ldl, const float* __restrict__ gate, int64_t ldg,
+                                                             const uint8_t* __restrict__ bp_new, const float* __restrict__ a_new, int k0, int64_t t_old, int C, int lag,
+                                                             int posterior, unsigned char* __restrict__ state, int j) {
+  const TrackGatedStreamLayout lay(C, lag, posterior != 0);
+  const int c = threadIdx.x;
+  const int S = 2 * C;
+  if (c >= S) return;
+  const int64_t k = k0 + (int64_t)j;
+  const int64_t ring = (t_old + k) % lag;
+  if (c < C) reinterpret_cast<float*>(state + lay.lg_ring)[ring * C + c] = logits[k * ldl + c];
+  if (c < 2) reinterpret_cast<float*>(state + lay.gz_ring)[ring * 2 + c] = gate[k * ldg + c];
+  (state + lay.bp_ring)[ring * S + c] = bp_new[k * S + c];
+  if (posterior) reinterpret_cast<float*>(state + lay.a_ring)[ring * S + c] = a_new[k * S + c];
+}
+
+// Block j: ring row j.
+__global__ __launch_bounds__(64) void track_gated_stream_keep_kernel(const float* __restrict__ logits, int64_t ldl, const float* __restrict__ gate, int64_t ldg,
+                                                                      const uint8_t* __restrict__ bp_new, const float* __restrict__ a_new, int k0, int64_t t_old, int C,
+                                                                      int lag, int posterior, unsigned char* __restrict__ state) {
+  track_gated_stream_keep_body(logits, ldl, gate, ldg, bp_new, a_new, k0, t_old, C, lag, posterior, state, (int)blockIdx.x);
+}
+
+// What sf_track_stream_push and track_gated_args_ok refuse, for the two gated stream launchers: C (2 .. 32), lag, lam, mu and - when there are rows - the strides.
+static bool track_gated_stream_args_ok(const char* who, int C, int lag, int n, int64_t ldl, int64_t ldg, float lam, float mu) {
+  if (lag < 0 || lag > 255) { sf_set_error("%s: lag = %d windows out of range (0 .. 255)", who, lag); return false; }
+  if (n < 0 || n > TRACK_STREAM_MAX_PUSH) { sf_set_error("%s: n = %d rows in one push (0 .. %d: split a longer catch-up)", who, n, TRACK_STREAM_MAX_PUSH); return false; }
+  return track_gated_args_ok(who, n, C, n ? ldl : (int64_t)C, n ? ldg : (int64_t)2, lam, mu);
+}
+
+extern "C" int sf_track_stream_gated_bytes(int C, int lag, int posterior) {
+  if (!track_gated_stream_args_ok("sf_track_stream_gated_bytes", C, lag, 0, 0, 0, 0.f, 0.f)) return -1;
+  return (int)TrackGatedStreamLayout(C, lag, posterior != 0).total;      // at most 16 + 512 + 255 * (32 * 4 + 8 + 64 * 4 + 64)
+}
+
+// the workspace of a gated push: [posterior: a (n, 2C) fp32][end (n) int32][back pointers (n, 2C) bytes] - TrackPoolWorkspace over rows of 2C
+extern "C" int sf_track_stream_gated_workspace_bytes(int C, int n, int posterior) {
+  if (!track_gated_stream_args_ok("sf_track_stream_gated_workspace_bytes", C, 0, n, C, 2, 0.f, 0.f)) return -1;
+  return (int)(((posterior ? (int64_t)n * 2 * C * 4 : 0) + (int64_t)n * 4 + (int64_t)n * 2 * C + 15) & ~(int64_t)15);      // at most 2^20 * 324
+}
+
+extern "C" int sf_track_pool_gated_workspace_bytes(int C, int total_rows, int posterior) { return sf_track_stream_gated_workspace_bytes(C, total_rows, posterior); }
+
+extern "C" int sf_track_stream_push_gated(void* state, int C, int lag, int posterior, int64_t rows_done, const float* logits, int64_t ldl, const float* gate_logits,
+                                          int64_t ldg, int n, float lam, float mu, const float* grid, int final, int32_t* cls_raw, float* conf_raw, float* sync_raw,
+                                          int32_t* cls_lag, int32_t* sync_lag, float* conf_lag, float* post_lag, int64_t ldp, float* p_sync_lag, int32_t* cls_post_lag,
+                                          float* conf_post_lag, float* offset_mean_lag, int32_t* cls_tail, int32_t* sync_tail, float* conf_tail, float* log_z,
+                                          void* workspace, void* stream) {
+  const char* who = "sf_track_stream_push_gated";
+  if (!track_gated_stream_args_ok(who, C, lag, n, ldl, ldg, lam, mu)) return -1;
+  SF_CHECK_ARG(state, "%s: null state", who);
+  SF_CHECK_ARG(rows_done >= 0 && rows_done <= (INT64_MAX >> 1), "%s: %lld rows pushed so far", who, (long long)rows_done);
+  const int64_t t_old = rows_done, t_new = rows_done + n;
+  const int64_t done_old = t_old > lag ? t_old - lag : 0;                                   // windows committed before this push
+  const int64_t done_new = final ? t_new : (t_new > lag ? t_new - lag : 0);
+  const int64_t n_commit = done_new - done_old, n_tail = t_new - done_new;
+  if (t_new == 0) return 0;
+  SF_CHECK_ARG(n == 0 || (logits && gate_logits && cls_raw && conf_raw && sync_raw && workspace), "%s: null pointer (new rows)", who);
+  SF_CHECK_ARG(n_commit == 0 || (cls_lag && sync_lag && conf_lag), "%s: null pointer (committed block)", who);
+  SF_CHECK_ARG(n_tail == 0 || (cls_tail && sync_tail && conf_tail), "%s: null pointer (tail)", who);
+  if (posterior) {
+    SF_CHECK_ARG(log_z, "%s: null log_z", who);
+    SF_CHECK_ARG(n_commit == 0 || (grid && post_lag && p_sync_lag && cls_post_lag && conf_post_lag && offset_mean_lag && ldp >= C),
+                 "%s: null pointer or post row stride ldp = %lld below C = %d (posterior block)", who, (long long)ldp, C);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const TrackGatedStreamLayout lay(C, lag, posterior != 0);
+  unsigned char* st = static_cast<unsigned char*>(state);
+  const TrackPoolWorkspace ws(static_cast<unsigned char*>(workspace), 2 * C, n, posterior != 0);
+  if (n > 0) {
+    hipLaunchKernelGGL(track_gated_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, logits, ldl, gate_logits, ldg, n, C, cls_raw, conf_raw, sync_raw);
+    SF_LAUNCH_CHECK();
+  }
+  if (n > 0 || posterior) {                                        // (n == 0 with the posterior: log_z of the prefix so far, from the carried a)
+    hipLaunchKernelGGL(track_gated_stream_scan_kernel, dim3(posterior ? 2 : 1), dim3(64), 0, s, logits, ldl, gate_logits, ldg, n, C, lam, mu, t_old, st, lag, posterior,
+                       ws.bp, ws.a, ws.end, log_z);
+    SF_LAUNCH_CHECK();
+  }
+  if (n_commit + n_tail > 0) {
+    TrackGatedStreamRows rows;
+    track_gated_rows_fill(rows, lay, st, logits, ldl, gate_logits, ldg, ws.bp, ws.a, ws.end, t_old, lag, C);
+    const TrackGatedStreamOut out{cls_lag, sync_lag, conf_lag, post_lag, ldp, p_sync_lag, cls_post_lag, conf_post_lag, offset_mean_lag, cls_tail, sync_tail, conf_tail};
+    const dim3 g((unsigned)(n_commit + (n_tail > 0 ? 1 : 0)));
+    if (posterior)
+      hipLaunchKernelGGL(track_gated_stream_readout_kernel<true>, g, dim3(64), 0, s, rows, lam, mu, grid, done_old, (int)n_commit, (int)n_tail, t_new - 1, out);
+    else
+      hipLaunchKernelGGL(track_gated_stream_readout_kernel<false>, g, dim3(64), 0, s, rows, lam, mu, grid, done_old, (int)n_commit, (int)n_tail, t_new - 1, out);
+    SF_LAUNCH_CHECK();
+  }
+  const int keep = n < lag ? n : lag;
+  if (keep > 0) {
+    hipLaunchKernelGGL(track_gated_stream_keep_kernel, dim3((unsigned)keep), dim3(64), 0, s, logits, ldl, gate_logits, ldg, (const uint8_t*)ws.bp, (const float*)ws.a,
+                       n - keep, t_old, C, lag, posterior, st);
+    SF_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+// The pool's kernels: sf_track_pool_push's mapping (blockIdx.y = the table row, blockIdx.x = the stream's own work item), every block running the gated bodies above on
+// its stream's context.  Stream e's gate rows are rows [row0, row0 + n) of the gate matrix, as its offset rows are of logits.
+__global__ __launch_bounds__(64) void track_gated_pool_scan_kernel(const int64_t* __restrict__ table, unsigned char* __restrict__ states, int64_t state_stride,
+                                                                    const float* __restrict__ logits, int64_t ldl, const float* __restrict__ gate, int64_t ldg, int C,
+                                                                    float lam, float mu, int lag, int posterior, unsigned char* __restrict__ workspace, int total_rows,
+                                                                    float* __restrict__ log_z) {
+  __shared__ __attribute__((aligned(16))) float s_u[64];
+  const TrackPoolEntry e(table, blockIdx.y, lag);
+  const bool fwd = blockIdx.x == 1;
+  if (e.t_new == 0 || (e.n == 0 && !fwd)) return;                  // an empty stream; nothing to scan (n == 0 with the posterior: log_z from the carried a)
+  const TrackPoolWorkspace ws(workspace, 2 * C, total_rows, posterior != 0);
+  track_gated_stream_scan_body(logits + e.row0 * ldl, ldl, gate + e.row0 * ldg, ldg, (int)e.n, C, lam, mu, e.t_old, states + e.slot * state_stride, lag, posterior,
+                               ws.bp + e.row0 * 2 * C, ws.a + e.row0 * 2 * C, ws.end + e.row0, log_z + blockIdx.y, fwd, s_u);
+}
+
+template <bool POST>
+__global__ __launch_bounds__(64) void track_gated_pool_readout_kernel(const int64_t* __restrict__ table, const unsigned char* __restrict__ states, int64_t state_stride,
+                                                                       const float* __restrict__ logits, int64_t ldl, const float* __restrict__ gate, int64_t ldg, int C,
+                                                                       float lam, float mu, int lag, const float* __restrict__ grid,
+                                                                       const unsigned char* __restrict__ workspace, int total_rows, TrackGatedStreamOut out) {
+  __shared__ __attribute__((aligned(16))) float s_u[64];
+  __shared__ float s_b[64];
+  __shared__ int s_tail[256];
+  const TrackPoolEntry e(table, blockIdx.y, lag);
+  if ((int64_t)blockIdx.x >= e.readout_blocks()) return;
+  const TrackGatedStreamLayout lay(C, lag, POST);
+  const TrackPoolWorkspace ws(const_cast<unsigned char*>(workspace), 2 * C, total_rows, POST);
+  TrackGatedStreamRows rows;
+  track_gated_rows_fill(rows, lay, states + e.slot * state_stride, logits + e.row0 * ldl, ldl, gate + e.row0 * ldg, ldg, ws.bp + e.row0 * 2 * C, ws.a + e.row0 * 2 * C,
+                        ws.end + e.row0, e.t_old, lag, C);
+  track_gated_stream_readout_body<POST>(rows, lam, mu, grid, e.done_old, (int)e.n_commit, (int)e.n_tail, e.t_new - 1, out.at(e.commit0, e.tail0), (int)blockIdx.x, s_u, s_b,
+                                        s_tail);
+}
+
+__global__ __launch_bounds__(64) void track_gated_pool_keep_kernel(const int64_t* __restrict__ table, unsigned char* __restrict__ states, int64_t state_stride,
+                                                                    const float* __restrict__ logits, int64_t ldl, const float* __restrict__ gate, int64_t ldg, int C,
+                                                                    int lag, int posterior, const unsigned char* __restrict__ workspace, int total_rows) {
+  const TrackPoolEntry e(table, blockIdx.y, lag);
+  const int64_t keep = e.keep(lag);
+  if ((int64_t)blockIdx.x >= keep) return;
+  const TrackPoolWorkspace ws(const_cast<unsigned char*>(workspace), 2 * C, total_rows, posterior != 0);
+  track_gated_stream_keep_body(logits + e.row0 * ldl, ldl, gate + e.row0 * ldg, ldg, ws.bp + e.row0 * 2 * C, ws.a + e.row0 * 2 * C, (int)(e.n - keep), e.t_old, C, lag,
+                               posterior, states + e.slot * state_stride, (int)blockIdx.x);
+}
+
+extern "C" int sf_track_pool_push_gated(void* states, int64_t state_stride, int n_slots, int C, int lag, int posterior, const int64_t* table_host,
+                                        const int64_t* table_dev, int n_active, const float* logits, int64_t ldl, const float* gate_logits, int64_t ldg, int total_rows,
+                                        float lam, float mu, const float* grid, int32_t* cls_raw, float* conf_raw, float* sync_raw, int32_t* cls_lag, int32_t* sync_lag,
+                                        float* conf_lag, float* post_lag, int64_t ldp, float* p_sync_lag, int32_t* cls_post_lag, float* conf_post_lag,
+                                        float* offset_mean_lag, int32_t* cls_tail, int32_t* sync_tail, float* conf_tail, float* log_z, void* workspace, void* stream) {
+  const char* who = "sf_track_pool_push_gated";
+  SF_CHECK_ARG(total_rows >= 0 && total_rows <= TRACK_STREAM_MAX_PUSH, "%s: total_rows = %d rows in one push (0 .. %d)", who, total_rows, TRACK_STREAM_MAX_PUSH);
+  if (!track_gated_stream_args_ok(who, C, lag, 0, 0, 0, lam, mu)) return -1;
+  SF_CHECK_ARG(n_active >= 1 && n_active <= TRACK_POOL_MAX_ACTIVE, "%s: n_active = %d streams in one push (1 .. %d)", who, n_active, TRACK_POOL_MAX_ACTIVE);
+  SF_CHECK_ARG(n_slots >= 1, "%s: n_slots = %d", who, n_slots);
+  SF_CHECK_ARG(states && table_host && table_dev, "%s: null pointer (states or table)", who);
+  const TrackGatedStreamLayout lay(C, lag, posterior != 0);
+  SF_CHECK_ARG(state_stride >= lay.total && state_stride % 16 == 0, "%s: state stride %lld: a multiple of 16, at least %lld bytes", who, (long long)state_stride,
+               (long long)lay.total);
+  TrackPoolTotals tot;
+  if (track_pool_table_check(who, table_host, n_active, n_slots, total_rows, lag, posterior, tot)) return -1;
+  SF_CHECK_ARG(tot.sum_n == 0 || ldl >= C, "%s: row stride ldl = %lld below C = %d", who, (long long)ldl, C);
+  SF_CHECK_ARG(tot.sum_n == 0 || ldg >= 2, "%s: gate row stride ldg = %lld below 2", who, (long long)ldg);
+  SF_CHECK_ARG(tot.sum_n == 0 || (logits && gate_logits && cls_raw && conf_raw && sync_raw && workspace), "%s: null pointer (new rows)", who);
+  SF_CHECK_ARG(tot.sum_commit == 0 || (cls_lag && sync_lag && conf_lag), "%s: null pointer (committed block)", who);
+  SF_CHECK_ARG(tot.sum_tail == 0 || (cls_tail && sync_tail && conf_tail), "%s: null pointer (tail)", who);
+  if (posterior) {
+    SF_CHECK_ARG(!tot.scan || log_z, "%s: null log_z", who);
+    SF_CHECK_ARG(tot.sum_commit == 0 || (grid && post_lag && p_sync_lag && cls_post_lag && conf_post_lag && offset_mean_lag && ldp >= C),
+                 "%s: null pointer or post row stride ldp = %lld below C = %d (posterior block)", who, (long long)ldp, C);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  unsigned char* st = static_cast<unsigned char*>(states);
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  if (tot.sum_n > 0) {                                             // one thread per row of the packed matrices
+    hipLaunchKernelGGL(track_gated_rows_kernel, dim3((unsigned)((total_rows + 255) / 256)), dim3(256), 0, s, logits, ldl, gate_logits, ldg, total_rows, C, cls_raw,
+                       conf_raw, sync_raw);
+    SF_LAUNCH_CHECK();
+  }
+  if (tot.scan) {
+    hipLaunchKernelGGL(track_gated_pool_scan_kernel, dim3(posterior ? 2 : 1, (unsigned)n_active), dim3(64), 0, s, table_dev, st, state_stride, logits, ldl, gate_logits, ldg,
+                       C, lam, mu, lag, posterior, ws, total_rows, log_z);
+    SF_LAUNCH_CHECK();
+  }
+  if (tot.max_read > 0) {
+    const TrackGatedStreamOut out{cls_lag, sync_lag, conf_lag, post_lag, ldp, p_sync_lag, cls_post_lag, conf_post_lag, offset_mean_lag, cls_tail, sync_tail, conf_tail};
+    const dim3 g((unsigned)tot.max_read, (unsigned)n_active);
+    if (posterior)
+      hipLaunchKernelGGL(track_gated_pool_readout_kernel<true>, g, dim3(64), 0, s, table_dev, (const unsigned char*)st, state_stride, logits, ldl, gate_logits, ldg, C, lam, mu,
+                         lag, grid, (const unsigned char*)ws, total_rows, out);
+    else
+      hipLaunchKernelGGL(track_gated_pool_readout_kernel<false>, g, dim3(64), 0, s, table_dev, (const unsigned char*)st, state_stride, logits, ldl, gate_logits, ldg, C, lam, mu,
+                         lag, grid, (const unsigned char*)ws, total_rows, out);
+    SF_LAUNCH_CHECK();
+  }
+  if (tot.max_keep > 0) {
+    hipLaunchKernelGGL(track_gated_pool_keep_kernel, dim3((unsigned)tot.max_keep, (unsigned)n_active), dim3(64), 0, s, table_dev, st, state_stride, logits, ldl, gate_logits,
+                       ldg, C, lag, posterior, (const unsigned char*)ws, total_rows);
+    SF_LAUNCH_CHECK();
+  }
   return 0;
 }

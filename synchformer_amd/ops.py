@@ -755,7 +755,8 @@ def track_posterior_gated(logits: torch.Tensor, gate_logits: torch.Tensor, lam: 
 
 class TrackStreamState:
     """The carried state of one stream's fixed-lag read-out (sf_track_stream_push): `buf` the opaque device buffer, `rows` the rows pushed so far (host count),
-    `closed` after a final push.  Its size does not depend on `rows`."""
+    `closed` after a final push.  Its size does not depend on `rows`.  `gated`: whether the buffer has the gated layout (TrackGatedStreamState)."""
+    gated = False
 
     def __init__(self, buf: torch.Tensor, C: int, lag: int, posterior: bool):
         self.buf, self.C, self.lag, self.posterior, self.rows, self.closed = buf, int(C), int(lag), bool(posterior), 0, False
@@ -787,6 +788,7 @@ def track_stream_push(state: TrackStreamState, logits: torch.Tensor, lam: float,
     w0 + i on the Viterbi path of rows 0 .. w0 + i + lag, never revised), the tail is the path of everything pushed so far on the m = min(lag, rows) windows not yet
     committed (cls_tail[-1]: the current offset).  final=True commits the tail from the whole prefix and closes the state.  The posterior fields are None without
     posterior.  Output sizes are host arithmetic; nothing is read back or synchronised, the state advances on the device in stream order."""
+    _track_kind(state, False, 'track_stream_push')
     assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.shape[1] == state.C, f'logits {tuple(logits.shape)} for a stream of {state.C} classes'
     if state.closed:
         raise RuntimeError('track_stream_push: the stream was closed by a final push')
@@ -851,7 +853,9 @@ def track_pool_plan(rows, counts, lag: int, final, slots=None) -> TrackPoolPlan:
 
 class TrackPoolState:
     """The carried states of a pool of streams (sf_track_pool_push): `buf` uint8 (n_slots, bytes) on the device, slot i the state of one stream
-    (sf_track_stream_push's layout); `rows[i]` the rows pushed into slot i so far and `closed[i]` after its final push (host counts)."""
+    (sf_track_stream_push's layout); `rows[i]` the rows pushed into slot i so far and `closed[i]` after its final push (host counts).  `gated`: whether the slots
+    have the gated layout (TrackGatedPoolState)."""
+    gated = False
 
     def __init__(self, buf: torch.Tensor, C: int, lag: int, posterior: bool):
         self.buf, self.C, self.lag, self.posterior = buf, int(C), int(lag), bool(posterior)
@@ -873,6 +877,24 @@ def track_pool_state(n_slots: int, C: int, lag: int, posterior: bool, device) ->
     return TrackPoolState(torch.zeros(int(n_slots), nbytes, device=device, dtype=torch.uint8), C, lag, posterior)
 
 
+def _track_pool_table(who: str, state: TrackPoolState, slots, counts, final, total: int):
+    """The host rules of a pool push and its descriptor table -> (slots, counts, final as a set, plan, the pinned host table, its device copy): distinct open slots of
+    the state, counts that add up to the `total` rows, track_pool_plan, one non-blocking upload from a FRESH pinned tensor (see track_pool_push)."""
+    slots, counts, final = [int(x) for x in slots], [int(x) for x in counts], {int(x) for x in final}
+    if len(slots) != len(counts) or not 1 <= len(slots) <= TRACK_POOL_MAX_ACTIVE:
+        raise ValueError(f'{who}: {len(slots)} slots, {len(counts)} counts (1 .. {TRACK_POOL_MAX_ACTIVE} streams in one push)')
+    if len(set(slots)) != len(slots) or not all(0 <= x < state.n_slots for x in slots) or not final <= set(slots):
+        raise ValueError(f'{who}: slots {slots} (final {sorted(final)}): distinct, below {state.n_slots}, the final ones among them')
+    if any(state.closed[x] for x in slots):
+        raise RuntimeError(f'{who}: slots {[x for x in slots if state.closed[x]]} were closed by a final push (reopen them)')
+    if min(counts) < 0 or sum(counts) != total:
+        raise ValueError(f'{who}: counts {counts} for {total} rows of logits')
+    plan = track_pool_plan([state.rows[x] for x in slots], counts, state.lag, [x in final for x in slots], slots)
+    host = torch.empty(len(slots), TRACK_POOL_ROW, dtype=torch.int64, pin_memory=True)
+    host.copy_(plan.table)
+    return slots, counts, final, plan, host, host.to(state.buf.device, non_blocking=True)
+
+
 def track_pool_push(state: TrackPoolState, slots, logits: torch.Tensor, counts, lam: float, grid: Optional[torch.Tensor] = None, final=(),
                     post: Optional[torch.Tensor] = None) -> list:
     """One push for many streams (sf_track_pool_push): logits fp32 (total, C) on the state's device with unit column stride, the new rows of all named streams
@@ -882,26 +904,15 @@ def track_pool_push(state: TrackPoolState, slots, logits: torch.Tensor, counts, 
     with one non-blocking copy on the current stream: no buffer is shared between two pushes, so a later push cannot race the upload (torch's pinned-memory
     allocator keeps the block until the copy has run).  Nothing is read back or synchronised.  `post` (posterior only), if given, is written instead of a fresh
     tensor: fp32 (total_commit, C) - track_pool_plan's count - with unit column stride and any row stride >= C."""
+    _track_kind(state, False, 'track_pool_push')
     C, dev = state.C, state.buf.device
-    slots, counts, final = [int(x) for x in slots], [int(x) for x in counts], {int(x) for x in final}
     assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.shape[1] == C, f'logits {tuple(logits.shape)} for streams of {C} classes'
-    if len(slots) != len(counts) or not 1 <= len(slots) <= TRACK_POOL_MAX_ACTIVE:
-        raise ValueError(f'track_pool_push: {len(slots)} slots, {len(counts)} counts (1 .. {TRACK_POOL_MAX_ACTIVE} streams in one push)')
-    if len(set(slots)) != len(slots) or not all(0 <= x < state.n_slots for x in slots) or not final <= set(slots):
-        raise ValueError(f'track_pool_push: slots {slots} (final {sorted(final)}): distinct, below {state.n_slots}, the final ones among them')
-    if any(state.closed[x] for x in slots):
-        raise RuntimeError(f'track_pool_push: slots {[x for x in slots if state.closed[x]]} were closed by a final push (reopen them)')
     total = logits.shape[0]
-    if min(counts) < 0 or sum(counts) != total:
-        raise ValueError(f'track_pool_push: counts {counts} for {total} rows of logits')
+    slots, counts, final, plan, host, table = _track_pool_table('track_pool_push', state, slots, counts, final, total)
     assert total == 0 or (logits.device == dev and logits.stride(1) == 1), 'logits: on the state\'s device, unit column stride'
     if state.posterior:
         assert grid is not None and grid.dtype == torch.float32 and grid.device == dev and grid.shape == (C,) and grid.is_contiguous(), f'a grid for {C} classes'
-    plan = track_pool_plan([state.rows[x] for x in slots], counts, state.lag, [x in final for x in slots], slots)
     K, M, n_act = plan.total_commit, plan.total_tail, len(slots)
-    host = torch.empty(n_act, TRACK_POOL_ROW, dtype=torch.int64, pin_memory=True)
-    host.copy_(plan.table)
-    table = host.to(dev, non_blocking=True)
     i32 = dict(device=dev, dtype=torch.int32)
     f32 = dict(device=dev, dtype=torch.float32)
     cls_raw, conf_raw = torch.empty(total, **i32), torch.empty(total, **f32)
@@ -935,6 +946,149 @@ def track_pool_push(state: TrackPoolState, slots, logits: torch.Tensor, counts, 
     fields = [cls_raw.split(ns), conf_raw.split(ns), cls_lag.split(ks), conf_lag.split(ks), cls_tail.split(ms), conf_tail.split(ms)]
     fields += [post.split(ks), cls_post.split(ks), conf_post.split(ks), mean.split(ks), log_z.split(1)] if state.posterior else [none] * 5
     outs = [TrackStreamOut(b[0], *views) for b, views in zip(plan.blocks, zip(*fields))]
+    for slot, n in zip(slots, ns):
+        state.rows[slot] += n
+        state.closed[slot] = slot in final
+    return outs
+
+
+class TrackGatedStreamState(TrackStreamState):
+    """The carried state of one stream's GATED fixed-lag read-out (sf_track_stream_push_gated): TrackStreamState's fields over a buffer of
+    sf_track_stream_gated_bytes(C, lag, posterior) bytes, 2C wide.  track_stream_push refuses it, track_stream_push_gated refuses a TrackStreamState."""
+    gated = True
+
+
+class TrackGatedPoolState(TrackPoolState):
+    """The carried states of a pool of GATED streams (sf_track_pool_push_gated): TrackPoolState's fields, each slot a gated state."""
+    gated = True
+
+
+
+def _track_kind(state, gated: bool, who: str):
+    """A state knows whether it is gated; a push of the other kind raises."""
+    if bool(getattr(state, 'gated', False)) != gated:
+        raise TypeError(f'{who}: the state is {"gated (use the *_gated push)" if not gated else "not gated (use the push without _gated)"}: the two layouts differ')
+
+
+def _gated_stream_bytes(C: int, lag: int, posterior: bool) -> int:
+    nbytes = _lib.load().sf_track_stream_gated_bytes(int(C), int(lag), int(bool(posterior)))
+    if nbytes < 0:
+        _lib.check(nbytes, 'sf_track_stream_gated_bytes')
+    return nbytes
+
+
+def track_stream_state_gated(C: int, lag: int, posterior: bool, device) -> TrackGatedStreamState:
+    """A fresh gated stream state for C classes (2 .. 32) and a decision lag of `lag` windows (0 .. 255): sf_track_stream_gated_bytes(C, lag, posterior) zeroed bytes."""
+    return TrackGatedStreamState(torch.zeros(_gated_stream_bytes(C, lag, posterior), device=device, dtype=torch.uint8), C, lag, posterior)
+
+
+def track_pool_state_gated(n_slots: int, C: int, lag: int, posterior: bool, device) -> TrackGatedPoolState:
+    """n_slots fresh gated stream states in one zeroed (n_slots, sf_track_stream_gated_bytes(C, lag, posterior)) buffer on `device`."""
+    if n_slots < 1:
+        raise ValueError(f'track_pool_state_gated: n_slots = {n_slots}')
+    return TrackGatedPoolState(torch.zeros(int(n_slots), _gated_stream_bytes(C, lag, posterior), device=device, dtype=torch.uint8), C, lag, posterior)
+
+
+TrackGatedStreamOut = namedtuple('TrackGatedStreamOut', TrackStreamOut._fields + ('sync_raw', 'sync_lag', 'sync_tail', 'p_sync_lag'))
+
+
+def _gated_push_inputs(who: str, C: int, dev, posterior: bool, logits: torch.Tensor, gate_logits: torch.Tensor, grid: Optional[torch.Tensor]) -> int:
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.shape[1] == C, f'{who}: logits {tuple(logits.shape)} for streams of {C} classes'
+    n = logits.shape[0]
+    assert gate_logits.dtype == torch.float32 and gate_logits.shape == (n, 2), f'{who}: gate logits of {tuple(gate_logits.shape)} for {n} rows'
+    assert n == 0 or (logits.device == dev and gate_logits.device == dev and logits.stride(1) == 1 and gate_logits.stride(1) == 1), \
+        'logits, gate_logits: on the state\'s device, unit column stride'
+    if posterior:
+        assert grid is not None and grid.dtype == torch.float32 and grid.device == dev and grid.shape == (C,) and grid.is_contiguous(), f'a grid for {C} classes'
+    return n
+
+
+def track_stream_push_gated(state: TrackGatedStreamState, logits: torch.Tensor, gate_logits: torch.Tensor, lam: float, mu: float, grid: Optional[torch.Tensor] = None,
+                            final: bool = False) -> TrackGatedStreamOut:
+    """Gated fixed-lag read-out of the next n rows of a stream (sf_track_stream_push_gated): logits fp32 (n, C) and gate_logits fp32 (n, 2) of the same
+    windows, on the state's device with unit column stride (n = 0 allowed) -> TrackGatedStreamOut: TrackStreamOut's fields read from the chain over (offset class,
+    synchronizable flag) - (cls_lag[i], sync_lag[i]) is window w0 + i on ops.track_decode_gated's path of rows 0 .. w0 + i + lag, post_lag / p_sync_lag[i] its row of
+    ops.track_posterior_gated on that prefix - plus sync_raw (n,) fp32, sync_lag (k,) int32, sync_tail (m,) int32 and p_sync_lag (k,) fp32 (None without posterior).
+    Counts, final and the no-read-back rule are track_stream_push's."""
+    _track_kind(state, True, 'track_stream_push_gated')
+    if state.closed:
+        raise RuntimeError('track_stream_push_gated: the stream was closed by a final push')
+    C, dev = state.C, state.buf.device
+    n = _gated_push_inputs('track_stream_push_gated', C, dev, state.posterior, logits, gate_logits, grid)
+    w0, k, m = track_stream_counts(state.rows, n, state.lag, final)
+    i32 = dict(device=dev, dtype=torch.int32)
+    f32 = dict(device=dev, dtype=torch.float32)
+    cls_raw, conf_raw, sync_raw = torch.empty(n, **i32), torch.empty(n, **f32), torch.empty(n, **f32)
+    cls_lag, sync_lag, conf_lag = torch.empty(k, **i32), torch.empty(k, **i32), torch.empty(k, **f32)
+    cls_tail, sync_tail, conf_tail = torch.empty(m, **i32), torch.empty(m, **i32), torch.empty(m, **f32)
+    post = p_sync = cls_post = conf_post = mean = log_z = None
+    if state.posterior:
+        post, p_sync, cls_post = torch.empty(k, C, **f32), torch.empty(k, **f32), torch.empty(k, **i32)
+        conf_post, mean = torch.empty(k, **f32), torch.empty(k, **f32)
+        log_z = torch.zeros(1, **f32)                                               # (stays 0 while the stream is empty: the empty product)
+    lib = _lib.load()
+    ws_bytes = lib.sf_track_stream_gated_workspace_bytes(C, n, int(state.posterior))
+    if ws_bytes < 0:
+        _lib.check(ws_bytes, 'sf_track_stream_gated_workspace_bytes')
+    ws = torch.empty(max(ws_bytes, 16), device=dev, dtype=torch.uint8)
+
+    def ptr(t):
+        return _dev(t, 'out') if t is not None and t.numel() else None
+
+    rc = lib.sf_track_stream_push_gated(_dev(state.buf, 'state'), C, state.lag, int(state.posterior), state.rows, ptr(logits), _ld(logits) if n else C, ptr(gate_logits),
+                                        _ld(gate_logits) if n else 2, n, float(lam), float(mu), _dev(grid, 'grid') if state.posterior else None, int(bool(final)),
+                                        ptr(cls_raw), ptr(conf_raw), ptr(sync_raw), ptr(cls_lag), ptr(sync_lag), ptr(conf_lag), ptr(post), C, ptr(p_sync), ptr(cls_post),
+                                        ptr(conf_post), ptr(mean), ptr(cls_tail), ptr(sync_tail), ptr(conf_tail), ptr(log_z), _dev(ws, 'workspace'), _stream())
+    _lib.check(rc, 'sf_track_stream_push_gated')
+    state.rows += n
+    state.closed = bool(final)
+    return TrackGatedStreamOut(w0, cls_raw, conf_raw, cls_lag, conf_lag, cls_tail, conf_tail, post, cls_post, conf_post, mean, log_z, sync_raw, sync_lag, sync_tail, p_sync)
+
+
+def track_pool_push_gated(state: TrackGatedPoolState, slots, logits: torch.Tensor, gate_logits: torch.Tensor, counts, lam: float, mu: float,
+                          grid: Optional[torch.Tensor] = None, final=(), post: Optional[torch.Tensor] = None) -> list:
+    """One gated push for many streams (sf_track_pool_push_gated): track_pool_push's arguments plus gate_logits fp32 (total, 2), packed like logits (the gate rows of a
+    stream are the rows of its offset logits), and mu -> one TrackGatedStreamOut per slot, views into the packed outputs, each equal bit for bit to
+    track_stream_push_gated on that stream alone.  The table, its upload and every host rule are track_pool_push's."""
+    _track_kind(state, True, 'track_pool_push_gated')
+    C, dev = state.C, state.buf.device
+    total = _gated_push_inputs('track_pool_push_gated', C, dev, state.posterior, logits, gate_logits, grid)
+    slots, counts, final, plan, host, table = _track_pool_table('track_pool_push_gated', state, slots, counts, final, total)
+    K, M, n_act = plan.total_commit, plan.total_tail, len(slots)
+    i32 = dict(device=dev, dtype=torch.int32)
+    f32 = dict(device=dev, dtype=torch.float32)
+    cls_raw, conf_raw, sync_raw = torch.empty(total, **i32), torch.empty(total, **f32), torch.empty(total, **f32)
+    cls_lag, sync_lag, conf_lag = torch.empty(K, **i32), torch.empty(K, **i32), torch.empty(K, **f32)
+    cls_tail, sync_tail, conf_tail = torch.empty(M, **i32), torch.empty(M, **i32), torch.empty(M, **f32)
+    assert post is None or state.posterior, 'post: only with the posterior'
+    p_sync = cls_post = conf_post = mean = log_z = None
+    if state.posterior:
+        if post is None:
+            post = torch.empty(K, C, **f32)
+        assert post.dtype == torch.float32 and post.shape == (K, C) and post.device == dev and (K == 0 or post.stride(1) == 1), f'post: fp32 ({K}, {C}), unit column stride'
+        p_sync, cls_post, conf_post, mean = torch.empty(K, **f32), torch.empty(K, **i32), torch.empty(K, **f32), torch.empty(K, **f32)
+        log_z = torch.zeros(n_act, **f32)                                           # (stays 0 for a stream that is still empty: the empty product)
+    lib = _lib.load()
+    ws_bytes = lib.sf_track_pool_gated_workspace_bytes(C, total, int(state.posterior))
+    if ws_bytes < 0:
+        _lib.check(ws_bytes, 'sf_track_pool_gated_workspace_bytes')
+    ws = torch.empty(max(ws_bytes, 16), device=dev, dtype=torch.uint8)
+
+    def ptr(t):
+        return _dev(t, 'out') if t is not None and t.numel() else None
+
+    rc = lib.sf_track_pool_push_gated(_dev(state.buf, 'states'), state.buf.stride(0), state.n_slots, C, state.lag, int(state.posterior), host.data_ptr(),
+                                      _dev(table, 'table'), n_act, ptr(logits), _ld(logits) if total else C, ptr(gate_logits), _ld(gate_logits) if total else 2, total,
+                                      float(lam), float(mu), _dev(grid, 'grid') if state.posterior else None, ptr(cls_raw), ptr(conf_raw), ptr(sync_raw), ptr(cls_lag),
+                                      ptr(sync_lag), ptr(conf_lag), ptr(post), _ld(post) if state.posterior and K else C, ptr(p_sync), ptr(cls_post), ptr(conf_post),
+                                      ptr(mean), ptr(cls_tail), ptr(sync_tail), ptr(conf_tail), ptr(log_z), _dev(ws, 'workspace'), _stream())
+    _lib.check(rc, 'sf_track_pool_push_gated')
+    ns, ks, ms = counts, [b[1] for b in plan.blocks], [b[2] for b in plan.blocks]
+    none = [None] * n_act
+    fields = [cls_raw.split(ns), conf_raw.split(ns), cls_lag.split(ks), conf_lag.split(ks), cls_tail.split(ms), conf_tail.split(ms)]
+    fields += [post.split(ks), cls_post.split(ks), conf_post.split(ks), mean.split(ks), log_z.split(1)] if state.posterior else [none] * 5
+    fields += [sync_raw.split(ns), sync_lag.split(ks), sync_tail.split(ms), p_sync.split(ks) if state.posterior else none]
+    outs = [TrackGatedStreamOut(b[0], *views) for b, views in zip(plan.blocks, zip(*fields))]
     for slot, n in zip(slots, ns):
         state.rows[slot] += n
         state.closed[slot] = slot in final

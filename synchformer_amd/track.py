@@ -22,6 +22,9 @@ confidence that carries the evidence of the whole recording, and an offset finer
     upd = stream.push(frames_1s, wave_1s)         # upd.cls_lag / offset_sec_lag: committed, never revised; upd.offset_sec_tail[-1]: the offset now
     upd = stream.flush()                          # end of the feed: the tail is committed
 
+    gated = OffsetTracker(engine, mel, gate=gate).stream(lag=16, gated=True)      # the live feed read over (offset class, synchronizable flag)
+    upd = gated.push(frames_1s, wave_1s)          # upd.sync_lag: 0 where the committed window says 'nothing to read here'; upd.p_sync_lag with posterior=True
+
     pool = tracker.pool(n_feeds=64, lag=16)       # many live feeds on one device: one tick = one batched pass for all of them
     a, b = pool.open(), pool.open()
     upds = pool.push({a: (frames_a, wave_a), b: (frames_b, wave_b)})     # {feed: OffsetUpdate}, each what the feed's own stream would return
@@ -114,7 +117,8 @@ class OffsetTracker:
     the same banks, start-aligned with offset window w; cls_path, conf_path, offset_sec_path and the posterior fields then come from the chain over (offset class,
     synchronizable flag), and gate_logits, sync_raw, sync_path, p_sync are filled.  mu: the cost of one change of the flag between neighbouring windows, in logit
     units.  mu = 2.0 is a DEFAULT, NOT A TUNED VALUE, as lam: choose both on held-out recordings of the domain.  A prior on the flag is a constant added to
-    gate_logits[:, 1] by the caller.  stream() and pool() do not take a gate yet."""
+    gate_logits[:, 1] by the caller.  stream() and pool() read a live feed through the same chain with gated=True (a carried state 2C wide) or, with
+    gated=False, as a tracker without a gate does; on a tracker with a gate the choice is explicit."""
 
     def __init__(self, engine, mel, hop_segments: int = 1, lam: float = 1.0, grid: Optional[torch.Tensor] = None, posterior: bool = False, gate=None,
                  mu: float = 2.0):
@@ -207,28 +211,39 @@ class OffsetTracker:
         banks = self.eng.extract_recording_from(lambda f0, f1: ingest.frames(raw_frames, f0, f1), ingest.n_frames(raw_frames.shape[0]), wave, self.mel, seg_chunk)
         return self.track_features(*banks, win_chunk=win_chunk)
 
-    def stream(self, lag: int = 16, seg_chunk: Optional[int] = None, ingest=None):
+    def stream(self, lag: int = 16, seg_chunk: Optional[int] = None, ingest=None, gated: Optional[bool] = None):
         """A live feed: push frames and samples as they arrive, get per push the windows that became final.  lag: window w is committed once
         `lag` more windows have arrived (0 .. 255), as the class of w on the Viterbi path of everything up to window w + lag - a decision delay of
         lag * hop * 0.32 s.  lag = 16 is a DEFAULT, NOT A TUNED VALUE (as lam): how far back a later window still changes the decision depends on lam and on
         the domain's logits; choose it on held-out recordings.  lag >= the number of windows gives the offline path at flush().  seg_chunk: as in track().
         ingest: an ingest.RecordingIngest - push then takes frames and samples as decoded (native frame rate, size, sample rate; track_raw's layouts).  An ingest
-        with programmes gives a ProgrammeStream: push / flush return one OffsetUpdate per programme."""
-        self._no_gate('stream')
+        with programmes gives a ProgrammeStream: push / flush return one OffsetUpdate per programme.
+        gated, on a tracker with a gate: True reads the feed out over (offset class, synchronizable flag) - the committed windows are those of the gated
+        offline read-out of the prefix 0 .. w + lag, and every OffsetUpdate carries gate_logits, sync_raw, sync_lag, sync_tail (p_sync_lag with the posterior);
+        False gives the stream of a tracker without a gate; None (the default) raises NotImplementedError: the choice is explicit.  On a tracker without a gate
+        gated=True is a ValueError."""
+        gated = self._gate_choice('stream', gated)
         if getattr(ingest, 'programmes', None) is not None:
-            return ProgrammeStream(self, lag, seg_chunk, ingest)
-        return OffsetStream(self, lag, seg_chunk, ingest)
+            return ProgrammeStream(self, lag, seg_chunk, ingest, gated=gated)
+        return OffsetStream(self, lag, seg_chunk, ingest, gated=gated)
 
-    def pool(self, n_feeds: int, lag: int = 16, seg_chunk: Optional[int] = None) -> 'OffsetStreamPool':
+    def pool(self, n_feeds: int, lag: int = 16, seg_chunk: Optional[int] = None, gated: Optional[bool] = None) -> 'OffsetStreamPool':
         """Up to `n_feeds` live feeds at once: each feed is what stream(lag, seg_chunk) is, but one push() advances all named feeds together - their
-        new segments share the towers' launch groups, their new windows the sync transformer's passes, their read-outs one ops.track_pool_push."""
-        self._no_gate('pool')
-        return OffsetStreamPool(self, n_feeds, lag, seg_chunk)
+        new segments share the towers' launch groups, their new windows the sync transformer's passes, their read-outs one ops.track_pool_push.  gated: as stream()'s
+        (True: the gate's 13-segment windows cross its sync transformer in passes of their own, the read-out is one ops.track_pool_push_gated)."""
+        return OffsetStreamPool(self, n_feeds, lag, seg_chunk, gated=self._gate_choice('pool', gated))
 
-    def _no_gate(self, who: str):
-        if self.gate is not None:
-            raise NotImplementedError(f'OffsetTracker.{who}: the fixed-lag read-outs carry a state C wide, a gate needs 2C (DESIGN 3.20, out of scope there): build the '
-                                      'tracker without a gate for live feeds')
+    def _gate_choice(self, who: str, gated: Optional[bool]) -> bool:
+        """Whether a live read-out runs through the gate: an explicit choice on a tracker that has one."""
+        if self.gate is None:
+            if gated:
+                raise ValueError(f'OffsetTracker.{who}(gated=True): the tracker has no gate (OffsetTracker(..., gate=<an engine with the syncability head>))')
+            return False
+        if gated is None:
+            raise NotImplementedError(f'OffsetTracker.{who}: this tracker has a gate, and the offline read-out of DESIGN 3.20 does not decide how a live feed is read: '
+                                      f'pass gated=True for the fixed-lag read-out over (offset class, synchronizable flag) (DESIGN 3.21, a carried state 2C wide) or '
+                                      f'gated=False for the one a tracker without a gate gives')
+        return bool(gated)
 
 
 @dataclass
@@ -257,6 +272,14 @@ class OffsetUpdate:
     offset_sec_post_lag: Optional[torch.Tensor] = None  # (k,) fp32: grid[cls_post_lag]
     offset_sec_mean_lag: Optional[torch.Tensor] = None  # (k,) fp32
     log_z: Optional[torch.Tensor] = None               # (1,) fp32: that of all the windows so far
+    # the gate (stream / pool with gated=True); None without it.  Optional attributes set by the feed and deliberately NOT dataclass fields, as
+    # OffsetTrack's: the field list and the positional constructor above stay what they were.  cls_lag, conf_lag, cls_tail, the posterior fields then come from the
+    # chain over (offset class, synchronizable flag)
+    gate_logits = None               # (n, 2) fp32: the syncability head on the new windows' first gate.n_window segments
+    sync_raw = None                  # (n,) fp32: sigmoid(z1 - z0)
+    sync_lag = None                  # (k,) int32: the flag of the committed windows, 1 = synchronizable (0: nothing to read here)
+    sync_tail = None                 # (m,) int32: the flag along the tail
+    p_sync_lag = None                # (k,) fp32: the flag's marginal given windows 0 .. w + lag (with posterior=True)
 
 
 def pool_schedule(feeds, hop: int = 1, seg_chunk: int = 224, win_chunk: int = 256) -> dict:
@@ -291,8 +314,10 @@ class _Feed:
     """What one live feed carries on the host and the steps of one advance - accept, (towers), (windows), (read-out), trim, update - shared by OffsetStream (one feed,
     its own launches) and OffsetStreamPool (many feeds, the three device steps batched across them)."""
 
-    def __init__(self, tracker: 'OffsetTracker', ingest=None):
-        self.tracker = tracker
+    def __init__(self, tracker: 'OffsetTracker', ingest=None, gated: bool = False):
+        if gated and tracker.gate is None:
+            raise ValueError('a gated feed needs a tracker with a gate')
+        self.tracker, self.gated = tracker, bool(gated)
         dev = tracker.eng.dev
         self._ingest = None if ingest is None else ingest.stream()
         self._frames = torch.empty(0, 3, 224, 224, device=dev, dtype=torch.uint8)
@@ -350,8 +375,9 @@ class _Feed:
             self._vfeat, self._afeat, self._s0 = self._vfeat[k:], self._afeat[k:], g['features_from']
         self.n_segments, self.n_windows = g['new_segments'][1], g['new_windows'][1]
 
-    def _update(self, out, logits: torch.Tensor, w0: int, w1: int) -> 'OffsetUpdate':
-        """The read-out of this advance (an ops.TrackStreamOut) and its logits (windows w0 .. w1 - 1) -> OffsetUpdate."""
+    def _update(self, out, logits: torch.Tensor, w0: int, w1: int, gate_logits: Optional[torch.Tensor] = None) -> 'OffsetUpdate':
+        """The read-out of this advance (an ops.TrackStreamOut, or TrackGatedStreamOut with the gate's logits of the same windows) and its logits (windows
+        w0 .. w1 - 1) -> OffsetUpdate."""
         tr = self.tracker
         k, m = out.cls_lag.shape[0], out.cls_tail.shape[0]
         upd = OffsetUpdate(w_new=w0, logits=logits, cls_raw=out.cls_raw, conf_raw=out.conf_raw, w0=out.w0, t_sec=window_times64(k, tr.hop, first_window=out.w0),
@@ -362,6 +388,8 @@ class _Feed:
             upd.post_lag, upd.cls_post_lag, upd.conf_post_lag, upd.offset_sec_mean_lag, upd.log_z = (out.post_lag, out.cls_post_lag, out.conf_post_lag,
                                                                                                        out.offset_mean_lag, out.log_z)
             upd.offset_sec_post_lag = tr.grid[out.cls_post_lag.long()]
+        if self.gated:
+            upd.gate_logits, upd.sync_raw, upd.sync_lag, upd.sync_tail, upd.p_sync_lag = gate_logits, out.sync_raw, out.sync_lag, out.sync_tail, out.p_sync_lag
         return upd
 
 
@@ -392,14 +420,16 @@ class OffsetStream(_Stream):
         frames   from 8 N on (N = segments done): at most 15, plus what the video is ahead of the audio, plus one push
         samples  from 5120 N on: at most 10239, plus what the audio is ahead of the video, plus one push
         segment features from the next window's first segment on: at most 13 + hop - 1
-        the read-out state: ops.track_stream_state's bytes
+        the read-out state: ops.track_stream_state's bytes (gated: ops.track_stream_state_gated's)
+    With gated=True the gate's logits of the same n new windows come from the same held features (gate.sync_windows with n_window = gate.n_window,
+    start-aligned, the first n rows: what track_features does offline) and the read-out is ops.track_stream_push_gated.
     The segment grid is the recording's (anchored at frame 0), so the windows, their logits (bit for bit where the tower schedule is position-independent: the
     un-fused one) and t_sec are those track() gives for the finished recording."""
 
-    def __init__(self, tracker: OffsetTracker, lag: int = 16, seg_chunk: Optional[int] = None, ingest=None):
-        super().__init__(tracker, ingest)
+    def __init__(self, tracker: OffsetTracker, lag: int = 16, seg_chunk: Optional[int] = None, ingest=None, gated: bool = False):
+        super().__init__(tracker, ingest, gated)
         self.lag, self.seg_chunk = int(lag), seg_chunk
-        self.state = ops.track_stream_state(tracker.eng.n_out, self.lag, tracker.posterior, tracker.eng.dev)
+        self.state = (ops.track_stream_state_gated if self.gated else ops.track_stream_state)(tracker.eng.n_out, self.lag, tracker.posterior, tracker.eng.dev)
 
     def _state_bytes(self) -> int:
         return int(self.state.buf.numel())
@@ -425,9 +455,18 @@ class OffsetStream(_Stream):
             assert logits.shape[0] == w1 - w0, (logits.shape, w0, w1)
         else:
             logits = torch.empty(0, eng.n_out, device=eng.dev, dtype=torch.float32)
-        out = ops.track_stream_push(self.state, logits, tr.lam, tr.grid if tr.posterior else None, final=final)
+        gate_logits = None
+        if self.gated:
+            gate = tr.gate
+            if w1 > w0:                                                          # start-aligned windows of the gate's own length: exactly the n new rows
+                gate_logits = gate.sync_windows(self._vfeat[lo:], self._afeat[lo:], hop=tr.hop, n_window=gate.n_window)[:w1 - w0]
+            else:
+                gate_logits = torch.empty(0, 2, device=eng.dev, dtype=torch.float32)
+            out = ops.track_stream_push_gated(self.state, logits, gate_logits, tr.lam, tr.mu, tr.grid if tr.posterior else None, final=final)
+        else:
+            out = ops.track_stream_push(self.state, logits, tr.lam, tr.grid if tr.posterior else None, final=final)
         self._trim(g)
-        return self._update(out, logits, w0, w1)
+        return self._update(out, logits, w0, w1, gate_logits)
 
 
 class ProgrammeStream(_Stream):
@@ -442,14 +481,14 @@ class ProgrammeStream(_Stream):
         audio_segments  P x segments
         state_bytes     P x ops.track_stream_state's bytes"""
 
-    def __init__(self, tracker: OffsetTracker, lag: int = 16, seg_chunk: Optional[int] = None, ingest=None):
+    def __init__(self, tracker: OffsetTracker, lag: int = 16, seg_chunk: Optional[int] = None, ingest=None, gated: bool = False):
         if getattr(ingest, 'programmes', None) is None:
             raise ValueError('ProgrammeStream: an ingest with programmes is required (RecordingIngest(..., audio_channels=, programmes=[...]))')
-        super().__init__(tracker, ingest)
+        super().__init__(tracker, ingest, gated)
         self.P = len(ingest.programmes)
         self.lag, self.seg_chunk = int(lag), seg_chunk
         self._wave = torch.empty(self.P, 0, device=tracker.eng.dev, dtype=torch.float32)
-        self.state = ops.track_pool_state(self.P, tracker.eng.n_out, self.lag, tracker.posterior, tracker.eng.dev)
+        self.state = (ops.track_pool_state_gated if self.gated else ops.track_pool_state)(self.P, tracker.eng.n_out, self.lag, tracker.posterior, tracker.eng.dev)
 
     def _state_bytes(self) -> int:
         return int(self.state.buf.numel())
@@ -489,17 +528,27 @@ class ProgrammeStream(_Stream):
         else:
             logits = torch.empty(P, 0, eng.n_out, device=eng.dev, dtype=torch.float32)
         slots = list(range(P))
-        outs = ops.track_pool_push(self.state, slots, logits.reshape(P * (w1 - w0), eng.n_out), [w1 - w0] * P, tr.lam, tr.grid if tr.posterior else None,
-                                   final=slots if final else ())
+        gate_logits = [None] * P
+        if self.gated:
+            gate = tr.gate
+            if w1 > w0:
+                gate_logits = gate.sync_windows_programmes(self._vfeat[lo:], self._afeat[lo:].transpose(0, 1), hop=tr.hop, n_window=gate.n_window)[:, :w1 - w0].contiguous()
+            else:
+                gate_logits = torch.empty(P, 0, 2, device=eng.dev, dtype=torch.float32)
+            outs = ops.track_pool_push_gated(self.state, slots, logits.reshape(P * (w1 - w0), eng.n_out), gate_logits.reshape(P * (w1 - w0), 2), [w1 - w0] * P, tr.lam,
+                                             tr.mu, tr.grid if tr.posterior else None, final=slots if final else ())
+        else:
+            outs = ops.track_pool_push(self.state, slots, logits.reshape(P * (w1 - w0), eng.n_out), [w1 - w0] * P, tr.lam, tr.grid if tr.posterior else None,
+                                       final=slots if final else ())
         self._trim(g)
-        return [self._update(out, logits[p], w0, w1) for p, out in enumerate(outs)]
+        return [self._update(out, logits[p], w0, w1, gate_logits[p]) for p, out in enumerate(outs)]
 
 
 class PoolFeed(_Feed):
     """One feed of an OffsetStreamPool (pool.open()): the handle push() is keyed by.  `held` / `held_bound` / the totals as an OffsetStream's."""
 
     def __init__(self, pool: 'OffsetStreamPool', slot: int, ingest=None):
-        super().__init__(pool.tracker, ingest)
+        super().__init__(pool.tracker, ingest, pool.gated)
         self.pool, self.slot = pool, slot
 
     def _state_bytes(self) -> int:
@@ -513,16 +562,19 @@ class OffsetStreamPool:
                   one-segment clips, in launch groups of at most seg_chunk segments, whatever feed they come from;
         windows   the new windows of all feeds are gathered from the held features into (nw, 14, t, 768) and cross the sync transformer in passes of at most
                   win_chunk = 256;
-        read-out  one ops.track_pool_push for all feeds;
+        read-out  one ops.track_pool_push for all feeds (gated=True, DESIGN 3.21: the windows' first gate.n_window segments are gathered as well and cross the
+                  gate's sync transformer in the same passes; one ops.track_pool_push_gated);
     and every feed trims its buffers as its own stream would.  Per feed the host arithmetic is OffsetStream's (the same code), `held <= held_bound` holds per
     feed, and on the un-fused tower schedule (the engine's seg_chunk < 6) every field of every update equals the same feed through its own OffsetStream bit for
     bit.  A feed named in `flush` gets its final push in that tick (with or without data) and its slot becomes free; feeds not named are untouched."""
 
-    def __init__(self, tracker: OffsetTracker, n_feeds: int, lag: int = 16, seg_chunk: Optional[int] = None, win_chunk: int = 256):
+    def __init__(self, tracker: OffsetTracker, n_feeds: int, lag: int = 16, seg_chunk: Optional[int] = None, win_chunk: int = 256, gated: bool = False):
         if n_feeds < 1:
             raise ValueError(f'OffsetStreamPool: n_feeds = {n_feeds}')
-        self.tracker, self.n_feeds, self.lag, self.seg_chunk, self.win_chunk = tracker, int(n_feeds), int(lag), seg_chunk, int(win_chunk)
-        self.state = ops.track_pool_state(self.n_feeds, tracker.eng.n_out, self.lag, tracker.posterior, tracker.eng.dev)
+        if gated and tracker.gate is None:
+            raise ValueError('OffsetStreamPool: gated=True needs a tracker with a gate')
+        self.tracker, self.n_feeds, self.lag, self.seg_chunk, self.win_chunk, self.gated = tracker, int(n_feeds), int(lag), seg_chunk, int(win_chunk), bool(gated)
+        self.state = (ops.track_pool_state_gated if self.gated else ops.track_pool_state)(self.n_feeds, tracker.eng.n_out, self.lag, tracker.posterior, tracker.eng.dev)
         self._free = list(range(self.n_feeds - 1, -1, -1))                       # slot 0 first
         self.feeds = {}                                                          # slot -> the open feed
 
@@ -587,19 +639,26 @@ class OffsetStreamPool:
         # windows: gathered from the held features of all feeds
         nw = len(plan['windows'])
         logits = torch.empty(nw, eng.n_out, device=eng.dev, dtype=torch.float32)
+        gate_logits = torch.empty(nw, 2, device=eng.dev, dtype=torch.float32) if self.gated else None
         if nw:
             nwin = plan['geometry'][0]['n_window']
             for i0, i1 in plan['passes']:
                 vwin = torch.stack([feeds[i]._vfeat[lo:lo + nwin] for i, _, lo in plan['windows'][i0:i1]])
                 awin = torch.stack([feeds[i]._afeat[lo:lo + nwin] for i, _, lo in plan['windows'][i0:i1]])
                 logits[i0:i1].copy_(eng.sync_transformer(vwin, awin))
+                if self.gated:                                                   # the gate's start-aligned windows: the first gate.n_window segments of the same gather
+                    gate_logits[i0:i1].copy_(tr.gate.sync_transformer(vwin[:, :tr.gate.n_window].contiguous(), awin[:, :tr.gate.n_window].contiguous()))
         # read-out: one call for all feeds
-        outs = ops.track_pool_push(self.state, [f.slot for f in feeds], logits, plan['counts'], tr.lam, tr.grid if tr.posterior else None,
-                                   final=[f.slot for f in flush])
+        if self.gated:
+            outs = ops.track_pool_push_gated(self.state, [f.slot for f in feeds], logits, gate_logits, plan['counts'], tr.lam, tr.mu,
+                                             tr.grid if tr.posterior else None, final=[f.slot for f in flush])
+        else:
+            outs = ops.track_pool_push(self.state, [f.slot for f in feeds], logits, plan['counts'], tr.lam, tr.grid if tr.posterior else None,
+                                       final=[f.slot for f in flush])
         res, row = {}, 0
         for f, g, n, out in zip(feeds, plan['geometry'], plan['counts'], outs):
             f._trim(g)
-            res[f] = f._update(out, logits[row:row + n], g['new_windows'][0], g['new_windows'][1])
+            res[f] = f._update(out, logits[row:row + n], g['new_windows'][0], g['new_windows'][1], gate_logits[row:row + n] if self.gated else None)
             row += n
         for f in flush:
             f.closed = True

@@ -1,7 +1,7 @@
 """Many live feeds on one device: A = one OffsetStream per feed, pushed in a loop (what a monitor had before the pool) against B = one
 OffsetStreamPool, in one process, alternating, and the read-out alone (ops.track_pool_push against a loop of ops.track_stream_push).  One JSON line per result.
 
-    python tools/track_pool.py [--feeds 16] [--seconds 20] [--stream 1.0] [--lag 16] [--posterior] [--reps 3] [--seg-chunk N] [--stages]
+    python tools/track_pool.py [--feeds 16] [--seconds 20] [--stream 1.0] [--lag 16] [--posterior] [--reps 3] [--seg-chunk N] [--stages] [--gate [--mu X]]
 
 Inputs are synthetic feeds from seeds (random frames and samples on the device, feed i from seed i, every feed a little shorter than the one before: content and
 length differ per feed; the weights are synth.make_state_dict's).  Every tick hands each feed that still has data its next `--stream` seconds (25 fps frames,
@@ -9,7 +9,10 @@ length differ per feed; the weights are synth.make_state_dict's).  Every tick ha
 window (a monitor reads the committed offsets every tick); one untimed run of each side first, then `--reps` runs of each, A and B alternating.  Reported per side:
 ms per tick, segments / s and the feeds one device carries in real time (feeds x tick seconds / tick time), each as the median with min and max over the runs.
 --stages adds one more, untimed-for-the-comparison run per side with a synchronise around the towers, the windows and the read-out: the per-stage split.
-The read-out alone: 256 streams x 1 row per tick at C = 21 after 300 rows of history each, the same alternation."""
+The read-out alone: 256 streams x 1 row per tick at C = 21 after 300 rows of history each, the same alternation.
+--gate: a third side G = the pool of a tracker with a synthetic 2-way syncability engine (towers=False), pool(gated=True), in the same alternation:
+what the gate adds per tick beside B of this run (its 13-segment windows through a second sync transformer and the 2C-wide read-out), the committed windows flagged
+not synchronizable, and the gated read-out alone (ops.track_pool_push_gated) beside ops.track_pool_push."""
 import argparse
 import json
 import statistics
@@ -40,6 +43,8 @@ def main():
     ap.add_argument('--stages', action='store_true')
     ap.add_argument('--readout-streams', type=int, default=256)
     ap.add_argument('--readout-ticks', type=int, default=100)
+    ap.add_argument('--gate', action='store_true', help='also run the pool gated by a synthetic 2-way syncability engine (towers=False)')
+    ap.add_argument('--mu', type=float, default=2.0, help='cost of one change of the synchronizable flag (with --gate)')
     args = ap.parse_args()
     if args.reps < 3:
         ap.error('--reps: at least three repetitions of each side')
@@ -49,7 +54,12 @@ def main():
     from synchformer_amd.track import OffsetTracker
     dev = torch.device('cuda:0')
     eng = SynchformerEngine(synth.make_state_dict(1337), dev) if args.seg_chunk is None else SynchformerEngine(synth.make_state_dict(1337), dev, seg_chunk=args.seg_chunk)
-    tracker = OffsetTracker(eng, MelFrontend(dev), lam=1.0, posterior=args.posterior)
+    mel = MelFrontend(dev)
+    tracker = OffsetTracker(eng, mel, lam=1.0, posterior=args.posterior)
+    gated_tracker = None
+    if args.gate:
+        gate = SynchformerEngine(synth.make_state_dict(4242, head='sync_head', n_pos=184, n_out=2), dev, towers=False)
+        gated_tracker = OffsetTracker(eng, mel, lam=1.0, posterior=args.posterior, gate=gate, mu=args.mu)
     base = dict(tool='track_pool', feeds=args.feeds, seconds=args.seconds, stream_s=args.stream, lag=args.lag, posterior=args.posterior, seg_chunk=eng.seg_chunk,
                 device=torch.cuda.get_device_name(0))
 
@@ -83,10 +93,13 @@ def main():
         segs = sum(s.n_segments for s in streams)
         return dt, ticks, segs, wins
 
-    def run_b():
-        pool = tracker.pool(args.feeds, lag=args.lag)
+    flagged = [0]
+
+    def run_b(gated=False):
+        pool = gated_tracker.pool(args.feeds, lag=args.lag, gated=True) if gated else tracker.pool(args.feeds, lag=args.lag)
         handles = [pool.open() for _ in feeds]
         wins = ticks = 0
+        zero = torch.zeros((), device=dev, dtype=torch.int64)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for t in range(n_ticks + 1):
@@ -95,18 +108,26 @@ def main():
                 break
             ups = pool.push({handles[i]: piece(i, t) for i in live if has(i, t)}, flush=[handles[i] for i in live if not has(i, t)])
             wins += sum(u.logits.shape[0] for u in ups.values())
+            if gated:
+                for u in ups.values():
+                    zero += (u.sync_lag == 0).sum()
             torch.cuda.synchronize()
             ticks += 1
         dt = time.perf_counter() - t0
+        flagged[0] = int(zero.item())
         return dt, ticks, sum(f.n_segments for f in handles), wins
 
     run_a()
     run_b()
-    res = dict(A=[], B=[])
+    res = dict(A=[], B=[], G=[])
+    if args.gate:
+        run_b(gated=True)
     for _ in range(args.reps):
         res['A'].append(run_a())
         res['B'].append(run_b())
-    assert len({r[1:] for r in res['A'] + res['B']}) == 1, 'the two sides did not do the same work'
+        if args.gate:
+            res['G'].append(run_b(gated=True))
+    assert len({r[1:] for r in res['A'] + res['B'] + res['G']}) == 1, 'the sides did not do the same work'
     _, ticks, segs, wins = res['A'][0]
     out = {}
     for side, what in (('A', 'one OffsetStream per feed, pushed in a loop'), ('B', 'one OffsetStreamPool')):
@@ -119,6 +140,12 @@ def main():
     print(json.dumps(dict(base, what='end_to_end', speedup_median=round(a_ms['median'] / b_ms['median'], 3), a_spread_ms=round(spread, 3),
                           gain_ms=round(a_ms['median'] - b_ms['median'], 3), b_beats_a_by_more_than_a_spread=bool(a_ms['min'] - b_ms['max'] > 0 and
                                                                                                                   a_ms['median'] - b_ms['median'] > spread))), flush=True)
+
+    if args.gate:
+        g_ms = _stats([1e3 * r[0] / ticks for r in res['G']])
+        print(json.dumps(dict(base, side='G', what='one OffsetStreamPool, gated', mu=args.mu, ticks=ticks, windows=wins, reps=args.reps, ms_per_tick=g_ms,
+                              gate_adds_ms_per_tick=round(g_ms['median'] - b_ms['median'], 3), gate_adds_fraction=round(g_ms['median'] / b_ms['median'] - 1, 4),
+                              windows_not_synchronizable=flagged[0])), flush=True)
 
     # ---- the per-stage split ----------------------------------------------------------------------------------------------------------------------------
     if args.stages:
@@ -175,16 +202,37 @@ def main():
             torch.cuda.synchronize()
         return 1e3 * (time.perf_counter() - t0) / T
 
+    gate_history, gate_rows = 3 * torch.randn(S, 300, 2, device=dev, generator=gen), 3 * torch.randn(T, S, 2, device=dev, generator=gen)
+
+    def readout_g():
+        state = ops.track_pool_state_gated(S, C, args.lag, args.posterior, dev)
+        ops.track_pool_push_gated(state, range(S), history.reshape(S * 300, C), gate_history.reshape(S * 300, 2), [300] * S, 1.0, args.mu, grid)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for t in range(T):
+            ops.track_pool_push_gated(state, range(S), rows[t], gate_rows[t], [1] * S, 1.0, args.mu, grid)
+            torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0) / T
+
     readout_a()
     readout_b()
-    ra, rb = [], []
+    ra, rb, rg = [], [], []
+    if args.gate:
+        readout_g()
     for _ in range(args.reps):
         ra.append(readout_a())
         rb.append(readout_b())
+        if args.gate:
+            rg.append(readout_g())
     sa, sb = _stats(ra, 4), _stats(rb, 4)
     print(json.dumps(dict(tool='track_pool', what='readout_alone', streams=S, rows_per_tick=1, classes=C, lag=args.lag, posterior=args.posterior, ticks=T, reps=args.reps,
                           a_stream_push_loop_ms_per_tick=sa, b_pool_push_ms_per_tick=sb, speedup_median=round(sa['median'] / sb['median'], 2),
                           b_beats_a_by_more_than_a_spread=bool(sa['min'] > sb['max'] and sa['median'] - sb['median'] > sa['max'] - sa['min']))), flush=True)
+    if args.gate:
+        sg = _stats(rg, 4)
+        print(json.dumps(dict(tool='track_pool', what='readout_alone_gated', streams=S, rows_per_tick=1, classes=C, lag=args.lag, posterior=args.posterior, mu=args.mu, ticks=T,
+                              reps=args.reps, g_pool_push_gated_ms_per_tick=sg, b_pool_push_ms_per_tick=sb, gate_adds_ms_per_tick=round(sg['median'] - sb['median'], 4))),
+              flush=True)
 
 
 if __name__ == '__main__':

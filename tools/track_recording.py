@@ -22,7 +22,9 @@ With --posterior the windows are also read out as marginals: the l
 With --gate a synthetic 2-way syncability engine without towers (184 position rows: windows of 13 segments) reads the same bank and the windows are
 read out over (offset class, synchronizable flag) at --mu: the line then carries, of this same run, the time of the offset windows and of the ungated read-out beside
 the time of the gate's windows and of the gated read-out (with --posterior both read-outs include their posterior launches), what the gate adds to track_total_s, the
-windows flagged not synchronizable, and the spans (start s, end s, offset s or null) of OffsetTrack.spans().  --stream keeps using the tracker without a gate.
+windows flagged not synchronizable, and the spans (start s, end s, offset s or null) of OffsetTrack.spans().  With --stream as well the recording is pushed a second
+time through the gated stream (OffsetTracker.stream(lag, gated=True)): 'stream_gated' carries the same per-stage times plus the gate's windows, the
+committed windows flagged not synchronizable, whether logits and gate_logits equal the offline track's, and what the gate adds per push beside 'stream' of this run.
 
 With --stream SECONDS the recording is also pushed through OffsetTracker.stream(lag) in pieces of that many seconds (from raw input when --fps /
 --size / --rate are given): the line then carries, per push, the milliseconds of the bank (the towers on the segments the push completed), the windows (the sync
@@ -199,7 +201,11 @@ def main():
         for t0, t1, off in spans:
             print(f'span {t0:8.2f} s .. {t1:8.2f} s  ' + ('not synchronizable' if off is None else f'offset {off:+.2f} s'), file=sys.stderr)
     if args.stream is not None:
-        extra['stream'] = stream_timing(args, tracker, eng, ops, (raw, raw_wave, ing) if raw_mode else (src[0], src[1], None), track)
+        source = (raw, raw_wave, ing) if raw_mode else (src[0], src[1], None)
+        extra['stream'] = stream_timing(args, tracker, eng, ops, source, track)
+        if args.gate:
+            extra['stream_gated'] = stream_timing(args, gated, eng, ops, source, gtrack, gated=True)
+            extra['stream_gated']['gate_adds_ms_per_push'] = round(extra['stream_gated']['push']['mean_ms'] - extra['stream']['push']['mean_ms'], 3)
     k = min(W, max(1, args.clip_windows))
     picks = [round(i * (W - 1) / max(1, k - 1)) for i in range(k)]
 
@@ -289,9 +295,10 @@ def programmes_main(args, dev):
         print(json.dumps(line))
 
 
-def stream_timing(args, tracker, eng, ops, source, track):
+def stream_timing(args, tracker, eng, ops, source, track, gated=False):
     """Pushes the recording through tracker.stream(lag) in pieces of args.stream seconds, twice (the first pass warms up); the three stages are timed by wrapping
-    the calls OffsetStream makes (engine.extract_segments_from, engine.sync_windows, ops.track_stream_push) between device synchronisations."""
+    the calls OffsetStream makes (engine.extract_segments_from, engine.sync_windows, ops.track_stream_push) between device synchronisations.  gated: through
+    tracker.stream(lag, gated=True) - the read-out is ops.track_stream_push_gated and the gate's own sync_windows is a fourth stage."""
     frames, wave, ing = source
     fps, rate = (float(ing.fps_in), ing.rate_in) if ing is not None else (25.0, 16000)
     ms = {}
@@ -311,10 +318,14 @@ def stream_timing(args, tracker, eng, ops, source, track):
 
     saved = [(eng, 'extract_segments_from', staged(eng, 'extract_segments_from', 'bank')), (eng, 'sync_windows', staged(eng, 'sync_windows', 'windows')),
              (ops, 'track_stream_push', staged(ops, 'track_stream_push', 'readout'))]
+    if gated:
+        setattr(ops, 'track_stream_push', saved[-1][2])
+        saved[-1] = (ops, 'track_stream_push_gated', staged(ops, 'track_stream_push_gated', 'readout'))
+        saved.append((tracker.gate, 'sync_windows', staged(tracker.gate, 'sync_windows', 'gate_windows')))
     try:
         for _ in range(2):
-            stream = tracker.stream(lag=args.lag, ingest=ing)
-            rows, logits, f, a, i = [], [], 0, 0, 1
+            stream = tracker.stream(lag=args.lag, ingest=ing, gated=True) if gated else tracker.stream(lag=args.lag, ingest=ing)
+            rows, logits, gate_logits, flagged, f, a, i = [], [], [], 0, 0, 0, 1
             t_start = time.perf_counter()
             while f < frames.shape[0] or a < wave.shape[-1]:
                 f1, a1 = min(frames.shape[0], round(i * args.stream * fps)), min(wave.shape[-1], round(i * args.stream * rate))
@@ -325,9 +336,16 @@ def stream_timing(args, tracker, eng, ops, source, track):
                 torch.cuda.synchronize()
                 rows.append(dict(ms, push=(time.perf_counter() - t0) * 1e3, windows_new=int(upd.logits.shape[0]), committed=int(upd.cls_lag.shape[0])))
                 logits.append(upd.logits)
+                if gated:
+                    gate_logits.append(upd.gate_logits)
+                    flagged += int((upd.sync_lag == 0).sum().item())
+                    rows[-1]['not_synchronizable'] = int((upd.sync_lag == 0).sum().item())
                 f, a, i = f1, a1, i + 1
             upd = stream.flush()
             logits.append(upd.logits)
+            if gated:
+                gate_logits.append(upd.gate_logits)
+                flagged += int((upd.sync_lag == 0).sum().item())
             torch.cuda.synchronize()
             total = time.perf_counter() - t_start
     finally:
@@ -342,7 +360,12 @@ def stream_timing(args, tracker, eng, ops, source, track):
         return {'mean_ms': round(sum(v) / max(len(v), 1), 3), 'max_ms': round(max(v, default=0.0), 3)}
 
     got = torch.cat(logits)
-    return {'piece_s': args.stream, 'lag': args.lag, 'pushes': len(rows), 'pushes_with_windows': len(busy), 'bank': stat('bank'), 'windows': stat('windows'),
+    more = {}
+    if gated:
+        gz = torch.cat(gate_logits)
+        more = {'gate_windows': stat('gate_windows'), 'windows_not_synchronizable': flagged,
+                'gate_logits_equal_offline': bool(gz.shape == track.gate_logits.shape and torch.equal(gz, track.gate_logits))}
+    return {**more, 'piece_s': args.stream, 'lag': args.lag, 'pushes': len(rows), 'pushes_with_windows': len(busy), 'bank': stat('bank'), 'windows': stat('windows'),
             'readout': stat('readout'), 'push': stat('push'), 'held_after': stream.held, 'total_s': round(total, 4),
             'logits_equal_offline': bool(got.shape == track.logits.shape and torch.equal(got, track.logits)),
             'max_abs_logit_diff_vs_offline': round((got - track.logits).abs().max().item(), 6) if got.shape == track.logits.shape else None}
