@@ -29,6 +29,7 @@ extern "C" {
 enum { SF_F32 = 0, SF_BF16 = 1, SF_F16 = 2, SF_U8 = 3, SF_I16 = 4, SF_I32 = 5 };   /* element types (SF_I16: PCM input of sf_resample_wave / _mix only; SF_I32: of sf_resample_wave_mix only) */
 enum { SF_EPI_NONE = 0, SF_EPI_GELU = 1 };                  /* GEMM epilogue activation */
 
+/* 25, with two purely additive entries since: sf_ingest_video_v210, sf_ingest_video_v210_fields; nothing that existed at 25 changed */
 #define SF_ABI_VERSION 25
 int sf_abi_version(void);
 const char* sf_last_error(void);
@@ -780,6 +781,28 @@ int sf_ingest_video_yuv_planes_fields(const void* raw, int bytes_per_sample, int
                                       const int32_t* x_first, const float* x_w, int taps_x, const int32_t* cy_first0, const float* cy_w0, const int32_t* cy_first1,
                                       const float* cy_w1, int taps_cy, const int32_t* cx_first, const float* cx_w, int taps_cx, const float* csc, int bottom_first,
                                       uint8_t* out, int T_out, void* stream);
+
+/* v210 frames (an addition under ABI v25): 10-bit 4:2:2 as SDI capture cards and QuickTime 'v210' deliver it.  A row of W pixels (W even) is the 10-bit
+ * fields Cb0 Y0 Cr0 Y1 Cb1 Y2 Cr1 Y3 .. (the uyvy422 order); field F lies in little-endian 32-bit word F / 3 at bit 10 (F % 3), bits 30 - 31 are unused:
+ *       Y [y, x] = (word[y][(2 x + 1) / 3] >> 10 ((2 x + 1) % 3)) & 1023        x < W            word[y] = raw + f * stride_frame + y * stride_row  (strides in BYTES)
+ *       Cb[y, j] = (word[y][(4 j)     / 3] >> 10 ((4 j)     % 3)) & 1023        j < W / 2        Cr: field 4 j + 2
+ *   A row occupies whole groups of four words (six pixels): stride_row >= 16 ceil(W / 6); the unused fields of a last partial group, the words between it and the
+ *   pitch and bits 30 - 31 may hold anything and never influence the output.  From the unpacked samples on this is sf_ingest_video_yuv_planes on yuv422p10le (Hc = H,
+ *   Wc = W / 2, shift 0, the 10-bit scale), and the output equals that entry's on the same samples bit for bit; the chroma rows take the luma vertical tables, so
+ *   there is no cy_* argument.  An odd H is legal.  Rows are read as aligned dwords.
+ *   -1 before anything is launched on: everything sf_ingest_video refuses about T_out, taps and out; n_src < 1, H < 1, W < 2 or odd; stride_row or stride_frame
+ *   negative or not a multiple of 4; stride_row < 16 ceil(W / 6); raw not 4-byte aligned; a null pointer with T_out > 0; a row too wide to stage.  T_out == 0 launches
+ *   nothing.  One launch.
+ * sf_ingest_video_v210_fields: the same on an interlaced recording, as sf_ingest_video_yuv_planes_fields defines fields - field_table holds field indices, the
+ *   rows of parity p start p stride_row in and are 2 stride_row apart, y_first0 / y_w0 and y_first1 / y_w1 are the vertical tables of the parities.  Additionally -1
+ *   on: H odd or below 2, bottom_first outside {0, 1}, a null table of either parity, n_src above 2^30 - 1. */
+int sf_ingest_video_v210(const void* raw, int64_t stride_frame, int64_t stride_row, int n_src, int H, int W, const int32_t* frame_table, const int32_t* y_first,
+                         const float* y_w, int taps_y, const int32_t* x_first, const float* x_w, int taps_x, const int32_t* cx_first, const float* cx_w, int taps_cx,
+                         const float* csc, uint8_t* out, int T_out, void* stream);
+int sf_ingest_video_v210_fields(const void* raw, int64_t stride_frame, int64_t stride_row, int n_src, int H, int W, const int32_t* field_table,
+                                const int32_t* y_first0, const float* y_w0, const int32_t* y_first1, const float* y_w1, int taps_y, const int32_t* x_first,
+                                const float* x_w, int taps_x, const int32_t* cx_first, const float* cx_w, int taps_cx, const float* csc, int bottom_first, uint8_t* out,
+                                int T_out, void* stream);
 
 /* Backward of sf_attention for tiny groups (n_tok <= 8, head_dim 64: Motionformer time attention, vit_helper.py:343-344): same
  * addressing as the forward; dq | dk | dv rows of the group's tokens are written (=), the CLS key's dk | dv of every (seq, group) goes to

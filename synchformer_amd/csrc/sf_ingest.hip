@@ -7,6 +7,8 @@
 //   sf_ingest_video_yuv16: the same for 10-bit YUV 4:2:0 frames in 16-bit samples (P010, yuv420p10le): the sample is (raw >> shift) & 1023.
 //   sf_ingest_video_yuv_planes: the general form of the two: three planes of 1- or 2-byte samples at any offsets and strides, chroma of Hc x Wc -
 //                      4:2:2 packed (uyvy422, yuyv422, y210), semi-planar (nv16, p210) and planar (yuv422p, yuv422p10le), the 4:2:0 layouts, 4:4:4 planar.
+//   sf_ingest_video_v210, sf_ingest_video_v210_fields: the same for v210 frames and fields: 10-bit 4:2:2 as SDI capture delivers it, three 10-bit fields
+//                      Cb Y Cr Y .. per 32-bit word - unpacked while staging, from there the 16-bit pipeline of yuv422p10le; two kernels of their own.
 //   sf_ingest_video_fields, sf_ingest_video_yuv_planes_fields: sf_ingest_video and the general entry on an INTERLACED recording: the table names fields,
 //                      each workgroup resizes the rows p, p + 2, .. of its frame with the vertical table of that parity - kernels of their own beside the
 //                      progressive ones, which stay the code they were.
@@ -36,6 +38,7 @@ typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 #define ING_PF 20              // staged dwords per lane per chunk at most: NP * R * RP / 4 <= 5120
 #define ING_ROW_SLACK 8        // samples behind a staged row that the horizontal pass may read (always against a zero weight)
 #define ING_LDS_BYTES16 98304  // the same for 2-byte samples: four staged rows of a 3840-wide luma plane at 35 taps take ~68 KiB (gfx950: 160 KiB per workgroup)
+#define ING_PF210 20           // the same for v210 rows (FORM = 3), which fetch 1.5 words per staged dword: see ing_plane_pass
 #define ING_PF16 40            // staged dwords per lane per chunk at most for 2-byte samples: NP * R * RP / 2 <= 10240, the row widths the 1-byte kernels serve
 
 // The resize of output rows [r0, r0 + 8) of NP planes of one frame that share their geometry and tables (NP = 1: one RGB channel, or luma; NP = 2: U and V), by the
@@ -67,16 +70,34 @@ typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 //   fetched once and split into the U and the V dwords.  Rows that are not 4-byte aligned and row ends take the strided loads.  What reaches LDS is the same either way.
 //   BS = 2 fetches twice the dwords it stages, so it stages at most ING_PF16 / 2 per lane and chunk (the launcher sizes R for that): the fetched words of a chunk then
 //   fit the registers of the plain form, all loads stay in flight together, and the kernel keeps three workgroups per CU instead of one (12.9 -> 5.0 us per frame).
+// FORM = 3, BS = 2: a v210 row - the 10-bit fields Cb0 Y0 Cr0 Y1 Cb1 Y2 Cr1 Y3 .. of a 4:2:2 row, field F in bits [10 (F % 3), 10 (F % 3) + 10) of
+//   little-endian word F / 3; s0 is word 0 of row 0 (4-byte aligned), sy the row pitch in bytes, s1 / sx / shift / pk are unused, the row has nw whole words (four
+//   per six pixels).  NP = 1 (luma, W columns): the item of columns x .. x + 3 (x % 4 == 0) takes fields 2 x + 1, + 3, + 5, + 7 - three words from (2 x + 1) / 3.
+//   NP = 2 (chroma, W = the chroma width): four chroma columns from j take fields 4 j .. 4 j + 14, U on 4 j + 4 i and V two further - six words from 4 j / 3, one
+//   fetch for both planes.  Either window starts 0, 1 or 2 fields into its first word, so field t of the window lies in word t / 3 or the next: one select, one
+//   shift, one mask.  The words come as one aligned dword load each (every v210 word is 4-byte aligned: no pointer tests), plain where the window lies inside the
+//   row, bounded by nw at the row's end (a word at or past nw reads as 0).  Loads of whole 16-byte groups were measured 22 % slower (profiles/ingest_v210.md) and
+//   are not here.  Columns at or beyond W are zeroed after the unpacking, so padding fields never reach LDS; what commit() writes is the plain 16-bit row of the
+//   yuv422p10le form (shift 0) at the same xlo.  Three words are fetched for two staged dwords, so the
+//   form stages at most ING_PF210 dwords per lane and chunk.  FORM = 4 is the same staging with the whole ING_PF16 budget, for rows too wide for four of them to
+//   fit ING_PF210 (above ~2500 columns): more registers, one wave per SIMD - rows that wide leave LDS for one or two workgroups per CU anyway.
+template <int NWD>
+__device__ __forceinline__ uint32_t ing_v210_field(const uint32_t (&d)[NWD], int r, int t) {
+  const int p = r + t % 3, lo = t / 3, hi = lo + 1 < NWD ? lo + 1 : NWD - 1;   // t is a constant where this is called: r + t % 3 < 3 whenever lo + 1 == NWD
+  return p >= 3 ? (d[hi] >> (10 * (p - 3))) & 1023u : (d[lo] >> (10 * p)) & 1023u;
+}
+
 template <int NP, int FORM, int BS>
 __device__ __forceinline__ void ing_plane_pass(unsigned char* lds, const uint8_t* __restrict__ s0, const uint8_t* __restrict__ s1, int64_t sy, int64_t sx, int H, int W,
                                                const int32_t* __restrict__ y_first, const float* __restrict__ y_w, int taps_y,
                                                const int32_t* __restrict__ x_first, const float* __restrict__ x_w, int taps_x, int R, int RP, int TW, int r0, int shift,
                                                int pk, float (&a0)[NP][4], float (&a1)[NP][4]) {
   static_assert(BS == 1 || BS == 2, "samples of one or two bytes");
-  static_assert(FORM >= 0 && FORM <= 2, "plain, interleaved or packed");
+  static_assert(FORM >= 0 && FORM <= 4, "plain, interleaved, packed, v210 or v210 with the whole staging budget");
+  static_assert(FORM < 3 || BS == 2, "v210 stages 16-bit samples");
   constexpr bool INTER = FORM == 1;
   constexpr int PAD = BS == 1 ? 3 : 1;                                          // zero rows in front of the transposed table: samples per dword - 1
-  constexpr int PF = BS == 1 ? ING_PF : FORM == 2 ? ING_PF16 / 2 : ING_PF16;      // packed words: twice the staged dwords are fetched, so half are staged
+  constexpr int PF = BS == 1 ? ING_PF : FORM == 3 ? ING_PF210 : FORM == 4 ? ING_PF16 : FORM == 2 ? ING_PF16 / 2 : ING_PF16;   // packed words: twice the staged dwords are fetched, so half are staged
   float* xw = (float*)lds;
   float* yw = xw + TW * ING_OUT;
   float* mid = yw + ING_TY * taps_y;
@@ -190,6 +211,35 @@ __device__ __forceinline__ void ing_plane_pass(unsigned char* lds, const uint8_t
                   v[2 * (NP - 1) + 1] = __builtin_amdgcn_perm(d[ND - 1], d[ND - 3], s16);
                 }
               }
+            }
+          }
+          if constexpr (FORM >= 3) {
+            packed = true;                                                      // (nothing below applies)
+            constexpr int NWD = 3 * NP;
+            const uint32_t* row = (const uint32_t*)(s0 + (int64_t)y * sy);
+            const int nw = 4 * (NP == 1 ? (W + 5) / 6 : (W + 2) / 3);             // whole groups of four words: six luma columns, three chroma columns
+            const uint32_t f0 = NP == 1 ? 2u * (uint32_t)(xlo + c) + 1u : 4u * (uint32_t)(xlo + c);
+            const int w0 = (int)(f0 / 3u), r = (int)f0 - 3 * w0;
+            const bool inside = w0 + NWD <= nw;
+            uint32_t d[NWD];
+            if (inside) {
+#pragma unroll
+              for (int i = 0; i < NWD; ++i) d[i] = row[w0 + i];
+            } else {                                                            // the last window of a row
+#pragma unroll
+              for (int i = 0; i < NWD; ++i) d[i] = w0 + i < nw ? row[w0 + i] : 0u;
+            }
+            uint32_t smp[4 * NP];                                               // luma: Y0 .. Y3; chroma: U0 V0 U1 V1 ..
+#pragma unroll
+            for (int i = 0; i < 4 * NP; ++i) smp[i] = c + i / NP < valid_x ? ing_v210_field<NWD>(d, r, 2 * i) : 0u;
+            if constexpr (NP == 1) {
+              v[0] = smp[0] | smp[1] << 16;
+              v[1] = smp[2] | smp[3] << 16;
+            } else {
+              v[0] = smp[0] | smp[2] << 16;
+              v[1] = smp[4] | smp[6] << 16;
+              v[2 * (NP - 1)] = smp[1] | smp[3] << 16;
+              v[2 * (NP - 1) + 1] = smp[5] | smp[7] << 16;
             }
           }
           if (packed) {
@@ -505,6 +555,49 @@ __global__ __launch_bounds__(256) void ingest_video_yuv_fields_kernel(const uint
   ing_csc_store(csc, ya, yb, c0, c1, out, fo, r0, tid);
 }
 
+// v210 frames: one workgroup = output rows [r0, r0 + 8) of all three channels of one output frame, as in ingest_video_yuv_kernel - the luma pass, then U
+// and V together, both on the v210 staging of ing_plane_pass (FORM = 3) over the same words; the chroma rows are the luma rows and take the luma vertical tables.
+// sy: the row pitch in bytes.  Kernels of their own, so that the instantiations above stay the code they were.  FORM: 3, or 4 for wide rows (ing_plane_pass).
+template <int FORM>
+__global__ __launch_bounds__(256) void ingest_video_v210_kernel(const uint8_t* __restrict__ raw, int64_t sf, int64_t sy, int n_src, int H, int W,
+                                                                 const int32_t* __restrict__ frame_table, const int32_t* __restrict__ y_first,
+                                                                 const float* __restrict__ y_w, int taps_y, const int32_t* __restrict__ x_first,
+                                                                 const float* __restrict__ x_w, int taps_x, const int32_t* __restrict__ cx_first,
+                                                                 const float* __restrict__ cx_w, int taps_cx, IngCsc csc, uint8_t* __restrict__ out, int R, int RP, int TW,
+                                                                 int RPc, int TWc) {
+  extern __shared__ __align__(16) unsigned char ing_lds[];
+  const int tid = threadIdx.x, r0 = blockIdx.x * ING_TY, fo = blockIdx.y;
+  const uint8_t* src = raw + (int64_t)ing_pick_frame(frame_table, fo, n_src) * sf;
+  float ya[1][4] = {}, yb[1][4] = {}, c0[2][4] = {}, c1[2][4] = {};
+  ing_plane_pass<1, FORM, 2>(ing_lds, src, src, sy, 0, H, W, y_first, y_w, taps_y, x_first, x_w, taps_x, R, RP, TW, r0, 0, 0, ya, yb);
+  __syncthreads();                                                             // every lane is past the LDS of the luma pass
+  ing_plane_pass<2, FORM, 2>(ing_lds, src, src, sy, 0, H, W >> 1, y_first, y_w, taps_y, cx_first, cx_w, taps_cx, 4, RPc, TWc, r0, 0, 0, c0, c1);
+  ing_csc_store(csc, ya, yb, c0, c1, out, fo, r0, tid);
+}
+
+// ingest_video_v210_kernel on the field that field_table names: the rows start `parity` pitches in, are two pitches apart, there are H / 2 of them, and the vertical
+// tables are those of the parity.  Every v210 word stays 4-byte aligned at any pitch the launcher admits, so both parities take the same loads.
+template <int FORM>
+__global__ __launch_bounds__(256) void ingest_video_v210_fields_kernel(const uint8_t* __restrict__ raw, int64_t sf, int64_t sy, int n_src, int H, int W,
+                                                                        const int32_t* __restrict__ field_table, const int32_t* __restrict__ y_first0,
+                                                                        const float* __restrict__ y_w0, const int32_t* __restrict__ y_first1,
+                                                                        const float* __restrict__ y_w1, int taps_y, const int32_t* __restrict__ x_first,
+                                                                        const float* __restrict__ x_w, int taps_x, const int32_t* __restrict__ cx_first,
+                                                                        const float* __restrict__ cx_w, int taps_cx, IngCsc csc, uint8_t* __restrict__ out, int R, int RP,
+                                                                        int TW, int RPc, int TWc, int bottom_first) {
+  extern __shared__ __align__(16) unsigned char ing_lds[];
+  const int tid = threadIdx.x, r0 = blockIdx.x * ING_TY, fo = blockIdx.y, Hf = H >> 1;
+  const IngField fl = ing_pick_field(field_table, fo, n_src, bottom_first);
+  const uint8_t* src = raw + (int64_t)fl.frame * sf + (fl.parity ? sy : 0);
+  const int32_t* yf = fl.parity ? y_first1 : y_first0;
+  const float* yw = fl.parity ? y_w1 : y_w0;
+  float ya[1][4] = {}, yb[1][4] = {}, c0[2][4] = {}, c1[2][4] = {};
+  ing_plane_pass<1, FORM, 2>(ing_lds, src, src, 2 * sy, 0, Hf, W, yf, yw, taps_y, x_first, x_w, taps_x, R, RP, TW, r0, 0, 0, ya, yb);
+  __syncthreads();                                                             // every lane is past the LDS of the luma pass
+  ing_plane_pass<2, FORM, 2>(ing_lds, src, src, 2 * sy, 0, Hf, W >> 1, yf, yw, taps_y, cx_first, cx_w, taps_cx, 4, RPc, TWc, r0, 0, 0, c0, c1);
+  ing_csc_store(csc, ya, yb, c0, c1, out, fo, r0, tid);
+}
+
 // The LDS geometry of ing_plane_pass over `planes` planes of width W: the staged row RP, the padded table's rows TW, the chunk R - what ING_LDS_BYTES leave after
 // the padded horizontal table and the tile's vertical weights, over the bytes of one staged row plus one row of the horizontal pass of every plane, at most
 // max_rows and at most ING_PF staging registers per lane, rounded down to a multiple of 4 - and the bytes in all.  false: not even 4 rows fit.  bs: bytes per
@@ -713,6 +806,66 @@ extern "C" int sf_ingest_video_yuv_planes_fields(const void* raw, int bytes_per_
   return ing_planes("sf_ingest_video_yuv_planes_fields", ING_FIELDS, raw, bytes_per_sample, stride_frame, y_off, stride_row, stride_col, u_off, v_off, stride_crow,
                     stride_ccol, shift, n_src, H, W, Hc, Wc, field_table, y_first0, y_w0, y_first1, y_w1, taps_y, x_first, x_w, taps_x, cy_first0, cy_w0, cy_first1, cy_w1,
                     taps_cy, cx_first, cx_w, taps_cx, csc, bottom_first, out, T_out, stream);
+}
+
+// The two v210 entries, beside ing_planes: that body's checks, messages and kernel picks are not touched.  fields: table holds field indices, y_first /
+// y_w are the tables of parity 0, y_first1 / y_w1 those of parity 1, bottom_first the field order; otherwise those three are unused.
+static int ing_v210(const char* who, bool fields, const void* raw, int64_t stride_frame, int64_t stride_row, int n_src, int H, int W, const int32_t* table,
+                    const int32_t* y_first, const float* y_w, const int32_t* y_first1, const float* y_w1, int taps_y, const int32_t* x_first, const float* x_w, int taps_x,
+                    const int32_t* cx_first, const float* cx_w, int taps_cx, const float* csc, int bottom_first, uint8_t* out, int T_out, void* stream) {
+  if (ing_check_args(who, T_out, {taps_y, taps_x, taps_cx}, out, W)) return -1;
+  SF_CHECK_ARG(n_src >= 1 && H >= 1 && W >= 2 && W % 2 == 0, "%s: source of %d frames %d x %d (v210 takes an even W of at least 2)", who, n_src, H, W);
+  SF_CHECK_ARG(stride_frame >= 0 && stride_row >= 0 && ((stride_frame | stride_row) & 3) == 0,
+               "%s: stride_frame = %lld, stride_row = %lld bytes (non-negative multiples of 4: v210 rows are 32-bit words)", who, (long long)stride_frame,
+               (long long)stride_row);
+  const int64_t row_bytes = 16 * (((int64_t)W + 5) / 6);
+  SF_CHECK_ARG(stride_row >= row_bytes, "%s: stride_row = %lld bytes below the %lld of a row of %d pixels (16 bytes per 6 pixels, whole groups)", who,
+               (long long)stride_row, (long long)row_bytes, W);
+  if (fields) {
+    SF_CHECK_ARG(H >= 2 && H % 2 == 0, "%s: H = %d (two fields take an even H of at least 2)", who, H);
+    SF_CHECK_ARG(n_src <= 0x3fffffff, "%s: source of %d frames", who, n_src);
+    SF_CHECK_ARG(bottom_first == 0 || bottom_first == 1, "%s: bottom_first = %d (0: top field first, 1: bottom field first)", who, bottom_first);
+  }
+  if (T_out == 0) return 0;
+  SF_CHECK_ARG(raw && table && y_first && y_w && (!fields || (y_first1 && y_w1)) && x_first && x_w && cx_first && cx_w && csc && out, "%s: null pointer", who);
+  SF_CHECK_ARG(((uintptr_t)raw & 3) == 0, "%s: raw must be 4-byte aligned", who);
+  IngGeom gy, gc;                                                               // fields: the field's tap count sizes the LDS
+  // rows too wide for four of them in ING_PF210 dwords per lane take the instantiation with the plain 16-bit budget: what that geometry fits is never refused
+  const bool big = ing_geometry_yuv(W, W / 2, taps_y, taps_x, taps_y, taps_cx, 2, ING_PF210, &gy, &gc) != 0;
+  const int wide = big ? ing_geometry_yuv(W, W / 2, taps_y, taps_x, taps_y, taps_cx, 2, 0, &gy, &gc) : 0;
+  SF_CHECK_ARG(wide != 1, "%s: W = %d is too wide for four staged source rows in LDS at taps_x = %d", who, W, taps_x);
+  SF_CHECK_ARG(wide != 2, "%s: Wc = %d is too wide for four staged rows of both chroma planes in LDS at taps_cx = %d", who, W / 2, taps_cx);
+  IngCsc k;
+  for (int i = 0; i < 9; ++i) k.m[i] = csc[i];
+  for (int i = 0; i < 3; ++i) k.o[i] = csc[9 + i];
+  const auto frames_kernel = big ? ingest_video_v210_kernel<4> : ingest_video_v210_kernel<3>;
+  const auto fields_kernel = big ? ingest_video_v210_fields_kernel<4> : ingest_video_v210_fields_kernel<3>;
+  const int rc = sf_prepare_kernel(fields ? (const void*)fields_kernel : (const void*)frames_kernel, ING_LDS_BYTES16, who);
+  if (rc) return rc;                                                            // more LDS than a kernel gets unasked
+  const dim3 grid(ING_OUT / ING_TY, (unsigned)T_out);
+  const int lds = gy.lds > gc.lds ? gy.lds : gc.lds;
+  if (fields)
+    hipLaunchKernelGGL(fields_kernel, grid, dim3(256), lds, (hipStream_t)stream, (const uint8_t*)raw, stride_frame, stride_row, n_src, H, W, table,
+                       y_first, y_w, y_first1, y_w1, taps_y, x_first, x_w, taps_x, cx_first, cx_w, taps_cx, k, out, gy.R, gy.RP, gy.TW, gc.RP, gc.TW, bottom_first);
+  else
+    hipLaunchKernelGGL(frames_kernel, grid, dim3(256), lds, (hipStream_t)stream, (const uint8_t*)raw, stride_frame, stride_row, n_src, H, W, table, y_first,
+                       y_w, taps_y, x_first, x_w, taps_x, cx_first, cx_w, taps_cx, k, out, gy.R, gy.RP, gy.TW, gc.RP, gc.TW);
+  return ing_launched(who);
+}
+
+extern "C" int sf_ingest_video_v210(const void* raw, int64_t stride_frame, int64_t stride_row, int n_src, int H, int W, const int32_t* frame_table,
+                                    const int32_t* y_first, const float* y_w, int taps_y, const int32_t* x_first, const float* x_w, int taps_x, const int32_t* cx_first,
+                                    const float* cx_w, int taps_cx, const float* csc, uint8_t* out, int T_out, void* stream) {
+  return ing_v210("sf_ingest_video_v210", false, raw, stride_frame, stride_row, n_src, H, W, frame_table, y_first, y_w, nullptr, nullptr, taps_y, x_first, x_w, taps_x,
+                  cx_first, cx_w, taps_cx, csc, 0, out, T_out, stream);
+}
+
+extern "C" int sf_ingest_video_v210_fields(const void* raw, int64_t stride_frame, int64_t stride_row, int n_src, int H, int W, const int32_t* field_table,
+                                           const int32_t* y_first0, const float* y_w0, const int32_t* y_first1, const float* y_w1, int taps_y, const int32_t* x_first,
+                                           const float* x_w, int taps_x, const int32_t* cx_first, const float* cx_w, int taps_cx, const float* csc, int bottom_first,
+                                           uint8_t* out, int T_out, void* stream) {
+  return ing_v210("sf_ingest_video_v210_fields", true, raw, stride_frame, stride_row, n_src, H, W, field_table, y_first0, y_w0, y_first1, y_w1, taps_y, x_first, x_w,
+                  taps_x, cx_first, cx_w, taps_cx, csc, bottom_first, out, T_out, stream);
 }
 
 // ---- audio ---------------------------------------------------------------------------------------------------------------------------------------------------

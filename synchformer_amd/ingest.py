@@ -40,13 +40,19 @@ deinterlacing filter (ops.ingest_video_fields, ops.ingest_video_planes_fields); 
 
     ing = RecordingIngest(dev, (30000, 1001), (1080, 1920), 48000, pix_fmt='uyvy422', field_order='tff')
 
+v210 is what SDI capture itself delivers for a 10-bit feed (DeckLink / AJA / Bluefish 10-bit YUV, QuickTime 'v210'): 4:2:2 in the uyvy422 order, three
+10-bit samples per 32-bit word, six pixels per 16 bytes, rows padded to 128 bytes (v210_row_words).  It is read as it arrives (ops.ingest_video_v210, _fields):
+
+    ing = RecordingIngest(dev, (30000, 1001), (1080, 1920), 48000, pix_fmt='v210', colorspace='bt709', field_order='tff')
+    feed = tracker.stream(ingest=ing)                           # raw frames (T, 1080, 1280) int32: a byte buffer becomes this with .view(torch.int32)
+
 Several audio programmes of one feed (an SDI / contribution feed carries up to 16 embedded channels - a stereo main mix, a second language, audio
 description - each of which can be out of sync on its own) are tracked against ONE pass of the picture:
 
     ing = RecordingIngest(dev, 25, (1080, 1920), 48000, pix_fmt='uyvy422', audio_channels=8, audio_interleaved=True, programmes=[(0, 1), (2, 3), 4])
     tracks = tracker.track_raw_programmes(raw_frames, raw_wave, ing)      # raw_wave (n, 8) int16 / int32 (s24 left-justified) / fp32 -> one OffsetTrack per programme
 
-Out of scope: decoding, 12-bit / 4:4:4 input through RecordingIngest (ops.ingest_video_planes takes a 4:4:4 planar layout), v210, deinterlacing filters, interlaced
+Out of scope: decoding, 12-bit / 4:4:4 input through RecordingIngest (ops.ingest_video_planes takes a 4:4:4 planar layout), the 12-bit and 4:4:4 packed words (v410, r210), big-endian v210, deinterlacing filters, interlaced
 4:2:0, a field order that changes mid-stream, telecine, BT.2020 in csc_matrix, transfer functions (PQ, HLG: a 10-bit HDR stream is converted by the matrix alone,
 no tone mapping), double-buffered uploads, several recordings per call; for programmes: de-embedding, channel-layout metadata, loudness normalisation, more than
 16 channels, u8 / packed s24 / float64 samples, per-programme sample rates or known delays.
@@ -64,6 +70,7 @@ PIX_FMTS_16 = ('p010', 'yuv420p10le')   # 10-bit samples in uint16: ops.ingest_v
 PIX_FMTS_422 = ('uyvy422', 'yuyv422', 'yuv422p', 'nv16', 'yuv422p10le', 'p210', 'y210')     # 4:2:2: ops.ingest_video_planes
 PIX_FMTS_422_16 = ('yuv422p10le', 'p210', 'y210')                                           # of those, 10-bit samples in uint16
 PIX_FMTS_PACKED = ('uyvy422', 'yuyv422', 'y210')                                            # raw frames (T, H, W, 2): a macropixel Y0 U Y1 V (in some order) per two columns
+PIX_FMTS_V210 = ('v210',)                                                                   # 10-bit 4:2:2, three samples per 32-bit word: ops.ingest_video_v210; raw frames (T, H, Pw) int32
 FIELD_ORDERS = ('progressive', 'tff', 'bff')                                                   # frames; interlaced, top / bottom field first
 MAX_AUDIO_CHANNELS = 16          # sf_resample_wave_mix's range (ops.MIX_MAX_CH)
 WAVE_DTYPES = (torch.float32, torch.int16, torch.int32)                                        # of an ingest with programmes: flt, s16, s32 (s24 left-justified)
@@ -125,6 +132,15 @@ def plane_layout(pix_fmt: str, H: int, W: int, strides=None) -> PlaneLayout:
     if pitched:                                                                   # H luma rows, then the rows of interleaved U V
         return PlaneLayout(b, H, W, Hc, W // 2, sf * b, 0, P, b, P * H, P * H + b, P, 2 * b, shift)
     return PlaneLayout(b, H, W, Hc, W // 2, sf * b, 0, P, b, H * W * b, (H * W + Hc * (W // 2)) * b, (W // 2) * b, b, shift)
+
+
+def v210_row_words(W: int, aligned: bool = True) -> int:
+    """The 32-bit words of a v210 row of W pixels: 32 ceil(W / 48), the conventional pitch of 128 ceil(W / 48) bytes (1920 -> 1280 words, 1280 -> 864, 720 -> 480);
+    aligned=False: the 4 ceil(W / 6) words that hold samples (whole groups of six pixels), the least a row can have."""
+    W = int(W)
+    if W < 1:
+        raise ValueError(f'v210_row_words: W = {W}')
+    return 32 * -(-W // 48) if aligned else 4 * -(-W // 6)
 
 
 def _fraction(fps) -> Fraction:
@@ -311,7 +327,7 @@ class RecordingIngest:
     YUV 4:2:0 (ops.ingest_video_yuv), or 'p010' / 'yuv420p10le': the same shape in uint16 (int16 is read as the same bits), 10-bit YUV 4:2:0
     (ops.ingest_video_yuv16), or one of PIX_FMTS_422: 4:2:2 (ops.ingest_video_planes) - 'uyvy422' / 'yuyv422' uint8 (T, H, W, 2), a pitched view read in place
     (inner strides 2, 1); 'y210' the same in uint16; 'nv16' uint8 / 'p210' uint16 (T, 2 H, W) at any row pitch; 'yuv422p' uint8 / 'yuv422p10le' uint16 (T, 2 H, W)
-    contiguous; even W only, an odd H is legal; the chroma rows take the luma tables, so 'topleft' is 'left' - converted with csc_matrix(colorspace, full_range, bit_depth) after the resize, or with csc = (M (3, 3), offsets (3,)) on the format's
+    contiguous; 'v210'  int32 / uint32 (T, H, Pw), Pw >= 4 ceil(W / 6) words at any row pitch (v210_row_words), interlaced too; even W only, an odd H is legal; the chroma rows take the luma tables, so 'topleft' is 'left' - converted with csc_matrix(colorspace, full_range, bit_depth) after the resize, or with csc = (M (3, 3), offsets (3,)) on the format's
     own sample scale when given (it overrides colorspace / full_range; e.g. BT.2020 coefficients).  chroma_loc: 'center', 'left' or 'topleft' (CHROMA_LOCS; YUV
     formats only).  ValueError on resize_side < crop, crop != 224, a source so large that a filter row passes 35 taps (short side above ~2160 at resize_side 256),
     an unknown pix_fmt, colorspace or chroma_loc, chroma_loc or csc with rgb24, and for a YUV format odd H or W or channels_last=True.
@@ -340,8 +356,8 @@ class RecordingIngest:
             mix = programme_matrix(programmes, int(audio_channels))
         if field_order not in FIELD_ORDERS:
             raise ValueError(f'field_order = {field_order!r}: one of {FIELD_ORDERS}')
-        if pix_fmt not in PIX_FMTS + PIX_FMTS_422:
-            raise ValueError(f'pix_fmt = {pix_fmt!r}: one of {PIX_FMTS + PIX_FMTS_422}')
+        if pix_fmt not in PIX_FMTS + PIX_FMTS_422 + PIX_FMTS_V210:
+            raise ValueError(f'pix_fmt = {pix_fmt!r}: one of {PIX_FMTS + PIX_FMTS_422 + PIX_FMTS_V210}')
         if chroma_loc not in CHROMA_LOCS:
             raise ValueError(f'chroma_loc = {chroma_loc!r}: one of {tuple(CHROMA_LOCS)}')
         if pix_fmt == 'rgb24' and (chroma_loc != 'center' or csc is not None):
@@ -357,9 +373,9 @@ class RecordingIngest:
         self.H, self.W = int(size_in[0]), int(size_in[1])
         if field_order != 'progressive':                                          # (a progressive object keeps the attributes it had: the class holds the defaults)
             self.field_order, self.interlaced = field_order, True
-        if self.interlaced and pix_fmt != 'rgb24' and pix_fmt not in PIX_FMTS_422:
+        if self.interlaced and pix_fmt != 'rgb24' and pix_fmt not in PIX_FMTS_422 + PIX_FMTS_V210:
             raise ValueError(f'field_order = {field_order!r} with pix_fmt = {pix_fmt!r}: interlaced 4:2:0 (field-sited chroma) is out of scope; rgb24 or one of '
-                             f'{PIX_FMTS_422}')
+                             f'{PIX_FMTS_422 + PIX_FMTS_V210}')
         if self.interlaced and (self.H % 2 or self.H < 2):
             raise ValueError(f'field_order = {field_order!r} with H = {self.H}: two fields take an even H')
         self.Hr, self.Wr = resized_dims(self.H, self.W, resize_side)
@@ -379,10 +395,11 @@ class RecordingIngest:
                              f'(a short side up to 2160 at 256)')
         self.pix_fmt = pix_fmt
         if pix_fmt != 'rgb24':
-            is422 = pix_fmt in PIX_FMTS_422
+            v210 = pix_fmt in PIX_FMTS_V210
+            is422 = pix_fmt in PIX_FMTS_422 or v210                                   # (v210 is 4:2:2 for every table below)
             if channels_last:
                 raise ValueError(f'channels_last=True with pix_fmt = {pix_fmt!r}: a YUV frame is '
-                                 f'{"(H, W, 2)" if pix_fmt in PIX_FMTS_PACKED else "(2 H, W)" if is422 else "(3 H / 2, W)"}')
+                                 f'{"(H, words per row)" if v210 else "(H, W, 2)" if pix_fmt in PIX_FMTS_PACKED else "(2 H, W)" if is422 else "(3 H / 2, W)"}')
             if self.W % 2 or (self.H % 2 and not is422):
                 raise ValueError(f'{self.H} x {self.W} with pix_fmt = {pix_fmt!r}: {"4:2:2 takes even W" if is422 else "4:2:0 takes even H and W"}')
             # chroma: an (H / 2, W / 2) image resized to the same (Hr, Wr), sliced at the same crop origin; never more taps than luma
@@ -394,7 +411,7 @@ class RecordingIngest:
             self.cx_first, self.cx_w, self.taps_cx = _crop_table(self.W // 2, self.Wr, self.x0, crop, self.dev, CHROMA_LOCS[chroma_loc][1])
             self.colorspace, self.full_range = colorspace, bool(full_range)
             if csc is None:
-                M, off = csc_matrix(colorspace, full_range, 10 if pix_fmt in PIX_FMTS_16 + PIX_FMTS_422_16 else 8)
+                M, off = csc_matrix(colorspace, full_range, 10 if pix_fmt in PIX_FMTS_16 + PIX_FMTS_422_16 + PIX_FMTS_V210 else 8)
             else:
                 M, off = (torch.as_tensor(v, dtype=torch.float64).cpu() for v in csc)
                 if M.shape != (3, 3) or off.shape != (3,):
@@ -425,6 +442,12 @@ class RecordingIngest:
         return -(-self.n * int(n_in) // self.o)
 
     def _check_frames(self, raw: torch.Tensor):
+        if self.pix_fmt in PIX_FMTS_V210:
+            need = v210_row_words(self.W, aligned=False)
+            if raw.dim() != 3 or raw.dtype not in (torch.int32, torch.uint32) or raw.shape[1] != self.H or raw.shape[2] < need:
+                raise ValueError(f'raw frames: expected int32 (T, {self.H}, Pw >= {need}) - v210 words, four per six pixels; a byte buffer becomes this with '
+                                 f'.view(torch.int32) - got {raw.dtype} {tuple(raw.shape)}')
+            return
         want = (self.H, self.W, 2) if self.pix_fmt in PIX_FMTS_PACKED else (2 * self.H, self.W) if self.pix_fmt in PIX_FMTS_422 else \
             (self.H * 3 // 2, self.W) if self.pix_fmt != 'rgb24' else (self.H, self.W, 3) if self.channels_last else (3, self.H, self.W)
         dtypes = (torch.uint16, torch.int16) if self.pix_fmt in PIX_FMTS_16 + PIX_FMTS_422_16 else (torch.uint8,)
@@ -455,6 +478,10 @@ class RecordingIngest:
                 return ops.ingest_video_fields(src, self.channels_last, table, self.y_tables, *x, bff)
             return ops.ingest_video(src, self.channels_last, table, *y, *x)
         cy, cx = (self.cy_first, self.cy_w), (self.cx_first, self.cx_w)
+        if self.pix_fmt in PIX_FMTS_V210:
+            if self.interlaced:
+                return ops.ingest_video_v210_fields(src, self.W, table, self.y_tables, *x, *cx, self.csc, bff)
+            return ops.ingest_video_v210(src, self.W, table, *y, *x, *cx, self.csc)
         if self.pix_fmt in PIX_FMTS_422:                                         # (the only YUV formats an interlaced ingest takes)
             layout = plane_layout(self.pix_fmt, self.H, self.W, src.stride())
             if self.interlaced:
@@ -569,7 +596,7 @@ class IngestStream:
         if raw is not None and raw.shape[0]:
             ing._check_frames(raw)
             new = raw.to(ing.dev, non_blocking=True)
-            new = new.view(torch.int16) if new.dtype == torch.uint16 else new     # (the same bits; the kernels read either)
+            new = new.view(torch.int16) if new.dtype == torch.uint16 else new.view(torch.int32) if new.dtype == torch.uint32 else new     # (the same bits; the kernels read either)
             src, base = (new, self.n_src) if src is None else (torch.cat([src, new]), base)
             self.n_src += int(raw.shape[0])
         u = 2 if ing.interlaced else 1                                            # an interlaced frame is two fields at twice the rate: the slots are the fields'

@@ -1279,6 +1279,54 @@ def ingest_video_planes_fields(raw: torch.Tensor, layout, field_table: torch.Ten
     return _ingest_chunks('sf_ingest_video_yuv_planes_fields', head, field_table, tail, out, raw.device)
 
 
+def _ingest_v210_source(who: str, raw: torch.Tensor, W: int, fields: bool = False):
+    """The v210 frames of `who` -> the launcher's (frame stride, row stride) in BYTES, then (n_src, H, W).  ValueError: a host tensor, another dtype or rank, odd W,
+    rows shorter than the whole groups of W pixels, a column stride other than 1, a negative stride; fields: an odd H."""
+    W = int(W)
+    if raw.dim() != 3 or raw.dtype not in (torch.int32, torch.uint32):
+        raise ValueError(f'{who}: expected int32 or uint32 v210 frames (n, H, words per row), got {raw.dtype} {tuple(raw.shape)}')
+    if W < 2 or W % 2:
+        raise ValueError(f'{who}: W = {W}: v210 takes an even W')
+    need = 4 * -(-W // 6)
+    if raw.shape[2] < need:
+        raise ValueError(f'{who}: rows of {raw.shape[2]} words, a v210 row of {W} pixels has {need} (four per six pixels, whole groups)')
+    n_src, H = raw.shape[0], raw.shape[1]
+    sf, sy, sx = raw.stride()
+    if sx != 1 or sf < 0 or sy < 0:
+        raise ValueError(f'{who}: v210 frames with strides {tuple(raw.stride())}: unit column stride and non-negative frame and row strides expected')
+    if fields and (H < 2 or H % 2):
+        raise ValueError(f'{who}: H = {H}: two fields take an even H')
+    if raw.device.type == 'cpu':                                               # (last: everything above is checked without a device)
+        raise ValueError(f'{who}: raw frames on the host: the launcher reads device memory')
+    return 4 * sf, 4 * sy, n_src, H, W
+
+
+def ingest_video_v210(raw: torch.Tensor, W: int, frame_table: torch.Tensor, y_first: torch.Tensor, y_w: torch.Tensor, x_first: torch.Tensor, x_w: torch.Tensor,
+                      cx_first: torch.Tensor, cx_w: torch.Tensor, csc, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ingest_video_planes for v210 frames (sf_ingest_video_v210): 10-bit 4:2:2 as SDI capture hands it out, the fields Cb Y Cr Y .. of a row three to a
+    32-bit word.  raw int32 or uint32 (the same bits) (n_src, H, Pw) on the device, unit stride along a row, any row stride of at least 4 ceil(W / 6) words (a pitched
+    capture surface is read in place; ingest.v210_row_words), any non-negative frame stride; W: the picture's width, even.  Padding words, the unused fields of a last
+    partial group and bits 30 - 31 never reach the output.  The tables as for ingest_video_planes on a 4:2:2 format - the chroma rows take the luma vertical tables, so
+    there are no cy tables; csc: 12 floats on the 10-bit scale -> uint8 (T_out, 3, 224, 224), bit for bit what ingest_video_planes gives for the same samples as
+    yuv422p10le.  ValueError on a host tensor, another dtype or rank, Pw below 4 ceil(W / 6), odd W, a negative stride; what the launcher refuses is a RuntimeError."""
+    geom = _ingest_v210_source('ingest_video_v210', raw, W)
+    csc_c = _ingest_csc('ingest_video_v210', csc)
+    head, tabs = (_dev(raw, 'raw'), *geom), _ingest_tables(frame_table, y=(y_first, y_w), x=(x_first, x_w), cx=(cx_first, cx_w))
+    return _ingest_chunks('sf_ingest_video_v210', head, frame_table, (*tabs, C.addressof(csc_c)), out, raw.device)
+
+
+def ingest_video_v210_fields(raw: torch.Tensor, W: int, field_table: torch.Tensor, y_tables, x_first: torch.Tensor, x_w: torch.Tensor, cx_first: torch.Tensor,
+                             cx_w: torch.Tensor, csc, bottom_first: bool, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ingest_video_v210 on an interlaced recording (sf_ingest_video_v210_fields): raw and W as there with H even; field_table, y_tables and bottom_first as for
+    ingest_video_fields (luma and chroma rows share the pair of vertical tables) -> uint8 (T_out, 3, 224, 224), every output frame one field."""
+    geom = _ingest_v210_source('ingest_video_v210_fields', raw, W, fields=True)
+    csc_c = _ingest_csc('ingest_video_v210_fields', csc)
+    _field_pairs('ingest_video_v210_fields', y=y_tables)
+    tabs = _field_tables(field_table, y=y_tables) + _ingest_tables(field_table, x=(x_first, x_w), cx=(cx_first, cx_w))
+    tail = (*tabs, C.addressof(csc_c), int(bool(bottom_first)))
+    return _ingest_chunks('sf_ingest_video_v210_fields', (_dev(raw, 'raw'), *geom), field_table, tail, out, raw.device)
+
+
 SF_I16 = 4
 
 

@@ -2,7 +2,7 @@
 beside the same windows through forward_clips on explicit 120-frame slices.  Prints one JSON line.
 
     python tools/track_recording.py [--seconds 60] [--hop 1] [--seg-chunk 224] [--host] [--clip-windows 8] [--fps 30000/1001 --size 1080x1920 --rate 48000]
-                                    [--pix-fmt {rgb24,nv12,yuv420p,p010,yuv420p10le,uyvy422,yuyv422,yuv422p,nv16,yuv422p10le,p210,y210}]
+                                    [--pix-fmt {rgb24,nv12,yuv420p,p010,yuv420p10le,uyvy422,yuyv422,yuv422p,nv16,yuv422p10le,p210,y210,v210}]
                                     [--chroma-loc {center,left,topleft}] [--field-order {progressive,tff,bff}] [--posterior]
                                     [--stream SECONDS [--lag N]] [--gate [--mu X]]
                                     [--audio-channels N [--audio-interleaved] [--sample-fmt {flt,s16,s32}] --programmes 0+1,2+3,4]
@@ -13,7 +13,8 @@ frames next to the bank from frames ingested beforehand.  With --pix-fmt nv12 / 
 the bytes per frame, which the line reports next to the times (with --host they are what is uploaded).  With --pix-fmt p010 / yuv420p10le they are 10-bit
 4:2:0 in 16-bit samples: the bytes of RGB again.  With a 4:2:2 layout the raw frames are (H, W, 2) for the packed uyvy422 / yuyv422
 (uint8) and y210 (uint16), (2 H, W) for yuv422p / nv16 (uint8) and yuv422p10le / p210 (uint16): 2 H W bytes per frame in 8 bits, 4 H W in 16.  --chroma-loc sites the chroma samples of a YUV layout (tables only: no cost on the device).
-With --field-order tff / bff the raw frames are interlaced (rgb24 and the 4:2:2 layouts): --fps stays the frame rate, every 25 fps frame is the one field
+With --pix-fmt v210 the raw frames are int32 (H, v210_row_words(W)): random words, 10-bit 4:2:2 at 128 ceil(W / 48) bytes per row (5120 at 1920).
+With --field-order tff / bff the raw frames are interlaced (rgb24, the 4:2:2 layouts and v210): --fps stays the frame rate, every 25 fps frame is the one field
 nearest its slot resized on its own, and the line reports the field order, the fields shown and the field's vertical taps (half the source rows are read).
 
 With --posterior the windows are also read out as marginals: the line then carries the mean and minimum of conf_post, log_z per window step
@@ -64,11 +65,11 @@ def main():
     ap.add_argument('--fps', default=None, help='raw frame rate, e.g. 30, 29.97 or 30000/1001 (default: 25, no ingest)')
     ap.add_argument('--size', default=None, help='raw frame size HxW, e.g. 1080x1920')
     ap.add_argument('--rate', type=int, default=None, help='raw sample rate in Hz, e.g. 48000')
-    ap.add_argument('--pix-fmt', choices=['rgb24', 'nv12', 'yuv420p', 'p010', 'yuv420p10le', 'uyvy422', 'yuyv422', 'yuv422p', 'nv16', 'yuv422p10le', 'p210', 'y210'],
-                    default=None, help='layout of the raw frames (default: rgb24, channels-last); 4:2:2: uyvy422 / yuyv422 / y210 frames are (H, W, 2), the others (2 H, W)')
+    ap.add_argument('--pix-fmt', choices=['rgb24', 'nv12', 'yuv420p', 'p010', 'yuv420p10le', 'uyvy422', 'yuyv422', 'yuv422p', 'nv16', 'yuv422p10le', 'p210', 'y210', 'v210'],
+                    default=None, help='layout of the raw frames (default: rgb24, channels-last); 4:2:2: uyvy422 / yuyv422 / y210 frames are (H, W, 2), the others (2 H, W); v210: int32 (H, words per row)')
     ap.add_argument('--chroma-loc', choices=['center', 'left', 'topleft'], default='center', help='where the chroma samples of a YUV layout sit')
     ap.add_argument('--field-order', choices=['progressive', 'tff', 'bff'], default='progressive',
-                    help='interlaced raw frames, top / bottom field first: the field nearest each 25 fps slot is ingested on its own (rgb24 and 4:2:2 layouts)')
+                    help='interlaced raw frames, top / bottom field first: the field nearest each 25 fps slot is ingested on its own (rgb24, 4:2:2 layouts and v210)')
     ap.add_argument('--posterior', action='store_true', help='also read the windows out as marginals (forward-backward)')
     ap.add_argument('--stream', type=float, default=None, metavar='SECONDS', help='also push the recording through OffsetTracker.stream in pieces of this length')
     ap.add_argument('--lag', type=int, default=16, help='decision lag of the stream, in windows')
@@ -82,7 +83,7 @@ def main():
     from synchformer_amd import ops, synth
     from synchformer_amd.engine import SynchformerEngine
     from synchformer_amd.frontend import MelFrontend, recording_geometry
-    from synchformer_amd.ingest import PIX_FMTS_422, PIX_FMTS_422_16, PIX_FMTS_PACKED, RecordingIngest
+    from synchformer_amd.ingest import PIX_FMTS_422, PIX_FMTS_422_16, PIX_FMTS_PACKED, PIX_FMTS_V210, RecordingIngest, v210_row_words
     from synchformer_amd.track import OffsetTracker
     dev = torch.device('cuda:0')
     if args.programmes is not None:
@@ -101,6 +102,9 @@ def main():
         # random bits are a valid frame in every layout (stray bits of a 16-bit word are dropped)
         raw_shape = (RH, RW, 3) if pix_fmt == 'rgb24' else (RH, RW, 2) if pix_fmt in PIX_FMTS_PACKED else (2 * RH, RW) if pix_fmt in PIX_FMTS_422 else (RH * 3 // 2, RW)
         frame_bytes = RH * RW * 3 if pix_fmt == 'rgb24' else RH * RW * (2 if pix_fmt in PIX_FMTS_422 else 3) // (1 if pix_fmt in PIX_FMTS_422 else 2) * (2 if deep else 1)
+        if pix_fmt in PIX_FMTS_V210:                                              # rows of 32-bit words at the conventional pitch; random words are a valid frame
+            raw_shape = (RH, v210_row_words(RW))
+            frame_bytes = 4 * raw_shape[0] * raw_shape[1]
         T_raw, n_raw = int(args.seconds * ing.fps_in), int(args.seconds * ing.rate_in)
         T, n = ing.n_frames(T_raw), ing.n_samples(n_raw)
     else:
@@ -114,7 +118,9 @@ def main():
     gen = torch.Generator().manual_seed(7)
     if raw_mode:
         dgen = torch.Generator(device=dev).manual_seed(7)
-        if deep:
+        if pix_fmt in PIX_FMTS_V210:
+            raw = torch.randint(-(1 << 31), (1 << 31) - 1, (T_raw, *raw_shape), generator=dgen, dtype=torch.int32, device=dev)
+        elif deep:
             raw = torch.randint(-32768, 32768, (T_raw, *raw_shape), generator=dgen, dtype=torch.int16, device=dev).view(torch.uint16)
         else:
             raw = torch.randint(0, 256, (T_raw, *raw_shape), generator=dgen, dtype=torch.uint8, device=dev)
@@ -230,7 +236,7 @@ def programmes_main(args, dev):
     from synchformer_amd import synth
     from synchformer_amd.engine import SynchformerEngine
     from synchformer_amd.frontend import MelFrontend
-    from synchformer_amd.ingest import PIX_FMTS_422, PIX_FMTS_422_16, PIX_FMTS_PACKED, RecordingIngest
+    from synchformer_amd.ingest import PIX_FMTS_422, PIX_FMTS_422_16, PIX_FMTS_PACKED, PIX_FMTS_V210, RecordingIngest, v210_row_words
     from synchformer_amd.track import OffsetTracker
     progs = [tuple(int(c) for c in part.split('+')) for part in args.programmes.split(',')]
     progs = [p[0] if len(p) == 1 else p for p in progs]
@@ -245,7 +251,9 @@ def programmes_main(args, dev):
     raw_shape = (RH, RW, 3) if pix_fmt == 'rgb24' else (RH, RW, 2) if pix_fmt in PIX_FMTS_PACKED else (2 * RH, RW) if pix_fmt in PIX_FMTS_422 else (RH * 3 // 2, RW)
     T_raw, n_raw = int(args.seconds * ing.fps_in), int(args.seconds * ing.rate_in)
     dgen = torch.Generator(device=dev).manual_seed(7)
-    if deep:
+    if pix_fmt in PIX_FMTS_V210:
+        raw = torch.randint(-(1 << 31), (1 << 31) - 1, (T_raw, RH, v210_row_words(RW)), generator=dgen, dtype=torch.int32, device=dev)
+    elif deep:
         raw = torch.randint(-32768, 32768, (T_raw, *raw_shape), generator=dgen, dtype=torch.int16, device=dev).view(torch.uint16)
     else:
         raw = torch.randint(0, 256, (T_raw, *raw_shape), generator=dgen, dtype=torch.uint8, device=dev)
