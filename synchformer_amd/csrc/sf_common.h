@@ -19,11 +19,13 @@ void sf_set_error(const char* fmt, ...);
   do {                                                           \
     if (!(cond)) { sf_set_error(__VA_ARGS__); return -1; }       \
   } while (0)
-#define SF_LAUNCH_CHECK()                                                        \
+// SF_LAUNCH_CHECK_AS(who): for a launcher template shared by several entries, whose __func__ would name the template and not the entry that was called
+#define SF_LAUNCH_CHECK_AS(who)                                                  \
   do {                                                                           \
     hipError_t e__ = hipGetLastError();                                          \
-    if (e__ != hipSuccess) { sf_set_error("%s: %s", __func__, hipGetErrorString(e__)); return (int)e__; } \
+    if (e__ != hipSuccess) { sf_set_error("%s: %s", who, hipGetErrorString(e__)); return (int)e__; } \
   } while (0)
+#define SF_LAUNCH_CHECK() SF_LAUNCH_CHECK_AS(__func__)
 
 // ---- per-device launch set-up (sf_misc.hip): safe for a process that drives several GPUs and for concurrent host threads ---------------
 // sf_prepare_kernel: hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, current device) - the attribute is per device, a process-wide

@@ -16,11 +16,12 @@
 //   1. track_fb_scan_kernel:     TWO workgroups of one wavefront each, side by side: block 0 the forward scan (a, and log_z), block 1 the backward scan (b);
 //   2. track_fb_combine_kernel:  one thread per window: post = softmax_c (a + b), its argmax and value, the posterior mean of the grid.
 //
-// sf_track_stream_push (further below) reads a stream of rows out at a fixed lag with carried state; sf_track_pool_push (at the end) does that for many streams
-// in one call: the same launches over a descriptor table, blockIdx.y = the stream, every block running the single-stream device functions on its stream's context.
-// sf_track_decode_gated / sf_track_posterior_gated (after the pool) are the two offline read-outs of one chain over (offset class, synchronizable flag), fed by a
-// second head; sf_track_stream_push_gated / sf_track_pool_push_gated (last) read that chain out of a stream at a fixed lag, from a carried state 2C wide: the stream's
-// four kinds of launch around the gated kernels' own step functions.
+// sf_track_decode_gated / sf_track_posterior_gated (next) are the two offline read-outs of one chain over (offset class, synchronizable flag), fed by a second head.
+// The last section reads either chain out of live feeds at a fixed lag with carried state, and is written ONCE: a chain is a small policy struct (TrackChainPlain over
+// the C offset classes, TrackChainGated over the 2C states) that says what a lane, a row's inputs, a step and a ring are, around the step functions of the offline
+// kernels; the rows struct, the state layout, the scan / read-out / keep bodies, the three stream and three pool kernels and the two launchers are templates on it.
+// sf_track_stream_push(_gated) read one stream, sf_track_pool_push(_gated) many in one call: the same launches over a descriptor table, blockIdx.y = the stream, every
+// block running the single-stream bodies on its stream's context.  The four entries pack their arguments and call the templates.
 #include "sf_common.h"
 #include "../../include/synchformer_hip.h"
 #include <algorithm>
@@ -288,530 +289,10 @@ extern "C" int sf_track_posterior(const float* logits, int64_t ldl, int W, int C
   return 0;
 }
 
-// ---- fixed-lag read-out of a stream (sf_track_stream_push) -------------------------------------------------------------------------------------------------
-// Rows arrive in pushes; window w is committed by the push that delivers row w + lag, as path_{w+lag}[w] / post_{w+lag}[w] (the offline read-outs of the prefix
-// 0 .. w + lag), and never revised.  Both scans are causal, so what a push needs of the past is the scan vectors after the last row (s; with the posterior a and
-// the double of subtracted maxima) and, of the last `lag` rows, the back pointers, the logits (conf_lag, and the backward recursion's log-softmax, which is
-// recomputed from them as the offline scan does) and - posterior - the normalised a.  The state buffer holds exactly that, the per-row parts as rings (row r in
-// slot r % lag); its size does not depend on how many rows have passed.  A push of n rows is three or four launches on the caller's stream:
-//   1. track_rows_kernel<false>:     cls_raw / conf_raw of the new rows (the offline kernel);
-//   2. track_stream_scan_kernel:     one wavefront per scan, side by side (block 0 Viterbi, block 1 forward): loads the carried vector, runs the n rows with the next
-//                                    row's load under the current step, writes back pointers / a and every row's end state (argmax s_r) into the push's workspace,
-//                                    stores the carried vectors;
-//   3. track_stream_readout_kernel:  one wavefront per window that becomes committed: its own backtrace from the end state of row w + lag (eight rows of back
-//                                    pointers per round, wave-uniform shuffles), with the posterior its own backward recursion over rows w + lag .. w + 1 and the
-//                                    combine of row w; one more wavefront backtraces the tail from the last row.  The windows are independent: a catch-up push of
-//                                    1000 rows spreads over the chip instead of running n * lag dependent steps in one wavefront;
-//   4. track_stream_keep_kernel:     copies the last min(lag, n) new rows into the rings (after 3, which still reads the slots they replace).
-// Rows before the push live in the rings, rows of the push in the caller's logits and the workspace: TrackStreamRows resolves a row index to either.
-struct TrackStreamRows {
-  const float* lg_new;  int64_t ldl;      // the push's logits
-  const uint8_t* bp_new;                  // workspace: back pointers (n, C)
-  const float* a_new;                     // workspace: normalised a (n, C); posterior only
-  const int32_t* end_new;                 // workspace: argmax s_r per new row
-  const float* lg_ring;  const uint8_t* bp_ring;  const float* a_ring;      // state: (lag, C) each
-  const int32_t* end_last;                // state: argmax s of the last row pushed
-  int64_t t_old;                          // rows before this push
-  int lag, C;
-  __device__ __forceinline__ const float* logits(int64_t r) const { return r >= t_old ? lg_new + (r - t_old) * ldl : lg_ring + (r % lag) * C; }
-  __device__ __forceinline__ const uint8_t* backptr(int64_t r) const { return r >= t_old ? bp_new + (r - t_old) * C : bp_ring + (r % lag) * C; }
-  __device__ __forceinline__ const float* a(int64_t r) const { return r >= t_old ? a_new + (r - t_old) * C : a_ring + (r % lag) * C; }
-  __device__ __forceinline__ int end(int64_t r) const { return r >= t_old ? end_new[r - t_old] : end_last[0]; }
-  __device__ __forceinline__ int width() const { return C; }
-};
-
-// the state buffer: [double shifted][int32 end_last, pad][s: 64 floats][posterior: a: 64 floats][logits ring][posterior: a ring][back pointer ring]
-struct TrackStreamLayout {
-  int64_t s, a, lg_ring, a_ring, bp_ring, total;
-  __host__ __device__ TrackStreamLayout(int C, int lag, bool posterior) {
-    s = 16;
-    a = s + TRACK_MAX_C * 4;
-    lg_ring = a + (posterior ? TRACK_MAX_C * 4 : 0);
-    a_ring = lg_ring + (int64_t)lag * C * 4;
-    bp_ring = a_ring + (posterior ? (int64_t)lag * C * 4 : 0);
-    total = (bp_ring + (int64_t)lag * C + 15) & ~(int64_t)15;
-  }
-};
-
 // The end state of a row: the lowest class whose renormalised score is the maximum, 0.  (No such lane - NaN scores - gives class 0, as a NaN never wins `>`.)
 __device__ __forceinline__ int track_wave_end_state(float s, bool live) {
   const unsigned long long hit = __ballot(live && s == 0.f);
   return hit ? __ffsll((long long)hit) - 1 : 0;
-}
-
-// The scan of one stream's push, by one wavefront: fwd = false the Viterbi scan, fwd = true the forward scan (wave-uniform).  s_u: TRACK_MAX_C floats of LDS, 16-byte
-// aligned.  The single-stream kernel and the pool's kernel (sf_track_pool_push) both run this body: one stream's arithmetic is the same in either.
-__device__ __forceinline__ void track_stream_scan_body(const float* __restrict__ logits, int64_t ldl, int n, int C, float lam, int64_t t_old,
-                                                       unsigned char* __restrict__ state, int lag, int posterior, uint8_t* __restrict__ bp_new,
-                                                       float* __restrict__ a_new, int32_t* __restrict__ end_new, float* __restrict__ log_z, bool fwd, float* s_u) {
-  const TrackStreamLayout lay(C, lag, posterior != 0);
-  const int c = threadIdx.x;
-  const bool live = c < C;
-  const int C4 = (C + 3) & ~3;
-  const float ninf = -INFINITY;
-  float* carried = reinterpret_cast<float*>(state + (fwd ? lay.a : lay.s));
-  double* st_shifted = reinterpret_cast<double*>(state);
-  int32_t* st_end = reinterpret_cast<int32_t*>(state + 8);
-  double shifted = (fwd && t_old > 0) ? st_shifted[0] : 0.0;
-  float v = (t_old > 0 && live) ? carried[c] : ninf;
-  int k = 0;
-  float l_next = (live && n > 0) ? logits[c] : ninf;
-  if (t_old == 0 && n > 0) {                                       // the first row of the stream: s_0 = e[0] / a_0 = e[0], as the offline scans begin
-    const float l = l_next;
-    if (n > 1) l_next = live ? logits[ldl + c] : ninf;
-    if (fwd) {
-      v = fb_log_softmax(l);
-      const float m = fb_finite_or_zero(wave_max(v));
-      v -= m;
-      shifted += (double)m;
-      if (live) a_new[c] = v;
-    } else {
-      v = l - wave_max(l);
-      if (live) bp_new[c] = 0;                                     // never followed: the backtrace stops at row 1
-      const int end = track_wave_end_state(v, live);               // (the ballot needs the whole wavefront)
-      if (c == 0) end_new[0] = end;
-    }
-    k = 1;
-  }
-  s_u[c] = v;
-  __syncthreads();
-  for (; k < n; ++k) {
-    const float l = l_next;
-    if (k + 1 < n) l_next = live ? logits[(int64_t)(k + 1) * ldl + c] : ninf;       // the next row's load travels under this step
-    if (fwd) {
-      float m;
-      v = fb_scan_step(s_u, C4, c, live, false, lam, fb_log_softmax(l), m);
-      shifted += (double)m;
-      if (live) a_new[(int64_t)k * C + c] = v;
-    } else {
-      int bp;
-      v = track_viterbi_step(s_u, C, c, live, lam, l, bp);
-      if (live) bp_new[(int64_t)k * C + c] = (uint8_t)bp;
-      const int end = track_wave_end_state(v, live);
-      if (c == 0) end_new[k] = end;
-    }
-    __syncthreads();                                               // every lane has read s_u
-    s_u[c] = v;
-    __syncthreads();
-  }
-  if (n > 0) {
-    const int end = track_wave_end_state(v, live);
-    if (live) carried[c] = v;
-    if (c == 0) {
-      if (fwd) st_shifted[0] = shifted;
-      else st_end[0] = end;
-    }
-  }
-  if (fwd) {
-    const float z = logf(wave_sum(expf(v)));                       // the normalised a of the last row: maximum 0
-    if (c == 0) log_z[0] = (float)(shifted + (double)z);
-  }
-}
-
-__global__ __launch_bounds__(64) void track_stream_scan_kernel(const float* __restrict__ logits, int64_t ldl, int n, int C, float lam, int64_t t_old,
-                                                                unsigned char* __restrict__ state, int lag, int posterior, uint8_t* __restrict__ bp_new,
-                                                                float* __restrict__ a_new, int32_t* __restrict__ end_new, float* __restrict__ log_z) {
-  __shared__ __attribute__((aligned(16))) float s_u[TRACK_MAX_C];
-  track_stream_scan_body(logits, ldl, n, C, lam, t_old, state, lag, posterior, bp_new, a_new, end_new, log_z, blockIdx.x == 1, s_u);      // block 1: the forward scan
-}
-
-// Follows the back pointers of rows R .. w + 1 from class `cur` (the class at row R) -> the class at row w.  Lane c loads backptr[r, c] of eight rows at a time, the
-// chain itself is eight wave-uniform shuffles.  KEEP: tail[r - w] = the class at row r, for every r in [w, R] (LDS, written by lane 0).
-template <bool KEEP, class Rows>
-__device__ __forceinline__ int track_stream_backtrace(const Rows& rows, int64_t R, int64_t w, int cur, int c, bool live, int* tail) {
-  const int C = rows.width();                                      // entries of one row of back pointers (the gated chain: 2C states)
-  for (int64_t r0 = R; r0 > w; r0 -= 8) {
-    int b[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) b[j] = (live && r0 - j > w) ? (int)rows.backptr(r0 - j)[c] : 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      if (r0 - j > w) {                                            // wave-uniform
-        if (KEEP && c == 0) tail[r0 - j - w] = cur;
-        const int p = __shfl(b[j], cur, 64);
-        cur = p < C ? p : C - 1;
-      }
-    }
-  }
-  if (KEEP && c == 0) tail[0] = cur;
-  return cur;
-}
-
-// Block i < n_commit: window w = w0 + i, read from the prefix that ends at row R = min(w + lag, t_last).  Block n_commit (if n_tail > 0): the tail, the path of the
-// whole prefix on the last n_tail rows.
-// bx = the block's index among the stream's n_commit + (n_tail > 0) blocks; s_u (16-byte aligned) / s_b: TRACK_MAX_C floats of LDS each, s_tail: 256 ints.
-template <bool POST>
-__device__ __forceinline__ void track_stream_readout_body(const TrackStreamRows& rows, float lam, const float* __restrict__ grid, int64_t w0, int n_commit, int n_tail,
-                                                          int64_t t_last, int32_t* __restrict__ cls_lag, float* __restrict__ conf_lag,
-                                                          float* __restrict__ post_lag, int64_t ldp, int32_t* __restrict__ cls_post_lag,
-                                                          float* __restrict__ conf_post_lag, float* __restrict__ offset_mean_lag,
-                                                          int32_t* __restrict__ cls_tail, float* __restrict__ conf_tail, int bx, float* s_u, float* s_b, int* s_tail) {
-  const int c = threadIdx.x;
-  const int C = rows.C;
-  const bool live = c < C;
-  if (bx == n_commit) {                                            // the tail
-    const int64_t w = t_last - (n_tail - 1);
-    int cur = rows.end(t_last);
-    cur = cur < 0 ? 0 : (cur >= C ? C - 1 : cur);
-    track_stream_backtrace<true>(rows, t_last, w, cur, c, live, s_tail);
-    __syncthreads();
-    for (int i = c; i < n_tail; i += 64) {
-      const float* row = rows.logits(w + i);
-      int best;
-      float m, sum;
-      track_row_stats(row, C, best, m, sum);
-      cls_tail[i] = s_tail[i];
-      conf_tail[i] = track_row_conf(row, C, s_tail[i], m, sum);
-    }
-    return;
-  }
-  const int i = bx;
-  const int64_t w = w0 + i;
-  const int64_t R = w + rows.lag < t_last ? w + rows.lag : t_last;
-  int cur = rows.end(R);
-  cur = cur < 0 ? 0 : (cur >= C ? C - 1 : cur);
-  cur = track_stream_backtrace<false>(rows, R, w, cur, c, live, nullptr);
-  if (c == 0) {
-    const float* row = rows.logits(w);
-    int best;
-    float m, sum;
-    track_row_stats(row, C, best, m, sum);
-    cls_lag[i] = cur;
-    conf_lag[i] = track_row_conf(row, C, cur, m, sum);
-  }
-  if (POST) {
-    // the backward scan of the prefix 0 .. R, from its end down to row w:  b_R = 0;  b_r[c] = lse_n (b_{r+1}[n] + e[r+1, n] - lam |n - c|), renormalised per step
-    const int C4 = (C + 3) & ~3;
-    const float ninf = -INFINITY;
-    float v = live ? 0.f : ninf;
-    float l_next = live ? rows.logits(R)[c] : ninf;
-    for (int64_t r = R; r > w; --r) {                              // b_{r-1} from b_r and row r
-      const float l = l_next;
-      if (r - 1 > w) l_next = live ? rows.logits(r - 1)[c] : ninf;
-      const float e = fb_log_softmax(l);
-      __syncthreads();                                             // every lane has read s_u
-      s_u[c] = v + e;
-      __syncthreads();
-      float m;
-      v = fb_scan_step(s_u, C4, c, live, true, lam, 0.f, m);
-    }
-    s_b[c] = v;
-    __syncthreads();
-    if (c == 0) {
-      int best;
-      float pbest, mean;
-      fb_combine_row(rows.a(w), s_b, C, grid, post_lag + (int64_t)i * ldp, best, pbest, mean);
-      cls_post_lag[i] = best;
-      conf_post_lag[i] = pbest;
-      offset_mean_lag[i] = mean;
-    }
-  }
-}
-
-template <bool POST>
-__global__ __launch_bounds__(64) void track_stream_readout_kernel(TrackStreamRows rows, float lam, const float* __restrict__ grid, int64_t w0, int n_commit, int n_tail,
-                                                                   int64_t t_last, int32_t* __restrict__ cls_lag, float* __restrict__ conf_lag,
-                                                                   float* __restrict__ post_lag, int64_t ldp, int32_t* __restrict__ cls_post_lag,
-                                                                   float* __restrict__ conf_post_lag, float* __restrict__ offset_mean_lag,
-                                                                   int32_t* __restrict__ cls_tail, float* __restrict__ conf_tail) {
-  __shared__ __attribute__((aligned(16))) float s_u[TRACK_MAX_C];
-  __shared__ float s_b[TRACK_MAX_C];
-  __shared__ int s_tail[256];
-  track_stream_readout_body<POST>(rows, lam, grid, w0, n_commit, n_tail, t_last, cls_lag, conf_lag, post_lag, ldp, cls_post_lag, conf_post_lag, offset_mean_lag, cls_tail,
-                                  conf_tail, (int)blockIdx.x, s_u, s_b, s_tail);
-}
-
-// Ring row j of a push: new row k = k0 + j (row t_old + k of the stream) into slot (t_old + k) % lag of the rings.
-__device__ __forceinline__ void track_stream_keep_body(const float* __restrict__ logits, int64_t ldl, const uint8_t* __restrict__ bp_new, const float* __restrict__ a_new,
-                                                       int k0, int64_t t_old, int C, int lag, int posterior, unsigned char* __restrict__ state, int j) {
-  const TrackStreamLayout lay(C, lag, posterior != 0);
-  const int c = threadIdx.x;
-  if (c >= C) return;
-  const int64_t k = k0 + (int64_t)j;
-  const int64_t slot = ((t_old + k) % lag) * C + c;
-  reinterpret_cast<float*>(state + lay.lg_ring)[slot] = logits[k * ldl + c];
-  (state + lay.bp_ring)[slot] = bp_new[k * C + c];
-  if (posterior) reinterpret_cast<float*>(state + lay.a_ring)[slot] = a_new[k * C + c];
-}
-
-// Block j: ring row j.
-__global__ __launch_bounds__(64) void track_stream_keep_kernel(const float* __restrict__ logits, int64_t ldl, const uint8_t* __restrict__ bp_new,
-                                                                const float* __restrict__ a_new, int k0, int64_t t_old, int C, int lag, int posterior,
-                                                                unsigned char* __restrict__ state) {
-  track_stream_keep_body(logits, ldl, bp_new, a_new, k0, t_old, C, lag, posterior, state, (int)blockIdx.x);
-}
-
-static bool track_stream_shape_ok(const char* who, int C, int lag) {
-  if (C < 2 || C > TRACK_MAX_C) { sf_set_error("%s: C = %d classes out of range (2 .. %d: one lane per class)", who, C, TRACK_MAX_C); return false; }
-  if (lag < 0 || lag > 255) { sf_set_error("%s: lag = %d windows out of range (0 .. 255)", who, lag); return false; }
-  return true;
-}
-
-extern "C" int sf_track_stream_bytes(int C, int lag, int posterior) {
-  if (!track_stream_shape_ok("sf_track_stream_bytes", C, lag)) return -1;
-  return (int)TrackStreamLayout(C, lag, posterior != 0).total;     // at most 16 + 512 + 255 * 64 * 9
-}
-
-// the workspace of a push: [posterior: a (n, C) fp32][end (n) int32][back pointers (n, C) bytes]
-#define TRACK_STREAM_MAX_PUSH (1 << 20)
-extern "C" int sf_track_stream_workspace_bytes(int C, int n, int posterior) {
-  SF_CHECK_ARG(C >= 2 && C <= TRACK_MAX_C, "sf_track_stream_workspace_bytes: C = %d classes out of range (2 .. %d)", C, TRACK_MAX_C);
-  SF_CHECK_ARG(n >= 0 && n <= TRACK_STREAM_MAX_PUSH, "sf_track_stream_workspace_bytes: n = %d rows in one push (0 .. %d)", n, TRACK_STREAM_MAX_PUSH);
-  return (int)(((posterior ? (int64_t)n * C * 4 : 0) + (int64_t)n * 4 + (int64_t)n * C + 15) & ~(int64_t)15);      // at most 2^20 * 324
-}
-
-extern "C" int sf_track_stream_push(void* state, int C, int lag, int posterior, int64_t rows_done, const float* logits, int64_t ldl, int n, float lam,
-                                    const float* grid, int final, int32_t* cls_raw, float* conf_raw, int32_t* cls_lag, float* conf_lag, float* post_lag, int64_t ldp,
-                                    int32_t* cls_post_lag, float* conf_post_lag, float* offset_mean_lag, int32_t* cls_tail, float* conf_tail, float* log_z,
-                                    void* workspace, void* stream) {
-  if (!track_stream_shape_ok("sf_track_stream_push", C, lag)) return -1;
-  SF_CHECK_ARG(state, "sf_track_stream_push: null state");
-  SF_CHECK_ARG(n >= 0 && n <= TRACK_STREAM_MAX_PUSH, "sf_track_stream_push: n = %d rows in one push (0 .. %d: split a longer catch-up)", n, TRACK_STREAM_MAX_PUSH);
-  SF_CHECK_ARG(rows_done >= 0 && rows_done <= (INT64_MAX >> 1), "sf_track_stream_push: %lld rows pushed so far", (long long)rows_done);
-  SF_CHECK_ARG(std::isfinite(lam) && lam >= 0.f, "sf_track_stream_push: lam must be finite and >= 0 (the cost of a class change)");
-  SF_CHECK_ARG(n == 0 || ldl >= C, "sf_track_stream_push: row stride ldl = %lld below C = %d", (long long)ldl, C);
-  const int64_t t_old = rows_done, t_new = rows_done + n;
-  const int64_t done_old = t_old > lag ? t_old - lag : 0;                                   // windows committed before this push
-  const int64_t done_new = final ? t_new : (t_new > lag ? t_new - lag : 0);
-  const int64_t n_commit = done_new - done_old, n_tail = t_new - done_new;
-  if (t_new == 0) return 0;
-  SF_CHECK_ARG(n == 0 || (logits && cls_raw && conf_raw && workspace), "sf_track_stream_push: null pointer (new rows)");
-  SF_CHECK_ARG(n_commit == 0 || (cls_lag && conf_lag), "sf_track_stream_push: null pointer (committed block)");
-  SF_CHECK_ARG(n_tail == 0 || (cls_tail && conf_tail), "sf_track_stream_push: null pointer (tail)");
-  if (posterior) {
-    SF_CHECK_ARG(log_z, "sf_track_stream_push: null log_z");
-    SF_CHECK_ARG(n_commit == 0 || (grid && post_lag && cls_post_lag && conf_post_lag && offset_mean_lag && ldp >= C),
-                 "sf_track_stream_push: null pointer or post row stride ldp = %lld below C = %d (posterior block)", (long long)ldp, C);
-  }
-  hipStream_t s = (hipStream_t)stream;
-  const TrackStreamLayout lay(C, lag, posterior != 0);
-  unsigned char* st = static_cast<unsigned char*>(state);
-  unsigned char* ws = static_cast<unsigned char*>(workspace);
-  float* a_new = reinterpret_cast<float*>(ws);
-  int32_t* end_new = reinterpret_cast<int32_t*>(ws + (posterior ? (int64_t)n * C * 4 : 0));
-  uint8_t* bp_new = reinterpret_cast<uint8_t*>(end_new + n);
-  if (n > 0) {
-    hipLaunchKernelGGL(track_rows_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, logits, ldl, n, C, cls_raw, conf_raw);
-    SF_LAUNCH_CHECK();
-  }
-  if (n > 0 || posterior) {                                        // (n == 0 with the posterior: log_z of the prefix so far, from the carried a)
-    hipLaunchKernelGGL(track_stream_scan_kernel, dim3(posterior ? 2 : 1), dim3(64), 0, s, logits, ldl, n, C, lam, t_old, st, lag, posterior, bp_new, a_new, end_new,
-                       log_z);
-    SF_LAUNCH_CHECK();
-  }
-  if (n_commit + n_tail > 0) {
-    TrackStreamRows rows;
-    rows.lg_new = logits;  rows.ldl = ldl;  rows.bp_new = bp_new;  rows.a_new = a_new;  rows.end_new = end_new;
-    rows.lg_ring = reinterpret_cast<const float*>(st + lay.lg_ring);  rows.bp_ring = st + lay.bp_ring;  rows.a_ring = reinterpret_cast<const float*>(st + lay.a_ring);
-    rows.end_last = reinterpret_cast<const int32_t*>(st + 8);
-    rows.t_old = t_old;  rows.lag = lag;  rows.C = C;
-    const dim3 g((unsigned)(n_commit + (n_tail > 0 ? 1 : 0)));
-    if (posterior)
-      hipLaunchKernelGGL(track_stream_readout_kernel<true>, g, dim3(64), 0, s, rows, lam, grid, done_old, (int)n_commit, (int)n_tail, t_new - 1, cls_lag, conf_lag, post_lag,
-                         ldp, cls_post_lag, conf_post_lag, offset_mean_lag, cls_tail, conf_tail);
-    else
-      hipLaunchKernelGGL(track_stream_readout_kernel<false>, g, dim3(64), 0, s, rows, lam, grid, done_old, (int)n_commit, (int)n_tail, t_new - 1, cls_lag, conf_lag, post_lag,
-                         ldp, cls_post_lag, conf_post_lag, offset_mean_lag, cls_tail, conf_tail);
-    SF_LAUNCH_CHECK();
-  }
-  const int keep = n < lag ? n : lag;
-  if (keep > 0) {
-    hipLaunchKernelGGL(track_stream_keep_kernel, dim3((unsigned)keep), dim3(64), 0, s, logits, ldl, (const uint8_t*)bp_new, (const float*)a_new, n - keep, t_old, C, lag,
-                       posterior, st);
-    SF_LAUNCH_CHECK();
-  }
-  return 0;
-}
-
-// ---- the same read-out for many streams in one call (sf_track_pool_push) ---------------------------------------------------------------------------------------
-// n_active streams that share C, lag and posterior, named by a descriptor table of 8 int64 per stream (slot, rows_done, n, row0, final, commit0, tail0, unused): the
-// states lie state_stride bytes apart in one buffer, the new rows of all streams in one logits matrix (stream e: rows [row0, row0 + n)), the committed blocks and
-// the tails back to back in table order.  The same four kinds of launch as one stream's push, each over all streams: blockIdx.y = the table row, blockIdx.x = that
-// stream's own work item (its scan / committed window or tail / ring row); the grid's x extent is the largest count in the table and a block beyond its stream's
-// count exits at once (a stream brings 0 .. n rows and commits 0 .. k windows: the mapping is ragged, an idle block costs one table read).  Every block builds its
-// stream's context from the table's DEVICE copy and runs the single-stream bodies above: one stream's bits do not depend on who shares the push.
-#define TRACK_POOL_MAX_ACTIVE 4096
-#define TRACK_POOL_ROW 8
-
-// One table row and sf_track_stream_push's counts for it (host and device: the launcher sizes the grids from the same arithmetic).
-struct TrackPoolEntry {
-  int64_t slot, t_old, n, row0, final, commit0, tail0;
-  int64_t t_new, done_old, n_commit, n_tail;
-  __host__ __device__ TrackPoolEntry(const int64_t* table, int64_t e, int lag) {
-    const int64_t* r = table + e * TRACK_POOL_ROW;
-    slot = r[0];  t_old = r[1];  n = r[2];  row0 = r[3];  final = r[4];  commit0 = r[5];  tail0 = r[6];
-    t_new = t_old + n;
-    done_old = t_old > lag ? t_old - lag : 0;
-    const int64_t done_new = final ? t_new : (t_new > lag ? t_new - lag : 0);
-    n_commit = done_new - done_old;
-    n_tail = t_new - done_new;
-  }
-  __host__ __device__ int64_t readout_blocks() const { return t_new == 0 ? 0 : n_commit + (n_tail > 0 ? 1 : 0); }
-  __host__ __device__ int64_t keep(int lag) const { return n < lag ? n : lag; }
-};
-
-// the workspace of a pool push: sf_track_stream_push's three arrays over total_rows rows; stream e's part starts at its row0
-struct TrackPoolWorkspace {
-  float* a;  int32_t* end;  uint8_t* bp;
-  __host__ __device__ TrackPoolWorkspace(unsigned char* ws, int C, int total_rows, bool posterior) {
-    a = reinterpret_cast<float*>(ws);
-    end = reinterpret_cast<int32_t*>(ws + (posterior ? (int64_t)total_rows * C * 4 : 0));
-    bp = reinterpret_cast<uint8_t*>(end + total_rows);
-  }
-};
-
-// grid (posterior ? 2 : 1, n_active): block (0, e) the Viterbi scan of stream e, block (1, e) its forward scan
-__global__ __launch_bounds__(64) void track_pool_scan_kernel(const int64_t* __restrict__ table, unsigned char* __restrict__ states, int64_t state_stride,
-                                                              const float* __restrict__ logits, int64_t ldl, int C, float lam, int lag, int posterior,
-                                                              unsigned char* __restrict__ workspace, int total_rows, float* __restrict__ log_z) {
-  __shared__ __attribute__((aligned(16))) float s_u[TRACK_MAX_C];
-  const TrackPoolEntry e(table, blockIdx.y, lag);
-  const bool fwd = blockIdx.x == 1;
-  if (e.t_new == 0 || (e.n == 0 && !fwd)) return;                  // an empty stream; nothing to scan (n == 0 with the posterior: log_z from the carried a)
-  const TrackPoolWorkspace ws(workspace, C, total_rows, posterior != 0);
-  track_stream_scan_body(logits + e.row0 * ldl, ldl, (int)e.n, C, lam, e.t_old, states + e.slot * state_stride, lag, posterior, ws.bp + e.row0 * C, ws.a + e.row0 * C,
-                         ws.end + e.row0, log_z + blockIdx.y, fwd, s_u);
-}
-
-// grid (the largest n_commit + (n_tail > 0) of the table, n_active)
-template <bool POST>
-__global__ __launch_bounds__(64) void track_pool_readout_kernel(const int64_t* __restrict__ table, const unsigned char* __restrict__ states, int64_t state_stride,
-                                                                 const float* __restrict__ logits, int64_t ldl, int C, float lam, int lag,
-                                                                 const float* __restrict__ grid, const unsigned char* __restrict__ workspace, int total_rows,
-                                                                 int32_t* __restrict__ cls_lag, float* __restrict__ conf_lag, float* __restrict__ post_lag, int64_t ldp,
-                                                                 int32_t* __restrict__ cls_post_lag, float* __restrict__ conf_post_lag,
-                                                                 float* __restrict__ offset_mean_lag, int32_t* __restrict__ cls_tail, float* __restrict__ conf_tail) {
-  __shared__ __attribute__((aligned(16))) float s_u[TRACK_MAX_C];
-  __shared__ float s_b[TRACK_MAX_C];
-  __shared__ int s_tail[256];
-  const TrackPoolEntry e(table, blockIdx.y, lag);
-  if ((int64_t)blockIdx.x >= e.readout_blocks()) return;
-  const TrackStreamLayout lay(C, lag, POST);
-  const TrackPoolWorkspace ws(const_cast<unsigned char*>(workspace), C, total_rows, POST);
-  const unsigned char* st = states + e.slot * state_stride;
-  TrackStreamRows rows;
-  rows.lg_new = logits + e.row0 * ldl;  rows.ldl = ldl;  rows.bp_new = ws.bp + e.row0 * C;  rows.a_new = ws.a + e.row0 * C;  rows.end_new = ws.end + e.row0;
-  rows.lg_ring = reinterpret_cast<const float*>(st + lay.lg_ring);  rows.bp_ring = st + lay.bp_ring;  rows.a_ring = reinterpret_cast<const float*>(st + lay.a_ring);
-  rows.end_last = reinterpret_cast<const int32_t*>(st + 8);
-  rows.t_old = e.t_old;  rows.lag = lag;  rows.C = C;
-  track_stream_readout_body<POST>(rows, lam, grid, e.done_old, (int)e.n_commit, (int)e.n_tail, e.t_new - 1, cls_lag + e.commit0, conf_lag + e.commit0,
-                                  post_lag + e.commit0 * ldp, ldp, cls_post_lag + e.commit0, conf_post_lag + e.commit0, offset_mean_lag + e.commit0,
-                                  cls_tail + e.tail0, conf_tail + e.tail0, (int)blockIdx.x, s_u, s_b, s_tail);
-}
-
-// grid (the largest min(n, lag) of the table, n_active)
-__global__ __launch_bounds__(64) void track_pool_keep_kernel(const int64_t* __restrict__ table, unsigned char* __restrict__ states, int64_t state_stride,
-                                                              const float* __restrict__ logits, int64_t ldl, int C, int lag, int posterior,
-                                                              const unsigned char* __restrict__ workspace, int total_rows) {
-  const TrackPoolEntry e(table, blockIdx.y, lag);
-  const int64_t keep = e.keep(lag);
-  if ((int64_t)blockIdx.x >= keep) return;
-  const TrackPoolWorkspace ws(const_cast<unsigned char*>(workspace), C, total_rows, posterior != 0);
-  track_stream_keep_body(logits + e.row0 * ldl, ldl, ws.bp + e.row0 * C, ws.a + e.row0 * C, (int)(e.n - keep), e.t_old, C, lag, posterior,
-                         states + e.slot * state_stride, (int)blockIdx.x);
-}
-
-// What a pool push's table adds up to; track_pool_table_check validates the HOST copy of the table (slots, row ranges, running sums) before anything is launched and
-// fills this in.  Shared by sf_track_pool_push and sf_track_pool_push_gated: the table is the same.
-struct TrackPoolTotals { int64_t sum_n, sum_commit, sum_tail, max_read, max_keep;  bool scan; };
-static int track_pool_table_check(const char* who, const int64_t* table_host, int n_active, int n_slots, int total_rows, int lag, int posterior, TrackPoolTotals& tot) {
-  struct Span { int64_t row0, n; };
-  static thread_local int64_t slots[TRACK_POOL_MAX_ACTIVE];
-  static thread_local Span spans[TRACK_POOL_MAX_ACTIVE];
-  int64_t sum_n = 0, sum_commit = 0, sum_tail = 0, max_read = 0, max_keep = 0;
-  int n_spans = 0;
-  bool scan = false;
-  for (int i = 0; i < n_active; ++i) {
-    const int64_t* r = table_host + (int64_t)i * TRACK_POOL_ROW;
-    SF_CHECK_ARG(r[0] >= 0 && r[0] < n_slots, "%s: table row %d: slot %lld outside the %d slots", who, i, (long long)r[0], n_slots);
-    SF_CHECK_ARG(r[1] >= 0 && r[1] <= (INT64_MAX >> 1), "%s: table row %d: %lld rows pushed so far", who, i, (long long)r[1]);
-    SF_CHECK_ARG(r[2] >= 0 && r[3] >= 0 && r[2] <= total_rows && r[3] <= total_rows - r[2],
-                 "%s: table row %d: rows [%lld, %lld + %lld) outside the %d rows of the push", who, i, (long long)r[3], (long long)r[3], (long long)r[2], total_rows);
-    const TrackPoolEntry e(table_host, i, lag);
-    SF_CHECK_ARG(e.commit0 == sum_commit && e.tail0 == sum_tail,
-                 "%s: table row %d: commit0 = %lld, tail0 = %lld, the counts of the rows before it give %lld, %lld", who, i, (long long)e.commit0,
-                 (long long)e.tail0, (long long)sum_commit, (long long)sum_tail);
-    slots[i] = e.slot;
-    if (e.n > 0) spans[n_spans++] = Span{e.row0, e.n};
-    if (e.t_new > 0) {
-      sum_commit += e.n_commit;
-      sum_tail += e.n_tail;
-      if (e.readout_blocks() > max_read) max_read = e.readout_blocks();
-      if (e.keep(lag) > max_keep) max_keep = e.keep(lag);
-      scan = scan || e.n > 0 || posterior;
-    }
-    sum_n += e.n;
-  }
-  std::sort(slots, slots + n_active);
-  for (int i = 1; i < n_active; ++i) SF_CHECK_ARG(slots[i] != slots[i - 1], "%s: slot %lld named twice in one push", who, (long long)slots[i]);
-  std::sort(spans, spans + n_spans, [](const Span& a, const Span& b) { return a.row0 < b.row0; });
-  for (int i = 1; i < n_spans; ++i)
-    SF_CHECK_ARG(spans[i - 1].row0 + spans[i - 1].n <= spans[i].row0, "%s: the rows [%lld, +%lld) and [%lld, +%lld) of two streams overlap", who,
-                 (long long)spans[i - 1].row0, (long long)spans[i - 1].n, (long long)spans[i].row0, (long long)spans[i].n);
-  tot = TrackPoolTotals{sum_n, sum_commit, sum_tail, max_read, max_keep, scan};
-  return 0;
-}
-
-extern "C" int sf_track_pool_workspace_bytes(int C, int total_rows, int posterior) {
-  SF_CHECK_ARG(C >= 2 && C <= TRACK_MAX_C, "sf_track_pool_workspace_bytes: C = %d classes out of range (2 .. %d)", C, TRACK_MAX_C);
-  SF_CHECK_ARG(total_rows >= 0 && total_rows <= TRACK_STREAM_MAX_PUSH, "sf_track_pool_workspace_bytes: %d rows in one push (0 .. %d)", total_rows, TRACK_STREAM_MAX_PUSH);
-  return sf_track_stream_workspace_bytes(C, total_rows, posterior);
-}
-
-extern "C" int sf_track_pool_push(void* states, int64_t state_stride, int n_slots, int C, int lag, int posterior, const int64_t* table_host, const int64_t* table_dev,
-                                  int n_active, const float* logits, int64_t ldl, int total_rows, float lam, const float* grid, int32_t* cls_raw, float* conf_raw,
-                                  int32_t* cls_lag, float* conf_lag, float* post_lag, int64_t ldp, int32_t* cls_post_lag, float* conf_post_lag,
-                                  float* offset_mean_lag, int32_t* cls_tail, float* conf_tail, float* log_z, void* workspace, void* stream) {
-  if (!track_stream_shape_ok("sf_track_pool_push", C, lag)) return -1;
-  SF_CHECK_ARG(std::isfinite(lam) && lam >= 0.f, "sf_track_pool_push: lam must be finite and >= 0 (the cost of a class change)");
-  SF_CHECK_ARG(n_active >= 1 && n_active <= TRACK_POOL_MAX_ACTIVE, "sf_track_pool_push: n_active = %d streams in one push (1 .. %d)", n_active, TRACK_POOL_MAX_ACTIVE);
-  SF_CHECK_ARG(n_slots >= 1, "sf_track_pool_push: n_slots = %d", n_slots);
-  SF_CHECK_ARG(states && table_host && table_dev, "sf_track_pool_push: null pointer (states or table)");
-  const TrackStreamLayout lay(C, lag, posterior != 0);
-  SF_CHECK_ARG(state_stride >= lay.total && state_stride % 16 == 0, "sf_track_pool_push: state stride %lld: a multiple of 16, at least %lld bytes", (long long)state_stride,
-               (long long)lay.total);
-  SF_CHECK_ARG(total_rows >= 0 && total_rows <= TRACK_STREAM_MAX_PUSH, "sf_track_pool_push: total_rows = %d rows in one push (0 .. %d)", total_rows, TRACK_STREAM_MAX_PUSH);
-  TrackPoolTotals tot;
-  if (track_pool_table_check("sf_track_pool_push", table_host, n_active, n_slots, total_rows, lag, posterior, tot)) return -1;
-  const int64_t sum_n = tot.sum_n, sum_commit = tot.sum_commit, sum_tail = tot.sum_tail, max_read = tot.max_read, max_keep = tot.max_keep;
-  const bool scan = tot.scan;
-  SF_CHECK_ARG(sum_n == 0 || ldl >= C, "sf_track_pool_push: row stride ldl = %lld below C = %d", (long long)ldl, C);
-  SF_CHECK_ARG(sum_n == 0 || (logits && cls_raw && conf_raw && workspace), "sf_track_pool_push: null pointer (new rows)");
-  SF_CHECK_ARG(sum_commit == 0 || (cls_lag && conf_lag), "sf_track_pool_push: null pointer (committed block)");
-  SF_CHECK_ARG(sum_tail == 0 || (cls_tail && conf_tail), "sf_track_pool_push: null pointer (tail)");
-  if (posterior) {
-    SF_CHECK_ARG(!scan || log_z, "sf_track_pool_push: null log_z");
-    SF_CHECK_ARG(sum_commit == 0 || (grid && post_lag && cls_post_lag && conf_post_lag && offset_mean_lag && ldp >= C),
-                 "sf_track_pool_push: null pointer or post row stride ldp = %lld below C = %d (posterior block)", (long long)ldp, C);
-  }
-  hipStream_t s = (hipStream_t)stream;
-  unsigned char* st = static_cast<unsigned char*>(states);
-  unsigned char* ws = static_cast<unsigned char*>(workspace);
-  if (sum_n > 0) {                                                 // one thread per row of the packed matrix (rows between two streams' ranges: their own argmax, unread)
-    hipLaunchKernelGGL(track_rows_kernel<false>, dim3((unsigned)((total_rows + 255) / 256)), dim3(256), 0, s, logits, ldl, total_rows, C, cls_raw, conf_raw);
-    SF_LAUNCH_CHECK();
-  }
-  if (scan) {
-    hipLaunchKernelGGL(track_pool_scan_kernel, dim3(posterior ? 2 : 1, (unsigned)n_active), dim3(64), 0, s, table_dev, st, state_stride, logits, ldl, C, lam, lag, posterior,
-                       ws, total_rows, log_z);
-    SF_LAUNCH_CHECK();
-  }
-  if (max_read > 0) {
-    const dim3 g((unsigned)max_read, (unsigned)n_active);
-    if (posterior)
-      hipLaunchKernelGGL(track_pool_readout_kernel<true>, g, dim3(64), 0, s, table_dev, (const unsigned char*)st, state_stride, logits, ldl, C, lam, lag, grid,
-                         (const unsigned char*)ws, total_rows, cls_lag, conf_lag, post_lag, ldp, cls_post_lag, conf_post_lag, offset_mean_lag, cls_tail, conf_tail);
-    else
-      hipLaunchKernelGGL(track_pool_readout_kernel<false>, g, dim3(64), 0, s, table_dev, (const unsigned char*)st, state_stride, logits, ldl, C, lam, lag, grid,
-                         (const unsigned char*)ws, total_rows, cls_lag, conf_lag, post_lag, ldp, cls_post_lag, conf_post_lag, offset_mean_lag, cls_tail, conf_tail);
-    SF_LAUNCH_CHECK();
-  }
-  if (max_keep > 0) {
-    hipLaunchKernelGGL(track_pool_keep_kernel, dim3((unsigned)max_keep, (unsigned)n_active), dim3(64), 0, s, table_dev, st, state_stride, logits, ldl, C, lag, posterior,
-                       (const unsigned char*)ws, total_rows);
-    SF_LAUNCH_CHECK();
-  }
-  return 0;
 }
 
 // ---- the read-outs gated by synchronizability (sf_track_decode_gated, sf_track_posterior_gated) ----------------------------------------------------
@@ -1092,160 +573,36 @@ extern "C" int sf_track_posterior_gated(const float* logits, int64_t ldl, const 
   return 0;
 }
 
-// ---- the gated read-outs of a stream at a fixed lag (sf_track_stream_push_gated, sf_track_pool_push_gated) -----------------------------------------
-// sf_track_stream_push's definition with the gated offline read-outs in place of the ungated ones: window w is committed by the push that delivers row w + lag as
-// path_{w+lag}[w] / post_{w+lag}[w] of sf_track_decode_gated / sf_track_posterior_gated on the prefix 0 .. w + lag.  The carried state is 2C wide: the scan vectors
-// over the states j = m * C + c, rings of back pointers (2C bytes a row) and of a (2C floats a row), and rings of BOTH inputs - the offset logits (C) and the gate
-// logits (2) - from which the emission is recomputed exactly as the offline scans compute it (no emission ring).  The same four kinds of launch, the per-step
-// arithmetic that of the offline kernels (track_gated_viterbi_step, track_gated_fb_step, track_gated_emission, track_gated_combine_row).
-struct TrackGatedStreamRows {
-  const float* lg_new;  int64_t ldl;      // the push's offset logits
-  const float* gz_new;  int64_t ldg;      // the push's gate logits
-  const uint8_t* bp_new;                  // workspace: back pointers (n, 2C)
-  const float* a_new;                     // workspace: normalised a (n, 2C); posterior only
-  const int32_t* end_new;                 // workspace: the end state per new row
-  const float* lg_ring;  const float* gz_ring;  const uint8_t* bp_ring;  const float* a_ring;      // state: (lag, C), (lag, 2), (lag, 2C), (lag, 2C)
-  const int32_t* end_last;                // state: the end state of the last row pushed
-  int64_t t_old;                          // rows before this push
-  int lag, C;
-  __device__ __forceinline__ const float* logits(int64_t r) const { return r >= t_old ? lg_new + (r - t_old) * ldl : lg_ring + (r % lag) * C; }
-  __device__ __forceinline__ const float* gate(int64_t r) const { return r >= t_old ? gz_new + (r - t_old) * ldg : gz_ring + (r % lag) * 2; }
-  __device__ __forceinline__ const uint8_t* backptr(int64_t r) const { return r >= t_old ? bp_new + (r - t_old) * 2 * C : bp_ring + (r % lag) * 2 * C; }
-  __device__ __forceinline__ const float* a(int64_t r) const { return r >= t_old ? a_new + (r - t_old) * 2 * C : a_ring + (r % lag) * 2 * C; }
-  __device__ __forceinline__ int end(int64_t r) const { return r >= t_old ? end_new[r - t_old] : end_last[0]; }
-  __device__ __forceinline__ int width() const { return 2 * C; }
-};
+// ---- fixed-lag read-out of live feeds (sf_track_stream_push, sf_track_pool_push and their _gated forms) --------------------------------
+// Rows arrive in pushes; window w is committed by the push that delivers row w + lag, as path_{w+lag}[w] / post_{w+lag}[w] (the offline read-outs of the prefix
+// 0 .. w + lag: sf_track_decode / sf_track_posterior, or their gated forms), and never revised.  Both scans are causal, so what a push needs of the past is the scan
+// vectors after the last row (s; with the posterior a and the double of subtracted maxima) and, of the last `lag` rows, the back pointers, the inputs (conf_lag, and
+// the backward recursion's emission, which is recomputed from them as the offline scan does: no emission ring) and - posterior - the normalised a.  The state buffer
+// holds exactly that, the per-row parts as rings (row r in slot r % lag); its size does not depend on how many rows have passed.  A push of n rows is three or four
+// launches on the caller's stream:
+//   1. the chain's rows kernel:      cls_raw / conf_raw (/ sync_raw) of the new rows (the offline kernel);
+//   2. track_stream_scan_kernel:     one wavefront per scan, side by side (block 0 Viterbi, block 1 forward): loads the carried vector, runs the n rows with the next
+//                                    row's loads under the current step, writes back pointers / a and every row's end state (argmax s_r) into the push's workspace,
+//                                    stores the carried vectors;
+//   3. track_stream_readout_kernel:  one wavefront per window that becomes committed: its own backtrace from the end state of row w + lag (eight rows of back
+//                                    pointers per round, wave-uniform shuffles), with the posterior its own backward recursion over rows w + lag .. w + 1 and the
+//                                    combine of row w; one more wavefront backtraces the tail from the last row.  The windows are independent: a catch-up push of
+//                                    1000 rows spreads over the chip instead of running n * lag dependent steps in one wavefront;
+//   4. track_stream_keep_kernel:     copies the last min(lag, n) new rows into the rings (after 3, which still reads the slots they replace).
+// All of it is templated on a CHAIN.  A chain says how many states a row has, what a lane of the scanning wavefront is (the chain object itself, built per thread),
+// what the inputs of a row are and how they are loaded (Src: pointers and strides positioned at a row; In: one row's values in a lane), the first row of the Viterbi
+// scan, the emission, the two steps, where a lane's entry lies in LDS, how one row is combined, what the keep step copies of the inputs, how a path state is written
+// out and which rows kernel runs first.  The arithmetic is that of the offline kernels' step functions: a chain calls them, it does not restate them.  A new chain
+// (say, a third state dimension) is a new policy struct; nothing below it changes.
 
-// the gated state buffer:
-//   [double shifted][int32 end_last, pad][s: 64 floats][posterior: a: 64 floats][offset logits ring (lag, C) fp32][gate logits ring (lag, 2) fp32]
-//   [posterior: a ring (lag, 2C) fp32][back pointer ring (lag, 2C) bytes], rounded up to 16 bytes.  Row r of the stream lies in slot r % lag of every ring.
-struct TrackGatedStreamLayout {
-  int64_t s, a, lg_ring, gz_ring, a_ring, bp_ring, total;
-  __host__ __device__ TrackGatedStreamLayout(int C, int lag, bool posterior) {
-    s = 16;
-    a = s + 64 * 4;
-    lg_ring = a + (posterior ? 64 * 4 : 0);
-    gz_ring = lg_ring + (int64_t)lag * C * 4;
-    a_ring = gz_ring + (int64_t)lag * 2 * 4;
-    bp_ring = a_ring + (posterior ? (int64_t)lag * 2 * C * 4 : 0);
-    total = (bp_ring + (int64_t)lag * 2 * C + 15) & ~(int64_t)15;
-  }
-};
-
-// One stream's view of its rows: the rings of its state and its part of the push (host and device: the single-stream launcher and the pool's kernels build it).
-__host__ __device__ __forceinline__ void track_gated_rows_fill(TrackGatedStreamRows& rows, const TrackGatedStreamLayout& lay, const unsigned char* st, const float* logits,
-                                                               int64_t ldl, const float* gate, int64_t ldg, const uint8_t* bp, const float* a, const int32_t* end,
-                                                               int64_t t_old, int lag, int C) {
-  rows.lg_new = logits;  rows.ldl = ldl;  rows.gz_new = gate;  rows.ldg = ldg;  rows.bp_new = bp;  rows.a_new = a;  rows.end_new = end;
-  rows.lg_ring = reinterpret_cast<const float*>(st + lay.lg_ring);  rows.gz_ring = reinterpret_cast<const float*>(st + lay.gz_ring);
-  rows.bp_ring = st + lay.bp_ring;  rows.a_ring = reinterpret_cast<const float*>(st + lay.a_ring);
-  rows.end_last = reinterpret_cast<const int32_t*>(st + 8);
-  rows.t_old = t_old;  rows.lag = lag;  rows.C = C;
-}
-
-// The scan of one stream's push, by one wavefront: fwd = false the Viterbi scan, fwd = true the forward scan (wave-uniform).  s_u: 64 floats of LDS, 16-byte aligned:
-// the Viterbi scores state-major, the forward vector as two planes of 32 (entries >= C hold -inf), as the offline kernels keep them.
-__device__ __forceinline__ void track_gated_stream_scan_body(const float* __restrict__ logits, int64_t ldl, const float* __restrict__ gate, int64_t ldg, int n, int C,
-                                                             float lam, float mu, int64_t t_old, unsigned char* __restrict__ state, int lag, int posterior,
-                                                             uint8_t* __restrict__ bp_new, float* __restrict__ a_new, int32_t* __restrict__ end_new,
-                                                             float* __restrict__ log_z, bool fwd, float* s_u) {
-  const TrackGatedStreamLayout lay(C, lag, posterior != 0);
-  const TrackGatedLane ln(C);
-  const int S = 2 * C;
-  const int C4 = (C + 3) & ~3;
-  const float ninf = -INFINITY;
-  const float log_c = logf((float)C);
-  const bool loads = ln.live && ln.m;                              // the lanes of plane 1 carry the offset logits
-  const int slot = fwd ? ln.m * 32 + ln.c : ln.j;
-  float* carried = reinterpret_cast<float*>(state + (fwd ? lay.a : lay.s));
-  double* st_shifted = reinterpret_cast<double*>(state);
-  int32_t* st_end = reinterpret_cast<int32_t*>(state + 8);
-  double shifted = (fwd && t_old > 0) ? st_shifted[0] : 0.0;
-  float v = (t_old > 0 && ln.live) ? carried[ln.j] : ninf;
-  int k = 0;
-  float l_next = (loads && n > 0) ? logits[ln.c] : ninf;
-  float z0_next = n > 0 ? gate[0] : 0.f, z1_next = n > 0 ? gate[1] : 0.f;
-  s_u[threadIdx.x] = ninf;
-  __syncthreads();
-  if (t_old == 0 && n > 0) {                                       // the first row of the stream: S_0 = E[0] / a_0 = E[0], as the offline scans begin
-    const float l = l_next, z0 = z0_next, z1 = z1_next;
-    if (n > 1) {
-      l_next = loads ? logits[ldl + ln.c] : ninf;
-      z0_next = gate[ldg];
-      z1_next = gate[ldg + 1];
-    }
-    const float e = track_gated_emission(ln, l, z0, z1, log_c);
-    if (fwd) {
-      v = e;
-      const float m = fb_finite_or_zero(wave_max(v));
-      v -= m;
-      shifted += (double)m;
-      if (ln.live) a_new[ln.j] = v;
-    } else {
-      v = e;
-      v -= wave_max(v);
-      if (ln.live) bp_new[ln.j] = 0;                               // never followed: the backtrace stops at row 1
-      const int end = track_wave_end_state(v, ln.live);            // (the ballot needs the whole wavefront)
-      if (ln.j == 0) end_new[0] = end;
-    }
-    k = 1;
-  }
-  if (ln.live) s_u[slot] = v;
-  __syncthreads();
-  for (; k < n; ++k) {
-    const float l = l_next, z0 = z0_next, z1 = z1_next;
-    if (k + 1 < n) {                                               // the next row's loads travel under this step
-      l_next = loads ? logits[(int64_t)(k + 1) * ldl + ln.c] : ninf;
-      z0_next = gate[(int64_t)(k + 1) * ldg];
-      z1_next = gate[(int64_t)(k + 1) * ldg + 1];
-    }
-    const float e = track_gated_emission(ln, l, z0, z1, log_c);
-    if (fwd) {
-      float m;
-      v = track_gated_fb_step(ln, s_u, C4, false, lam, mu, e, m);
-      shifted += (double)m;
-      if (ln.live) a_new[(int64_t)k * S + ln.j] = v;
-    } else {
-      int bp;
-      v = track_gated_viterbi_step(ln, s_u, C, lam, mu, e, bp);
-      if (ln.live) bp_new[(int64_t)k * S + ln.j] = (uint8_t)bp;
-      const int end = track_wave_end_state(v, ln.live);
-      if (ln.j == 0) end_new[k] = end;
-    }
-    __syncthreads();                                               // every lane has read s_u
-    if (ln.live) s_u[slot] = v;
-    __syncthreads();
-  }
-  if (n > 0) {
-    const int end = track_wave_end_state(v, ln.live);
-    if (ln.live) carried[ln.j] = v;
-    if (ln.j == 0) {
-      if (fwd) st_shifted[0] = shifted;
-      else st_end[0] = end;
-    }
-  }
-  if (fwd) {
-    const float z = logf(wave_sum(expf(v)));                       // the normalised a of the last row: maximum 0
-    if (ln.j == 0) log_z[0] = (float)(shifted + (double)z);
-  }
-}
-
-__global__ __launch_bounds__(64) void track_gated_stream_scan_kernel(const float* __restrict__ logits, int64_t ldl, const float* __restrict__ gate, int64_t ldg, int n,
-                                                                      int C, float lam, float mu, int64_t t_old, unsigned char* __restrict__ state, int lag,
-                                                                      int posterior, uint8_t* __restrict__ bp_new, float* __restrict__ a_new,
-                                                                      int32_t* __restrict__ end_new, float* __restrict__ log_z) {
-  __shared__ __attribute__((aligned(16))) float s_u[64];
-  track_gated_stream_scan_body(logits, ldl, gate, ldg, n, C, lam, mu, t_old, state, lag, posterior, bp_new, a_new, end_new, log_z, blockIdx.x == 1, s_u);
-}
-
-// Every pointer of the committed block and the tail of one stream's read-out.
-struct TrackGatedStreamOut {
+// Every pointer of the committed block and the tail of one stream's read-out.  The plain chain leaves the sync pointers null and never touches them.
+struct TrackStreamOut {
   int32_t* cls_lag;  int32_t* sync_lag;  float* conf_lag;
   float* post_lag;  int64_t ldp;  float* p_sync_lag;  int32_t* cls_post_lag;  float* conf_post_lag;  float* offset_mean_lag;
   int32_t* cls_tail;  int32_t* sync_tail;  float* conf_tail;
   // the same block `commit0` committed windows / `tail0` tail entries further on (a pool's packed outputs)
-  __host__ __device__ TrackGatedStreamOut at(int64_t commit0, int64_t tail0) const {
-    TrackGatedStreamOut o = *this;
+  __host__ __device__ TrackStreamOut at(int64_t commit0, int64_t tail0) const {
+    TrackStreamOut o = *this;
     o.cls_lag += commit0;  o.sync_lag += commit0;  o.conf_lag += commit0;
     o.post_lag += commit0 * ldp;  o.p_sync_lag += commit0;  o.cls_post_lag += commit0;  o.conf_post_lag += commit0;  o.offset_mean_lag += commit0;
     o.cls_tail += tail0;  o.sync_tail += tail0;  o.conf_tail += tail0;
@@ -1253,29 +610,348 @@ struct TrackGatedStreamOut {
   }
 };
 
-// Block i < n_commit: window w = w0 + i, read from the prefix that ends at row R = min(w + lag, t_last); block n_commit (if n_tail > 0): the tail.  The backtrace is
-// track_stream_backtrace over rows of 2C back pointers (every index read clamped below 2C); the state j it arrives at is written as cls = j % C, sync = j / C.
-// s_u (16-byte aligned) / s_b: 64 floats of LDS each, s_tail: 256 ints.
-template <bool POST>
-__device__ __forceinline__ void track_gated_stream_readout_body(const TrackGatedStreamRows& rows, float lam, float mu, const float* __restrict__ grid, int64_t w0,
-                                                                int n_commit, int n_tail, int64_t t_last, const TrackGatedStreamOut& out, int bx, float* s_u, float* s_b,
-                                                                int* s_tail) {
-  const int C = rows.C, S = 2 * C;
-  const TrackGatedLane ln(C);
+// The chain over the C offset classes (sf_track_decode / sf_track_posterior): lane j = class j, one logit per row and lane, the scan vectors contiguous in LDS (the
+// idle lanes store their -inf, which is what fb_transition_lse reads behind class C - 1).
+struct TrackChainPlain {
+  static constexpr int MAX_C = TRACK_MAX_C;
+  static constexpr int GATE_WIDTH = 0;                             // floats of a row's second input: none
+  static constexpr bool LDS_PREFILL = false;
+  static constexpr bool VITERBI_TAKES_EMISSION = false;            // track_viterbi_step takes the logit: its e = l - max is its own
+  __host__ __device__ static int states(int C) { return C; }
+  struct Src {
+    const float* lg;  int64_t ldl;
+    __host__ __device__ Src at(int64_t r) const { return Src{lg + r * ldl, ldl}; }
+    bool ok() const { return lg != nullptr; }
+    bool strides_ok(const char* who, int C) const {
+      if (ldl < C) { sf_set_error("%s: row stride ldl = %lld below C = %d", who, (long long)ldl, C); return false; }
+      return true;
+    }
+  };
+  struct In { float l; };
+  static bool sync_ok(const void*) { return true; }                // the chain has no sync outputs: nothing to refuse
+  static void launch_rows(const Src& src, int n, int C, int32_t* cls_raw, float* conf_raw, float*, hipStream_t s) {
+    hipLaunchKernelGGL(track_rows_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src.lg, src.ldl, n, C, cls_raw, conf_raw);
+  }
+
+  int j;
+  bool live;
+  __device__ __forceinline__ TrackChainPlain(int C) : j(threadIdx.x), live(j < C) {}
+  __device__ __forceinline__ In load(const Src& row, bool have) const { return In{(live && have) ? row.lg[j] : -INFINITY}; }
+  template <class Rows>
+  __device__ __forceinline__ In load_row(const Rows& rows, int64_t r) const { return In{live ? rows.logits(r)[j] : -INFINITY}; }
+  __device__ __forceinline__ float first_viterbi(const In& in, float) const { return in.l - wave_max(in.l); }      // s_0 = e[0]; -inf in the idle lanes
+  __device__ __forceinline__ float emission(const In& in) const { return fb_log_softmax(in.l); }
+  __device__ __forceinline__ float viterbi_step(const float* s_u, int C, float lam, float, const In& in, float, int& bp) const {
+    return track_viterbi_step(s_u, C, j, live, lam, in.l, bp);
+  }
+  __device__ __forceinline__ float fb_step(const float* s_u, int C4, bool back, float lam, float, float e, float& m) const {
+    return fb_scan_step(s_u, C4, j, live, back, lam, e, m);
+  }
+  __device__ __forceinline__ void put(float* s_u, bool, float v) const { s_u[j] = v; }
+  __device__ __forceinline__ static int put_state(int state, int, int32_t* cls, int32_t*, int64_t i) { cls[i] = state;  return state; }
+  __device__ __forceinline__ static void combine(const float* a, const float* b, int C, const float* __restrict__ grid, const TrackStreamOut& out, int i) {
+    int best;
+    float pbest, mean;
+    fb_combine_row(a, b, C, grid, out.post_lag + (int64_t)i * out.ldp, best, pbest, mean);
+    out.cls_post_lag[i] = best;
+    out.conf_post_lag[i] = pbest;
+    out.offset_mean_lag[i] = mean;
+  }
+  __device__ __forceinline__ static void keep_inputs(const Src& row, float* lg_slot, float*, int c, int) { lg_slot[c] = row.lg[c]; }
+};
+
+// The chain over the 2C states j = m * C + c (sf_track_decode_gated / sf_track_posterior_gated): a lane is a TrackGatedLane, a row brings the offset logit (in the
+// lanes of plane 1) and the two gate logits (wave-uniform), the Viterbi scores lie state-major in LDS and the forward vector as two planes of 32 over a -inf fill.
+struct TrackChainGated : TrackGatedLane {
+  static constexpr int MAX_C = TRACK_GATE_MAX_C;
+  static constexpr int GATE_WIDTH = 2;
+  static constexpr bool LDS_PREFILL = true;
+  static constexpr bool VITERBI_TAKES_EMISSION = true;             // both scans of a row start from one emission
+  __host__ __device__ static int states(int C) { return 2 * C; }
+  struct Src {
+    const float* lg;  int64_t ldl;  const float* gz;  int64_t ldg;
+    __host__ __device__ Src at(int64_t r) const { return Src{lg + r * ldl, ldl, gz + r * ldg, ldg}; }
+    bool ok() const { return lg != nullptr && gz != nullptr; }
+    bool strides_ok(const char* who, int C) const {
+      if (ldl < C) { sf_set_error("%s: row stride ldl = %lld below C = %d", who, (long long)ldl, C); return false; }
+      if (ldg < 2) { sf_set_error("%s: gate row stride ldg = %lld below 2", who, (long long)ldg); return false; }
+      return true;
+    }
+  };
+  struct In { float l, z0, z1; };
+  static bool sync_ok(const void* p) { return p != nullptr; }
+  static void launch_rows(const Src& src, int n, int C, int32_t* cls_raw, float* conf_raw, float* sync_raw, hipStream_t s) {
+    hipLaunchKernelGGL(track_gated_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src.lg, src.ldl, src.gz, src.ldg, n, C, cls_raw, conf_raw, sync_raw);
+  }
+
+  float log_c;
+  bool loads;                                                      // the lanes of plane 1 carry the offset logits
+  __device__ __forceinline__ TrackChainGated(int C) : TrackGatedLane(C), log_c(logf((float)C)), loads(live && m) {}
+  __device__ __forceinline__ In load(const Src& row, bool have) const {
+    return In{(loads && have) ? row.lg[c] : -INFINITY, have ? row.gz[0] : 0.f, have ? row.gz[1] : 0.f};
+  }
+  template <class Rows>
+  __device__ __forceinline__ In load_row(const Rows& rows, int64_t r) const {
+    const float* gz = rows.gate(r);
+    return In{loads ? rows.logits(r)[c] : -INFINITY, gz[0], gz[1]};
+  }
+  __device__ __forceinline__ float emission(const In& in) const { return track_gated_emission(*this, in.l, in.z0, in.z1, log_c); }
+  __device__ __forceinline__ float first_viterbi(const In&, float e) const { return e - wave_max(e); }      // S_0 = E[0]
+  __device__ __forceinline__ float viterbi_step(const float* s_u, int C, float lam, float mu, const In&, float e, int& bp) const {
+    return track_gated_viterbi_step(*this, s_u, C, lam, mu, e, bp);
+  }
+  __device__ __forceinline__ float fb_step(const float* s_u, int C4, bool back, float lam, float mu, float e, float& mx) const {
+    return track_gated_fb_step(*this, s_u, C4, back, lam, mu, e, mx);
+  }
+  __device__ __forceinline__ void put(float* s_u, bool fwd, float v) const {
+    if (live) s_u[fwd ? m * 32 + c : j] = v;
+  }
+  __device__ __forceinline__ static int put_state(int state, int C, int32_t* cls, int32_t* sync, int64_t i) {
+    cls[i] = state % C;
+    sync[i] = state / C;
+    return state % C;
+  }
+  __device__ __forceinline__ static void combine(const float* a, const float* b, int C, const float* __restrict__ grid, const TrackStreamOut& out, int i) {
+    int best;
+    float pbest, mean, ps;
+    track_gated_combine_row(a, b, C, grid, out.post_lag + (int64_t)i * out.ldp, best, pbest, mean, ps);
+    out.p_sync_lag[i] = ps;
+    out.cls_post_lag[i] = best;
+    out.conf_post_lag[i] = pbest;
+    out.offset_mean_lag[i] = mean;
+  }
+  __device__ __forceinline__ static void keep_inputs(const Src& row, float* lg_slot, float* gz_slot, int c, int C) {
+    if (c < C) lg_slot[c] = row.lg[c];
+    if (c < 2) gz_slot[c] = row.gz[c];
+  }
+};
+
+// the state buffer: [double shifted][int32 end_last, pad][s: 64 floats][posterior: a: 64 floats][offset logits ring (lag, C) fp32][gated: gate logits ring (lag, 2) fp32]
+//   [posterior: a ring (lag, S) fp32][back pointer ring (lag, S) bytes], rounded up to 16 bytes; S = the chain's states.  Row r of the stream lies in slot r % lag of
+//   every ring.
+template <class Chain>
+struct TrackStreamLayout {
+  int64_t s, a, lg_ring, gz_ring, a_ring, bp_ring, total;
+  __host__ __device__ TrackStreamLayout(int C, int lag, bool posterior) {
+    const int64_t S = Chain::states(C);
+    s = 16;
+    a = s + TRACK_MAX_C * 4;
+    lg_ring = a + (posterior ? TRACK_MAX_C * 4 : 0);
+    gz_ring = lg_ring + (int64_t)lag * C * 4;
+    a_ring = gz_ring + (int64_t)lag * Chain::GATE_WIDTH * 4;
+    bp_ring = a_ring + (posterior ? (int64_t)lag * S * 4 : 0);
+    total = (bp_ring + (int64_t)lag * S + 15) & ~(int64_t)15;
+  }
+};
+using TrackGatedStreamLayout = TrackStreamLayout<TrackChainGated>;      // (the name the header's description of the gated state uses)
+
+// Follows the back pointers of rows R .. w + 1 from class `cur` (the class at row R) -> the class at row w.  Lane c loads backptr[r, c] of eight rows at a time, the
+// chain itself is eight wave-uniform shuffles.  KEEP: tail[r - w] = the class at row r, for every r in [w, R] (LDS, written by lane 0).
+template <bool KEEP, class Rows>
+__device__ __forceinline__ int track_stream_backtrace(const Rows& rows, int64_t R, int64_t w, int cur, int c, bool live, int* tail) {
+  const int C = rows.width();                                      // entries of one row of back pointers (the gated chain: 2C states)
+  for (int64_t r0 = R; r0 > w; r0 -= 8) {
+    int b[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) b[j] = (live && r0 - j > w) ? (int)rows.backptr(r0 - j)[c] : 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (r0 - j > w) {                                            // wave-uniform
+        if (KEEP && c == 0) tail[r0 - j - w] = cur;
+        const int p = __shfl(b[j], cur, 64);
+        cur = p < C ? p : C - 1;
+      }
+    }
+  }
+  if (KEEP && c == 0) tail[0] = cur;
+  return cur;
+}
+
+#define TRACK_POOL_MAX_ACTIVE 4096
+#define TRACK_POOL_ROW 8
+
+// One table row and sf_track_stream_push's counts for it (host and device: the launcher sizes the grids from the same arithmetic).
+struct TrackPoolEntry {
+  int64_t slot, t_old, n, row0, final, commit0, tail0;
+  int64_t t_new, done_old, n_commit, n_tail;
+  __host__ __device__ TrackPoolEntry(const int64_t* table, int64_t e, int lag) {
+    const int64_t* r = table + e * TRACK_POOL_ROW;
+    slot = r[0];  t_old = r[1];  n = r[2];  row0 = r[3];  final = r[4];  commit0 = r[5];  tail0 = r[6];
+    t_new = t_old + n;
+    done_old = t_old > lag ? t_old - lag : 0;
+    const int64_t done_new = final ? t_new : (t_new > lag ? t_new - lag : 0);
+    n_commit = done_new - done_old;
+    n_tail = t_new - done_new;
+  }
+  __host__ __device__ int64_t readout_blocks() const { return t_new == 0 ? 0 : n_commit + (n_tail > 0 ? 1 : 0); }
+  __host__ __device__ int64_t keep(int lag) const { return n < lag ? n : lag; }
+};
+
+// the workspace of a push of total_rows rows of S states: [posterior: a (total_rows, S) fp32][end (total_rows) int32][back pointers (total_rows, S) bytes]; in a pool
+// push stream e's part starts at its row0
+struct TrackPoolWorkspace {
+  float* a;  int32_t* end;  uint8_t* bp;
+  __host__ __device__ TrackPoolWorkspace(unsigned char* ws, int S, int total_rows, bool posterior) {
+    a = reinterpret_cast<float*>(ws);
+    end = reinterpret_cast<int32_t*>(ws + (posterior ? (int64_t)total_rows * S * 4 : 0));
+    bp = reinterpret_cast<uint8_t*>(end + total_rows);
+  }
+  __host__ __device__ TrackPoolWorkspace at(int64_t row0, int S) const {
+    TrackPoolWorkspace w = *this;
+    w.a += row0 * S;  w.end += row0;  w.bp += row0 * S;
+    return w;
+  }
+};
+static int64_t track_workspace_bytes(int S, int n, int posterior) {
+  return ((posterior ? (int64_t)n * S * 4 : 0) + (int64_t)n * 4 + (int64_t)n * S + 15) & ~(int64_t)15;      // at most 2^20 * 324
+}
+
+// Rows before the push live in the rings of the state, rows of the push in the caller's inputs and the workspace: TrackStreamRows resolves a row index to either.
+template <class Chain>
+struct TrackStreamRows {
+  typename Chain::Src src;                // the push's inputs
+  const uint8_t* bp_new;                  // workspace: back pointers (n, S)
+  const float* a_new;                     // workspace: normalised a (n, S); posterior only
+  const int32_t* end_new;                 // workspace: the end state (argmax s_r) per new row
+  const float* lg_ring;  const float* gz_ring;       // state: the rings of the inputs, (lag, C) and - gated - (lag, 2)
+  const uint8_t* bp_ring;  const float* a_ring;      // state: (lag, S) each
+  const int32_t* end_last;                // state: the end state of the last row pushed
+  int64_t t_old;                          // rows before this push
+  int lag, C;
+  __device__ __forceinline__ int width() const { return Chain::states(C); }
+  __device__ __forceinline__ const float* logits(int64_t r) const { return r >= t_old ? src.lg + (r - t_old) * src.ldl : lg_ring + (r % lag) * C; }
+  __device__ __forceinline__ const float* gate(int64_t r) const { return r >= t_old ? src.gz + (r - t_old) * src.ldg : gz_ring + (r % lag) * 2; }      // (gated only)
+  __device__ __forceinline__ const uint8_t* backptr(int64_t r) const { return r >= t_old ? bp_new + (r - t_old) * width() : bp_ring + (r % lag) * width(); }
+  __device__ __forceinline__ const float* a(int64_t r) const { return r >= t_old ? a_new + (r - t_old) * width() : a_ring + (r % lag) * width(); }
+  __device__ __forceinline__ int end(int64_t r) const { return r >= t_old ? end_new[r - t_old] : end_last[0]; }
+};
+
+// One stream's view of its rows: the rings of its state and its part of the push (host and device: the single-stream launcher and the pool's kernels build it).
+template <class Chain>
+__host__ __device__ __forceinline__ TrackStreamRows<Chain> track_stream_rows(const unsigned char* st, const typename Chain::Src& src, const TrackPoolWorkspace& ws,
+                                                                             int64_t t_old, int lag, int C, bool posterior) {
+  const TrackStreamLayout<Chain> lay(C, lag, posterior);
+  TrackStreamRows<Chain> rows;
+  rows.src = src;  rows.bp_new = ws.bp;  rows.a_new = ws.a;  rows.end_new = ws.end;
+  rows.lg_ring = reinterpret_cast<const float*>(st + lay.lg_ring);  rows.gz_ring = reinterpret_cast<const float*>(st + lay.gz_ring);
+  rows.bp_ring = st + lay.bp_ring;  rows.a_ring = reinterpret_cast<const float*>(st + lay.a_ring);
+  rows.end_last = reinterpret_cast<const int32_t*>(st + 8);
+  rows.t_old = t_old;  rows.lag = lag;  rows.C = C;
+  return rows;
+}
+
+// The scan of one stream's push, by one wavefront: fwd = false the Viterbi scan, fwd = true the forward scan (wave-uniform).  s_u: TRACK_MAX_C floats of LDS, 16-byte
+// aligned, laid out as the chain's offline kernels keep them.  The single-stream kernel and the pool's kernel both run this body: one stream's arithmetic is the same
+// in either.
+template <class Chain>
+__device__ __forceinline__ void track_stream_scan_body(const typename Chain::Src& src, int n, int C, float lam, float mu, int64_t t_old,
+                                                       unsigned char* __restrict__ state, int lag, int posterior, uint8_t* __restrict__ bp_new,
+                                                       float* __restrict__ a_new, int32_t* __restrict__ end_new, float* __restrict__ log_z, bool fwd, float* s_u) {
+  const TrackStreamLayout<Chain> lay(C, lag, posterior != 0);
+  const Chain ch(C);
+  const unsigned S = Chain::states(C);                             // (unsigned: a row index times S needs no sign word)
+  const int C4 = (C + 3) & ~3;
+  const float ninf = -INFINITY;
+  float* carried = reinterpret_cast<float*>(state + (fwd ? lay.a : lay.s));
+  double* st_shifted = reinterpret_cast<double*>(state);
+  int32_t* st_end = reinterpret_cast<int32_t*>(state + 8);
+  double shifted = (fwd && t_old > 0) ? st_shifted[0] : 0.0;
+  float v = (t_old > 0 && ch.live) ? carried[ch.j] : ninf;
+  int k = 0;
+  typename Chain::In next = ch.load(src, n > 0);
+  if (Chain::LDS_PREFILL) {
+    s_u[threadIdx.x] = ninf;
+    __syncthreads();
+  }
+  if (t_old == 0 && n > 0) {                                       // the first row of the stream: s_0 / a_0 = the emission of row 0, as the offline scans begin
+    const typename Chain::In in = next;
+    if (n > 1) next = ch.load(src.at(1), true);
+    const float e = (Chain::VITERBI_TAKES_EMISSION || fwd) ? ch.emission(in) : 0.f;
+    if (fwd) {
+      v = e;
+      const float m = fb_finite_or_zero(wave_max(v));
+      v -= m;
+      shifted += (double)m;
+      if (ch.live) a_new[ch.j] = v;
+    } else {
+      v = ch.first_viterbi(in, e);
+      if (ch.live) bp_new[ch.j] = 0;                               // never followed: the backtrace stops at row 1
+      const int end = track_wave_end_state(v, ch.live);            // (the ballot needs the whole wavefront)
+      if (ch.j == 0) end_new[0] = end;
+    }
+    k = 1;
+  }
+  ch.put(s_u, fwd, v);
+  __syncthreads();
+  // One 4-byte no-op, executed once per push.  The loop below is one wavefront running n dependent steps, and its time depends on where its 8-byte instructions lie
+  // against an 8-byte boundary: with the loop heads 4 bytes off, the plain scan of 1000 rows measured 1143 us against 1112 us (kernel trace, MI355X).  The kernel
+  // arguments are loaded by 20 bytes less code than before the kernels became templates; this puts the loops of all four scan kernels back where they lay
+  // (profiles/track_refactor.md has the loop heads' offsets and the times).  Whoever changes the code in front of the loop checks the offsets again.
+  asm volatile("s_nop 0");
+  for (; k < n; ++k) {
+    const typename Chain::In in = next;
+    if (k + 1 < n) next = ch.load(src.at(k + 1), true);            // the next row's loads travel under this step
+    const float e = (Chain::VITERBI_TAKES_EMISSION || fwd) ? ch.emission(in) : 0.f;
+    if (fwd) {
+      float m;
+      v = ch.fb_step(s_u, C4, false, lam, mu, e, m);
+      shifted += (double)m;
+      if (ch.live) a_new[(int64_t)k * S + ch.j] = v;
+    } else {
+      int bp;
+      v = ch.viterbi_step(s_u, C, lam, mu, in, e, bp);
+      if (ch.live) bp_new[(int64_t)k * S + ch.j] = (uint8_t)bp;
+      const int end = track_wave_end_state(v, ch.live);
+      if (ch.j == 0) end_new[k] = end;
+    }
+    __syncthreads();                                               // every lane has read s_u
+    ch.put(s_u, fwd, v);
+    __syncthreads();
+  }
+  if (n > 0) {
+    const int end = track_wave_end_state(v, ch.live);
+    if (ch.live) carried[ch.j] = v;
+    if (ch.j == 0) {
+      if (fwd) st_shifted[0] = shifted;
+      else st_end[0] = end;
+    }
+  }
+  if (fwd) {
+    const float z = logf(wave_sum(expf(v)));                       // the normalised a of the last row: maximum 0
+    if (ch.j == 0) log_z[0] = (float)(shifted + (double)z);
+  }
+}
+
+template <class Chain>
+__global__ __launch_bounds__(64) void track_stream_scan_kernel(typename Chain::Src src, int n, int C, float lam, float mu, int64_t t_old,
+                                                                unsigned char* __restrict__ state, int lag, int posterior, uint8_t* __restrict__ bp_new,
+                                                                float* __restrict__ a_new, int32_t* __restrict__ end_new, float* __restrict__ log_z) {
+  __shared__ __attribute__((aligned(16))) float s_u[TRACK_MAX_C];
+  track_stream_scan_body<Chain>(src, n, C, lam, mu, t_old, state, lag, posterior, bp_new, a_new, end_new, log_z, blockIdx.x == 1, s_u);      // block 1: the forward scan
+}
+
+// Block i < n_commit: window w = w0 + i, read from the prefix that ends at row R = min(w + lag, t_last).  Block n_commit (if n_tail > 0): the tail, the path of the
+// whole prefix on the last n_tail rows.  The backtrace runs over rows of S back pointers (every index read clamped below S); the state it arrives at is written by the
+// chain (cls alone, or cls = j % C and sync = j / C).
+// bx = the block's index among the stream's n_commit + (n_tail > 0) blocks; s_u (16-byte aligned) / s_b: TRACK_MAX_C floats of LDS each, s_tail: 256 ints.
+template <class Chain, bool POST>
+__device__ __forceinline__ void track_stream_readout_body(const TrackStreamRows<Chain>& rows, float lam, float mu, const float* __restrict__ grid, int64_t w0,
+                                                          int n_commit, int n_tail, int64_t t_last, const TrackStreamOut& out, int bx, float* s_u, float* s_b,
+                                                          int* s_tail) {
+  const int C = rows.C, S = Chain::states(C);
+  const Chain ch(C);
   if (bx == n_commit) {                                            // the tail
     const int64_t w = t_last - (n_tail - 1);
     int cur = rows.end(t_last);
     cur = cur < 0 ? 0 : (cur >= S ? S - 1 : cur);
-    track_stream_backtrace<true>(rows, t_last, w, cur, ln.j, ln.live, s_tail);
+    track_stream_backtrace<true>(rows, t_last, w, cur, ch.j, ch.live, s_tail);
     __syncthreads();
     for (int i = threadIdx.x; i < n_tail; i += 64) {
       const float* row = rows.logits(w + i);
       int best;
       float m, sum;
       track_row_stats(row, C, best, m, sum);
-      const int cls = s_tail[i] % C;
-      out.cls_tail[i] = cls;
-      out.sync_tail[i] = s_tail[i] / C;
+      const int cls = Chain::put_state(s_tail[i], C, out.cls_tail, out.sync_tail, i);
       out.conf_tail[i] = track_row_conf(row, C, cls, m, sum);
     }
     return;
@@ -1285,93 +961,87 @@ __device__ __forceinline__ void track_gated_stream_readout_body(const TrackGated
   const int64_t R = w + rows.lag < t_last ? w + rows.lag : t_last;
   int cur = rows.end(R);
   cur = cur < 0 ? 0 : (cur >= S ? S - 1 : cur);
-  cur = track_stream_backtrace<false>(rows, R, w, cur, ln.j, ln.live, nullptr);
-  if (ln.j == 0) {
+  cur = track_stream_backtrace<false>(rows, R, w, cur, ch.j, ch.live, nullptr);
+  if (ch.j == 0) {
     const float* row = rows.logits(w);
     int best;
     float m, sum;
     track_row_stats(row, C, best, m, sum);
-    out.cls_lag[i] = cur % C;
-    out.sync_lag[i] = cur / C;
-    out.conf_lag[i] = track_row_conf(row, C, cur % C, m, sum);
+    const int cls = Chain::put_state(cur, C, out.cls_lag, out.sync_lag, i);
+    out.conf_lag[i] = track_row_conf(row, C, cls, m, sum);
   }
   if (POST) {
     // the backward scan of the prefix 0 .. R, from its end down to row w:  b_R = 0;  b_r[j] = lse_n (b_{r+1}[n] + E[r+1, n] + T(j, n)), renormalised per step
     const int C4 = (C + 3) & ~3;
     const float ninf = -INFINITY;
-    const float log_c = logf((float)C);
-    const bool loads = ln.live && ln.m;
-    const int slot = ln.m * 32 + ln.c;
-    s_u[threadIdx.x] = ninf;                                       // (ordered before the planes' stores by the loop's first barrier)
-    float v = ln.live ? 0.f : ninf;
-    float l_next = loads ? rows.logits(R)[ln.c] : ninf;
-    float z0_next = rows.gate(R)[0], z1_next = rows.gate(R)[1];
+    if (Chain::LDS_PREFILL) s_u[threadIdx.x] = ninf;               // (ordered before the lanes' stores by the loop's first barrier)
+    float v = ch.live ? 0.f : ninf;
+    typename Chain::In next = ch.load_row(rows, R);
     for (int64_t r = R; r > w; --r) {                              // b_{r-1} from b_r and row r
-      const float l = l_next, z0 = z0_next, z1 = z1_next;
-      if (r - 1 > w) {
-        l_next = loads ? rows.logits(r - 1)[ln.c] : ninf;
-        z0_next = rows.gate(r - 1)[0];
-        z1_next = rows.gate(r - 1)[1];
-      }
-      const float e = track_gated_emission(ln, l, z0, z1, log_c);
+      const typename Chain::In in = next;
+      if (r - 1 > w) next = ch.load_row(rows, r - 1);
+      const float e = ch.emission(in);
       __syncthreads();                                             // every lane has read s_u
-      if (ln.live) s_u[slot] = v + e;
+      ch.put(s_u, true, v + e);
       __syncthreads();
       float m;
-      v = track_gated_fb_step(ln, s_u, C4, true, lam, mu, 0.f, m);
+      v = ch.fb_step(s_u, C4, true, lam, mu, 0.f, m);
     }
-    if (ln.live) s_b[ln.j] = v;
+    if (ch.live) s_b[ch.j] = v;                                    // (the combine reads the S live entries only)
     __syncthreads();
-    if (ln.j == 0) {
-      int best;
-      float pbest, mean, ps;
-      track_gated_combine_row(rows.a(w), s_b, C, grid, out.post_lag + (int64_t)i * out.ldp, best, pbest, mean, ps);
-      out.p_sync_lag[i] = ps;
-      out.cls_post_lag[i] = best;
-      out.conf_post_lag[i] = pbest;
-      out.offset_mean_lag[i] = mean;
-    }
+    if (ch.j == 0) Chain::combine(rows.a(w), s_b, C, grid, out, i);
   }
 }
 
-template <bool POST>
-__global__ __launch_bounds__(64) void track_gated_stream_readout_kernel(TrackGatedStreamRows rows, float lam, float mu, const float* __restrict__ grid, int64_t w0,
-                                                                         int n_commit, int n_tail, int64_t t_last, TrackGatedStreamOut out) {
-  __shared__ __attribute__((aligned(16))) float s_u[64];
-  __shared__ float s_b[64];
+template <class Chain, bool POST>
+__global__ __launch_bounds__(64) void track_stream_readout_kernel(TrackStreamRows<Chain> rows, float lam, float mu, const float* __restrict__ grid, int64_t w0,
+                                                                   int n_commit, int n_tail, int64_t t_last, TrackStreamOut out) {
+  __shared__ __attribute__((aligned(16))) float s_u[TRACK_MAX_C];
+  __shared__ float s_b[TRACK_MAX_C];
   __shared__ int s_tail[256];
-  track_gated_stream_readout_body<POST>(rows, lam, mu, grid, w0, n_commit, n_tail, t_last, out, (int)blockIdx.x, s_u, s_b, s_tail);
+  track_stream_readout_body<Chain, POST>(rows, lam, mu, grid, w0, n_commit, n_tail, t_last, out, (int)blockIdx.x, s_u, s_b, s_tail);
 }
 
-// Ring row j of a push: new row k = k0 + j (row t_old + k of the stream) into slot (t_old + k) % lag of the rings: C offset logits, 2 gate logits, 2C back pointers
-// and (posterior) 2C entries of a, one lane per entry.
-__device__ __forceinline__ void track_gated_stream_keep_body(const float* __restrict__ logits, int64_t ldl, const float* __restrict__ gate, int64_t ldg,
-                                                             const uint8_t* __restrict__ bp_new, const float* __restrict__ a_new, int k0, int64_t t_old, int C, int lag,
-                                                             int posterior, unsigned char* __restrict__ state, int j) {
-  const TrackGatedStreamLayout lay(C, lag, posterior != 0);
+// Ring row j of a push: new row k = k0 + j (row t_old + k of the stream) into slot (t_old + k) % lag of the rings: the row's inputs (what the chain keeps of them), S
+// back pointers and (posterior) S entries of a, one lane per entry.
+template <class Chain>
+__device__ __forceinline__ void track_stream_keep_body(const typename Chain::Src& src, const uint8_t* __restrict__ bp_new, const float* __restrict__ a_new, int k0,
+                                                       int64_t t_old, int C, int lag, int posterior, unsigned char* __restrict__ state, int j) {
+  const TrackStreamLayout<Chain> lay(C, lag, posterior != 0);
   const int c = threadIdx.x;
-  const int S = 2 * C;
+  const int S = Chain::states(C);
   if (c >= S) return;
   const int64_t k = k0 + (int64_t)j;
   const int64_t ring = (t_old + k) % lag;
-  if (c < C) reinterpret_cast<float*>(state + lay.lg_ring)[ring * C + c] = logits[k * ldl + c];
-  if (c < 2) reinterpret_cast<float*>(state + lay.gz_ring)[ring * 2 + c] = gate[k * ldg + c];
+  Chain::keep_inputs(src.at(k), reinterpret_cast<float*>(state + lay.lg_ring) + ring * C, reinterpret_cast<float*>(state + lay.gz_ring) + ring * Chain::GATE_WIDTH, c, C);
   (state + lay.bp_ring)[ring * S + c] = bp_new[k * S + c];
   if (posterior) reinterpret_cast<float*>(state + lay.a_ring)[ring * S + c] = a_new[k * S + c];
 }
 
 // Block j: ring row j.
-__global__ __launch_bounds__(64) void track_gated_stream_keep_kernel(const float* __restrict__ logits, int64_t ldl, const float* __restrict__ gate, int64_t ldg,
-                                                                      const uint8_t* __restrict__ bp_new, const float* __restrict__ a_new, int k0, int64_t t_old, int C,
-                                                                      int lag, int posterior, unsigned char* __restrict__ state) {
-  track_gated_stream_keep_body(logits, ldl, gate, ldg, bp_new, a_new, k0, t_old, C, lag, posterior, state, (int)blockIdx.x);
+template <class Chain>
+__global__ __launch_bounds__(64) void track_stream_keep_kernel(typename Chain::Src src, const uint8_t* __restrict__ bp_new, const float* __restrict__ a_new, int k0,
+                                                                int64_t t_old, int C, int lag, int posterior, unsigned char* __restrict__ state) {
+  track_stream_keep_body<Chain>(src, bp_new, a_new, k0, t_old, C, lag, posterior, state, (int)blockIdx.x);
 }
 
-// What sf_track_stream_push and track_gated_args_ok refuse, for the two gated stream launchers: C (2 .. 32), lag, lam, mu and - when there are rows - the strides.
+static bool track_stream_shape_ok(const char* who, int C, int lag) {
+  if (C < 2 || C > TRACK_MAX_C) { sf_set_error("%s: C = %d classes out of range (2 .. %d: one lane per class)", who, C, TRACK_MAX_C); return false; }
+  if (lag < 0 || lag > 255) { sf_set_error("%s: lag = %d windows out of range (0 .. 255)", who, lag); return false; }
+  return true;
+}
+
+// What sf_track_stream_push and track_gated_args_ok refuse, for the two gated launchers: C (2 .. 32), lag, lam, mu and - when there are rows - the strides.
+#define TRACK_STREAM_MAX_PUSH (1 << 20)
 static bool track_gated_stream_args_ok(const char* who, int C, int lag, int n, int64_t ldl, int64_t ldg, float lam, float mu) {
   if (lag < 0 || lag > 255) { sf_set_error("%s: lag = %d windows out of range (0 .. 255)", who, lag); return false; }
   if (n < 0 || n > TRACK_STREAM_MAX_PUSH) { sf_set_error("%s: n = %d rows in one push (0 .. %d: split a longer catch-up)", who, n, TRACK_STREAM_MAX_PUSH); return false; }
   return track_gated_args_ok(who, n, C, n ? ldl : (int64_t)C, n ? ldg : (int64_t)2, lam, mu);
+}
+
+extern "C" int sf_track_stream_bytes(int C, int lag, int posterior) {
+  if (!track_stream_shape_ok("sf_track_stream_bytes", C, lag)) return -1;
+  return (int)TrackStreamLayout<TrackChainPlain>(C, lag, posterior != 0).total;      // at most 16 + 512 + 255 * 64 * 9
 }
 
 extern "C" int sf_track_stream_gated_bytes(int C, int lag, int posterior) {
@@ -1379,13 +1049,81 @@ extern "C" int sf_track_stream_gated_bytes(int C, int lag, int posterior) {
   return (int)TrackGatedStreamLayout(C, lag, posterior != 0).total;      // at most 16 + 512 + 255 * (32 * 4 + 8 + 64 * 4 + 64)
 }
 
-// the workspace of a gated push: [posterior: a (n, 2C) fp32][end (n) int32][back pointers (n, 2C) bytes] - TrackPoolWorkspace over rows of 2C
-extern "C" int sf_track_stream_gated_workspace_bytes(int C, int n, int posterior) {
-  if (!track_gated_stream_args_ok("sf_track_stream_gated_workspace_bytes", C, 0, n, C, 2, 0.f, 0.f)) return -1;
-  return (int)(((posterior ? (int64_t)n * 2 * C * 4 : 0) + (int64_t)n * 4 + (int64_t)n * 2 * C + 15) & ~(int64_t)15);      // at most 2^20 * 324
+extern "C" int sf_track_stream_workspace_bytes(int C, int n, int posterior) {
+  SF_CHECK_ARG(C >= 2 && C <= TRACK_MAX_C, "sf_track_stream_workspace_bytes: C = %d classes out of range (2 .. %d)", C, TRACK_MAX_C);
+  SF_CHECK_ARG(n >= 0 && n <= TRACK_STREAM_MAX_PUSH, "sf_track_stream_workspace_bytes: n = %d rows in one push (0 .. %d)", n, TRACK_STREAM_MAX_PUSH);
+  return (int)track_workspace_bytes(C, n, posterior);
 }
 
-extern "C" int sf_track_pool_gated_workspace_bytes(int C, int total_rows, int posterior) { return sf_track_stream_gated_workspace_bytes(C, total_rows, posterior); }
+extern "C" int sf_track_stream_gated_workspace_bytes(int C, int n, int posterior) {
+  if (!track_gated_stream_args_ok("sf_track_stream_gated_workspace_bytes", C, 0, n, C, 2, 0.f, 0.f)) return -1;
+  return (int)track_workspace_bytes(2 * C, n, posterior);
+}
+
+// One stream's push, after the entry's own checks of C, lag, n, the strides and the costs: the counts, the null checks and the launches.  `who` names the entry.
+template <class Chain>
+static int track_stream_push_impl(const char* who, void* state, int C, int lag, int posterior, int64_t rows_done, const typename Chain::Src& src, int n, float lam,
+                                  float mu, const float* grid, int final, int32_t* cls_raw, float* conf_raw, float* sync_raw, const TrackStreamOut& out, float* log_z,
+                                  void* workspace, void* stream) {
+  const int64_t t_old = rows_done, t_new = rows_done + n;
+  const int64_t done_old = t_old > lag ? t_old - lag : 0;                                   // windows committed before this push
+  const int64_t done_new = final ? t_new : (t_new > lag ? t_new - lag : 0);
+  const int64_t n_commit = done_new - done_old, n_tail = t_new - done_new;
+  if (t_new == 0) return 0;
+  SF_CHECK_ARG(n == 0 || (src.ok() && cls_raw && conf_raw && Chain::sync_ok(sync_raw) && workspace), "%s: null pointer (new rows)", who);
+  SF_CHECK_ARG(n_commit == 0 || (out.cls_lag && Chain::sync_ok(out.sync_lag) && out.conf_lag), "%s: null pointer (committed block)", who);
+  SF_CHECK_ARG(n_tail == 0 || (out.cls_tail && Chain::sync_ok(out.sync_tail) && out.conf_tail), "%s: null pointer (tail)", who);
+  if (posterior) {
+    SF_CHECK_ARG(log_z, "%s: null log_z", who);
+    SF_CHECK_ARG(n_commit == 0 || (grid && out.post_lag && Chain::sync_ok(out.p_sync_lag) && out.cls_post_lag && out.conf_post_lag && out.offset_mean_lag && out.ldp >= C),
+                 "%s: null pointer or post row stride ldp = %lld below C = %d (posterior block)", who, (long long)out.ldp, C);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  unsigned char* st = static_cast<unsigned char*>(state);
+  const TrackPoolWorkspace ws(static_cast<unsigned char*>(workspace), Chain::states(C), n, posterior != 0);
+  if (n > 0) {
+    Chain::launch_rows(src, n, C, cls_raw, conf_raw, sync_raw, s);
+    SF_LAUNCH_CHECK_AS(who);
+  }
+  if (n > 0 || posterior) {                                        // (n == 0 with the posterior: log_z of the prefix so far, from the carried a)
+    hipLaunchKernelGGL(track_stream_scan_kernel<Chain>, dim3(posterior ? 2 : 1), dim3(64), 0, s, src, n, C, lam, mu, t_old, st, lag, posterior, ws.bp, ws.a, ws.end, log_z);
+    SF_LAUNCH_CHECK_AS(who);
+  }
+  if (n_commit + n_tail > 0) {
+    const TrackStreamRows<Chain> rows = track_stream_rows<Chain>(st, src, ws, t_old, lag, C, posterior != 0);
+    const dim3 g((unsigned)(n_commit + (n_tail > 0 ? 1 : 0)));
+    if (posterior)
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(track_stream_readout_kernel<Chain, true>), g, dim3(64), 0, s, rows, lam, mu, grid, done_old, (int)n_commit, (int)n_tail, t_new - 1,
+                         out);
+    else
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(track_stream_readout_kernel<Chain, false>), g, dim3(64), 0, s, rows, lam, mu, grid, done_old, (int)n_commit, (int)n_tail, t_new - 1,
+                         out);
+    SF_LAUNCH_CHECK_AS(who);
+  }
+  const int keep = n < lag ? n : lag;
+  if (keep > 0) {
+    hipLaunchKernelGGL(track_stream_keep_kernel<Chain>, dim3((unsigned)keep), dim3(64), 0, s, src, (const uint8_t*)ws.bp, (const float*)ws.a, n - keep, t_old, C, lag,
+                       posterior, st);
+    SF_LAUNCH_CHECK_AS(who);
+  }
+  return 0;
+}
+
+extern "C" int sf_track_stream_push(void* state, int C, int lag, int posterior, int64_t rows_done, const float* logits, int64_t ldl, int n, float lam,
+                                    const float* grid, int final, int32_t* cls_raw, float* conf_raw, int32_t* cls_lag, float* conf_lag, float* post_lag, int64_t ldp,
+                                    int32_t* cls_post_lag, float* conf_post_lag, float* offset_mean_lag, int32_t* cls_tail, float* conf_tail, float* log_z,
+                                    void* workspace, void* stream) {
+  const char* who = "sf_track_stream_push";
+  if (!track_stream_shape_ok(who, C, lag)) return -1;
+  SF_CHECK_ARG(state, "%s: null state", who);
+  SF_CHECK_ARG(n >= 0 && n <= TRACK_STREAM_MAX_PUSH, "%s: n = %d rows in one push (0 .. %d: split a longer catch-up)", who, n, TRACK_STREAM_MAX_PUSH);
+  SF_CHECK_ARG(rows_done >= 0 && rows_done <= (INT64_MAX >> 1), "%s: %lld rows pushed so far", who, (long long)rows_done);
+  SF_CHECK_ARG(std::isfinite(lam) && lam >= 0.f, "%s: lam must be finite and >= 0 (the cost of a class change)", who);
+  SF_CHECK_ARG(n == 0 || ldl >= C, "%s: row stride ldl = %lld below C = %d", who, (long long)ldl, C);
+  const TrackStreamOut out{cls_lag, nullptr, conf_lag, post_lag, ldp, nullptr, cls_post_lag, conf_post_lag, offset_mean_lag, cls_tail, nullptr, conf_tail};
+  return track_stream_push_impl<TrackChainPlain>(who, state, C, lag, posterior, rows_done, TrackChainPlain::Src{logits, ldl}, n, lam, 0.f, grid, final, cls_raw, conf_raw,
+                                                 nullptr, out, log_z, workspace, stream);
+}
 
 extern "C" int sf_track_stream_push_gated(void* state, int C, int lag, int posterior, int64_t rows_done, const float* logits, int64_t ldl, const float* gate_logits,
                                           int64_t ldg, int n, float lam, float mu, const float* grid, int final, int32_t* cls_raw, float* conf_raw, float* sync_raw,
@@ -1396,95 +1134,177 @@ extern "C" int sf_track_stream_push_gated(void* state, int C, int lag, int poste
   if (!track_gated_stream_args_ok(who, C, lag, n, ldl, ldg, lam, mu)) return -1;
   SF_CHECK_ARG(state, "%s: null state", who);
   SF_CHECK_ARG(rows_done >= 0 && rows_done <= (INT64_MAX >> 1), "%s: %lld rows pushed so far", who, (long long)rows_done);
-  const int64_t t_old = rows_done, t_new = rows_done + n;
-  const int64_t done_old = t_old > lag ? t_old - lag : 0;                                   // windows committed before this push
-  const int64_t done_new = final ? t_new : (t_new > lag ? t_new - lag : 0);
-  const int64_t n_commit = done_new - done_old, n_tail = t_new - done_new;
-  if (t_new == 0) return 0;
-  SF_CHECK_ARG(n == 0 || (logits && gate_logits && cls_raw && conf_raw && sync_raw && workspace), "%s: null pointer (new rows)", who);
-  SF_CHECK_ARG(n_commit == 0 || (cls_lag && sync_lag && conf_lag), "%s: null pointer (committed block)", who);
-  SF_CHECK_ARG(n_tail == 0 || (cls_tail && sync_tail && conf_tail), "%s: null pointer (tail)", who);
+  const TrackStreamOut out{cls_lag, sync_lag, conf_lag, post_lag, ldp, p_sync_lag, cls_post_lag, conf_post_lag, offset_mean_lag, cls_tail, sync_tail, conf_tail};
+  return track_stream_push_impl<TrackChainGated>(who, state, C, lag, posterior, rows_done, TrackChainGated::Src{logits, ldl, gate_logits, ldg}, n, lam, mu, grid, final,
+                                                 cls_raw, conf_raw, sync_raw, out, log_z, workspace, stream);
+}
+
+// ---- the same read-out for many streams in one call (sf_track_pool_push, sf_track_pool_push_gated) --------------------------------------------------------------
+// n_active streams that share C, lag and posterior, named by a descriptor table of 8 int64 per stream (slot, rows_done, n, row0, final, commit0, tail0, unused): the
+// states lie state_stride bytes apart in one buffer, the new rows of all streams in one logits matrix (stream e: rows [row0, row0 + n); its gate rows are the same rows
+// of the gate matrix), the committed blocks and the tails back to back in table order.  The same four kinds of launch as one stream's push, each over all streams:
+// blockIdx.y = the table row, blockIdx.x = that stream's own work item (its scan / committed window or tail / ring row); the grid's x extent is the largest count in the
+// table and a block beyond its stream's count exits at once (a stream brings 0 .. n rows and commits 0 .. k windows: the mapping is ragged, an idle block costs one
+// table read).  Every block builds its stream's context from the table's DEVICE copy and runs the single-stream bodies above: one stream's bits do not depend on who
+// shares the push.  (TrackPoolEntry and TrackPoolWorkspace, above the bodies, are the table row and the workspace of either kind of push.)
+
+// What a pool push's table adds up to; track_pool_table_check validates the HOST copy of the table (slots, row ranges, running sums) before anything is launched and
+// fills this in.  Shared by sf_track_pool_push and sf_track_pool_push_gated: the table is the same.
+struct TrackPoolTotals { int64_t sum_n, sum_commit, sum_tail, max_read, max_keep;  bool scan; };
+static int track_pool_table_check(const char* who, const int64_t* table_host, int n_active, int n_slots, int total_rows, int lag, int posterior, TrackPoolTotals& tot) {
+  struct Span { int64_t row0, n; };
+  static thread_local int64_t slots[TRACK_POOL_MAX_ACTIVE];
+  static thread_local Span spans[TRACK_POOL_MAX_ACTIVE];
+  int64_t sum_n = 0, sum_commit = 0, sum_tail = 0, max_read = 0, max_keep = 0;
+  int n_spans = 0;
+  bool scan = false;
+  for (int i = 0; i < n_active; ++i) {
+    const int64_t* r = table_host + (int64_t)i * TRACK_POOL_ROW;
+    SF_CHECK_ARG(r[0] >= 0 && r[0] < n_slots, "%s: table row %d: slot %lld outside the %d slots", who, i, (long long)r[0], n_slots);
+    SF_CHECK_ARG(r[1] >= 0 && r[1] <= (INT64_MAX >> 1), "%s: table row %d: %lld rows pushed so far", who, i, (long long)r[1]);
+    SF_CHECK_ARG(r[2] >= 0 && r[3] >= 0 && r[2] <= total_rows && r[3] <= total_rows - r[2],
+                 "%s: table row %d: rows [%lld, %lld + %lld) outside the %d rows of the push", who, i, (long long)r[3], (long long)r[3], (long long)r[2], total_rows);
+    const TrackPoolEntry e(table_host, i, lag);
+    SF_CHECK_ARG(e.commit0 == sum_commit && e.tail0 == sum_tail,
+                 "%s: table row %d: commit0 = %lld, tail0 = %lld, the counts of the rows before it give %lld, %lld", who, i, (long long)e.commit0,
+                 (long long)e.tail0, (long long)sum_commit, (long long)sum_tail);
+    slots[i] = e.slot;
+    if (e.n > 0) spans[n_spans++] = Span{e.row0, e.n};
+    if (e.t_new > 0) {
+      sum_commit += e.n_commit;
+      sum_tail += e.n_tail;
+      if (e.readout_blocks() > max_read) max_read = e.readout_blocks();
+      if (e.keep(lag) > max_keep) max_keep = e.keep(lag);
+      scan = scan || e.n > 0 || posterior;
+    }
+    sum_n += e.n;
+  }
+  std::sort(slots, slots + n_active);
+  for (int i = 1; i < n_active; ++i) SF_CHECK_ARG(slots[i] != slots[i - 1], "%s: slot %lld named twice in one push", who, (long long)slots[i]);
+  std::sort(spans, spans + n_spans, [](const Span& a, const Span& b) { return a.row0 < b.row0; });
+  for (int i = 1; i < n_spans; ++i)
+    SF_CHECK_ARG(spans[i - 1].row0 + spans[i - 1].n <= spans[i].row0, "%s: the rows [%lld, +%lld) and [%lld, +%lld) of two streams overlap", who,
+                 (long long)spans[i - 1].row0, (long long)spans[i - 1].n, (long long)spans[i].row0, (long long)spans[i].n);
+  tot = TrackPoolTotals{sum_n, sum_commit, sum_tail, max_read, max_keep, scan};
+  return 0;
+}
+
+// grid (posterior ? 2 : 1, n_active): block (0, e) the Viterbi scan of stream e, block (1, e) its forward scan
+template <class Chain>
+__global__ __launch_bounds__(64) void track_pool_scan_kernel(const int64_t* __restrict__ table, unsigned char* __restrict__ states, int64_t state_stride,
+                                                              typename Chain::Src src, int C, float lam, float mu, int lag, int posterior,
+                                                              unsigned char* __restrict__ workspace, int total_rows, float* __restrict__ log_z) {
+  __shared__ __attribute__((aligned(16))) float s_u[TRACK_MAX_C];
+  const TrackPoolEntry e(table, blockIdx.y, lag);
+  const bool fwd = blockIdx.x == 1;
+  if (e.t_new == 0 || (e.n == 0 && !fwd)) return;                  // an empty stream; nothing to scan (n == 0 with the posterior: log_z from the carried a)
+  const int S = Chain::states(C);
+  const TrackPoolWorkspace ws = TrackPoolWorkspace(workspace, S, total_rows, posterior != 0).at(e.row0, S);
+  track_stream_scan_body<Chain>(src.at(e.row0), (int)e.n, C, lam, mu, e.t_old, states + e.slot * state_stride, lag, posterior, ws.bp, ws.a, ws.end, log_z + blockIdx.y,
+                                fwd, s_u);
+}
+
+// grid (the largest n_commit + (n_tail > 0) of the table, n_active)
+template <class Chain, bool POST>
+__global__ __launch_bounds__(64) void track_pool_readout_kernel(const int64_t* __restrict__ table, const unsigned char* __restrict__ states, int64_t state_stride,
+                                                                 typename Chain::Src src, int C, float lam, float mu, int lag, const float* __restrict__ grid,
+                                                                 const unsigned char* __restrict__ workspace, int total_rows, TrackStreamOut out) {
+  __shared__ __attribute__((aligned(16))) float s_u[TRACK_MAX_C];
+  __shared__ float s_b[TRACK_MAX_C];
+  __shared__ int s_tail[256];
+  const TrackPoolEntry e(table, blockIdx.y, lag);
+  if ((int64_t)blockIdx.x >= e.readout_blocks()) return;
+  const int S = Chain::states(C);
+  const TrackPoolWorkspace ws = TrackPoolWorkspace(const_cast<unsigned char*>(workspace), S, total_rows, POST).at(e.row0, S);
+  const TrackStreamRows<Chain> rows = track_stream_rows<Chain>(states + e.slot * state_stride, src.at(e.row0), ws, e.t_old, lag, C, POST);
+  track_stream_readout_body<Chain, POST>(rows, lam, mu, grid, e.done_old, (int)e.n_commit, (int)e.n_tail, e.t_new - 1, out.at(e.commit0, e.tail0), (int)blockIdx.x, s_u,
+                                         s_b, s_tail);
+}
+
+// grid (the largest min(n, lag) of the table, n_active)
+template <class Chain>
+__global__ __launch_bounds__(64) void track_pool_keep_kernel(const int64_t* __restrict__ table, unsigned char* __restrict__ states, int64_t state_stride,
+                                                              typename Chain::Src src, int C, int lag, int posterior, const unsigned char* __restrict__ workspace,
+                                                              int total_rows) {
+  const TrackPoolEntry e(table, blockIdx.y, lag);
+  const int64_t keep = e.keep(lag);
+  if ((int64_t)blockIdx.x >= keep) return;
+  const int S = Chain::states(C);
+  const TrackPoolWorkspace ws = TrackPoolWorkspace(const_cast<unsigned char*>(workspace), S, total_rows, posterior != 0).at(e.row0, S);
+  track_stream_keep_body<Chain>(src.at(e.row0), ws.bp, ws.a, (int)(e.n - keep), e.t_old, C, lag, posterior, states + e.slot * state_stride, (int)blockIdx.x);
+}
+
+extern "C" int sf_track_pool_workspace_bytes(int C, int total_rows, int posterior) {
+  SF_CHECK_ARG(C >= 2 && C <= TRACK_MAX_C, "sf_track_pool_workspace_bytes: C = %d classes out of range (2 .. %d)", C, TRACK_MAX_C);
+  SF_CHECK_ARG(total_rows >= 0 && total_rows <= TRACK_STREAM_MAX_PUSH, "sf_track_pool_workspace_bytes: %d rows in one push (0 .. %d)", total_rows, TRACK_STREAM_MAX_PUSH);
+  return sf_track_stream_workspace_bytes(C, total_rows, posterior);
+}
+
+extern "C" int sf_track_pool_gated_workspace_bytes(int C, int total_rows, int posterior) { return sf_track_stream_gated_workspace_bytes(C, total_rows, posterior); }
+
+// A pool's push, after the entry's own checks of C, lag, total_rows and the costs: the table, the strides, the null checks and the launches.  `who` names the entry.
+template <class Chain>
+static int track_pool_push_impl(const char* who, void* states, int64_t state_stride, int n_slots, int C, int lag, int posterior, const int64_t* table_host,
+                                const int64_t* table_dev, int n_active, const typename Chain::Src& src, int total_rows, float lam, float mu, const float* grid,
+                                int32_t* cls_raw, float* conf_raw, float* sync_raw, const TrackStreamOut& out, float* log_z, void* workspace, void* stream) {
+  SF_CHECK_ARG(n_active >= 1 && n_active <= TRACK_POOL_MAX_ACTIVE, "%s: n_active = %d streams in one push (1 .. %d)", who, n_active, TRACK_POOL_MAX_ACTIVE);
+  SF_CHECK_ARG(n_slots >= 1, "%s: n_slots = %d", who, n_slots);
+  SF_CHECK_ARG(states && table_host && table_dev, "%s: null pointer (states or table)", who);
+  const TrackStreamLayout<Chain> lay(C, lag, posterior != 0);
+  SF_CHECK_ARG(state_stride >= lay.total && state_stride % 16 == 0, "%s: state stride %lld: a multiple of 16, at least %lld bytes", who, (long long)state_stride,
+               (long long)lay.total);
+  TrackPoolTotals tot;
+  if (track_pool_table_check(who, table_host, n_active, n_slots, total_rows, lag, posterior, tot)) return -1;
+  if (tot.sum_n > 0 && !src.strides_ok(who, C)) return -1;
+  SF_CHECK_ARG(tot.sum_n == 0 || (src.ok() && cls_raw && conf_raw && Chain::sync_ok(sync_raw) && workspace), "%s: null pointer (new rows)", who);
+  SF_CHECK_ARG(tot.sum_commit == 0 || (out.cls_lag && Chain::sync_ok(out.sync_lag) && out.conf_lag), "%s: null pointer (committed block)", who);
+  SF_CHECK_ARG(tot.sum_tail == 0 || (out.cls_tail && Chain::sync_ok(out.sync_tail) && out.conf_tail), "%s: null pointer (tail)", who);
   if (posterior) {
-    SF_CHECK_ARG(log_z, "%s: null log_z", who);
-    SF_CHECK_ARG(n_commit == 0 || (grid && post_lag && p_sync_lag && cls_post_lag && conf_post_lag && offset_mean_lag && ldp >= C),
-                 "%s: null pointer or post row stride ldp = %lld below C = %d (posterior block)", who, (long long)ldp, C);
+    SF_CHECK_ARG(!tot.scan || log_z, "%s: null log_z", who);
+    SF_CHECK_ARG(tot.sum_commit == 0 || (grid && out.post_lag && Chain::sync_ok(out.p_sync_lag) && out.cls_post_lag && out.conf_post_lag && out.offset_mean_lag && out.ldp >= C),
+                 "%s: null pointer or post row stride ldp = %lld below C = %d (posterior block)", who, (long long)out.ldp, C);
   }
   hipStream_t s = (hipStream_t)stream;
-  const TrackGatedStreamLayout lay(C, lag, posterior != 0);
-  unsigned char* st = static_cast<unsigned char*>(state);
-  const TrackPoolWorkspace ws(static_cast<unsigned char*>(workspace), 2 * C, n, posterior != 0);
-  if (n > 0) {
-    hipLaunchKernelGGL(track_gated_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, logits, ldl, gate_logits, ldg, n, C, cls_raw, conf_raw, sync_raw);
-    SF_LAUNCH_CHECK();
+  unsigned char* st = static_cast<unsigned char*>(states);
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  if (tot.sum_n > 0) {                                             // one thread per row of the packed matrices (rows between two streams' ranges: their own argmax, unread)
+    Chain::launch_rows(src, total_rows, C, cls_raw, conf_raw, sync_raw, s);
+    SF_LAUNCH_CHECK_AS(who);
   }
-  if (n > 0 || posterior) {                                        // (n == 0 with the posterior: log_z of the prefix so far, from the carried a)
-    hipLaunchKernelGGL(track_gated_stream_scan_kernel, dim3(posterior ? 2 : 1), dim3(64), 0, s, logits, ldl, gate_logits, ldg, n, C, lam, mu, t_old, st, lag, posterior,
-                       ws.bp, ws.a, ws.end, log_z);
-    SF_LAUNCH_CHECK();
+  if (tot.scan) {
+    hipLaunchKernelGGL(track_pool_scan_kernel<Chain>, dim3(posterior ? 2 : 1, (unsigned)n_active), dim3(64), 0, s, table_dev, st, state_stride, src, C, lam, mu, lag,
+                       posterior, ws, total_rows, log_z);
+    SF_LAUNCH_CHECK_AS(who);
   }
-  if (n_commit + n_tail > 0) {
-    TrackGatedStreamRows rows;
-    track_gated_rows_fill(rows, lay, st, logits, ldl, gate_logits, ldg, ws.bp, ws.a, ws.end, t_old, lag, C);
-    const TrackGatedStreamOut out{cls_lag, sync_lag, conf_lag, post_lag, ldp, p_sync_lag, cls_post_lag, conf_post_lag, offset_mean_lag, cls_tail, sync_tail, conf_tail};
-    const dim3 g((unsigned)(n_commit + (n_tail > 0 ? 1 : 0)));
+  if (tot.max_read > 0) {
+    const dim3 g((unsigned)tot.max_read, (unsigned)n_active);
     if (posterior)
-      hipLaunchKernelGGL(track_gated_stream_readout_kernel<true>, g, dim3(64), 0, s, rows, lam, mu, grid, done_old, (int)n_commit, (int)n_tail, t_new - 1, out);
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(track_pool_readout_kernel<Chain, true>), g, dim3(64), 0, s, table_dev, (const unsigned char*)st, state_stride, src, C, lam, mu, lag,
+                         grid, (const unsigned char*)ws, total_rows, out);
     else
-      hipLaunchKernelGGL(track_gated_stream_readout_kernel<false>, g, dim3(64), 0, s, rows, lam, mu, grid, done_old, (int)n_commit, (int)n_tail, t_new - 1, out);
-    SF_LAUNCH_CHECK();
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(track_pool_readout_kernel<Chain, false>), g, dim3(64), 0, s, table_dev, (const unsigned char*)st, state_stride, src, C, lam, mu, lag,
+                         grid, (const unsigned char*)ws, total_rows, out);
+    SF_LAUNCH_CHECK_AS(who);
   }
-  const int keep = n < lag ? n : lag;
-  if (keep > 0) {
-    hipLaunchKernelGGL(track_gated_stream_keep_kernel, dim3((unsigned)keep), dim3(64), 0, s, logits, ldl, gate_logits, ldg, (const uint8_t*)ws.bp, (const float*)ws.a,
-                       n - keep, t_old, C, lag, posterior, st);
-    SF_LAUNCH_CHECK();
+  if (tot.max_keep > 0) {
+    hipLaunchKernelGGL(track_pool_keep_kernel<Chain>, dim3((unsigned)tot.max_keep, (unsigned)n_active), dim3(64), 0, s, table_dev, st, state_stride, src, C, lag, posterior,
+                       (const unsigned char*)ws, total_rows);
+    SF_LAUNCH_CHECK_AS(who);
   }
   return 0;
 }
 
-// The pool's kernels: sf_track_pool_push's mapping (blockIdx.y = the table row, blockIdx.x = the stream's own work item), every block running the gated bodies above on
-// its stream's context.  Stream e's gate rows are rows [row0, row0 + n) of the gate matrix, as its offset rows are of logits.
-__global__ __launch_bounds__(64) void track_gated_pool_scan_kernel(const int64_t* __restrict__ table, unsigned char* __restrict__ states, int64_t state_stride,
-                                                                    const float* __restrict__ logits, int64_t ldl, const float* __restrict__ gate, int64_t ldg, int C,
-                                                                    float lam, float mu, int lag, int posterior, unsigned char* __restrict__ workspace, int total_rows,
-                                                                    float* __restrict__ log_z) {
-  __shared__ __attribute__((aligned(16))) float s_u[64];
-  const TrackPoolEntry e(table, blockIdx.y, lag);
-  const bool fwd = blockIdx.x == 1;
-  if (e.t_new == 0 || (e.n == 0 && !fwd)) return;                  // an empty stream; nothing to scan (n == 0 with the posterior: log_z from the carried a)
-  const TrackPoolWorkspace ws(workspace, 2 * C, total_rows, posterior != 0);
-  track_gated_stream_scan_body(logits + e.row0 * ldl, ldl, gate + e.row0 * ldg, ldg, (int)e.n, C, lam, mu, e.t_old, states + e.slot * state_stride, lag, posterior,
-                               ws.bp + e.row0 * 2 * C, ws.a + e.row0 * 2 * C, ws.end + e.row0, log_z + blockIdx.y, fwd, s_u);
-}
-
-template <bool POST>
-__global__ __launch_bounds__(64) void track_gated_pool_readout_kernel(const int64_t* __restrict__ table, const unsigned char* __restrict__ states, int64_t state_stride,
-                                                                       const float* __restrict__ logits, int64_t ldl, const float* __restrict__ gate, int64_t ldg, int C,
-                                                                       float lam, float mu, int lag, const float* __restrict__ grid,
-                                                                       const unsigned char* __restrict__ workspace, int total_rows, TrackGatedStreamOut out) {
-  __shared__ __attribute__((aligned(16))) float s_u[64];
-  __shared__ float s_b[64];
-  __shared__ int s_tail[256];
-  const TrackPoolEntry e(table, blockIdx.y, lag);
-  if ((int64_t)blockIdx.x >= e.readout_blocks()) return;
-  const TrackGatedStreamLayout lay(C, lag, POST);
-  const TrackPoolWorkspace ws(const_cast<unsigned char*>(workspace), 2 * C, total_rows, POST);
-  TrackGatedStreamRows rows;
-  track_gated_rows_fill(rows, lay, states + e.slot * state_stride, logits + e.row0 * ldl, ldl, gate + e.row0 * ldg, ldg, ws.bp + e.row0 * 2 * C, ws.a + e.row0 * 2 * C,
-                        ws.end + e.row0, e.t_old, lag, C);
-  track_gated_stream_readout_body<POST>(rows, lam, mu, grid, e.done_old, (int)e.n_commit, (int)e.n_tail, e.t_new - 1, out.at(e.commit0, e.tail0), (int)blockIdx.x, s_u, s_b,
-                                        s_tail);
-}
-
-__global__ __launch_bounds__(64) void track_gated_pool_keep_kernel(const int64_t* __restrict__ table, unsigned char* __restrict__ states, int64_t state_stride,
-                                                                    const float* __restrict__ logits, int64_t ldl, const float* __restrict__ gate, int64_t ldg, int C,
-                                                                    int lag, int posterior, const unsigned char* __restrict__ workspace, int total_rows) {
-  const TrackPoolEntry e(table, blockIdx.y, lag);
-  const int64_t keep = e.keep(lag);
-  if ((int64_t)blockIdx.x >= keep) return;
-  const TrackPoolWorkspace ws(const_cast<unsigned char*>(workspace), 2 * C, total_rows, posterior != 0);
-  track_gated_stream_keep_body(logits + e.row0 * ldl, ldl, gate + e.row0 * ldg, ldg, ws.bp + e.row0 * 2 * C, ws.a + e.row0 * 2 * C, (int)(e.n - keep), e.t_old, C, lag,
-                               posterior, states + e.slot * state_stride, (int)blockIdx.x);
+extern "C" int sf_track_pool_push(void* states, int64_t state_stride, int n_slots, int C, int lag, int posterior, const int64_t* table_host, const int64_t* table_dev,
+                                  int n_active, const float* logits, int64_t ldl, int total_rows, float lam, const float* grid, int32_t* cls_raw, float* conf_raw,
+                                  int32_t* cls_lag, float* conf_lag, float* post_lag, int64_t ldp, int32_t* cls_post_lag, float* conf_post_lag,
+                                  float* offset_mean_lag, int32_t* cls_tail, float* conf_tail, float* log_z, void* workspace, void* stream) {
+  const char* who = "sf_track_pool_push";
+  if (!track_stream_shape_ok(who, C, lag)) return -1;
+  SF_CHECK_ARG(std::isfinite(lam) && lam >= 0.f, "%s: lam must be finite and >= 0 (the cost of a class change)", who);
+  SF_CHECK_ARG(total_rows >= 0 && total_rows <= TRACK_STREAM_MAX_PUSH, "%s: total_rows = %d rows in one push (0 .. %d)", who, total_rows, TRACK_STREAM_MAX_PUSH);
+  const TrackStreamOut out{cls_lag, nullptr, conf_lag, post_lag, ldp, nullptr, cls_post_lag, conf_post_lag, offset_mean_lag, cls_tail, nullptr, conf_tail};
+  return track_pool_push_impl<TrackChainPlain>(who, states, state_stride, n_slots, C, lag, posterior, table_host, table_dev, n_active, TrackChainPlain::Src{logits, ldl},
+                                               total_rows, lam, 0.f, grid, cls_raw, conf_raw, nullptr, out, log_z, workspace, stream);
 }
 
 extern "C" int sf_track_pool_push_gated(void* states, int64_t state_stride, int n_slots, int C, int lag, int posterior, const int64_t* table_host,
@@ -1495,52 +1315,8 @@ extern "C" int sf_track_pool_push_gated(void* states, int64_t state_stride, int 
   const char* who = "sf_track_pool_push_gated";
   SF_CHECK_ARG(total_rows >= 0 && total_rows <= TRACK_STREAM_MAX_PUSH, "%s: total_rows = %d rows in one push (0 .. %d)", who, total_rows, TRACK_STREAM_MAX_PUSH);
   if (!track_gated_stream_args_ok(who, C, lag, 0, 0, 0, lam, mu)) return -1;
-  SF_CHECK_ARG(n_active >= 1 && n_active <= TRACK_POOL_MAX_ACTIVE, "%s: n_active = %d streams in one push (1 .. %d)", who, n_active, TRACK_POOL_MAX_ACTIVE);
-  SF_CHECK_ARG(n_slots >= 1, "%s: n_slots = %d", who, n_slots);
-  SF_CHECK_ARG(states && table_host && table_dev, "%s: null pointer (states or table)", who);
-  const TrackGatedStreamLayout lay(C, lag, posterior != 0);
-  SF_CHECK_ARG(state_stride >= lay.total && state_stride % 16 == 0, "%s: state stride %lld: a multiple of 16, at least %lld bytes", who, (long long)state_stride,
-               (long long)lay.total);
-  TrackPoolTotals tot;
-  if (track_pool_table_check(who, table_host, n_active, n_slots, total_rows, lag, posterior, tot)) return -1;
-  SF_CHECK_ARG(tot.sum_n == 0 || ldl >= C, "%s: row stride ldl = %lld below C = %d", who, (long long)ldl, C);
-  SF_CHECK_ARG(tot.sum_n == 0 || ldg >= 2, "%s: gate row stride ldg = %lld below 2", who, (long long)ldg);
-  SF_CHECK_ARG(tot.sum_n == 0 || (logits && gate_logits && cls_raw && conf_raw && sync_raw && workspace), "%s: null pointer (new rows)", who);
-  SF_CHECK_ARG(tot.sum_commit == 0 || (cls_lag && sync_lag && conf_lag), "%s: null pointer (committed block)", who);
-  SF_CHECK_ARG(tot.sum_tail == 0 || (cls_tail && sync_tail && conf_tail), "%s: null pointer (tail)", who);
-  if (posterior) {
-    SF_CHECK_ARG(!tot.scan || log_z, "%s: null log_z", who);
-    SF_CHECK_ARG(tot.sum_commit == 0 || (grid && post_lag && p_sync_lag && cls_post_lag && conf_post_lag && offset_mean_lag && ldp >= C),
-                 "%s: null pointer or post row stride ldp = %lld below C = %d (posterior block)", who, (long long)ldp, C);
-  }
-  hipStream_t s = (hipStream_t)stream;
-  unsigned char* st = static_cast<unsigned char*>(states);
-  unsigned char* ws = static_cast<unsigned char*>(workspace);
-  if (tot.sum_n > 0) {                                             // one thread per row of the packed matrices
-    hipLaunchKernelGGL(track_gated_rows_kernel, dim3((unsigned)((total_rows + 255) / 256)), dim3(256), 0, s, logits, ldl, gate_logits, ldg, total_rows, C, cls_raw,
-                       conf_raw, sync_raw);
-    SF_LAUNCH_CHECK();
-  }
-  if (tot.scan) {
-    hipLaunchKernelGGL(track_gated_pool_scan_kernel, dim3(posterior ? 2 : 1, (unsigned)n_active), dim3(64), 0, s, table_dev, st, state_stride, logits, ldl, gate_logits, ldg,
-                       C, lam, mu, lag, posterior, ws, total_rows, log_z);
-    SF_LAUNCH_CHECK();
-  }
-  if (tot.max_read > 0) {
-    const TrackGatedStreamOut out{cls_lag, sync_lag, conf_lag, post_lag, ldp, p_sync_lag, cls_post_lag, conf_post_lag, offset_mean_lag, cls_tail, sync_tail, conf_tail};
-    const dim3 g((unsigned)tot.max_read, (unsigned)n_active);
-    if (posterior)
-      hipLaunchKernelGGL(track_gated_pool_readout_kernel<true>, g, dim3(64), 0, s, table_dev, (const unsigned char*)st, state_stride, logits, ldl, gate_logits, ldg, C, lam, mu,
-                         lag, grid, (const unsigned char*)ws, total_rows, out);
-    else
-      hipLaunchKernelGGL(track_gated_pool_readout_kernel<false>, g, dim3(64), 0, s, table_dev, (const unsigned char*)st, state_stride, logits, ldl, gate_logits, ldg, C, lam, mu,
-                         lag, grid, (const unsigned char*)ws, total_rows, out);
-    SF_LAUNCH_CHECK();
-  }
-  if (tot.max_keep > 0) {
-    hipLaunchKernelGGL(track_gated_pool_keep_kernel, dim3((unsigned)tot.max_keep, (unsigned)n_active), dim3(64), 0, s, table_dev, st, state_stride, logits, ldl, gate_logits,
-                       ldg, C, lag, posterior, (const unsigned char*)ws, total_rows);
-    SF_LAUNCH_CHECK();
-  }
-  return 0;
+  const TrackStreamOut out{cls_lag, sync_lag, conf_lag, post_lag, ldp, p_sync_lag, cls_post_lag, conf_post_lag, offset_mean_lag, cls_tail, sync_tail, conf_tail};
+  return track_pool_push_impl<TrackChainGated>(who, states, state_stride, n_slots, C, lag, posterior, table_host, table_dev, n_active,
+                                               TrackChainGated::Src{logits, ldl, gate_logits, ldg}, total_rows, lam, mu, grid, cls_raw, conf_raw, sync_raw, out, log_z,
+                                               workspace, stream);
 }

@@ -762,15 +762,73 @@ class TrackStreamState:
         self.buf, self.C, self.lag, self.posterior, self.rows, self.closed = buf, int(C), int(lag), bool(posterior), 0, False
 
 
+class TrackPoolState:
+    """The carried states of a pool of streams (sf_track_pool_push): `buf` uint8 (n_slots, bytes) on the device, slot i the state of one stream
+    (sf_track_stream_push's layout); `rows[i]` the rows pushed into slot i so far and `closed[i]` after its final push (host counts).  `gated`: whether the slots
+    have the gated layout (TrackGatedPoolState)."""
+    gated = False
+
+    def __init__(self, buf: torch.Tensor, C: int, lag: int, posterior: bool):
+        self.buf, self.C, self.lag, self.posterior = buf, int(C), int(lag), bool(posterior)
+        self.n_slots = int(buf.shape[0])
+        self.rows, self.closed = [0] * self.n_slots, [False] * self.n_slots
+
+    def reopen(self, slot: int):
+        """Slot `slot` starts a new stream: only the host count is reset - the device state is read only when rows_done > 0."""
+        self.rows[slot], self.closed[slot] = 0, False
+
+
+class TrackGatedStreamState(TrackStreamState):
+    """The carried state of one stream's GATED fixed-lag read-out (sf_track_stream_push_gated, DESIGN 3.21): TrackStreamState's fields over a buffer of
+    sf_track_stream_gated_bytes(C, lag, posterior) bytes, 2C wide.  track_stream_push refuses it, track_stream_push_gated refuses a TrackStreamState."""
+    gated = True
+
+
+class TrackGatedPoolState(TrackPoolState):
+    """The carried states of a pool of GATED streams (sf_track_pool_push_gated): TrackPoolState's fields, each slot a gated state."""
+    gated = True
+
+
+def _track_kind(state, gated: bool, who: str):
+    """A state knows whether it is gated; a push of the other kind raises."""
+    if bool(getattr(state, 'gated', False)) != gated:
+        raise TypeError(f'{who}: the state is {"gated (use the *_gated push)" if not gated else "not gated (use the push without _gated)"}: the two layouts differ')
+
+
+def _track_state(cls, shape, C: int, lag: int, posterior: bool, device):
+    entry = 'sf_track_stream_gated_bytes' if cls.gated else 'sf_track_stream_bytes'
+    nbytes = getattr(_lib.load(), entry)(int(C), int(lag), int(bool(posterior)))
+    if nbytes < 0:
+        _lib.check(nbytes, entry)
+    return cls(torch.zeros(*shape, nbytes, device=device, dtype=torch.uint8), C, lag, posterior)
+
+
 def track_stream_state(C: int, lag: int, posterior: bool, device) -> TrackStreamState:
     """A fresh stream state for C classes (2 .. 64) and a decision lag of `lag` windows (0 .. 255): sf_track_stream_bytes(C, lag, posterior) zeroed bytes on `device`."""
-    nbytes = _lib.load().sf_track_stream_bytes(int(C), int(lag), int(bool(posterior)))
-    if nbytes < 0:
-        _lib.check(nbytes, 'sf_track_stream_bytes')
-    return TrackStreamState(torch.zeros(nbytes, device=device, dtype=torch.uint8), C, lag, posterior)
+    return _track_state(TrackStreamState, (), C, lag, posterior, device)
+
+
+def track_stream_state_gated(C: int, lag: int, posterior: bool, device) -> TrackGatedStreamState:
+    """A fresh gated stream state for C classes (2 .. 32) and a decision lag of `lag` windows (0 .. 255): sf_track_stream_gated_bytes(C, lag, posterior) zeroed bytes."""
+    return _track_state(TrackGatedStreamState, (), C, lag, posterior, device)
+
+
+def track_pool_state(n_slots: int, C: int, lag: int, posterior: bool, device) -> TrackPoolState:
+    """n_slots fresh stream states in one zeroed (n_slots, sf_track_stream_bytes(C, lag, posterior)) buffer on `device` (the size is a multiple of 16: the stride)."""
+    if n_slots < 1:
+        raise ValueError(f'track_pool_state: n_slots = {n_slots}')
+    return _track_state(TrackPoolState, (int(n_slots),), C, lag, posterior, device)
+
+
+def track_pool_state_gated(n_slots: int, C: int, lag: int, posterior: bool, device) -> TrackGatedPoolState:
+    """n_slots fresh gated stream states in one zeroed (n_slots, sf_track_stream_gated_bytes(C, lag, posterior)) buffer on `device`."""
+    if n_slots < 1:
+        raise ValueError(f'track_pool_state_gated: n_slots = {n_slots}')
+    return _track_state(TrackGatedPoolState, (int(n_slots),), C, lag, posterior, device)
 
 
 TrackStreamOut = namedtuple('TrackStreamOut', 'w0 cls_raw conf_raw cls_lag conf_lag cls_tail conf_tail post_lag cls_post_lag conf_post_lag offset_mean_lag log_z')
+TrackGatedStreamOut = namedtuple('TrackGatedStreamOut', TrackStreamOut._fields + ('sync_raw', 'sync_lag', 'sync_tail', 'p_sync_lag'))
 
 
 def track_stream_counts(rows: int, n: int, lag: int, final: bool = False):
@@ -778,6 +836,84 @@ def track_stream_counts(rows: int, n: int, lag: int, final: bool = False):
     done_old = max(0, rows - lag)
     done_new = rows + n if final else max(0, rows + n - lag)
     return done_old, done_new - done_old, rows + n - done_new
+
+
+# the size query of each push's workspace, by the public name of the push (its C entry is 'sf_' + that name)
+_TRACK_WORKSPACE_ENTRY = {'track_stream_push': 'sf_track_stream_workspace_bytes', 'track_stream_push_gated': 'sf_track_stream_gated_workspace_bytes',
+                          'track_pool_push': 'sf_track_pool_workspace_bytes', 'track_pool_push_gated': 'sf_track_pool_gated_workspace_bytes'}
+
+
+def _track_push_call(who: str, state, head: tuple, logits: torch.Tensor, gate_logits: Optional[torch.Tensor], lam: float, mu: float,
+                     grid: Optional[torch.Tensor], final: tuple, k: int, m: int, n_z: int, post: Optional[torch.Tensor] = None) -> tuple:
+    """What the four pushes share (gate_logits None: the plain chain): the input rules - logits fp32 (n, C), gate_logits fp32 (n, 2), on the state's device with unit
+    column stride, with the posterior a contiguous fp32 grid (C,) - then the outputs of a push of n rows that commits k windows and leaves m in the tail (the sync
+    fields for a gated state only, the posterior fields - log_z with n_z entries - with the posterior only: the others stay None), the workspace and the call of the
+    C entry with `head`, the inputs, the costs, the grid, `final` and the outputs -> the outputs in TrackGatedStreamOut's field order (without w0).  Straight-line on
+    purpose: a one-row push is bound by this function, not by its kernels."""
+    C, dev, gated, posterior = state.C, state.buf.device, gate_logits is not None, state.posterior
+    n = logits.shape[0]
+    assert n == 0 or (logits.device == dev and logits.stride(1) == 1 and (not gated or (gate_logits.device == dev and gate_logits.stride(1) == 1))), \
+        'logits, gate_logits: on the state\'s device, unit column stride'
+    if posterior:
+        assert grid is not None and grid.dtype == torch.float32 and grid.device == dev and grid.shape == (C,) and grid.is_contiguous(), f'a grid for {C} classes'
+    i32 = dict(device=dev, dtype=torch.int32)
+    f32 = dict(device=dev, dtype=torch.float32)
+    cls_raw, conf_raw = torch.empty(n, **i32), torch.empty(n, **f32)
+    cls_lag, conf_lag = torch.empty(k, **i32), torch.empty(k, **f32)
+    cls_tail, conf_tail = torch.empty(m, **i32), torch.empty(m, **f32)
+    sync_raw = sync_lag = sync_tail = p_sync = cls_post = conf_post = mean = log_z = None
+    if gated:
+        sync_raw, sync_lag, sync_tail = torch.empty(n, **f32), torch.empty(k, **i32), torch.empty(m, **i32)
+    assert post is None or posterior, 'post: only with the posterior'
+    if posterior:
+        if post is None:
+            post = torch.empty(k, C, **f32)
+        assert post.dtype == torch.float32 and post.shape == (k, C) and post.device == dev and (k == 0 or post.stride(1) == 1), f'post: fp32 ({k}, {C}), unit column stride'
+        cls_post, conf_post, mean = torch.empty(k, **i32), torch.empty(k, **f32), torch.empty(k, **f32)
+        log_z = torch.zeros(n_z, **f32)                                             # (stays 0 for a stream that is still empty: the empty product)
+        if gated:
+            p_sync = torch.empty(k, **f32)
+    lib = _lib.load()
+    ws_entry = _TRACK_WORKSPACE_ENTRY[who]
+    ws_bytes = getattr(lib, ws_entry)(C, n, int(posterior))
+    if ws_bytes < 0:
+        _lib.check(ws_bytes, ws_entry)
+    ws = torch.empty(max(ws_bytes, 16), device=dev, dtype=torch.uint8)
+
+    def ptr(t):
+        return _dev(t, 'out') if t is not None and t.numel() else None
+
+    ldl, g, ldp = _ld(logits) if n else C, _dev(grid, 'grid') if posterior else None, _ld(post) if posterior and k else C
+    if gated:
+        rc = getattr(lib, 'sf_' + who)(
+            *head, ptr(logits), ldl, ptr(gate_logits), _ld(gate_logits) if n else 2, n, float(lam), float(mu), g, *final, ptr(cls_raw), ptr(conf_raw), ptr(sync_raw),
+            ptr(cls_lag), ptr(sync_lag), ptr(conf_lag), ptr(post), ldp, ptr(p_sync), ptr(cls_post), ptr(conf_post), ptr(mean), ptr(cls_tail), ptr(sync_tail), ptr(conf_tail),
+            ptr(log_z), _dev(ws, 'workspace'), _stream())
+    else:
+        rc = getattr(lib, 'sf_' + who)(
+            *head, ptr(logits), ldl, n, float(lam), g, *final, ptr(cls_raw), ptr(conf_raw), ptr(cls_lag), ptr(conf_lag), ptr(post), ldp, ptr(cls_post), ptr(conf_post),
+            ptr(mean), ptr(cls_tail), ptr(conf_tail), ptr(log_z), _dev(ws, 'workspace'), _stream())
+    if rc:
+        _lib.check(rc, 'sf_' + who)
+    return cls_raw, conf_raw, cls_lag, conf_lag, cls_tail, conf_tail, post, cls_post, conf_post, mean, log_z, sync_raw, sync_lag, sync_tail, p_sync
+
+
+def _track_stream_push(who: str, state: TrackStreamState, logits: torch.Tensor, gate_logits: Optional[torch.Tensor], lam: float, mu: float,
+                       grid: Optional[torch.Tensor], final: bool):
+    """track_stream_push (gate_logits None) and track_stream_push_gated: `who` is the public name."""
+    gated = gate_logits is not None
+    _track_kind(state, gated, who)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.shape[1] == state.C, f'{who}: logits {tuple(logits.shape)} for a stream of {state.C} classes'
+    n = logits.shape[0]
+    assert not gated or (gate_logits.dtype == torch.float32 and gate_logits.shape == (n, 2)), f'{who}: gate logits of {tuple(gate_logits.shape)} for {n} rows'
+    if state.closed:
+        raise RuntimeError(f'{who}: the stream was closed by a final push')
+    w0, k, m = track_stream_counts(state.rows, n, state.lag, final)
+    head = (_dev(state.buf, 'state'), state.C, state.lag, int(state.posterior), state.rows)
+    o = _track_push_call(who, state, head, logits, gate_logits, lam, mu, grid, (int(bool(final)),), k, m, 1)
+    state.rows += n
+    state.closed = bool(final)
+    return TrackGatedStreamOut(w0, *o) if gated else TrackStreamOut(w0, *o[:11])
 
 
 def track_stream_push(state: TrackStreamState, logits: torch.Tensor, lam: float, grid: Optional[torch.Tensor] = None, final: bool = False) -> TrackStreamOut:
@@ -788,40 +924,17 @@ def track_stream_push(state: TrackStreamState, logits: torch.Tensor, lam: float,
     w0 + i on the Viterbi path of rows 0 .. w0 + i + lag, never revised), the tail is the path of everything pushed so far on the m = min(lag, rows) windows not yet
     committed (cls_tail[-1]: the current offset).  final=True commits the tail from the whole prefix and closes the state.  The posterior fields are None without
     posterior.  Output sizes are host arithmetic; nothing is read back or synchronised, the state advances on the device in stream order."""
-    _track_kind(state, False, 'track_stream_push')
-    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.shape[1] == state.C, f'logits {tuple(logits.shape)} for a stream of {state.C} classes'
-    if state.closed:
-        raise RuntimeError('track_stream_push: the stream was closed by a final push')
-    n, C, dev = logits.shape[0], state.C, state.buf.device
-    assert n == 0 or (logits.device == dev and logits.stride(1) == 1), 'logits: on the state\'s device, unit column stride'
-    if state.posterior:
-        assert grid is not None and grid.dtype == torch.float32 and grid.device == dev and grid.shape == (C,) and grid.is_contiguous(), f'a grid for {C} classes'
-    w0, k, m = track_stream_counts(state.rows, n, state.lag, final)
-    i32 = dict(device=dev, dtype=torch.int32)
-    f32 = dict(device=dev, dtype=torch.float32)
-    cls_raw, conf_raw = torch.empty(n, **i32), torch.empty(n, **f32)
-    cls_lag, conf_lag = torch.empty(k, **i32), torch.empty(k, **f32)
-    cls_tail, conf_tail = torch.empty(m, **i32), torch.empty(m, **f32)
-    post = cls_post = conf_post = mean = log_z = None
-    if state.posterior:
-        post, cls_post, conf_post, mean = torch.empty(k, C, **f32), torch.empty(k, **i32), torch.empty(k, **f32), torch.empty(k, **f32)
-        log_z = torch.zeros(1, **f32)                                               # (stays 0 while the stream is empty: the empty product)
-    lib = _lib.load()
-    ws_bytes = lib.sf_track_stream_workspace_bytes(C, n, int(state.posterior))
-    if ws_bytes < 0:
-        _lib.check(ws_bytes, 'sf_track_stream_workspace_bytes')
-    ws = torch.empty(max(ws_bytes, 16), device=dev, dtype=torch.uint8)
+    return _track_stream_push('track_stream_push', state, logits, None, lam, 0.0, grid, final)
 
-    def ptr(t):
-        return _dev(t, 'out') if t is not None and t.numel() else None
 
-    rc = lib.sf_track_stream_push(_dev(state.buf, 'state'), C, state.lag, int(state.posterior), state.rows, ptr(logits), _ld(logits) if n else C, n, float(lam),
-                                  _dev(grid, 'grid') if state.posterior else None, int(bool(final)), ptr(cls_raw), ptr(conf_raw), ptr(cls_lag), ptr(conf_lag), ptr(post),
-                                  C, ptr(cls_post), ptr(conf_post), ptr(mean), ptr(cls_tail), ptr(conf_tail), ptr(log_z), _dev(ws, 'workspace'), _stream())
-    _lib.check(rc, 'sf_track_stream_push')
-    state.rows += n
-    state.closed = bool(final)
-    return TrackStreamOut(w0, cls_raw, conf_raw, cls_lag, conf_lag, cls_tail, conf_tail, post, cls_post, conf_post, mean, log_z)
+def track_stream_push_gated(state: TrackGatedStreamState, logits: torch.Tensor, gate_logits: torch.Tensor, lam: float, mu: float, grid: Optional[torch.Tensor] = None,
+                            final: bool = False) -> TrackGatedStreamOut:
+    """Gated fixed-lag read-out of the next n rows of a stream (sf_track_stream_push_gated, DESIGN 3.21): logits fp32 (n, C) and gate_logits fp32 (n, 2) of the same
+    windows, on the state's device with unit column stride (n = 0 allowed) -> TrackGatedStreamOut: TrackStreamOut's fields read from the chain over (offset class,
+    synchronizable flag) - (cls_lag[i], sync_lag[i]) is window w0 + i on ops.track_decode_gated's path of rows 0 .. w0 + i + lag, post_lag / p_sync_lag[i] its row of
+    ops.track_posterior_gated on that prefix - plus sync_raw (n,) fp32, sync_lag (k,) int32, sync_tail (m,) int32 and p_sync_lag (k,) fp32 (None without posterior).
+    Counts, final and the no-read-back rule are track_stream_push's."""
+    return _track_stream_push('track_stream_push_gated', state, logits, gate_logits, lam, mu, grid, final)
 
 
 TRACK_POOL_ROW = 8                       # int64 per descriptor row: slot, rows_done, n, row0, final, commit0, tail0, unused
@@ -851,32 +964,6 @@ def track_pool_plan(rows, counts, lag: int, final, slots=None) -> TrackPoolPlan:
     return TrackPoolPlan(table, row0, commit0, tail0, blocks)
 
 
-class TrackPoolState:
-    """The carried states of a pool of streams (sf_track_pool_push): `buf` uint8 (n_slots, bytes) on the device, slot i the state of one stream
-    (sf_track_stream_push's layout); `rows[i]` the rows pushed into slot i so far and `closed[i]` after its final push (host counts).  `gated`: whether the slots
-    have the gated layout (TrackGatedPoolState)."""
-    gated = False
-
-    def __init__(self, buf: torch.Tensor, C: int, lag: int, posterior: bool):
-        self.buf, self.C, self.lag, self.posterior = buf, int(C), int(lag), bool(posterior)
-        self.n_slots = int(buf.shape[0])
-        self.rows, self.closed = [0] * self.n_slots, [False] * self.n_slots
-
-    def reopen(self, slot: int):
-        """Slot `slot` starts a new stream: only the host count is reset - the device state is read only when rows_done > 0."""
-        self.rows[slot], self.closed[slot] = 0, False
-
-
-def track_pool_state(n_slots: int, C: int, lag: int, posterior: bool, device) -> TrackPoolState:
-    """n_slots fresh stream states in one zeroed (n_slots, sf_track_stream_bytes(C, lag, posterior)) buffer on `device` (the size is a multiple of 16: the stride)."""
-    if n_slots < 1:
-        raise ValueError(f'track_pool_state: n_slots = {n_slots}')
-    nbytes = _lib.load().sf_track_stream_bytes(int(C), int(lag), int(bool(posterior)))
-    if nbytes < 0:
-        _lib.check(nbytes, 'sf_track_stream_bytes')
-    return TrackPoolState(torch.zeros(int(n_slots), nbytes, device=device, dtype=torch.uint8), C, lag, posterior)
-
-
 def _track_pool_table(who: str, state: TrackPoolState, slots, counts, final, total: int):
     """The host rules of a pool push and its descriptor table -> (slots, counts, final as a set, plan, the pinned host table, its device copy): distinct open slots of
     the state, counts that add up to the `total` rows, track_pool_plan, one non-blocking upload from a FRESH pinned tensor (see track_pool_push)."""
@@ -895,6 +982,30 @@ def _track_pool_table(who: str, state: TrackPoolState, slots, counts, final, tot
     return slots, counts, final, plan, host, host.to(state.buf.device, non_blocking=True)
 
 
+def _track_pool_push(who: str, state: TrackPoolState, slots, logits: torch.Tensor, gate_logits: Optional[torch.Tensor], counts, lam: float, mu: float,
+                     grid: Optional[torch.Tensor], final, post: Optional[torch.Tensor]) -> list:
+    """track_pool_push (gate_logits None) and track_pool_push_gated: `who` is the public name."""
+    gated = gate_logits is not None
+    _track_kind(state, gated, who)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.shape[1] == state.C, f'{who}: logits {tuple(logits.shape)} for streams of {state.C} classes'
+    total = logits.shape[0]
+    assert not gated or (gate_logits.dtype == torch.float32 and gate_logits.shape == (total, 2)), f'{who}: gate logits of {tuple(gate_logits.shape)} for {total} rows'
+    slots, counts, final, plan, host, table = _track_pool_table(who, state, slots, counts, final, total)
+    head = (_dev(state.buf, 'states'), state.buf.stride(0), state.n_slots, state.C, state.lag, int(state.posterior), host.data_ptr(), _dev(table, 'table'), len(slots))
+    o = _track_push_call(who, state, head, logits, gate_logits, lam, mu, grid, (), plan.total_commit, plan.total_tail, len(slots), post)
+    # one result per slot: views into the packed outputs (one split per field, not one slice per slot and field); the fields' sizes in TrackGatedStreamOut's order
+    ns, ks, ms = counts, [b[1] for b in plan.blocks], [b[2] for b in plan.blocks]
+    sizes = (ns, ns, ks, ks, ms, ms, ks, ks, ks, ks, 1, ns, ks, ms, ks)
+    none = [None] * len(slots)
+    out, width = (TrackGatedStreamOut, 15) if gated else (TrackStreamOut, 11)
+    fields = [none if t is None else t.split(size) for t, size in zip(o[:width], sizes)]
+    outs = [out(b[0], *views) for b, views in zip(plan.blocks, zip(*fields))]
+    for slot, n in zip(slots, ns):
+        state.rows[slot] += n
+        state.closed[slot] = slot in final
+    return outs
+
+
 def track_pool_push(state: TrackPoolState, slots, logits: torch.Tensor, counts, lam: float, grid: Optional[torch.Tensor] = None, final=(),
                     post: Optional[torch.Tensor] = None) -> list:
     """One push for many streams (sf_track_pool_push): logits fp32 (total, C) on the state's device with unit column stride, the new rows of all named streams
@@ -904,145 +1015,7 @@ def track_pool_push(state: TrackPoolState, slots, logits: torch.Tensor, counts, 
     with one non-blocking copy on the current stream: no buffer is shared between two pushes, so a later push cannot race the upload (torch's pinned-memory
     allocator keeps the block until the copy has run).  Nothing is read back or synchronised.  `post` (posterior only), if given, is written instead of a fresh
     tensor: fp32 (total_commit, C) - track_pool_plan's count - with unit column stride and any row stride >= C."""
-    _track_kind(state, False, 'track_pool_push')
-    C, dev = state.C, state.buf.device
-    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.shape[1] == C, f'logits {tuple(logits.shape)} for streams of {C} classes'
-    total = logits.shape[0]
-    slots, counts, final, plan, host, table = _track_pool_table('track_pool_push', state, slots, counts, final, total)
-    assert total == 0 or (logits.device == dev and logits.stride(1) == 1), 'logits: on the state\'s device, unit column stride'
-    if state.posterior:
-        assert grid is not None and grid.dtype == torch.float32 and grid.device == dev and grid.shape == (C,) and grid.is_contiguous(), f'a grid for {C} classes'
-    K, M, n_act = plan.total_commit, plan.total_tail, len(slots)
-    i32 = dict(device=dev, dtype=torch.int32)
-    f32 = dict(device=dev, dtype=torch.float32)
-    cls_raw, conf_raw = torch.empty(total, **i32), torch.empty(total, **f32)
-    cls_lag, conf_lag = torch.empty(K, **i32), torch.empty(K, **f32)
-    cls_tail, conf_tail = torch.empty(M, **i32), torch.empty(M, **f32)
-    assert post is None or state.posterior, 'post: only with the posterior'
-    cls_post = conf_post = mean = log_z = None
-    if state.posterior:
-        if post is None:
-            post = torch.empty(K, C, **f32)
-        assert post.dtype == torch.float32 and post.shape == (K, C) and post.device == dev and (K == 0 or post.stride(1) == 1), f'post: fp32 ({K}, {C}), unit column stride'
-        cls_post, conf_post, mean = torch.empty(K, **i32), torch.empty(K, **f32), torch.empty(K, **f32)
-        log_z = torch.zeros(n_act, **f32)                                           # (stays 0 for a stream that is still empty: the empty product)
-    lib = _lib.load()
-    ws_bytes = lib.sf_track_pool_workspace_bytes(C, total, int(state.posterior))
-    if ws_bytes < 0:
-        _lib.check(ws_bytes, 'sf_track_pool_workspace_bytes')
-    ws = torch.empty(max(ws_bytes, 16), device=dev, dtype=torch.uint8)
-
-    def ptr(t):
-        return _dev(t, 'out') if t is not None and t.numel() else None
-
-    rc = lib.sf_track_pool_push(_dev(state.buf, 'states'), state.buf.stride(0), state.n_slots, C, state.lag, int(state.posterior), host.data_ptr(), _dev(table, 'table'),
-                                n_act, ptr(logits), _ld(logits) if total else C, total, float(lam), _dev(grid, 'grid') if state.posterior else None, ptr(cls_raw),
-                                ptr(conf_raw), ptr(cls_lag), ptr(conf_lag), ptr(post), _ld(post) if state.posterior and K else C, ptr(cls_post), ptr(conf_post), ptr(mean),
-                                ptr(cls_tail), ptr(conf_tail), ptr(log_z), _dev(ws, 'workspace'), _stream())
-    _lib.check(rc, 'sf_track_pool_push')
-    # one TrackStreamOut per slot: views into the packed outputs (one split per field, not one slice per slot and field)
-    ns, ks, ms = counts, [b[1] for b in plan.blocks], [b[2] for b in plan.blocks]
-    none = [None] * n_act
-    fields = [cls_raw.split(ns), conf_raw.split(ns), cls_lag.split(ks), conf_lag.split(ks), cls_tail.split(ms), conf_tail.split(ms)]
-    fields += [post.split(ks), cls_post.split(ks), conf_post.split(ks), mean.split(ks), log_z.split(1)] if state.posterior else [none] * 5
-    outs = [TrackStreamOut(b[0], *views) for b, views in zip(plan.blocks, zip(*fields))]
-    for slot, n in zip(slots, ns):
-        state.rows[slot] += n
-        state.closed[slot] = slot in final
-    return outs
-
-
-class TrackGatedStreamState(TrackStreamState):
-    """The carried state of one stream's GATED fixed-lag read-out (sf_track_stream_push_gated, DESIGN 3.21): TrackStreamState's fields over a buffer of
-    sf_track_stream_gated_bytes(C, lag, posterior) bytes, 2C wide.  track_stream_push refuses it, track_stream_push_gated refuses a TrackStreamState."""
-    gated = True
-
-
-class TrackGatedPoolState(TrackPoolState):
-    """The carried states of a pool of GATED streams (sf_track_pool_push_gated): TrackPoolState's fields, each slot a gated state."""
-    gated = True
-
-
-
-def _track_kind(state, gated: bool, who: str):
-    """A state knows whether it is gated; a push of the other kind raises."""
-    if bool(getattr(state, 'gated', False)) != gated:
-        raise TypeError(f'{who}: the state is {"gated (use the *_gated push)" if not gated else "not gated (use the push without _gated)"}: the two layouts differ')
-
-
-def _gated_stream_bytes(C: int, lag: int, posterior: bool) -> int:
-    nbytes = _lib.load().sf_track_stream_gated_bytes(int(C), int(lag), int(bool(posterior)))
-    if nbytes < 0:
-        _lib.check(nbytes, 'sf_track_stream_gated_bytes')
-    return nbytes
-
-
-def track_stream_state_gated(C: int, lag: int, posterior: bool, device) -> TrackGatedStreamState:
-    """A fresh gated stream state for C classes (2 .. 32) and a decision lag of `lag` windows (0 .. 255): sf_track_stream_gated_bytes(C, lag, posterior) zeroed bytes."""
-    return TrackGatedStreamState(torch.zeros(_gated_stream_bytes(C, lag, posterior), device=device, dtype=torch.uint8), C, lag, posterior)
-
-
-def track_pool_state_gated(n_slots: int, C: int, lag: int, posterior: bool, device) -> TrackGatedPoolState:
-    """n_slots fresh gated stream states in one zeroed (n_slots, sf_track_stream_gated_bytes(C, lag, posterior)) buffer on `device`."""
-    if n_slots < 1:
-        raise ValueError(f'track_pool_state_gated: n_slots = {n_slots}')
-    return TrackGatedPoolState(torch.zeros(int(n_slots), _gated_stream_bytes(C, lag, posterior), device=device, dtype=torch.uint8), C, lag, posterior)
-
-
-TrackGatedStreamOut = namedtuple('TrackGatedStreamOut', TrackStreamOut._fields + ('sync_raw', 'sync_lag', 'sync_tail', 'p_sync_lag'))
-
-
-def _gated_push_inputs(who: str, C: int, dev, posterior: bool, logits: torch.Tensor, gate_logits: torch.Tensor, grid: Optional[torch.Tensor]) -> int:
-    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.shape[1] == C, f'{who}: logits {tuple(logits.shape)} for streams of {C} classes'
-    n = logits.shape[0]
-    assert gate_logits.dtype == torch.float32 and gate_logits.shape == (n, 2), f'{who}: gate logits of {tuple(gate_logits.shape)} for {n} rows'
-    assert n == 0 or (logits.device == dev and gate_logits.device == dev and logits.stride(1) == 1 and gate_logits.stride(1) == 1), \
-        'logits, gate_logits: on the state\'s device, unit column stride'
-    if posterior:
-        assert grid is not None and grid.dtype == torch.float32 and grid.device == dev and grid.shape == (C,) and grid.is_contiguous(), f'a grid for {C} classes'
-    return n
-
-
-def track_stream_push_gated(state: TrackGatedStreamState, logits: torch.Tensor, gate_logits: torch.Tensor, lam: float, mu: float, grid: Optional[torch.Tensor] = None,
-                            final: bool = False) -> TrackGatedStreamOut:
-    """Gated fixed-lag read-out of the next n rows of a stream (sf_track_stream_push_gated, DESIGN 3.21): logits fp32 (n, C) and gate_logits fp32 (n, 2) of the same
-    windows, on the state's device with unit column stride (n = 0 allowed) -> TrackGatedStreamOut: TrackStreamOut's fields read from the chain over (offset class,
-    synchronizable flag) - (cls_lag[i], sync_lag[i]) is window w0 + i on ops.track_decode_gated's path of rows 0 .. w0 + i + lag, post_lag / p_sync_lag[i] its row of
-    ops.track_posterior_gated on that prefix - plus sync_raw (n,) fp32, sync_lag (k,) int32, sync_tail (m,) int32 and p_sync_lag (k,) fp32 (None without posterior).
-    Counts, final and the no-read-back rule are track_stream_push's."""
-    _track_kind(state, True, 'track_stream_push_gated')
-    if state.closed:
-        raise RuntimeError('track_stream_push_gated: the stream was closed by a final push')
-    C, dev = state.C, state.buf.device
-    n = _gated_push_inputs('track_stream_push_gated', C, dev, state.posterior, logits, gate_logits, grid)
-    w0, k, m = track_stream_counts(state.rows, n, state.lag, final)
-    i32 = dict(device=dev, dtype=torch.int32)
-    f32 = dict(device=dev, dtype=torch.float32)
-    cls_raw, conf_raw, sync_raw = torch.empty(n, **i32), torch.empty(n, **f32), torch.empty(n, **f32)
-    cls_lag, sync_lag, conf_lag = torch.empty(k, **i32), torch.empty(k, **i32), torch.empty(k, **f32)
-    cls_tail, sync_tail, conf_tail = torch.empty(m, **i32), torch.empty(m, **i32), torch.empty(m, **f32)
-    post = p_sync = cls_post = conf_post = mean = log_z = None
-    if state.posterior:
-        post, p_sync, cls_post = torch.empty(k, C, **f32), torch.empty(k, **f32), torch.empty(k, **i32)
-        conf_post, mean = torch.empty(k, **f32), torch.empty(k, **f32)
-        log_z = torch.zeros(1, **f32)                                               # (stays 0 while the stream is empty: the empty product)
-    lib = _lib.load()
-    ws_bytes = lib.sf_track_stream_gated_workspace_bytes(C, n, int(state.posterior))
-    if ws_bytes < 0:
-        _lib.check(ws_bytes, 'sf_track_stream_gated_workspace_bytes')
-    ws = torch.empty(max(ws_bytes, 16), device=dev, dtype=torch.uint8)
-
-    def ptr(t):
-        return _dev(t, 'out') if t is not None and t.numel() else None
-
-    rc = lib.sf_track_stream_push_gated(_dev(state.buf, 'state'), C, state.lag, int(state.posterior), state.rows, ptr(logits), _ld(logits) if n else C, ptr(gate_logits),
-                                        _ld(gate_logits) if n else 2, n, float(lam), float(mu), _dev(grid, 'grid') if state.posterior else None, int(bool(final)),
-                                        ptr(cls_raw), ptr(conf_raw), ptr(sync_raw), ptr(cls_lag), ptr(sync_lag), ptr(conf_lag), ptr(post), C, ptr(p_sync), ptr(cls_post),
-                                        ptr(conf_post), ptr(mean), ptr(cls_tail), ptr(sync_tail), ptr(conf_tail), ptr(log_z), _dev(ws, 'workspace'), _stream())
-    _lib.check(rc, 'sf_track_stream_push_gated')
-    state.rows += n
-    state.closed = bool(final)
-    return TrackGatedStreamOut(w0, cls_raw, conf_raw, cls_lag, conf_lag, cls_tail, conf_tail, post, cls_post, conf_post, mean, log_z, sync_raw, sync_lag, sync_tail, p_sync)
+    return _track_pool_push('track_pool_push', state, slots, logits, None, counts, lam, 0.0, grid, final, post)
 
 
 def track_pool_push_gated(state: TrackGatedPoolState, slots, logits: torch.Tensor, gate_logits: torch.Tensor, counts, lam: float, mu: float,
@@ -1050,49 +1023,7 @@ def track_pool_push_gated(state: TrackGatedPoolState, slots, logits: torch.Tenso
     """One gated push for many streams (sf_track_pool_push_gated): track_pool_push's arguments plus gate_logits fp32 (total, 2), packed like logits (the gate rows of a
     stream are the rows of its offset logits), and mu -> one TrackGatedStreamOut per slot, views into the packed outputs, each equal bit for bit to
     track_stream_push_gated on that stream alone.  The table, its upload and every host rule are track_pool_push's."""
-    _track_kind(state, True, 'track_pool_push_gated')
-    C, dev = state.C, state.buf.device
-    total = _gated_push_inputs('track_pool_push_gated', C, dev, state.posterior, logits, gate_logits, grid)
-    slots, counts, final, plan, host, table = _track_pool_table('track_pool_push_gated', state, slots, counts, final, total)
-    K, M, n_act = plan.total_commit, plan.total_tail, len(slots)
-    i32 = dict(device=dev, dtype=torch.int32)
-    f32 = dict(device=dev, dtype=torch.float32)
-    cls_raw, conf_raw, sync_raw = torch.empty(total, **i32), torch.empty(total, **f32), torch.empty(total, **f32)
-    cls_lag, sync_lag, conf_lag = torch.empty(K, **i32), torch.empty(K, **i32), torch.empty(K, **f32)
-    cls_tail, sync_tail, conf_tail = torch.empty(M, **i32), torch.empty(M, **i32), torch.empty(M, **f32)
-    assert post is None or state.posterior, 'post: only with the posterior'
-    p_sync = cls_post = conf_post = mean = log_z = None
-    if state.posterior:
-        if post is None:
-            post = torch.empty(K, C, **f32)
-        assert post.dtype == torch.float32 and post.shape == (K, C) and post.device == dev and (K == 0 or post.stride(1) == 1), f'post: fp32 ({K}, {C}), unit column stride'
-        p_sync, cls_post, conf_post, mean = torch.empty(K, **f32), torch.empty(K, **i32), torch.empty(K, **f32), torch.empty(K, **f32)
-        log_z = torch.zeros(n_act, **f32)                                           # (stays 0 for a stream that is still empty: the empty product)
-    lib = _lib.load()
-    ws_bytes = lib.sf_track_pool_gated_workspace_bytes(C, total, int(state.posterior))
-    if ws_bytes < 0:
-        _lib.check(ws_bytes, 'sf_track_pool_gated_workspace_bytes')
-    ws = torch.empty(max(ws_bytes, 16), device=dev, dtype=torch.uint8)
-
-    def ptr(t):
-        return _dev(t, 'out') if t is not None and t.numel() else None
-
-    rc = lib.sf_track_pool_push_gated(_dev(state.buf, 'states'), state.buf.stride(0), state.n_slots, C, state.lag, int(state.posterior), host.data_ptr(),
-                                      _dev(table, 'table'), n_act, ptr(logits), _ld(logits) if total else C, ptr(gate_logits), _ld(gate_logits) if total else 2, total,
-                                      float(lam), float(mu), _dev(grid, 'grid') if state.posterior else None, ptr(cls_raw), ptr(conf_raw), ptr(sync_raw), ptr(cls_lag),
-                                      ptr(sync_lag), ptr(conf_lag), ptr(post), _ld(post) if state.posterior and K else C, ptr(p_sync), ptr(cls_post), ptr(conf_post),
-                                      ptr(mean), ptr(cls_tail), ptr(sync_tail), ptr(conf_tail), ptr(log_z), _dev(ws, 'workspace'), _stream())
-    _lib.check(rc, 'sf_track_pool_push_gated')
-    ns, ks, ms = counts, [b[1] for b in plan.blocks], [b[2] for b in plan.blocks]
-    none = [None] * n_act
-    fields = [cls_raw.split(ns), conf_raw.split(ns), cls_lag.split(ks), conf_lag.split(ks), cls_tail.split(ms), conf_tail.split(ms)]
-    fields += [post.split(ks), cls_post.split(ks), conf_post.split(ks), mean.split(ks), log_z.split(1)] if state.posterior else [none] * 5
-    fields += [sync_raw.split(ns), sync_lag.split(ks), sync_tail.split(ms), p_sync.split(ks) if state.posterior else none]
-    outs = [TrackGatedStreamOut(b[0], *views) for b, views in zip(plan.blocks, zip(*fields))]
-    for slot, n in zip(slots, ns):
-        state.rows[slot] += n
-        state.closed[slot] = slot in final
-    return outs
+    return _track_pool_push('track_pool_push_gated', state, slots, logits, gate_logits, counts, lam, mu, grid, final, post)
 
 
 def _ingest_tables(frame_table: torch.Tensor, **tables):

@@ -111,3 +111,21 @@ def test_bad_arguments_are_rejected_without_a_device():
     assert ops.track_stream_counts(0, 5, 16) == (0, 0, 5) and ops.track_stream_counts(5, 20, 16) == (0, 9, 16) and ops.track_stream_counts(25, 0, 16, True) == (9, 16, 0)
     for rows, n, lag, final in ((0, 0, 3, False), (0, 1, 0, False), (7, 3, 3, False), (2, 9, 3, True), (40, 0, 255, True)):
         assert ops.track_stream_counts(rows, n, lag, final) == TS.counts(rows, n, lag, final)
+
+
+def test_pinned_digest_inputs():
+    """tests/golden/track_stream_digests.json (the bytes tests/test_track_pinned_gpu.py holds the read-outs to) against its generator, without a GPU: the recorded case
+    set is the generator's, every case's inputs - drawn on the CPU under fixed seeds - still hash to what was recorded, and the chunk pattern has the pushes it must
+    have: 0 rows on the empty stream, the first row alone, a push below the lag, one equal to it, one above it, 0 rows in mid-stream, and rows left for the rest."""
+    import json
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden'))
+    import make_track_stream_digests as TD
+    with open(TD.OUT) as f:
+        rec = json.load(f)
+    assert len(rec['recorded_from']) == 40 and set(rec['cases']) == set(TD.CASES)
+    for name in TD.CASES:
+        assert TD.input_digest(name) == rec['cases'][name]['input'], f'{name}: the generated INPUT differs from the recorded one'
+    for lag in (0, 1, 16, 255):
+        c = TD.chunks(lag)
+        assert c[:2] == (0, 1) and c[2] <= lag // 2 and c[3] == lag and c[4] > lag and c[5] == 0 and c[6] is None
+        assert TD.n_rows(lag) >= 300 and TD.n_rows(lag) - sum(c[:6]) >= 20
