@@ -29,7 +29,8 @@ extern "C" {
 enum { SF_F32 = 0, SF_BF16 = 1, SF_F16 = 2, SF_U8 = 3, SF_I16 = 4, SF_I32 = 5 };   /* element types (SF_I16: PCM input of sf_resample_wave / _mix only; SF_I32: of sf_resample_wave_mix only) */
 enum { SF_EPI_NONE = 0, SF_EPI_GELU = 1 };                  /* GEMM epilogue activation */
 
-/* 25, with two purely additive entries since: sf_ingest_video_v210, sf_ingest_video_v210_fields; nothing that existed at 25 changed */
+/* 25, with purely additive entries since (additions under v25): sf_ingest_video_v210, sf_ingest_video_v210_fields; sf_track_pairwise,
+ * sf_track_pairwise_gated; nothing that existed at 25 changed */
 #define SF_ABI_VERSION 25
 int sf_abi_version(void);
 const char* sf_last_error(void);
@@ -620,6 +621,27 @@ int sf_track_decode_gated(const float* logits, int64_t ldl, const float* gate_lo
                           float* sync_raw, int32_t* cls_path, int32_t* sync_path, float* conf_path, uint8_t* backptr, void* stream);
 int sf_track_posterior_gated(const float* logits, int64_t ldl, const float* gate_logits, int64_t ldg, int W, int C, float lam, float mu, const float* grid, float* post,
                              int64_t ldp, float* p_sync, int32_t* cls_post, float* conf_post, float* offset_mean, float* log_z, float* workspace, void* stream);
+
+/* Pairwise marginals of neighbouring windows (additions under ABI v25): the joint of (c_w, c_{w+1}) under the chains of sf_track_posterior /
+ * sf_track_posterior_gated, given all windows.  With a, b, e as sf_track_posterior defines them, per boundary w = 0 .. W - 2:
+ *     t[p, c]      = a_w[p] - lam |p - c| + e[w+1, c] + b_{w+1}[c]
+ *     xi[w, p, c]  = exp(t[p, c] - lse_{p,c} t)       (W - 1, C, C) fp32 contiguous, or NULL: not stored.  Sums to 1; its row sums are post[w], its column sums post[w+1]
+ *     p_change[w]  = sum_{p != c} xi[w, p, c]          summed directly, not 1 - the diagonal: a small value keeps its digits
+ *     jump_abs[w]  = sum xi[w, p, c] |p - c|           the expected class step; sum_w jump_abs = - d log_z / d lam
+ *     (top_from[w], top_to[w]) = the off-diagonal pair of largest xi, p_top[w] its mass; ties take the lowest p, then the lowest c: no off-diagonal mass gives (0, 1, 0.0)
+ *     log_z[0]     as sf_track_posterior writes it (bit for bit: the same scan)
+ * sf_track_pairwise_gated: the pair is over the states (p, m') -> (c, m) with E[w+1, c, m] for e and -lam |p - c| - mu [m' != m] for the transition; the outputs above
+ * come from the pair marginal with both flags summed out (xi is the (C, C) class-pair marginal), p_flip[w] = the mass with m' != m; sum_w p_flip = - d log_z / d mu.
+ * A pair with a masked (-inf) end is exactly 0 (plain chain; the gated chain does not serve masked classes).  NaN or +inf input: values unspecified, top_from and top_to
+ * in [0, C) and different.  Limits as the posterior entries: 2 <= C <= 64 (gated: 32), lam and mu finite and >= 0, ldl >= C, ldg >= 2; -1 and a message before anything
+ * is launched otherwise, and for a null pointer (xi excepted; the W - 1 = 0 rows of W == 1 may be null).  W == 0 returns 0 and needs no buffers; W == 1 writes log_z only.
+ * workspace: 2 W C floats (gated: 4 W C), caller-owned.  Two launches on the caller's stream: the scan kernel of the posterior entry, unchanged, then one wavefront per
+ * boundary (four per block; the lane is the destination state, a_w in LDS; fixed-order wave reductions, no atomics: the same bits from call to call).  Nothing is read
+ * back, allocated or synchronised. */
+int sf_track_pairwise(const float* logits, int64_t ldl, int W, int C, float lam, float* p_change, float* jump_abs, int32_t* top_from, int32_t* top_to, float* p_top,
+                      float* xi, float* log_z, float* workspace, void* stream);
+int sf_track_pairwise_gated(const float* logits, int64_t ldl, const float* gate_logits, int64_t ldg, int W, int C, float lam, float mu, float* p_change,
+                            float* jump_abs, float* p_flip, int32_t* top_from, int32_t* top_to, float* p_top, float* xi, float* log_z, float* workspace, void* stream);
 
 /* The gated read-outs of a STREAM at a fixed lag (ABI v25): sf_track_stream_push and sf_track_pool_push with the chain over (offset class, synchronizable
  * flag) of sf_track_decode_gated / sf_track_posterior_gated.  Rows (l_t, z_t) arrive in order: l_t the offset logits (C), z_t the gate logits (2) of the start-aligned

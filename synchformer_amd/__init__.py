@@ -9,9 +9,9 @@ from .model import (AST, AVCLIP, DoNothingBridge, GlobalTransformer, GlobalTrans
 __all__ = ['Synchformer', 'AVCLIP', 'MotionFormer', 'AST', 'GlobalTransformer', 'GlobalTransformerWithSyncabilityHead',
            'RandInitPositionalEncoding', 'DoNothingBridge', 'instantiate_from_config', 'get_obj_from_str',
            'install_reference_aliases', 'uninstall_reference_aliases', 'sync_yaml_model_config', 'avclip_yaml_model_config',
-           'OffsetTracker', 'OffsetTrack', 'OffsetStreamPool', 'RecordingIngest']
+           'OffsetTracker', 'OffsetTrack', 'OffsetStreamPool', 'RecordingIngest', 'fit_smoothness', 'SmoothnessFit']
 
 from . import ops as _ops  # noqa: E402
 _ops.register_torch_ops()      # torch.ops.synchformer.* (dispatcher-visible leaf ops)
-from .track import OffsetStreamPool, OffsetTrack, OffsetTracker  # noqa: E402,F401  (recording-level read-out: DESIGN 3.10; a pool of live feeds: 3.16)
+from .track import OffsetStreamPool, OffsetTrack, OffsetTracker, SmoothnessFit, fit_smoothness  # noqa: E402,F401  (recording-level read-out: DESIGN 3.10; a pool of live feeds: 3.16; the fit of lam / mu: 3.23)
 from .ingest import RecordingIngest  # noqa: E402,F401  (recordings at their native frame rate, size and sample rate: DESIGN 3.11)

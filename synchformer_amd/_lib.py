@@ -98,6 +98,8 @@ SIGNATURES = {
     'sf_track_posterior': [_ptr, _i64, _i32, _i32, _f32, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
     'sf_track_decode_gated': [_ptr, _i64, _ptr, _i64, _i32, _i32, _f32, _f32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
     'sf_track_posterior_gated': [_ptr, _i64, _ptr, _i64, _i32, _i32, _f32, _f32, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
+    'sf_track_pairwise': [_ptr, _i64, _i32, _i32, _f32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
+    'sf_track_pairwise_gated': [_ptr, _i64, _ptr, _i64, _i32, _i32, _f32, _f32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
     'sf_track_stream_bytes': [_i32, _i32, _i32],
     'sf_track_stream_workspace_bytes': [_i32, _i32, _i32],
     'sf_track_stream_push': [_ptr, _i32, _i32, _i32, _i64, _ptr, _i64, _i32, _f32, _ptr, _i32, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],

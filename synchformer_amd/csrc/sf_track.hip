@@ -17,6 +17,8 @@
 //   2. track_fb_combine_kernel:  one thread per window: post = softmax_c (a + b), its argmax and value, the posterior mean of the grid.
 //
 // sf_track_decode_gated / sf_track_posterior_gated (next) are the two offline read-outs of one chain over (offset class, synchronizable flag), fed by a second head.
+// sf_track_pairwise / sf_track_pairwise_gated (after them) combine the two scans across a boundary: the joint marginal of neighbouring windows, its off-diagonal mass
+// (the probability that the offset changed there) and the expected class step - what a fit of lam / mu needs.
 // The last section reads either chain out of live feeds at a fixed lag with carried state, and is written ONCE: a chain is a small policy struct (TrackChainPlain over
 // the C offset classes, TrackChainGated over the 2C states) that says what a lane, a row's inputs, a step and a ring are, around the step functions of the offline
 // kernels; the rows struct, the state layout, the scan / read-out / keep bodies, the three stream and three pool kernels and the two launchers are templates on it.
@@ -308,11 +310,12 @@ __device__ __forceinline__ int track_wave_end_state(float s, bool live) {
 __device__ __forceinline__ float gate_softplus(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
 
 // What a lane of the gated scans is: its state's plane m and class c, its partner's lane.  Idle lanes (j >= 2C) act as state 0 and are their own partner.
+// lane: the thread's lane in its wavefront - threadIdx.x in the one-wave blocks of the scans.
 struct TrackGatedLane {
   int j, m, c, partner;
   bool live;
-  __device__ __forceinline__ TrackGatedLane(int C) {
-    j = threadIdx.x;
+  __device__ __forceinline__ TrackGatedLane(int C, int lane = threadIdx.x) {
+    j = lane;
     live = j < 2 * C;
     m = (live && j >= C) ? 1 : 0;
     c = live ? j - m * C : 0;
@@ -569,6 +572,198 @@ extern "C" int sf_track_posterior_gated(const float* logits, int64_t ldl, const 
   SF_LAUNCH_CHECK();
   hipLaunchKernelGGL(track_gated_fb_combine_kernel, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, s, (const float*)workspace, W, C, grid, post, ldp, p_sync, cls_post,
                      conf_post, offset_mean);
+  SF_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- pairwise marginals of neighbouring windows (sf_track_pairwise, sf_track_pairwise_gated) --------------------------------------------------------
+// With a, b the scans above (left in the workspace by the unchanged scan kernels) the joint marginal of windows w and w + 1 is
+//     xi_w[p, c] = exp(t[p, c] - lse_{p,c} t),        t[p, c] = a_w[p] - lam |p - c| + e[w+1, c] + b_{w+1}[c]
+// (the constants the scans subtracted per row cancel), over the states (p, m') -> (c, m) with - mu [m' != m] for the gated chain.  One wavefront per boundary, four
+// boundaries per 256-thread block; the lane is the DESTINATION state, a_w lies in the wave's LDS slice (entries beyond C hold -inf and add +0) and is read as a broadcast
+// while the lane walks the predecessors: walk 1 the maximum, walk 2 the sums and the lane's best off-diagonal pair, walk 3 (only with xi) the stores, lane c writing
+// column c of row p.  Every wave reduction is a butterfly in a fixed order; no atomics: the outputs are the same bits from call to call.
+
+// What a lane gathers in walk 2: sum = all of its column, off = the entries with p != c, jump = sum |p - c| x; best / bp = its largest off-diagonal entry, the lowest p
+// on ties (strict `>` in ascending p; a NaN never wins).  bp starts at the lowest p != c, so a column without mass still names an off-diagonal pair.
+struct TrackPairAcc {
+  float sum, off, jump, best;
+  int bp;
+  __device__ __forceinline__ TrackPairAcc(int c) : sum(0.f), off(0.f), jump(0.f), best(0.f), bp(c == 0 ? 1 : 0) {}
+  __device__ __forceinline__ void add(float x, int p, int c) {
+    sum += x;
+    if (p != c) {
+      off += x;
+      jump += x * fabsf((float)(p - c));
+      if (x > best) { best = x; bp = p; }
+    }
+  }
+};
+
+// The wave's best off-diagonal pair from the lanes' candidates (x, p, c): the largest x, then the lowest p, then the lowest c - a total order, so the butterfly leaves
+// the same triple in every lane.  Lanes that hold no column pass x = -1 and never win.
+__device__ __forceinline__ void track_pair_top(float& x, int& p, int& c) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float x2 = __shfl_xor(x, o, 64);
+    const int p2 = __shfl_xor(p, o, 64), c2 = __shfl_xor(c, o, 64);
+    if (x2 > x || (x2 == x && (p2 < p || (p2 == p && c2 < c)))) { x = x2; p = p2; c = c2; }
+  }
+}
+
+// The boundary's scalars, by lane 0 of its wave.  z = the sum over all pairs of exp(t - max t) (>= 1 unless every pair is masked).  Whatever the input held, bp and
+// bc lie in [0, C) and differ: a candidate replaces a lane's first one (the lowest p != c) only through `x > best` with p != c, which neither a NaN nor the +0 of an
+// entry beyond C passes, and the winning lane is one that holds a column (C >= 2 of them pass best >= 0, the others -1).
+__device__ __forceinline__ void track_pair_write(int w, float z, float off, float jump, float best, int bp, int bc, float* __restrict__ p_change,
+                                                 float* __restrict__ jump_abs, int32_t* __restrict__ top_from, int32_t* __restrict__ top_to, float* __restrict__ p_top) {
+  p_change[w] = off / z;
+  jump_abs[w] = jump / z;
+  top_from[w] = bp;
+  top_to[w] = bc;
+  p_top[w] = best / z;
+}
+
+__global__ __launch_bounds__(256) void track_pairwise_kernel(const float* __restrict__ logits, int64_t ldl, const float* __restrict__ ws, int W, int C, float lam,
+                                                             float* __restrict__ p_change, float* __restrict__ jump_abs, int32_t* __restrict__ top_from,
+                                                             int32_t* __restrict__ top_to, float* __restrict__ p_top, float* __restrict__ xi) {
+  __shared__ __attribute__((aligned(16))) float s_a[4][TRACK_MAX_C];
+  const int wv = threadIdx.x >> 6, c = threadIdx.x & 63;
+  const int wb = blockIdx.x * 4 + wv;
+  const bool active = wb < W - 1;                                  // wave-uniform; an idle wave walks the last boundary again and stores nothing
+  const int64_t w = active ? wb : W - 2;
+  const bool live = c < C;
+  const int C4 = (C + 3) & ~3;
+  const float ninf = -INFINITY;
+  float* u = s_a[wv];
+  u[c] = live ? ws[w * C + c] : ninf;                              // a_w
+  const float e = fb_log_softmax(live ? logits[(w + 1) * ldl + c] : ninf);
+  const float d = live ? e + ws[((int64_t)W + w + 1) * C + c] : ninf;   // e[w+1, c] + b_{w+1}[c]
+  __syncthreads();
+  float mx = ninf;
+  for (int p = 0; p < C4; p += 4) {
+    const float4 v = *reinterpret_cast<const float4*>(u + p);
+    mx = fmaxf(mx, v.x - lam * fabsf((float)(p - c)));
+    mx = fmaxf(mx, v.y - lam * fabsf((float)(p + 1 - c)));
+    mx = fmaxf(mx, v.z - lam * fabsf((float)(p + 2 - c)));
+    mx = fmaxf(mx, v.w - lam * fabsf((float)(p + 3 - c)));
+  }
+  const float sub = fb_finite_or_zero(wave_max(mx + d));
+  TrackPairAcc acc(c);
+  for (int p = 0; p < C4; p += 4) {
+    const float4 v = *reinterpret_cast<const float4*>(u + p);
+    acc.add(expf(v.x - lam * fabsf((float)(p - c)) + d - sub), p, c);
+    acc.add(expf(v.y - lam * fabsf((float)(p + 1 - c)) + d - sub), p + 1, c);
+    acc.add(expf(v.z - lam * fabsf((float)(p + 2 - c)) + d - sub), p + 2, c);
+    acc.add(expf(v.w - lam * fabsf((float)(p + 3 - c)) + d - sub), p + 3, c);
+  }
+  const float z = wave_sum(acc.sum), off = wave_sum(acc.off), jump = wave_sum(acc.jump);
+  float best = live ? acc.best : -1.f;
+  int bp = acc.bp, bc = c;
+  track_pair_top(best, bp, bc);
+  if (!active) return;
+  if (c == 0) track_pair_write((int)w, z, off, jump, best, bp, bc, p_change, jump_abs, top_from, top_to, p_top);
+  if (xi && live) {
+    float* out = xi + w * C * C + c;
+    for (int p = 0; p < C; ++p) out[(int64_t)p * C] = expf(u[p] - lam * fabsf((float)(p - c)) + d - sub) / z;
+  }
+}
+
+extern "C" int sf_track_pairwise(const float* logits, int64_t ldl, int W, int C, float lam, float* p_change, float* jump_abs, int32_t* top_from, int32_t* top_to,
+                                 float* p_top, float* xi, float* log_z, float* workspace, void* stream) {
+  SF_CHECK_ARG(W >= 0, "sf_track_pairwise: W = %d windows", W);
+  SF_CHECK_ARG(C >= 2 && C <= TRACK_MAX_C, "sf_track_pairwise: C = %d classes out of range (2 .. %d: one lane per class)", C, TRACK_MAX_C);
+  SF_CHECK_ARG(ldl >= C, "sf_track_pairwise: row stride ldl = %lld below C = %d", (long long)ldl, C);
+  SF_CHECK_ARG(std::isfinite(lam) && lam >= 0.f, "sf_track_pairwise: lam must be finite and >= 0 (the cost of a class change)");
+  if (W == 0) return 0;
+  SF_CHECK_ARG(logits && log_z && workspace && (W == 1 || (p_change && jump_abs && top_from && top_to && p_top)), "sf_track_pairwise: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(track_fb_scan_kernel, dim3(2), dim3(64), 0, s, logits, ldl, W, C, lam, workspace, log_z);
+  SF_LAUNCH_CHECK();
+  if (W == 1) return 0;
+  hipLaunchKernelGGL(track_pairwise_kernel, dim3((unsigned)((W - 1 + 3) / 4)), dim3(256), 0, s, logits, ldl, (const float*)workspace, W, C, lam, p_change, jump_abs,
+                     top_from, top_to, p_top, xi);
+  SF_LAUNCH_CHECK();
+  return 0;
+}
+
+// The same over the 2C states: lane j = (m, c) is the destination state, a_w lies in LDS as two planes of 32 floats.  The lane walks its own plane and the other plane
+// minus mu; y = the two added = the mass of (p, any flag) -> (c, m).  The class pair (p -> c) is y + the partner lane's y (the same bits in both lanes: the sum
+// commutes); the lanes of plane 0 gather the class outputs and store xi, every live lane gathers the mass that changes the flag.
+__global__ __launch_bounds__(256) void track_pairwise_gated_kernel(const float* __restrict__ logits, int64_t ldl, const float* __restrict__ gate, int64_t ldg,
+                                                                   const float* __restrict__ ws, int W, int C, float lam, float mu, float* __restrict__ p_change,
+                                                                   float* __restrict__ jump_abs, float* __restrict__ p_flip, int32_t* __restrict__ top_from,
+                                                                   int32_t* __restrict__ top_to, float* __restrict__ p_top, float* __restrict__ xi) {
+  __shared__ __attribute__((aligned(16))) float s_a[4][64];
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int wb = blockIdx.x * 4 + wv;
+  const bool active = wb < W - 1;                                  // wave-uniform; an idle wave walks the last boundary again and stores nothing
+  const int64_t w = active ? wb : W - 2;
+  const int S = 2 * C;
+  const int C4 = (C + 3) & ~3;
+  const float ninf = -INFINITY;
+  const TrackGatedLane ln(C, lane);
+  const bool live = ln.live;
+  const int m = ln.m, c = ln.c, partner = ln.partner;
+  float* u = s_a[wv];
+  u[lane] = (lane & 31) < C ? ws[w * S + (lane >> 5) * C + (lane & 31)] : ninf;       // a_w: slot (m', p) = m' * 32 + p
+  const float em = track_gated_emission(ln, (live && m) ? logits[(w + 1) * ldl + c] : ninf, gate[(w + 1) * ldg], gate[(w + 1) * ldg + 1], logf((float)C));
+  const float d = live ? em + ws[((int64_t)W + w + 1) * S + lane] : ninf;               // E[w+1, j] + b_{w+1}[j]
+  __syncthreads();
+  const float* own = u + m * 32;
+  const float* oth = u + (1 - m) * 32;
+  float mx = ninf;
+  for (int p = 0; p < C4; p += 4) {
+    const float4 v = *reinterpret_cast<const float4*>(own + p), o = *reinterpret_cast<const float4*>(oth + p);
+    mx = fmaxf(mx, fmaxf(v.x, o.x - mu) - lam * fabsf((float)(p - c)));
+    mx = fmaxf(mx, fmaxf(v.y, o.y - mu) - lam * fabsf((float)(p + 1 - c)));
+    mx = fmaxf(mx, fmaxf(v.z, o.z - mu) - lam * fabsf((float)(p + 2 - c)));
+    mx = fmaxf(mx, fmaxf(v.w, o.w - mu) - lam * fabsf((float)(p + 3 - c)));
+  }
+  const float sub = fb_finite_or_zero(wave_max(mx + d));
+  const bool gathers = live && m == 0;
+  TrackPairAcc acc(c);
+  float flip = 0.f;
+  for (int p = 0; p < C; ++p) {
+    const float pen = lam * fabsf((float)(p - c));
+    const float x_oth = expf(oth[p] - mu - pen + d - sub);
+    const float y = expf(own[p] - pen + d - sub) + x_oth;
+    flip += x_oth;
+    const float yc = y + __shfl(y, partner, 64);
+    if (gathers) acc.add(yc, p, c);
+  }
+  const float z = wave_sum(acc.sum), off = wave_sum(acc.off), jump = wave_sum(acc.jump), flips = wave_sum(flip);
+  float best = gathers ? acc.best : -1.f;
+  int bp = acc.bp, bc = c;
+  track_pair_top(best, bp, bc);
+  if (!active) return;
+  if (lane == 0) {
+    track_pair_write((int)w, z, off, jump, best, bp, bc, p_change, jump_abs, top_from, top_to, p_top);
+    p_flip[w] = flips / z;
+  }
+  if (xi) {                                                        // wave-uniform: every lane takes part in the shuffle, plane 0 stores
+    float* out = xi + w * C * C + c;
+    for (int p = 0; p < C; ++p) {
+      const float pen = lam * fabsf((float)(p - c));
+      const float y = expf(own[p] - pen + d - sub) + expf(oth[p] - mu - pen + d - sub);
+      const float yc = y + __shfl(y, partner, 64);
+      if (gathers) out[(int64_t)p * C] = yc / z;
+    }
+  }
+}
+
+extern "C" int sf_track_pairwise_gated(const float* logits, int64_t ldl, const float* gate_logits, int64_t ldg, int W, int C, float lam, float mu, float* p_change,
+                                       float* jump_abs, float* p_flip, int32_t* top_from, int32_t* top_to, float* p_top, float* xi, float* log_z, float* workspace,
+                                       void* stream) {
+  if (!track_gated_args_ok("sf_track_pairwise_gated", W, C, ldl, ldg, lam, mu)) return -1;
+  if (W == 0) return 0;
+  SF_CHECK_ARG(logits && gate_logits && log_z && workspace && (W == 1 || (p_change && jump_abs && p_flip && top_from && top_to && p_top)),
+               "sf_track_pairwise_gated: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(track_gated_fb_scan_kernel, dim3(2), dim3(64), 0, s, logits, ldl, gate_logits, ldg, W, C, lam, mu, workspace, log_z);
+  SF_LAUNCH_CHECK();
+  if (W == 1) return 0;
+  hipLaunchKernelGGL(track_pairwise_gated_kernel, dim3((unsigned)((W - 1 + 3) / 4)), dim3(256), 0, s, logits, ldl, gate_logits, ldg, (const float*)workspace, W, C, lam,
+                     mu, p_change, jump_abs, p_flip, top_from, top_to, p_top, xi);
   SF_LAUNCH_CHECK();
   return 0;
 }

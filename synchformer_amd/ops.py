@@ -753,6 +753,52 @@ def track_posterior_gated(logits: torch.Tensor, gate_logits: torch.Tensor, lam: 
     return post, p_sync, cls_post, conf_post, offset_mean, log_z
 
 
+def _pairwise_outputs(W: int, C: int, dev, xi: bool, n_float: int):
+    """The outputs the two pairwise read-outs share: n_float fp32 vectors and top_from / top_to int32 of W - 1 rows, xi (W - 1, C, C) or None, log_z (1,)."""
+    n = max(W - 1, 0)
+    floats = [torch.empty(n, device=dev, dtype=torch.float32) for _ in range(n_float)]
+    top_from, top_to = torch.empty(n, device=dev, dtype=torch.int32), torch.empty(n, device=dev, dtype=torch.int32)
+    xi_t = torch.empty(n, C, C, device=dev, dtype=torch.float32) if xi else None
+    log_z = torch.empty(1, device=dev, dtype=torch.float32) if W else torch.zeros(1, device=dev, dtype=torch.float32)
+    return floats, top_from, top_to, xi_t, log_z
+
+
+def track_pairwise(logits: torch.Tensor, lam: float, xi: bool = False):
+    """Pairwise marginals of neighbouring windows (sf_track_pairwise): logits as track_posterior takes them ->
+    (p_change fp32 (W-1,), jump_abs fp32 (W-1,), top_from int32 (W-1,), top_to int32 (W-1,), p_top fp32 (W-1,), xi fp32 (W-1, C, C) or None, log_z fp32 (1,)):
+    per boundary between windows w and w + 1, given all windows, the probability that the class changes, the expected class step |c_{w+1} - c_w|, the likeliest
+    change (from class, to class) with its probability, and with xi=True the whole joint marginal xi[w, p, c] = P(c_w = p, c_{w+1} = c).  log_z is
+    track_posterior's, bit for bit.  Allocates the outputs and the 2 W C floats of workspace; nothing is read back (log_z is 0 for W = 0)."""
+    assert logits.dtype == torch.float32 and logits.dim() == 2
+    W, C = logits.shape
+    assert W == 0 or logits.stride(1) == 1, 'logits: unit column stride'
+    dev = logits.device
+    (p_change, jump_abs, p_top), top_from, top_to, xi_t, log_z = _pairwise_outputs(W, C, dev, xi, 3)
+    ws = torch.empty(2 * max(W, 1) * C, device=dev, dtype=torch.float32)
+    rc = _lib.load().sf_track_pairwise(_dev(logits, 'logits'), _ld(logits) if W else C, W, C, float(lam), _dev(p_change, 'p_change'), _dev(jump_abs, 'jump_abs'),
+                                       _dev(top_from, 'top_from'), _dev(top_to, 'top_to'), _dev(p_top, 'p_top'), _dev(xi_t, 'xi') if xi else None,
+                                       _dev(log_z, 'log_z'), _dev(ws, 'workspace'), _stream())
+    _lib.check(rc, 'sf_track_pairwise')
+    return p_change, jump_abs, top_from, top_to, p_top, xi_t, log_z
+
+
+def track_pairwise_gated(logits: torch.Tensor, gate_logits: torch.Tensor, lam: float, mu: float, xi: bool = False):
+    """Pairwise marginals under the chain over (offset class, synchronizable flag) (sf_track_pairwise_gated): inputs as track_decode_gated ->
+    (p_change, jump_abs, p_flip, top_from, top_to, p_top, xi or None, log_z): track_pairwise's outputs from the pair marginal with both flags summed out, and
+    p_flip fp32 (W-1,), the probability that the flag changes at the boundary.  log_z is track_posterior_gated's, bit for bit.  Allocates the outputs and the
+    4 W C floats of workspace; nothing is read back."""
+    W, C = _gated_inputs(logits, gate_logits)
+    dev = logits.device
+    (p_change, jump_abs, p_flip, p_top), top_from, top_to, xi_t, log_z = _pairwise_outputs(W, C, dev, xi, 4)
+    ws = torch.empty(4 * max(W, 1) * C, device=dev, dtype=torch.float32)
+    rc = _lib.load().sf_track_pairwise_gated(_dev(logits, 'logits'), _ld(logits) if W else C, _dev(gate_logits, 'gate_logits'), _ld(gate_logits) if W else 2, W, C,
+                                             float(lam), float(mu), _dev(p_change, 'p_change'), _dev(jump_abs, 'jump_abs'), _dev(p_flip, 'p_flip'),
+                                             _dev(top_from, 'top_from'), _dev(top_to, 'top_to'), _dev(p_top, 'p_top'), _dev(xi_t, 'xi') if xi else None,
+                                             _dev(log_z, 'log_z'), _dev(ws, 'workspace'), _stream())
+    _lib.check(rc, 'sf_track_pairwise_gated')
+    return p_change, jump_abs, p_flip, top_from, top_to, p_top, xi_t, log_z
+
+
 class TrackStreamState:
     """The carried state of one stream's fixed-lag read-out (sf_track_stream_push): `buf` the opaque device buffer, `rows` the rows pushed so far (host count),
     `closed` after a final push.  Its size does not depend on `rows`.  `gated`: whether the buffer has the gated layout (TrackGatedStreamState)."""

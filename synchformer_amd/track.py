@@ -86,6 +86,33 @@ class OffsetTrack:
     sync_raw = None                  # (W,) fp32: sigmoid(z1 - z0), the gate's own per-window probability
     sync_path = None                 # (W,) int32: the flag along the joint Viterbi path (cls_path is that path's class), 1 = synchronizable
     p_sync = None                    # (W,) fp32: the flag's marginal given all windows (with posterior=True)
+    # the pairwise read-out (OffsetTracker(pairwise=True), ops.track_pairwise / track_pairwise_gated); None without it.  Plain attributes as the gate's:
+    # one row per boundary between windows w and w + 1
+    t_change = None                  # (W-1,) fp32: the boundary's time, half-way between the two window centres
+    p_change = None                  # (W-1,) fp32: the probability, given all windows, that the offset class changes at the boundary
+    jump_abs = None                  # (W-1,) fp32: the expected class step |c_{w+1} - c_w|
+    p_change_top = None              # (W-1,) fp32: the probability of the likeliest change, change_from_sec -> change_to_sec
+    change_from_sec = None           # (W-1,) fp32: grid[top_from]
+    change_to_sec = None             # (W-1,) fp32: grid[top_to]
+    p_flip = None                    # (W-1,) fp32: the probability that the synchronizable flag changes at the boundary (with a gate)
+
+    def changes(self, min_prob: float = 0.5):
+        """Host side (OffsetTracker(pairwise=True)): the boundaries where the offset changed with probability p_change >= min_prob, as a list of
+        (t_sec, from_sec, to_sec, p_change, p_top) in time order - from_sec -> to_sec the likeliest change there, p_top its probability.  Overlapping windows
+        SMEAR a change over neighbouring boundaries (a window that straddles it votes for either side), and each of them can stay under min_prob although the
+        change is certain: expected_changes() does not have that problem, the probability of a change within an interval is not built.  Synchronises."""
+        if self.p_change is None:
+            raise ValueError('OffsetTrack.changes: no pairwise read-out on this track (OffsetTracker(..., pairwise=True))')
+        cols = [x.detach().cpu().double().tolist() for x in (self.t_change, self.change_from_sec, self.change_to_sec, self.p_change, self.p_change_top)]
+        return [row for row in zip(*cols) if row[3] >= min_prob]
+
+    def expected_changes(self) -> float:
+        """Host side (OffsetTracker(pairwise=True)): the expected number of offset changes along the recording, sum_w p_change[w].  A change that overlapping
+        windows smear over neighbouring boundaries, each under changes()'s min_prob, still counts here with its whole mass; the probability of a change
+        within an interval is not built.  Synchronises."""
+        if self.p_change is None:
+            raise ValueError('OffsetTrack.expected_changes: no pairwise read-out on this track (OffsetTracker(..., pairwise=True))')
+        return float(self.p_change.detach().double().sum().item())
 
     def spans(self):
         """Host side: the runs of constant (sync_path, cls_path) as a list of (t0_sec, t1_sec, offset_sec or None), in time order - None where the path says 'not
@@ -118,10 +145,13 @@ class OffsetTracker:
     synchronizable flag), and gate_logits, sync_raw, sync_path, p_sync are filled.  mu: the cost of one change of the flag between neighbouring windows, in logit
     units.  mu = 2.0 is a DEFAULT, NOT A TUNED VALUE, as lam: choose both on held-out recordings of the domain.  A prior on the flag is a constant added to
     gate_logits[:, 1] by the caller.  stream() and pool() read a live feed through the same chain with gated=True (a carried state 2C wide) or, with
-    gated=False, as a tracker without a gate does; on a tracker with a gate the choice is explicit."""
+    gated=False, as a tracker without a gate does; on a tracker with a gate the choice is explicit.
+    pairwise: also read out the boundaries between neighbouring windows (ops.track_pairwise, with a gate ops.track_pairwise_gated; two more launches):
+    fills OffsetTrack.t_change .. change_to_sec (p_flip with a gate) for OffsetTrack.changes() / expected_changes().  fit_smoothness (below) fits lam and mu on
+    labelled recordings."""
 
     def __init__(self, engine, mel, hop_segments: int = 1, lam: float = 1.0, grid: Optional[torch.Tensor] = None, posterior: bool = False, gate=None,
-                 mu: float = 2.0):
+                 mu: float = 2.0, pairwise: bool = False):
         if hop_segments < 1:
             raise ValueError(f'hop_segments = {hop_segments}')
         if not (lam >= 0 and lam != float('inf')):
@@ -144,6 +174,7 @@ class OffsetTracker:
             if not 1 <= gate.n_window <= engine.n_window:
                 raise ValueError(f'gate: its window of {gate.n_window} segments does not fit the offset window of {engine.n_window} it is start-aligned with')
         self.gate, self.mu = gate, float(mu)
+        self.pairwise = bool(pairwise)
 
     def track_features(self, vbank: torch.Tensor, abank: torch.Tensor, win_chunk: int = 256) -> OffsetTrack:
         """Segment feature banks (N, 8, 768) / (N, 6, 768) (engine.extract_recording, or features the caller already holds) -> OffsetTrack."""
@@ -171,6 +202,14 @@ class OffsetTracker:
                                                                                                                                        self.mu, self.grid)
         if self.posterior:
             track.offset_sec_post = self.grid[track.cls_post.long()]
+        if self.pairwise:
+            if gate_logits is None:
+                track.p_change, track.jump_abs, top_from, top_to, track.p_change_top, _, _ = ops.track_pairwise(logits, self.lam)
+            else:
+                track.p_change, track.jump_abs, track.p_flip, top_from, top_to, track.p_change_top, _, _ = ops.track_pairwise_gated(logits, gate_logits, self.lam,
+                                                                                                                                   self.mu)
+            track.t_change = 0.5 * (track.t_sec[:-1] + track.t_sec[1:])
+            track.change_from_sec, track.change_to_sec = self.grid[top_from.long()], self.grid[top_to.long()]
         return track
 
     def track_features_programmes(self, vbank: torch.Tensor, abanks: torch.Tensor, win_chunk: int = 256) -> List[OffsetTrack]:
@@ -665,3 +704,126 @@ class OffsetStreamPool:
             del self.feeds[f.slot]
             self._free.append(f.slot)
         return res
+
+
+# ---- fitting lam and mu on labelled recordings ---------------------------------------------------------------------------------------------------------
+@dataclass
+class SmoothnessFit:
+    """What fit_smoothness found.  J = sum_w |c_{w+1} - c_w| (class steps), F = the number of changes of the synchronizable flag, summed over the recordings."""
+    lam: float
+    mu: Optional[float]              # None for the plain chain
+    lam_at_bound: bool               # the likelihood still rises at 0 or at lam_max: lam is that bound, not a maximum (labels that never change: lam_max)
+    mu_at_bound: bool
+    jumps_observed: float            # J* of the labels
+    jumps_expected: float            # E[J] under the chain at the fit; equal to J* at an interior maximum
+    flips_observed: float            # F* (0 for the plain chain)
+    flips_expected: float
+    log_likelihood: float            # sum_r (score of the labelled path - log_z) at the fit, <= 0
+    se_lam: float                    # 1 / sqrt(-d E[J] / d lam) by a central difference at the fit (the curvature of the log-likelihood along lam); inf when flat
+    se_mu: Optional[float]
+    evaluations: int                 # calls of `stats` per recording
+
+    @property
+    def at_bound(self) -> bool:
+        return self.lam_at_bound or self.mu_at_bound
+
+
+def _device_stats(logits, gate_logits, lam: float, mu: float):
+    """fit_smoothness's default `stats`: the pairwise read-out on the device, summed in float64 on the host."""
+    if gate_logits is None:
+        out = ops.track_pairwise(logits, lam)
+        return float(out[1].double().sum().item()), 0.0, float(out[6].item())
+    out = ops.track_pairwise_gated(logits, gate_logits, lam, mu)
+    return float(out[1].double().sum().item()), float(out[2].double().sum().item()), float(out[7].item())
+
+
+def _host64(x) -> torch.Tensor:
+    return (x.detach().cpu() if isinstance(x, torch.Tensor) else torch.as_tensor(x)).double()
+
+
+def _bisect_decreasing(g, hi: float, iters: int):
+    """The root of a decreasing g on [0, hi] by `iters` halvings -> (x, at_bound): 0 when g(0) <= 0, hi when g(hi) >= 0, both with at_bound."""
+    if g(0.0) <= 0:
+        return 0.0, True
+    if g(hi) >= 0:
+        return float(hi), True
+    lo = 0.0
+    for _ in range(iters):
+        mid = 0.5 * (lo + hi)
+        if g(mid) > 0:
+            lo = mid
+        else:
+            hi = mid
+    return 0.5 * (lo + hi), False
+
+
+def fit_smoothness(recordings, gated: bool = False, lam_max: float = 16.0, mu_max: float = 16.0, iters: int = 30, sweeps: int = 4, stats=None) -> SmoothnessFit:
+    """Fit OffsetTracker's lam (gated: and mu) on labelled recordings by maximum conditional likelihood.
+    recordings: a list of (logits (W, C) fp32, labels (W,) int) - the window logits of a recording (OffsetTrack.logits) and the true class of every window; with
+    gated=True each item is (logits, labels, gate_logits (W, 2), sync_labels (W,) in {0, 1}).  The class label is required in every window: for an in-sync recording
+    whose audio was shifted by a known amount it is known whether or not the window is synchronizable.
+    The chain is a conditional random field, p(path | logits) ~ exp(sum e - lam J - mu F); its log-likelihood sum_r (score of the labels - log_z) is concave in
+    (lam, mu) with the gradient (E[J] - J*, E[F] - F*), and the expectations are the sums of jump_abs / p_flip of the pairwise read-out.  Plain chain: `iters`
+    halvings of [0, lam_max] on E[J] - J*, which decreases in lam.  Gated: `sweeps` rounds of that for lam at fixed mu, then for mu on E[F] - F* at fixed lam
+    (coordinate ascent, from mu = min(2, mu_max)).  A parameter whose gradient does not change sign inside its interval ends at the bound, flagged.
+    stats(logits, gate_logits or None, lam, mu) -> (sum_w jump_abs, sum_w p_flip, log_z): by default ops.track_pairwise(_gated) on the device the logits lie on,
+    summed in float64; anything with the same contract serves (the tests pass a float64 oracle and run this function without a GPU).
+    ValueError for no recordings, mismatched lengths, or labels outside [0, C) / {0, 1}."""
+    stats = _device_stats if stats is None else stats
+    if not (lam_max > 0 and mu_max > 0 and iters >= 1 and sweeps >= 1):
+        raise ValueError(f'fit_smoothness: lam_max = {lam_max}, mu_max = {mu_max}, iters = {iters}, sweeps = {sweeps}')
+    recs, j_obs, f_obs, emit = [], 0.0, 0.0, 0.0
+    for r, item in enumerate(recordings):
+        if len(item) != (4 if gated else 2):
+            raise ValueError(f'fit_smoothness: recording {r} has {len(item)} entries, expected ' + ('(logits, labels, gate_logits, sync_labels)' if gated else '(logits, labels)'))
+        logits, labels = item[0], torch.as_tensor(item[1]).detach().cpu().reshape(-1).long()
+        if len(logits.shape) != 2 or labels.numel() != logits.shape[0]:
+            raise ValueError(f'fit_smoothness: recording {r}: {labels.numel()} labels for logits of {tuple(logits.shape)}')
+        W, C = logits.shape
+        if W and (labels.min() < 0 or labels.max() >= C):
+            raise ValueError(f'fit_smoothness: recording {r}: labels outside [0, {C})')
+        e = torch.log_softmax(_host64(logits), 1)[torch.arange(W), labels]
+        gate_logits = None
+        if gated:
+            gate_logits, sync = item[2], torch.as_tensor(item[3]).detach().cpu().reshape(-1).long()
+            if tuple(gate_logits.shape) != (W, 2) or sync.numel() != W:
+                raise ValueError(f'fit_smoothness: recording {r}: gate logits of {tuple(gate_logits.shape)} and {sync.numel()} sync labels for {W} windows')
+            if W and (sync.min() < 0 or sync.max() > 1):
+                raise ValueError(f'fit_smoothness: recording {r}: sync labels outside {{0, 1}}')
+            z = _host64(gate_logits)
+            d = z[:, 1] - z[:, 0]
+            e = torch.where(sync == 1, torch.nn.functional.logsigmoid(d) + e, torch.nn.functional.logsigmoid(-d) - torch.log(torch.tensor(float(C), dtype=torch.float64)))
+            f_obs += float((sync[1:] - sync[:-1]).abs().sum())
+        j_obs += float((labels[1:] - labels[:-1]).abs().sum())
+        emit += float(e.sum())
+        if W:
+            recs.append((logits, gate_logits))
+    if not recs:
+        raise ValueError('fit_smoothness: no recordings')
+    count = [0]
+
+    def totals(lam: float, mu: float):
+        count[0] += 1
+        out = [stats(l, g, float(lam), float(mu)) for l, g in recs]
+        return tuple(float(sum(o[k] for o in out)) for k in range(3))
+
+    def stderr(which: int, lam: float, mu: float, top: float):
+        x = (lam, mu)[which]
+        h = max(0.02 * x, 0.005)
+        lo, hi = max(x - h, 0.0), min(x + h, top)
+        at = (lambda v: (v, mu)) if which == 0 else (lambda v: (lam, v))
+        slope = (totals(*at(hi))[which] - totals(*at(lo))[which]) / (hi - lo)
+        return float('inf') if not slope < 0 else (-slope) ** -0.5
+
+    mu, mu_bound, se_mu = (min(2.0, float(mu_max)), False, None) if gated else (0.0, False, None)
+    for _ in range(sweeps if gated else 1):
+        lam, lam_bound = _bisect_decreasing(lambda x: totals(x, mu)[0] - j_obs, float(lam_max), iters)
+        if gated:
+            mu, mu_bound = _bisect_decreasing(lambda x: totals(lam, x)[1] - f_obs, float(mu_max), iters)
+    j_exp, f_exp, log_z = totals(lam, mu)
+    se_lam = stderr(0, lam, mu, float(lam_max))
+    if gated:
+        se_mu = stderr(1, lam, mu, float(mu_max))
+    return SmoothnessFit(lam=lam, mu=mu if gated else None, lam_at_bound=lam_bound, mu_at_bound=mu_bound, jumps_observed=j_obs, jumps_expected=j_exp,
+                         flips_observed=f_obs, flips_expected=f_exp, log_likelihood=emit - lam * j_obs - (mu * f_obs if gated else 0.0) - log_z, se_lam=se_lam,
+                         se_mu=se_mu, evaluations=count[0])

@@ -3,7 +3,7 @@ beside the same windows through forward_clips on explicit 120-frame slices.  Pri
 
     python tools/track_recording.py [--seconds 60] [--hop 1] [--seg-chunk 224] [--host] [--clip-windows 8] [--fps 30000/1001 --size 1080x1920 --rate 48000]
                                     [--pix-fmt {rgb24,nv12,yuv420p,p010,yuv420p10le,uyvy422,yuyv422,yuv422p,nv16,yuv422p10le,p210,y210,v210}]
-                                    [--chroma-loc {center,left,topleft}] [--field-order {progressive,tff,bff}] [--posterior]
+                                    [--chroma-loc {center,left,topleft}] [--field-order {progressive,tff,bff}] [--posterior] [--pairwise]
                                     [--stream SECONDS [--lag N]] [--gate [--mu X]]
                                     [--audio-channels N [--audio-interleaved] [--sample-fmt {flt,s16,s32}] --programmes 0+1,2+3,4]
 
@@ -19,6 +19,10 @@ nearest its slot resized on its own, and the line reports the field order, the f
 
 With --posterior the windows are also read out as marginals: the line then carries the mean and minimum of conf_post, log_z per window step
 (log_z / max(W - 1, 1)), the largest |offset_sec_mean - offset_sec_path| and the time of the two extra launches (the read-out alone, on the track's logits).
+
+With --pairwise the boundaries between neighbouring windows are read out too (OffsetTracker(pairwise=True)): the line then carries
+OffsetTrack.expected_changes(), OffsetTrack.changes() (time s, from s, to s, p_change, p_top per boundary with p_change >= 0.5) and the time of the two extra launches
+(ops.track_pairwise alone, on the track's logits); with --gate also the gated track's expected changes of the offset and of the flag.
 
 With --gate a synthetic 2-way syncability engine without towers (184 position rows: windows of 13 segments) reads the same bank and the windows are
 read out over (offset class, synchronizable flag) at --mu: the line then carries, of this same run, the time of the offset windows and of the ungated read-out beside
@@ -71,6 +75,7 @@ def main():
     ap.add_argument('--field-order', choices=['progressive', 'tff', 'bff'], default='progressive',
                     help='interlaced raw frames, top / bottom field first: the field nearest each 25 fps slot is ingested on its own (rgb24, 4:2:2 layouts and v210)')
     ap.add_argument('--posterior', action='store_true', help='also read the windows out as marginals (forward-backward)')
+    ap.add_argument('--pairwise', action='store_true', help='also read out the boundaries between windows: change probabilities, expected number of changes')
     ap.add_argument('--stream', type=float, default=None, metavar='SECONDS', help='also push the recording through OffsetTracker.stream in pieces of this length')
     ap.add_argument('--lag', type=int, default=16, help='decision lag of the stream, in windows')
     ap.add_argument('--gate', action='store_true', help='also gate the track by a synthetic 2-way syncability engine (towers=False) on the same bank')
@@ -134,7 +139,7 @@ def main():
         wave = torch.rand(n, generator=gen) * 2 - 1
         fd, wd = frames.to(dev), wave.to(dev)
         src = (frames.pin_memory(), wave.pin_memory()) if args.host else (fd, wd)
-    tracker = OffsetTracker(eng, mel, hop_segments=args.hop, posterior=args.posterior)
+    tracker = OffsetTracker(eng, mel, hop_segments=args.hop, posterior=args.posterior, pairwise=args.pairwise)
 
     def timed(fn, reps=1):
         fn()
@@ -175,9 +180,13 @@ def main():
                       'log_z_per_step': round(track.log_z.item() / max(W - 1, 1), 4),
                       'max_abs_mean_minus_path_s': round((track.offset_sec_mean - track.offset_sec_path).abs().max().item(), 4),
                       'posterior_s': round(t_post, 6)})
+    if args.pairwise:
+        t_pair, _ = timed(lambda: ops.track_pairwise(track.logits, tracker.lam), reps=20)
+        extra.update({'expected_changes': round(track.expected_changes(), 3), 'changes': [[round(v, 3) for v in row] for row in track.changes()],
+                      'pairwise_s': round(t_pair, 6)})
     if args.gate:
         gate = SynchformerEngine(synth.make_state_dict(4242, head='sync_head', n_pos=184, n_out=2), dev, towers=False)
-        gated = OffsetTracker(eng, mel, hop_segments=args.hop, posterior=args.posterior, gate=gate, mu=args.mu)
+        gated = OffsetTracker(eng, mel, hop_segments=args.hop, posterior=args.posterior, gate=gate, mu=args.mu, pairwise=args.pairwise)
         gtrack = gated.track_features(vbank, abank, win_chunk=args.win_chunk)
         grid = gated.grid
 
@@ -204,6 +213,8 @@ def main():
                          'spans': [[round(t0, 2), round(t1, 2), None if off is None else round(off, 3)] for t0, t1, off in spans]}
         if args.posterior:
             extra['gate']['p_sync_mean'] = round(gtrack.p_sync.mean().item(), 4)
+        if args.pairwise:
+            extra['gate'].update({'expected_changes': round(gtrack.expected_changes(), 3), 'expected_flips': round(gtrack.p_flip.double().sum().item(), 3)})
         for t0, t1, off in spans:
             print(f'span {t0:8.2f} s .. {t1:8.2f} s  ' + ('not synchronizable' if off is None else f'offset {off:+.2f} s'), file=sys.stderr)
     if args.stream is not None:
