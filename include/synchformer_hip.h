@@ -164,7 +164,11 @@ void sf_gemm_mx_force_schedule(int sched);         /* ... and for sf_gemm_mxfp8 
 
 /* y[omap(r), :] (=|+=) LayerNorm(x[imap(r), :]) * gamma + beta over 768 columns; x fp32, y bf16|fp32.
  * Replaces nn.LayerNorm at vit_helper.py:366-375, motionformer.py:232, modeling_ast.py:301,315,535,
- * sync_model.py:157,169, modules/transformer.py:94-95 and norm1/norm2 inside motionformer.py:329. */
+ * sync_model.py:157,169, modules/transformer.py:94-95 and norm1/norm2 inside motionformer.py:329.
+ * Contract of the 768-column row launchers (sf_layernorm768, sf_layernorm768_mxfp8, sf_add_scale_ln768, sf_broadcast_rows768, sf_gather_rows768), checked by
+ * each of them - a violation returns -1 with sf_last_error set and launches nothing: every row stride is a multiple of 4 elements; every fp32 row pointer, gamma,
+ * beta and table is 16-byte aligned, a bf16 output 8-byte aligned (the kernels move 16 bytes per lane and write bf16 rows 8 bytes per lane); with a row map
+ * rows < 2^31 (the map works on 32-bit row indices); accumulate needs an fp32 y. */
 int sf_layernorm768(const float* x, int64_t ldx, const int64_t* in_map, const float* gamma, const float* beta, void* y,
                     int y_dtype, int64_t ldy, const int64_t* out_map, int accumulate, int64_t rows, float eps,
                     void* stream);
@@ -176,7 +180,7 @@ int sf_broadcast_rows768(float* dst, int64_t ld, int64_t dst_seq_rows, const flo
                          void* stream);
 
 /* y[r, :] = cast(x[imap(r), :]) (768 cols, x fp32, y bf16|fp32): the x[:, 0] / x[:, 1:] style slicing at
- * motionformer.py:231,332, ast.py:232-236, sync_model.py:172. */
+ * motionformer.py:231,332, ast.py:232-236, sync_model.py:172.  ldx % 4 == 0, ldy % 4 == 0 and the alignment contract stated at sf_layernorm768. */
 int sf_gather_rows768(const float* x, int64_t ldx, const int64_t* in_map, void* y, int y_dtype, int64_t ldy,
                       int64_t rows, void* stream);
 

@@ -7,6 +7,12 @@
 
 #define D_MODEL 768
 
+// The row kernels move 16 bytes per lane (float4) and write bf16 rows 8 bytes per lane (uint2): fp32 row pointers, gamma and beta must be 16-byte aligned, a bf16
+// output 8-byte aligned, every row stride a multiple of 4 elements.  The launchers refuse anything else - a column slice at an odd offset is an error, not a fault.
+static inline bool sf_aligned(const void* p, uintptr_t a) { return ((uintptr_t)p % a) == 0; }
+// map_row works on 32-bit row indices
+#define SF_MAP_ROWS_MAX ((int64_t)1 << 31)
+
 // ------------------------------------------------------------------------------------------------------
 // LayerNorm over 768 columns.  One wave per row: lane holds 3 x float4 (cols i*256 + lane*4 .. +3), so
 // every wave-instruction touches 1 KiB contiguous.  Two-pass (mean, then centred variance) in registers -
@@ -65,6 +71,9 @@ extern "C" int sf_layernorm768(const float* x, int64_t ldx, const int64_t* in_ma
   SF_CHECK_ARG(y_dtype == SF_BF16 || y_dtype == SF_F32, "sf_layernorm768: y_dtype must be bf16 or f32");
   SF_CHECK_ARG(!(accumulate && y_dtype != SF_F32), "sf_layernorm768: accumulate needs f32 output");
   SF_CHECK_ARG((ldx % 4) == 0 && (ldy % 4) == 0, "sf_layernorm768: ld must be a multiple of 4");
+  SF_CHECK_ARG(sf_aligned(x, 16) && sf_aligned(gamma, 16) && sf_aligned(beta, 16) && sf_aligned(y, y_dtype == SF_F32 ? 16 : 8),
+               "sf_layernorm768: x, gamma, beta and an f32 y must be 16-byte aligned, a bf16 y 8-byte aligned");
+  SF_CHECK_ARG((!in_map && !out_map) || rows < SF_MAP_ROWS_MAX, "sf_layernorm768: a row map serves fewer than 2^31 rows");
   if (rows <= 0) return 0;
   dim3 grid((unsigned)((rows + 3) / 4)), block(256);
   hipStream_t s = (hipStream_t)stream;
@@ -133,6 +142,8 @@ extern "C" int sf_add_scale_ln768(const float* branch, int64_t ldb, const float*
                                   int64_t ldx, const float* gamma, const float* beta, uint16_t* y, int64_t ldy, int64_t rows, float eps, void* stream) {
   SF_CHECK_ARG(branch && residual && x && gamma && beta && y && (!seq_scale || seq_rows >= 1), "sf_add_scale_ln768: bad arguments");
   SF_CHECK_ARG((ldb % 4) == 0 && (ldr % 4) == 0 && (ldx % 4) == 0 && (ldy % 4) == 0, "sf_add_scale_ln768: row strides must be multiples of 4 elements");
+  SF_CHECK_ARG(sf_aligned(branch, 16) && sf_aligned(residual, 16) && sf_aligned(x, 16) && sf_aligned(gamma, 16) && sf_aligned(beta, 16) && sf_aligned(y, 8),
+               "sf_add_scale_ln768: branch, residual, x, gamma and beta must be 16-byte aligned, y 8-byte aligned");
   if (rows <= 0) return 0;
   hipLaunchKernelGGL(add_scale_ln768_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, branch, ldb, seq_scale, seq_rows, residual, ldr,
                      x, ldx, gamma, beta, y, ldy, rows, eps);
@@ -198,6 +209,7 @@ extern "C" int sf_layernorm768_mxfp8(const float* x, int64_t ldx, const float* g
   SF_CHECK_ARG(x && gamma && beta && q && scales, "sf_layernorm768_mxfp8: null pointer");
   SF_CHECK_ARG((ldx % 4) == 0 && (ldq % 16) == 0 && (lds % 4) == 0 && lds >= rows * 4 && ((uintptr_t)q % 16) == 0 && ((uintptr_t)scales % 4) == 0,
                "sf_layernorm768_mxfp8: aligned rows and scale planes of >= rows * 4 bytes are required");
+  SF_CHECK_ARG(sf_aligned(x, 16) && sf_aligned(gamma, 16) && sf_aligned(beta, 16), "sf_layernorm768_mxfp8: x, gamma and beta must be 16-byte aligned");
   if (rows <= 0) return 0;
   hipLaunchKernelGGL(layernorm768_mxfp8_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, ldx, gamma, beta, q, ldq, scales, lds,
                      rows, eps);
@@ -230,6 +242,7 @@ extern "C" int sf_broadcast_rows768(float* dst, int64_t ld, int64_t dst_seq_rows
                                     int64_t n_seq, void* stream) {
   SF_CHECK_ARG(dst && table, "sf_broadcast_rows768: null pointer");
   SF_CHECK_ARG(L > 0 && dst_seq_rows >= L && (ld % 4) == 0, "sf_broadcast_rows768: bad shape");
+  SF_CHECK_ARG(sf_aligned(dst, 16) && sf_aligned(table, 16), "sf_broadcast_rows768: dst and table must be 16-byte aligned");
   const int64_t total = L * n_seq;
   if (total <= 0) return 0;
   hipLaunchKernelGGL(broadcast_rows768_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
@@ -265,6 +278,9 @@ extern "C" int sf_gather_rows768(const float* x, int64_t ldx, const int64_t* in_
                                  int64_t rows, void* stream) {
   SF_CHECK_ARG(x && y, "sf_gather_rows768: null pointer");
   SF_CHECK_ARG(y_dtype == SF_BF16 || y_dtype == SF_F32, "sf_gather_rows768: y_dtype must be bf16 or f32");
+  SF_CHECK_ARG((ldx % 4) == 0 && (ldy % 4) == 0, "sf_gather_rows768: ld must be a multiple of 4");
+  SF_CHECK_ARG(sf_aligned(x, 16) && sf_aligned(y, y_dtype == SF_F32 ? 16 : 8), "sf_gather_rows768: x and an f32 y must be 16-byte aligned, a bf16 y 8-byte aligned");
+  SF_CHECK_ARG(!in_map || rows < SF_MAP_ROWS_MAX, "sf_gather_rows768: a row map serves fewer than 2^31 rows");
   if (rows <= 0) return 0;
   dim3 grid((unsigned)((rows + 3) / 4)), block(256);
   RowMap im = sf_rowmap(in_map);

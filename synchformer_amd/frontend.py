@@ -27,6 +27,20 @@ def mel_filterbank(n_freqs=513, f_min=0.0, f_max=8000.0, n_mels=128, sample_rate
     return fb.astype(np.float32)
 
 
+def mel_tables(n_mels=128, sample_rate=16000) -> dict:
+    """The host tables sf_mel_frontend reads (numpy): tw_cos / tw_sin (400, 513) fp32 - the DFT twiddles of the 400-sample periodic Hann window centred
+    in the 1024-point frame, window folded in -, fb (513, n_mels) fp32 and every filter's non-zero bin range [fb_lo, fb_hi) (int32)."""
+    win, n_fft, bins = 400, 1024, 513
+    n = np.arange(win)
+    hann = 0.5 - 0.5 * np.cos(2.0 * np.pi * n / win)                      # periodic Hann
+    ang = 2.0 * np.pi * np.outer((n_fft - win) // 2 + n, np.arange(bins)) / n_fft
+    fb = mel_filterbank(bins, 0.0, sample_rate / 2, n_mels, sample_rate)
+    nz = fb > 0
+    lo = np.where(nz.any(0), nz.argmax(0), 0).astype(np.int32)
+    hi = np.where(nz.any(0), bins - nz[::-1].argmax(0), 0).astype(np.int32)
+    return dict(tw_cos=(hann[:, None] * np.cos(ang)).astype(np.float32), tw_sin=(-hann[:, None] * np.sin(ang)).astype(np.float32), fb=fb, fb_lo=lo, fb_hi=hi)
+
+
 def segment_ranges(v_len_frames: int, a_len_frames: int, v_fps: int = 25, a_fps: int = 16000, segment_size_vframes: int = 16,
                    n_segments: int = 14, step_size_seg: float = 0.5) -> dict:
     """GenerateMultipleSegments with is_start_random=False, audio_jitter_sec=0 (dataset/transforms.py:421-500; configs/sync.yaml:222-227):
@@ -89,18 +103,10 @@ class MelFrontend:
         if self.dev.type != 'cuda':
             raise RuntimeError('MelFrontend runs on a HIP device only (no CPU fallback)')
         self.n_mels, self.pad_to, self.mean, self.std, self.hop = n_mels, pad_to, float(mean), float(std), 160
-        win, n_fft, bins = 400, 1024, 513
-        n = np.arange(win)
-        hann = 0.5 - 0.5 * np.cos(2.0 * np.pi * n / win)                      # periodic Hann
-        ang = 2.0 * np.pi * np.outer((n_fft - win) // 2 + n, np.arange(bins)) / n_fft
-        self.tw_cos = torch.from_numpy((hann[:, None] * np.cos(ang)).astype(np.float32)).to(self.dev)
-        self.tw_sin = torch.from_numpy((-hann[:, None] * np.sin(ang)).astype(np.float32)).to(self.dev)
-        fb = mel_filterbank(bins, 0.0, sample_rate / 2, n_mels, sample_rate)
-        nz = fb > 0
-        lo = np.where(nz.any(0), nz.argmax(0), 0).astype(np.int32)
-        hi = np.where(nz.any(0), bins - nz[::-1].argmax(0), 0).astype(np.int32)
-        self.fb = torch.from_numpy(fb).to(self.dev)
-        self.fb_lo, self.fb_hi = torch.from_numpy(lo).to(self.dev), torch.from_numpy(hi).to(self.dev)
+        t = mel_tables(n_mels, sample_rate)
+        self.tw_cos, self.tw_sin = torch.from_numpy(t['tw_cos']).to(self.dev), torch.from_numpy(t['tw_sin']).to(self.dev)
+        self.fb = torch.from_numpy(t['fb']).to(self.dev)
+        self.fb_lo, self.fb_hi = torch.from_numpy(t['fb_lo']).to(self.dev), torch.from_numpy(t['fb_hi']).to(self.dev)
         self._ws = None
 
     def __call__(self, wave: torch.Tensor) -> torch.Tensor:

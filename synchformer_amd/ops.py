@@ -209,7 +209,7 @@ def broadcast_rows(dst: torch.Tensor, table: torch.Tensor, n_seq: int, dst_seq_r
 
 
 def gather_rows(x: torch.Tensor, out: torch.Tensor, rows: int, in_map: RowMap = None):
-    assert x.dtype == torch.float32
+    assert x.dtype == torch.float32 and x.shape[1] == 768 and out.shape[1] == 768
     rc = _lib.load().sf_gather_rows768(_dev(x, 'x'), _ld(x), _map(in_map), _dev(out, 'out'), _DT[out.dtype], _ld(out), rows,
                                        _stream())
     _lib.check(rc, 'sf_gather_rows768')
