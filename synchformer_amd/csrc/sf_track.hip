@@ -3,27 +3,31 @@
 // between neighbouring classes, the path that maximises
 //     sum_w e[w, c_w] - lam * sum_{w >= 1} |c_w - c_{w-1}|,        e[w, c] = logits[w, c] - max_c logits[w, .]
 // does not.  e is log-softmax up to a row constant (a row constant cannot change the path), and for dyadic logits / lam every operation below is exact in fp32.
-// Three launches on the caller's stream, all latency-bound (W x C <= W x 64 floats):
+// sf_track_decode: three launches on the caller's stream, all latency-bound (W x C <= W x 64 floats):
 //   1. track_rows_kernel<false>: one thread per window: argmax (lowest index on ties), softmax probability of that class (fp32 statistics);
 //   2. track_viterbi_kernel:     ONE wavefront, lane c = class c, the previous step's scores in LDS: the forward scan over W, then the backtrace;
 //   3. track_rows_kernel<true>:  one thread per window: softmax probability of the path's class.
 // Reference read-out this stands next to: decode_single_video_prediction (example.py:38-56: softmax + top-k of ONE window) on the class grid of
 // make_class_grid (dataset/transforms.py:221-239); the reference has no recording-level read-out.
 //
-// sf_track_posterior (below the Viterbi launcher) reads the same chain out as marginals: the path above is the mode of
+// sf_track_posterior reads the same chain out as marginals: the path above is the mode of
 //     p(c_0 .. c_{W-1})  ~  exp(sum_w e[w, c_w] - lam * sum_w |c_w - c_{w-1}|),        e = the true log-softmax,
 // and the forward-backward algorithm gives post[w, c] = p(c_w = c) and log_z = log of the sum over all paths.  Two launches:
 //   1. track_fb_scan_kernel:     TWO workgroups of one wavefront each, side by side: block 0 the forward scan (a, and log_z), block 1 the backward scan (b);
 //   2. track_fb_combine_kernel:  one thread per window: post = softmax_c (a + b), its argmax and value, the posterior mean of the grid.
+// sf_track_pairwise combines the two scans across a boundary (track_pairwise_kernel, track_pairwise_gated_kernel): the joint marginal of neighbouring windows, its off-diagonal mass (the
+// probability that the offset changed there) and the expected class step - what a fit of lam / mu needs.
+// The _gated forms read out one chain over (offset class, synchronizable flag), fed by a second head.
 //
-// sf_track_decode_gated / sf_track_posterior_gated (next) are the two offline read-outs of one chain over (offset class, synchronizable flag), fed by a second head.
-// sf_track_pairwise / sf_track_pairwise_gated (after them) combine the two scans across a boundary: the joint marginal of neighbouring windows, its off-diagonal mass
-// (the probability that the offset changed there) and the expected class step - what a fit of lam / mu needs.
-// The last section reads either chain out of live feeds at a fixed lag with carried state, and is written ONCE: a chain is a small policy struct (TrackChainPlain over
-// the C offset classes, TrackChainGated over the 2C states) that says what a lane, a row's inputs, a step and a ring are, around the step functions of the offline
-// kernels; the rows struct, the state layout, the scan / read-out / keep bodies, the three stream and three pool kernels and the two launchers are templates on it.
-// sf_track_stream_push(_gated) read one stream, sf_track_pool_push(_gated) many in one call: the same launches over a descriptor table, blockIdx.y = the stream, every
-// block running the single-stream bodies on its stream's context.  The four entries pack their arguments and call the templates.
+// The file has three parts.  First the arithmetic: the rows kernels and the step functions of the plain and the gated chain.  Then the two chains: a chain is a small
+// policy struct (TrackChainPlain over the C offset classes, TrackChainGated over the 2C states) that says what a lane, a row's inputs, a step, an LDS slot and a ring
+// are, around those step functions.  Everything after them is written ONCE, as templates on a chain, but for two pieces that measured slower folded and say so where
+// they stand (the plain chain's own Viterbi kernel, the two pairwise kernels; a chain names its kernel through launch_viterbi / launch_pairwise): the
+// whole-recording kernels (Viterbi scan + backtrace, the two forward-backward scans, the combine) with the three launchers of the whole-recording entries, and the
+// read-out of live feeds at a fixed lag with carried state - the rows struct, the state layout, the scan / read-out / keep bodies, the three stream and three pool
+// kernels and their two launchers.  sf_track_stream_push(_gated) read
+// one stream, sf_track_pool_push(_gated) many in one call: the same launches over a descriptor table, blockIdx.y = the stream, every block running the single-stream
+// bodies on its stream's context.  Every extern "C" entry packs its arguments (a chain's Src, a TrackStreamOut) and calls a launcher template.
 #include "sf_common.h"
 #include "../../include/synchformer_hip.h"
 #include <algorithm>
@@ -82,73 +86,6 @@ __device__ __forceinline__ float track_viterbi_step(const float* s_prev, int C, 
   return s;
 }
 
-// One wavefront.  Lane c < C owns class c; lanes >= C run along with -inf scores so that every cross-lane operation sees a full EXEC mask.
-//   s_0 = e[0];   s_w[c] = max_p (s_{w-1}[p] - lam * |p - c|) + e[w, c]   (lowest p on ties -> backptr[w, c]);   s_w -= max_c s_w[c]   (bounds the scores for any W)
-// The end state is argmax s_{W-1} (lowest index on ties); the backtrace follows backptr from there.  Non-finite logits give NaN scores: a NaN never wins `>`, so the
-// predecessor stays 0, and the backtrace clamps what it reads: every backptr entry and every class written lies in [0, C).
-__global__ __launch_bounds__(64) void track_viterbi_kernel(const float* __restrict__ logits, int64_t ldl, int W, int C, float lam, int32_t* __restrict__ cls_path,
-                                                            uint8_t* __restrict__ backptr) {
-  __shared__ float s_prev[TRACK_MAX_C];
-  const int c = threadIdx.x;
-  const bool live = c < C;
-  const float ninf = -INFINITY;
-  float l = live ? logits[c] : ninf;
-  float s = l - wave_max(l);                                 // s_0 = e[0]; -inf - finite = -inf in the idle lanes (NaN there when the row maximum is +-inf: never read)
-  s_prev[c] = s;
-  __syncthreads();
-  float l_next = (live && W > 1) ? logits[ldl + c] : ninf;
-  for (int w = 1; w < W; ++w) {
-    l = l_next;
-    if (w + 1 < W) l_next = live ? logits[(int64_t)(w + 1) * ldl + c] : ninf;      // the next row's load travels under this step's scan
-    int bp;
-    s = track_viterbi_step(s_prev, C, c, live, lam, l, bp);
-    if (live) backptr[(int64_t)w * C + c] = (uint8_t)bp;
-    __syncthreads();                                               // every lane has read s_prev
-    s_prev[c] = s;
-    __syncthreads();
-  }
-  // (the barriers above order this wave's backptr stores before its loads below)
-  int cur = 0;
-  {
-    float m = s_prev[0];
-    for (int p = 1; p < C; ++p) if (s_prev[p] > m) { m = s_prev[p]; cur = p; }
-  }
-  // backtrace: lane c loads backptr[w, c] of eight rows at a time (independent of the chain), the chain itself is eight wave-uniform shuffles
-  for (int w0 = W - 1; w0 >= 1; w0 -= 8) {
-    int b[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) b[j] = (live && w0 - j >= 1) ? (int)backptr[(int64_t)(w0 - j) * C + c] : 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      if (w0 - j >= 1) {                                           // wave-uniform
-        if (c == 0) cls_path[w0 - j] = cur;
-        const int p = __shfl(b[j], cur, 64);
-        cur = p < C ? p : C - 1;
-      }
-    }
-  }
-  if (c == 0) cls_path[0] = cur;
-}
-
-extern "C" int sf_track_decode(const float* logits, int64_t ldl, int W, int C, float lam, int32_t* cls_raw, float* conf_raw, int32_t* cls_path, float* conf_path,
-                               uint8_t* backptr, void* stream) {
-  SF_CHECK_ARG(W >= 0, "sf_track_decode: W = %d windows", W);
-  SF_CHECK_ARG(C >= 2 && C <= TRACK_MAX_C, "sf_track_decode: C = %d classes out of range (2 .. %d: one lane per class)", C, TRACK_MAX_C);
-  SF_CHECK_ARG(ldl >= C, "sf_track_decode: row stride ldl = %lld below C = %d", (long long)ldl, C);
-  SF_CHECK_ARG(std::isfinite(lam) && lam >= 0.f, "sf_track_decode: lam must be finite and >= 0 (the cost of a class change)");
-  if (W == 0) return 0;
-  SF_CHECK_ARG(logits && cls_raw && conf_raw && cls_path && conf_path && backptr, "sf_track_decode: null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 grid((unsigned)((W + 255) / 256));
-  hipLaunchKernelGGL(track_rows_kernel<false>, grid, dim3(256), 0, s, logits, ldl, W, C, cls_raw, conf_raw);
-  SF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(track_viterbi_kernel, dim3(1), dim3(64), 0, s, logits, ldl, W, C, lam, cls_path, backptr);
-  SF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(track_rows_kernel<true>, grid, dim3(256), 0, s, logits, ldl, W, C, cls_path, conf_path);
-  SF_LAUNCH_CHECK();
-  return 0;
-}
-
 // ---- forward-backward (posterior) read-out --------------------------------------------------------------------------------------------------------------
 // Log domain throughout (a scaled linear-domain recursion underflows: exp(-lam * 20 steps) is 0 in fp32 at lam = 8).  -inf is a masked class: every
 // subtraction that could meet (-inf) - (-inf) is guarded (fb_finite_or_zero on the subtrahend), so a row with one finite logit produces no NaN.
@@ -193,50 +130,6 @@ __device__ __forceinline__ float fb_scan_step(const float* u, int C4, int c, boo
   return v - m;
 }
 
-// Block 0, the forward scan over rows 0 .. W-1:   a_0 = e[0];        a_w[c] = e[w, c] + lse_p (a_{w-1}[p] - lam |p - c|);
-// block 1, the backward scan over rows W-1 .. 0:  b_{W-1} = 0;       b_w[c] = lse_n (b_{w+1}[n] + e[w+1, n] - lam |n - c|).
-// One wavefront each, lane c = class c, the vector the transition reads (a_{w-1}, or b_{w+1} + e[w+1]) in LDS, the next row's load under the current step.
-// After every step the vector's maximum is subtracted (scores stay within [-(lam (C - 1) + row range), 0] for any W: a per-row constant cancels in post)
-// and, in the forward block, added to a double: log_z = the subtracted maxima + lse_c of the last, normalised a.  ws = a (W, C) then b (W, C), fp32.
-__global__ __launch_bounds__(64) void track_fb_scan_kernel(const float* __restrict__ logits, int64_t ldl, int W, int C, float lam, float* __restrict__ ws,
-                                                            float* __restrict__ log_z) {
-  __shared__ __attribute__((aligned(16))) float s_u[TRACK_MAX_C];
-  const int c = threadIdx.x;
-  const bool live = c < C;
-  const bool back = blockIdx.x == 1;                              // wave-uniform
-  const int C4 = (C + 3) & ~3;
-  const float ninf = -INFINITY;
-  float* out = ws + (back ? (int64_t)W * C : 0);
-  const int64_t row0 = back ? W - 1 : 0, step = back ? -1 : 1;     // scan position k reads row row0 + step * k
-  double shifted = 0.0;
-
-  float e = fb_log_softmax(live ? logits[row0 * ldl + c] : ninf);
-  float v = back ? (live ? 0.f : ninf) : e;
-  float m = fb_finite_or_zero(wave_max(v));
-  v -= m;
-  shifted += (double)m;
-  if (live) out[row0 * C + c] = v;
-  s_u[c] = back ? v + e : v;
-  __syncthreads();
-  float l_next = (live && W > 1) ? logits[(row0 + step) * ldl + c] : ninf;
-  for (int k = 1; k < W; ++k) {
-    const int64_t row = row0 + step * k;
-    const float l = l_next;
-    if (k + 1 < W) l_next = live ? logits[(row + step) * ldl + c] : ninf;
-    e = fb_log_softmax(l);
-    v = fb_scan_step(s_u, C4, c, live, back, lam, e, m);
-    shifted += (double)m;
-    if (live) out[row * C + c] = v;
-    __syncthreads();                                               // every lane has read s_u
-    s_u[c] = back ? v + e : v;
-    __syncthreads();
-  }
-  if (!back) {
-    const float z = logf(wave_sum(expf(v)));                       // the normalised a_{W-1}: maximum 0 (idle and masked lanes add exp(-inf) = 0)
-    if (c == 0) log_z[0] = (float)(shifted + (double)z);
-  }
-}
-
 // One window, by one thread: prow[c] = exp(a[c] + b[c] - lse_c (a + b)); best = its argmax (first maximum wins), pbest its value; mean = sum_c prow[c] grid[c].
 __device__ __forceinline__ void fb_combine_row(const float* a, const float* b, int C, const float* __restrict__ grid, float* __restrict__ prow, int& best,
                                                float& pbest, float& mean) {
@@ -255,40 +148,6 @@ __device__ __forceinline__ void fb_combine_row(const float* a, const float* b, i
     mean += p * grid[c];
     if (c == 0 || p > pbest) { pbest = p; best = c; }
   }
-}
-
-// One thread per window:  s = a_w + b_w;  post[w, c] = exp(s[c] - lse_c s);  cls_post = argmax_c post (first maximum wins; a NaN never wins `>`), conf_post its
-// value;  offset_mean = sum_c post[w, c] grid[c] in ascending c.
-__global__ __launch_bounds__(256) void track_fb_combine_kernel(const float* __restrict__ ws, int W, int C, const float* __restrict__ grid, float* __restrict__ post,
-                                                               int64_t ldp, int32_t* __restrict__ cls_post, float* __restrict__ conf_post,
-                                                               float* __restrict__ offset_mean) {
-  const int w = blockIdx.x * 256 + threadIdx.x;
-  if (w >= W) return;
-  const float* a = ws + (int64_t)w * C;
-  int best;
-  float pbest, mean;
-  fb_combine_row(a, a + (int64_t)W * C, C, grid, post + (int64_t)w * ldp, best, pbest, mean);
-  cls_post[w] = best;
-  conf_post[w] = pbest;
-  offset_mean[w] = mean;
-}
-
-extern "C" int sf_track_posterior(const float* logits, int64_t ldl, int W, int C, float lam, const float* grid, float* post, int64_t ldp, int32_t* cls_post,
-                                  float* conf_post, float* offset_mean, float* log_z, float* workspace, void* stream) {
-  SF_CHECK_ARG(W >= 0, "sf_track_posterior: W = %d windows", W);
-  SF_CHECK_ARG(C >= 2 && C <= TRACK_MAX_C, "sf_track_posterior: C = %d classes out of range (2 .. %d: one lane per class)", C, TRACK_MAX_C);
-  SF_CHECK_ARG(ldl >= C, "sf_track_posterior: row stride ldl = %lld below C = %d", (long long)ldl, C);
-  SF_CHECK_ARG(ldp >= C, "sf_track_posterior: post row stride ldp = %lld below C = %d", (long long)ldp, C);
-  SF_CHECK_ARG(std::isfinite(lam) && lam >= 0.f, "sf_track_posterior: lam must be finite and >= 0 (the cost of a class change)");
-  if (W == 0) return 0;
-  SF_CHECK_ARG(logits && grid && post && cls_post && conf_post && offset_mean && log_z && workspace, "sf_track_posterior: null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(track_fb_scan_kernel, dim3(2), dim3(64), 0, s, logits, ldl, W, C, lam, workspace, log_z);
-  SF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(track_fb_combine_kernel, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, s, (const float*)workspace, W, C, grid, post, ldp, cls_post,
-                     conf_post, offset_mean);
-  SF_LAUNCH_CHECK();
-  return 0;
 }
 
 // The end state of a row: the lowest class whose renormalised score is the maximum, 0.  (No such lane - NaN scores - gives class 0, as a NaN never wins `>`.)
@@ -334,7 +193,7 @@ __device__ __forceinline__ float track_gated_emission(const TrackGatedLane& ln, 
 
 // One step of the gated Viterbi scan, by the whole wavefront: s_prev (LDS, 2C floats, state-major) = the previous, renormalised scores, e = this row's emission of
 // the lane's state -> the new renormalised score; bp = the predecessor STATE (one byte).  The lane scans the C predecessors of its own plane (lowest p on ties), takes
-// the other plane's best from its partner, subtracts mu, and settles the tie between the planes (m' = 0 wins).  The offline kernel and the stream's scan both call
+// the other plane's best from its partner, subtracts mu, and settles the tie between the planes (m' = 0 wins).  The whole-recording kernel and the stream's scan both call
 // this: the arithmetic is shared, not copied.
 __device__ __forceinline__ float track_gated_viterbi_step(const TrackGatedLane& ln, const float* s_prev, int C, float lam, float mu, float e, int& bp) {
   const float* sp = s_prev + ln.m * C;                             // the lane's own plane
@@ -380,142 +239,6 @@ __global__ __launch_bounds__(256) void track_gated_rows_kernel(const float* __re
   sync_raw[w] = 1.0f / (1.0f + expf(-d));
 }
 
-// One wavefront, lane j = state j = m * C + c.   S_0 = E[0];   S_w[j] = E[w, j] + max_j' (S_{w-1}[j'] + T(j', j)), the LOWEST predecessor state on ties -> backptr[w, j]
-// (one byte);   S_w -= max_j S_w[j].  Inside a plane the lowest p wins (strict `>` in ascending p); between the planes m' = 0 wins: a lane of plane 0 takes the other
-// plane's candidate only when it is strictly larger, a lane of plane 1 also when it is equal.  (The partner picks its p BEFORE mu is subtracted, a scan over all 2C
-// predecessors would pick after: the two differ only where fp32 rounds two different candidates of the other plane to one value by subtracting mu - the partner then
-// keeps the truly larger one.  With exact arithmetic, e.g. dyadic inputs, they are the same rule.)  The end state is the lowest state whose score is the maximum; the
-// backtrace is track_viterbi_kernel's (eight rows of back pointers per load) and writes cls_path = j % C, sync_path = j / C.  NaN scores never win a comparison, and
-// the backtrace clamps what it reads: every byte and every index written lies in [0, 2C) / [0, C) / {0, 1}.
-__global__ __launch_bounds__(64) void track_gated_viterbi_kernel(const float* __restrict__ logits, int64_t ldl, const float* __restrict__ gate, int64_t ldg, int W, int C,
-                                                                  float lam, float mu, int32_t* __restrict__ cls_path, int32_t* __restrict__ sync_path,
-                                                                  uint8_t* __restrict__ backptr) {
-  __shared__ float s_prev[64];
-  const TrackGatedLane ln(C);
-  const int S = 2 * C;
-  const float ninf = -INFINITY;
-  const float log_c = logf((float)C);
-  const bool loads = ln.live && ln.m;                              // the lanes of plane 1 carry the offset logits
-  float s = track_gated_emission(ln, loads ? logits[ln.c] : ninf, gate[0], gate[1], log_c);
-  s -= wave_max(s);
-  s_prev[ln.j] = s;
-  __syncthreads();
-  float l_next = (loads && W > 1) ? logits[ldl + ln.c] : ninf;
-  float z0_next = W > 1 ? gate[ldg] : 0.f, z1_next = W > 1 ? gate[ldg + 1] : 0.f;
-  for (int w = 1; w < W; ++w) {
-    const float l = l_next, z0 = z0_next, z1 = z1_next;
-    if (w + 1 < W) {                                               // the next row's loads travel under this step's scan
-      l_next = loads ? logits[(int64_t)(w + 1) * ldl + ln.c] : ninf;
-      z0_next = gate[(int64_t)(w + 1) * ldg];
-      z1_next = gate[(int64_t)(w + 1) * ldg + 1];
-    }
-    int bp;
-    s = track_gated_viterbi_step(ln, s_prev, C, lam, mu, track_gated_emission(ln, l, z0, z1, log_c), bp);
-    if (ln.live) backptr[(int64_t)w * S + ln.j] = (uint8_t)bp;
-    __syncthreads();                                               // every lane has read s_prev
-    s_prev[ln.j] = s;
-    __syncthreads();
-  }
-  // (the barriers above order this wave's backptr stores before its loads below)
-  int cur = track_wave_end_state(s, ln.live);
-  for (int w0 = W - 1; w0 >= 1; w0 -= 8) {
-    int b[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) b[i] = (ln.live && w0 - i >= 1) ? (int)backptr[(int64_t)(w0 - i) * S + ln.j] : 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      if (w0 - i >= 1) {                                           // wave-uniform
-        if (ln.j == 0) { cls_path[w0 - i] = cur % C;  sync_path[w0 - i] = cur / C; }
-        const int p = __shfl(b[i], cur, 64);
-        cur = p < S ? p : S - 1;
-      }
-    }
-  }
-  if (ln.j == 0) { cls_path[0] = cur % C;  sync_path[0] = cur / C; }
-}
-
-static bool track_gated_args_ok(const char* who, int W, int C, int64_t ldl, int64_t ldg, float lam, float mu) {
-  if (W < 0) { sf_set_error("%s: W = %d windows", who, W); return false; }
-  if (C < 2 || C > TRACK_GATE_MAX_C) { sf_set_error("%s: C = %d classes out of range (2 .. %d: one lane per (class, flag) state)", who, C, TRACK_GATE_MAX_C); return false; }
-  if (ldl < C) { sf_set_error("%s: row stride ldl = %lld below C = %d", who, (long long)ldl, C); return false; }
-  if (ldg < 2) { sf_set_error("%s: gate row stride ldg = %lld below 2", who, (long long)ldg); return false; }
-  if (!(std::isfinite(lam) && lam >= 0.f)) { sf_set_error("%s: lam must be finite and >= 0 (the cost of a class change)", who); return false; }
-  if (!(std::isfinite(mu) && mu >= 0.f)) { sf_set_error("%s: mu must be finite and >= 0 (the cost of a change of the synchronizable flag)", who); return false; }
-  return true;
-}
-
-extern "C" int sf_track_decode_gated(const float* logits, int64_t ldl, const float* gate_logits, int64_t ldg, int W, int C, float lam, float mu, int32_t* cls_raw,
-                                     float* conf_raw, float* sync_raw, int32_t* cls_path, int32_t* sync_path, float* conf_path, uint8_t* backptr, void* stream) {
-  if (!track_gated_args_ok("sf_track_decode_gated", W, C, ldl, ldg, lam, mu)) return -1;
-  if (W == 0) return 0;
-  SF_CHECK_ARG(logits && gate_logits && cls_raw && conf_raw && sync_raw && cls_path && sync_path && conf_path && backptr, "sf_track_decode_gated: null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 grid((unsigned)((W + 255) / 256));
-  hipLaunchKernelGGL(track_gated_rows_kernel, grid, dim3(256), 0, s, logits, ldl, gate_logits, ldg, W, C, cls_raw, conf_raw, sync_raw);
-  SF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(track_gated_viterbi_kernel, dim3(1), dim3(64), 0, s, logits, ldl, gate_logits, ldg, W, C, lam, mu, cls_path, sync_path, backptr);
-  SF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(track_rows_kernel<true>, grid, dim3(256), 0, s, logits, ldl, W, C, cls_path, conf_path);
-  SF_LAUNCH_CHECK();
-  return 0;
-}
-
-// The two scans of 3.14 over the 2C states: block 0 forward (a, and log_z), block 1 backward (b), one wavefront each.
-//     a_0 = E[0];        a_w[j] = E[w, j] + lse_j' (a_{w-1}[j'] + T(j', j));        b_{W-1} = 0;        b_w[j] = lse_n (b_{w+1}[n] + E[w+1, n] + T(j, n))
-// The vector the transition reads lies in LDS as two planes of 32 floats (entries >= C hold -inf, so fb_transition_lse's float4 reads stay aligned and add +0);
-// lse over the 2C predecessors = logaddexp(lse over the own plane, the partner's lse over its own plane - mu).  The maximum is subtracted after every step and, in the
-// forward block, summed in a double.  ws = a (W, 2C) then b (W, 2C), fp32, state-major rows j = m * C + c.
-__global__ __launch_bounds__(64) void track_gated_fb_scan_kernel(const float* __restrict__ logits, int64_t ldl, const float* __restrict__ gate, int64_t ldg, int W, int C,
-                                                                  float lam, float mu, float* __restrict__ ws, float* __restrict__ log_z) {
-  __shared__ __attribute__((aligned(16))) float s_u[64];
-  const TrackGatedLane ln(C);
-  const int S = 2 * C;
-  const bool back = blockIdx.x == 1;                              // wave-uniform
-  const int C4 = (C + 3) & ~3;
-  const float ninf = -INFINITY;
-  const float log_c = logf((float)C);
-  const bool loads = ln.live && ln.m;
-  const int slot = ln.m * 32 + ln.c;
-  float* out = ws + (back ? (int64_t)W * S : 0);
-  const int64_t row0 = back ? W - 1 : 0, step = back ? -1 : 1;     // scan position k reads row row0 + step * k
-  double shifted = 0.0;
-
-  s_u[threadIdx.x] = ninf;
-  __syncthreads();
-  float e = track_gated_emission(ln, loads ? logits[row0 * ldl + ln.c] : ninf, gate[row0 * ldg], gate[row0 * ldg + 1], log_c);
-  float v = back ? (ln.live ? 0.f : ninf) : e;
-  float m = fb_finite_or_zero(wave_max(v));
-  v -= m;
-  shifted += (double)m;
-  if (ln.live) {
-    out[row0 * S + ln.j] = v;
-    s_u[slot] = back ? v + e : v;
-  }
-  __syncthreads();
-  float l_next = (loads && W > 1) ? logits[(row0 + step) * ldl + ln.c] : ninf;
-  float z0_next = W > 1 ? gate[(row0 + step) * ldg] : 0.f, z1_next = W > 1 ? gate[(row0 + step) * ldg + 1] : 0.f;
-  for (int k = 1; k < W; ++k) {
-    const int64_t row = row0 + step * k;
-    const float l = l_next, z0 = z0_next, z1 = z1_next;
-    if (k + 1 < W) {
-      l_next = loads ? logits[(row + step) * ldl + ln.c] : ninf;
-      z0_next = gate[(row + step) * ldg];
-      z1_next = gate[(row + step) * ldg + 1];
-    }
-    e = track_gated_emission(ln, l, z0, z1, log_c);
-    v = track_gated_fb_step(ln, s_u, C4, back, lam, mu, e, m);
-    shifted += (double)m;
-    if (ln.live) out[row * S + ln.j] = v;
-    __syncthreads();                                               // every lane has read s_u
-    if (ln.live) s_u[slot] = back ? v + e : v;
-    __syncthreads();
-  }
-  if (!back) {
-    const float z = logf(wave_sum(expf(v)));                       // the normalised a_{W-1}: maximum 0 (idle lanes add exp(-inf) = 0)
-    if (ln.j == 0) log_z[0] = (float)(shifted + (double)z);
-  }
-}
-
 // One window, by one thread: a, b (2C floats each, state-major) -> prow[c] = post2[c, 0] + post2[c, 1] with post2 = exp(a + b - lse_j (a + b)); ps = sum_c post2[c, 1]
 // clamped at 1; best = argmax_c prow (first maximum wins), pbest its value; mean = sum_c prow[c] grid[c] in ascending c.
 __device__ __forceinline__ void track_gated_combine_row(const float* a, const float* b, int C, const float* __restrict__ grid, float* __restrict__ prow, int& best,
@@ -542,47 +265,12 @@ __device__ __forceinline__ void track_gated_combine_row(const float* a, const fl
   ps = fminf(ps, 1.f);
 }
 
-// One thread per window:  s = a_w + b_w over the 2C states;  post2 = exp(s - lse_j s);  post[w, c] = post2[c, 0] + post2[c, 1];  p_sync[w] = sum_c post2[c, 1] (at most
-// 1);  cls_post = argmax_c post (first maximum wins; a NaN never wins `>`), conf_post its value;  offset_mean = sum_c post[w, c] grid[c] in ascending c.
-__global__ __launch_bounds__(256) void track_gated_fb_combine_kernel(const float* __restrict__ ws, int W, int C, const float* __restrict__ grid, float* __restrict__ post,
-                                                                      int64_t ldp, float* __restrict__ p_sync, int32_t* __restrict__ cls_post,
-                                                                      float* __restrict__ conf_post, float* __restrict__ offset_mean) {
-  const int w = blockIdx.x * 256 + threadIdx.x;
-  if (w >= W) return;
-  const int S = 2 * C;
-  const float* a = ws + (int64_t)w * S;
-  int best;
-  float pbest, mean, ps;
-  track_gated_combine_row(a, a + (int64_t)W * S, C, grid, post + (int64_t)w * ldp, best, pbest, mean, ps);
-  p_sync[w] = ps;
-  cls_post[w] = best;
-  conf_post[w] = pbest;
-  offset_mean[w] = mean;
-}
-
-extern "C" int sf_track_posterior_gated(const float* logits, int64_t ldl, const float* gate_logits, int64_t ldg, int W, int C, float lam, float mu, const float* grid,
-                                        float* post, int64_t ldp, float* p_sync, int32_t* cls_post, float* conf_post, float* offset_mean, float* log_z,
-                                        float* workspace, void* stream) {
-  if (!track_gated_args_ok("sf_track_posterior_gated", W, C, ldl, ldg, lam, mu)) return -1;
-  SF_CHECK_ARG(ldp >= C, "sf_track_posterior_gated: post row stride ldp = %lld below C = %d", (long long)ldp, C);
-  if (W == 0) return 0;
-  SF_CHECK_ARG(logits && gate_logits && grid && post && p_sync && cls_post && conf_post && offset_mean && log_z && workspace, "sf_track_posterior_gated: null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(track_gated_fb_scan_kernel, dim3(2), dim3(64), 0, s, logits, ldl, gate_logits, ldg, W, C, lam, mu, workspace, log_z);
-  SF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(track_gated_fb_combine_kernel, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, s, (const float*)workspace, W, C, grid, post, ldp, p_sync, cls_post,
-                     conf_post, offset_mean);
-  SF_LAUNCH_CHECK();
-  return 0;
-}
-
 // ---- pairwise marginals of neighbouring windows (sf_track_pairwise, sf_track_pairwise_gated) --------------------------------------------------------
-// With a, b the scans above (left in the workspace by the unchanged scan kernels) the joint marginal of windows w and w + 1 is
+// With a, b the two forward-backward scans (left in the workspace by track_fb_scan_kernel) the joint marginal of windows w and w + 1 is
 //     xi_w[p, c] = exp(t[p, c] - lse_{p,c} t),        t[p, c] = a_w[p] - lam |p - c| + e[w+1, c] + b_{w+1}[c]
-// (the constants the scans subtracted per row cancel), over the states (p, m') -> (c, m) with - mu [m' != m] for the gated chain.  One wavefront per boundary, four
-// boundaries per 256-thread block; the lane is the DESTINATION state, a_w lies in the wave's LDS slice (entries beyond C hold -inf and add +0) and is read as a broadcast
-// while the lane walks the predecessors: walk 1 the maximum, walk 2 the sums and the lane's best off-diagonal pair, walk 3 (only with xi) the stores, lane c writing
-// column c of row p.  Every wave reduction is a butterfly in a fixed order; no atomics: the outputs are the same bits from call to call.
+// (the constants the scans subtracted per row cancel), over the states (p, m') -> (c, m) with - mu [m' != m] for the gated chain.  The two pairwise kernels (below the
+// chains) walk it, one wavefront per boundary; these are the pieces of them that do not depend on the chain.  Every wave reduction is a butterfly in a fixed order; no
+// atomics: the outputs are the same bits from call to call.
 
 // What a lane gathers in walk 2: sum = all of its column, off = the entries with p != c, jump = sum |p - c| x; best / bp = its largest off-diagonal entry, the lowest p
 // on ties (strict `>` in ascending p; a NaN never wins).  bp starts at the lowest p != c, so a column without mass still names an off-diagonal pair.
@@ -623,6 +311,342 @@ __device__ __forceinline__ void track_pair_write(int w, float z, float off, floa
   p_top[w] = best / z;
 }
 
+// ---- the two chains ------------------------------------------------------------------------------------------------------------------------------------------
+// The kernels and launchers below this section are templates on a CHAIN (two pieces excepted, which say why where they stand).  A chain says how many states a row has, what a lane of the scanning wavefront is (the chain
+// object itself, built per thread), what the inputs of a row are and how they are loaded (Src: pointers and strides positioned at a row; In: one row's values in a
+// lane), the first row of the Viterbi scan, the emission, the two steps, where a lane's entry lies in LDS, how one row is combined,
+// what the keep step copies of the inputs, how a path state is written out and which rows, Viterbi and pairwise kernels are its own.  The arithmetic is that of the step functions above: a
+// chain calls them, it does not restate them.  A new chain (say, a third state dimension) is a new policy struct; nothing below it changes.
+
+// Every pointer of the committed block and the tail of one stream's read-out; the offline posterior entries fill in the posterior block alone, one entry per window.
+// The plain chain leaves the sync pointers null and never touches them.
+struct TrackStreamOut {
+  int32_t* cls_lag;  int32_t* sync_lag;  float* conf_lag;
+  float* post_lag;  int64_t ldp;  float* p_sync_lag;  int32_t* cls_post_lag;  float* conf_post_lag;  float* offset_mean_lag;
+  int32_t* cls_tail;  int32_t* sync_tail;  float* conf_tail;
+  // the same block `commit0` committed windows / `tail0` tail entries further on (a pool's packed outputs)
+  __host__ __device__ TrackStreamOut at(int64_t commit0, int64_t tail0) const {
+    TrackStreamOut o = *this;
+    o.cls_lag += commit0;  o.sync_lag += commit0;  o.conf_lag += commit0;
+    o.post_lag += commit0 * ldp;  o.p_sync_lag += commit0;  o.cls_post_lag += commit0;  o.conf_post_lag += commit0;  o.offset_mean_lag += commit0;
+    o.cls_tail += tail0;  o.sync_tail += tail0;  o.conf_tail += tail0;
+    return o;
+  }
+};
+
+// The chain over the C offset classes (sf_track_decode / sf_track_posterior): lane j = class j, one logit per row and lane, the scan vectors contiguous in LDS (the
+// idle lanes store their -inf, which is what fb_transition_lse reads behind class C - 1).
+struct TrackChainPlain {
+  static constexpr int MAX_C = TRACK_MAX_C;
+  static constexpr int GATE_WIDTH = 0;                             // floats of a row's second input: none
+  static constexpr bool LDS_PREFILL = false;
+  static constexpr bool VITERBI_TAKES_EMISSION = false;            // track_viterbi_step takes the logit: its e = l - max is its own
+  static constexpr const char* LANE_IS = "class";
+  __host__ __device__ static int states(int C) { return C; }
+  struct Src {
+    const float* lg;  int64_t ldl;
+    __host__ __device__ Src at(int64_t r) const { return Src{lg + r * ldl, ldl}; }
+    bool ok() const { return lg != nullptr; }
+    bool strides_ok(const char* who, int C) const {
+      if (ldl < C) { sf_set_error("%s: row stride ldl = %lld below C = %d", who, (long long)ldl, C); return false; }
+      return true;
+    }
+  };
+  struct In { float l; };
+  static bool sync_ok(const void*) { return true; }                // the chain has no sync outputs: nothing to refuse
+  static void launch_rows(const Src& src, int n, int C, int32_t* cls_raw, float* conf_raw, float*, hipStream_t s) {
+    hipLaunchKernelGGL(track_rows_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src.lg, src.ldl, n, C, cls_raw, conf_raw);
+  }
+  // the chain's Viterbi and pairwise kernels of a whole recording (defined below them: which are templates on the chain and which are not, and why)
+  static void launch_viterbi(const Src& src, int W, int C, float lam, float mu, int32_t* cls_path, int32_t* sync_path, uint8_t* backptr, hipStream_t s);
+  static void launch_pairwise(const Src& src, const float* ws, int W, int C, float lam, float mu, float* p_change, float* jump_abs, float* p_flip, int32_t* top_from,
+                              int32_t* top_to, float* p_top, float* xi, hipStream_t s);
+
+  int j;
+  bool live;
+  __device__ __forceinline__ TrackChainPlain(int C, int lane = threadIdx.x) : j(lane), live(j < C) {}
+  __device__ __forceinline__ In load(const Src& row, bool have) const { return In{(live && have) ? row.lg[j] : -INFINITY}; }
+  template <class Rows>
+  __device__ __forceinline__ In load_row(const Rows& rows, int64_t r) const { return In{live ? rows.logits(r)[j] : -INFINITY}; }
+  __device__ __forceinline__ float first_viterbi(const In& in, float) const { return in.l - wave_max(in.l); }      // s_0 = e[0]; -inf in the idle lanes
+  __device__ __forceinline__ float emission(const In& in) const { return fb_log_softmax(in.l); }
+  __device__ __forceinline__ float viterbi_step(const float* s_u, int C, float lam, float, const In& in, float, int& bp) const {
+    return track_viterbi_step(s_u, C, j, live, lam, in.l, bp);
+  }
+  __device__ __forceinline__ float fb_step(const float* s_u, int C4, bool back, float lam, float, float e, float& m) const {
+    return fb_scan_step(s_u, C4, j, live, back, lam, e, m);
+  }
+  __device__ __forceinline__ void put(float* s_u, bool, float v) const { s_u[j] = v; }
+  __device__ __forceinline__ static int put_state(int state, int, int32_t* cls, int32_t*, int64_t i) { cls[i] = state;  return state; }
+  __device__ __forceinline__ static void combine(const float* a, const float* b, int C, const float* __restrict__ grid, const TrackStreamOut& out, int i) {
+    int best;
+    float pbest, mean;
+    fb_combine_row(a, b, C, grid, out.post_lag + (int64_t)i * out.ldp, best, pbest, mean);
+    out.cls_post_lag[i] = best;
+    out.conf_post_lag[i] = pbest;
+    out.offset_mean_lag[i] = mean;
+  }
+  __device__ __forceinline__ static void keep_inputs(const Src& row, float* lg_slot, float*, int c, int) { lg_slot[c] = row.lg[c]; }
+};
+
+// The chain over the 2C states j = m * C + c (sf_track_decode_gated / sf_track_posterior_gated): a lane is a TrackGatedLane, a row brings the offset logit (in the
+// lanes of plane 1) and the two gate logits (wave-uniform), the Viterbi scores lie state-major in LDS and the forward vector as two planes of 32 over a -inf fill.
+struct TrackChainGated : TrackGatedLane {
+  static constexpr int MAX_C = TRACK_GATE_MAX_C;
+  static constexpr int GATE_WIDTH = 2;
+  static constexpr bool LDS_PREFILL = true;
+  static constexpr bool VITERBI_TAKES_EMISSION = true;             // both scans of a row start from one emission
+  static constexpr const char* LANE_IS = "(class, flag) state";
+  __host__ __device__ static int states(int C) { return 2 * C; }
+  struct Src {
+    const float* lg;  int64_t ldl;  const float* gz;  int64_t ldg;
+    __host__ __device__ Src at(int64_t r) const { return Src{lg + r * ldl, ldl, gz + r * ldg, ldg}; }
+    bool ok() const { return lg != nullptr && gz != nullptr; }
+    bool strides_ok(const char* who, int C) const {
+      if (ldl < C) { sf_set_error("%s: row stride ldl = %lld below C = %d", who, (long long)ldl, C); return false; }
+      if (ldg < 2) { sf_set_error("%s: gate row stride ldg = %lld below 2", who, (long long)ldg); return false; }
+      return true;
+    }
+  };
+  struct In { float l, z0, z1; };
+  static bool sync_ok(const void* p) { return p != nullptr; }
+  static void launch_rows(const Src& src, int n, int C, int32_t* cls_raw, float* conf_raw, float* sync_raw, hipStream_t s) {
+    hipLaunchKernelGGL(track_gated_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src.lg, src.ldl, src.gz, src.ldg, n, C, cls_raw, conf_raw, sync_raw);
+  }
+  static void launch_viterbi(const Src& src, int W, int C, float lam, float mu, int32_t* cls_path, int32_t* sync_path, uint8_t* backptr, hipStream_t s);
+  static void launch_pairwise(const Src& src, const float* ws, int W, int C, float lam, float mu, float* p_change, float* jump_abs, float* p_flip, int32_t* top_from,
+                              int32_t* top_to, float* p_top, float* xi, hipStream_t s);
+
+  float log_c;
+  bool loads;                                                      // the lanes of plane 1 carry the offset logits
+  __device__ __forceinline__ TrackChainGated(int C, int lane = threadIdx.x) : TrackGatedLane(C, lane), log_c(logf((float)C)), loads(live && m) {}
+  __device__ __forceinline__ In load(const Src& row, bool have) const {
+    return In{(loads && have) ? row.lg[c] : -INFINITY, have ? row.gz[0] : 0.f, have ? row.gz[1] : 0.f};
+  }
+  template <class Rows>
+  __device__ __forceinline__ In load_row(const Rows& rows, int64_t r) const {
+    const float* gz = rows.gate(r);
+    return In{loads ? rows.logits(r)[c] : -INFINITY, gz[0], gz[1]};
+  }
+  __device__ __forceinline__ float emission(const In& in) const { return track_gated_emission(*this, in.l, in.z0, in.z1, log_c); }
+  __device__ __forceinline__ float first_viterbi(const In&, float e) const { return e - wave_max(e); }      // S_0 = E[0]
+  __device__ __forceinline__ float viterbi_step(const float* s_u, int C, float lam, float mu, const In&, float e, int& bp) const {
+    return track_gated_viterbi_step(*this, s_u, C, lam, mu, e, bp);
+  }
+  __device__ __forceinline__ float fb_step(const float* s_u, int C4, bool back, float lam, float mu, float e, float& mx) const {
+    return track_gated_fb_step(*this, s_u, C4, back, lam, mu, e, mx);
+  }
+  __device__ __forceinline__ void put(float* s_u, bool fwd, float v) const {
+    if (live) s_u[fwd ? m * 32 + c : j] = v;
+  }
+  __device__ __forceinline__ static int put_state(int state, int C, int32_t* cls, int32_t* sync, int64_t i) {
+    cls[i] = state % C;
+    sync[i] = state / C;
+    return state % C;
+  }
+  __device__ __forceinline__ static void combine(const float* a, const float* b, int C, const float* __restrict__ grid, const TrackStreamOut& out, int i) {
+    int best;
+    float pbest, mean, ps;
+    track_gated_combine_row(a, b, C, grid, out.post_lag + (int64_t)i * out.ldp, best, pbest, mean, ps);
+    out.p_sync_lag[i] = ps;
+    out.cls_post_lag[i] = best;
+    out.conf_post_lag[i] = pbest;
+    out.offset_mean_lag[i] = mean;
+  }
+  __device__ __forceinline__ static void keep_inputs(const Src& row, float* lg_slot, float* gz_slot, int c, int C) {
+    if (c < C) lg_slot[c] = row.lg[c];
+    if (c < 2) gz_slot[c] = row.gz[c];
+  }
+};
+
+// Follows the back pointers of rows R .. w + 1 from state `cur` (the state at row R) -> the state at row w.  Lane c loads backptr[r, c] of eight rows at a time, the
+// chain itself is eight wave-uniform shuffles.  rows: .width() the entries of one row of back pointers (the gated chain: 2C states; every index read is clamped below
+// it), .backptr(r) row r of them.  sink(r, state) is called by the whole wavefront for every r in [w, R], in descending r: what to do with the state at row r.
+template <class Rows, class Sink>
+__device__ __forceinline__ int track_backtrace(const Rows& rows, int64_t R, int64_t w, int cur, int c, bool live, const Sink& sink) {
+  const int S = rows.width();
+  for (int64_t r0 = R; r0 > w; r0 -= 8) {
+    int b[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) b[j] = (live && r0 - j > w) ? (int)rows.backptr(r0 - j)[c] : 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (r0 - j > w) {                                            // wave-uniform
+        sink(r0 - j, cur);
+        const int p = __shfl(b[j], cur, 64);
+        cur = p < S ? p : S - 1;
+      }
+    }
+  }
+  sink(w, cur);
+  return cur;
+}
+
+// ---- the read-outs of a whole recording (sf_track_decode, sf_track_posterior, sf_track_pairwise and their _gated forms) ----------------
+
+// The back pointers of a recording: row r of S bytes.
+struct TrackPathRows {
+  const uint8_t* bp;  int S;
+  __device__ __forceinline__ int width() const { return S; }
+  __device__ __forceinline__ const uint8_t* backptr(int64_t r) const { return bp + r * S; }
+};
+
+// One wavefront, lane j = state j of the chain; lanes beyond the chain's states run along with -inf scores so that every cross-lane operation sees a full EXEC mask.
+//   s_0 = E[0];   s_w[j] = max_j' (s_{w-1}[j'] + T(j', j)) + E[w, j]   (the lowest predecessor on ties -> backptr[w, j], one byte);   s_w -= max_j s_w[j]
+// (the renormalisation bounds the scores for any W).  T = -lam |p - c|, and -mu [m' != m] between the planes of the gated chain.  Inside a plane the lowest p wins
+// (strict `>` in ascending p); between the planes m' = 0 wins: a lane of plane 0 takes the other plane's candidate only when it is strictly larger, a lane of plane 1
+// also when it is equal.  (The partner picks its p BEFORE mu is subtracted, a scan over all 2C predecessors would pick after: the two differ only where fp32 rounds two
+// different candidates of the other plane to one value by subtracting mu - the partner then keeps the truly larger one.  With exact arithmetic, e.g. dyadic inputs,
+// they are the same rule.)  The end state is the lowest state whose score is the maximum, 0 after the renormalisation; the backtrace follows backptr from there (the
+// barriers of the scan order this wave's backptr stores before its loads) and the chain writes the path: cls_path alone, or cls_path = j % C and sync_path = j / C.
+// Non-finite logits give NaN scores: a NaN never wins a comparison, so the predecessor stays 0, and the backtrace clamps what it reads: every byte and every index
+// written lies in [0, S) / [0, C) / {0, 1}.
+template <class Chain>
+__global__ __launch_bounds__(64) void track_viterbi_kernel(typename Chain::Src src, int W, int C, float lam, float mu, int32_t* __restrict__ cls_path,
+                                                            int32_t* __restrict__ sync_path, uint8_t* __restrict__ backptr) {
+  __shared__ float s_u[TRACK_MAX_C];
+  const Chain ch(C);
+  const unsigned S = Chain::states(C);                             // (unsigned: a row index times S needs no sign word)
+  typename Chain::In in = ch.load(src, true);
+  typename Chain::In next = ch.load(src.at(1), W > 1);
+  float s = ch.first_viterbi(in, Chain::VITERBI_TAKES_EMISSION ? ch.emission(in) : 0.f);
+  ch.put(s_u, false, s);
+  __syncthreads();
+  for (int w = 1; w < W; ++w) {
+    in = next;
+    if (w + 1 < W) next = ch.load(src.at(w + 1), true);            // the next row's loads travel under this step's scan
+    int bp;
+    s = ch.viterbi_step(s_u, C, lam, mu, in, Chain::VITERBI_TAKES_EMISSION ? ch.emission(in) : 0.f, bp);
+    if (ch.live) backptr[(int64_t)w * S + ch.j] = (uint8_t)bp;
+    __syncthreads();                                               // every lane has read s_u
+    ch.put(s_u, false, s);
+    __syncthreads();
+  }
+  track_backtrace(TrackPathRows{backptr, (int)S}, W - 1, 0, track_wave_end_state(s, ch.live), ch.j, ch.live,
+                  [&](int64_t r, int state) { if (ch.j == 0) Chain::put_state(state, C, cls_path, sync_path, r); });
+}
+
+// The plain chain does NOT run the template above: it keeps this kernel, which is the template written out for it by hand, with loose pointers for arguments, a
+// serial scan of LDS for the end state and a backtrace of its own over 32-bit row indices.  The template's plain instantiation gives the same bytes and measured 1.7 %
+// slower over 4096 rows (2.1 % before a no-op moved its scan loop, which had landed 4 bytes early, back); the cause of the rest was not found - an int row index in
+// the shared backtrace made it worse - so the piece stays doubled (profiles/track_offline_refactor.md).  s_prev is what the template calls s_u.
+__global__ __launch_bounds__(64) void track_viterbi_plain_kernel(const float* __restrict__ logits, int64_t ldl, int W, int C, float lam, int32_t* __restrict__ cls_path,
+                                                                  uint8_t* __restrict__ backptr) {
+  __shared__ float s_prev[TRACK_MAX_C];
+  const int c = threadIdx.x;
+  const bool live = c < C;
+  const float ninf = -INFINITY;
+  float l = live ? logits[c] : ninf;
+  float s = l - wave_max(l);                                 // s_0 = e[0]; -inf - finite = -inf in the idle lanes (NaN there when the row maximum is +-inf: never read)
+  s_prev[c] = s;
+  __syncthreads();
+  float l_next = (live && W > 1) ? logits[ldl + c] : ninf;
+  for (int w = 1; w < W; ++w) {
+    l = l_next;
+    if (w + 1 < W) l_next = live ? logits[(int64_t)(w + 1) * ldl + c] : ninf;      // the next row's load travels under this step's scan
+    int bp;
+    s = track_viterbi_step(s_prev, C, c, live, lam, l, bp);
+    if (live) backptr[(int64_t)w * C + c] = (uint8_t)bp;
+    __syncthreads();                                               // every lane has read s_prev
+    s_prev[c] = s;
+    __syncthreads();
+  }
+  // (the barriers above order this wave's backptr stores before its loads below)
+  int cur = 0;
+  {
+    float m = s_prev[0];
+    for (int p = 1; p < C; ++p) if (s_prev[p] > m) { m = s_prev[p]; cur = p; }
+  }
+  // backtrace: lane c loads backptr[w, c] of eight rows at a time (independent of the chain), the chain itself is eight wave-uniform shuffles
+  for (int w0 = W - 1; w0 >= 1; w0 -= 8) {
+    int b[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) b[j] = (live && w0 - j >= 1) ? (int)backptr[(int64_t)(w0 - j) * C + c] : 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (w0 - j >= 1) {                                           // wave-uniform
+        if (c == 0) cls_path[w0 - j] = cur;
+        const int p = __shfl(b[j], cur, 64);
+        cur = p < C ? p : C - 1;
+      }
+    }
+  }
+  if (c == 0) cls_path[0] = cur;
+}
+
+void TrackChainPlain::launch_viterbi(const Src& src, int W, int C, float lam, float, int32_t* cls_path, int32_t*, uint8_t* backptr, hipStream_t s) {
+  hipLaunchKernelGGL(track_viterbi_plain_kernel, dim3(1), dim3(64), 0, s, src.lg, src.ldl, W, C, lam, cls_path, backptr);
+}
+void TrackChainGated::launch_viterbi(const Src& src, int W, int C, float lam, float mu, int32_t* cls_path, int32_t* sync_path, uint8_t* backptr, hipStream_t s) {
+  hipLaunchKernelGGL(track_viterbi_kernel<TrackChainGated>, dim3(1), dim3(64), 0, s, src, W, C, lam, mu, cls_path, sync_path, backptr);
+}
+
+// Block 0, the forward scan over rows 0 .. W-1:   a_0 = E[0];        a_w[j] = E[w, j] + lse_j' (a_{w-1}[j'] + T(j', j));
+// block 1, the backward scan over rows W-1 .. 0:  b_{W-1} = 0;       b_w[j] = lse_n (b_{w+1}[n] + E[w+1, n] + T(j, n)).
+// One wavefront each, lane j = state j, the vector the transition reads (a_{w-1}, or b_{w+1} + E[w+1]) in LDS as the chain lays it out (contiguous; the gated chain:
+// two planes of 32 floats over a -inf fill, so fb_transition_lse's float4 reads stay aligned and add +0), the next row's loads under the current step.
+// After every step the vector's maximum is subtracted (scores stay within [-(lam (C - 1) + row range), 0] for any W: a per-row constant cancels in post)
+// and, in the forward block, added to a double: log_z = the subtracted maxima + lse of the last, normalised a.  ws = a (W, S) then b (W, S), fp32, state-major rows.
+template <class Chain>
+__global__ __launch_bounds__(64) void track_fb_scan_kernel(typename Chain::Src src, int W, int C, float lam, float mu, float* __restrict__ ws,
+                                                            float* __restrict__ log_z) {
+  __shared__ __attribute__((aligned(16))) float s_u[TRACK_MAX_C];
+  const Chain ch(C);
+  const unsigned S = Chain::states(C);
+  const bool back = blockIdx.x == 1;                              // wave-uniform
+  const int C4 = (C + 3) & ~3;
+  const float ninf = -INFINITY;
+  float* out = ws + (back ? (int64_t)W * S : 0);
+  const int64_t row0 = back ? W - 1 : 0, step = back ? -1 : 1;     // scan position k reads row row0 + step * k
+  double shifted = 0.0;
+
+  if (Chain::LDS_PREFILL) {
+    s_u[threadIdx.x] = ninf;
+    __syncthreads();
+  }
+  float e = ch.emission(ch.load(src.at(row0), true));
+  float v = back ? (ch.live ? 0.f : ninf) : e;
+  float m = fb_finite_or_zero(wave_max(v));
+  v -= m;
+  shifted += (double)m;
+  if (ch.live) out[row0 * S + ch.j] = v;
+  ch.put(s_u, true, back ? v + e : v);
+  __syncthreads();
+  typename Chain::In next = ch.load(src.at(row0 + step), W > 1);
+  for (int k = 1; k < W; ++k) {
+    const int64_t row = row0 + step * k;
+    const typename Chain::In in = next;
+    if (k + 1 < W) next = ch.load(src.at(row + step), true);
+    e = ch.emission(in);
+    v = ch.fb_step(s_u, C4, back, lam, mu, e, m);
+    shifted += (double)m;
+    if (ch.live) out[row * S + ch.j] = v;
+    __syncthreads();                                               // every lane has read s_u
+    ch.put(s_u, true, back ? v + e : v);
+    __syncthreads();
+  }
+  if (!back) {
+    const float z = logf(wave_sum(expf(v)));                       // the normalised a_{W-1}: maximum 0 (idle and masked lanes add exp(-inf) = 0)
+    if (ch.j == 0) log_z[0] = (float)(shifted + (double)z);
+  }
+}
+
+// One thread per window: the chain's combine of a_w + b_w (fb_combine_row / track_gated_combine_row) into entry w of the posterior block.
+template <class Chain>
+__global__ __launch_bounds__(256) void track_fb_combine_kernel(const float* __restrict__ ws, int W, int C, const float* __restrict__ grid, TrackStreamOut out) {
+  const int w = blockIdx.x * 256 + threadIdx.x;
+  if (w >= W) return;
+  const unsigned S = Chain::states(C);
+  const float* a = ws + (int64_t)w * S;
+  Chain::combine(a, a + (int64_t)W * S, C, grid, out, w);
+}
+
+// The pairwise kernels are NOT a template on the chain: folded onto chain hooks (a lane's term, which lanes gather) they walk a_w one float per LDS read where these
+// read float4s, and the gated one needs a block barrier more to lay a_w out through put(); measured, the folded kernels took 9.7 us where these take 8.4 us (plain)
+// and 14.6 us where these take 13.7 us (gated) at W = 173 (profiles/track_offline_refactor.md).  What they share is shared as functions: TrackPairAcc, track_pair_top,
+// track_pair_write, the emissions.  One wavefront per boundary, four boundaries per 256-thread block; the lane is the DESTINATION state, a_w lies in the wave's LDS
+// slice (entries beyond C hold -inf and add +0) and is read as a broadcast while the lane walks the predecessors: walk 1 the maximum, walk 2 the sums and the lane's
+// best off-diagonal pair, walk 3 (only with xi) the stores, lane c writing column c of row p.
 __global__ __launch_bounds__(256) void track_pairwise_kernel(const float* __restrict__ logits, int64_t ldl, const float* __restrict__ ws, int W, int C, float lam,
                                                              float* __restrict__ p_change, float* __restrict__ jump_abs, int32_t* __restrict__ top_from,
                                                              int32_t* __restrict__ top_to, float* __restrict__ p_top, float* __restrict__ xi) {
@@ -666,24 +690,6 @@ __global__ __launch_bounds__(256) void track_pairwise_kernel(const float* __rest
     float* out = xi + w * C * C + c;
     for (int p = 0; p < C; ++p) out[(int64_t)p * C] = expf(u[p] - lam * fabsf((float)(p - c)) + d - sub) / z;
   }
-}
-
-extern "C" int sf_track_pairwise(const float* logits, int64_t ldl, int W, int C, float lam, float* p_change, float* jump_abs, int32_t* top_from, int32_t* top_to,
-                                 float* p_top, float* xi, float* log_z, float* workspace, void* stream) {
-  SF_CHECK_ARG(W >= 0, "sf_track_pairwise: W = %d windows", W);
-  SF_CHECK_ARG(C >= 2 && C <= TRACK_MAX_C, "sf_track_pairwise: C = %d classes out of range (2 .. %d: one lane per class)", C, TRACK_MAX_C);
-  SF_CHECK_ARG(ldl >= C, "sf_track_pairwise: row stride ldl = %lld below C = %d", (long long)ldl, C);
-  SF_CHECK_ARG(std::isfinite(lam) && lam >= 0.f, "sf_track_pairwise: lam must be finite and >= 0 (the cost of a class change)");
-  if (W == 0) return 0;
-  SF_CHECK_ARG(logits && log_z && workspace && (W == 1 || (p_change && jump_abs && top_from && top_to && p_top)), "sf_track_pairwise: null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(track_fb_scan_kernel, dim3(2), dim3(64), 0, s, logits, ldl, W, C, lam, workspace, log_z);
-  SF_LAUNCH_CHECK();
-  if (W == 1) return 0;
-  hipLaunchKernelGGL(track_pairwise_kernel, dim3((unsigned)((W - 1 + 3) / 4)), dim3(256), 0, s, logits, ldl, (const float*)workspace, W, C, lam, p_change, jump_abs,
-                     top_from, top_to, p_top, xi);
-  SF_LAUNCH_CHECK();
-  return 0;
 }
 
 // The same over the 2C states: lane j = (m, c) is the destination state, a_w lies in LDS as two planes of 32 floats.  The lane walks its own plane and the other plane
@@ -751,21 +757,126 @@ __global__ __launch_bounds__(256) void track_pairwise_gated_kernel(const float* 
   }
 }
 
+void TrackChainPlain::launch_pairwise(const Src& src, const float* ws, int W, int C, float lam, float, float* p_change, float* jump_abs, float*, int32_t* top_from,
+                                      int32_t* top_to, float* p_top, float* xi, hipStream_t s) {
+  hipLaunchKernelGGL(track_pairwise_kernel, dim3((unsigned)((W - 1 + 3) / 4)), dim3(256), 0, s, src.lg, src.ldl, ws, W, C, lam, p_change, jump_abs, top_from, top_to, p_top,
+                     xi);
+}
+void TrackChainGated::launch_pairwise(const Src& src, const float* ws, int W, int C, float lam, float mu, float* p_change, float* jump_abs, float* p_flip,
+                                      int32_t* top_from, int32_t* top_to, float* p_top, float* xi, hipStream_t s) {
+  hipLaunchKernelGGL(track_pairwise_gated_kernel, dim3((unsigned)((W - 1 + 3) / 4)), dim3(256), 0, s, src.lg, src.ldl, src.gz, src.ldg, ws, W, C, lam, mu, p_change,
+                     jump_abs, p_flip, top_from, top_to, p_top, xi);
+}
+
+// What every entry of a chain refuses before it looks at a pointer, in two parts: W, C (one lane per state) and the strides; then the costs (the plain entries pass
+// mu = 0).  In two parts because the two posterior entries differ in where they check `ldp`: sf_track_posterior between the parts, sf_track_posterior_gated after both.
+template <class Chain>
+static bool track_shape_ok(const char* who, int W, int C, const typename Chain::Src& src) {
+  if (W < 0) { sf_set_error("%s: W = %d windows", who, W); return false; }
+  if (C < 2 || C > Chain::MAX_C) { sf_set_error("%s: C = %d classes out of range (2 .. %d: one lane per %s)", who, C, Chain::MAX_C, Chain::LANE_IS); return false; }
+  return src.strides_ok(who, C);
+}
+static bool track_costs_ok(const char* who, float lam, float mu) {
+  if (!(std::isfinite(lam) && lam >= 0.f)) { sf_set_error("%s: lam must be finite and >= 0 (the cost of a class change)", who); return false; }
+  if (!(std::isfinite(mu) && mu >= 0.f)) { sf_set_error("%s: mu must be finite and >= 0 (the cost of a change of the synchronizable flag)", who); return false; }
+  return true;
+}
+template <class Chain>
+static bool track_args_ok(const char* who, int W, int C, const typename Chain::Src& src, float lam, float mu) {
+  return track_shape_ok<Chain>(who, W, C, src) && track_costs_ok(who, lam, mu);
+}
+
+// Three launches on the caller's stream, all latency-bound (W x S <= W x 64 floats): the chain's rows kernel (cls_raw / conf_raw, sync_raw), the Viterbi scan with
+// its backtrace, and track_rows_kernel<true>: the softmax probability of the path's class.
+template <class Chain>
+static int track_decode_impl(const char* who, const typename Chain::Src& src, int W, int C, float lam, float mu, int32_t* cls_raw, float* conf_raw, float* sync_raw,
+                             int32_t* cls_path, int32_t* sync_path, float* conf_path, uint8_t* backptr, void* stream) {
+  if (!track_args_ok<Chain>(who, W, C, src, lam, mu)) return -1;
+  if (W == 0) return 0;
+  SF_CHECK_ARG(src.ok() && cls_raw && conf_raw && Chain::sync_ok(sync_raw) && cls_path && Chain::sync_ok(sync_path) && conf_path && backptr, "%s: null pointer", who);
+  hipStream_t s = (hipStream_t)stream;
+  Chain::launch_rows(src, W, C, cls_raw, conf_raw, sync_raw, s);
+  SF_LAUNCH_CHECK_AS(who);
+  Chain::launch_viterbi(src, W, C, lam, mu, cls_path, sync_path, backptr, s);
+  SF_LAUNCH_CHECK_AS(who);
+  hipLaunchKernelGGL(track_rows_kernel<true>, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, s, src.lg, src.ldl, W, C, cls_path, conf_path);
+  SF_LAUNCH_CHECK_AS(who);
+  return 0;
+}
+
+// Two launches: both scans side by side (two workgroups of one wavefront), then one thread per window.  out: the posterior block, entry w = window w.
+// ldp_first: whether the entry checks `ldp` before the costs (sf_track_posterior) or after them (sf_track_posterior_gated), as each always did.
+template <class Chain>
+static int track_posterior_impl(const char* who, const typename Chain::Src& src, int W, int C, float lam, float mu, const float* grid, const TrackStreamOut& out,
+                                bool ldp_first, float* log_z, float* workspace, void* stream) {
+  if (!track_shape_ok<Chain>(who, W, C, src)) return -1;
+  if (ldp_first) SF_CHECK_ARG(out.ldp >= C, "%s: post row stride ldp = %lld below C = %d", who, (long long)out.ldp, C);
+  if (!track_costs_ok(who, lam, mu)) return -1;
+  SF_CHECK_ARG(out.ldp >= C, "%s: post row stride ldp = %lld below C = %d", who, (long long)out.ldp, C);
+  if (W == 0) return 0;
+  SF_CHECK_ARG(src.ok() && grid && out.post_lag && Chain::sync_ok(out.p_sync_lag) && out.cls_post_lag && out.conf_post_lag && out.offset_mean_lag && log_z && workspace,
+               "%s: null pointer", who);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(track_fb_scan_kernel<Chain>, dim3(2), dim3(64), 0, s, src, W, C, lam, mu, workspace, log_z);
+  SF_LAUNCH_CHECK_AS(who);
+  hipLaunchKernelGGL(track_fb_combine_kernel<Chain>, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, s, (const float*)workspace, W, C, grid, out);
+  SF_LAUNCH_CHECK_AS(who);
+  return 0;
+}
+
+// The scans of the posterior (they leave a, b in the workspace and log_z), then one wavefront per boundary.  A single window has log_z and no boundary.
+template <class Chain>
+static int track_pairwise_impl(const char* who, const typename Chain::Src& src, int W, int C, float lam, float mu, float* p_change, float* jump_abs, float* p_flip,
+                               int32_t* top_from, int32_t* top_to, float* p_top, float* xi, float* log_z, float* workspace, void* stream) {
+  if (!track_args_ok<Chain>(who, W, C, src, lam, mu)) return -1;
+  if (W == 0) return 0;
+  SF_CHECK_ARG(src.ok() && log_z && workspace && (W == 1 || (p_change && jump_abs && Chain::sync_ok(p_flip) && top_from && top_to && p_top)), "%s: null pointer", who);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(track_fb_scan_kernel<Chain>, dim3(2), dim3(64), 0, s, src, W, C, lam, mu, workspace, log_z);
+  SF_LAUNCH_CHECK_AS(who);
+  if (W == 1) return 0;
+  Chain::launch_pairwise(src, (const float*)workspace, W, C, lam, mu, p_change, jump_abs, p_flip, top_from, top_to, p_top, xi, s);
+  SF_LAUNCH_CHECK_AS(who);
+  return 0;
+}
+
+extern "C" int sf_track_decode(const float* logits, int64_t ldl, int W, int C, float lam, int32_t* cls_raw, float* conf_raw, int32_t* cls_path, float* conf_path,
+                               uint8_t* backptr, void* stream) {
+  return track_decode_impl<TrackChainPlain>("sf_track_decode", TrackChainPlain::Src{logits, ldl}, W, C, lam, 0.f, cls_raw, conf_raw, nullptr, cls_path, nullptr,
+                                            conf_path, backptr, stream);
+}
+
+extern "C" int sf_track_decode_gated(const float* logits, int64_t ldl, const float* gate_logits, int64_t ldg, int W, int C, float lam, float mu, int32_t* cls_raw,
+                                     float* conf_raw, float* sync_raw, int32_t* cls_path, int32_t* sync_path, float* conf_path, uint8_t* backptr, void* stream) {
+  return track_decode_impl<TrackChainGated>("sf_track_decode_gated", TrackChainGated::Src{logits, ldl, gate_logits, ldg}, W, C, lam, mu, cls_raw, conf_raw, sync_raw,
+                                            cls_path, sync_path, conf_path, backptr, stream);
+}
+
+extern "C" int sf_track_posterior(const float* logits, int64_t ldl, int W, int C, float lam, const float* grid, float* post, int64_t ldp, int32_t* cls_post,
+                                  float* conf_post, float* offset_mean, float* log_z, float* workspace, void* stream) {
+  const TrackStreamOut out{nullptr, nullptr, nullptr, post, ldp, nullptr, cls_post, conf_post, offset_mean, nullptr, nullptr, nullptr};
+  return track_posterior_impl<TrackChainPlain>("sf_track_posterior", TrackChainPlain::Src{logits, ldl}, W, C, lam, 0.f, grid, out, true, log_z, workspace, stream);
+}
+
+extern "C" int sf_track_posterior_gated(const float* logits, int64_t ldl, const float* gate_logits, int64_t ldg, int W, int C, float lam, float mu, const float* grid,
+                                        float* post, int64_t ldp, float* p_sync, int32_t* cls_post, float* conf_post, float* offset_mean, float* log_z,
+                                        float* workspace, void* stream) {
+  const TrackStreamOut out{nullptr, nullptr, nullptr, post, ldp, p_sync, cls_post, conf_post, offset_mean, nullptr, nullptr, nullptr};
+  return track_posterior_impl<TrackChainGated>("sf_track_posterior_gated", TrackChainGated::Src{logits, ldl, gate_logits, ldg}, W, C, lam, mu, grid, out, false,
+                                               log_z, workspace, stream);
+}
+
+extern "C" int sf_track_pairwise(const float* logits, int64_t ldl, int W, int C, float lam, float* p_change, float* jump_abs, int32_t* top_from, int32_t* top_to,
+                                 float* p_top, float* xi, float* log_z, float* workspace, void* stream) {
+  return track_pairwise_impl<TrackChainPlain>("sf_track_pairwise", TrackChainPlain::Src{logits, ldl}, W, C, lam, 0.f, p_change, jump_abs, nullptr, top_from, top_to,
+                                              p_top, xi, log_z, workspace, stream);
+}
+
 extern "C" int sf_track_pairwise_gated(const float* logits, int64_t ldl, const float* gate_logits, int64_t ldg, int W, int C, float lam, float mu, float* p_change,
                                        float* jump_abs, float* p_flip, int32_t* top_from, int32_t* top_to, float* p_top, float* xi, float* log_z, float* workspace,
                                        void* stream) {
-  if (!track_gated_args_ok("sf_track_pairwise_gated", W, C, ldl, ldg, lam, mu)) return -1;
-  if (W == 0) return 0;
-  SF_CHECK_ARG(logits && gate_logits && log_z && workspace && (W == 1 || (p_change && jump_abs && p_flip && top_from && top_to && p_top)),
-               "sf_track_pairwise_gated: null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(track_gated_fb_scan_kernel, dim3(2), dim3(64), 0, s, logits, ldl, gate_logits, ldg, W, C, lam, mu, workspace, log_z);
-  SF_LAUNCH_CHECK();
-  if (W == 1) return 0;
-  hipLaunchKernelGGL(track_pairwise_gated_kernel, dim3((unsigned)((W - 1 + 3) / 4)), dim3(256), 0, s, logits, ldl, gate_logits, ldg, (const float*)workspace, W, C, lam,
-                     mu, p_change, jump_abs, p_flip, top_from, top_to, p_top, xi);
-  SF_LAUNCH_CHECK();
-  return 0;
+  return track_pairwise_impl<TrackChainGated>("sf_track_pairwise_gated", TrackChainGated::Src{logits, ldl, gate_logits, ldg}, W, C, lam, mu, p_change, jump_abs, p_flip,
+                                              top_from, top_to, p_top, xi, log_z, workspace, stream);
 }
 
 // ---- fixed-lag read-out of live feeds (sf_track_stream_push, sf_track_pool_push and their _gated forms) --------------------------------
@@ -784,142 +895,7 @@ extern "C" int sf_track_pairwise_gated(const float* logits, int64_t ldl, const f
 //                                    combine of row w; one more wavefront backtraces the tail from the last row.  The windows are independent: a catch-up push of
 //                                    1000 rows spreads over the chip instead of running n * lag dependent steps in one wavefront;
 //   4. track_stream_keep_kernel:     copies the last min(lag, n) new rows into the rings (after 3, which still reads the slots they replace).
-// All of it is templated on a CHAIN.  A chain says how many states a row has, what a lane of the scanning wavefront is (the chain object itself, built per thread),
-// what the inputs of a row are and how they are loaded (Src: pointers and strides positioned at a row; In: one row's values in a lane), the first row of the Viterbi
-// scan, the emission, the two steps, where a lane's entry lies in LDS, how one row is combined, what the keep step copies of the inputs, how a path state is written
-// out and which rows kernel runs first.  The arithmetic is that of the offline kernels' step functions: a chain calls them, it does not restate them.  A new chain
-// (say, a third state dimension) is a new policy struct; nothing below it changes.
-
-// Every pointer of the committed block and the tail of one stream's read-out.  The plain chain leaves the sync pointers null and never touches them.
-struct TrackStreamOut {
-  int32_t* cls_lag;  int32_t* sync_lag;  float* conf_lag;
-  float* post_lag;  int64_t ldp;  float* p_sync_lag;  int32_t* cls_post_lag;  float* conf_post_lag;  float* offset_mean_lag;
-  int32_t* cls_tail;  int32_t* sync_tail;  float* conf_tail;
-  // the same block `commit0` committed windows / `tail0` tail entries further on (a pool's packed outputs)
-  __host__ __device__ TrackStreamOut at(int64_t commit0, int64_t tail0) const {
-    TrackStreamOut o = *this;
-    o.cls_lag += commit0;  o.sync_lag += commit0;  o.conf_lag += commit0;
-    o.post_lag += commit0 * ldp;  o.p_sync_lag += commit0;  o.cls_post_lag += commit0;  o.conf_post_lag += commit0;  o.offset_mean_lag += commit0;
-    o.cls_tail += tail0;  o.sync_tail += tail0;  o.conf_tail += tail0;
-    return o;
-  }
-};
-
-// The chain over the C offset classes (sf_track_decode / sf_track_posterior): lane j = class j, one logit per row and lane, the scan vectors contiguous in LDS (the
-// idle lanes store their -inf, which is what fb_transition_lse reads behind class C - 1).
-struct TrackChainPlain {
-  static constexpr int MAX_C = TRACK_MAX_C;
-  static constexpr int GATE_WIDTH = 0;                             // floats of a row's second input: none
-  static constexpr bool LDS_PREFILL = false;
-  static constexpr bool VITERBI_TAKES_EMISSION = false;            // track_viterbi_step takes the logit: its e = l - max is its own
-  __host__ __device__ static int states(int C) { return C; }
-  struct Src {
-    const float* lg;  int64_t ldl;
-    __host__ __device__ Src at(int64_t r) const { return Src{lg + r * ldl, ldl}; }
-    bool ok() const { return lg != nullptr; }
-    bool strides_ok(const char* who, int C) const {
-      if (ldl < C) { sf_set_error("%s: row stride ldl = %lld below C = %d", who, (long long)ldl, C); return false; }
-      return true;
-    }
-  };
-  struct In { float l; };
-  static bool sync_ok(const void*) { return true; }                // the chain has no sync outputs: nothing to refuse
-  static void launch_rows(const Src& src, int n, int C, int32_t* cls_raw, float* conf_raw, float*, hipStream_t s) {
-    hipLaunchKernelGGL(track_rows_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src.lg, src.ldl, n, C, cls_raw, conf_raw);
-  }
-
-  int j;
-  bool live;
-  __device__ __forceinline__ TrackChainPlain(int C) : j(threadIdx.x), live(j < C) {}
-  __device__ __forceinline__ In load(const Src& row, bool have) const { return In{(live && have) ? row.lg[j] : -INFINITY}; }
-  template <class Rows>
-  __device__ __forceinline__ In load_row(const Rows& rows, int64_t r) const { return In{live ? rows.logits(r)[j] : -INFINITY}; }
-  __device__ __forceinline__ float first_viterbi(const In& in, float) const { return in.l - wave_max(in.l); }      // s_0 = e[0]; -inf in the idle lanes
-  __device__ __forceinline__ float emission(const In& in) const { return fb_log_softmax(in.l); }
-  __device__ __forceinline__ float viterbi_step(const float* s_u, int C, float lam, float, const In& in, float, int& bp) const {
-    return track_viterbi_step(s_u, C, j, live, lam, in.l, bp);
-  }
-  __device__ __forceinline__ float fb_step(const float* s_u, int C4, bool back, float lam, float, float e, float& m) const {
-    return fb_scan_step(s_u, C4, j, live, back, lam, e, m);
-  }
-  __device__ __forceinline__ void put(float* s_u, bool, float v) const { s_u[j] = v; }
-  __device__ __forceinline__ static int put_state(int state, int, int32_t* cls, int32_t*, int64_t i) { cls[i] = state;  return state; }
-  __device__ __forceinline__ static void combine(const float* a, const float* b, int C, const float* __restrict__ grid, const TrackStreamOut& out, int i) {
-    int best;
-    float pbest, mean;
-    fb_combine_row(a, b, C, grid, out.post_lag + (int64_t)i * out.ldp, best, pbest, mean);
-    out.cls_post_lag[i] = best;
-    out.conf_post_lag[i] = pbest;
-    out.offset_mean_lag[i] = mean;
-  }
-  __device__ __forceinline__ static void keep_inputs(const Src& row, float* lg_slot, float*, int c, int) { lg_slot[c] = row.lg[c]; }
-};
-
-// The chain over the 2C states j = m * C + c (sf_track_decode_gated / sf_track_posterior_gated): a lane is a TrackGatedLane, a row brings the offset logit (in the
-// lanes of plane 1) and the two gate logits (wave-uniform), the Viterbi scores lie state-major in LDS and the forward vector as two planes of 32 over a -inf fill.
-struct TrackChainGated : TrackGatedLane {
-  static constexpr int MAX_C = TRACK_GATE_MAX_C;
-  static constexpr int GATE_WIDTH = 2;
-  static constexpr bool LDS_PREFILL = true;
-  static constexpr bool VITERBI_TAKES_EMISSION = true;             // both scans of a row start from one emission
-  __host__ __device__ static int states(int C) { return 2 * C; }
-  struct Src {
-    const float* lg;  int64_t ldl;  const float* gz;  int64_t ldg;
-    __host__ __device__ Src at(int64_t r) const { return Src{lg + r * ldl, ldl, gz + r * ldg, ldg}; }
-    bool ok() const { return lg != nullptr && gz != nullptr; }
-    bool strides_ok(const char* who, int C) const {
-      if (ldl < C) { sf_set_error("%s: row stride ldl = %lld below C = %d", who, (long long)ldl, C); return false; }
-      if (ldg < 2) { sf_set_error("%s: gate row stride ldg = %lld below 2", who, (long long)ldg); return false; }
-      return true;
-    }
-  };
-  struct In { float l, z0, z1; };
-  static bool sync_ok(const void* p) { return p != nullptr; }
-  static void launch_rows(const Src& src, int n, int C, int32_t* cls_raw, float* conf_raw, float* sync_raw, hipStream_t s) {
-    hipLaunchKernelGGL(track_gated_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src.lg, src.ldl, src.gz, src.ldg, n, C, cls_raw, conf_raw, sync_raw);
-  }
-
-  float log_c;
-  bool loads;                                                      // the lanes of plane 1 carry the offset logits
-  __device__ __forceinline__ TrackChainGated(int C) : TrackGatedLane(C), log_c(logf((float)C)), loads(live && m) {}
-  __device__ __forceinline__ In load(const Src& row, bool have) const {
-    return In{(loads && have) ? row.lg[c] : -INFINITY, have ? row.gz[0] : 0.f, have ? row.gz[1] : 0.f};
-  }
-  template <class Rows>
-  __device__ __forceinline__ In load_row(const Rows& rows, int64_t r) const {
-    const float* gz = rows.gate(r);
-    return In{loads ? rows.logits(r)[c] : -INFINITY, gz[0], gz[1]};
-  }
-  __device__ __forceinline__ float emission(const In& in) const { return track_gated_emission(*this, in.l, in.z0, in.z1, log_c); }
-  __device__ __forceinline__ float first_viterbi(const In&, float e) const { return e - wave_max(e); }      // S_0 = E[0]
-  __device__ __forceinline__ float viterbi_step(const float* s_u, int C, float lam, float mu, const In&, float e, int& bp) const {
-    return track_gated_viterbi_step(*this, s_u, C, lam, mu, e, bp);
-  }
-  __device__ __forceinline__ float fb_step(const float* s_u, int C4, bool back, float lam, float mu, float e, float& mx) const {
-    return track_gated_fb_step(*this, s_u, C4, back, lam, mu, e, mx);
-  }
-  __device__ __forceinline__ void put(float* s_u, bool fwd, float v) const {
-    if (live) s_u[fwd ? m * 32 + c : j] = v;
-  }
-  __device__ __forceinline__ static int put_state(int state, int C, int32_t* cls, int32_t* sync, int64_t i) {
-    cls[i] = state % C;
-    sync[i] = state / C;
-    return state % C;
-  }
-  __device__ __forceinline__ static void combine(const float* a, const float* b, int C, const float* __restrict__ grid, const TrackStreamOut& out, int i) {
-    int best;
-    float pbest, mean, ps;
-    track_gated_combine_row(a, b, C, grid, out.post_lag + (int64_t)i * out.ldp, best, pbest, mean, ps);
-    out.p_sync_lag[i] = ps;
-    out.cls_post_lag[i] = best;
-    out.conf_post_lag[i] = pbest;
-    out.offset_mean_lag[i] = mean;
-  }
-  __device__ __forceinline__ static void keep_inputs(const Src& row, float* lg_slot, float* gz_slot, int c, int C) {
-    if (c < C) lg_slot[c] = row.lg[c];
-    if (c < 2) gz_slot[c] = row.gz[c];
-  }
-};
+// All of it is templated on a chain (above), as the whole-recording kernels are, and runs a row through the same hooks in the same order as they do.
 
 // the state buffer: [double shifted][int32 end_last, pad][s: 64 floats][posterior: a: 64 floats][offset logits ring (lag, C) fp32][gated: gate logits ring (lag, 2) fp32]
 //   [posterior: a ring (lag, S) fp32][back pointer ring (lag, S) bytes], rounded up to 16 bytes; S = the chain's states.  Row r of the stream lies in slot r % lag of
@@ -939,28 +915,6 @@ struct TrackStreamLayout {
   }
 };
 using TrackGatedStreamLayout = TrackStreamLayout<TrackChainGated>;      // (the name the header's description of the gated state uses)
-
-// Follows the back pointers of rows R .. w + 1 from class `cur` (the class at row R) -> the class at row w.  Lane c loads backptr[r, c] of eight rows at a time, the
-// chain itself is eight wave-uniform shuffles.  KEEP: tail[r - w] = the class at row r, for every r in [w, R] (LDS, written by lane 0).
-template <bool KEEP, class Rows>
-__device__ __forceinline__ int track_stream_backtrace(const Rows& rows, int64_t R, int64_t w, int cur, int c, bool live, int* tail) {
-  const int C = rows.width();                                      // entries of one row of back pointers (the gated chain: 2C states)
-  for (int64_t r0 = R; r0 > w; r0 -= 8) {
-    int b[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) b[j] = (live && r0 - j > w) ? (int)rows.backptr(r0 - j)[c] : 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      if (r0 - j > w) {                                            // wave-uniform
-        if (KEEP && c == 0) tail[r0 - j - w] = cur;
-        const int p = __shfl(b[j], cur, 64);
-        cur = p < C ? p : C - 1;
-      }
-    }
-  }
-  if (KEEP && c == 0) tail[0] = cur;
-  return cur;
-}
 
 #define TRACK_POOL_MAX_ACTIVE 4096
 #define TRACK_POOL_ROW 8
@@ -1139,7 +1093,7 @@ __device__ __forceinline__ void track_stream_readout_body(const TrackStreamRows<
     const int64_t w = t_last - (n_tail - 1);
     int cur = rows.end(t_last);
     cur = cur < 0 ? 0 : (cur >= S ? S - 1 : cur);
-    track_stream_backtrace<true>(rows, t_last, w, cur, ch.j, ch.live, s_tail);
+    track_backtrace(rows, t_last, w, cur, ch.j, ch.live, [&](int64_t r, int state) { if (ch.j == 0) s_tail[r - w] = state; });
     __syncthreads();
     for (int i = threadIdx.x; i < n_tail; i += 64) {
       const float* row = rows.logits(w + i);
@@ -1156,7 +1110,7 @@ __device__ __forceinline__ void track_stream_readout_body(const TrackStreamRows<
   const int64_t R = w + rows.lag < t_last ? w + rows.lag : t_last;
   int cur = rows.end(R);
   cur = cur < 0 ? 0 : (cur >= S ? S - 1 : cur);
-  cur = track_stream_backtrace<false>(rows, R, w, cur, ch.j, ch.live, nullptr);
+  cur = track_backtrace(rows, R, w, cur, ch.j, ch.live, [](int64_t, int) {});
   if (ch.j == 0) {
     const float* row = rows.logits(w);
     int best;
@@ -1226,12 +1180,12 @@ static bool track_stream_shape_ok(const char* who, int C, int lag) {
   return true;
 }
 
-// What sf_track_stream_push and track_gated_args_ok refuse, for the two gated launchers: C (2 .. 32), lag, lam, mu and - when there are rows - the strides.
+// What sf_track_stream_push and the gated chain's track_args_ok refuse, for the two gated launchers: C (2 .. 32), lag, lam, mu and - when there are rows - the strides.
 #define TRACK_STREAM_MAX_PUSH (1 << 20)
 static bool track_gated_stream_args_ok(const char* who, int C, int lag, int n, int64_t ldl, int64_t ldg, float lam, float mu) {
   if (lag < 0 || lag > 255) { sf_set_error("%s: lag = %d windows out of range (0 .. 255)", who, lag); return false; }
   if (n < 0 || n > TRACK_STREAM_MAX_PUSH) { sf_set_error("%s: n = %d rows in one push (0 .. %d: split a longer catch-up)", who, n, TRACK_STREAM_MAX_PUSH); return false; }
-  return track_gated_args_ok(who, n, C, n ? ldl : (int64_t)C, n ? ldg : (int64_t)2, lam, mu);
+  return track_args_ok<TrackChainGated>(who, n, C, TrackChainGated::Src{nullptr, n ? ldl : (int64_t)C, nullptr, n ? ldg : (int64_t)2}, lam, mu);
 }
 
 extern "C" int sf_track_stream_bytes(int C, int lag, int posterior) {
