@@ -139,7 +139,7 @@ def agg_encoder_layer_cls(tokens, sd, p, heads=12, keep=None):
     qkv = qkv.reshape(N, L + 1, 3, heads, d).permute(2, 0, 3, 1, 4)
     kk = None                                                       # keep (N, L) bool: [cls = keep; tokens] as key mask (mf:308-317)
     if keep is not None:
-        kk = torch.cat([torch.ones(N, 1, dtype=torch.bool), keep], 1).unsqueeze(1)
+        kk = torch.cat([torch.ones(N, 1, dtype=torch.bool, device=keep.device), keep], 1).unsqueeze(1)
     a = _softmax_attn(qkv[0], qkv[1], qkv[2], d ** -0.5, kk).transpose(1, 2).reshape(N, L + 1, Dm)
     z = z + _lin(a, sd, p + '.self_attn.out_proj')
     z = z + _lin(_gelu(_lin(_ln(z, sd, p + '.norm2', EPS_VIS), sd, p + '.linear1')), sd, p + '.linear2')

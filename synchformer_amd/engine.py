@@ -587,6 +587,8 @@ class SynchformerEngine:
                     ops.quantize_mxfp8(xn, xq, xs)
                 else:
                     ops.gemm(hid_b, b['fc2'].w, b['fc2'].b, X, residual=X)
+                if self.capture_blocks is not None:
+                    self.capture_blocks[bi] = X.clone()
                 continue
             ops.gemm_mxfp8(xq, xs, mx['fc1'].q, mx['fc1'].s, mx['fc1'].b, hq, gelu=True, out_scales=hs)
             if fuse and bi + 1 < nb:
@@ -594,6 +596,8 @@ class SynchformerEngine:
                 ops.gemm_mx_res_ln(hq, hs, mx['fc2'].q, mx['fc2'].s, mx['fc2'].b, X, nx.g, nx.b, xq, xs, EPS_VIS)
             else:
                 ops.gemm_mxfp8(hq, hs, mx['fc2'].q, mx['fc2'].s, mx['fc2'].b, X, residual=X)
+            if self.capture_blocks is not None:
+                self.capture_blocks[bi] = X.clone()
 
     def _visual_tail(self, X, n, out, tok_keep):
         # drop CLS -> final norm -> per-frame sequences with the aggregator CLS in front (mf:231-232, 356-375): all inside the pooled launch, which reads the
