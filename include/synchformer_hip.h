@@ -683,6 +683,34 @@ int sf_track_pool_push_gated(void* states, int64_t state_stride, int n_slots, in
                              int64_t ldp, float* p_sync_lag, int32_t* cls_post_lag, float* conf_post_lag, float* offset_mean_lag, int32_t* cls_tail, int32_t* sync_tail,
                              float* conf_tail, float* log_z, void* workspace, void* stream);
 
+/* The WIDE chain (additions under ABI v25): the whole-recording read-outs over S states at unevenly spaced positions - a search over D lags x C classes
+ * beyond the class grid.  logits (W, D, C) fp32: window w paired at lag d, row stride ldw >= (D - 1) ldd + C, lag stride ldd >= C, unit class stride; gate_logits
+ * (W, D, 2) fp32 with strides ldgw, ldgd likewise, or NULL.  State s (in the caller's order) reads the pair state_src[s] = d * C + c (all distinct, inside [0, D C)) and
+ * stands at pos[s] (fp32, finite, non-decreasing: class steps).  Both tables come twice, as sf_track_pool_push takes its table: the HOST copies are validated, the
+ * DEVICE copies are what the kernels read.
+ *     e[w, s] = logits[w, d, c] - lse_c logits[w, d, .] + g[w, d],     g = -softplus(z0 - z1) (log sigmoid of the gate's margin), 0 without a gate
+ * sf_track_decode_wide:  s_0 = e[0];  s_w[c] = max_p (s_{w-1}[p] - lam |pos[p] - pos[c]|) + e[w, c], the lowest p among the maximisers, the end state the lowest argmax,
+ *   scores renormalised by a maximum every step.  state_raw[w] = the lowest argmax of e[w, .], conf_raw[w] its softmax probability over all S states; state_path the
+ *   path, conf_path that softmax probability at the path's state.  For the path and these probabilities e is taken up to the row constant max_d (g - lse)[w, d], which
+ *   changes none of them and keeps the scan exact where it can be (one lag, or rows that agree across the lags: e = the logit).
+ * sf_track_posterior_wide:  the recurrences of sf_track_posterior with |p - c| replaced by |pos[p] - pos[c]|: post (W, S) (row stride ldp >= S), state_post / conf_post
+ *   its argmax (lowest state on ties) and value, offset_mean[w] = sum_s post[w, s] off[s] (off (S,) fp32 on the device: the states' offsets in seconds), p_lag (W, D)
+ *   dense: the sum of post over each lag's states, log_z[0] (<= W log D without a gate, with equality at lam = 0: every window's emissions sum to D over the states).  A -inf logit masks its state.
+ * Both: 2 <= S <= 1024, 2 <= C <= 64, 1 <= D <= 1024, S <= D C, lam finite and >= 0; -1 and a message before the device is touched for these, a stride below its
+ * bound, a pos that is not finite and ascending, a state_src out of range or repeated, a null pointer when W > 0.  W == 0 returns 0 and writes nothing.  Caller's
+ * stream, nothing allocated, read back or synchronised, no atomics: the same bits eager and under graph replay.  workspace: sf_track_wide_workspace_bytes(W, D, S,
+ * posterior, &bytes) bytes (posterior = 0 for the decode entry), 16-byte aligned, caller-owned, dead after the call; the back pointers in it are uint16 (W, S).
+ * One workgroup of ceil(S / 64) wavefronts, thread s = state s; a step costs O(S) over all states (two scans under a decayed operator, 16 LDS slots and one barrier
+ * across the wavefronts).  NaN and +inf: values unspecified, every index written inside [0, S). */
+int sf_track_wide_workspace_bytes(int W, int D, int S, int posterior, int64_t* bytes);
+int sf_track_decode_wide(const float* logits, int64_t ldw, int64_t ldd, const float* gate_logits, int64_t ldgw, int64_t ldgd, int W, int D, int C, int S,
+                         const int32_t* state_src_host, const float* pos_host, const int32_t* state_src_dev, const float* pos_dev, float lam, int32_t* state_raw,
+                         float* conf_raw, int32_t* state_path, float* conf_path, void* workspace, void* stream);
+int sf_track_posterior_wide(const float* logits, int64_t ldw, int64_t ldd, const float* gate_logits, int64_t ldgw, int64_t ldgd, int W, int D, int C, int S,
+                            const int32_t* state_src_host, const float* pos_host, const int32_t* state_src_dev, const float* pos_dev, float lam, const float* off,
+                            float* post, int64_t ldp, int32_t* state_post, float* conf_post, float* offset_mean, float* p_lag, float* log_z, void* workspace,
+                            void* stream);
+
 /* ---- Ingest of a decoded recording at its native frame rate, size and sample rate: the step the reference leaves to an ffmpeg subprocess in front of its code
  * (example.py:16-53: fps=25, short side 256, even dimensions, -ar 16000), plus the centre 224 crop of RGBSpatialCrop (dataset/transforms.py:68-95).  The host
  * computes the geometry (synchformer_amd.ingest) into DEVICE tables.

@@ -10,7 +10,7 @@ from pathlib import Path
 
 LIB_DIR = Path(__file__).resolve().parent / 'lib'
 LIB_NAME = 'libsynchformer_hip.so'
-ABI_VERSION = 25    # 25: sf_track_stream_push_gated, sf_track_pool_push_gated and their three size queries (the fixed-lag read-outs of live feeds over (offset class, synchronizable flag): a 2C-wide carried state), and - additions under 25, nothing existing changed - sf_ingest_video_v210, sf_ingest_video_v210_fields (v210 frames and fields: 10-bit 4:2:2, three samples per 32-bit word); 24: sf_track_decode_gated, sf_track_posterior_gated (the offline read-outs of one chain over (offset class, synchronizable flag): a second, 2-way head gates the offset track); 23: sf_resample_wave_mix (several audio programmes of one multi-channel wave: planar or interleaved fp32 / s16 / s32, a (P, ch) mix matrix, P resampled rows from one read of the input); 22: sf_ingest_video_fields, sf_ingest_video_yuv_planes_fields (interlaced recordings: the field nearest each 25 fps slot, resized on its own); 21: sf_ingest_video_yuv_planes (the general YUV ingest entry: 4:2:2 packed, planar and semi-planar, 8- and 10-bit; three planes at any offsets and strides); 20: sf_track_pool_push, sf_track_pool_workspace_bytes (the fixed-lag read-out of many streams in one call: a descriptor table, launches independent of the stream count); 19: sf_track_stream_push, sf_track_stream_bytes, sf_track_stream_workspace_bytes (fixed-lag read-out of a stream of window logits with carried state); 18: sf_track_posterior (forward-backward marginals of the track chain: post, cls_post, conf_post, offset_mean, log_z); 17: sf_ingest_video_yuv16 (P010 / yuv420p10le frames: 10-bit 4:2:0 through the same resize pipeline); 16: sf_ingest_video_yuv (NV12 / I420 frames: YUV 4:2:0 to RGB inside the resize kernel); 15: sf_ingest_video, sf_resample_wave (a recording at its native frame rate, size and sample rate); 14: sf_track_decode (per-window argmax + Viterbi path over a recording's window logits); 13: sf_stage1_video_augment, sf_stage1_audio_augment (Stage-1 train-time augmentations from raw clips); 12: sf_agg_cls_pool (the aggregators' CLS query pooled in one pass), sf_gemm_res_ln768_periodic (patch embedding + position table + norm3 in one launch); 11: sf_im2col_video_crops, sf_mel_frontend_starts (train-time inputs from raw clips); 10: sf_scale_rows_map (whole-token dropout of the sync transformer's inputs); 9: key-mask forms of the round-4 fused attention launches (sf_qkv_space_attention_masked, sf_qkv_time_attention2_masked), sf_qkv_time_attention2_mx, sf_side_rows, sf_gemm_bf16 config 12; 8: sf_qkv_time_attention2; 7: sf_qkv_space_attention (round 4); 6: sf_layernorm768_bwd_branch; 5: the CLS query inside the grouped attention backward kernels (sf_attention_{group,tiny}_bwd_clsq, sf_attention_cls(_combine)_stats); 4: MXFP8-output attention launches (sf_attention_cls_partial_mx, sf_attention_cls_combine_mx, sf_qkv_time_attention_mx_q); 3: round 3, second half (sf_gemm_mx_res_ln768, sf_qkv_time_attention_mx, sf_gemm_tn_pp, sf_branch_grad, ... added); 2: sf_gemm_res_ln_force_schedule
+ABI_VERSION = 25    # 25 (additions, nothing existing changed): sf_track_decode_wide, sf_track_posterior_wide, sf_track_wide_workspace_bytes (the wide chain); 25: sf_track_stream_push_gated, sf_track_pool_push_gated and their three size queries (the fixed-lag read-outs of live feeds over (offset class, synchronizable flag): a 2C-wide carried state), and - additions under 25, nothing existing changed - sf_ingest_video_v210, sf_ingest_video_v210_fields (v210 frames and fields: 10-bit 4:2:2, three samples per 32-bit word); 24: sf_track_decode_gated, sf_track_posterior_gated (the offline read-outs of one chain over (offset class, synchronizable flag): a second, 2-way head gates the offset track); 23: sf_resample_wave_mix (several audio programmes of one multi-channel wave: planar or interleaved fp32 / s16 / s32, a (P, ch) mix matrix, P resampled rows from one read of the input); 22: sf_ingest_video_fields, sf_ingest_video_yuv_planes_fields (interlaced recordings: the field nearest each 25 fps slot, resized on its own); 21: sf_ingest_video_yuv_planes (the general YUV ingest entry: 4:2:2 packed, planar and semi-planar, 8- and 10-bit; three planes at any offsets and strides); 20: sf_track_pool_push, sf_track_pool_workspace_bytes (the fixed-lag read-out of many streams in one call: a descriptor table, launches independent of the stream count); 19: sf_track_stream_push, sf_track_stream_bytes, sf_track_stream_workspace_bytes (fixed-lag read-out of a stream of window logits with carried state); 18: sf_track_posterior (forward-backward marginals of the track chain: post, cls_post, conf_post, offset_mean, log_z); 17: sf_ingest_video_yuv16 (P010 / yuv420p10le frames: 10-bit 4:2:0 through the same resize pipeline); 16: sf_ingest_video_yuv (NV12 / I420 frames: YUV 4:2:0 to RGB inside the resize kernel); 15: sf_ingest_video, sf_resample_wave (a recording at its native frame rate, size and sample rate); 14: sf_track_decode (per-window argmax + Viterbi path over a recording's window logits); 13: sf_stage1_video_augment, sf_stage1_audio_augment (Stage-1 train-time augmentations from raw clips); 12: sf_agg_cls_pool (the aggregators' CLS query pooled in one pass), sf_gemm_res_ln768_periodic (patch embedding + position table + norm3 in one launch); 11: sf_im2col_video_crops, sf_mel_frontend_starts (train-time inputs from raw clips); 10: sf_scale_rows_map (whole-token dropout of the sync transformer's inputs); 9: key-mask forms of the round-4 fused attention launches (sf_qkv_space_attention_masked, sf_qkv_time_attention2_masked), sf_qkv_time_attention2_mx, sf_side_rows, sf_gemm_bf16 config 12; 8: sf_qkv_time_attention2; 7: sf_qkv_space_attention (round 4); 6: sf_layernorm768_bwd_branch; 5: the CLS query inside the grouped attention backward kernels (sf_attention_{group,tiny}_bwd_clsq, sf_attention_cls(_combine)_stats); 4: MXFP8-output attention launches (sf_attention_cls_partial_mx, sf_attention_cls_combine_mx, sf_qkv_time_attention_mx_q); 3: round 3, second half (sf_gemm_mx_res_ln768, sf_qkv_time_attention_mx, sf_gemm_tn_pp, sf_branch_grad, ... added); 2: sf_gemm_res_ln_force_schedule
 SF_NOT_APPLICABLE = -2   # include/synchformer_hip.h: "this launcher does not serve the shape, nothing was launched" (never a hipError_t)
 
 _i64, _i32, _f32, _ptr = C.c_int64, C.c_int, C.c_float, C.c_void_p
@@ -112,6 +112,11 @@ SIGNATURES = {
     'sf_track_pool_gated_workspace_bytes': [_i32, _i32, _i32],
     'sf_track_pool_push_gated': [_ptr, _i64, _i32, _i32, _i32, _i32, _ptr, _ptr, _i32, _ptr, _i64, _ptr, _i64, _i32, _f32, _f32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr,
                                  _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
+    # the wide chain (additions under ABI 25): whole-recording read-outs over S <= 1024 states at uneven positions (D lags x C classes)
+    'sf_track_wide_workspace_bytes': [_i32, _i32, _i32, _i32, _ptr],
+    'sf_track_decode_wide': [_ptr, _i64, _i64, _ptr, _i64, _i64, _i32, _i32, _i32, _i32, _ptr, _ptr, _ptr, _ptr, _f32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
+    'sf_track_posterior_wide': [_ptr, _i64, _i64, _ptr, _i64, _i64, _i32, _i32, _i32, _i32, _ptr, _ptr, _ptr, _ptr, _f32, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr,
+                                _ptr, _ptr],
     'sf_ingest_video': [_ptr, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _ptr, _ptr, _ptr, _i32, _ptr, _ptr, _i32, _ptr, _i32, _ptr],
     'sf_resample_wave': [_ptr, _i32, _i32, _i64, _i64, _ptr, _i32, _i32, _i32, _i32, _ptr, _i64, _ptr],
     'sf_resample_wave_mix': [_ptr, _i32, _i32, _i64, _i64, _i64, _ptr, _i32, _ptr, _i32, _i32, _i32, _i32, _ptr, _i64, _i64, _ptr],

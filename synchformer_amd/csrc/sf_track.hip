@@ -29,6 +29,7 @@
 // one stream, sf_track_pool_push(_gated) many in one call: the same launches over a descriptor table, blockIdx.y = the stream, every block running the single-stream
 // bodies on its stream's context.  Every extern "C" entry packs its arguments (a chain's Src, a TrackStreamOut) and calls a launcher template.
 #include "sf_common.h"
+#include "sf_track_math.h"
 #include "../../include/synchformer_hip.h"
 #include <algorithm>
 #include <cmath>
@@ -90,7 +91,7 @@ __device__ __forceinline__ float track_viterbi_step(const float* s_prev, int C, 
 // Log domain throughout (a scaled linear-domain recursion underflows: exp(-lam * 20 steps) is 0 in fp32 at lam = 8).  -inf is a masked class: every
 // subtraction that could meet (-inf) - (-inf) is guarded (fb_finite_or_zero on the subtrahend), so a row with one finite logit produces no NaN.
 
-__device__ __forceinline__ float fb_finite_or_zero(float m) { return (m > -INFINITY && m < INFINITY) ? m : 0.f; }      // false for NaN too
+// (fb_finite_or_zero: sf_track_math.h, shared with the wide chain)
 
 // lse_p (u[p] - lam * |p - c|) over the C4 = C rounded up to 4 entries of u (LDS; entries >= C hold -inf and add exp(-inf) = +0: the sum is the sum over
 // p < C in ascending p, bit for bit).  A max pass, then a sum-of-exp pass.  All lanes read the same address: the LDS broadcasts.
@@ -166,7 +167,7 @@ __device__ __forceinline__ int track_wave_end_state(float s, bool live) {
 // (Viterbi) / lse (forward-backward) from its partner lane (m, c) <-> (1 - m, c), which has just computed exactly that: max_p (s[p, 1-m] - lam |p - c|) - mu.
 #define TRACK_GATE_MAX_C 32
 
-__device__ __forceinline__ float gate_softplus(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
+// (gate_softplus: sf_track_math.h, shared with the wide chain)
 
 // What a lane of the gated scans is: its state's plane m and class c, its partner's lane.  Idle lanes (j >= 2C) act as state 0 and are their own partner.
 // lane: the thread's lane in its wavefront - threadIdx.x in the one-wave blocks of the scans.

@@ -909,6 +909,31 @@ class SynchformerEngine:
                 logits[p, w0:w0 + nw].copy_(self._sync_stack(v2, a2, nw, Sv, Sa, src_maps=maps))
         return logits
 
+    def sync_windows_lagged(self, vbank: torch.Tensor, abank: torch.Tensor, lags, hop: int = 1, win_chunk: int = 256, n_window: int = 14) -> torch.Tensor:
+        """sync_windows with the audio moved by whole segments: banks (N, tv, 768) / (N, ta, 768), lags strictly ascending integers (segments) ->
+        logits (W, D, n_out) fp32: window w at lag lags[j] pairs visual segments [v0 + w hop, + n_window) with audio segments [v0 + lags[j] + w hop, + n_window)
+        (frontend.lagged_window_geometry: v0, and the W every lag shares).  vproj / aproj run once over the banks; a lag is sync_windows' launch with another
+        origin of the audio row map, so no tower and no projection runs again.  Works as it stands on a towers=False engine with n_window = its own."""
+        from .frontend import lagged_window_geometry
+        if vbank.dim() != 3 or abank.dim() != 3 or vbank.shape[0] != abank.shape[0] or vbank.shape[2] != D or abank.shape[2] != D:
+            raise ValueError(f'sync_windows_lagged: expected banks (N, tv, {D}) / (N, ta, {D}), got {tuple(vbank.shape)} / {tuple(abank.shape)}')
+        if win_chunk < 1:
+            raise ValueError(f'sync_windows_lagged: win_chunk = {win_chunk}')
+        g = lagged_window_geometry(int(vbank.shape[0]), lags, hop, n_window)
+        W, v0, lags = g['n_windows'], g['v0'], g['lags']
+        tv, ta = vbank.shape[1], abank.shape[1]
+        Sv, Sa = n_window * tv, n_window * ta
+        self._sync_table(Sv, Sa)                                                # ValueError when pos_emb is too short for one window
+        v2 = self.project(vbank.to(self.dev, torch.float32).unsqueeze(0), 'v')[0]
+        a2 = self.project(abank.to(self.dev, torch.float32).unsqueeze(0), 'a')[0]
+        logits = torch.empty(W, len(lags), self.n_out, device=self.dev, dtype=torch.float32)
+        for j, d in enumerate(lags):
+            for w0 in range(0, W, win_chunk):
+                nw = min(win_chunk, W - w0)
+                maps = (ops.rowmap(Sv, Sv, hop * tv, 0, 1, (v0 + w0 * hop) * tv), ops.rowmap(Sa, Sa, hop * ta, 0, 1, (v0 + d + w0 * hop) * ta))
+                logits[w0:w0 + nw, j].copy_(self._sync_stack(v2, a2, nw, Sv, Sa, src_maps=maps))
+        return logits
+
     def sync_transformer(self, vfeat: torch.Tensor, afeat: torch.Tensor) -> torch.Tensor:
         """vproj/aproj + GlobalTransformer: segment features (B,S,tv,768) / (B,S,ta,768) fp32 -> logits (B, n_out)."""
         return self.global_transformer(self.project(vfeat, 'v'), self.project(afeat, 'a'))

@@ -97,6 +97,23 @@ def stream_geometry(v_len_frames: int, a_len_frames: int, segments_done: int, ho
                 features_from=min(hop_segments * n_win, n_seg))
 
 
+def lagged_window_geometry(n_segments: int, lags, hop: int = 1, n_window: int = 14) -> dict:
+    """The windows of a search over audio lags (engine.sync_windows_lagged): pure host arithmetic.  lags: strictly ascending integers, in segments
+    (0.32 s each), possibly negative.  Window w at lag d pairs visual segments [v0 + w hop, + n_window) with audio segments [v0 + d + w hop, + n_window), so its audio
+    starts 0.32 d s after its picture (a_start = v_start + offset_sec); v0 = max(0, -lags[0]) keeps the most negative lag inside the bank, and every lag has the same
+    W = (n_segments - n_window - v0 - max(0, lags[-1])) // hop + 1 windows -> dict(n_windows, v0, lags, hop, n_window).  ValueError when W < 1."""
+    lags = [int(d) for d in lags]
+    if len(lags) < 1 or any(b <= a for a, b in zip(lags, lags[1:])):
+        raise ValueError(f'lagged_window_geometry: lags {lags}: at least one, strictly ascending')
+    if hop < 1 or n_window < 1:
+        raise ValueError(f'lagged_window_geometry: hop = {hop}, n_window = {n_window}')
+    v0 = max(0, -lags[0])
+    room = int(n_segments) - n_window - v0 - max(0, lags[-1])
+    if room < 0:
+        raise ValueError(f'lagged_window_geometry: {n_segments} segments hold no window of {n_window} at lags {lags[0]} .. {lags[-1]}')
+    return dict(n_windows=room // hop + 1, v0=v0, lags=lags, hop=int(hop), n_window=int(n_window))
+
+
 class MelFrontend:
     def __init__(self, device, sample_rate=16000, n_mels=128, pad_to=66, mean=AST_MEAN, std=AST_STD):
         self.dev = torch.device(device)

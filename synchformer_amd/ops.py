@@ -753,6 +753,127 @@ def track_posterior_gated(logits: torch.Tensor, gate_logits: torch.Tensor, lam: 
     return post, p_sync, cls_post, conf_post, offset_mean, log_z
 
 
+TRACK_WIDE_MAX_S, TRACK_WIDE_MAX_D = 1024, 1024      # sf_track_wide.hip: one thread per state in one workgroup; lags per window
+
+
+def track_wide_states(lags, grid, seg_sec: float = 0.32):
+    """The states of a search over audio lags, on the host in float64: lags ascending integers (segments of seg_sec seconds), grid (C,) the offsets
+    of the classes -> (state_src int32, pos fp32, off fp32, lag_of int32, cls_of int32), CPU tensors of S = D C entries.  State (lag index d, class c) stands for the
+    offset seg_sec * lags[d] + grid[c] (a_start = v_start + offset_sec); offsets are taken to the microsecond, so that 0.32 * 5 - 1.6 and 0.0 coincide (precondition: grid and seg_sec in whole microseconds up to fp32
+    resolution; ValueError otherwise, nothing is quantised silently).  The states
+    are sorted by (offset, d, c); state_src = d * C + c, lag_of = d (the INDEX into lags), cls_of = c, off the offset in seconds, pos = off / (grid[1] - grid[0]):
+    the position in class steps, which is what `lam` is charged on.  lags = (0,) with the default grid gives pos = c - 10 exactly."""
+    lags = [int(d) for d in lags]
+    g = torch.as_tensor(grid).detach().cpu().double()
+    if len(lags) < 1 or any(b <= a for a, b in zip(lags, lags[1:])) or g.dim() != 1 or g.numel() < 2:
+        raise ValueError(f'track_wide_states: lags {lags} (at least one, strictly ascending), a grid of {tuple(g.shape)}')
+    C = g.numel()
+    sec = [[seg_sec * d + float(g[c]) for c in range(C)] for d in lags]
+    us = [[int(round(v * 1e6)) for v in row] for row in sec]
+    step = int(round(float(g[1] - g[0]) * 1e6))
+    if step <= 0:
+        raise ValueError(f'track_wide_states: the grid steps by {float(g[1] - g[0])} s')
+    # PRECONDITION: the offsets lie on the microsecond lattice up to what an fp32 grid can say (2^-22 relative, 0.24 us at 1 s).  A grid that does not - a step of
+    # 1/3 s - would be quantised silently, and two of its offsets could be merged or split by the rounding: refuse it.
+    worst = max(abs(u / 1e6 - v) / max(1.0, abs(v)) for ru, rv in zip(us, sec) for u, v in zip(ru, rv))
+    if worst > 2.0 ** -22 or abs(step / 1e6 - float(g[1] - g[0])) > 2.0 ** -22:
+        raise ValueError(f'track_wide_states: the offsets seg_sec * lag + grid[c] are taken to the microsecond, and this grid / seg_sec = {seg_sec} is off that lattice '
+                         f'by up to {worst:.2e} (relative): give a grid in whole microseconds')
+    order = sorted((us[j][c], j, c) for j in range(len(lags)) for c in range(C))
+    key = torch.tensor([o[0] for o in order], dtype=torch.float64)
+    lag_of = torch.tensor([o[1] for o in order], dtype=torch.int32)
+    cls_of = torch.tensor([o[2] for o in order], dtype=torch.int32)
+    return lag_of * C + cls_of, (key / step).float(), (key / 1e6).float(), lag_of, cls_of
+
+
+class TrackWideTables:
+    """The two tables of the wide read-outs as the launchers take them - host copies they validate, device copies the kernels read - plus the states' offsets on
+    the device.  Made once (track_wide_tables), before any graph capture; the ops only pass pointers."""
+
+    def __init__(self, state_src: torch.Tensor, pos: torch.Tensor, off: torch.Tensor, D: int, C: int, device):
+        self.D, self.C, self.S = int(D), int(C), int(state_src.numel())
+        self.src_host = state_src.detach().cpu().to(torch.int32).contiguous()
+        self.pos_host = pos.detach().cpu().to(torch.float32).contiguous()
+        off_host = off.detach().cpu().to(torch.float32).contiguous()
+        if not (self.src_host.dim() == 1 and self.pos_host.shape == self.src_host.shape == off_host.shape):
+            raise ValueError(f'track_wide_tables: state_src {tuple(state_src.shape)}, pos {tuple(pos.shape)}, off {tuple(off.shape)}')
+        if not (2 <= self.S <= TRACK_WIDE_MAX_S and 1 <= self.D <= TRACK_WIDE_MAX_D and self.S <= self.D * self.C):
+            raise ValueError(f'track_wide_tables: S = {self.S} states (2 .. {TRACK_WIDE_MAX_S}) for D = {self.D} lags (1 .. {TRACK_WIDE_MAX_D}) x C = {self.C} classes')
+        self.src, self.pos, self.off = self.src_host.to(device), self.pos_host.to(device), off_host.to(device)
+
+
+def track_wide_tables(state_src: torch.Tensor, pos: torch.Tensor, off: torch.Tensor, D: int, C: int, device) -> TrackWideTables:
+    """state_src, pos, off as track_wide_states returns them (or any tables of the contract: S <= 1024 states in the caller's order, pos ascending) for logits
+    (W, D, C) -> the tables object track_decode_wide / track_posterior_wide take.  Copies to the device (synchronous, pageable memory): not under graph capture."""
+    return TrackWideTables(state_src, pos, off, D, C, device)
+
+
+def _wide_inputs(who: str, logits: torch.Tensor, tables: TrackWideTables, gate_logits: Optional[torch.Tensor]):
+    """The checks the two wide read-outs share -> (W, the six stride arguments): logits fp32 (W, D, C) with unit class stride, gate_logits fp32 (W, D, 2) or None."""
+    assert logits.dtype == torch.float32 and logits.dim() == 3 and tuple(logits.shape[1:]) == (tables.D, tables.C), \
+        f'{who}: logits {tuple(logits.shape)} for tables of D = {tables.D} lags x C = {tables.C} classes'
+    assert logits.device == tables.src.device, f'{who}: logits on {logits.device}, the tables on {tables.src.device}'
+    W = logits.shape[0]
+    assert W == 0 or logits.stride(2) == 1, f'{who}: logits: unit class stride'
+    ld = (logits.stride(0), logits.stride(1)) if W else (tables.D * tables.C, tables.C)
+    lg = (2 * tables.D, 2)
+    if gate_logits is not None:
+        assert gate_logits.dtype == torch.float32 and gate_logits.shape == (W, tables.D, 2) and gate_logits.device == logits.device, \
+            f'{who}: gate logits of {tuple(gate_logits.shape)} for {W} windows x {tables.D} lags'
+        assert W == 0 or gate_logits.stride(2) == 1, f'{who}: gate_logits: unit class stride'
+        if W:
+            lg = (gate_logits.stride(0), gate_logits.stride(1))
+    return W, ld, lg
+
+
+def _wide_workspace(W: int, tables: TrackWideTables, posterior: bool, dev) -> torch.Tensor:
+    n = C.c_int64(0)
+    _lib.check(_lib.load().sf_track_wide_workspace_bytes(W, tables.D, tables.S, int(posterior), C.addressof(n)), 'sf_track_wide_workspace_bytes')
+    return torch.empty(n.value, device=dev, dtype=torch.uint8)
+
+
+def track_decode_wide(logits: torch.Tensor, tables: TrackWideTables, lam: float, gate_logits: Optional[torch.Tensor] = None):
+    """The Viterbi read-out of the wide chain (sf_track_decode_wide): logits fp32 (W, D, C) on the tables' device (engine.sync_windows_lagged), rows in
+    time order, unit class stride, any row and lag stride; gate_logits fp32 (W, D, 2) or None -> (state_raw int32, conf_raw fp32, state_path int32, conf_path fp32),
+    (W,) each: the per-window argmax over the S states (lowest state on ties) with its softmax probability over all states, and the path under a cost `lam` per class
+    step of |pos| with that probability at the path's state.  tables.lag_of / cls_of of track_wide_states map a state back.  Allocates the outputs and the workspace."""
+    W, ld, lg = _wide_inputs('track_decode_wide', logits, tables, gate_logits)
+    dev = logits.device
+    state_raw, state_path = torch.empty(W, device=dev, dtype=torch.int32), torch.empty(W, device=dev, dtype=torch.int32)
+    conf_raw, conf_path = torch.empty(W, device=dev, dtype=torch.float32), torch.empty(W, device=dev, dtype=torch.float32)
+    ws = _wide_workspace(W, tables, False, dev)
+    rc = _lib.load().sf_track_decode_wide(_dev(logits, 'logits'), ld[0], ld[1], None if gate_logits is None else _dev(gate_logits, 'gate_logits'), lg[0], lg[1], W,
+                                          tables.D, tables.C, tables.S, tables.src_host.data_ptr(), tables.pos_host.data_ptr(), _dev(tables.src, 'state_src'),
+                                          _dev(tables.pos, 'pos'), float(lam), _dev(state_raw, 'state_raw'), _dev(conf_raw, 'conf_raw'),
+                                          _dev(state_path, 'state_path'), _dev(conf_path, 'conf_path'), _dev(ws, 'workspace'), _stream())
+    _lib.check(rc, 'sf_track_decode_wide')
+    return state_raw, conf_raw, state_path, conf_path
+
+
+def track_posterior_wide(logits: torch.Tensor, tables: TrackWideTables, lam: float, gate_logits: Optional[torch.Tensor] = None, post: Optional[torch.Tensor] = None):
+    """The posterior read-out of the wide chain (sf_track_posterior_wide): inputs as track_decode_wide -> (post fp32 (W, S), state_post int32 (W,), conf_post fp32
+    (W,), offset_mean fp32 (W,), p_lag fp32 (W, D), log_z fp32 (1,)): the marginals of the states, their argmax and its value, the posterior mean of tables.off
+    (seconds), the marginal of each lag, and the log partition sum (<= W log D without a gate, with equality at lam = 0).  Allocates the outputs and the workspace (`post`, if given, is written
+    instead: fp32 (W, S), unit column stride, any row stride >= S); nothing is read back: log_z stays on the device (0 for W = 0)."""
+    W, ld, lg = _wide_inputs('track_posterior_wide', logits, tables, gate_logits)
+    dev, S = logits.device, tables.S
+    if post is None:
+        post = torch.empty(W, S, device=dev, dtype=torch.float32)
+    assert post.dtype == torch.float32 and post.shape == (W, S) and post.device == dev and (W == 0 or post.stride(1) == 1), 'post: fp32 (W, S), unit column stride'
+    state_post = torch.empty(W, device=dev, dtype=torch.int32)
+    conf_post, offset_mean = torch.empty(W, device=dev, dtype=torch.float32), torch.empty(W, device=dev, dtype=torch.float32)
+    p_lag = torch.empty(W, tables.D, device=dev, dtype=torch.float32)
+    log_z = torch.empty(1, device=dev, dtype=torch.float32) if W else torch.zeros(1, device=dev, dtype=torch.float32)
+    ws = _wide_workspace(W, tables, True, dev)
+    rc = _lib.load().sf_track_posterior_wide(_dev(logits, 'logits'), ld[0], ld[1], None if gate_logits is None else _dev(gate_logits, 'gate_logits'), lg[0], lg[1], W,
+                                             tables.D, tables.C, S, tables.src_host.data_ptr(), tables.pos_host.data_ptr(), _dev(tables.src, 'state_src'),
+                                             _dev(tables.pos, 'pos'), float(lam), _dev(tables.off, 'off'), _dev(post, 'post'), post.stride(0) if W else S,
+                                             _dev(state_post, 'state_post'), _dev(conf_post, 'conf_post'), _dev(offset_mean, 'offset_mean'), _dev(p_lag, 'p_lag'),
+                                             _dev(log_z, 'log_z'), _dev(ws, 'workspace'), _stream())
+    _lib.check(rc, 'sf_track_posterior_wide')
+    return post, state_post, conf_post, offset_mean, p_lag, log_z
+
+
 def _pairwise_outputs(W: int, C: int, dev, xi: bool, n_float: int):
     """The outputs the two pairwise read-outs share: n_float fp32 vectors and top_from / top_to int32 of W - 1 rows, xi (W - 1, C, C) or None, log_z (1,)."""
     n = max(W - 1, 0)

@@ -132,6 +132,49 @@ class OffsetTrack:
         return out
 
 
+@dataclass
+class WideOffsetTrack:
+    """Read-out of one recording over a search of audio lags (OffsetTracker.track_features_wide, DESIGN 3.24): W windows in time order, D lags, S = D C states;
+    tensors on the engine's device.  State (lag d, class c) stands for the offset 0.32 d + grid[c] seconds (a_start = v_start + offset_sec)."""
+    t_sec: torch.Tensor              # (W,) fp32: centres of the windows' PICTURE, window_times + 0.32 first_segment
+    lags: tuple                      # the D lags, in segments of 0.32 s, ascending
+    logits: torch.Tensor             # (W, D, C) fp32: window w paired at lag lags[j]
+    gate_logits: Optional[torch.Tensor]   # (W, D, 2) fp32 with a gate (class 1 = synchronizable), else None
+    lag_raw: torch.Tensor            # (W,) int32: the lag (segments) of the per-window argmax over all states
+    cls_raw: torch.Tensor            # (W,) int32: its class
+    conf_raw: torch.Tensor           # (W,) fp32: its softmax probability over all states
+    offset_sec_raw: torch.Tensor     # (W,) fp32: its offset
+    state_path: torch.Tensor         # (W,) int32: the Viterbi path, as states of the table (ops.track_wide_states)
+    lag_path: torch.Tensor           # (W,) int32: the path's lag (segments)
+    cls_path: torch.Tensor           # (W,) int32: the path's class
+    conf_path: torch.Tensor          # (W,) fp32: the softmax probability of the path's state
+    offset_sec_path: torch.Tensor    # (W,) fp32: the path's offset
+    n_segments: int                  # segments in the bank
+    first_segment: int               # v0: the visual segment window 0 starts at (max(0, -lags[0]))
+    # the posterior read-out (OffsetTracker(posterior=True), ops.track_posterior_wide); None without it
+    post: Optional[torch.Tensor] = None              # (W, S) fp32: marginal of state s in window w given all windows
+    p_lag: Optional[torch.Tensor] = None             # (W, D) fp32: marginal of each lag
+    state_post: Optional[torch.Tensor] = None        # (W,) int32: argmax_s post
+    conf_post: Optional[torch.Tensor] = None         # (W,) fp32: its value
+    offset_sec_post: Optional[torch.Tensor] = None   # (W,) fp32: the offset of state_post
+    offset_sec_mean: Optional[torch.Tensor] = None   # (W,) fp32: sum_s post[w, s] offset[s]
+    log_z: Optional[torch.Tensor] = None             # (1,) fp32: log partition sum, <= W log D without a gate
+
+    def spans(self):
+        """Host side, as OffsetTrack.spans over offset_sec_path: the runs of a constant path state as (t0_sec, t1_sec, offset_sec), in time order; neighbouring spans
+        meet half-way between their windows' centres.  Two states of one offset (0.32 * 5 - 1.6 = 0.0) are one run.  Synchronises."""
+        t = self.t_sec.detach().cpu().double().tolist()
+        off = self.offset_sec_path.detach().cpu().tolist()
+        out, a = [], 0
+        for w in range(1, len(off) + 1):
+            if w == len(off) or off[w] != off[a]:
+                t0 = t[a] if a == 0 else 0.5 * (t[a - 1] + t[a])
+                t1 = t[w - 1] if w == len(off) else 0.5 * (t[w - 1] + t[w])
+                out.append((t0, t1, float(off[a])))
+                a = w
+        return out
+
+
 class OffsetTracker:
     """engine: a SynchformerEngine; mel: a frontend.MelFrontend on the same device; hop_segments: windows advance by this many segments (1 = 0.32 s);
     lam: cost of one class step between neighbouring windows in the Viterbi read-out, in logit units (0 = the per-window argmax; large = one class for the
@@ -175,6 +218,7 @@ class OffsetTracker:
                 raise ValueError(f'gate: its window of {gate.n_window} segments does not fit the offset window of {engine.n_window} it is start-aligned with')
         self.gate, self.mu = gate, float(mu)
         self.pairwise = bool(pairwise)
+        self._wide_cache = {}                                                    # lags -> the wide read-outs' tables on the device (_wide_tables)
 
     def track_features(self, vbank: torch.Tensor, abank: torch.Tensor, win_chunk: int = 256) -> OffsetTrack:
         """Segment feature banks (N, 8, 768) / (N, 6, 768) (engine.extract_recording, or features the caller already holds) -> OffsetTrack."""
@@ -211,6 +255,74 @@ class OffsetTracker:
             track.t_change = 0.5 * (track.t_sec[:-1] + track.t_sec[1:])
             track.change_from_sec, track.change_to_sec = self.grid[top_from.long()], self.grid[top_to.long()]
         return track
+
+    WIDE_TABLES_KEPT = 8                                                         # sets of lags whose tables stay on the device (the oldest goes first)
+
+    def _wide_tables(self, lags):
+        """The states of a search over `lags` (ops.track_wide_states on the tracker's grid) and their tables on the device, kept for the last WIDE_TABLES_KEPT sets
+        of lags -> (lags as a tuple, ops.TrackWideTables, lag values (S,) int32, classes (S,) int32 on the device)."""
+        lags = tuple(int(d) for d in lags)
+        if lags not in self._wide_cache:
+            src, pos, off, lag_of, cls_of = ops.track_wide_states(lags, self.grid)
+            tables = ops.track_wide_tables(src, pos, off, len(lags), int(self.grid.numel()), self.eng.dev)
+            lag_val = torch.tensor(lags, dtype=torch.int32)[lag_of.long()]
+            while len(self._wide_cache) >= self.WIDE_TABLES_KEPT:
+                self._wide_cache.pop(next(iter(self._wide_cache)))
+            self._wide_cache[lags] = (lags, tables, lag_val.to(self.eng.dev), cls_of.to(self.eng.dev))
+        return self._wide_cache[lags]
+
+    def track_features_wide(self, vbank: torch.Tensor, abank: torch.Tensor, lags, win_chunk: int = 256) -> WideOffsetTrack:
+        """track_features beyond the class grid: the banks are read at every lag of `lags` (strictly ascending integers, segments of 0.32 s; D lags x C
+        classes <= 1024 states) through engine.sync_windows_lagged - no tower runs again - and the (W, D, C) logits are read out by track_logits_wide; `lam` keeps
+        its meaning, the cost of one class step.  A tracker with a gate passes its logits at the same lags as the emission's gate term.  What the model's logits look
+        like at a lag whose residual lies outside the grid is NOT known here (no trained checkpoint): the read-out is the chain's, whatever it is fed."""
+        lags = tuple(int(d) for d in lags)
+        logits = self.eng.sync_windows_lagged(vbank, abank, lags, hop=self.hop, win_chunk=win_chunk)
+        gate_logits = None
+        if self.gate is not None:                                                # start-aligned windows of the gate's own length at the same lags: the first W rows
+            gate_logits = self.gate.sync_windows_lagged(vbank, abank, lags, hop=self.hop, win_chunk=win_chunk, n_window=self.gate.n_window)
+            if gate_logits.shape[0] < logits.shape[0]:
+                raise ValueError(f'track_features_wide: the gate\'s window of {self.gate.n_window} segments gives {gate_logits.shape[0]} windows at these lags, the offset '
+                                 f'window of {self.eng.n_window} segments {logits.shape[0]}: the gate\'s window must not be the longer one')
+            gate_logits = gate_logits[:logits.shape[0]]
+        return self.track_logits_wide(logits, lags, gate_logits, n_segments=int(vbank.shape[0]))
+
+    def track_logits_wide(self, logits: torch.Tensor, lags, gate_logits: Optional[torch.Tensor] = None, n_segments: Optional[int] = None) -> WideOffsetTrack:
+        """The read-out of window logits the caller already holds: logits fp32 (W, D, C) on the engine's device, window w paired at lag lags[j] (what
+        engine.sync_windows_lagged returns), gate_logits fp32 (W, D, 2) or None -> WideOffsetTrack, through ops.track_decode_wide (with posterior=True also
+        ops.track_posterior_wide) over the states (lag, class) at the offsets 0.32 lag + grid[c].  n_segments: the bank's length, for the track's record (default: the
+        shortest bank that holds these windows)."""
+        lags, tables, lag_val, cls_val = self._wide_tables(lags)
+        if logits.dim() != 3 or tuple(logits.shape[1:]) != (len(lags), int(self.grid.numel())):
+            raise ValueError(f'track_logits_wide: logits {tuple(logits.shape)} for {len(lags)} lags x {int(self.grid.numel())} classes')
+        v0 = max(0, -lags[0])
+        if n_segments is None:
+            n_segments = v0 + max(0, lags[-1]) + self.eng.n_window + self.hop * max(0, logits.shape[0] - 1)
+        state_raw, conf_raw, state_path, conf_path = ops.track_decode_wide(logits, tables, self.lam, gate_logits)
+        raw, path = state_raw.long(), state_path.long()
+        seg_sec = 0.32
+        track = WideOffsetTrack(t_sec=(window_times64(logits.shape[0], self.hop) + seg_sec * v0).float().to(self.eng.dev), lags=lags, logits=logits,
+                                gate_logits=gate_logits, lag_raw=lag_val[raw], cls_raw=cls_val[raw], conf_raw=conf_raw, offset_sec_raw=tables.off[raw],
+                                state_path=state_path, lag_path=lag_val[path], cls_path=cls_val[path], conf_path=conf_path, offset_sec_path=tables.off[path],
+                                n_segments=int(n_segments), first_segment=v0)
+        if self.posterior:
+            track.post, track.state_post, track.conf_post, track.offset_sec_mean, track.p_lag, track.log_z = ops.track_posterior_wide(logits, tables, self.lam,
+                                                                                                                                       gate_logits)
+            track.offset_sec_post = tables.off[track.state_post.long()]
+        return track
+
+    def track_wide(self, frames: torch.Tensor, wave: torch.Tensor, lags, seg_chunk: Optional[int] = None, win_chunk: int = 256) -> WideOffsetTrack:
+        """track() over a search of audio lags: inputs as track(), `lags` as track_features_wide -> WideOffsetTrack."""
+        return self.track_features_wide(*self.eng.extract_recording(frames, wave, self.mel, seg_chunk), lags, win_chunk=win_chunk)
+
+    def track_raw_wide(self, raw_frames: torch.Tensor, raw_wave: torch.Tensor, ingest, lags, seg_chunk: Optional[int] = None, win_chunk: int = 256) -> WideOffsetTrack:
+        """track_raw() over a search of audio lags: inputs as track_raw(), `lags` as track_features_wide -> WideOffsetTrack."""
+        if getattr(ingest, 'programmes', None) is not None:
+            raise ValueError(f'track_raw_wide: the ingest has {len(ingest.programmes)} audio programmes; the wide read-out serves one')
+        ingest._check_frames(raw_frames)
+        wave = ingest.wave(raw_wave)
+        banks = self.eng.extract_recording_from(lambda f0, f1: ingest.frames(raw_frames, f0, f1), ingest.n_frames(raw_frames.shape[0]), wave, self.mel, seg_chunk)
+        return self.track_features_wide(*banks, lags, win_chunk=win_chunk)
 
     def track_features_programmes(self, vbank: torch.Tensor, abanks: torch.Tensor, win_chunk: int = 256) -> List[OffsetTrack]:
         """One visual bank (N, 8, 768) and the audio banks of P programmes (P, N, 6, 768) (engine.extract_recording_programmes_from) -> one OffsetTrack per

@@ -31,6 +31,10 @@ windows flagged not synchronizable, and the spans (start s, end s, offset s or n
 time through the gated stream (OffsetTracker.stream(lag, gated=True)): 'stream_gated' carries the same per-stage times plus the gate's windows, the
 committed windows flagged not synchronizable, whether logits and gate_logits equal the offline track's, and what the gate adds per push beside 'stream' of this run.
 
+With --lags A:B[:STEP] (written --lags=-12:12 when A is negative) the same bank is also read out over the audio lags A .. B (whole segments of 0.32 s: offsets beyond the +-2 s class grid) through
+OffsetTracker.track_features_wide: 'wide' carries the lags, the states, the windows every lag shares, the time of the wide track beside the plain track's of this run
+(and of its lagged windows alone), and the spans (start s, end s, offset s) of WideOffsetTrack.spans(), which are printed to stderr as well.
+
 With --stream SECONDS the recording is also pushed through OffsetTracker.stream(lag) in pieces of that many seconds (from raw input when --fps /
 --size / --rate are given): the line then carries, per push, the milliseconds of the bank (the towers on the segments the push completed), the windows (the sync
 transformer on the windows it completed) and the read-out (ops.track_stream_push) - each timed by wall clock between device synchronisations, which a
@@ -80,6 +84,7 @@ def main():
     ap.add_argument('--lag', type=int, default=16, help='decision lag of the stream, in windows')
     ap.add_argument('--gate', action='store_true', help='also gate the track by a synthetic 2-way syncability engine (towers=False) on the same bank')
     ap.add_argument('--mu', type=float, default=2.0, help='cost of one change of the synchronizable flag (with --gate)')
+    ap.add_argument('--lags', default=None, metavar='A:B[:STEP]', help='also read the bank out over the audio lags A .. B (segments of 0.32 s): offsets beyond +-2 s; write --lags=-12:12 when A is negative')
     ap.add_argument('--programmes', default=None, help="audio programmes of the wave's channels, e.g. 0+1,2+3,4: one offset track per programme against one pass of the picture")
     ap.add_argument('--audio-channels', type=int, default=None, help='channels of the raw wave (with --programmes; default: the highest channel named + 1)')
     ap.add_argument('--audio-interleaved', action='store_true', help='the raw wave is (n, ch), as a feed delivers it (with --programmes)')
@@ -217,6 +222,19 @@ def main():
             extra['gate'].update({'expected_changes': round(gtrack.expected_changes(), 3), 'expected_flips': round(gtrack.p_flip.double().sum().item(), 3)})
         for t0, t1, off in spans:
             print(f'span {t0:8.2f} s .. {t1:8.2f} s  ' + ('not synchronizable' if off is None else f'offset {off:+.2f} s'), file=sys.stderr)
+    if args.lags is not None:                                                    # the wide read-out: a search over audio lags beyond the class grid
+        lo, hi, *st = [int(x) for x in args.lags.split(':')]
+        lags = tuple(range(lo, hi + 1, st[0] if st else 1))
+        t_wide, wtrack = timed(lambda: tracker.track_features_wide(vbank, abank, lags, win_chunk=args.win_chunk), reps=3)
+        t_lw, _ = timed(lambda: eng.sync_windows_lagged(vbank, abank, lags, hop=args.hop, win_chunk=args.win_chunk), reps=3)
+        wspans = wtrack.spans()
+        extra['wide'] = {'lags': [lags[0], lags[-1], lags[1] - lags[0] if len(lags) > 1 else 1], 'states': len(lags) * int(tracker.grid.numel()),
+                         'windows': int(wtrack.logits.shape[0]), 'first_segment': wtrack.first_segment, 'wide_track_s': round(t_wide, 5), 'plain_track_s': round(t_win, 5),
+                         'lagged_windows_s': round(t_lw, 5), 'wide_readout_s': round(t_wide - t_lw, 6),
+                         'spans': [[round(t0, 2), round(t1, 2), round(off, 3)] for t0, t1, off in wspans]}
+        print(f'wide read-out over lags {lags[0]} .. {lags[-1]}: {t_wide * 1e3:.2f} ms (plain track {t_win * 1e3:.2f} ms)', file=sys.stderr)
+        for t0, t1, off in wspans:
+            print(f'wide span {t0:8.2f} s .. {t1:8.2f} s  offset {off:+.2f} s', file=sys.stderr)
     if args.stream is not None:
         source = (raw, raw_wave, ing) if raw_mode else (src[0], src[1], None)
         extra['stream'] = stream_timing(args, tracker, eng, ops, source, track)
