@@ -61,10 +61,7 @@ __device__ __forceinline__ float4 ap_ldg_nt(const float* p) {   // X rows are re
 // Sum over the wave, the same bits in every lane: four DPP adds give every lane its 16-lane row's sum (quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror,
 // row_mirror), the four row sums are then read as scalars - no ds_bpermute round trips and no lane-address registers (wave_sum's butterfly costs six).
 __device__ __forceinline__ float ap_wave_sum(float x) {
-  x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xF, 0xF, true));
-  x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x4E, 0xF, 0xF, true));
-  x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x141, 0xF, 0xF, true));
-  x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x140, 0xF, 0xF, true));
+  x = sum16_dpp(x);
   const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 0)), r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 16));
   const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 48));
   return (r0 + r1) + (r2 + r3);

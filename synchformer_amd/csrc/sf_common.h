@@ -107,6 +107,12 @@ __device__ __forceinline__ float sum8_dpp(float x) {
   x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x141, 0xF, 0xF, true));
   return x;
 }
+// Sum over the 16 lanes of a DPP row (lanes sharing lane >> 4), every lane of the row ends with the total: the same and row_mirror.
+__device__ __forceinline__ float sum16_dpp(float x) {
+  x = sum8_dpp(x);
+  x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x140, 0xF, 0xF, true));
+  return x;
+}
 
 // ---- wave reductions ------------------------------------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {

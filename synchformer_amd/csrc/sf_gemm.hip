@@ -8,7 +8,7 @@
 // (as patch-gather GEMMs), vproj/aproj and the offset head.
 //
 // Structure (per workgroup = one BM x BN output tile):
-//   * operand tiles go HBM/L2 -> LDS directly (global_load_lds_dwordx4: 1 KiB per wave-instruction) into an
+//   * operand tiles go HBM/L2 -> LDS directly (LDS-DMA: 1 KiB per wave-instruction) into an
 //     NS-deep ring of BK-wide stages; NS-1 stages are kept in flight with COUNTED s_waitcnt vmcnt(N) and one raw
 //     s_barrier per K-step (never vmcnt(0) in the steady state) - with K as short as 768 the loop is bound by
 //     operand-delivery latency, not MFMA rate, unless several stages are outstanding (profiles/r01 notes).
@@ -130,9 +130,9 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::MIN_WAVES_PER_SIMD) void gemm_bf
     for (int kt = 0; kt < nk; ++kt) {
       // wait until tile kt has landed: only the (<= NS-2) younger stages may still be outstanding
       const int ahead = min(NS - 2, nk - 1 - kt);
-      if (NS >= 4 && ahead >= 2) wait_vmcnt_barrier<2 * P>();
-      else if (NS >= 3 && ahead == 1) wait_vmcnt_barrier<P>();
-      else wait_vmcnt_barrier<0>();
+      if (NS >= 4 && ahead >= 2) sf_wait_vmcnt_barrier<2 * P>();
+      else if (NS >= 3 && ahead == 1) sf_wait_vmcnt_barrier<P>();
+      else sf_wait_vmcnt_barrier<0>();
       // every wave has passed compute(kt-1): slot `fill` (== slot of tile kt-1) is free -> refill with tile kt+NS-1
       if (kt + NS - 1 < nk) stage(fill, kt + NS - 1);
       const char* sa = smem + cur * Cfg::STAGE;
@@ -174,12 +174,12 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::MIN_WAVES_PER_SIMD) void gemm_bf
     };
     auto sync_for = [&](int tile) {   // make `tile` visible: younger stages (<= NS-3 of them) may stay in flight
       const int ahead = min(NS - 3, nk - 1 - tile);
-      if (ahead >= 1) wait_vmcnt_barrier<P>(); else wait_vmcnt_barrier<0>();
+      if (ahead >= 1) sf_wait_vmcnt_barrier<P>(); else sf_wait_vmcnt_barrier<0>();
     };
     static_assert(NS == 4, "sync_for() is written for a 4-deep ring");
     bf16x8 a0[FI], b0[FJ], a1[FI], b1[FJ];
     // tile 0
-    { const int ahead = min(NS - 2, nk - 1); if (ahead >= 2) wait_vmcnt_barrier<2 * P>(); else if (ahead == 1) wait_vmcnt_barrier<P>(); else wait_vmcnt_barrier<0>(); }
+    { const int ahead = min(NS - 2, nk - 1); if (ahead >= 2) sf_wait_vmcnt_barrier<2 * P>(); else if (ahead == 1) sf_wait_vmcnt_barrier<P>(); else sf_wait_vmcnt_barrier<0>(); }
     load_frags(0, a0, b0);
     int kt = 0;
     for (; kt + 1 < nk; kt += 2) {             // two tiles per trip so fragment buffers are statically named
@@ -225,10 +225,10 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::MIN_WAVES_PER_SIMD) void gemm_bf
       float4 res[2][4];
 #pragma unroll
       for (int ps = 0; ps < 4; ++ps) res[0][ps] = res[1][ps] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (HAS_RES) epi_group_load_res(res[0], rr, roff0, rstep);
+      if (HAS_RES) sf_epi_load_res<4, SF_EPI_LOAD_AUX>(res[0], rr, roff0, rstep);
 #pragma unroll
       for (int g = 0; g < FI; ++g) {
-        if (HAS_RES && g + 1 < FI) epi_group_load_res(res[(g + 1) & 1], rr, roff0 + (g + 1) * 4 * rstep, rstep);
+        if (HAS_RES && g + 1 < FI) sf_epi_load_res<4, SF_EPI_LOAD_AUX>(res[(g + 1) & 1], rr, roff0 + (g + 1) * 4 * rstep, rstep);
 #pragma unroll
         for (int j = 0; j < FJ; ++j)
 #pragma unroll
@@ -236,8 +236,8 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::MIN_WAVES_PER_SIMD) void gemm_bf
         float4 v[4];
 #pragma unroll
         for (int ps = 0; ps < 4; ++ps) v[ps] = *reinterpret_cast<const float4*>(slab + (ps * 4 + (lane >> 4)) * EPI_LD + ecol);
-        if (!(SF_ABL & 1)) epi_group_store<OUT_BF16, GELU, HAS_RES>(v, bias4, res[g & 1], rc, coff0 + g * 4 * cstep, cstep);
-        else if (v[0].x == 1.2345e30f) epi_group_store<OUT_BF16, GELU, HAS_RES>(v, bias4, res[g & 1], rc, coff0, cstep);
+        if (!(SF_ABL & 1)) sf_epi_store<OUT_BF16, GELU, HAS_RES, 4, SF_EPI_STORE_AUX>(v, bias4, res[g & 1], rc, coff0 + g * 4 * cstep, cstep);
+        else if (v[0].x == 1.2345e30f) sf_epi_store<OUT_BF16, GELU, HAS_RES, 4, SF_EPI_STORE_AUX>(v, bias4, res[g & 1], rc, coff0, cstep);
       }
     }
   } else {
@@ -364,7 +364,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_persistent_kernel(GemmArgs p
       b_src[i] = p.W + (int64_t)br * p.ldw + gch * 8;
     }
   };
-  const uint32_t lds_wave = __builtin_amdgcn_readfirstlane(lds_addr(smem) + (wave * 4) * 1024);
+  const uint32_t lds_wave = __builtin_amdgcn_readfirstlane(sf_lds_addr(smem) + (wave * 4) * 1024);
   // k-loop rotation: the 32 workgroups of an XCD run in near lockstep (same tile shape, same start), so without it they all ask the XCD's L2
   // for the SAME operand lines at the same moment (the A panel shared by the column tiles of a row panel, the W rows shared by everything) and
   // queue on those lines' channels.  Starting every workgroup at a different k-tile spreads the requests over the whole k-extent of the
@@ -375,9 +375,9 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_persistent_kernel(GemmArgs p
   auto stage = [&](int s, int kt_) {
     const int kt = kmap(kt_);
     const uint32_t l = lds_wave + s * P_STAGE;
-    if (SF_A_NT) dma4_nt(a_src[0] + kt * PBK, a_src[1] + kt * PBK, a_src[2] + kt * PBK, a_src[3] + kt * PBK, l);
-    else dma4(a_src[0] + kt * PBK, a_src[1] + kt * PBK, a_src[2] + kt * PBK, a_src[3] + kt * PBK, l);
-    dma4(b_src[0] + kt * p.wk, b_src[1] + kt * p.wk, b_src[2] + kt * p.wk, b_src[3] + kt * p.wk, l + PBM * PBK * 2);
+    if (SF_A_NT) sf_dma4_nt(a_src[0] + kt * PBK, a_src[1] + kt * PBK, a_src[2] + kt * PBK, a_src[3] + kt * PBK, l);
+    else sf_dma4(a_src[0] + kt * PBK, a_src[1] + kt * PBK, a_src[2] + kt * PBK, a_src[3] + kt * PBK, l);
+    sf_dma4(b_src[0] + kt * p.wk, b_src[1] + kt * p.wk, b_src[2] + kt * p.wk, b_src[3] + kt * p.wk, l + PBM * PBK * 2);
   };
 
   uint32_t t = t_begin + li;
@@ -409,7 +409,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_persistent_kernel(GemmArgs p
     if (WIDE && p.bias && lane < 16 && n0 + wn * 64 < p.N) bias_raw = *reinterpret_cast<const float4*>(p.bias + n0 + wn * 64 + lane * 4);
 
     for (int kt = 0; kt < nk; ++kt) {
-      wait_vmcnt_barrier<0>();                                   // tile kt landed everywhere; slot (kt+1)&1 is free
+      sf_wait_vmcnt_barrier<0>();                                   // tile kt landed everywhere; slot (kt+1)&1 is free
       const bool refill = kt + 1 < nk && !(kt == 0 && stage1_in_flight);
       if (!SF_DMA_SPREAD && refill) stage((kt + 1) & 1, kt + 1);
       const char* sa = smem + (kt & 1) * P_STAGE + a_base;
@@ -432,16 +432,14 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_persistent_kernel(GemmArgs p
           const uint32_t l = lds_wave + ((kt + 1) & 1) * P_STAGE;
           const int ko = kmap(kt + 1) * PBK;
           const int64_t kow = kmap(kt + 1) * p.wk;
-          if (kk == 0) dma4(a_src[0] + ko, a_src[1] + ko, a_src[2] + ko, a_src[3] + ko, l);
-          else dma4(b_src[0] + kow, b_src[1] + kow, b_src[2] + kow, b_src[3] + kow, l + PBM * PBK * 2);
+          if (kk == 0) sf_dma4(a_src[0] + ko, a_src[1] + ko, a_src[2] + ko, a_src[3] + ko, l);
+          else sf_dma4(b_src[0] + kow, b_src[1] + kow, b_src[2] + kow, b_src[3] + kow, l + PBM * PBK * 2);
           __builtin_amdgcn_sched_barrier(0);
         }
       }
     }
     // all waves finished reading both slots -> slot 0 can take the next tile's first stage, slot 1 is epilogue scratch
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    sf_barrier();
     const int64_t em0 = m0; const int en0 = n0;
     const uint32_t tnext = t + per_xcd_blocks;
     const bool more = tnext < t_end;
@@ -507,11 +505,11 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_persistent_kernel(GemmArgs p
       float4 res[2][4];
 #pragma unroll
       for (int ps = 0; ps < 4; ++ps) res[0][ps] = res[1][ps] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (HAS_RES) epi_group_load_res(res[0], rr, roff0, rstep);
+      if (HAS_RES) sf_epi_load_res<4, SF_EPI_LOAD_AUX>(res[0], rr, roff0, rstep);
 #pragma unroll
       for (int g = 0; g < 8; ++g) {
         const int i = g >> 1, q2 = g & 1;
-        if (HAS_RES && g + 1 < 8) epi_group_load_res(res[(g + 1) & 1], rr, roff0 + (g + 1) * 4 * rstep, rstep);
+        if (HAS_RES && g + 1 < 8) sf_epi_load_res<4, SF_EPI_LOAD_AUX>(res[(g + 1) & 1], rr, roff0 + (g + 1) * 4 * rstep, rstep);
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -522,8 +520,8 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_persistent_kernel(GemmArgs p
         float4 v[4];
 #pragma unroll
         for (int ps = 0; ps < 4; ++ps) v[ps] = *reinterpret_cast<const float4*>(slab + (ps * 4 + (lane >> 4)) * P_EPI_LD + ecol);
-        if (!(SF_ABL & 1)) epi_group_store<OUT_BF16, GELU, HAS_RES>(v, bias4, res[g & 1], rc, coff0 + g * 4 * cstep, cstep);
-        else if (v[0].x == 1.2345e30f) epi_group_store<OUT_BF16, GELU, HAS_RES>(v, bias4, res[g & 1], rc, coff0, cstep);
+        if (!(SF_ABL & 1)) sf_epi_store<OUT_BF16, GELU, HAS_RES, 4, SF_EPI_STORE_AUX>(v, bias4, res[g & 1], rc, coff0 + g * 4 * cstep, cstep);
+        else if (v[0].x == 1.2345e30f) sf_epi_store<OUT_BF16, GELU, HAS_RES, 4, SF_EPI_STORE_AUX>(v, bias4, res[g & 1], rc, coff0, cstep);
       }
     }
     if (!more) break;
@@ -622,13 +620,13 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_w4_kernel(GemmArgs p) {
       b_src[i] = (uint32_t)(((int64_t)br * p.ldw + gch * 8) * 2);
     }
   };
-  const uint32_t lds_wave = __builtin_amdgcn_readfirstlane(lds_addr(smem) + (wave * 8) * 1024);
+  const uint32_t lds_wave = __builtin_amdgcn_readfirstlane(sf_lds_addr(smem) + (wave * 8) * 1024);
   auto dma_quad = [&](int s, int kt, int q) {                     // q = 0, 1: A pieces 0-3 / 4-7;  q = 2, 3: B pieces 0-3 / 4-7
     const uint32_t l = lds_wave + s * P_STAGE + (q >= 2 ? PBM * PBK * 2 : 0) + (q & 1) * 4096;
     const uint32_t ko = (uint32_t)kt * (PBK * 2);
     const uint32_t* src = q >= 2 ? b_src : a_src;
     const int o = (q & 1) * 4;
-    dma4s(src[o] + ko, src[o + 1] + ko, src[o + 2] + ko, src[o + 3] + ko, q >= 2 ? (const void*)p.W : (const void*)p.A, l);
+    sf_dma4s(src[o] + ko, src[o + 1] + ko, src[o + 2] + ko, src[o + 3] + ko, q >= 2 ? (const void*)p.W : (const void*)p.A, l);
   };
   auto stage = [&](int s, int kt) { dma_quad(s, kt, 0); dma_quad(s, kt, 1); dma_quad(s, kt, 2); dma_quad(s, kt, 3); };
 
@@ -678,7 +676,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_w4_kernel(GemmArgs p) {
       }
     };
 
-    wait_vmcnt_barrier<0>();                                      // k-tile 0 of this tile is visible
+    sf_wait_vmcnt_barrier<0>();                                      // k-tile 0 of this tile is visible
 #pragma unroll
     for (int b = 0; b < 8; ++b) read_frag(f0[b], smem, b, 0);
     for (int kt = 0; kt < nk; ++kt) {
@@ -691,14 +689,12 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_w4_kernel(GemmArgs p) {
       if (more_k) {
         // every fragment of this k-tile is in registers once f1 has landed: publish k-tile kt + 1 and free this slot
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        wait_vmcnt_barrier<0>();
+        sf_wait_vmcnt_barrier<0>();
       }
       step(f1, f0, stn, 0, more_k, kt + 2 < nk, kt & 1, kt + 2);
     }
     // all waves are done with both slots -> next tile's first two k-tiles go in flight under the epilogue
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    sf_barrier();
     const int64_t em0 = m0; const int en0 = n0;
     const uint32_t tnext = t + per_xcd_blocks;
     const bool more = tnext < t_end;
@@ -716,11 +712,11 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_w4_kernel(GemmArgs p) {
         float4 res[2][4];
 #pragma unroll
         for (int ps = 0; ps < 4; ++ps) res[0][ps] = res[1][ps] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (HAS_RES) epi_group_load_res(res[0], rr, roff0, rstep);
+        if (HAS_RES) sf_epi_load_res<4, SF_EPI_LOAD_AUX>(res[0], rr, roff0, rstep);
 #pragma unroll
         for (int g = 0; g < 8; ++g) {
           const int i = g >> 1, q2 = g & 1;
-          if (HAS_RES && g + 1 < 8) epi_group_load_res(res[(g + 1) & 1], rr, roff0 + (g + 1) * 4 * rstep, rstep);
+          if (HAS_RES && g + 1 < 8) sf_epi_load_res<4, SF_EPI_LOAD_AUX>(res[(g + 1) & 1], rr, roff0 + (g + 1) * 4 * rstep, rstep);
 #pragma unroll
           for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -731,7 +727,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_w4_kernel(GemmArgs p) {
           float4 v[4];
 #pragma unroll
           for (int ps = 0; ps < 4; ++ps) v[ps] = *reinterpret_cast<const float4*>(slab + (ps * 4 + (lane >> 4)) * P_EPI_LD + ecol);
-          epi_group_store<OUT_BF16, GELU, HAS_RES>(v, bias4, res[g & 1], rc, coff0 + g * 4 * cstep, cstep);
+          sf_epi_store<OUT_BF16, GELU, HAS_RES, 4, SF_EPI_STORE_AUX>(v, bias4, res[g & 1], rc, coff0 + g * 4 * cstep, cstep);
         }
       }
     }
@@ -1045,12 +1041,12 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_splitk_kernel(TnArgs p) {
   const int64_t a_step = (int64_t)TN_BK * p.lda, b_step = (int64_t)TN_BK * p.ldb;
   // stage() is called with kt = 0, 1, 2, ... in order: the source pointers advance by 32 token rows per call; rows beyond `valid`
   // (last k-tile of a ragged chunk) read the zero page.  The four pieces of a wave (A rows 8w..8w+7, then B rows 8w..8w+7) are
-  // consecutive in LDS and issued from inline asm (dma4): hipcc puts a vmcnt(0) in front of the fragment reads when it sees the
+  // consecutive in LDS and issued from inline asm (sf_dma4): hipcc puts a vmcnt(0) in front of the fragment reads when it sees the
   // global_load_lds builtin in this loop, which serialises prefetch and compute; the waits below are the hand-counted ones.
-  const uint32_t lds_wave = __builtin_amdgcn_readfirstlane(lds_addr(smem) + wave * 4096);
+  const uint32_t lds_wave = __builtin_amdgcn_readfirstlane(sf_lds_addr(smem) + wave * 4096);
   auto stage = [&](int slot, int kt) {
     const int lim = valid - kt * TN_BK;
-    dma4(krow[0] < lim ? a_src[0] : zero, krow[1] < lim ? a_src[1] : zero, krow[0] < lim ? b_src[0] : zero, krow[1] < lim ? b_src[1] : zero,
+    sf_dma4(krow[0] < lim ? a_src[0] : zero, krow[1] < lim ? a_src[1] : zero, krow[0] < lim ? b_src[0] : zero, krow[1] < lim ? b_src[1] : zero,
          lds_wave + slot * TN_STAGE);
 #pragma unroll
     for (int i = 0; i < 2; ++i) { a_src[i] += a_step; b_src[i] += b_step; }
@@ -1083,7 +1079,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_splitk_kernel(TnArgs p) {
   for (int kt = 0; kt < nk; ++kt) {
     // tile kt has landed when at most the (<= 2) younger stages are outstanding (4 LDS-DMA instructions per thread per stage)
     const int ahead = min(TN_NS - 2, nk - 1 - kt);
-    if (ahead >= 2) wait_vmcnt_barrier<8>(); else if (ahead == 1) wait_vmcnt_barrier<4>(); else wait_vmcnt_barrier<0>();
+    if (ahead >= 2) sf_wait_vmcnt_barrier<8>(); else if (ahead == 1) sf_wait_vmcnt_barrier<4>(); else sf_wait_vmcnt_barrier<0>();
     // every wave is past compute(kt-1): its slot is free -> refill with tile kt+3
     if (kt + TN_NS - 1 < nk) stage((kt + TN_NS - 1) & (TN_NS - 1), kt + TN_NS - 1);
     const char* st = smem + (kt & (TN_NS - 1)) * TN_STAGE;

@@ -1,7 +1,9 @@
-// Shared pieces of the bf16 GEMM kernels (sf_gemm.hip, sf_gemm_pp.hip): argument block, LDS-DMA issue helpers, the branch-free
-// buffer-op epilogue tail and the counted-wait + barrier primitive.
+// Shared pieces of the bf16 GEMM kernels (sf_gemm.hip, sf_gemm_pp.hip, sf_gemm_w4.hip, sf_gemm_tn_pp.hip): the argument block and the measurement switches.
+// The LDS-DMA, wait and barrier primitives are sf_lds_prims.h's, the branch-free buffer-op epilogue tail is sf_gemm_epi.h's (both included here).
 #pragma once
 #include "sf_common.h"
+#include "sf_lds_prims.h"
+#include "sf_gemm_epi.h"
 #include <stdlib.h>
 #include "../../include/synchformer_hip.h"
 
@@ -29,61 +31,6 @@ struct GemmArgs {
   uint32_t stagger = 0;   // config 11: the workgroups that own one tile fewer than their XCD's first start this many x ~1.2 us late (SF_PP_STAGGER)
 };
 
-__device__ __forceinline__ void glds16(const void* gsrc, char* lds_dst_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds_dst_wave_base, 16, 0, 0);
-}
-
-__device__ __forceinline__ uint32_t lds_addr(const void* p) {   // LDS byte address of a __shared__ pointer
-  return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char*)p;
-}
-// Four LDS-DMA pieces (1 KiB each, consecutive in LDS from wave-uniform address `l0`) issued from inline asm, so
-// hipcc neither counts them nor guards later ds_reads with vmcnt(0) (it does for the builtin once the loop gets
-// complicated - that wait serialised prefetch and compute in the first persistent kernel).  Every wait for these
-// loads is a hand-placed counted s_waitcnt.  M0 (LDS destination base) is saved/restored inside the statement.
-__device__ __forceinline__ void dma4(const void* g0, const void* g1, const void* g2, const void* g3, uint32_t l0) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, off\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(g0), "v"(g1), "v"(g2), "v"(g3), "s"(l0)
-      : "memory", "scc");
-}
-
-// The same four pieces addressed as SGPR base + zero-extended 32-bit lane offsets (operands below 4 GiB): half the address registers per piece.
-__device__ __forceinline__ void dma4s(uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3, const void* sbase, uint32_t l0) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %5\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %5\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %5\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %5\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(v0), "v"(v1), "v"(v2), "v"(v3), "s"(sbase), "s"(l0)
-      : "memory", "scc");
-}
-
-__device__ __forceinline__ void dma4_nt(const void* g0, const void* g1, const void* g2, const void* g3, uint32_t l0) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off nt\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, off nt\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, off nt\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(g0), "v"(g1), "v"(g2), "v"(g3), "s"(l0)
-      : "memory", "scc");
-}
-
 // cache-policy bits of the epilogue's buffer ops (aux operand: bit 0 sc0/glc, bit 1 nt/slc, bit 4 sc1)
 // Outputs are written once and the fp32 residual is read once: marked non-temporal (nt) so that they do not evict the weight matrix
 // (3.5-4.7 MB against a 4 MB L2 per XCD) and the A panels the other column tiles of the same rows are about to read.  Measured on
@@ -106,56 +53,6 @@ __device__ __forceinline__ void dma4_nt(const void* g0, const void* g1, const vo
 #ifndef SF_A_NT
 #define SF_A_NT 0      // 1: stream the A operand (activations) through L2 with the nt hint as well
 #endif
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-
-// Branch-free epilogue tail for one group of 16 rows x 64 cols per wave (4 float4 per lane, rows 4 apart):
-// + bias, erf-GELU, + fp32 residual, convert, store.  Row bounds come for free from the buffer descriptors
-// (num_records = M * ld * esz: rows >= M are dropped by the hardware range check), so there is no exec-mask
-// branching and hipcc keeps counted vmcnt waits: stores never wait for earlier stores, and the residual rows of
-// the NEXT group are already in flight (loaded before this group's stores were issued).
-template <bool OUT_BF16, bool GELU, bool HAS_RES>
-__device__ __forceinline__ void epi_group_store(float4 (&v)[4], const float4& bias4, const float4 (&res)[4],
-                                                __amdgpu_buffer_rsrc_t rc, uint32_t coff, uint32_t cstep) {
-#pragma unroll
-  for (int ps = 0; ps < 4; ++ps) {
-    float4 x = v[ps];
-    x.x += bias4.x; x.y += bias4.y; x.z += bias4.z; x.w += bias4.w;
-    if (GELU) {
-      sf_f32x2_t g0 = {x.x, x.y}, g1 = {x.z, x.w};
-      gelu_erf4(g0, g1);
-      x.x = g0.x; x.y = g0.y; x.z = g1.x; x.w = g1.y;
-    }
-    if (HAS_RES) { x.x += res[ps].x; x.y += res[ps].y; x.z += res[ps].z; x.w += res[ps].w; }
-    if (OUT_BF16) {
-      u32x2 o; o.x = pack_bf2(x.x, x.y); o.y = pack_bf2(x.z, x.w);
-      __builtin_amdgcn_raw_buffer_store_b64(o, rc, coff + ps * cstep, 0, SF_EPI_STORE_AUX);
-    } else {
-      u32x4 o;
-      o.x = __float_as_uint(x.x); o.y = __float_as_uint(x.y); o.z = __float_as_uint(x.z); o.w = __float_as_uint(x.w);
-      __builtin_amdgcn_raw_buffer_store_b128(o, rc, coff + ps * cstep, 0, SF_EPI_STORE_AUX);
-    }
-  }
-}
-__device__ __forceinline__ void epi_group_load_res(float4 (&res)[4], __amdgpu_buffer_rsrc_t rr, uint32_t roff, uint32_t rstep) {
-#pragma unroll
-  for (int ps = 0; ps < 4; ++ps) {
-    const u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(rr, roff + ps * rstep, 0, SF_EPI_LOAD_AUX);
-    res[ps] = make_float4(__uint_as_float(t.x), __uint_as_float(t.y), __uint_as_float(t.z), __uint_as_float(t.w));
-  }
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt_barrier() {
-  // Counted wait for this wave's own LDS-DMA pieces, then the workgroup barrier.  The wait is the BUILTIN (gfx9
-  // encoding: vmcnt[3:0] | expcnt<<4 | lgkmcnt<<8 | vmcnt[5:4]<<14, other counters left at max) so that hipcc's
-  // waitcnt pass sees it and stops inserting its own conservative vmcnt(0) in the loop; the empty asm statements are
-  // compiler memory fences (the raw s_barrier builtin alone does not order LDS accesses for the compiler).
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_waitcnt((N & 0xF) | (0x7 << 4) | (0xF << 8) | ((N >> 4) << 14));
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 // config 11 (sf_gemm_pp.hip): the quadrant-phased persistent 256 x 256 x 64 kernel
 bool sf_gemm_pp_supported(const GemmArgs& a);

@@ -13,7 +13,7 @@
 // and writes the normalised bf16 rows: the stream is read once and written once, and the separate LayerNorm launch disappears.
 //
 // Main loop: K-steps of 32 (a stage = 128 x 32 of A + 768 x 32 of W = 56 KiB; two ring slots = 112 KiB), operands HBM/L2 -> LDS by LDS-DMA
-// (global_load_lds_dwordx4 from inline asm, SGPR base + 32-bit lane offset: 7 pieces of 1 KiB per wave per stage), one counted wait +
+// (LDS-DMA from inline asm - sf_lds_prims.h -, SGPR base + 32-bit lane offset: 7 pieces of 1 KiB per wave per stage), one counted wait +
 // raw s_barrier per K-step, the refill of the other slot issued behind the first MFMA cluster.  LDS rows are 64 B; 16-byte chunk c of row r
 // sits at slot c ^ ((r >> 2) & 3) (applied to the SOURCE address of the lane-linear DMA and to the fragment reads): the 16-lane groups a
 // ds_read_b128 is served in then touch 16 distinct slots of the 256-byte bank row.
@@ -21,7 +21,6 @@
 // epilogue runs, so the epilogue's HBM traffic and the next main loop's first operand loads overlap.
 #include "sf_gemm_ln_common.h"
 #include <stdlib.h>
-#include <type_traits>
 #include "../../include/synchformer_hip.h"
 
 #ifndef SF_RL_PP
@@ -84,7 +83,7 @@ __device__ __forceinline__ void gemm_res_ln768_body(const ResLnArgs& p) {
   const int64_t wstep = (int64_t)16 * p.ldw * 2;
   const void* sb0 = wbase; const void* sb1 = wbase + wstep; const void* sb2 = wbase + 2 * wstep;
   const void* sb3 = wbase + 3 * wstep; const void* sb4 = wbase + 4 * wstep; const void* sb5 = wbase + 5 * wstep;
-  const uint32_t lds0 = __builtin_amdgcn_readfirstlane(rl_lds_addr(smem));
+  const uint32_t lds0 = __builtin_amdgcn_readfirstlane(sf_lds_addr(smem));
   const uint32_t lds_a_w = lds0 + wave * 1024, lds_b_w = lds0 + RL_A_BYTES + wave * 6 * 1024;
 
   // fragment read offsets (bytes) inside an operand tile for the two 16-deep k-steps of a stage
@@ -136,11 +135,11 @@ __device__ __forceinline__ void gemm_res_ln768_body(const ResLnArgs& p) {
   int kq2 = 0;
   auto pp_issue_w = [&](int c, int slot) {
     if (ABL & 8) return;
-    rl_dma2(voff_w[0], voff_w[1], c == 0 ? w0 + wo2 : (c == 1 ? wb1 + wo1 : wb2 + wo1), lds0 + slot * RP_STRIDE + RP_W_OFF + c * RP_THIRD + wave * 2048);
+    sf_dma2(voff_w[0], voff_w[1], c == 0 ? w0 + wo2 : (c == 1 ? wb1 + wo1 : wb2 + wo1), lds0 + slot * RP_STRIDE + RP_W_OFF + c * RP_THIRD + wave * 2048);
   };
   auto pp_issue_a = [&](int slot) {
     if (ABL & 8) return;
-    rl_dma1(voff_a0, reinterpret_cast<const char*>(sa) + ao2, lds0 + slot * RP_STRIDE + wave * 1024);
+    sf_dma1(voff_a0, reinterpret_cast<const char*>(sa) + ao2, lds0 + slot * RP_STRIDE + wave * 1024);
   };
   auto pp_advance = [&]() {                                        // end of a k-step: kt+2 becomes kt+1, the next rotated k-step becomes kt+2
     wo1 = wo2;
@@ -148,12 +147,12 @@ __device__ __forceinline__ void gemm_res_ln768_body(const ResLnArgs& p) {
   };
   auto pp_prologue = [&]() {                                       // A | W0, W1, W2 of k-step 0 and A | W0 of k-step 1: 10 pieces per wave
     const int k0 = kmap(0), k1 = kmap(1);
-    rl_dma1(voff_a0 + k0 * (RL_BK * 2), sa, lds0 + wave * 1024);
-    rl_dma2(voff_w[0], voff_w[1], w0 + (int64_t)k0 * p.wk, lds0 + RP_W_OFF + wave * 2048);
-    rl_dma2(voff_w[0], voff_w[1], w0 + third_b + (int64_t)k0 * p.wk, lds0 + RP_W_OFF + RP_THIRD + wave * 2048);
-    rl_dma2(voff_w[0], voff_w[1], w0 + 2 * third_b + (int64_t)k0 * p.wk, lds0 + RP_W_OFF + 2 * RP_THIRD + wave * 2048);
-    rl_dma1(voff_a0 + k1 * (RL_BK * 2), sa, lds0 + RP_STRIDE + wave * 1024);
-    rl_dma2(voff_w[0], voff_w[1], w0 + (int64_t)k1 * p.wk, lds0 + RP_STRIDE + RP_W_OFF + wave * 2048);
+    sf_dma1(voff_a0 + k0 * (RL_BK * 2), sa, lds0 + wave * 1024);
+    sf_dma2(voff_w[0], voff_w[1], w0 + (int64_t)k0 * p.wk, lds0 + RP_W_OFF + wave * 2048);
+    sf_dma2(voff_w[0], voff_w[1], w0 + third_b + (int64_t)k0 * p.wk, lds0 + RP_W_OFF + RP_THIRD + wave * 2048);
+    sf_dma2(voff_w[0], voff_w[1], w0 + 2 * third_b + (int64_t)k0 * p.wk, lds0 + RP_W_OFF + 2 * RP_THIRD + wave * 2048);
+    sf_dma1(voff_a0 + k1 * (RL_BK * 2), sa, lds0 + RP_STRIDE + wave * 1024);
+    sf_dma2(voff_w[0], voff_w[1], w0 + (int64_t)k1 * p.wk, lds0 + RP_STRIDE + RP_W_OFF + wave * 2048);
     wo1 = (uint32_t)k1 * p.wk;
     kq2 = nk > 2 ? kmap(2) : 0;
     wo2 = (uint32_t)kq2 * p.wk; ao2 = (uint32_t)kq2 * (RL_BK * 2);
@@ -233,37 +232,37 @@ __device__ __forceinline__ void gemm_res_ln768_body(const ResLnArgs& p) {
         for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
           for (int i = 0; i < 2; ++i) a[i][ks] = *reinterpret_cast<const bf16x8*>(smem + i * 2048 + fa[ks]);
-        read_w(std::integral_constant<int, 0>{});
+        read_w(sf_ic<0>{});
         __builtin_amdgcn_sched_barrier(0);
         if (more1) pp_issue_w(1, S ^ 1);
-        if (ABL & 8) rl_wait_vmcnt<0>();                           // W third 1 of this k-step has landed; the youngest stage stays in flight
-        else if (!more1) rl_wait_vmcnt<2>();
-        else if (behind) rl_wait_vmcnt<7 + 48>();
-        else rl_wait_vmcnt<7>();
-        rl_barrier();
+        if (ABL & 8) sf_wait_vmcnt<0>();                           // W third 1 of this k-step has landed; the youngest stage stays in flight
+        else if (!more1) sf_wait_vmcnt<2>();
+        else if (behind) sf_wait_vmcnt<7 + 48>();
+        else sf_wait_vmcnt<7>();
+        sf_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        mma(std::integral_constant<int, 0>{});
+        mma(sf_ic<0>{});
         __builtin_amdgcn_sched_barrier(0);
-        rl_barrier();
+        sf_barrier();
         // ---- phase 1: third 1 ----
-        read_w(std::integral_constant<int, 1>{});
+        read_w(sf_ic<1>{});
         __builtin_amdgcn_sched_barrier(0);
         if (more1) pp_issue_w(2, S ^ 1);
 #ifndef SF_RL_A_EARLY
 #define SF_RL_A_EARLY 1   // the A piece of k-step kt+2 (the only piece of a stage that comes from HBM: ~2 us; W hits L2) is issued HERE, a phase earlier than its stage's W third 0: its slot - A of
 #endif                    // this k-step - is free since phase 0 (fragments in registers, the wm = 1 waves one barrier behind have read them too), and the pieces issued behind it are needed late enough
         if (SF_RL_A_EARLY && more2) pp_issue_a(S);
-        if (!more1 || (ABL & 8)) rl_wait_vmcnt<0>();               // W third 2 has landed
-        else if (SF_RL_A_EARLY && more2) { if (behind) rl_wait_vmcnt<8 + 48>(); else rl_wait_vmcnt<8>(); }
-        else if (behind) rl_wait_vmcnt<7 + 48>();
-        else rl_wait_vmcnt<7>();
-        rl_barrier();
+        if (!more1 || (ABL & 8)) sf_wait_vmcnt<0>();               // W third 2 has landed
+        else if (SF_RL_A_EARLY && more2) { if (behind) sf_wait_vmcnt<8 + 48>(); else sf_wait_vmcnt<8>(); }
+        else if (behind) sf_wait_vmcnt<7 + 48>();
+        else sf_wait_vmcnt<7>();
+        sf_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        mma(std::integral_constant<int, 1>{});
+        mma(sf_ic<1>{});
         __builtin_amdgcn_sched_barrier(0);
-        rl_barrier();
+        sf_barrier();
         // ---- phase 2: third 2; the fragment addresses move on to the other stage ----
-        read_w(std::integral_constant<int, 2>{});
+        read_w(sf_ic<2>{});
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
           asm volatile("v_xor_b32 %0, 0x10000, %0" : "+v"(fa[ks]));
@@ -273,32 +272,32 @@ __device__ __forceinline__ void gemm_res_ln768_body(const ResLnArgs& p) {
         if (more2) { if (!SF_RL_A_EARLY) pp_issue_a(S); pp_issue_w(0, S); }
         pp_advance();
         if (more1) {                                               // A | W third 0 of the next k-step have landed
-          if (ABL & 8) rl_wait_vmcnt<0>();
-          else if (!more2) rl_wait_vmcnt<4>();
-          else if (behind) rl_wait_vmcnt<7 + 48>();
-          else rl_wait_vmcnt<7>();
+          if (ABL & 8) sf_wait_vmcnt<0>();
+          else if (!more2) sf_wait_vmcnt<4>();
+          else if (behind) sf_wait_vmcnt<7 + 48>();
+          else sf_wait_vmcnt<7>();
         }
-        rl_barrier();
+        sf_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        mma(std::integral_constant<int, 2>{});
+        mma(sf_ic<2>{});
         __builtin_amdgcn_sched_barrier(0);
-        rl_barrier();
+        sf_barrier();
       };
       // A | W third 0 of k-step 0 have landed (this wave's pieces), then everybody's
-      if (ABL & 8) rl_wait_vmcnt<0>();
-      else if (SF_RL_STORECNT && y_stores_behind) rl_wait_vmcnt<7 + 48>();
-      else rl_wait_vmcnt<7>();
-      rl_barrier();
-      if (wm == 1) rl_barrier();                                   // the wm = 1 waves run one barrier behind
+      if (ABL & 8) sf_wait_vmcnt<0>();
+      else if (SF_RL_STORECNT && y_stores_behind) sf_wait_vmcnt<7 + 48>();
+      else sf_wait_vmcnt<7>();
+      sf_barrier();
+      if (wm == 1) sf_barrier();                                   // the wm = 1 waves run one barrier behind
       for (int kt = 0; kt < nk; kt += 2) {
         const bool more = kt + 2 < nk;
-        kstep(std::integral_constant<int, 0>{}, kt, true, more, kt == 0);
-        kstep(std::integral_constant<int, 1>{}, kt + 1, more, more, false);
+        kstep(sf_ic<0>{}, kt, true, more, kt == 0);
+        kstep(sf_ic<1>{}, kt + 1, more, more, false);
       }
-      if (wm == 0) rl_barrier();                                   // re-align; also: every wave is done with both stages
+      if (wm == 0) sf_barrier();                                   // re-align; also: every wave is done with both stages
     } else {
     for (int kt = 0; kt < nk; ++kt) {
-      rl_wait_vmcnt_barrier<0>();                                  // stage kt landed everywhere; slot (kt+1)&1 is free
+      sf_wait_vmcnt_barrier<0>();                                  // stage kt landed everywhere; slot (kt+1)&1 is free
       const bool refill = kt + 1 < nk && !(kt == 0 && stage1_in_flight) && !(ABL & 8);
       const char* st = smem + (kt & 1) * RL_STAGE;
 #pragma unroll
@@ -324,8 +323,8 @@ __device__ __forceinline__ void gemm_res_ln768_body(const ResLnArgs& p) {
                 const int piece = SF_RL_SPREAD == 2 ? (ks == 1 ? 6 : i * 3 + (j >> 1)) : ks * 4 + i * 2 + (j == 4);   // 0 .. 6: A, W0 .. W5
                 __builtin_amdgcn_sched_barrier(0);
                 if (refill && !((ABL & 32) && (piece & 1) == 0 && piece > 0)) {
-                  if (piece == 0) { if (SF_RL_A_NT) rl_dma1_nt(voff_a0 + ko, sa, la); else rl_dma1(voff_a0 + ko, sa, la); }
-                  else rl_dma1(voff_b0 + kow, piece == 1 ? sb0 : piece == 2 ? sb1 : piece == 3 ? sb2 : piece == 4 ? sb3 : piece == 5 ? sb4 : sb5,
+                  if (piece == 0) { if (SF_RL_A_NT) sf_dma1_nt(voff_a0 + ko, sa, la); else sf_dma1(voff_a0 + ko, sa, la); }
+                  else sf_dma1(voff_b0 + kow, piece == 1 ? sb0 : piece == 2 ? sb1 : piece == 3 ? sb2 : piece == 4 ? sb3 : piece == 5 ? sb4 : sb5,
                                lb + (piece - 1) * 1024);
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -345,9 +344,7 @@ __device__ __forceinline__ void gemm_res_ln768_body(const ResLnArgs& p) {
       }
     }
     // every wave is done with both slots -> they take the next tile's first two stages while this tile's epilogue runs
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    sf_barrier();
     }
     const int64_t em0 = m0;
     const uint32_t tnext = t + gridDim.x;
@@ -387,7 +384,7 @@ __device__ __forceinline__ void gemm_res_ln768_body(const ResLnArgs& p) {
         if (PERIODIC) { rl += rper0; if (rl >= (int)p.r_period) rl -= (int)p.r_period; }
         vo[ps] = (uint32_t)(rl * (int)p.ldr + gcol0 + c * 64) * 4u;
       }
-      rl_dma_r4(vo[0], vo[1], vo[2], vo[3], rbase, ring_lds + (s % 3) * 4096);
+      sf_dma4s_nt(vo[0], vo[1], vo[2], vo[3], rbase, ring_lds + (s % 3) * 4096);
     };
     issue_res(0); issue_res(1); issue_res(2);
     float4 xr[4][3][4];
@@ -430,7 +427,7 @@ __device__ __forceinline__ void gemm_res_ln768_body(const ResLnArgs& p) {
 #pragma unroll
           for (int c = 0; c < 3; ++c) {
             const float4 v = xr[g][c][ps];
-            rl_u32x4 o;
+            u32x4 o;
             o.x = __float_as_uint(v.x); o.y = __float_as_uint(v.y); o.z = __float_as_uint(v.z); o.w = __float_as_uint(v.w);
             __builtin_amdgcn_raw_buffer_store_b128(o, rx, xoff0 + (uint32_t)(g * 4 + ps) * xstep + (uint32_t)c * 256u, 0, SF_RL_STORE_AUX);
           }
@@ -445,12 +442,10 @@ __device__ __forceinline__ void gemm_res_ln768_body(const ResLnArgs& p) {
         float sres = 0.f;
 #pragma unroll
         for (int c = 0; c < 3; ++c) sres += (xr[g][c][ps].x + xr[g][c][ps].y) + (xr[g][c][ps].z + xr[g][c][ps].w);
-        sres = rl_row16_sum(sres);
+        sres = sum16_dpp(sres);
         if ((elane & 15) == 0) stat[srow0 + (g * 16 + ps * 4) * 4 + wn] = sres;
       }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");              // raw barrier: __syncthreads() would also drain the 48 stores in flight
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    sf_lgkm0_barrier();                                           // raw barrier: __syncthreads() would also drain the 48 stores in flight
     // every wave is past its residual ring: the operand slots take the next tile's first two stages while the rest of the epilogue runs
     stage1_in_flight = false;
     if (more) {
@@ -477,12 +472,10 @@ __device__ __forceinline__ void gemm_res_ln768_body(const ResLnArgs& p) {
           const float dx = v.x - mu, dy = v.y - mu, dz = v.z - mu, dw = v.w - mu;
           sres += (dx * dx + dy * dy) + (dz * dz + dw * dw);
         }
-        sres = rl_row16_sum(sres);
+        sres = sum16_dpp(sres);
         if ((elane & 15) == 0) stat2[srow0 + (g * 16 + ps * 4) * 4 + wn] = sres;
       }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    sf_lgkm0_barrier();
     // ---- pass 4: normalise, scale, shift, bf16, store ------------------------------------------------------------------------------
     const uint32_t yoff0 = (uint32_t)(row0 * p.ldy + gcol0) * 2u, ystep = (uint32_t)(4 * p.ldy) * 2u;
     float4 gm[3], bt[3];
@@ -502,7 +495,7 @@ __device__ __forceinline__ void gemm_res_ln768_body(const ResLnArgs& p) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
           const float4 v = xr[g][c][ps];
-          rl_u32x2 o;
+          u32x2 o;
           o.x = pack_bf2((v.x - mu) * rs * gm[c].x + bt[c].x, (v.y - mu) * rs * gm[c].y + bt[c].y);
           o.y = pack_bf2((v.z - mu) * rs * gm[c].z + bt[c].z, (v.w - mu) * rs * gm[c].w + bt[c].w);
           if (!(ABL & 4) || o.x == 0x12345678u) __builtin_amdgcn_raw_buffer_store_b64(o, ry, yoff0 + (uint32_t)(g * 4 + ps) * ystep + (uint32_t)c * 128u, 0, SF_RL_STORE_AUX);

@@ -16,7 +16,7 @@
 // tiles; profiles/r04_experiments.md section 6): kept as the tested alternative behind sf_gemm_res_ln_force_schedule(2) / SF_RL_SCHED=2, not used by the engine.
 #ifdef SF_ABLATION   // schedule 2 of sf_gemm_res_ln768: a measured-slower alternative, compiled into the ablation build only
 #include "sf_common.h"
-#include <type_traits>
+#include "sf_lds_prims.h"
 #include <stdlib.h>
 #include "../../include/synchformer_hip.h"
 
@@ -47,39 +47,13 @@ struct G2Args {
   uint32_t tiles;
 };
 
-__device__ __forceinline__ void g2_dma1(uint32_t voff, const void* sbase, uint32_t lds) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds) : "memory");
-}
-__device__ __forceinline__ void g2_dma_dword_addr(const void* gaddr, uint32_t lds) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gaddr), "s"(lds) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void g2_wait_vmcnt() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_waitcnt((N & 0xF) | (0x7 << 4) | (0xF << 8) | ((N >> 4) << 14));
-}
-__device__ __forceinline__ void g2_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-__device__ __forceinline__ uint32_t g2_lds_addr(const void* p) { return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char*)p; }
 // sum over the 64 lanes of a wave, every lane ends with the total: 4 DPP steps inside the 16-lane rows, then the two cross-row exchanges
 __device__ __forceinline__ float g2_wave_sum(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true));   // row_half_mirror
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, true));   // row_mirror
+  v = sum16_dpp(v);
   v += __shfl_xor(v, 16, 64);
   v += __shfl_xor(v, 32, 64);
   return v;
 }
-
-template <int V> using g2_ic = std::integral_constant<int, V>;
 
 __global__ __launch_bounds__(512, 2) void gemm_res_ln768_v2_kernel(G2Args p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -95,7 +69,7 @@ __global__ __launch_bounds__(512, 2) void gemm_res_ln768_v2_kernel(G2Args p) {
   uint32_t t = t0 + li;
   if (t >= t1) return;
 
-  const uint32_t lds0 = __builtin_amdgcn_readfirstlane(g2_lds_addr(smem));
+  const uint32_t lds0 = __builtin_amdgcn_readfirstlane(sf_lds_addr(smem));
   const uint32_t lds_a_w = __builtin_amdgcn_readfirstlane(lds0 + wave * 3072);
   const uint32_t lds_w_w = __builtin_amdgcn_readfirstlane(lds0 + G2_A_BYTES + wave * 2048);
   const uint32_t w8 = (uint32_t)(8 * p.ldw * 2);
@@ -131,19 +105,19 @@ __global__ __launch_bounds__(512, 2) void gemm_res_ln768_v2_kernel(G2Args p) {
 #pragma unroll 1
     for (int pass = 0; pass < 2; ++pass) {
       const char* wbase = reinterpret_cast<const char*>(p.W + (int64_t)pass * G2_COLS * p.ldw);
-      auto issue_a = [&](int pc, int S, int kt) { g2_dma1(voff_a[pc], xbase + kt * 128, lds_a_w + S * G2_STAGE + pc * 1024); };
+      auto issue_a = [&](int pc, int S, int kt) { sf_dma1(voff_a[pc], xbase + kt * 128, lds_a_w + S * G2_STAGE + pc * 1024); };
       auto issue_w = [&](int j, int S, int kt) {
-        g2_dma1(voff_w[j], wbase + kt * 128, lds_w_w + S * G2_STAGE + j * G2_W_PART);
-        g2_dma1((voff_w[j] ^ 64u) + w8, wbase + kt * 128, lds_w_w + S * G2_STAGE + j * G2_W_PART + 1024);
+        sf_dma1(voff_w[j], wbase + kt * 128, lds_w_w + S * G2_STAGE + j * G2_W_PART);
+        sf_dma1((voff_w[j] ^ 64u) + w8, wbase + kt * 128, lds_w_w + S * G2_STAGE + j * G2_W_PART + 1024);
       };
       // ---- prologue (every wave is out of the staging chunks: barrier at the bottom of the previous epilogue) ----
-      if (wave < 6 && p.bias) g2_dma_dword_addr(p.bias + pass * G2_COLS + wave * 64 + lane, lds0 + G2_BIAS_OFF + wave * 256);
+      if (wave < 6 && p.bias) sf_dma_dword_addr(p.bias + pass * G2_COLS + wave * 64 + lane, lds0 + G2_BIAS_OFF + wave * 256);
       issue_w(0, 0, 0); issue_a(0, 0, 0);
       issue_w(1, 0, 0); issue_a(1, 0, 0); issue_a(2, 0, 0);
       issue_w(2, 0, 0);
       issue_w(0, 1, 1); issue_a(0, 1, 1);
-      g2_wait_vmcnt<5>();
-      g2_barrier();
+      sf_wait_vmcnt<5>();
+      sf_barrier();
       f32x16 acc[3][3];
       {
         const float* bs = reinterpret_cast<const float*>(smem + G2_BIAS_OFF);
@@ -194,37 +168,37 @@ __global__ __launch_bounds__(512, 2) void gemm_res_ln768_v2_kernel(G2Args p) {
           read_w(st, 0);
           __builtin_amdgcn_sched_barrier(0);
           if (ld1) { issue_w(1, S ^ 1, kt + 1); issue_a(1, S ^ 1, kt + 1); issue_a(2, S ^ 1, kt + 1); }
-          g2_barrier();
+          sf_barrier();
           __builtin_amdgcn_sched_barrier(0);
-          mma(g2_ic<0>{});
+          mma(sf_ic<0>{});
           __builtin_amdgcn_sched_barrier(0);
-          g2_barrier();
+          sf_barrier();
           read_w(st, 1);
           __builtin_amdgcn_sched_barrier(0);
-          if (ld1) { issue_w(2, S ^ 1, kt + 1); g2_wait_vmcnt<9>(); } else g2_wait_vmcnt<0>();
-          g2_barrier();
+          if (ld1) { issue_w(2, S ^ 1, kt + 1); sf_wait_vmcnt<9>(); } else sf_wait_vmcnt<0>();
+          sf_barrier();
           __builtin_amdgcn_sched_barrier(0);
-          mma(g2_ic<1>{});
+          mma(sf_ic<1>{});
           __builtin_amdgcn_sched_barrier(0);
-          g2_barrier();
+          sf_barrier();
           read_w(st, 2);
           __builtin_amdgcn_sched_barrier(0);
-          if (ld2) { issue_w(0, S, kt + 2); issue_a(0, S, kt + 2); g2_wait_vmcnt<5>(); }
-          else if (ld1) g2_wait_vmcnt<2>();
-          else g2_wait_vmcnt<0>();
-          g2_barrier();
+          if (ld2) { issue_w(0, S, kt + 2); issue_a(0, S, kt + 2); sf_wait_vmcnt<5>(); }
+          else if (ld1) sf_wait_vmcnt<2>();
+          else sf_wait_vmcnt<0>();
+          sf_barrier();
           __builtin_amdgcn_sched_barrier(0);
-          mma(g2_ic<2>{});
+          mma(sf_ic<2>{});
           __builtin_amdgcn_sched_barrier(0);
-          g2_barrier();
+          sf_barrier();
         };
-        if (wm == 1) g2_barrier();                                  // waves 4-7 run one barrier behind waves 0-3
+        if (wm == 1) sf_barrier();                                  // waves 4-7 run one barrier behind waves 0-3
 #pragma unroll 1
         for (int kt = 0; kt < nk; kt += 2) {
-          ktile(g2_ic<0>{}, kt, true, kt + 2 < nk);
-          ktile(g2_ic<1>{}, kt + 1, kt + 2 < nk, kt + 3 < nk);
+          ktile(sf_ic<0>{}, kt, true, kt + 2 < nk);
+          ktile(sf_ic<1>{}, kt + 1, kt + 2 < nk, kt + 3 < nk);
         }
-        if (wm == 0) g2_barrier();                                  // re-align; every wave is done with both stages
+        if (wm == 0) sf_barrier();                                  // re-align; every wave is done with both stages
       }
 
       // ---- epilogue of the pass: six chunks of 32 rows (row block i of wave row wmc) through two LDS buffers --------------------------------------------------
@@ -247,8 +221,8 @@ __global__ __launch_bounds__(512, 2) void gemm_res_ln768_v2_kernel(G2Args p) {
             if (gr > p.M - 1) gr = p.M - 1;
             const char* src = reinterpret_cast<const char*>(p.R + gr * p.ldr + col0);
             const uint32_t dst = lds0 + (n & 1) * (32 * G2_CH_LD) + r * G2_CH_LD;
-            g2_dma1((uint32_t)el * 16u, src, dst);
-            if (has2) g2_dma1((uint32_t)el * 16u, src + 1024, dst + 1024);
+            sf_dma1((uint32_t)el * 16u, src, dst);
+            if (has2) sf_dma1((uint32_t)el * 16u, src + 1024, dst + 1024);
           }
         };
         if (!(G2_ABL & 1)) issue_r(0);
@@ -257,9 +231,9 @@ __global__ __launch_bounds__(512, 2) void gemm_res_ln768_v2_kernel(G2Args p) {
           const int wmc = n >= 3 ? 1 : 0, i = n - 3 * wmc;
           char* buf = smem + (n & 1) * (32 * G2_CH_LD);
           if (!(G2_ABL & 1)) {
-            if (n + 1 < 6) { issue_r(n + 1); g2_wait_vmcnt<8>(); } else g2_wait_vmcnt<0>();     // the residual of chunk n has landed (and the stores of chunk n-1 have retired)
+            if (n + 1 < 6) { issue_r(n + 1); sf_wait_vmcnt<8>(); } else sf_wait_vmcnt<0>();     // the residual of chunk n has landed (and the stores of chunk n-1 have retired)
           }
-          g2_barrier();
+          sf_barrier();
           // (a) the four waves of wave row wmc add their row block i: chunk row l31, columns wn * 96 + 32 j + 8 g + 4 hi
           if (wm == wmc) {
 #pragma unroll
@@ -275,7 +249,7 @@ __global__ __launch_bounds__(512, 2) void gemm_res_ln768_v2_kernel(G2Args p) {
                 *dst = v;
               }
           }
-          g2_barrier();
+          sf_barrier();
           // (b) rows 4 wave .. + 3 of the chunk, whole rows per wave
           {
             float y1[4][4], y2[4][4];
@@ -358,7 +332,7 @@ __global__ __launch_bounds__(512, 2) void gemm_res_ln768_v2_kernel(G2Args p) {
               }
             }
           }
-          g2_barrier();                                             // the chunk is consumed: its buffer may take the residual of chunk n + 2
+          sf_barrier();                                             // the chunk is consumed: its buffer may take the residual of chunk n + 2
         }
       }
     }

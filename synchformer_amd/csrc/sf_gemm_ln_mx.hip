@@ -12,7 +12,7 @@
 // step) are exactly the 2 x 16 bytes it supplies to one v_mfma_scale_f32_32x32x64_f8f6f4 (16 bytes of each of the row's two 32-k MX blocks, see
 // sf_gemm_mx.hip): 4 scaled MFMAs per phase (64 cycles each) where the bf16 kernel has 8 (32 cycles each) - twice the k per byte and per cycle.
 // Scales: the stage-major planes hold one dword per row per 128 k = per PAIR of k-steps; lanes < 32 supply the scale of the step's first block, lanes >= 32 of
-// its second (ds_read_u8 of byte 2 * (step & 1) + hi of the dword).  A pair's 768 + 128 dwords travel as an EIGHTH piece per wave per k-step (global_load_lds_dword, 64 dwords):
+// its second (ds_read_u8 of byte 2 * (step & 1) + hi of the dword).  A pair's 768 + 128 dwords travel as an EIGHTH piece per wave per k-step (sf_dma_dword, 64 dwords):
 // with the A | W0 group of k-step k comes half (k & 1 ? 0 : 1) of pair (k + 1) >> 1 - half 0 = W rows 0-511, half 1 = W rows 512-767 | the tile's 128 A rows |
 // 2 dummy pieces (every wave issues the same number of loads, so every counted wait is vmcnt(8)).  Three 4-KiB scale slots (pair % 3) live in the
 // epilogue's transposition slabs, which are idle while the main loop runs.
@@ -20,7 +20,6 @@
 // un-fused pair gives it; a 32-column block = 8 consecutive lanes, amax on DPP) and stages the scale bytes in LDS for two coalesced dword stores per lane.
 #include "sf_gemm_ln_common.h"
 #include <stdlib.h>
-#include <type_traits>
 #include "../../include/synchformer_hip.h"
 
 #define XL_BK 64                                        // fp8 elements = bytes per row per k-step
@@ -52,21 +51,6 @@ struct MxResLnArgs {
   uint32_t stagger;                                               // as in sf_gemm_ln.hip: the workgroups with one tile fewer start stagger x ~1.2 us late (SF_RL_STAGGER)
 };
 
-// 64 dwords (one per lane) -> 256 consecutive bytes of LDS
-__device__ __forceinline__ void xl_dma_dword(uint32_t v0, const void* sbase, uint32_t l0) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 3\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(v0), "s"(sbase), "s"(l0) : "memory");
-}
-
-// The lane index, re-derived where it is needed (mbcnt over an opaque zero: not hoisted, not kept): the kernel runs at the 256-register limit, and a thread
-// id kept live across the tile loop was spilled - its reload in the epilogue sat behind a compiler vmcnt(0), i.e. behind the 48 X stores in flight.
-__device__ __forceinline__ int xl_lane() {
-  int z = 0;
-  asm volatile("" : "+v"(z));
-  return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, z));
-}
-
 __global__ __launch_bounds__(512, 2) void gemm_mx_res_ln768_kernel(MxResLnArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -75,7 +59,7 @@ __global__ __launch_bounds__(512, 2) void gemm_mx_res_ln768_kernel(MxResLnArgs p
   // ---- LDS-DMA addressing: lane i of a piece fills (row i >> 2, slot i & 3) with source chunk slot ^ ((row >> 2) & 3) ----
   const int prow = lane >> 2, pslot = lane & 3;
   const int pchunk = pslot ^ ((prow >> 2) & 3);
-  const uint32_t lds0 = __builtin_amdgcn_readfirstlane(rl_lds_addr(smem));
+  const uint32_t lds0 = __builtin_amdgcn_readfirstlane(sf_lds_addr(smem));
   const uint32_t lane4 = (uint32_t)lane * 4u;
 
   const int nk = p.K / XL_BK;                                      // even (K % 128 == 0)
@@ -89,7 +73,7 @@ __global__ __launch_bounds__(512, 2) void gemm_mx_res_ln768_kernel(MxResLnArgs p
   auto set_tile = [&](int64_t mm) {                                // (lane quantities re-derived from an opaque thread id in 32-bit arithmetic: kept live across
     sa = reinterpret_cast<const char*>(p.A) + mm * p.lda;          // the main loop they were spilled, and the reload sat behind a vmcnt(0) on the X stores)
     sa_sc = reinterpret_cast<const char*>(p.sA) + mm * 4;
-    const int sl = xl_lane();
+    const int sl = sf_lane();
     const int srow = sl >> 2, schunk = (sl & 3) ^ ((srow >> 2) & 3);
     const int64_t left = p.M - 1 - mm;                             // tail tile: rows beyond M re-read the last valid row (their outputs are dropped)
     const int last = left < 127 ? (int)left : 127;
@@ -121,17 +105,17 @@ __global__ __launch_bounds__(512, 2) void gemm_mx_res_ln768_kernel(MxResLnArgs p
     if (ODD) {                                                     // half 0 of the NEXT pair (the one after kq's): W rows wave * 64 .. + 63
       wslot = wslot == 2 * XL_SC_SLOT ? 0u : wslot + XL_SC_SLOT;
       const int pq = (kq + 1 == nk ? 0 : kq + 1) >> 1;
-      xl_dma_dword(lane4, reinterpret_cast<const char*>(p.sW) + (int64_t)pq * p.ldsw + wave * 256, lds0 + XL_SC_OFF + wslot + wave * 256);
+      sf_dma_dword(lane4, reinterpret_cast<const char*>(p.sW) + (int64_t)pq * p.ldsw + wave * 256, lds0 + XL_SC_OFF + wslot + wave * 256);
     } else {                                                       // half 1 of kq's own pair
       const int pq = kq >> 1;
       const char* src = h1_is_a ? sa_sc + (int64_t)pq * p.ldsa : reinterpret_cast<const char*>(p.sW) + (int64_t)pq * p.ldsw;
-      xl_dma_dword(lane4, src + sc_src1, lds0 + XL_SC_OFF + wslot + sc_dst1);
+      sf_dma_dword(lane4, src + sc_src1, lds0 + XL_SC_OFF + wslot + sc_dst1);
     }
   };
   auto pp_issue_w = [&](int c, int slot) {
-    rl_dma2(voff_w[0], voff_w[1], c == 0 ? w0 + wo2 : (c == 1 ? wb1 + wo1 : wb2 + wo1), lds0 + slot * RP_STRIDE + RP_W_OFF + c * RP_THIRD + wave * 2048);
+    sf_dma2(voff_w[0], voff_w[1], c == 0 ? w0 + wo2 : (c == 1 ? wb1 + wo1 : wb2 + wo1), lds0 + slot * RP_STRIDE + RP_W_OFF + c * RP_THIRD + wave * 2048);
   };
-  auto pp_issue_a = [&](int slot) { rl_dma1(voff_a0, reinterpret_cast<const char*>(sa) + wo2, lds0 + slot * RP_STRIDE + wave * 1024); };
+  auto pp_issue_a = [&](int slot) { sf_dma1(voff_a0, reinterpret_cast<const char*>(sa) + wo2, lds0 + slot * RP_STRIDE + wave * 1024); };
   auto pp_advance = [&]() {                                        // end of a k-step: kt+2 becomes kt+1, the next rotated k-step becomes kt+2
     wo1 = wo2;
     if (++kq2 == nk) { kq2 = 0; wo2 = 0; } else wo2 += XL_BK;
@@ -139,14 +123,14 @@ __global__ __launch_bounds__(512, 2) void gemm_mx_res_ln768_kernel(MxResLnArgs p
   auto pp_prologue = [&]() {   // pair 0's scales | A | W0 of k-step 0, then W1, W2 of k-step 0, A | W0 of k-step 1 + half 0 of pair 1: 13 pieces per wave
     const int k0 = kmap(0), k1 = kmap(1);
     wslot = 0;
-    xl_dma_dword(lane4, reinterpret_cast<const char*>(p.sW) + (int64_t)(k0 >> 1) * p.ldsw + wave * 256, lds0 + XL_SC_OFF + wave * 256);
+    sf_dma_dword(lane4, reinterpret_cast<const char*>(p.sW) + (int64_t)(k0 >> 1) * p.ldsw + wave * 256, lds0 + XL_SC_OFF + wave * 256);
     issue_scale(std::false_type{}, k0);
-    rl_dma1(voff_a0, reinterpret_cast<const char*>(sa) + k0 * XL_BK, lds0 + wave * 1024);
-    rl_dma2(voff_w[0], voff_w[1], w0 + k0 * XL_BK, lds0 + RP_W_OFF + wave * 2048);
-    rl_dma2(voff_w[0], voff_w[1], wb1 + k0 * XL_BK, lds0 + RP_W_OFF + RP_THIRD + wave * 2048);
-    rl_dma2(voff_w[0], voff_w[1], wb2 + k0 * XL_BK, lds0 + RP_W_OFF + 2 * RP_THIRD + wave * 2048);
-    rl_dma1(voff_a0, reinterpret_cast<const char*>(sa) + k1 * XL_BK, lds0 + RP_STRIDE + wave * 1024);
-    rl_dma2(voff_w[0], voff_w[1], w0 + k1 * XL_BK, lds0 + RP_STRIDE + RP_W_OFF + wave * 2048);
+    sf_dma1(voff_a0, reinterpret_cast<const char*>(sa) + k0 * XL_BK, lds0 + wave * 1024);
+    sf_dma2(voff_w[0], voff_w[1], w0 + k0 * XL_BK, lds0 + RP_W_OFF + wave * 2048);
+    sf_dma2(voff_w[0], voff_w[1], wb1 + k0 * XL_BK, lds0 + RP_W_OFF + RP_THIRD + wave * 2048);
+    sf_dma2(voff_w[0], voff_w[1], wb2 + k0 * XL_BK, lds0 + RP_W_OFF + 2 * RP_THIRD + wave * 2048);
+    sf_dma1(voff_a0, reinterpret_cast<const char*>(sa) + k1 * XL_BK, lds0 + RP_STRIDE + wave * 1024);
+    sf_dma2(voff_w[0], voff_w[1], w0 + k1 * XL_BK, lds0 + RP_STRIDE + RP_W_OFF + wave * 2048);
     issue_scale(std::true_type{}, k1);
     wo1 = (uint32_t)k1 * XL_BK;
     kq2 = nk > 2 ? kmap(2) : 0;
@@ -185,7 +169,7 @@ __global__ __launch_bounds__(512, 2) void gemm_mx_res_ln768_kernel(MxResLnArgs p
       int fa[2], fw[2];                                            // fragment addresses in the CURRENT stage (bit 16 flipped once per k-step)
       int fsa, fsw;                                                // this half-wave's scale BYTE (block hi of step 0) in the current slot: A rows wm*64 + l31 (+ i*32), W rows wn*192 + l31 (+ c*64 + jj*32)
       {
-        const int pl = xl_lane();
+        const int pl = sf_lane();
         const int pl31 = pl & 31, phi = pl >> 5;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
@@ -234,31 +218,31 @@ __global__ __launch_bounds__(512, 2) void gemm_mx_res_ln768_kernel(MxResLnArgs p
           a[i] = frag(smem + i * 2048, fa);
           sav[i] = (int)*reinterpret_cast<const uint8_t*>(smem + fsa + i * 128 + S * 2);
         }
-        read_w(std::integral_constant<int, 0>{}, Sc);
+        read_w(sf_ic<0>{}, Sc);
         __builtin_amdgcn_sched_barrier(0);
         if (more1) pp_issue_w(1, S ^ 1);
-        if (!more1) rl_wait_vmcnt<2>();                            // W third 1 of this k-step has landed; the youngest stage stays in flight
-        else if (behind) rl_wait_vmcnt<8 + XL_STORES>();
-        else rl_wait_vmcnt<8>();
-        rl_barrier();
+        if (!more1) sf_wait_vmcnt<2>();                            // W third 1 of this k-step has landed; the youngest stage stays in flight
+        else if (behind) sf_wait_vmcnt<8 + XL_STORES>();
+        else sf_wait_vmcnt<8>();
+        sf_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        mma(std::integral_constant<int, 0>{});
+        mma(sf_ic<0>{});
         __builtin_amdgcn_sched_barrier(0);
-        rl_barrier();
+        sf_barrier();
         // ---- phase 1: third 1 ----
-        read_w(std::integral_constant<int, 1>{}, Sc);
+        read_w(sf_ic<1>{}, Sc);
         __builtin_amdgcn_sched_barrier(0);
         if (more1) pp_issue_w(2, S ^ 1);
-        if (!more1) rl_wait_vmcnt<0>();                            // W third 2 has landed
-        else if (behind) rl_wait_vmcnt<8 + XL_STORES>();
-        else rl_wait_vmcnt<8>();
-        rl_barrier();
+        if (!more1) sf_wait_vmcnt<0>();                            // W third 2 has landed
+        else if (behind) sf_wait_vmcnt<8 + XL_STORES>();
+        else sf_wait_vmcnt<8>();
+        sf_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        mma(std::integral_constant<int, 1>{});
+        mma(sf_ic<1>{});
         __builtin_amdgcn_sched_barrier(0);
-        rl_barrier();
+        sf_barrier();
         // ---- phase 2: third 2; the fragment addresses move on to the other stage ----
-        read_w(std::integral_constant<int, 2>{}, Sc);
+        read_w(sf_ic<2>{}, Sc);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
           asm volatile("v_xor_b32 %0, 0x10000, %0" : "+v"(fa[ks]));
@@ -272,36 +256,36 @@ __global__ __launch_bounds__(512, 2) void gemm_mx_res_ln768_kernel(MxResLnArgs p
         if (more2) { pp_issue_a(S); pp_issue_w(0, S); issue_scale(std::integral_constant<bool, S == 1>{}, kq2); }
         pp_advance();
         if (more1) {                                               // A | W third 0 (| scale piece) of the next k-step have landed
-          if (!more2) rl_wait_vmcnt<4>();
-          else if (behind) rl_wait_vmcnt<8 + XL_STORES>();
-          else rl_wait_vmcnt<8>();
+          if (!more2) sf_wait_vmcnt<4>();
+          else if (behind) sf_wait_vmcnt<8 + XL_STORES>();
+          else sf_wait_vmcnt<8>();
         }
-        rl_barrier();
+        sf_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        mma(std::integral_constant<int, 2>{});
+        mma(sf_ic<2>{});
         __builtin_amdgcn_sched_barrier(0);
-        rl_barrier();
+        sf_barrier();
       };
       // pair 0's scales | A | W third 0 of k-step 0 have landed (this wave's pieces), then everybody's
-      if (SF_XL_STORECNT && stores_behind) rl_wait_vmcnt<8 + XL_STORES>();
-      else rl_wait_vmcnt<8>();
-      rl_barrier();
-      if (wm == 1) rl_barrier();                                   // the wm = 1 waves run one barrier behind
+      if (SF_XL_STORECNT && stores_behind) sf_wait_vmcnt<8 + XL_STORES>();
+      else sf_wait_vmcnt<8>();
+      sf_barrier();
+      if (wm == 1) sf_barrier();                                   // the wm = 1 waves run one barrier behind
       int kt_first = 0;
       asm volatile("" : "+s"(kt_first));
       for (int kt = 0; kt < nk; kt += 2) {
         const bool more = kt + 2 < nk;
-        kstep(std::integral_constant<int, 0>{}, true, more, kt == kt_first);
-        kstep(std::integral_constant<int, 1>{}, more, more, false);
+        kstep(sf_ic<0>{}, true, more, kt == kt_first);
+        kstep(sf_ic<1>{}, more, more, false);
       }
-      if (wm == 0) rl_barrier();                                   // re-align; also: every wave is done with both stages and the scale slots
+      if (wm == 0) sf_barrier();                                   // re-align; also: every wave is done with both stages and the scale slots
     }
     const int64_t em0 = m0;
     const uint32_t tnext = t + gridDim.x;
     const bool more = tnext < p.tiles;
 
     // ---- epilogue, passes 1-3: as in gemm_res_ln768_kernel (sf_gemm_ln.hip has the commentary) ----------------------------------------------
-    const int elane = xl_lane(), l31 = elane & 31, hi = elane >> 5, lr = elane >> 4, ecol = (elane & 15) * 4;
+    const int elane = sf_lane(), l31 = elane & 31, hi = elane >> 5, lr = elane >> 4, ecol = (elane & 15) * 4;
     const int gcol0 = wn * 192 + ecol;                             // + c * 64
     float* slab = reinterpret_cast<float*>(smem + RP_SLAB_OFF + wave * RL_SLAB_BYTES);
     const int ring_off = (wave >> 2) * RP_STRIDE + (wave & 3) * RL_RING_WAVE;
@@ -321,7 +305,7 @@ __global__ __launch_bounds__(512, 2) void gemm_mx_res_ln768_kernel(MxResLnArgs p
         if (rl > rlast) rl = rlast;
         vo[ps] = (uint32_t)(rl * (int)p.ldr + gcol0 + c * 64) * 4u;
       }
-      rl_dma_r4(vo[0], vo[1], vo[2], vo[3], rbase, ring_lds + (s % 3) * 4096);
+      sf_dma4s_nt(vo[0], vo[1], vo[2], vo[3], rbase, ring_lds + (s % 3) * 4096);
     };
     issue_res(0); issue_res(1); issue_res(2);
     float4 xr[4][3][4];
@@ -359,7 +343,7 @@ __global__ __launch_bounds__(512, 2) void gemm_mx_res_ln768_kernel(MxResLnArgs p
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
           const float4 v = xr[g][c][ps];
-          rl_u32x4 o;
+          u32x4 o;
           o.x = __float_as_uint(v.x); o.y = __float_as_uint(v.y); o.z = __float_as_uint(v.z); o.w = __float_as_uint(v.w);
           __builtin_amdgcn_raw_buffer_store_b128(o, rx, xoff0 + (uint32_t)(g * 4 + ps) * xstep + (uint32_t)c * 256u, 0, 2);
         }
@@ -371,12 +355,10 @@ __global__ __launch_bounds__(512, 2) void gemm_mx_res_ln768_kernel(MxResLnArgs p
         float sres = 0.f;
 #pragma unroll
         for (int c = 0; c < 3; ++c) sres += (xr[g][c][ps].x + xr[g][c][ps].y) + (xr[g][c][ps].z + xr[g][c][ps].w);
-        sres = rl_row16_sum(sres);
+        sres = sum16_dpp(sres);
         if ((elane & 15) == 0) stat[srow0 + (g * 16 + ps * 4) * 4 + wn] = sres;
       }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");              // raw barrier: __syncthreads() would also drain the 48 stores in flight
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    sf_lgkm0_barrier();                                           // raw barrier: __syncthreads() would also drain the 48 stores in flight
     // every wave is past its residual ring and its slab: the operand slots and scale slots 0 / 1 take the next tile's first loads
     if (more) {
       m0 = (int64_t)tnext * RL_BM;
@@ -398,12 +380,10 @@ __global__ __launch_bounds__(512, 2) void gemm_mx_res_ln768_kernel(MxResLnArgs p
           const float dx = v.x - mu, dy = v.y - mu, dz = v.z - mu, dw = v.w - mu;
           sres += (dx * dx + dy * dy) + (dz * dz + dw * dw);
         }
-        sres = rl_row16_sum(sres);
+        sres = sum16_dpp(sres);
         if ((elane & 15) == 0) stat2[srow0 + (g * 16 + ps * 4) * 4 + wn] = sres;
       }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    sf_lgkm0_barrier();
     // ---- pass 4: normalise, scale, shift, bf16-round, quantise to e4m3 with the block's E8M0 scale, store ------------------------------------
     const uint32_t yoff0 = (uint32_t)(row0 * p.ldy + gcol0), ystep = (uint32_t)(4 * p.ldy);
     uint8_t* ys = reinterpret_cast<uint8_t*>(smem + XL_YS_OFF);
@@ -445,9 +425,7 @@ __global__ __launch_bounds__(512, 2) void gemm_mx_res_ln768_kernel(MxResLnArgs p
         }
       }
     // the tile's 768 scale dwords (6 planes x 128 rows), coalesced: two stores per lane (the second only in waves 0-3); rows >= M get an offset the range check drops
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    sf_lgkm0_barrier();
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       const int d = wave * 64 + elane + k * 512;

@@ -12,9 +12,8 @@
 // half-wave supplies the other 16) and ONE scale byte - that of block (lane >> 5) - taken from a dword (the 4 block scales of the row for the 128-deep
 // stage) that is loaded from the stage-major scale planes one stage ahead.  Which byte of a block lands in which operand dword cannot matter: A and W
 // use the same map and the dot product is a sum over the block; which BLOCK a byte is counted in does, and was established on the hardware.
-#include "sf_common.h"
+#include "sf_gemm_epi.h"
 #include <stdlib.h>
-#include <type_traits>
 #include "../../include/synchformer_hip.h"
 
 #ifndef SF_MX_ABL
@@ -32,13 +31,12 @@
 #define MX_SCALE_OFF (2 * MX_STAGE)          // 2 slots x (1 KiB of A scale dwords + 1 KiB of W scale dwords) behind the operand slots
 #define MX_LDS (MX_SCALE_OFF + 4096)       // 132 KiB; the epilogue slabs overlay operand slot 1 (only stage 0 of the next tile is prefetched under the epilogue)
 #ifndef SF_MX_STORE_AUX
-#define SF_MX_STORE_AUX 2
+#define SF_MX_STORE_AUX 2                // cache-policy bits of the epilogue's stores (as SF_EPI_STORE_AUX of the bf16 GEMMs: nt)
 #endif
+#define SF_MX_LOAD_AUX 2                 // the fp32 residual is read once: nt
 
 typedef __attribute__((ext_vector_type(8))) int mx_i32x8;
 typedef __attribute__((ext_vector_type(4))) int mx_i32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int mx_u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int mx_u32x2;
 
 struct MxArgs {
   const uint8_t* A; int64_t lda; const uint8_t* sA; int64_t ldsa;
@@ -51,100 +49,6 @@ struct MxArgs {
   int N, K;
   uint32_t tiles_n, tiles_total, nchunk;
 };
-
-__device__ __forceinline__ uint32_t mx_lds_addr(const void* p) { return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char*)p; }
-
-// Four LDS-DMA pieces (1 KiB each, consecutive in LDS from the wave-uniform address l0): SGPR base + zero-extended 32-bit lane offsets (the
-// operands stay below 4 GiB; 64-bit lane pointers do not fit next to 128 accumulators + the wider MX fragments: they spilled into the k-loop).
-__device__ __forceinline__ void mx_dma4(uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3, const void* sbase, uint32_t l0) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %5\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %5\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %5\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %5\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(v0), "v"(v1), "v"(v2), "v"(v3), "s"(sbase), "s"(l0)
-      : "memory", "scc");
-}
-
-__device__ __forceinline__ void mx_dma1(uint32_t v0, const void* sbase, uint32_t l0) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(v0), "s"(sbase), "s"(l0) : "memory");
-}
-__device__ __forceinline__ void mx_dma2(uint32_t v0, uint32_t v1, const void* sbase, uint32_t l0) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(v0), "v"(v1), "s"(sbase), "s"(l0)
-      : "memory", "scc");
-}
-
-__device__ __forceinline__ void mx_wait_vmcnt0_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_waitcnt((0 & 0xF) | (0x7 << 4) | (0xF << 8) | (0 << 14));
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
-// OUT: 0 = fp32, 1 = bf16, 2 = MXFP8 (the output is the next MX GEMM's A operand: e4m3 bytes + one E8M0 byte per 32 columns, quantised from the bf16-
-// rounded value exactly as sf_quantize_mxfp8 would from a bf16 buffer; a 32-column block = 8 consecutive lanes of the 16-lane row group).
-template <int OUT, bool GELU, bool HAS_RES, int NPS = 4>
-__device__ __forceinline__ void mx_epi_store(float4 (&v)[NPS], const float4& bias4, const float4 (&res)[NPS], __amdgpu_buffer_rsrc_t rc, uint32_t coff, uint32_t cstep,
-                                             __amdgpu_buffer_rsrc_t rsc = __amdgpu_buffer_rsrc_t(), uint32_t sc_off = 0, int rows_left = 0) {
-  constexpr bool OUT_BF16 = OUT == 1;
-#pragma unroll
-  for (int ps = 0; ps < NPS; ++ps) {
-    float4 x = v[ps];
-    x.x += bias4.x; x.y += bias4.y; x.z += bias4.z; x.w += bias4.w;
-    if (GELU) {
-      sf_f32x2_t g0 = {x.x, x.y}, g1 = {x.z, x.w};
-      gelu_erf4(g0, g1);
-      x.x = g0.x; x.y = g0.y; x.z = g1.x; x.w = g1.y;
-    }
-    if (HAS_RES) { x.x += res[ps].x; x.y += res[ps].y; x.z += res[ps].z; x.w += res[ps].w; }
-    if (OUT == 2) {
-      const uint32_t p01 = pack_bf2(x.x, x.y), p23 = pack_bf2(x.z, x.w);
-      const float f0 = __uint_as_float(p01 << 16), f1 = __uint_as_float(p01 & 0xffff0000u), f2 = __uint_as_float(p23 << 16), f3 = __uint_as_float(p23 & 0xffff0000u);
-      float amax = fmaxf(fmaxf(fabsf(f0), fabsf(f1)), fmaxf(fabsf(f2), fabsf(f3)));
-      // max over the block's eight lanes on DPP (no LDS traffic): quad_perm [1,0,3,2], quad_perm [2,3,0,1], then row_half_mirror (lane i <-> 7 - i)
-      amax = fmaxf(amax, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(amax), 0xB1, 0xF, 0xF, true)));
-      amax = fmaxf(amax, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(amax), 0x4E, 0xF, 0xF, true)));
-      amax = fmaxf(amax, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(amax), 0x141, 0xF, 0xF, true)));
-      int be = sf_mx_be(amax);
-      be = be < 1 ? 1 : (be > 254 ? 254 : be);
-      const float inv = __uint_as_float((uint32_t)(254 - be) << 23);
-      int w = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(f0 * inv, 448.f, -448.f), __builtin_amdgcn_fmed3f(f1 * inv, 448.f, -448.f), 0, false);
-      w = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(f2 * inv, 448.f, -448.f), __builtin_amdgcn_fmed3f(f3 * inv, 448.f, -448.f), w, true);
-      __builtin_amdgcn_raw_buffer_store_b32((uint32_t)w, rc, coff + ps * cstep, 0, SF_MX_STORE_AUX);
-      // one scale byte per row and 32-column block, from the first lane of the block's eight; every other lane (and rows >= M, which would land in the
-      // next plane) gets an out-of-range offset that the buffer range check drops - no exec-mask branch in the store loop
-      __builtin_amdgcn_raw_buffer_store_b8((uint8_t)be, rsc, ps * 4 < rows_left ? sc_off + ps * 16 : 0xffffffffu, 0, 0);
-    } else if (OUT_BF16) {
-      mx_u32x2 o; o.x = pack_bf2(x.x, x.y); o.y = pack_bf2(x.z, x.w);
-      __builtin_amdgcn_raw_buffer_store_b64(o, rc, coff + ps * cstep, 0, SF_MX_STORE_AUX);
-    } else {
-      mx_u32x4 o;
-      o.x = __float_as_uint(x.x); o.y = __float_as_uint(x.y); o.z = __float_as_uint(x.z); o.w = __float_as_uint(x.w);
-      __builtin_amdgcn_raw_buffer_store_b128(o, rc, coff + ps * cstep, 0, SF_MX_STORE_AUX);
-    }
-  }
-}
-template <int NPS>
-__device__ __forceinline__ void mx_load_res(float4 (&res)[NPS], __amdgpu_buffer_rsrc_t rr, uint32_t roff, uint32_t rstep) {
-#pragma unroll
-  for (int ps = 0; ps < NPS; ++ps) {
-    const mx_u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(rr, roff + ps * rstep, 0, 2);
-    res[ps] = make_float4(__uint_as_float(t.x), __uint_as_float(t.y), __uint_as_float(t.z), __uint_as_float(t.w));
-  }
-}
 
 template <int OUT, bool GELU, bool HAS_RES>
 __global__ __launch_bounds__(512, 2) void gemm_mxfp8_persistent_kernel(MxArgs p) {
@@ -191,20 +95,20 @@ __global__ __launch_bounds__(512, 2) void gemm_mxfp8_persistent_kernel(MxArgs p)
       b_src[i] = (uint32_t)((int64_t)br * p.ldw + gch * 16);
     }
   };
-  const uint32_t lds_wave = __builtin_amdgcn_readfirstlane(mx_lds_addr(smem) + (wave * 4) * 1024);
+  const uint32_t lds_wave = __builtin_amdgcn_readfirstlane(sf_lds_addr(smem) + (wave * 4) * 1024);
   auto stage = [&](int s, int kt) {
     const uint32_t l = lds_wave + s * MX_STAGE;
-    mx_dma4(a_src[0] + kt * MXBK, a_src[1] + kt * MXBK, a_src[2] + kt * MXBK, a_src[3] + kt * MXBK, p.A, l);
-    mx_dma4(b_src[0] + kt * MXBK, b_src[1] + kt * MXBK, b_src[2] + kt * MXBK, b_src[3] + kt * MXBK, p.W, l + MXBM * MXBK);
+    sf_dma4s(a_src[0] + kt * MXBK, a_src[1] + kt * MXBK, a_src[2] + kt * MXBK, a_src[3] + kt * MXBK, p.A, l);
+    sf_dma4s(b_src[0] + kt * MXBK, b_src[1] + kt * MXBK, b_src[2] + kt * MXBK, b_src[3] + kt * MXBK, p.W, l + MXBM * MXBK);
   };
   // scale matrices are STAGE-major: plane kt (ld bytes apart) holds one dword per row = the four E8M0 bytes of that row's 128-deep stage kt, so the
   // scales of a stage's 256 A rows (and of its 256 W rows) are ONE contiguous KiB = one LDS-DMA piece each (waves 0 and 1), next to the stage's 64
   // operand pieces.  As six dword loads per lane they were 48 more vector-memory instructions per stage - on the path that bounds the k-loop.
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-  const uint32_t lds_sc = __builtin_amdgcn_readfirstlane(mx_lds_addr(smem) + MX_SCALE_OFF);
+  const uint32_t lds_sc = __builtin_amdgcn_readfirstlane(sf_lds_addr(smem) + MX_SCALE_OFF);
   auto scale_piece = [&](int s, int kt, int64_t mm, int nn) {      // planes are padded to whole 256-row tiles (host check): no clamping
-    if (wave_u == 0) mx_dma1((uint32_t)lane * 16u, p.sA + (int64_t)kt * p.ldsa + mm * 4, lds_sc + s * 2048);
-    else if (wave_u == 1) mx_dma1((uint32_t)lane * 16u, p.sW + (int64_t)kt * p.ldsw + (int64_t)nn * 4, lds_sc + s * 2048 + 1024);
+    if (wave_u == 0) sf_dma1((uint32_t)lane * 16u, p.sA + (int64_t)kt * p.ldsa + mm * 4, lds_sc + s * 2048);
+    else if (wave_u == 1) sf_dma1((uint32_t)lane * 16u, p.sW + (int64_t)kt * p.ldsw + (int64_t)nn * 4, lds_sc + s * 2048 + 1024);
   };
   const int sa_rd = MX_SCALE_OFF + (wm * 128 + l31) * 4, sb_rd = MX_SCALE_OFF + 1024 + (wn * 64 + l31) * 4;
 
@@ -237,7 +141,7 @@ __global__ __launch_bounds__(512, 2) void gemm_mxfp8_persistent_kernel(MxArgs p)
     // and sinks the MFMAs of the first 64-deep step below the fragment reads of the second (96 fragment registers live, ~60 spills in the loop).
     auto kstep = [&](int kt, auto refill_tag) {
       constexpr bool REFILL = decltype(refill_tag)::value;
-      mx_wait_vmcnt0_barrier();                                    // stage kt (and its scale dwords) landed; slot (kt+1)&1 is free
+      sf_wait_vmcnt_barrier<0>();                                    // stage kt (and its scale dwords) landed; slot (kt+1)&1 is free
       uint32_t sa_c[4], sb_c[2];
 #pragma unroll
       for (int i = 0; i < 4; ++i) sa_c[i] = *reinterpret_cast<const uint32_t*>(smem + sa_rd + (kt & 1) * 2048 + i * 128);
@@ -282,8 +186,8 @@ __global__ __launch_bounds__(512, 2) void gemm_mxfp8_persistent_kernel(MxArgs p)
               __builtin_amdgcn_sched_barrier(0);
               const uint32_t l = lds_wave + ((kt + 1) & 1) * MX_STAGE;
               const int ko = (kt + 1) * MXBK;
-              if (ih == 0) mx_dma2(a_src[2 * ii] + ko, a_src[2 * ii + 1] + ko, p.A, l + ii * 2048);
-              else mx_dma2(b_src[2 * ii] + ko, b_src[2 * ii + 1] + ko, p.W, l + MXBM * MXBK + ii * 2048);
+              if (ih == 0) sf_dma2_nop0(a_src[2 * ii] + ko, a_src[2 * ii + 1] + ko, p.A, l + ii * 2048);
+              else sf_dma2_nop0(b_src[2 * ii] + ko, b_src[2 * ii + 1] + ko, p.W, l + MXBM * MXBK + ii * 2048);
               __builtin_amdgcn_sched_barrier(0);
             }
           }
@@ -291,8 +195,8 @@ __global__ __launch_bounds__(512, 2) void gemm_mxfp8_persistent_kernel(MxArgs p)
             __builtin_amdgcn_sched_barrier(0);
             const uint32_t l = lds_wave + ((kt + 1) & 1) * MX_STAGE;
             const int ko = (kt + 1) * MXBK;
-            if (ih == 0) mx_dma4(a_src[0] + ko, a_src[1] + ko, a_src[2] + ko, a_src[3] + ko, p.A, l);
-            else mx_dma4(b_src[0] + ko, b_src[1] + ko, b_src[2] + ko, b_src[3] + ko, p.W, l + MXBM * MXBK);
+            if (ih == 0) sf_dma4s(a_src[0] + ko, a_src[1] + ko, a_src[2] + ko, a_src[3] + ko, p.A, l);
+            else sf_dma4s(b_src[0] + ko, b_src[1] + ko, b_src[2] + ko, b_src[3] + ko, p.W, l + MXBM * MXBK);
             __builtin_amdgcn_sched_barrier(0);
           }
         }
@@ -300,8 +204,8 @@ __global__ __launch_bounds__(512, 2) void gemm_mxfp8_persistent_kernel(MxArgs p)
         if (SF_MX_DMA == 0 && REFILL && !(SF_MX_ABL & 2)) {
           const uint32_t l = lds_wave + ((kt + 1) & 1) * MX_STAGE;
           const int ko = (kt + 1) * MXBK;
-          if (kk == 0) mx_dma4(a_src[0] + ko, a_src[1] + ko, a_src[2] + ko, a_src[3] + ko, p.A, l);
-          else mx_dma4(b_src[0] + ko, b_src[1] + ko, b_src[2] + ko, b_src[3] + ko, p.W, l + MXBM * MXBK);
+          if (kk == 0) sf_dma4s(a_src[0] + ko, a_src[1] + ko, a_src[2] + ko, a_src[3] + ko, p.A, l);
+          else sf_dma4s(b_src[0] + ko, b_src[1] + ko, b_src[2] + ko, b_src[3] + ko, p.W, l + MXBM * MXBK);
           __builtin_amdgcn_sched_barrier(0);
         }
         // the refill's 8 LDS-DMA issues ride behind the MFMAs of the FIRST 64-deep step: the whole stage is requested by the middle of the k-step
@@ -310,17 +214,15 @@ __global__ __launch_bounds__(512, 2) void gemm_mxfp8_persistent_kernel(MxArgs p)
         if (SF_MX_DMA == 1 && REFILL && kk == 0 && !(SF_MX_ABL & 2)) {
           const uint32_t l = lds_wave + ((kt + 1) & 1) * MX_STAGE;
           const int ko = (kt + 1) * MXBK;
-          mx_dma4(a_src[0] + ko, a_src[1] + ko, a_src[2] + ko, a_src[3] + ko, p.A, l);
-          mx_dma4(b_src[0] + ko, b_src[1] + ko, b_src[2] + ko, b_src[3] + ko, p.W, l + MXBM * MXBK);
+          sf_dma4s(a_src[0] + ko, a_src[1] + ko, a_src[2] + ko, a_src[3] + ko, p.A, l);
+          sf_dma4s(b_src[0] + ko, b_src[1] + ko, b_src[2] + ko, b_src[3] + ko, p.W, l + MXBM * MXBK);
           __builtin_amdgcn_sched_barrier(0);
         }
       }
     };
     for (int kt = 0; kt + 1 < nk; ++kt) kstep(kt, std::true_type{});
     kstep(nk - 1, std::false_type{});
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    sf_barrier();
     const int64_t em0 = m0; const int en0 = n0;
     const uint32_t tnext = t + per_xcd_blocks;
     const bool more = tnext < t_end;
@@ -339,11 +241,11 @@ __global__ __launch_bounds__(512, 2) void gemm_mxfp8_persistent_kernel(MxArgs p)
       float4 res[2][4];
 #pragma unroll
       for (int ps = 0; ps < 4; ++ps) res[0][ps] = res[1][ps] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (HAS_RES) mx_load_res<4>(res[0], rr, roff0, rstep);
+      if (HAS_RES) sf_epi_load_res<4, SF_MX_LOAD_AUX>(res[0], rr, roff0, rstep);
 #pragma unroll
       for (int g = 0; g < 8; ++g) {
         const int i = g >> 1, q2 = g & 1;
-        if (HAS_RES && g + 1 < 8) mx_load_res<4>(res[(g + 1) & 1], rr, roff0 + (g + 1) * 4 * rstep, rstep);
+        if (HAS_RES && g + 1 < 8) sf_epi_load_res<4, SF_MX_LOAD_AUX>(res[(g + 1) & 1], rr, roff0 + (g + 1) * 4 * rstep, rstep);
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -358,10 +260,10 @@ __global__ __launch_bounds__(512, 2) void gemm_mxfp8_persistent_kernel(MxArgs p)
           const int colblock = gcol >> 5;                          // this lane's 32-column block of the output row
           const int64_t left = p.M - (row0 + g * 16);            // rows_left <= 0 for every lane that must not write a scale byte
           const uint32_t sc_off = (uint32_t)((int64_t)(colblock >> 2) * p.ldsc + (colblock & 3) + (row0 + g * 16) * 4);
-          mx_epi_store<OUT, GELU, HAS_RES>(v, bias4, res[g & 1], rc, coff0 + g * 4 * cstep, cstep, rsc, sc_off,
+          sf_epi_store<OUT, GELU, HAS_RES, 4, SF_MX_STORE_AUX>(v, bias4, res[g & 1], rc, coff0 + g * 4 * cstep, cstep, rsc, sc_off,
                                            (lane & 7) == 0 ? (int)(left > 64 ? 64 : left) : 0);
         } else {
-          mx_epi_store<OUT, GELU, HAS_RES>(v, bias4, res[g & 1], rc, coff0 + g * 4 * cstep, cstep);
+          sf_epi_store<OUT, GELU, HAS_RES, 4, SF_MX_STORE_AUX>(v, bias4, res[g & 1], rc, coff0 + g * 4 * cstep, cstep);
         }
       }
     }
@@ -375,7 +277,7 @@ __global__ __launch_bounds__(512, 2) void gemm_mxfp8_persistent_kernel(MxArgs p)
 // Round 3: the quadrant-phased schedule of sf_gemm_pp.hip on MXFP8 operands (same BYTE geometry: a 128-deep fp8 k-tile = 4 half-tiles of 16 KiB,
 // a quadrant = 64 x 32 outputs = 4 MFMAs of 32x32x64 = the 256 matrix cycles of 8 bf16 MFMAs).  Differences to the bf16 kernel:
 //   * the scale dwords of a k-tile (one per row: the four E8M0 bytes of its 128-deep stage) are a NINTH piece per wave and k-tile - 64 rows x 4 bytes
-//     by global_load_lds_dword, waves 0-3 the A rows, waves 4-7 the W rows - issued with half-tile A0, all six dwords a lane needs read in phase 0
+//     by sf_dma_dword, waves 0-3 the A rows, waves 4-7 the W rows - issued with half-tile A0, all six dwords a lane needs read in phase 0
 //     (so the scale buffer is free for its refill two phases later, like A0): every counted wait is vmcnt(9);
 //   * a lane's scale byte of MFMA step kk is byte 2 kk + (lane >> 5) of its dword: the dwords are shifted by (lane >> 5) * 8 once per k-tile and the
 //     bytes picked with constant v_bfe in the read segment (the matrix segment stays pure MFMA);
@@ -392,33 +294,6 @@ __global__ __launch_bounds__(512, 2) void gemm_mxfp8_persistent_kernel(MxArgs p)
 #ifndef SF_MX_STORECNT
 #define SF_MX_STORECNT 1
 #endif
-
-__device__ __forceinline__ void mq_dma2(uint32_t v0, uint32_t v1, const void* sbase, uint32_t l0) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %4\n\ts_nop 3\n\tglobal_load_lds_dwordx4 %1, %3\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep) : "v"(v0), "v"(v1), "s"(sbase), "s"(l0) : "memory", "scc");
-}
-// 64 lanes x 4 bytes (a 256-byte piece): lane offset in %1, SGPR base
-__device__ __forceinline__ void mq_dma_dword(uint32_t v0, const void* sbase, uint32_t l0) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 3\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(v0), "s"(sbase), "s"(l0) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void mq_wait_vmcnt() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_waitcnt((N & 0xF) | (0x7 << 4) | (0xF << 8) | ((N >> 4) << 14));
-}
-__device__ __forceinline__ void mq_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-template <int V> using mq_ic = std::integral_constant<int, V>;
 
 template <int OUT, bool GELU, bool HAS_RES>
 __global__ __launch_bounds__(512, 2) void gemm_mxfp8_pp_kernel(MxArgs p) {
@@ -497,7 +372,7 @@ __global__ __launch_bounds__(512, 2) void gemm_mxfp8_pp_kernel(MxArgs p) {
       }
     }
   };
-  const uint32_t lds0 = __builtin_amdgcn_readfirstlane(mx_lds_addr(smem));
+  const uint32_t lds0 = __builtin_amdgcn_readfirstlane(sf_lds_addr(smem));
   const uint32_t lds_wave = lds0 + wave * 2048;
   const uint32_t lds_sc_w = lds0 + MQ_SCALE_OFF + wave * 256;      // + stage * 2048: [A rows 0-255 | W rows 0-255] dwords
   const uint32_t lane4 = (uint32_t)lane * 4u;
@@ -511,9 +386,9 @@ __global__ __launch_bounds__(512, 2) void gemm_mxfp8_pp_kernel(MxArgs p) {
     constexpr bool isA = PART == 0 || PART == 3;
     constexpr int h = PART >= 2 ? 1 : 0;
     const uint32_t l = lds_wave + ST * MQ_STAGE + (isA ? h : 2 + h) * MQ_HALF;
-    if (isA) mq_dma2(oA[h][0], oA[h][1], curA, l);
-    else mq_dma2(oW[h][0], oW[h][1], curW, l);
-    if (PART == 0) mq_dma_dword(lane4, curS, lds_sc_w + ST * 2048);
+    if (isA) sf_dma2(oA[h][0], oA[h][1], curA, l);
+    else sf_dma2(oW[h][0], oW[h][1], curW, l);
+    if (PART == 0) sf_dma_dword(lane4, curS, lds_sc_w + ST * 2048);
     if (PART == 3 && ld_ok) {
       if (++ld_kt == nk) {
         ld_kt = 0;
@@ -531,7 +406,7 @@ __global__ __launch_bounds__(512, 2) void gemm_mxfp8_pp_kernel(MxArgs p) {
   int64_t m0; int n0;
   tile_origin(t, m0, n0);
   char* bslab = smem + MQ_SLAB_OFF + wave * MQ_SLAB_BYTES;
-  const uint32_t slab_lds = __builtin_amdgcn_readfirstlane(mx_lds_addr(bslab));
+  const uint32_t slab_lds = __builtin_amdgcn_readfirstlane(sf_lds_addr(bslab));
   const uint32_t esz = OUT == 2 ? 1u : (OUT_BF16 ? 2u : 4u);
   const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(p.C, (short)0, (int)(uint32_t)(p.M * p.ldc * esz), 0x00020000);
   const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.R), (short)0, HAS_RES ? (int)(uint32_t)(p.M * p.ldr * 4) : 0, 0x00020000);
@@ -540,16 +415,16 @@ __global__ __launch_bounds__(512, 2) void gemm_mxfp8_pp_kernel(MxArgs p) {
   const bool has_bias = p.bias != nullptr;
   // the wave's 64 bias values: one 256-byte LDS-DMA piece into the (idle) slab at the top of the tile - no compiler-visible load, no compiler vmcnt(0)
   auto issue_bias = [&](int n0_) {
-    if (has_bias) mq_dma_dword(lane4, reinterpret_cast<const char*>(p.bias + min(n0_ + wn * 64, p.N - 64)), slab_lds);
+    if (has_bias) sf_dma_dword(lane4, reinterpret_cast<const char*>(p.bias + min(n0_ + wn * 64, p.N - 64)), slab_lds);
   };
 
   ld_set(ld_t);
   curA = ldA; curW = ldW; curS = ldS;
   issue_bias(n0);
-  issue(mq_ic<0>{}, mq_ic<0>{}); issue(mq_ic<1>{}, mq_ic<0>{}); issue(mq_ic<2>{}, mq_ic<0>{}); issue(mq_ic<3>{}, mq_ic<0>{});
-  issue(mq_ic<0>{}, mq_ic<1>{}); issue(mq_ic<1>{}, mq_ic<1>{});
-  mq_wait_vmcnt<9>();                                             // A0 (+ scales) | B0 of k-tile 0 have landed: B1, A1, A0 + scales, B0 (2 + 2 + 3 + 2) are younger
-  mq_barrier();
+  issue(sf_ic<0>{}, sf_ic<0>{}); issue(sf_ic<1>{}, sf_ic<0>{}); issue(sf_ic<2>{}, sf_ic<0>{}); issue(sf_ic<3>{}, sf_ic<0>{});
+  issue(sf_ic<0>{}, sf_ic<1>{}); issue(sf_ic<1>{}, sf_ic<1>{});
+  sf_wait_vmcnt<9>();                                             // A0 (+ scales) | B0 of k-tile 0 have landed: B1, A1, A0 + scales, B0 (2 + 2 + 3 + 2) are younger
+  sf_barrier();
   int extra = 0;
 
   for (;;) {
@@ -570,9 +445,9 @@ __global__ __launch_bounds__(512, 2) void gemm_mxfp8_pp_kernel(MxArgs p) {
     uint32_t sa[2][2], sb[2];                                     // scale dwords [ha][i], [hb], shifted so that byte 2 kk is this lane's block of step kk
 
     auto wait_loads = [&](bool issued, bool first) {
-      if (!issued) mq_wait_vmcnt<0>();
-      else if (SF_MX_STORECNT && first && extra) mq_wait_vmcnt<9 + EPI_VM>();
-      else mq_wait_vmcnt<9>();
+      if (!issued) sf_wait_vmcnt<0>();
+      else if (SF_MX_STORECNT && first && extra) sf_wait_vmcnt<9 + EPI_VM>();
+      else sf_wait_vmcnt<9>();
     };
     auto frag = [&](const char* base, const int (&off)[2][2], int kk) -> mx_i32x8 {
       const mx_i32x4 lo = *reinterpret_cast<const mx_i32x4*>(base + off[kk][0]);
@@ -617,24 +492,24 @@ __global__ __launch_bounds__(512, 2) void gemm_mxfp8_pp_kernel(MxArgs p) {
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) { sbv[kk] = pick(sb[0], kk); sav[0][kk] = pick(sa[0][0], kk); sav[1][kk] = pick(sa[0][1], kk); }
       __builtin_amdgcn_sched_barrier(0);
-      wait_loads(issue(mq_ic<2>{}, mq_ic<S ^ 1>{}), first);        // B1(kt+1) issued; B1(kt) landed
-      mq_barrier();
+      wait_loads(issue(sf_ic<2>{}, sf_ic<S ^ 1>{}), first);        // B1(kt+1) issued; B1(kt) landed
+      sf_barrier();
       __builtin_amdgcn_sched_barrier(0);
-      mma(mq_ic<0>{}, mq_ic<0>{}, b0, sav, sbv);
+      mma(sf_ic<0>{}, sf_ic<0>{}, b0, sav, sbv);
       __builtin_amdgcn_sched_barrier(0);
-      mq_barrier();
+      sf_barrier();
       // ---- phase 1: (A0, B1) ----
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) b1[kk] = frag(st + MQ_HALF, b_off, kk);
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) sbv[kk] = pick(sb[1], kk);
       __builtin_amdgcn_sched_barrier(0);
-      wait_loads(issue(mq_ic<3>{}, mq_ic<S ^ 1>{}), first);        // A1(kt+1) issued; A1(kt) landed
-      mq_barrier();
+      wait_loads(issue(sf_ic<3>{}, sf_ic<S ^ 1>{}), first);        // A1(kt+1) issued; A1(kt) landed
+      sf_barrier();
       __builtin_amdgcn_sched_barrier(0);
-      mma(mq_ic<0>{}, mq_ic<1>{}, b1, sav, sbv);
+      mma(sf_ic<0>{}, sf_ic<1>{}, b1, sav, sbv);
       __builtin_amdgcn_sched_barrier(0);
-      mq_barrier();
+      sf_barrier();
       // ---- phase 2: (A1, B1); the fragment addresses move on to the other stage ----
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk)
@@ -650,33 +525,33 @@ __global__ __launch_bounds__(512, 2) void gemm_mxfp8_pp_kernel(MxArgs p) {
           asm volatile("v_xor_b32 %0, 0x10000, %0" : "+v"(b_off[kk][h]));
         }
       __builtin_amdgcn_sched_barrier(0);
-      issue(mq_ic<0>{}, mq_ic<S>{});                               // A0 + scales of k-tile kt+2; phase 3 reads nothing: no wait
-      mq_barrier();
+      issue(sf_ic<0>{}, sf_ic<S>{});                               // A0 + scales of k-tile kt+2; phase 3 reads nothing: no wait
+      sf_barrier();
       __builtin_amdgcn_sched_barrier(0);
-      mma(mq_ic<1>{}, mq_ic<1>{}, b1, sav, sbv);
+      mma(sf_ic<1>{}, sf_ic<1>{}, b1, sav, sbv);
       __builtin_amdgcn_sched_barrier(0);
-      mq_barrier();
+      sf_barrier();
       // ---- phase 3: (A1, B0) ----
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) sbv[kk] = pick(sb[0], kk);
-      wait_loads(issue(mq_ic<1>{}, mq_ic<S>{}), first);            // B0(kt+2) issued; A0 + scales | B0 of k-tile kt+1 landed
-      mq_barrier();
+      wait_loads(issue(sf_ic<1>{}, sf_ic<S>{}), first);            // B0(kt+2) issued; A0 + scales | B0 of k-tile kt+1 landed
+      sf_barrier();
       __builtin_amdgcn_sched_barrier(0);
-      mma(mq_ic<1>{}, mq_ic<0>{}, b0, sav, sbv);
+      mma(sf_ic<1>{}, sf_ic<0>{}, b0, sav, sbv);
       __builtin_amdgcn_sched_barrier(0);
-      mq_barrier();
+      sf_barrier();
     };
 
-    if (wm == 1) mq_barrier();                                    // the wm = 1 waves run one barrier behind
+    if (wm == 1) sf_barrier();                                    // the wm = 1 waves run one barrier behind
     int kt_first = 0;
     asm volatile("" : "+s"(kt_first));                             // opaque zero: `kt == 0` lets hipcc peel the first iteration - a second copy of the body, with spills
     for (int kt = 0; kt < nk; kt += 2) {
-      ktile(mq_ic<0>{}, kt == kt_first);
-      ktile(mq_ic<1>{}, false);
+      ktile(sf_ic<0>{}, kt == kt_first);
+      ktile(sf_ic<1>{}, false);
     }
-    if (wm == 0) mq_barrier();
+    if (wm == 0) sf_barrier();
 
-    if (!ld_ok) mq_wait_vmcnt<0>();                                // a dry iterator's pieces must have landed before this workgroup's LDS can be handed on
+    if (!ld_ok) sf_wait_vmcnt<0>();                                // a dry iterator's pieces must have landed before this workgroup's LDS can be handed on
     const int64_t em0 = m0; const int en0 = n0;
     extra = 0;
     if (WIDEBF) {
@@ -704,14 +579,14 @@ __global__ __launch_bounds__(512, 2) void gemm_mxfp8_pp_kernel(MxArgs p) {
               sf_f32x2_t g0 = {acc[ib][j][g * 4 + 0] + bia[j][g].x, acc[ib][j][g * 4 + 1] + bia[j][g].y};
               sf_f32x2_t g1 = {acc[ib][j][g * 4 + 2] + bia[j][g].z, acc[ib][j][g * 4 + 3] + bia[j][g].w};
               if (GELU) gelu_erf4(g0, g1);
-              mx_u32x2 w2; w2.x = pack_bf2(g0.x, g0.y); w2.y = pack_bf2(g1.x, g1.y);
-              *reinterpret_cast<mx_u32x2*>(bslab + wr_off + ((g ^ wsw) << 4)) = w2;
+              u32x2 w2; w2.x = pack_bf2(g0.x, g0.y); w2.y = pack_bf2(g1.x, g1.y);
+              *reinterpret_cast<u32x2*>(bslab + wr_off + ((g ^ wsw) << 4)) = w2;
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
               const int tr = h * 16 + (el >> 2);
-              const mx_u32x4 o = *reinterpret_cast<const mx_u32x4*>(bslab + tr * 64 + (((el & 3) ^ ((tr >> 1) & 3)) << 4));
+              const u32x4 o = *reinterpret_cast<const u32x4*>(bslab + tr * 64 + (((el & 3) ^ ((tr >> 1) & 3)) << 4));
               __builtin_amdgcn_raw_buffer_store_b128(o, rc, (uint32_t)((em0 + wm * 128 + ib * 32 + tr) * p.ldc + en0 + wn * 64 + j * 32 + (el & 3) * 8) * 2u, 0, SF_MX_STORE_AUX);
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -770,16 +645,16 @@ __global__ __launch_bounds__(512, 2) void gemm_mxfp8_pp_kernel(MxArgs p) {
             // the low lane and 16..31 into the high lane, in order
             const auto s02 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
             const auto s13 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);
-            mx_u32x4 o; o.x = s02[0]; o.y = s02[1]; o.z = s13[0]; o.w = s13[1];
+            u32x4 o; o.x = s02[0]; o.y = s02[1]; o.z = s13[0]; o.w = s13[1];
             // through the wave's 2-KiB slab (32 tokens x 64 bytes, 16-byte chunk c of row t at slot c ^ ((t >> 1) & 3)): stored from the registers a row would go
             // out as 32-byte pieces, 32 write requests per instruction (measured: slower than the 4-byte stores it replaced); from the slab a store is 16 rows x 64 bytes
-            *reinterpret_cast<mx_u32x4*>(bslab + el31 * 64 + (((j * 2 + ehi) ^ ((el31 >> 1) & 3)) << 4)) = o;
+            *reinterpret_cast<u32x4*>(bslab + el31 * 64 + (((j * 2 + ehi) ^ ((el31 >> 1) & 3)) << 4)) = o;
           }
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
           for (int h = 0; h < 2; ++h) {
             const int tr = h * 16 + (el >> 2);
-            const mx_u32x4 o = *reinterpret_cast<const mx_u32x4*>(bslab + tr * 64 + (((el & 3) ^ ((tr >> 1) & 3)) << 4));
+            const u32x4 o = *reinterpret_cast<const u32x4*>(bslab + tr * 64 + (((el & 3) ^ ((tr >> 1) & 3)) << 4));
             __builtin_amdgcn_raw_buffer_store_b128(o, rc, (uint32_t)((em0 + wm * 128 + ib * 32 + tr) * p.ldc + en0 + wn * 64 + (el & 3) * 16), 0, SF_MX_STORE_AUX);
           }
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -802,11 +677,11 @@ __global__ __launch_bounds__(512, 2) void gemm_mxfp8_pp_kernel(MxArgs p) {
       float4 res[2][2];
 #pragma unroll
       for (int ps = 0; ps < 2; ++ps) res[0][ps] = res[1][ps] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (HAS_RES) mx_load_res<2>(res[0], rr, roff0, rstep);
+      if (HAS_RES) sf_epi_load_res<2, SF_MX_LOAD_AUX>(res[0], rr, roff0, rstep);
 #pragma unroll
       for (int g = 0; g < 16; ++g) {                               // rows g * 8 .. + 7 of the wave's 128
         const int i = g >> 2, q4 = g & 3;
-        if (HAS_RES && g + 1 < 16) mx_load_res<2>(res[(g + 1) & 1], rr, roff0 + (g + 1) * 2 * rstep, rstep);
+        if (HAS_RES && g + 1 < 16) sf_epi_load_res<2, SF_MX_LOAD_AUX>(res[(g + 1) & 1], rr, roff0 + (g + 1) * 2 * rstep, rstep);
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -820,9 +695,9 @@ __global__ __launch_bounds__(512, 2) void gemm_mxfp8_pp_kernel(MxArgs p) {
           const int colblock = gcol >> 5;
           const int64_t left = p.M - (row0 + g * 8);
           const uint32_t sc_off = (uint32_t)((int64_t)(colblock >> 2) * p.ldsc + (colblock & 3) + (row0 + g * 8) * 4);
-          mx_epi_store<OUT, GELU, HAS_RES, 2>(v, bias4, res[g & 1], rc, coff0 + g * 2 * cstep, cstep, rsc, sc_off, (el & 7) == 0 ? (int)(left > 64 ? 64 : left) : 0);
+          sf_epi_store<OUT, GELU, HAS_RES, 2, SF_MX_STORE_AUX>(v, bias4, res[g & 1], rc, coff0 + g * 2 * cstep, cstep, rsc, sc_off, (el & 7) == 0 ? (int)(left > 64 ? 64 : left) : 0);
         } else {
-          mx_epi_store<OUT, GELU, HAS_RES, 2>(v, bias4, res[g & 1], rc, coff0 + g * 2 * cstep, cstep);
+          sf_epi_store<OUT, GELU, HAS_RES, 2, SF_MX_STORE_AUX>(v, bias4, res[g & 1], rc, coff0 + g * 2 * cstep, cstep);
         }
       }
     }

@@ -26,7 +26,6 @@
 // (-3 %: any instruction between the MFMAs costs the matrix pipe more than the read segment gains); reads balanced 8 / 4 / 8 / 4 (with the first:
 // -5 %); two 16-MFMA phases per k-tile, i.e. half the barriers (+1 %, within noise).  The matrix segment has to stay pure MFMA.
 #include "sf_gemm_common.h"
-#include <type_traits>
 
 #define Q_HALF (128 * 128)             // 16 KiB half-tile: 128 rows x 64 k (bf16)
 #define Q_STAGE (4 * Q_HALF)           // A0 | A1 | B0 | B1
@@ -49,19 +48,7 @@
 #define SF_PP_STORECNT 1               // first k-tile after an epilogue: allow the epilogue's stores to stay in flight (vmcnt 8 + stores)
 #endif
 
-// two LDS-DMA pieces (1 KiB each, consecutive in LDS from the wave-uniform byte address l0): SGPR base + 32-bit lane offsets
-__device__ __forceinline__ void pp_dma2(uint32_t v0, uint32_t v1, const void* sbase, uint32_t l0) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %4\n\ts_nop 3\n\tglobal_load_lds_dwordx4 %1, %3\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(v0), "v"(v1), "s"(sbase), "s"(l0)
-      : "memory", "scc");
-}
-// the same with a cache-policy suffix on the two loads (measurement builds: -DSF_PP_A_POLN=1 streams the A panels through L2 without displacing the
+// sf_dma2 with a cache-policy suffix on the two loads of an A half-tile (measurement builds: -DSF_PP_A_POLN=1 streams the A panels through L2 without displacing the
 // chunk's weight slice; " sc1" / " sc0 sc1" = the other policies of the instruction)
 #ifndef SF_PP_A_POLN
 #define SF_PP_A_POLN 0                 // 0 default policy | 1 nt | 2 sc1 | 3 sc0 sc1
@@ -75,40 +62,7 @@ __device__ __forceinline__ void pp_dma2(uint32_t v0, uint32_t v1, const void* sb
 #else
 #define SF_PP_A_POL ""
 #endif
-__device__ __forceinline__ void pp_dma2_a(uint32_t v0, uint32_t v1, const void* sbase, uint32_t l0) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %4\n\ts_nop 3\n\tglobal_load_lds_dwordx4 %1, %3" SF_PP_A_POL "\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3" SF_PP_A_POL "\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(v0), "v"(v1), "s"(sbase), "s"(l0)
-      : "memory", "scc");
-}
-// one 256-byte piece: 64 lanes x 4 bytes (the wave's 64 bias values) to the wave-uniform LDS byte address l0
-__device__ __forceinline__ void pp_dma_row256(const void* gsrc, uint32_t l0) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(l0)
-      : "memory");
-}
-template <int N>
-__device__ __forceinline__ void pp_wait_vmcnt() {
-  __builtin_amdgcn_s_waitcnt((N & 0xF) | (0x7 << 4) | (0xF << 8) | ((N >> 4) << 14));
-}
-__device__ __forceinline__ void pp_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-#define PP_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
-
-template <int V> using ic = std::integral_constant<int, V>;
+SF_DEF_DMA2(pp_dma2_a, "3", SF_PP_A_POL)
 
 #if SF_PP_ABL & 32
 // tracing build (SF_PP_ABL & 32): per wave, s_memtime cycles spent in [read segment | wait at the first barrier | matrix segment | wait at the second
@@ -190,8 +144,8 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pp_kernel(GemmArgs p) {
       }
     }
   };
-  const uint32_t lds_wave = __builtin_amdgcn_readfirstlane(lds_addr(smem) + wave * 2048);
-  const uint32_t slab_dummy = __builtin_amdgcn_readfirstlane(lds_addr(smem) + 2 * Q_STAGE + wave * Q_SLAB_BYTES + 1024);   // 2 KiB behind the slab's bias row
+  const uint32_t lds_wave = __builtin_amdgcn_readfirstlane(sf_lds_addr(smem) + wave * 2048);
+  const uint32_t slab_dummy = __builtin_amdgcn_readfirstlane(sf_lds_addr(smem) + 2 * Q_STAGE + wave * Q_SLAB_BYTES + 1024);   // 2 KiB behind the slab's bias row
   const char* curA = nullptr; const char* curW = nullptr;
   const int64_t wk2 = p.wk * 2;
   // PART: 0 = A0, 1 = B0, 2 = B1, 3 = A1 (the order in which a k-tile's halves are read); returns whether a load was issued
@@ -207,7 +161,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pp_kernel(GemmArgs p) {
       const uint32_t l = ld_ok ? real : slab_dummy;
       if ((SF_PP_ABL & 2) && !decltype(SUREc)::value) {}
       else if (isA) pp_dma2_a(oA[h][0], oA[h][1], curA, l);
-      else pp_dma2(oW[h][0], oW[h][1], curW, l);
+      else sf_dma2(oW[h][0], oW[h][1], curW, l);
       if (PART == 3 && ld_ok) {
         if (++ld_kt == nk) {
           ld_kt = 0;
@@ -224,8 +178,8 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pp_kernel(GemmArgs p) {
     if (did) {
       const uint32_t l = lds_wave + ST * Q_STAGE + (isA ? h : 2 + h) * Q_HALF;
       if ((SF_PP_ABL & 2) && !decltype(SUREc)::value) {}
-      else if (isA) pp_dma2(oA[h][0], oA[h][1], ldA + (int64_t)ld_kt * 128, l);
-      else pp_dma2(oW[h][0], oW[h][1], ldW + (int64_t)ld_kt * p.wk * 2, l);
+      else if (isA) sf_dma2(oA[h][0], oA[h][1], ldA + (int64_t)ld_kt * 128, l);
+      else sf_dma2(oW[h][0], oW[h][1], ldW + (int64_t)ld_kt * p.wk * 2, l);
       if (PART == 3) {                                           // k-tile complete: advance (to the next tile after the last k-tile)
         if (++ld_kt == nk) {
           ld_kt = 0;
@@ -243,7 +197,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pp_kernel(GemmArgs p) {
   int64_t m0; int n0;
   tile_origin(t, m0, n0);
   char* bslab = smem + 2 * Q_STAGE + wave * Q_SLAB_BYTES;
-  const uint32_t slab_lds = __builtin_amdgcn_readfirstlane(lds_addr(bslab));
+  const uint32_t slab_lds = __builtin_amdgcn_readfirstlane(sf_lds_addr(bslab));
   const uint32_t esz = OUT_BF16 ? 2u : 4u;
   const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(p.C, (short)0, (int)(uint32_t)(p.M * p.ldc * esz), 0x00020000);
   const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.R), (short)0, HAS_RES ? (int)(uint32_t)(p.M * p.ldr * 4) : 0, 0x00020000);
@@ -253,18 +207,18 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pp_kernel(GemmArgs p) {
   // WIDE: the wave's 64 bias values travel by one LDS-DMA piece into the (idle) epilogue slab at the top of the tile - no
   // compiler-visible load in the kernel, so hipcc never inserts a vmcnt(0) that would drain the operand stream
   auto issue_bias = [&](int n0_) {
-    if (WIDE && has_bias) pp_dma_row256(p.bias + min(n0_ + wn * 64 + lane, p.N - 1), slab_lds);
+    if (WIDE && has_bias) sf_dma_dword_addr(p.bias + min(n0_ + wn * 64 + lane, p.N - 1), slab_lds);
   };
 
   // ---- prologue: k-tile 0 and A0 | B0 of k-tile 1 in flight -------------------------------------------------------------------
   ld_set(ld_t);
   curA = ldA; curW = ldW;
   issue_bias(n0);
-  issue(ic<0>{}, ic<0>{}, ic<1>{}); issue(ic<1>{}, ic<0>{}, ic<1>{}); issue(ic<2>{}, ic<0>{}, ic<1>{}); issue(ic<3>{}, ic<0>{}, ic<1>{});
-  issue(ic<0>{}, ic<1>{}, ic<1>{}); issue(ic<1>{}, ic<1>{}, ic<1>{});
+  issue(sf_ic<0>{}, sf_ic<0>{}, sf_ic<1>{}); issue(sf_ic<1>{}, sf_ic<0>{}, sf_ic<1>{}); issue(sf_ic<2>{}, sf_ic<0>{}, sf_ic<1>{}); issue(sf_ic<3>{}, sf_ic<0>{}, sf_ic<1>{});
+  issue(sf_ic<0>{}, sf_ic<1>{}, sf_ic<1>{}); issue(sf_ic<1>{}, sf_ic<1>{}, sf_ic<1>{});
   asm volatile("" ::: "memory");
-  pp_wait_vmcnt<8>();                                            // A0 | B0 of k-tile 0 have landed (this wave's pieces)   // A0 | B0 (schedule 3: and B1) of k-tile 0 have landed (this wave's pieces)
-  pp_barrier();
+  sf_wait_vmcnt_nofence<8>();                                            // A0 | B0 of k-tile 0 have landed (this wave's pieces)   // A0 | B0 (schedule 3: and B1) of k-tile 0 have landed (this wave's pieces)
+  sf_barrier();
   int extra = 0;                                                 // epilogue stores that may still be in flight behind the loads (first k-tile of a tile)
 
   for (;;) {
@@ -279,9 +233,9 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pp_kernel(GemmArgs p) {
 
     auto wait_loads = [&](bool issued, bool first) {
       asm volatile("" ::: "memory");
-      if (!SF_PP_SLIM && !issued) pp_wait_vmcnt<0>();
-      else if (SF_PP_STORECNT && first && extra) pp_wait_vmcnt<8 + EPI_STORES>();
-      else pp_wait_vmcnt<8>();
+      if (!SF_PP_SLIM && !issued) sf_wait_vmcnt_nofence<0>();
+      else if (SF_PP_STORECNT && first && extra) sf_wait_vmcnt_nofence<8 + EPI_STORES>();
+      else sf_wait_vmcnt_nofence<8>();
     };
     auto mma = [&](auto HAc, auto HBc, const bf16x8 (&bf)[4]) {
       constexpr int HA = decltype(HAc)::value, HB = decltype(HBc)::value;
@@ -302,11 +256,11 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pp_kernel(GemmArgs p) {
 #if SF_PP_ABL & 32
     unsigned long long tr_t0, tr_t1, tr_t2, tr_t3, tr_acc[5] = {0, 0, 0, 0, 0};
     PP_T(tr_t0);
-    auto bar_a = [&]() { PP_T(tr_t1); pp_barrier(); PP_T(tr_t2); tr_acc[0] += tr_t1 - tr_t0; tr_acc[1] += tr_t2 - tr_t1; };
-    auto bar_b = [&]() { PP_T(tr_t3); pp_barrier(); PP_T(tr_t0); tr_acc[2] += tr_t3 - tr_t2; tr_acc[3] += tr_t0 - tr_t3; };
+    auto bar_a = [&]() { PP_T(tr_t1); sf_barrier(); PP_T(tr_t2); tr_acc[0] += tr_t1 - tr_t0; tr_acc[1] += tr_t2 - tr_t1; };
+    auto bar_b = [&]() { PP_T(tr_t3); sf_barrier(); PP_T(tr_t0); tr_acc[2] += tr_t3 - tr_t2; tr_acc[3] += tr_t0 - tr_t3; };
 #else
-    auto bar_a = [&]() { pp_barrier(); };
-    auto bar_b = [&]() { pp_barrier(); };
+    auto bar_a = [&]() { sf_barrier(); };
+    auto bar_b = [&]() { sf_barrier(); };
 #endif
     auto ktile = [&](auto Sc, auto SURE, bool first) {
       constexpr int S = decltype(Sc)::value;
@@ -320,20 +274,20 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pp_kernel(GemmArgs p) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) if (rd) a[i][kk] = *reinterpret_cast<const bf16x8*>(st + i * 4096 + a_off[kk]);
       __builtin_amdgcn_sched_barrier(0);
-      wait_loads(issue(ic<2>{}, ic<S ^ 1>{}, SURE), first);            // B1(kt+1) issued; B1(kt) landed
+      wait_loads(issue(sf_ic<2>{}, sf_ic<S ^ 1>{}, SURE), first);            // B1(kt+1) issued; B1(kt) landed
       bar_a();
       __builtin_amdgcn_sched_barrier(0);
-      mma(ic<0>{}, ic<0>{}, b0);
+      mma(sf_ic<0>{}, sf_ic<0>{}, b0);
       __builtin_amdgcn_sched_barrier(0);
       bar_b();
       // ---- phase 1: (A0, B1) ----
 #pragma unroll
       for (int kk = 0; kk < 4; ++kk) { if (SF_PP_ABL & 64) b1[kk] = b0[kk]; else if (rd) b1[kk] = *reinterpret_cast<const bf16x8*>(st + Q_HALF + b_off[kk]); }   // (ABL 64: no B1 fragment reads - a sixth of the LDS read bytes)
       __builtin_amdgcn_sched_barrier(0);
-      wait_loads(issue(ic<3>{}, ic<S ^ 1>{}, SURE), first);            // A1(kt+1) issued; A1(kt) landed
+      wait_loads(issue(sf_ic<3>{}, sf_ic<S ^ 1>{}, SURE), first);            // A1(kt+1) issued; A1(kt) landed
       bar_a();
       __builtin_amdgcn_sched_barrier(0);
-      mma(ic<0>{}, ic<1>{}, b1);
+      mma(sf_ic<0>{}, sf_ic<1>{}, b1);
       __builtin_amdgcn_sched_barrier(0);
       bar_b();
       // ---- phase 2: (A1, B1) ----
@@ -342,31 +296,31 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pp_kernel(GemmArgs p) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) if (rd && !(SF_PP_ABL & 128)) a[i][kk] = *reinterpret_cast<const bf16x8*>(st + Q_HALF + i * 4096 + a_off[kk]);   // (ABL 128: no A1 reads - a third)
       __builtin_amdgcn_sched_barrier(0);
-      issue(ic<0>{}, ic<S>{}, SURE);                             // A0(kt+2); phase 3 reads nothing: no wait
+      issue(sf_ic<0>{}, sf_ic<S>{}, SURE);                             // A0(kt+2); phase 3 reads nothing: no wait
       bar_a();
       __builtin_amdgcn_sched_barrier(0);
-      mma(ic<1>{}, ic<1>{}, b1);
+      mma(sf_ic<1>{}, sf_ic<1>{}, b1);
       __builtin_amdgcn_sched_barrier(0);
       bar_b();
       // ---- phase 3: (A1, B0) ----
-      wait_loads(issue(ic<1>{}, ic<S>{}, SURE), first);                // B0(kt+2); A0 | B0 of k-tile kt+1 landed
+      wait_loads(issue(sf_ic<1>{}, sf_ic<S>{}, SURE), first);                // B0(kt+2); A0 | B0 of k-tile kt+1 landed
       bar_a();
       __builtin_amdgcn_sched_barrier(0);
-      mma(ic<1>{}, ic<0>{}, b0);
+      mma(sf_ic<1>{}, sf_ic<0>{}, b0);
       __builtin_amdgcn_sched_barrier(0);
       bar_b();
     };
 
-    if (wm == 1 && !(SF_PP_ABL & 8)) pp_barrier();                                   // the wm = 1 waves run one barrier behind
+    if (wm == 1 && !(SF_PP_ABL & 8)) sf_barrier();                                   // the wm = 1 waves run one barrier behind
     int kt_first = 0;
     if (SF_PP_NOPEEL) asm volatile("" : "+s"(kt_first));           // opaque zero: with a literal `kt == 0` hipcc peels the first iteration (a second copy of the body)
     for (int kt = 0; kt < nk; kt += 2) {       // (two copies of the k-tile body - a branch-free one for the steady state - cost 250+ spilled registers)
-      ktile(ic<0>{}, ic<0>{}, kt == kt_first);
-      ktile(ic<1>{}, ic<0>{}, false);
+      ktile(sf_ic<0>{}, sf_ic<0>{}, kt == kt_first);
+      ktile(sf_ic<1>{}, sf_ic<0>{}, false);
     }
-    if (wm == 0 && !(SF_PP_ABL & 8)) pp_barrier();                                   // re-align: both groups run the epilogue concurrently
+    if (wm == 0 && !(SF_PP_ABL & 8)) sf_barrier();                                   // re-align: both groups run the epilogue concurrently
 
-    if (SF_PP_SLIM && !ld_ok) pp_wait_vmcnt<0>();                  // dummy pieces of a dry iterator land in the slab: all of them before the epilogue uses it
+    if (SF_PP_SLIM && !ld_ok) sf_wait_vmcnt_nofence<0>();                  // dummy pieces of a dry iterator land in the slab: all of them before the epilogue uses it
     const int64_t em0 = m0; const int en0 = n0;
     extra = 0;
 #if SF_PP_ABL & 32
@@ -392,14 +346,14 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pp_kernel(GemmArgs p) {
         const int colbase = en0 + wn * 64;
         if (!has_bias) {
           if (el < 16) *reinterpret_cast<float4*>(bslab + el * 16) = make_float4(0.f, 0.f, 0.f, 0.f);
-          PP_WAVE_SYNC();
+          SF_WAVE_SYNC();
         }
         float4 bia[2][4];
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
           for (int g = 0; g < 4; ++g) bia[j][g] = *reinterpret_cast<const float4*>(bslab + (j * 32 + g * 8 + ehi * 4) * 4);
-        PP_WAVE_SYNC();
+        SF_WAVE_SYNC();
         const int wr_off = el31 * 128 + ((ehi ^ ((el31 >> 3) & 1)) << 3), sw7 = el31 & 7;
         const int tr0 = el >> 3, ch = el & 7;
         const int rd_off = tr0 * 128 + ((ch ^ (tr0 & 7)) << 4);
@@ -416,7 +370,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pp_kernel(GemmArgs p) {
                 w.y = pack_bf2(acc[i][j][g * 4 + 2] + bia[j][g].z, acc[i][j][g * 4 + 3] + bia[j][g].w);
                 *reinterpret_cast<u32x2*>(bslab + wr_off + (((j * 4 + g) ^ sw7) << 4)) = w;
               }
-            PP_WAVE_SYNC();
+            SF_WAVE_SYNC();
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
               const u32x4 v = *reinterpret_cast<const u32x4*>(bslab + rd_off + q * 8 * 128);
@@ -424,7 +378,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pp_kernel(GemmArgs p) {
               if (q & 1) { o.x = v.z; o.y = v.w; o.z = v.x; o.w = v.y; } else { o = v; }
               __builtin_amdgcn_raw_buffer_store_b128(o, rc2, cbase + (uint32_t)((i * 32 + q * 8) * p.ldc) * 2u, 0, SF_EPI_STORE_AUX);
             }
-            PP_WAVE_SYNC();
+            SF_WAVE_SYNC();
           }
 #pragma unroll
           for (int j = 0; j < 2; ++j)
@@ -440,7 +394,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pp_kernel(GemmArgs p) {
               u32x2 w; w.x = pack_bf2(x.x, x.y); w.y = pack_bf2(x.z, x.w);
               *reinterpret_cast<u32x2*>(bslab + wr_off + (((j * 4 + g) ^ sw7) << 4)) = w;
             }
-          PP_WAVE_SYNC();
+          SF_WAVE_SYNC();
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const u32x4 v = *reinterpret_cast<const u32x4*>(bslab + rd_off + q * 8 * 128);
@@ -448,7 +402,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pp_kernel(GemmArgs p) {
             if (q & 1) { o.x = v.z; o.y = v.w; o.z = v.x; o.w = v.y; } else { o = v; }
             __builtin_amdgcn_raw_buffer_store_b128(o, rc, cbase + (uint32_t)((i * 32 + q * 8) * p.ldc) * 2u, 0, SF_EPI_STORE_AUX);
           }
-          PP_WAVE_SYNC();
+          SF_WAVE_SYNC();
         }
       }
     } else if (en0 + wn * 64 < p.N) {
@@ -464,11 +418,11 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pp_kernel(GemmArgs p) {
       float4 res[2][4];
 #pragma unroll
       for (int ps = 0; ps < 4; ++ps) res[0][ps] = res[1][ps] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (HAS_RES) epi_group_load_res(res[0], rr, roff0, rstep);
+      if (HAS_RES) sf_epi_load_res<4, SF_EPI_LOAD_AUX>(res[0], rr, roff0, rstep);
 #pragma unroll
       for (int g = 0; g < 8; ++g) {
         const int i = g >> 1, q2 = g & 1;
-        if (HAS_RES && g + 1 < 8) epi_group_load_res(res[(g + 1) & 1], rr, roff0 + (g + 1) * 4 * rstep, rstep);
+        if (HAS_RES && g + 1 < 8) sf_epi_load_res<4, SF_EPI_LOAD_AUX>(res[(g + 1) & 1], rr, roff0 + (g + 1) * 4 * rstep, rstep);
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -479,7 +433,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pp_kernel(GemmArgs p) {
         float4 v[4];
 #pragma unroll
         for (int ps = 0; ps < 4; ++ps) v[ps] = *reinterpret_cast<const float4*>(slab + (ps * 4 + (lane >> 4)) * 64 + ecol);
-        epi_group_store<OUT_BF16, GELU, HAS_RES>(v, bias4, res[g & 1], rc, coff0 + g * 4 * cstep, cstep);
+        sf_epi_store<OUT_BF16, GELU, HAS_RES, 4, SF_EPI_STORE_AUX>(v, bias4, res[g & 1], rc, coff0 + g * 4 * cstep, cstep);
       }
     }
 #if SF_PP_ABL & 32

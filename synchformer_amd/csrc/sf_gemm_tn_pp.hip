@@ -23,7 +23,6 @@
 //     the sum is 4 v_dot2_f32_bf16 against ones per fragment, issued behind the phase's MFMAs - by all four wave columns wn (sharing the k-steps between them
 //     needs a run-time selection of the fragment, i.e. branches in the matrix segment: measured +10 %); wn = 0 writes bias_part (split, N).
 #include "sf_gemm_common.h"
-#include <type_traits>
 
 #define TQ_HALF (64 * 256)             // 16 KiB half-tile: 64 token rows x 128 columns (bf16)
 #define TQ_STAGE (4 * TQ_HALF)         // A0 | A1 | B0 | B1
@@ -61,23 +60,6 @@ __device__ __forceinline__ void tq_dma2(uint32_t v0, uint32_t v1, __amdgpu_buffe
       : "=&s"(keep)
       : "v"(v0), "v"(v1), "s"(r), "s"(l0)
       : "memory", "scc");
-}
-template <int N>
-__device__ __forceinline__ void tq_wait_vmcnt() {
-  __builtin_amdgcn_s_waitcnt((N & 0xF) | (0x7 << 4) | (0xF << 8) | ((N >> 4) << 14));
-}
-__device__ __forceinline__ void tq_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-template <int V> using tq_ic = std::integral_constant<int, V>;
-// The lane index, re-derived where it is needed (mbcnt over an opaque zero: neither hoisted nor kept): at 256 registers a thread id kept live across the
-// k-loop is spilled, and its reload sits behind a compiler vmcnt(0) - i.e. behind the whole operand stream in flight.
-__device__ __forceinline__ int tq_lane() {
-  int z = 0;
-  asm volatile("" : "+v"(z));
-  return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, z));
 }
 
 __global__ __launch_bounds__(512, 2) void gemm_tn_pp_kernel(TnPpArgs p) {
@@ -125,7 +107,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_pp_kernel(TnPpArgs p) {
   auto ld_set = [&](uint32_t t) {
     uint32_t s; int i0, j0;
     item_origin(t, s, i0, j0);
-    const int ll = tq_lane();                                    // lane quantities are re-derived per item, not kept across the k-loop
+    const int ll = sf_lane();                                    // lane quantities are re-derived per item, not kept across the k-loop
     const int kr = ll >> 4, slot = ll & 15;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -139,8 +121,8 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_pp_kernel(TnPpArgs p) {
       }
     }
   };
-  const uint32_t lds_wave = __builtin_amdgcn_readfirstlane(lds_addr(smem) + wave * 2048);
-  const uint32_t slab_dummy = __builtin_amdgcn_readfirstlane(lds_addr(smem) + 2 * TQ_STAGE + wave * TQ_SLAB_BYTES + 1024);
+  const uint32_t lds_wave = __builtin_amdgcn_readfirstlane(sf_lds_addr(smem) + wave * 2048);
+  const uint32_t slab_dummy = __builtin_amdgcn_readfirstlane(sf_lds_addr(smem) + 2 * TQ_STAGE + wave * TQ_SLAB_BYTES + 1024);
   // PART: 0 = A0, 1 = B0, 2 = B1, 3 = A1 (the order in which a k-tile's halves are read).  Branch-free: a dry iterator keeps issuing (dummy pieces into this
   // wave's idle epilogue slab), so every counted wait keeps its count
   auto issue = [&](auto PARTc, auto STc) {
@@ -176,11 +158,11 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_pp_kernel(TnPpArgs p) {
 
   // ---- prologue: k-tile 0 and A0 | B0 of k-tile 1 in flight -------------------------------------------------------------------
   ld_set(ld_t);
-  issue(tq_ic<0>{}, tq_ic<0>{}); issue(tq_ic<1>{}, tq_ic<0>{}); issue(tq_ic<2>{}, tq_ic<0>{}); issue(tq_ic<3>{}, tq_ic<0>{});
-  issue(tq_ic<0>{}, tq_ic<1>{}); issue(tq_ic<1>{}, tq_ic<1>{});
+  issue(sf_ic<0>{}, sf_ic<0>{}); issue(sf_ic<1>{}, sf_ic<0>{}); issue(sf_ic<2>{}, sf_ic<0>{}); issue(sf_ic<3>{}, sf_ic<0>{});
+  issue(sf_ic<0>{}, sf_ic<1>{}); issue(sf_ic<1>{}, sf_ic<1>{});
   asm volatile("" ::: "memory");
-  tq_wait_vmcnt<8>();                                            // A0 | B0 of k-tile 0 have landed (this wave's pieces)
-  tq_barrier();
+  sf_wait_vmcnt_nofence<8>();                                            // A0 | B0 of k-tile 0 have landed (this wave's pieces)
+  sf_barrier();
   int extra = 0;                                                 // epilogue stores that may still be in flight behind the loads (first k-tile of an item)
   typedef __attribute__((ext_vector_type(2))) __bf16 tq_bf2;
   const tq_bf2 ones2 = __builtin_bit_cast(tq_bf2, 0x3F803F80u);
@@ -213,8 +195,8 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_pp_kernel(TnPpArgs p) {
 
     auto wait_loads = [&](bool first) {
       asm volatile("" ::: "memory");
-      if (SF_TQ_STORECNT && first && extra) { if (extra > TQ_EPI_STORES) tq_wait_vmcnt<8 + TQ_EPI_STORES + 4>(); else tq_wait_vmcnt<8 + TQ_EPI_STORES>(); }
-      else tq_wait_vmcnt<8>();
+      if (SF_TQ_STORECNT && first && extra) { if (extra > TQ_EPI_STORES) sf_wait_vmcnt_nofence<8 + TQ_EPI_STORES + 4>(); else sf_wait_vmcnt_nofence<8 + TQ_EPI_STORES>(); }
+      else sf_wait_vmcnt_nofence<8>();
     };
     auto frag = [&](const char* base, int off) -> bf16x8 {
       union { bf16x8 v; tq_s4 h[2]; } u;
@@ -245,61 +227,61 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_pp_kernel(TnPpArgs p) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) a[i][kk] = frag(st, a_off[i][kk]);
       __builtin_amdgcn_sched_barrier(0);
-      issue(tq_ic<2>{}, tq_ic<S ^ 1>{});                          // B1(kt+1) issued; B1(kt) landed
+      issue(sf_ic<2>{}, sf_ic<S ^ 1>{});                          // B1(kt+1) issued; B1(kt) landed
       wait_loads(first);
-      tq_barrier();
+      sf_barrier();
       __builtin_amdgcn_sched_barrier(0);
-      mma(tq_ic<0>{}, tq_ic<0>{}, b0);
+      mma(sf_ic<0>{}, sf_ic<0>{}, b0);
       __builtin_amdgcn_sched_barrier(0);
-      bias_acc(tq_ic<0>{});                                       // behind the phase's MFMAs (the fragments are in registers by now; in the read segment the
+      bias_acc(sf_ic<0>{});                                       // behind the phase's MFMAs (the fragments are in registers by now; in the read segment the
       __builtin_amdgcn_sched_barrier(0);                          // sums would wait for the LDS reads in front of the DMA issue and the barrier)
-      tq_barrier();
+      sf_barrier();
       // ---- phase 1: (A0, B1) ----
 #pragma unroll
       for (int kk = 0; kk < 4; ++kk) b1[kk] = frag(st + TQ_HALF, b_off[kk]);
       __builtin_amdgcn_sched_barrier(0);
-      issue(tq_ic<3>{}, tq_ic<S ^ 1>{});                          // A1(kt+1) issued; A1(kt) landed
+      issue(sf_ic<3>{}, sf_ic<S ^ 1>{});                          // A1(kt+1) issued; A1(kt) landed
       wait_loads(first);
-      tq_barrier();
+      sf_barrier();
       __builtin_amdgcn_sched_barrier(0);
-      mma(tq_ic<0>{}, tq_ic<1>{}, b1);
+      mma(sf_ic<0>{}, sf_ic<1>{}, b1);
       __builtin_amdgcn_sched_barrier(0);
-      tq_barrier();
+      sf_barrier();
       // ---- phase 2: (A1, B1) ----
 #pragma unroll
       for (int kk = 0; kk < 4; ++kk)
 #pragma unroll
         for (int i = 0; i < 2; ++i) a[i][kk] = frag(st + TQ_HALF, a_off[i][kk]);
       __builtin_amdgcn_sched_barrier(0);
-      issue(tq_ic<0>{}, tq_ic<S>{});                              // A0(kt+2); phase 3 reads nothing: no wait
-      tq_barrier();
+      issue(sf_ic<0>{}, sf_ic<S>{});                              // A0(kt+2); phase 3 reads nothing: no wait
+      sf_barrier();
       __builtin_amdgcn_sched_barrier(0);
-      mma(tq_ic<1>{}, tq_ic<1>{}, b1);
+      mma(sf_ic<1>{}, sf_ic<1>{}, b1);
       __builtin_amdgcn_sched_barrier(0);
-      bias_acc(tq_ic<1>{});
+      bias_acc(sf_ic<1>{});
       __builtin_amdgcn_sched_barrier(0);
-      tq_barrier();
+      sf_barrier();
       // ---- phase 3: (A1, B0) ----
-      issue(tq_ic<1>{}, tq_ic<S>{});                              // B0(kt+2); A0 | B0 of k-tile kt+1 landed
+      issue(sf_ic<1>{}, sf_ic<S>{});                              // B0(kt+2); A0 | B0 of k-tile kt+1 landed
       wait_loads(first);
-      tq_barrier();
+      sf_barrier();
       __builtin_amdgcn_sched_barrier(0);
-      mma(tq_ic<1>{}, tq_ic<0>{}, b0);
+      mma(sf_ic<1>{}, sf_ic<0>{}, b0);
       __builtin_amdgcn_sched_barrier(0);
-      tq_barrier();
+      sf_barrier();
     };
 
-    if (wm == 1) tq_barrier();                                   // the wm = 1 waves run one barrier behind
+    if (wm == 1) sf_barrier();                                   // the wm = 1 waves run one barrier behind
     for (int kt = 0; kt < nk; kt += 2) {
-      ktile(tq_ic<0>{}, kt == 0);
-      ktile(tq_ic<1>{}, false);
+      ktile(sf_ic<0>{}, kt == 0);
+      ktile(sf_ic<1>{}, false);
     }
-    if (wm == 0) tq_barrier();                                   // re-align: both groups run the epilogue concurrently
+    if (wm == 0) sf_barrier();                                   // re-align: both groups run the epilogue concurrently
 
-    if (!ld_ok) tq_wait_vmcnt<0>();                              // dummy pieces of a dry iterator land in the slab: all of them before the epilogue uses it
+    if (!ld_ok) sf_wait_vmcnt_nofence<0>();                              // dummy pieces of a dry iterator land in the slab: all of them before the epilogue uses it
     // ---- epilogue: 8 branch-free groups of 16 rows x 64 cols through the wave's slab, fp32 row stores into this chunk's plane ----
     {
-      const int el = tq_lane(), el31 = el & 31, ehi = el >> 5;    // (re-derived: see tq_lane)
+      const int el = sf_lane(), el31 = el & 31, ehi = el >> 5;    // (re-derived: see sf_lane)
       extra = TQ_EPI_STORES;
       if (do_bias) {                                             // 4 more stores per wave in front of the tile's 32
         extra = TQ_EPI_STORES + 4;
@@ -332,7 +314,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_pp_kernel(TnPpArgs p) {
         float4 v[4];
 #pragma unroll
         for (int ps = 0; ps < 4; ++ps) v[ps] = *reinterpret_cast<const float4*>(slab + (ps * 4 + (el >> 4)) * 64 + ecol);
-        epi_group_store<false, false, false>(v, zero4, nores, rc, coff0 + g * 4 * cstep, cstep);
+        sf_epi_store<false, false, false, 4, SF_EPI_STORE_AUX>(v, zero4, nores, rc, coff0 + g * 4 * cstep, cstep);
       }
     }
     t += per_xcd_blocks;

@@ -25,7 +25,6 @@
 // instructions per tile against ~5 issue slots per MFMA gap x 768 MFMAs, and packed-fp32 VALU beside MFMAs is an anti-lever (MI355X_MICROARCH.md).
 #ifdef SF_ABLATION   // config 12: a measured-slower alternative, compiled into the ablation build only
 #include "sf_gemm_common.h"
-#include <type_traits>
 
 #define R4_PART (128 * 128)            // 16 KiB part: 128 rows x 64 k (bf16)
 #define R4_STAGE (4 * R4_PART)         // A0 | A1 | B0 | B1
@@ -60,31 +59,6 @@
 __device__ __forceinline__ void r4_dma1(uint32_t v, __amdgpu_buffer_rsrc_t r, uint32_t so, uint32_t l0) {
   asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" :: "v"(v), "s"(r), "s"(so), "s"(l0) : "memory");
 }
-// 256 bytes: 64 lanes x 4 B from per-lane addresses
-__device__ __forceinline__ void r4_dma_row256(const void* gsrc, uint32_t l0) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(l0)
-      : "memory");
-}
-template <int N>
-__device__ __forceinline__ void r4_wait_vmcnt() {
-  __builtin_amdgcn_s_waitcnt((N & 0xF) | (0x7 << 4) | (0xF << 8) | ((N >> 4) << 14));
-}
-__device__ __forceinline__ void r4_wait_lgkm0() {               // the builtin (not asm): hipcc's own counter tracking sees it
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_waitcnt(0xF | (0x7 << 4) | (0x0 << 8) | (0x3 << 14));
-}
-__device__ __forceinline__ void r4_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-#define R4_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
 
 // The MFMA as an asm statement with the accumulator block PINNED to the accumulation registers ("+a"): with the builtin hipcc spreads the 256 accumulators over both
 // halves of the unified file and spills 200+ registers; volatile also keeps the stream in program order.  Hazards the assembler cannot see: a block is touched by every
@@ -97,7 +71,6 @@ __device__ __forceinline__ void r4_mfma0(f32x16& c, const bf16x8& a, const bf16x
   asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=a"(c) : "v"(a), "v"(b));
 }
 __device__ __forceinline__ void r4_acc_fence() { asm volatile("s_nop 15\n\ts_nop 15" ::: "memory"); }
-template <int V> using r4c = std::integral_constant<int, V>;
 struct R4Kt { uint32_t a, w; };        // scalar byte offsets of a k-tile's A rows / W rows (tile origin + 128 kt)
 
 template <bool GELU>
@@ -122,7 +95,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_r4_kernel(GemmArgs p) {
     m0 = (int64_t)tm * 256; n0 = (int)tn * 256;
   };
 
-  // ---- lane-derived offsets, RE-DERIVED at the top of every tile from an asm mbcnt (nothing lane-derived stays live across the epilogue: hipcc spilled them otherwise,
+  // ---- lane-derived offsets, RE-DERIVED at the top of every tile from sf_lane_asm() (nothing lane-derived stays live across the epilogue: hipcc spilled them otherwise,
   // and a scratch reload drags a vmcnt(0) through the operand stream) ----
   //   fragment reads inside a part: row r is 128 B, 16-byte chunk c at slot c ^ ((r >> 1) & 7);  a_off / b_off: + i * 4096 for the second 32-row block
   //   LDS-DMA: piece j (0..3) of part h of this wave = part rows (4 wave + j) * 8 .. + 7 = tile rows (wave >> 1) * 128 + h * 64 + (4 (wave & 1) + j) * 8 + (lane >> 3);
@@ -131,8 +104,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_r4_kernel(GemmArgs p) {
   int a_off[4], b_off[4];
   uint32_t vA, vW;
   auto derive = [&]() {
-    int ln;
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
+    const int ln = sf_lane_asm();
     const int dl31 = ln & 31, dhi = ln >> 5, sw = (dl31 >> 1) & 7;
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
@@ -149,7 +121,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_r4_kernel(GemmArgs p) {
   const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(p.A), (short)0, (int)(uint32_t)(p.M * p.lda * 2), 0x00020000);
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(p.W), (short)0, (int)(uint32_t)((int64_t)p.N * p.ldw * 2), 0x00020000);
   const uint32_t rowb = (uint32_t)((wave >> 1) * 128 + (wave & 1) * 32);
-  const uint32_t lds0 = __builtin_amdgcn_readfirstlane(lds_addr(smem));
+  const uint32_t lds0 = __builtin_amdgcn_readfirstlane(sf_lds_addr(smem));
   const uint32_t lds_wave = lds0 + (uint32_t)wave * 4096u;
   uint32_t it_t = li, it_k = 0, it_a, it_w;
   {
@@ -183,7 +155,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_r4_kernel(GemmArgs p) {
     else r4_dma1(((J & 1) ? (vW ^ 64u) : vW) + (d.w + row * ldw2), rw, 0u, l);
   };
   auto issue_part = [&](auto PARTc, auto Sc, const R4Kt& d) {
-    issue_piece(PARTc, Sc, r4c<0>{}, d); issue_piece(PARTc, Sc, r4c<1>{}, d); issue_piece(PARTc, Sc, r4c<2>{}, d); issue_piece(PARTc, Sc, r4c<3>{}, d);
+    issue_piece(PARTc, Sc, sf_ic<0>{}, d); issue_piece(PARTc, Sc, sf_ic<1>{}, d); issue_piece(PARTc, Sc, sf_ic<2>{}, d); issue_piece(PARTc, Sc, sf_ic<3>{}, d);
   };
 
   // ---- compute-side state -----------------------------------------------------------------------------------------------------------------------
@@ -191,16 +163,15 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_r4_kernel(GemmArgs p) {
   int64_t m0; int n0;
   tile_origin(t, m0, n0);
   char* wslab = smem + 2 * R4_STAGE + wave * R4_WAVE_AREA;
-  const uint32_t bias_lds = __builtin_amdgcn_readfirstlane(lds_addr(wslab) + R4_SLAB);
+  const uint32_t bias_lds = __builtin_amdgcn_readfirstlane(sf_lds_addr(wslab) + R4_SLAB);
   const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(p.C, (short)0, (int)(uint32_t)(p.M * p.ldc * 2), 0x00020000);
   const bool has_bias = p.bias != nullptr;
   uint32_t tpar = 0;                                             // tile parity: which bias buffer holds this tile's values
   auto issue_bias = [&](int n0_, uint32_t par) {                 // the wave's 128 bias floats of a tile -> LDS (2 pieces of 256 B)
     if (has_bias) {
-      int ln;
-      asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
-      r4_dma_row256(p.bias + min(n0_ + wn * 128 + ln, p.N - 1), bias_lds + par * R4_BIASB);
-      r4_dma_row256(p.bias + min(n0_ + wn * 128 + 64 + ln, p.N - 1), bias_lds + par * R4_BIASB + 256);
+      const int ln = sf_lane_asm();
+      sf_dma_dword_addr(p.bias + min(n0_ + wn * 128 + ln, p.N - 1), bias_lds + par * R4_BIASB);
+      sf_dma_dword_addr(p.bias + min(n0_ + wn * 128 + 64 + ln, p.N - 1), bias_lds + par * R4_BIASB + 256);
     }
   };
 
@@ -213,21 +184,21 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_r4_kernel(GemmArgs p) {
   {
     const R4Kt d0 = it_next(), d1 = it_next();
     issue_bias(n0, 0);
-    issue_part(r4c<0>{}, r4c<0>{}, d0); issue_part(r4c<2>{}, r4c<0>{}, d0); issue_part(r4c<3>{}, r4c<0>{}, d0); issue_part(r4c<1>{}, r4c<0>{}, d0);
-    issue_part(r4c<0>{}, r4c<1>{}, d1); issue_part(r4c<3>{}, r4c<1>{}, d1); issue_part(r4c<2>{}, r4c<1>{}, d1); issue_part(r4c<1>{}, r4c<1>{}, d1);
+    issue_part(sf_ic<0>{}, sf_ic<0>{}, d0); issue_part(sf_ic<2>{}, sf_ic<0>{}, d0); issue_part(sf_ic<3>{}, sf_ic<0>{}, d0); issue_part(sf_ic<1>{}, sf_ic<0>{}, d0);
+    issue_part(sf_ic<0>{}, sf_ic<1>{}, d1); issue_part(sf_ic<3>{}, sf_ic<1>{}, d1); issue_part(sf_ic<2>{}, sf_ic<1>{}, d1); issue_part(sf_ic<1>{}, sf_ic<1>{}, d1);
     asm volatile("" ::: "memory");
-    if (R4_ABL & 2) r4_wait_vmcnt<0>(); else r4_wait_vmcnt<28>();   // P_0 = A0(0) (and the bias) landed
-    r4_barrier();
+    if (R4_ABL & 2) sf_wait_vmcnt_nofence<0>(); else sf_wait_vmcnt_nofence<28>();   // P_0 = A0(0) (and the bias) landed
+    sf_barrier();
 #pragma unroll
     for (int r = 0; r < 8; ++r) fA[0][r >> 2][r & 3] = *reinterpret_cast<const bf16x8*>(smem + (r >> 2) * 4096 + a_off[r & 3]);
-    r4_wait_lgkm0();
-    if (R4_ABL & 2) r4_wait_vmcnt<0>(); else r4_wait_vmcnt<24>();   // P_1 = B0(0)
-    r4_barrier();
+    sf_wait_lgkm0();
+    if (R4_ABL & 2) sf_wait_vmcnt_nofence<0>(); else sf_wait_vmcnt_nofence<24>();   // P_1 = B0(0)
+    sf_barrier();
 #pragma unroll
     for (int r = 0; r < 8; ++r) fB[0][r >> 2][r & 3] = *reinterpret_cast<const bf16x8*>(smem + 2 * R4_PART + (r >> 2) * 4096 + b_off[r & 3]);
-    r4_wait_lgkm0();
-    if (R4_ABL & 2) r4_wait_vmcnt<0>(); else r4_wait_vmcnt<16>();   // P_2 = B1(0), P_3 = A1(0)
-    r4_barrier();
+    sf_wait_lgkm0();
+    if (R4_ABL & 2) sf_wait_vmcnt_nofence<0>(); else sf_wait_vmcnt_nofence<16>();   // P_2 = B1(0), P_3 = A1(0)
+    sf_barrier();
     D0 = it_next(); D1 = it_next();
   }
 
@@ -257,44 +228,44 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_r4_kernel(GemmArgs p) {
           if (decltype(ZEROc)::value && kk == 0) r4_mfma0(acc[HA * 2 + i][HB * 2 + j], fB[HB][j][kk], fA[HA][i][kk]);
           else r4_mfma(acc[HA * 2 + i][HB * 2 + j], fB[HB][j][kk], fA[HA][i][kk]);
         } else if (m == 0) asm volatile("" :: "v"(fA[HA][0][0]), "v"(fA[HA][1][3]), "v"(fB[HB][0][0]), "v"(fB[HB][1][3]));
-        if (R4_RD2) { if (m < 4) { rd(r4c<2 * (m & 3)>{}); rd(r4c<2 * (m & 3) + 1>{}); } }
-        else if (m < 8) rd(r4c<(m & 7)>{});
+        if (R4_RD2) { if (m < 4) { rd(sf_ic<2 * (m & 3)>{}); rd(sf_ic<2 * (m & 3) + 1>{}); } }
+        else if (m < 8) rd(sf_ic<(m & 7)>{});
         if (R4_DMA_ROT) {                                          // wave w issues piece j behind MFMA 4 j + w: the CU's vector-memory queue sees ONE piece per MFMA slot
-          if (wave == (m & 3)) issue_piece(FPc, FSc, r4c<(m >> 2) & 3>{}, d);
+          if (wave == (m & 3)) issue_piece(FPc, FSc, sf_ic<(m >> 2) & 3>{}, d);
         } else {
           constexpr int d0 = R4_DMA_LATE ? 8 : 5;                  // LDS-DMA pieces behind MFMAs d0, d0 + 2, d0 + 4, d0 + 6 (all four waves at once)
-          if (m >= d0 && ((m - d0) & 1) == 0 && (m - d0) / 2 < 4) issue_piece(FPc, FSc, r4c<((m - d0) / 2) & 3>{}, d);
+          if (m >= d0 && ((m - d0) & 1) == 0 && (m - d0) / 2 < 4) issue_piece(FPc, FSc, sf_ic<((m - d0) / 2) & 3>{}, d);
         }
         __builtin_amdgcn_sched_barrier(0);
       };
-      slot(r4c<0>{}); slot(r4c<1>{}); slot(r4c<2>{}); slot(r4c<3>{}); slot(r4c<4>{}); slot(r4c<5>{}); slot(r4c<6>{}); slot(r4c<7>{});
-      slot(r4c<8>{}); slot(r4c<9>{}); slot(r4c<10>{}); slot(r4c<11>{}); slot(r4c<12>{}); slot(r4c<13>{}); slot(r4c<14>{}); slot(r4c<15>{});
+      slot(sf_ic<0>{}); slot(sf_ic<1>{}); slot(sf_ic<2>{}); slot(sf_ic<3>{}); slot(sf_ic<4>{}); slot(sf_ic<5>{}); slot(sf_ic<6>{}); slot(sf_ic<7>{});
+      slot(sf_ic<8>{}); slot(sf_ic<9>{}); slot(sf_ic<10>{}); slot(sf_ic<11>{}); slot(sf_ic<12>{}); slot(sf_ic<13>{}); slot(sf_ic<14>{}); slot(sf_ic<15>{});
       if (R4_BAR2 && !decltype(ODDc)::value) return;               // (barrier after the odd phases only)
       constexpr int YOUNG = R4_BAR2 ? 16 : 20;                     // pieces issued after the part(s) that must have landed: 4 per phase over the last 4 (5) phases
-      r4_wait_lgkm0();                                             // the fragment reads since the last barrier are complete: their parts may be refilled after this one
+      sf_wait_lgkm0();                                             // the fragment reads since the last barrier are complete: their parts may be refilled after this one
       if (R4_ABL & 2) {}
-      else if (relaxed) r4_wait_vmcnt<(YOUNG + R4_EPI_STORES > 63 ? 63 : YOUNG + R4_EPI_STORES)>();   // the epilogue's stores sit between the parts read next and the younger loads
-      else r4_wait_vmcnt<YOUNG>();                                 // the parts read in the next (two) phases have landed (this wave's pieces)
-      if (!(R4_ABL & 16)) r4_barrier();
+      else if (relaxed) sf_wait_vmcnt_nofence<(YOUNG + R4_EPI_STORES > 63 ? 63 : YOUNG + R4_EPI_STORES)>();   // the epilogue's stores sit between the parts read next and the younger loads
+      else sf_wait_vmcnt_nofence<YOUNG>();                                 // the parts read in the next (two) phases have landed (this wave's pieces)
+      if (!(R4_ABL & 16)) sf_barrier();
     };
     // a pair of k-tiles (even in stage 0, odd in stage 1)
     // (a part is refilled TWO phases after the phase that read it - the barrier in between, also with R4_BAR2, proves every wave is done with it - by the same part two
     //  k-tiles ahead: D0 | D1 = the k-tiles 2 and 3 ahead of the pair's even one; phase f issues P_(f+8), the waits leave the 16 (20) youngest pieces in flight)
     auto pair = [&](auto FIRSTc, bool rel) {
       constexpr int F = decltype(FIRSTc)::value;                   // first pair of a tile: every block's first MFMA (k-step 0 of phases E0 .. E3) starts from zero
-      phase(r4c<0>{}, r4c<0>{}, r4c<3>{}, r4c<0>{}, r4c<0>{}, r4c<0>{}, D0, rel, r4c<F>{}, r4c<0>{});      // E0: (A0,B0) | read B1(kt)   | refill A0 s0 <- A0(kt+2)
-      phase(r4c<0>{}, r4c<1>{}, r4c<1>{}, r4c<0>{}, r4c<2>{}, r4c<0>{}, D0, rel, r4c<F>{}, r4c<1>{});      // E1: (A0,B1) | read A1(kt)   | refill B0 s0 <- B0(kt+2)
-      phase(r4c<1>{}, r4c<1>{}, r4c<0>{}, r4c<1>{}, r4c<3>{}, r4c<0>{}, D0, rel, r4c<F>{}, r4c<0>{});      // E2: (A1,B1) | read A0(kt+1) | refill B1 s0 <- B1(kt+2)
-      phase(r4c<1>{}, r4c<0>{}, r4c<3>{}, r4c<1>{}, r4c<1>{}, r4c<0>{}, D0, rel, r4c<F>{}, r4c<1>{});      // E3: (A1,B0) | read B1(kt+1) | refill A1 s0 <- A1(kt+2)
-      phase(r4c<0>{}, r4c<1>{}, r4c<2>{}, r4c<1>{}, r4c<0>{}, r4c<1>{}, D1, false, r4c<0>{}, r4c<0>{});    // O0: (A0,B1) | read B0(kt+1) | refill A0 s1 <- A0(kt+3)
-      phase(r4c<0>{}, r4c<0>{}, r4c<1>{}, r4c<1>{}, r4c<3>{}, r4c<1>{}, D1, false, r4c<0>{}, r4c<1>{});    // O1: (A0,B0) | read A1(kt+1) | refill B1 s1 <- B1(kt+3)
-      phase(r4c<1>{}, r4c<0>{}, r4c<0>{}, r4c<0>{}, r4c<2>{}, r4c<1>{}, D1, false, r4c<0>{}, r4c<0>{});    // O2: (A1,B0) | read A0(kt+2) | refill B0 s1 <- B0(kt+3)
-      phase(r4c<1>{}, r4c<1>{}, r4c<2>{}, r4c<0>{}, r4c<1>{}, r4c<1>{}, D1, false, r4c<0>{}, r4c<1>{});    // O3: (A1,B1) | read B0(kt+2) | refill A1 s1 <- A1(kt+3)
+      phase(sf_ic<0>{}, sf_ic<0>{}, sf_ic<3>{}, sf_ic<0>{}, sf_ic<0>{}, sf_ic<0>{}, D0, rel, sf_ic<F>{}, sf_ic<0>{});      // E0: (A0,B0) | read B1(kt)   | refill A0 s0 <- A0(kt+2)
+      phase(sf_ic<0>{}, sf_ic<1>{}, sf_ic<1>{}, sf_ic<0>{}, sf_ic<2>{}, sf_ic<0>{}, D0, rel, sf_ic<F>{}, sf_ic<1>{});      // E1: (A0,B1) | read A1(kt)   | refill B0 s0 <- B0(kt+2)
+      phase(sf_ic<1>{}, sf_ic<1>{}, sf_ic<0>{}, sf_ic<1>{}, sf_ic<3>{}, sf_ic<0>{}, D0, rel, sf_ic<F>{}, sf_ic<0>{});      // E2: (A1,B1) | read A0(kt+1) | refill B1 s0 <- B1(kt+2)
+      phase(sf_ic<1>{}, sf_ic<0>{}, sf_ic<3>{}, sf_ic<1>{}, sf_ic<1>{}, sf_ic<0>{}, D0, rel, sf_ic<F>{}, sf_ic<1>{});      // E3: (A1,B0) | read B1(kt+1) | refill A1 s0 <- A1(kt+2)
+      phase(sf_ic<0>{}, sf_ic<1>{}, sf_ic<2>{}, sf_ic<1>{}, sf_ic<0>{}, sf_ic<1>{}, D1, false, sf_ic<0>{}, sf_ic<0>{});    // O0: (A0,B1) | read B0(kt+1) | refill A0 s1 <- A0(kt+3)
+      phase(sf_ic<0>{}, sf_ic<0>{}, sf_ic<1>{}, sf_ic<1>{}, sf_ic<3>{}, sf_ic<1>{}, D1, false, sf_ic<0>{}, sf_ic<1>{});    // O1: (A0,B0) | read A1(kt+1) | refill B1 s1 <- B1(kt+3)
+      phase(sf_ic<1>{}, sf_ic<0>{}, sf_ic<0>{}, sf_ic<0>{}, sf_ic<2>{}, sf_ic<1>{}, D1, false, sf_ic<0>{}, sf_ic<0>{});    // O2: (A1,B0) | read A0(kt+2) | refill B0 s1 <- B0(kt+3)
+      phase(sf_ic<1>{}, sf_ic<1>{}, sf_ic<2>{}, sf_ic<0>{}, sf_ic<1>{}, sf_ic<1>{}, D1, false, sf_ic<0>{}, sf_ic<1>{});    // O3: (A1,B1) | read B0(kt+2) | refill A1 s1 <- A1(kt+3)
       D0 = it_next(); D1 = it_next();
     };
-    pair(r4c<1>{}, had_stores);
+    pair(sf_ic<1>{}, had_stores);
 #pragma unroll 1
-    for (int kt = 2; kt < nk; kt += 2) pair(r4c<0>{}, false);
+    for (int kt = 2; kt < nk; kt += 2) pair(sf_ic<0>{}, false);
 
     // ---- epilogue: bf16 (GELU) rows through the wave's 4-KiB slab, 16-byte row stores (the transposed-block epilogue of config 11, twice 64 features) ----
     r4_acc_fence();
@@ -302,8 +273,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_r4_kernel(GemmArgs p) {
     had_stores = false;
     if (!(R4_ABL & 1) && en0 + wn * 128 < p.N) {                  // wave-uniform (N % 128 == 0)
       had_stores = true;
-      int el;                                                     // lane id from mbcnt, as asm: not hoisted out of the tile loop (nothing lane-derived stays live across the k-loop)
-      asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(el));
+      const int el = sf_lane_asm();                               // not hoisted out of the tile loop (nothing lane-derived stays live across the k-loop)
       const int el31 = el & 31, ehi = el >> 5;
       const int wr_off = el31 * 128 + ((ehi ^ ((el31 >> 3) & 1)) << 3), sw7 = el31 & 7;
       const int tr0 = el >> 3, ch = el & 7;
@@ -333,7 +303,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_r4_kernel(GemmArgs p) {
               u32x2 w; w.x = pack_bf2(x.x, x.y); w.y = pack_bf2(x.z, x.w);
               *reinterpret_cast<u32x2*>(wslab + wr_off + (((j * 4 + g) ^ sw7) << 4)) = w;
             }
-          R4_WAVE_SYNC();
+          SF_WAVE_SYNC();
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const u32x4 v = *reinterpret_cast<const u32x4*>(wslab + rd_off + q * 8 * 128);
@@ -341,7 +311,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_r4_kernel(GemmArgs p) {
             if (q & 1) { o.x = v.z; o.y = v.w; o.z = v.x; o.w = v.y; } else { o = v; }
             __builtin_amdgcn_raw_buffer_store_b128(o, rc, cbase + (uint32_t)((i * 32 + q * 8) * p.ldc) * 2u, 0, SF_EPI_STORE_AUX);
           }
-          R4_WAVE_SYNC();
+          SF_WAVE_SYNC();
           __builtin_amdgcn_sched_barrier(0);                       // one 32-token block at a time: its 32 accumulator registers + the GELU's temporaries, not the whole tile's
         }
       }

@@ -86,7 +86,7 @@ __device__ __forceinline__ void qkv_space_attn_body(const QsArgs& p) {
       if (x < 240) {
         const int ch = x & 7, w3 = (x >> 3) % 3, hs = (x >> 3) / 3, srow = hs % 5, hd = hs / 5;
         const uint32_t voff = (uint32_t)(((srow == 0 ? 0 : 1 + f * 4 + (srow - 1)) * p.lds_ + w3 * QKT_D + hd * 64 + ch * 8) * 2);
-        qkt_dma1(voff, reinterpret_cast<const char*>(p.side + seq * 33 * p.lds_ + hp * 128), lds0 + QS_SIDE_OFF + wave * 1024);
+        sf_dma1(voff, reinterpret_cast<const char*>(p.side + seq * 33 * p.lds_ + hp * 128), lds0 + QS_SIDE_OFF + wave * 1024);
       }
     }
     f32x16 acc[3][3];
@@ -103,7 +103,7 @@ __device__ __forceinline__ void qkv_space_attn_body(const QsArgs& p) {
       // MASK: the group's key flags -> additive score terms (the S accumulators START at them: 0 or -inf, no arithmetic in the softmax); the byte loads fly under the hand-over
       uint8_t kflag = 1;
       if (MASK && etid >= 256 && etid < 256 + QS_TOK + 1) { const int k = etid - 256; kflag = k == 0 ? p.key_keep[seq * p.seq_rows] : p.key_keep[xrow0 + k - 1]; }
-      qkt_barrier();
+      sf_barrier();
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
         const int cb = (wn * 3 + j) * 32;                           // first tile column of the block (wave-uniform)
@@ -135,7 +135,7 @@ __device__ __forceinline__ void qkv_space_attn_body(const QsArgs& p) {
         const int x = etid - 256, ch = x & 7, rr = (x >> 3) % 11, hd = (x >> 3) / 11;
         *reinterpret_cast<uint4*>(smem + hd * 3 * QS_ARR + QS_ARR + qs_arr_off(QS_TOK + 1 + rr, ch)) = make_uint4(0u, 0u, 0u, 0u);
       }
-      qkt_barrier();
+      sf_barrier();
     }
 
     // ---- epilogue (2): the space attention of (frame, head), the arithmetic of attn_mfma_kernel<64, 13> -----------------------------------------------------
@@ -351,11 +351,11 @@ __device__ __forceinline__ void qkv_space_attn_body(const QsArgs& p) {
         // four units u, u + 4, u + 8, u + 12 share a SIMD (waves w, w + 4), so the two SIMDs with four units are the ones that hold a single: 7 | 7 | 6 | 6 tiles
         const int u = ((wave + (int)tcount) & 7) + 8 * uu;         // wave-uniform
         if (u >= 14) break;
-        if (u < 12) { const int h = u >= 6 ? 1 : 0, pu = u - 6 * h; unit(qkt_ic<2>{}, h, 2 * pu, 2 * pu + 1); }
-        else unit(qkt_ic<1>{}, u - 12, 12, 12);
+        if (u < 12) { const int h = u >= 6 ? 1 : 0, pu = u - 6 * h; unit(sf_ic<2>{}, h, 2 * pu, 2 * pu + 1); }
+        else unit(sf_ic<1>{}, u - 12, 12, 12);
       }
     }
-    qkt_barrier();                                                   // every wave is out of the attention arrays: the next tile's operands may land
+    sf_barrier();                                                   // every wave is out of the attention arrays: the next tile's operands may land
     t += sched.step;
     ++tcount;
     if (t >= sched.t_end) break;

@@ -23,7 +23,7 @@
 //   * Host side: one argument check and one launch (grid computation included) for the four launchers (the bf16 and the MX form of either kernel).
 #pragma once
 #include "sf_common.h"
-#include <type_traits>
+#include "sf_lds_prims.h"
 #include <stdlib.h>
 
 #define QKT_ROWS 192                     // token rows of the tile
@@ -38,30 +38,6 @@
 typedef __attribute__((ext_vector_type(8))) int qkt_i32x8;
 typedef short qkt_s4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) qkt_s4 qkt_lds_s4;
-
-__device__ __forceinline__ void qkt_dma1(uint32_t voff, const void* sbase, uint32_t lds) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds) : "memory");
-}
-__device__ __forceinline__ void qkt_dma_dword_addr(const void* gaddr, uint32_t lds) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gaddr), "s"(lds) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void qkt_wait_vmcnt() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_waitcnt((N & 0xF) | (0x7 << 4) | (0xF << 8) | ((N >> 4) << 14));
-}
-__device__ __forceinline__ void qkt_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-__device__ __forceinline__ uint32_t qkt_lds_addr(const void* p) { return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char*)p; }
-
-template <int V> using qkt_ic = std::integral_constant<int, V>;
 
 // Persistent schedule, one workgroup per CU: block b sits on XCD b % 8; every XCD owns a contiguous range of row tiles (frames | patch blocks) and sweeps it once per
 // chunk of `hc` head pairs (pair fastest inside a chunk).  A workgroup walks items t = li, li + step, .. < t_end of its XCD.
@@ -109,7 +85,7 @@ struct QktTile {
 
   __device__ __forceinline__ QktTile(char* smem_, const QktOperands& o_, int wave_, int lane_)
       : smem(smem_), o(o_), wave(wave_), lane(lane_), wm(wave_ >> 2), wn(wave_ & 3), sc_seg(wave_ % 3), sc_lanes(sc_seg == 0 ? 48 : (sc_seg == 1 ? 64 : 32)),
-        a8((uint32_t)(8 * o_.ldx * ESZ)), w8((uint32_t)(8 * o_.ldw * ESZ)), lds0(__builtin_amdgcn_readfirstlane(qkt_lds_addr(smem_))),
+        a8((uint32_t)(8 * o_.ldx * ESZ)), w8((uint32_t)(8 * o_.ldw * ESZ)), lds0(__builtin_amdgcn_readfirstlane(sf_lds_addr(smem_))),
         lds_a_w(__builtin_amdgcn_readfirstlane(lds0 + wave_ * 3072)), lds_w_w(__builtin_amdgcn_readfirstlane(lds0 + QKT_A_BYTES + wave_ * 2048)),
         sc_lds(__builtin_amdgcn_readfirstlane(lds0 + SC_OFF + (sc_seg == 0 ? 0 : (sc_seg == 1 ? 768 : 768 + 1024)))) {}
 
@@ -158,18 +134,18 @@ struct QktTile {
   __device__ __forceinline__ void issue_sc(int kt) const {
     const char* base = sc_seg == 0 ? reinterpret_cast<const char*>(o.sX) + (int64_t)kt * o.ldsx + xrow * 4
                                    : reinterpret_cast<const char*>(o.sW) + (int64_t)kt * o.ldsw + (int64_t)hp * 512;
-    if (lane < sc_lanes) qkt_dma1(sc_voff, base, sc_lds + (kt & 1) * QKT_SC_BYTES);
+    if (lane < sc_lanes) sf_dma1(sc_voff, base, sc_lds + (kt & 1) * QKT_SC_BYTES);
   }
   __device__ __forceinline__ void issue_a(int pc, int S, int kt) const {   // piece pc: 8 pc rows further down; the chunk swizzle flips bit 2 with every 8 rows
-    qkt_dma1(((pc & 1) ? (voff_a ^ 64u) : voff_a) + (uint32_t)pc * a8, xbase + kt * 128, lds_a_w + S * QKT_STAGE + pc * 1024);
+    sf_dma1(((pc & 1) ? (voff_a ^ 64u) : voff_a) + (uint32_t)pc * a8, xbase + kt * 128, lds_a_w + S * QKT_STAGE + pc * 1024);
   }
   __device__ __forceinline__ void issue_w(int j, int S, int kt) const {
-    qkt_dma1(voff_w[j], wbase + kt * 128, lds_w_w + S * QKT_STAGE + j * QKT_W_PART);
-    qkt_dma1((voff_w[j] ^ 64u) + w8, wbase + kt * 128, lds_w_w + S * QKT_STAGE + j * QKT_W_PART + 1024);
+    sf_dma1(voff_w[j], wbase + kt * 128, lds_w_w + S * QKT_STAGE + j * QKT_W_PART);
+    sf_dma1((voff_w[j] ^ 64u) + w8, wbase + kt * 128, lds_w_w + S * QKT_STAGE + j * QKT_W_PART + 1024);
   }
   // 6 x 64 bias floats (waves 0..5): tile columns 64 wave .. + 63 = (head hd = wave / 3, q | k | v = wave % 3).  One of the kernel's side loads, in front of project()
   __device__ __forceinline__ void issue_bias() const {
-    if (wave < 6 && o.bias) qkt_dma_dword_addr(o.bias + (wave % 3) * QKT_D + (hp * 2 + wave / 3) * 64 + lane, lds0 + QKT_BIAS_OFF + wave * 256);
+    if (wave < 6 && o.bias) sf_dma_dword_addr(o.bias + (wave % 3) * QKT_D + (hp * 2 + wave / 3) * 64 + lane, lds0 + QKT_BIAS_OFF + wave * 256);
   }
 
   // The projection of the item: acc block (j, i) = features 96 wn + 32 j + 8 g + 4 hi + r of the tile, tokens 96 wm + 32 i + l31.  Starts behind the barrier that ended
@@ -181,8 +157,8 @@ struct QktTile {
     issue_w(1, 0, 0); issue_a(1, 0, 0); issue_a(2, 0, 0);
     issue_w(2, 0, 0);
     issue_w(0, 1, 1); issue_a(0, 1, 1);
-    if (!NO_PROLOGUE_WAIT) qkt_wait_vmcnt<5>();                     // the kernel's side loads, (scales,) A | W0 | W1 of k-tile 0 (this wave's pieces) have landed
-    qkt_barrier();
+    if (!NO_PROLOGUE_WAIT) sf_wait_vmcnt<5>();                     // the kernel's side loads, (scales,) A | W0 | W1 of k-tile 0 (this wave's pieces) have landed
+    sf_barrier();
 
     // accumulators start at the bias
     {
@@ -257,40 +233,40 @@ struct QktTile {
       }
       __builtin_amdgcn_sched_barrier(0);
       if (ld1) { issue_w(1, S ^ 1, kt + 1); issue_a(1, S ^ 1, kt + 1); issue_a(2, S ^ 1, kt + 1); }      // W1, A1, A2 of k-tile kt+1
-      qkt_barrier();
+      sf_barrier();
       __builtin_amdgcn_sched_barrier(0);
-      mma(qkt_ic<0>{});
+      mma(sf_ic<0>{});
       __builtin_amdgcn_sched_barrier(0);
-      qkt_barrier();
+      sf_barrier();
       // ---- phase 1: feature block 1 ----
       read_w(st, 1, S);
       __builtin_amdgcn_sched_barrier(0);
       // (MX: the scale piece of k-tile kt+1 goes in FRONT of W2 - the phase-2 wait below then retires it with A | W0 | W1 - into the other parity's area, last read in phase 0 of kt-1)
-      if (ld1) { if (MX) issue_sc(kt + 1); issue_w(2, S ^ 1, kt + 1); if (MX) qkt_wait_vmcnt<10>(); else qkt_wait_vmcnt<9>(); } else qkt_wait_vmcnt<0>();   // W2 of k-tile kt+1 issued; W2 of this k-tile has landed
-      qkt_barrier();
+      if (ld1) { if (MX) issue_sc(kt + 1); issue_w(2, S ^ 1, kt + 1); if (MX) sf_wait_vmcnt<10>(); else sf_wait_vmcnt<9>(); } else sf_wait_vmcnt<0>();   // W2 of k-tile kt+1 issued; W2 of this k-tile has landed
+      sf_barrier();
       __builtin_amdgcn_sched_barrier(0);
-      mma(qkt_ic<1>{});
+      mma(sf_ic<1>{});
       __builtin_amdgcn_sched_barrier(0);
-      qkt_barrier();
+      sf_barrier();
       // ---- phase 2: feature block 2 ----
       read_w(st, 2, S);
       __builtin_amdgcn_sched_barrier(0);
-      if (ld2) { issue_w(0, S, kt + 2); issue_a(0, S, kt + 2); qkt_wait_vmcnt<5>(); }                     // W0, A0 of k-tile kt+2; A | W0 | W1 of k-tile kt+1 have landed
-      else if (ld1) qkt_wait_vmcnt<2>();
-      else qkt_wait_vmcnt<0>();
-      qkt_barrier();
+      if (ld2) { issue_w(0, S, kt + 2); issue_a(0, S, kt + 2); sf_wait_vmcnt<5>(); }                     // W0, A0 of k-tile kt+2; A | W0 | W1 of k-tile kt+1 have landed
+      else if (ld1) sf_wait_vmcnt<2>();
+      else sf_wait_vmcnt<0>();
+      sf_barrier();
       __builtin_amdgcn_sched_barrier(0);
-      mma(qkt_ic<2>{});
+      mma(sf_ic<2>{});
       __builtin_amdgcn_sched_barrier(0);
-      qkt_barrier();
+      sf_barrier();
     };
-    if (wm == 1) qkt_barrier();                                     // waves 4-7 run one barrier behind waves 0-3
+    if (wm == 1) sf_barrier();                                     // waves 4-7 run one barrier behind waves 0-3
 #pragma unroll 1
     for (int kt = 0; kt < NK; kt += 2) {
-      ktile(qkt_ic<0>{}, kt, true, kt + 2 < NK);
-      ktile(qkt_ic<1>{}, kt + 1, kt + 2 < NK, kt + 3 < NK);
+      ktile(sf_ic<0>{}, kt, true, kt + 2 < NK);
+      ktile(sf_ic<1>{}, kt + 1, kt + 2 < NK, kt + 3 < NK);
     }
-    if (wm == 0) qkt_barrier();                                     // re-align; every wave is done with both stages
+    if (wm == 0) sf_barrier();                                     // re-align; every wave is done with both stages
   }
 };
 

@@ -24,7 +24,7 @@
 //   * persistent, one workgroup per CU; inside an XCD's range of row tiles the heads go in chunks of 6 (head fastest), two 56 KiB operand slots;
 //     the slabs (8 x 12.5 KiB) overlay slot 1, so only the next tile's FIRST k-tile is prefetched under the epilogue.  160 KiB of LDS exactly.
 #include "sf_common.h"
-#include <type_traits>
+#include "sf_lds_prims.h"
 #include <stdlib.h>
 #include "../../include/synchformer_hip.h"
 
@@ -88,37 +88,7 @@ struct QtArgs {
 };
 
 typedef __attribute__((ext_vector_type(2))) __bf16 qt_bf2;
-typedef __attribute__((ext_vector_type(2))) unsigned int qt_u32x2;
-
-__device__ __forceinline__ void qt_dma1(uint32_t voff, const void* sbase, uint32_t lds) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds) : "memory");
-}
-// one dword per lane (64-bit lane addresses) -> 4 consecutive bytes per lane from the wave-uniform LDS address lds; inactive lanes write nothing
-__device__ __forceinline__ void qt_dma_dword_addr(const void* gaddr, uint32_t lds) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gaddr), "s"(lds) : "memory");
-}
 typedef __attribute__((ext_vector_type(8))) int qt_i32x8;
-template <int N>
-__device__ __forceinline__ void qt_wait_vmcnt() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_waitcnt((N & 0xF) | (0x7 << 4) | (0xF << 8) | ((N >> 4) << 14));
-}
-__device__ __forceinline__ void qt_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-__device__ __forceinline__ uint32_t qt_lds_addr(const void* p) { return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char*)p; }
-__device__ __forceinline__ void qt_wait_vmcnt0_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_waitcnt((0 & 0xF) | (0x7 << 4) | (0xF << 8) | (0 << 14));
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 __device__ __forceinline__ float qt_dot8(const uint4& a, const uint4& b) {
   float d = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(qt_bf2, a.x), __builtin_bit_cast(qt_bf2, b.x), 0.f, false);
   d = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(qt_bf2, a.y), __builtin_bit_cast(qt_bf2, b.y), d, false);
@@ -228,12 +198,12 @@ __global__ __launch_bounds__(512, 2) void qkv_time_attn_kernel(QtArgs p) {
       }
     }
   };
-  const uint32_t lds0 = __builtin_amdgcn_readfirstlane(qt_lds_addr(smem));
+  const uint32_t lds0 = __builtin_amdgcn_readfirstlane(sf_lds_addr(smem));
   const uint32_t lds_a_w = __builtin_amdgcn_readfirstlane(lds0 + wave * 4096), lds_b_w = __builtin_amdgcn_readfirstlane(lds0 + QT_A_BYTES + wave * 3072);
   auto piece = [&](int pc, int slot, int kt) {                     // pc = 0 .. 3: A pieces, 4 .. 6: B pieces of k-tile kt
-    if (pc < 4) qt_dma1(voff_a[pc], reinterpret_cast<const char*>(p.X) + kt * 128, lds_a_w + slot * QT_STAGE + pc * 1024);
-    else if (PP) qt_dma1(voff_b[pc - 4], wbase + kt * 128, lds0 + QT_A_BYTES + slot * QT_STAGE + (pc - 4) * 8192 + wave * 1024);
-    else qt_dma1(voff_b[pc - 4], wbase + kt * 128, lds_b_w + slot * QT_STAGE + (pc - 4) * 1024);
+    if (pc < 4) sf_dma1(voff_a[pc], reinterpret_cast<const char*>(p.X) + kt * 128, lds_a_w + slot * QT_STAGE + pc * 1024);
+    else if (PP) sf_dma1(voff_b[pc - 4], wbase + kt * 128, lds0 + QT_A_BYTES + slot * QT_STAGE + (pc - 4) * 8192 + wave * 1024);
+    else sf_dma1(voff_b[pc - 4], wbase + kt * 128, lds_b_w + slot * QT_STAGE + (pc - 4) * 1024);
   };
   // PP: the CLS q | k | v (3 x 128 B) of this wave's sequence and head as one masked LDS-DMA piece (lanes 0-23, 16 bytes each) into the wave's 384 B
   const uint32_t lds_cls = __builtin_amdgcn_readfirstlane(lds0 + QT_CLS_OFF + wave * 384);
@@ -250,18 +220,18 @@ __global__ __launch_bounds__(512, 2) void qkv_time_attn_kernel(QtArgs p) {
     if (g0 > n_patches - 1) g0 = n_patches - 1;
     const char* cls = reinterpret_cast<const char*>(p.qkv_cls + (int64_t)(g0 / (uint32_t)p.n_groups) * p.ldc + head * 64);
     const uint32_t dst = MX ? __builtin_amdgcn_readfirstlane(lds0 + cls_slot_mx(tm, par)) : lds_cls;
-    if (lane < 24) qt_dma1((uint32_t)(((lane >> 3) * QT_D + (lane & 7) * 8) * 2), cls, dst);
+    if (lane < 24) sf_dma1((uint32_t)(((lane >> 3) * QT_D + (lane & 7) * 8) * 2), cls, dst);
   };
   // MX: the scale dwords of k-tile kt - this wave's 32 token rows (lanes 0-31) and its 24 of the head's W rows (lanes 32-55) - as ONE piece of 56 dwords
   const uint32_t lds_sc = __builtin_amdgcn_readfirstlane(lds0 + QT_SC_OFF + wave * QT_SC_WAVE);
   auto scale_piece = [&](int kt) {
-    if (lane < 56) qt_dma_dword_addr(sc_addr + (uint64_t)(uint32_t)kt * sc_step, lds_sc);
+    if (lane < 56) sf_dma_dword_addr(sc_addr + (uint64_t)(uint32_t)kt * sc_step, lds_sc);
   };
   // the head's bias: lanes 0-47 of wave 0 fetch 16 bytes each of the q | k | v thirds (768 floats apart), the other lanes re-read lane 0's
   const uint32_t voff_bias = lane < 48 ? (uint32_t)(((lane >> 4) * QT_D + (lane & 15) * 4) * 4) : 0u;
   const uint32_t lds_bias = lds0 + QT_BIAS_OFF;
   auto bias_piece = [&]() {                                        // wave-uniform branch; after set_tile (uses `head`)
-    if (wave == 0 && p.bias && (!MX || lane < 48)) qt_dma1(voff_bias, reinterpret_cast<const char*>(p.bias) + head * 256, lds_bias);   // MX: the 256 B behind the 768 are the scale area
+    if (wave == 0 && p.bias && (!MX || lane < 48)) sf_dma1(voff_bias, reinterpret_cast<const char*>(p.bias) + head * 256, lds_bias);   // MX: the 256 B behind the 768 are the scale area
   };
   set_tile(t);
 #pragma unroll
@@ -269,7 +239,7 @@ __global__ __launch_bounds__(512, 2) void qkv_time_attn_kernel(QtArgs p) {
   bias_piece();
   if (MX) scale_piece(0);
   int tpar = 0;                                                    // MX: parity of the current tile (CLS landing slots)
-  if (PP) { cls_piece(0); qt_wait_vmcnt<0>(); }
+  if (PP) { cls_piece(0); sf_wait_vmcnt<0>(); }
 
   constexpr int nk = MX ? QT_D / 128 : QT_D / QT_BK;                // 12 k-tiles of 64 bf16 / 6 of 128 fp8: 128 bytes per row either way
   const float sc = p.scale * 1.44269504088896f;                    // softmax in base 2
@@ -293,7 +263,7 @@ __global__ __launch_bounds__(512, 2) void qkv_time_attn_kernel(QtArgs p) {
     auto kstep = [&](int kt, auto refill_tag, auto first_tag) {
       constexpr bool REFILL = decltype(refill_tag)::value;
       constexpr bool FIRST = decltype(first_tag)::value;
-      qt_wait_vmcnt0_barrier();                                    // k-tile kt landed everywhere; the other slot is free (kt = 0: every wave is out of the slabs)
+      sf_wait_vmcnt_barrier<0>();                                    // k-tile kt landed everywhere; the other slot is free (kt = 0: every wave is out of the slabs)
       if (FIRST) {
         if (lane < 24) *reinterpret_cast<uint4*>(smem + QT_CLS_OFF + wave * 384 + lane * 16) = cls_raw;     // the explicit wait above covered the load
         const float* bs = reinterpret_cast<const float*>(smem + QT_BIAS_OFF);
@@ -343,7 +313,7 @@ __global__ __launch_bounds__(512, 2) void qkv_time_attn_kernel(QtArgs p) {
       uint32_t sxd = 0, swd[6] = {0, 0, 0, 0, 0, 0};               // MX: the k-tile's scale dwords, shifted so that byte 2 kk is this half-wave's block of MFMA kk
       int sxv[2] = {0, 0}, swv[2][2] = {{0, 0}, {0, 0}};
       // every wave is out of its slab (they overlay stage 1) and has waited for its pieces of k-tile 0 (vmcnt 0 in front of the epilogue's stores)
-      qt_barrier();
+      sf_barrier();
       if (!(QT_ABL & 2)) { piece(4, 1, 1); piece(0, 1, 1); piece(1, 1, 1); }          // W0, A0, A1 of k-tile 1
       {
         const float* bs = reinterpret_cast<const float*>(smem + QT_BIAS_OFF);
@@ -411,52 +381,50 @@ __global__ __launch_bounds__(512, 2) void qkv_time_attn_kernel(QtArgs p) {
           for (int b = 0; b < 6; ++b) swd[b] = *reinterpret_cast<const uint32_t*>(smem + fsw + b * 16) >> shi;
           sxv[0] = (int)(sxd & 0xffu); sxv[1] = (int)((sxd >> 16) & 0xffu);
         }
-        read_w(st, std::integral_constant<int, 0>{});
+        read_w(st, sf_ic<0>{});
         __builtin_amdgcn_sched_barrier(0);
         if (ld1) { piece(5, S ^ 1, kt + 1); piece(2, S ^ 1, kt + 1); piece(3, S ^ 1, kt + 1); }   // W1, A2, A3 of k-tile kt+1
-        if (!first) { if (QT_ABL & 2) qt_wait_vmcnt<0>(); else if (more1) qt_wait_vmcnt<9>(); else qt_wait_vmcnt<3>(); }   // W third 1 of this k-tile has landed
-        qt_barrier();
+        if (!first) { if (QT_ABL & 2) sf_wait_vmcnt<0>(); else if (more1) sf_wait_vmcnt<9>(); else sf_wait_vmcnt<3>(); }   // W third 1 of this k-tile has landed
+        sf_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        mma(std::integral_constant<int, 0>{});
+        mma(sf_ic<0>{});
         __builtin_amdgcn_sched_barrier(0);
-        qt_barrier();
+        sf_barrier();
         // ---- phase 1: k third ----
-        read_w(st, std::integral_constant<int, 1>{});
+        read_w(st, sf_ic<1>{});
         __builtin_amdgcn_sched_barrier(0);
         if (MX && ld1) scale_piece(kt + 1);                                                        // (every wave has read k-tile kt's dwords in phase 0)
         if (ld1) piece(6, S ^ 1, kt + 1);                                                          // W2 of k-tile kt+1
-        if (!first) { if (!more1 || (QT_ABL & 2)) qt_wait_vmcnt<0>(); else if (MX) qt_wait_vmcnt<8>(); else qt_wait_vmcnt<7>(); }   // W third 2 has landed
-        qt_barrier();
+        if (!first) { if (!more1 || (QT_ABL & 2)) sf_wait_vmcnt<0>(); else if (MX) sf_wait_vmcnt<8>(); else sf_wait_vmcnt<7>(); }   // W third 2 has landed
+        sf_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        mma(std::integral_constant<int, 1>{});
+        mma(sf_ic<1>{});
         __builtin_amdgcn_sched_barrier(0);
-        qt_barrier();
+        sf_barrier();
         // ---- phase 2: v third ----
-        read_w(st, std::integral_constant<int, 2>{});
+        read_w(st, sf_ic<2>{});
         __builtin_amdgcn_sched_barrier(0);
         if (ld2) { piece(4, S, kt + 2); piece(0, S, kt + 2); piece(1, S, kt + 2); }                // W0, A0, A1 of k-tile kt+2
-        if (more1) { if (QT_ABL & 2) qt_wait_vmcnt<0>(); else if (more2) qt_wait_vmcnt<4>(); else qt_wait_vmcnt<1>(); }   // A | W third 0 of k-tile kt+1 have landed
-        qt_barrier();
+        if (more1) { if (QT_ABL & 2) sf_wait_vmcnt<0>(); else if (more2) sf_wait_vmcnt<4>(); else sf_wait_vmcnt<1>(); }   // A | W third 0 of k-tile kt+1 have landed
+        sf_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        mma(std::integral_constant<int, 2>{});
+        mma(sf_ic<2>{});
         __builtin_amdgcn_sched_barrier(0);
-        qt_barrier();
+        sf_barrier();
       };
-      if (wg == 1) qt_barrier();
+      if (wg == 1) sf_barrier();
       for (int kt = 0; kt < nk; kt += 2) {
         const bool more = kt + 2 < nk;
-        ktile(std::integral_constant<int, 0>{}, kt, true, more, kt == 0);
-        ktile(std::integral_constant<int, 1>{}, kt + 1, more, more, false);
+        ktile(sf_ic<0>{}, kt, true, more, kt == 0);
+        ktile(sf_ic<1>{}, kt + 1, more, more, false);
       }
-      if (wg == 0) qt_barrier();                                   // re-align; every wave is done with both stages
+      if (wg == 0) sf_barrier();                                   // re-align; every wave is done with both stages
     } else {
     kstep(0, std::true_type{}, std::true_type{});
     for (int kt = 1; kt + 1 < nk; ++kt) kstep(kt, std::true_type{}, std::false_type{});
     kstep(nk - 1, std::false_type{}, std::false_type{});
     // every wave is done with both slots: slot 0 takes the next tile's first k-tile, the slabs (over slot 1) take this tile's q | k | v
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    sf_barrier();
     }
     const uint32_t etm = tm; const int ehead = head;
     const uint32_t tnext = t + per_xcd_blocks;
@@ -480,10 +448,10 @@ __global__ __launch_bounds__(512, 2) void qkv_time_attn_kernel(QtArgs p) {
     for (int j = 0; j < 6; ++j)
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        qt_u32x2 w;
+        u32x2 w;
         w.x = pack_bf2(acc[j][g * 4 + 0], acc[j][g * 4 + 1]);
         w.y = pack_bf2(acc[j][g * 4 + 2], acc[j][g * 4 + 3]);
-        *reinterpret_cast<qt_u32x2*>(slab + el31 * QT_SLAB_LD + (j * 32 + g * 8 + ehi * 4) * 2) = w;
+        *reinterpret_cast<u32x2*>(slab + el31 * QT_SLAB_LD + (j * 32 + g * 8 + ehi * 4) * 2) = w;
       }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     // The wave's four patches belong to ONE sequence (n_groups % 4 == 0); np of them exist (ragged last tile).
@@ -501,7 +469,7 @@ __global__ __launch_bounds__(512, 2) void qkv_time_attn_kernel(QtArgs p) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       cls_piece(tpar ^ 1);
     }
-    if (np == 0 && PP) qt_wait_vmcnt<0>();                         // (waves with patches wait in front of their stores, below)
+    if (np == 0 && PP) sf_wait_vmcnt<0>();                         // (waves with patches wait in front of their stores, below)
     if (np > 0) {                                                  // wave-uniform
       const int64_t seq = g0 / (uint32_t)p.n_groups;
       const int pp0 = (int)(g0 - (uint32_t)seq * (uint32_t)p.n_groups);
@@ -581,7 +549,7 @@ __global__ __launch_bounds__(512, 2) void qkv_time_attn_kernel(QtArgs p) {
         // vector-memory path of a CU charges for)
         // PP: the next tile's k-tile 0, bias and CLS pieces (issued at the top of this epilogue) have landed by now; waiting for them HERE, in front of
         // this epilogue's stores, keeps the stores out of every counted wait of the next k-loop
-        if (PP) qt_wait_vmcnt<0>();
+        if (PP) sf_wait_vmcnt<0>();
         const int qh = (elane >> 3) & 1, ds = elane & 7;
         sf_f32x2_t v[9][4];
         {
@@ -630,15 +598,14 @@ __global__ __launch_bounds__(512, 2) void qkv_time_attn_kernel(QtArgs p) {
             const int be_hi = __shfl_xor(be, 4, 64);                                   // the head's other block (lanes ds ^ 4)
             if (live) {
               const int64_t orow = orow0 + (int64_t)(qh * 4 + qq) * p.n_groups;
-              qt_u32x2 q8; q8.x = sf_fp8x4(f, inv); q8.y = sf_fp8x4(f + 4, inv);
-              *reinterpret_cast<qt_u32x2*>(p.out_q + orow * p.ldq + ehead * 64 + ds * 8) = q8;
+              u32x2 q8; q8.x = sf_fp8x4(f, inv); q8.y = sf_fp8x4(f + 4, inv);
+              *reinterpret_cast<u32x2*>(p.out_q + orow * p.ldq + ehead * 64 + ds * 8) = q8;
               if (ds == 0) *reinterpret_cast<uint16_t*>(p.out_s + (int64_t)(ehead >> 1) * p.splane + orow * 4 + (ehead & 1) * 2) = (uint16_t)(be | (be_hi << 8));
             }
           } else
           if (live) {
-            typedef __attribute__((ext_vector_type(4))) unsigned int qt_u32x4;
-            qt_u32x4* dst = reinterpret_cast<qt_u32x4*>(optr + (int64_t)(qh * 4 + qq) * p.n_groups * p.ldo);
-            const qt_u32x4 wv = {w.x, w.y, w.z, w.w};
+            u32x4* dst = reinterpret_cast<u32x4*>(optr + (int64_t)(qh * 4 + qq) * p.n_groups * p.ldo);
+            const u32x4 wv = {w.x, w.y, w.z, w.w};
             if (QT_OUT_NT) __builtin_nontemporal_store(wv, dst); else *dst = wv;
           }
         }

@@ -91,7 +91,7 @@ __device__ __forceinline__ void qkv_time2_attn_body(const Qt2Args& p) {
 
   // the CLS blocks start as zeros; only their row 0 is ever written again
   for (int x = tid; x < (MX ? 1024 : 6 * 2048) / 16; x += 512) *reinterpret_cast<uint4*>(smem + QT2_CB_OFF + x * 16) = make_uint4(0u, 0u, 0u, 0u);
-  qkt_barrier();                                                   // (a left-over item writes row 0 of the blocks before its first barrier)
+  sf_barrier();                                                   // (a left-over item writes row 0 of the blocks before its first barrier)
 
   const float sc2 = p.scale * 1.44269504088896f;                   // softmax in base 2
   uint32_t tcount = 0;
@@ -113,7 +113,7 @@ __device__ __forceinline__ void qkv_time2_attn_body(const Qt2Args& p) {
       // ---- side loads, in front of the main loop's own pieces (the previous item's attention is over: barrier at the bottom of the loop): bias, the CLS row ----
       tile.issue_bias();
       if (wave == 7) {                                              // CLS row: chunk x = (hd * 3 + which) * 8 + ch, 48 chunks of 16 B
-        if (lane < 48) qkt_dma1(cls_voff, reinterpret_cast<const char*>(p.side + seq * 33 * p.lds_ + hp * 128), lds0 + QT2_LAND_OFF);
+        if (lane < 48) sf_dma1(cls_voff, reinterpret_cast<const char*>(p.side + seq * 33 * p.lds_ + hp * 128), lds0 + QT2_LAND_OFF);
       }
       f32x16 acc[3][3];
       tile.project(acc);
@@ -162,7 +162,7 @@ __device__ __forceinline__ void qkv_time2_attn_body(const Qt2Args& p) {
           const int fr = etid / QT2_TP, pl = etid - fr * QT2_TP;
           reinterpret_cast<float*>(smem + QT2_MASK_OFF)[etid == QT2_ROWS ? QT2_ROWS : pl * 8 + fr] = kflag ? 0.f : -INFINITY;
         }
-        qkt_barrier();
+        sf_barrier();
       }
     } else {
       // ---- the left-over item: 4 patches x 8 frames of q | k | v of both heads from `side` -> array rows 0..31 (row = 8 i + f); the CLS row -> the blocks --------
@@ -192,7 +192,7 @@ __device__ __forceinline__ void qkv_time2_attn_body(const Qt2Args& p) {
         const uint8_t kf = r == 32 ? p.key_keep[seq * p.seq_rows] : p.key_keep[seq * p.seq_rows + 1 + (int64_t)(r & 7) * QT2_NP + QT2_ROWS + (r >> 3)];
         reinterpret_cast<float*>(smem + QT2_MASK_OFF)[r == 32 ? QT2_ROWS : r] = kf ? 0.f : -INFINITY;
       }
-      qkt_barrier();
+      sf_barrier();
     }
 
     // ---- epilogue (2): the time attention of the item's patches and the CLS query's partial over the item's keys ------------------------------------------------
@@ -426,14 +426,14 @@ __device__ __forceinline__ void qkv_time2_attn_body(const Qt2Args& p) {
       const int wr = (wave + (int)tcount) & 7;                      // rotate the roles over the SIMDs from item to item (wave-uniform)
       if (main_item) {
         // every wave: three of the 24 patch units (wr, wr + 8, wr + 16) and a quarter of one head's CLS-query work (key tiles 3 q .. 3 q + 2 -> record 4 tb + q)
-        if (!(QT2_ABL & 8)) patch_units(qkt_ic<3>{}, wr, 8);
-        if (!(QT2_ABL & 4)) cls_unit(qkt_ic<3>{}, qkt_ic<0>{}, wr & 1, 3 * (wr >> 1), tb * 4 + (wr >> 1));
+        if (!(QT2_ABL & 8)) patch_units(sf_ic<3>{}, wr, 8);
+        if (!(QT2_ABL & 4)) cls_unit(sf_ic<3>{}, sf_ic<0>{}, wr & 1, 3 * (wr >> 1), tb * 4 + (wr >> 1));
       } else if (!(QT2_ABL & 16)) {
-        if (wr < 2) cls_unit(qkt_ic<2>{}, qkt_ic<1>{}, wr, 0, 32);
-        else if (wr < 6) { const int u = (wr - 2) & 1; patch_units(qkt_ic<1>{}, ((wr - 2) >> 1) * 12 + u, 0); }
+        if (wr < 2) cls_unit(sf_ic<2>{}, sf_ic<1>{}, wr, 0, 32);
+        else if (wr < 6) { const int u = (wr - 2) & 1; patch_units(sf_ic<1>{}, ((wr - 2) >> 1) * 12 + u, 0); }
       }
     }
-    qkt_barrier();                                                  // every wave is out of the attention arrays: the next item's operands may land
+    sf_barrier();                                                  // every wave is out of the attention arrays: the next item's operands may land
     t += sched.step;
     ++tcount;
     if (t >= sched.t_end) break;
