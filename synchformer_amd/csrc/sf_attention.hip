@@ -838,10 +838,8 @@ static int attention_group_bwd_impl(const bf16_t* q, const bf16_t* k, const bf16
   a.cls_stats = cls_stats; a.o = o; a.ldo = ldo; a.dq_cls_part = dq_cls_part;
   const int64_t units = n_seq * n_groups * heads;
   SF_CHECK_ARG(units < ((int64_t)1 << 31), "sf_attention_group_bwd: too many groups");
-  static int waves = -1;
-  if (waves < 0) { const char* e = getenv("SF_GB_WAVES"); waves = e ? atoi(e) : GB_WAVES; }      // measurement hook: 8 = round 2's workgroup (two tiles per wave)
-  static int x32 = -1;
-  if (x32 < 0) { const char* e = getenv("SF_GB_X32"); x32 = e ? atoi(e) : 1; }                     // measurement hook: 0 = round 3's v_mfma_f32_16x16x16_bf16 passes
+  static const int waves = sf_env_int("SF_GB_WAVES", GB_WAVES);   // measurement hook: 8 = round 2's workgroup (two tiles per wave)
+  static const int x32 = sf_env_int("SF_GB_X32", 1);              // measurement hook: 0 = round 3's v_mfma_f32_16x16x16_bf16 passes
   if (waves == 8) {
     if (int rc = sf_prepare_kernel((const void*)attn_group_bwd_kernel<8, false>, GB_LDS(8), "sf_attention_group_bwd")) return rc;
     hipLaunchKernelGGL((attn_group_bwd_kernel<8, false>), dim3((unsigned)units), dim3(8 * 64), GB_LDS(8), (hipStream_t)stream, a);

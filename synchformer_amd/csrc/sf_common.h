@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
+#include "sf_launch_plan.h"
 
 typedef uint16_t bf16_t;   // raw bfloat16 bits
 typedef __attribute__((ext_vector_type(8))) short bf16x8;
@@ -33,6 +34,7 @@ void sf_set_error(const char* fmt, ...);
 // current device, cached per device (0 on error, sf_last_error set).
 int sf_prepare_kernel(const void* kernel, int lds_bytes, const char* who);
 int sf_cu_count(const char* who);
+// (what a launcher does with that count - the grid, tile-count, column-chunk and measurement-knob rules - is sf_launch_plan.h's, included above)
 
 // ---- row maps -----------------------------------------------------------------------------------------
 // A logical row r (< 2^31) of an operand lives at physical row

@@ -535,35 +535,15 @@ static int launch_gemm_persistent(GemmArgs a, hipStream_t s) {
   if (int rc = sf_prepare_kernel((const void*)kern, P_LDS, "sf_gemm_bf16")) return rc;
   const int n_cu = sf_cu_count("sf_gemm_bf16");
   if (n_cu <= 0) return -1;
-  const int64_t tiles_m = (a.M + PBM - 1) / PBM;
-  a.tiles_n = (uint32_t)((a.N + PBN - 1) / PBN);
-  const int64_t total = tiles_m * a.tiles_n;
-  if (total >= ((int64_t)1 << 31)) { sf_set_error("sf_gemm_bf16: too many tiles"); return -1; }
-  a.tiles_total = (uint32_t)total;
-  // Column-chunked sweeps keep the weight slice of a sweep (nchunk * 256 * K bf16) within ~2.4 MB of the XCD's 4 MB L2, so that the
-  // streamed A panels and outputs stop evicting it: PMC on M = 351,456 - qkv 1912 -> 1132 MiB fetched per launch (518 algorithmic),
-  // fc1 5604 -> 1167, and +2-4 % speed (profiles/r01_gemm_configs.md).  Only for short K: with K = 3072 an A panel is 1.5 MB and
-  // re-reading it per sweep costs more than it saves (fc2 already fetches its algorithmic bytes).  SF_GEMM_NCHUNK overrides (experiments).
-  static int env_chunk = -2;
-  if (env_chunk == -2) { const char* e = getenv("SF_GEMM_NCHUNK"); env_chunk = e ? atoi(e) : -1; }
-  if (env_chunk >= 0) a.nchunk = (uint32_t)env_chunk;
-  else a.nchunk = a.K <= 1024 ? (uint32_t)(2400000 / (512 * a.K) > 0 ? 2400000 / (512 * a.K) : 1) : 0u;
-  int64_t blocks = (n_cu / 8) * 8;                               // one workgroup per CU, a multiple of the 8 XCDs
-  if (blocks < 8) blocks = 8;                                    // (a device / partition with fewer than 8 CUs: never an empty grid)
-  const int64_t need = ((total + 7) / 8) * 8;
-  if (blocks > need) blocks = need;
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(512), P_LDS, s, a);
+  if (!sf_tile_counts(a.M, a.N, PBM, PBN, &a.tiles_n, &a.tiles_total)) { sf_set_error("sf_gemm_bf16: too many tiles"); return -1; }
+  a.nchunk = sf_gemm_nchunk(a.K);
+  hipLaunchKernelGGL(kern, dim3((unsigned)sf_xcd_grid(n_cu, a.tiles_total)), dim3(512), P_LDS, s, a);
   SF_LAUNCH_CHECK();
   return 0;
 }
 
 static int dispatch_gemm_persistent(const GemmArgs& a, bool out_bf16, bool gelu, bool res, hipStream_t s) {
-  if (out_bf16) {
-    if (gelu) return res ? launch_gemm_persistent<true, true, true>(a, s) : launch_gemm_persistent<true, true, false>(a, s);
-    return res ? launch_gemm_persistent<true, false, true>(a, s) : launch_gemm_persistent<true, false, false>(a, s);
-  }
-  if (gelu) return res ? launch_gemm_persistent<false, true, true>(a, s) : launch_gemm_persistent<false, true, false>(a, s);
-  return res ? launch_gemm_persistent<false, false, true>(a, s) : launch_gemm_persistent<false, false, false>(a, s);
+  return sf_gemm_dispatch_epi(out_bf16, gelu, res, [&](auto O, auto G, auto R) { return launch_gemm_persistent<O() != 0, G() != 0, R() != 0>(a, s); });
 }
 
 #ifdef SF_ABLATION   // measured-slower alternatives live in the ablation build only (synchformer_amd/build.py::build_ablation, tests load it explicitly)
@@ -742,28 +722,15 @@ static int launch_gemm_w4(GemmArgs a, hipStream_t s) {
   if (int rc = sf_prepare_kernel((const void*)kern, W4_LDS, "sf_gemm_bf16")) return rc;
   const int n_cu = sf_cu_count("sf_gemm_bf16");
   if (n_cu <= 0) return -1;
-  const int64_t tiles_m = (a.M + PBM - 1) / PBM;
-  a.tiles_n = (uint32_t)((a.N + PBN - 1) / PBN);
-  const int64_t total = tiles_m * a.tiles_n;
-  if (total >= ((int64_t)1 << 31)) { sf_set_error("sf_gemm_bf16: too many tiles"); return -1; }
-  a.tiles_total = (uint32_t)total;
-  a.nchunk = a.K <= 1024 ? (uint32_t)(2400000 / (512 * a.K) > 0 ? 2400000 / (512 * a.K) : 1) : 0u;
-  int64_t blocks = (n_cu / 8) * 8;
-  if (blocks < 8) blocks = 8;                                    // (a device / partition with fewer than 8 CUs: never an empty grid)
-  const int64_t need = ((total + 7) / 8) * 8;
-  if (blocks > need) blocks = need;
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), W4_LDS, s, a);
+  if (!sf_tile_counts(a.M, a.N, PBM, PBN, &a.tiles_n, &a.tiles_total)) { sf_set_error("sf_gemm_bf16: too many tiles"); return -1; }
+  a.nchunk = sf_l2_nchunk(a.K, 512, 1024);                       // (no SF_GEMM_NCHUNK override here)
+  hipLaunchKernelGGL(kern, dim3((unsigned)sf_xcd_grid(n_cu, a.tiles_total)), dim3(256), W4_LDS, s, a);
   SF_LAUNCH_CHECK();
   return 0;
 }
 
 static int dispatch_gemm_w4(const GemmArgs& a, bool out_bf16, bool gelu, bool res, hipStream_t s) {
-  if (out_bf16) {
-    if (gelu) return res ? launch_gemm_w4<true, true, true>(a, s) : launch_gemm_w4<true, true, false>(a, s);
-    return res ? launch_gemm_w4<true, false, true>(a, s) : launch_gemm_w4<true, false, false>(a, s);
-  }
-  if (gelu) return res ? launch_gemm_w4<false, true, true>(a, s) : launch_gemm_w4<false, true, false>(a, s);
-  return res ? launch_gemm_w4<false, false, true>(a, s) : launch_gemm_w4<false, false, false>(a, s);
+  return sf_gemm_dispatch_epi(out_bf16, gelu, res, [&](auto O, auto G, auto R) { return launch_gemm_w4<O() != 0, G() != 0, R() != 0>(a, s); });
 }
 
 #endif  // SF_ABLATION
@@ -787,11 +754,7 @@ template <class Cfg, bool OUT_BF16, bool GELU, bool HAS_RES, bool FAST>
 static int launch_gemm(GemmArgs a, hipStream_t s) {
   auto kern = gemm_bf16_kernel<Cfg, OUT_BF16, GELU, HAS_RES, FAST>;
   if (int rc = sf_prepare_kernel((const void*)kern, Cfg::LDS, "sf_gemm_bf16")) return rc;
-  const int64_t tiles_m = (a.M + Cfg::BM - 1) / Cfg::BM;
-  a.tiles_n = (uint32_t)((a.N + Cfg::BN - 1) / Cfg::BN);
-  const int64_t total = tiles_m * a.tiles_n;
-  if (total >= ((int64_t)1 << 31)) { sf_set_error("sf_gemm_bf16: too many tiles"); return -1; }
-  a.tiles_total = (uint32_t)total;
+  if (!sf_tile_counts(a.M, a.N, Cfg::BM, Cfg::BN, &a.tiles_n, &a.tiles_total)) { sf_set_error("sf_gemm_bf16: too many tiles"); return -1; }
   hipLaunchKernelGGL(kern, dim3(a.tiles_total, a.batch_inner > 0 ? (unsigned)g_batch_count : 1u), dim3(Cfg::THREADS), Cfg::LDS, s, a);
   SF_LAUNCH_CHECK();
   return 0;
@@ -804,12 +767,7 @@ static int dispatch_gemm(const GemmArgs& a, bool out_bf16, bool gelu, bool res, 
     if (out_bf16) return res ? launch_gemm<Cfg, true, false, true, false>(a, s) : launch_gemm<Cfg, true, false, false, false>(a, s);
     return res ? launch_gemm<Cfg, false, false, true, false>(a, s) : launch_gemm<Cfg, false, false, false, false>(a, s);
   }
-  if (out_bf16) {
-    if (gelu) return res ? launch_gemm<Cfg, true, true, true, true>(a, s) : launch_gemm<Cfg, true, true, false, true>(a, s);
-    return res ? launch_gemm<Cfg, true, false, true, true>(a, s) : launch_gemm<Cfg, true, false, false, true>(a, s);
-  }
-  if (gelu) return res ? launch_gemm<Cfg, false, true, true, true>(a, s) : launch_gemm<Cfg, false, true, false, true>(a, s);
-  return res ? launch_gemm<Cfg, false, false, true, true>(a, s) : launch_gemm<Cfg, false, false, false, true>(a, s);
+  return sf_gemm_dispatch_epi(out_bf16, gelu, res, [&](auto O, auto G, auto R) { return launch_gemm<Cfg, O() != 0, G() != 0, R() != 0, true>(a, s); });
 }
 
 // The automatic tile-configuration choice of sf_gemm_bf16 (-1 = no configuration serves these arguments: a k-tile-major weight outside the persistent kernels' range).

@@ -4,7 +4,6 @@
 #include "sf_common.h"
 #include "sf_lds_prims.h"
 #include "sf_gemm_epi.h"
-#include <stdlib.h>
 #include "../../include/synchformer_hip.h"
 
 #ifndef SF_ABL
@@ -30,6 +29,26 @@ struct GemmArgs {
   int64_t sA0, sA1, sW0, sW1, sC0, sC1;
   uint32_t stagger = 0;   // config 11: the workgroups that own one tile fewer than their XCD's first start this many x ~1.2 us late (SF_PP_STAGGER)
 };
+
+// The eight <OUT_BF16, GELU, HAS_RES> instantiations of a launcher template, chosen at run time: f(sf_ic<out_bf16>(), sf_ic<gelu>(), sf_ic<res>()) with a generic
+// lambda that names the launcher.  (The order of the eight calls is the order in which the kernels reach the code object: keep it.)
+template <class F>
+static int sf_gemm_dispatch_epi(bool out_bf16, bool gelu, bool res, F f) {
+  constexpr sf_ic<0> n{};
+  constexpr sf_ic<1> y{};
+  if (out_bf16) {
+    if (gelu) return res ? f(y, y, y) : f(y, y, n);
+    return res ? f(y, n, y) : f(y, n, n);
+  }
+  if (gelu) return res ? f(n, y, y) : f(n, y, n);
+  return res ? f(n, n, y) : f(n, n, n);
+}
+
+// GemmArgs::nchunk of configs 7, 11 and 12: the L2 rule of sf_launch_plan.h for bf16 rows, unless SF_GEMM_NCHUNK overrides it (experiments)
+static inline uint32_t sf_gemm_nchunk(int64_t K) {
+  static const int env_chunk = sf_env_int("SF_GEMM_NCHUNK", -1);
+  return env_chunk >= 0 ? (uint32_t)env_chunk : sf_l2_nchunk(K, 512, 1024);
+}
 
 // cache-policy bits of the epilogue's buffer ops (aux operand: bit 0 sc0/glc, bit 1 nt/slc, bit 4 sc1)
 // Outputs are written once and the fp32 residual is read once: marked non-temporal (nt) so that they do not evict the weight matrix

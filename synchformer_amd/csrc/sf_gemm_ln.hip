@@ -519,25 +519,37 @@ int sf_gemm_res_ln768_v2_launch(const uint16_t* A, int64_t lda, const uint16_t* 
 #ifndef SF_RL_DEFAULT_SCHED
 #define SF_RL_DEFAULT_SCHED SF_RL_PP
 #endif
+// W given k-step-major: [K / 32][768][32] (every stage's 48 KiB slice contiguous)
+static bool rl_w_kmajor(int64_t ldw, int64_t K) { return ldw == RL_BK && K > RL_BK; }
+
+// The argument rules the two entries share, under the name of the entry that was called.  0 or -1 (sf_last_error set).  What depends on M, and the "row
+// strides too large" check behind it, stays in the entries: they sit behind the entries' `M <= 0` return and their own 4 GiB checks, and which error a call
+// with several faults reports must not change.
+static int rl_check_args(const char* who, const bf16_t* A, int64_t lda, const bf16_t* W, int64_t ldw, const float* bias, const float* R, int64_t ldr, const float* X,
+                         int64_t ldx, const float* gamma, const float* beta, const bf16_t* Y, int64_t ldy, int64_t K) {
+  SF_CHECK_ARG(A && W && R && X && gamma && beta && Y, "%s: null pointer", who);
+  SF_CHECK_ARG(K > 0 && (K % RL_BK) == 0 && K < (1 << 20), "%s: K=%lld must be a positive multiple of 32", who, (long long)K);
+  SF_CHECK_ARG((lda % 8) == 0 && (ldw % 8) == 0 && lda >= K && (ldw >= K || rl_w_kmajor(ldw, K)), "%s: lda/ldw must be >= K and multiples of 8 elements", who);
+  SF_CHECK_ARG((ldr % 4) == 0 && (ldx % 4) == 0 && (ldy % 4) == 0 && ldr >= RL_N && ldx >= RL_N && ldy >= RL_N,
+               "%s: ldr/ldx/ldy must be >= 768 and multiples of 4 elements", who);
+  SF_CHECK_ARG(((uintptr_t)A % 16) == 0 && ((uintptr_t)W % 16) == 0 && ((uintptr_t)R % 16) == 0 && ((uintptr_t)X % 16) == 0 &&
+                   ((uintptr_t)Y % 8) == 0 && ((uintptr_t)gamma % 16) == 0 && ((uintptr_t)beta % 16) == 0 && (!bias || ((uintptr_t)bias % 16) == 0),
+               "%s: operands must be 16-byte aligned", who);
+  return 0;
+}
+
 extern "C" int sf_gemm_res_ln768(const bf16_t* A, int64_t lda, const bf16_t* W, int64_t ldw, const float* bias, const float* R, int64_t ldr,
                                  float* X, int64_t ldx, const float* gamma, const float* beta, float eps, bf16_t* Y, int64_t ldy, int64_t M,
                                  int64_t K, void* stream) {
-  SF_CHECK_ARG(A && W && R && X && gamma && beta && Y, "sf_gemm_res_ln768: null pointer");
-  SF_CHECK_ARG(K > 0 && (K % RL_BK) == 0 && K < (1 << 20), "sf_gemm_res_ln768: K=%lld must be a positive multiple of 32", (long long)K);
-  const bool w_kmajor = ldw == RL_BK && K > RL_BK;                 // W given k-step-major: [K / 32][768][32] (every stage's 48 KiB slice contiguous)
-  SF_CHECK_ARG((lda % 8) == 0 && (ldw % 8) == 0 && lda >= K && (ldw >= K || w_kmajor), "sf_gemm_res_ln768: lda/ldw must be >= K and multiples of 8 elements");
-  SF_CHECK_ARG((ldr % 4) == 0 && (ldx % 4) == 0 && (ldy % 4) == 0 && ldr >= RL_N && ldx >= RL_N && ldy >= RL_N,
-               "sf_gemm_res_ln768: ldr/ldx/ldy must be >= 768 and multiples of 4 elements");
-  SF_CHECK_ARG(((uintptr_t)A % 16) == 0 && ((uintptr_t)W % 16) == 0 && ((uintptr_t)R % 16) == 0 && ((uintptr_t)X % 16) == 0 &&
-                   ((uintptr_t)Y % 8) == 0 && ((uintptr_t)gamma % 16) == 0 && ((uintptr_t)beta % 16) == 0 && (!bias || ((uintptr_t)bias % 16) == 0),
-               "sf_gemm_res_ln768: operands must be 16-byte aligned");
+  if (int rc = rl_check_args("sf_gemm_res_ln768", A, lda, W, ldw, bias, R, ldr, X, ldx, gamma, beta, Y, ldy, K)) return rc;
+  const bool w_kmajor = rl_w_kmajor(ldw, K);
   if (M <= 0) return 0;
+  // SF_RL_SCHED, read once: 0 round 2's loop, 1 quadrant-phased (needs K % 64 == 0), 2 schedule 2
+  static const int env_sched = sf_env_int("SF_RL_SCHED", SF_RL_DEFAULT_SCHED);
   // Round 4, schedule 2 (sf_gemm_ln2.hip: 192 complete rows per workgroup in two column passes on the 192 x 384 main loop of sf_qkv_space_attention): taken for a
   // ROW-MAJOR weight when selected (sf_gemm_res_ln_force_schedule(2), or SF_RL_SCHED=2) and the shape fits (K % 128 == 0, lda / ldw multiples of 64)
   {
-    static int sched2 = -1;
-    if (sched2 < 0) { const char* e = getenv("SF_RL_SCHED"); sched2 = (e ? atoi(e) : SF_RL_DEFAULT_SCHED) == 2 ? 1 : 0; }
-    const bool want2 = g_rl_force_sched == 2 || (g_rl_force_sched < 0 && sched2);
+    const bool want2 = g_rl_force_sched == 2 || (g_rl_force_sched < 0 && env_sched == 2);
 #ifdef SF_ABLATION
     if (want2 && !w_kmajor && (K % 128) == 0 && K >= 128 && (lda % 64) == 0 && (ldw % 64) == 0 && ldw >= K)
       return sf_gemm_res_ln768_v2_launch(A, lda, W, ldw, bias, R, ldr, X, ldx, gamma, beta, eps, Y, ldy, M, K, stream);
@@ -560,15 +572,14 @@ extern "C" int sf_gemm_res_ln768(const bf16_t* A, int64_t lda, const bf16_t* W, 
   const int64_t tiles = m_pad / RL_BM;
   SF_CHECK_ARG(tiles < ((int64_t)1 << 31), "sf_gemm_res_ln768: too many tiles");
   a.tiles = (uint32_t)tiles;
-  { static int st = -1; if (st < 0) { const char* e = getenv("SF_RL_STAGGER"); st = e ? atoi(e) : 12; if (st < 0) st = 0; } a.stagger = K >= 768 ? (uint32_t)st : 0u; }   // (a tile of a shorter k-loop is shorter than the delay)
-  { static int ph = -1; if (ph < 0) { const char* e = getenv("SF_RL_PHASES"); ph = e ? atoi(e) : 1; if (ph < 1) ph = 1; } a.phases = (uint32_t)ph; }
-  int64_t blocks = tiles < n_cu ? tiles : n_cu;                    // one persistent workgroup per CU
-  static int abl = -1, max_blocks = -1, sched = -1;
-  if (max_blocks < 0) { const char* e = getenv("SF_RL_BLOCKS"); max_blocks = e ? atoi(e) : 0; }   // measurement hook: fewer resident workgroups
+  static const int stagger = std::max(sf_env_int("SF_RL_STAGGER", 12), 0), phases = std::max(sf_env_int("SF_RL_PHASES", 1), 1);
+  a.stagger = K >= 768 ? (uint32_t)stagger : 0u;                   // (a tile of a shorter k-loop is shorter than the delay)
+  a.phases = (uint32_t)phases;
+  int64_t blocks = sf_cu_grid(n_cu, tiles);
+  static const int max_blocks = sf_env_int("SF_RL_BLOCKS", 0);     // measurement hook: fewer resident workgroups
   if (max_blocks > 0 && blocks > max_blocks) blocks = max_blocks;
-  if (abl < 0) { const char* e = getenv("SF_RL_ABL"); abl = e ? atoi(e) : 0; }
-  if (sched < 0) { const char* e = getenv("SF_RL_SCHED"); sched = e ? atoi(e) : SF_RL_PP; }       // 0: round 2's loop, 1: quadrant-phased (needs K % 64 == 0)
-  const bool pp = (sched != 0 || g_rl_force_sched == 1) && g_rl_force_sched != 0 && (K % 64) == 0 && K >= 128;
+  static const int abl = sf_env_int("SF_RL_ABL", 0);
+  const bool pp = (env_sched != 0 || g_rl_force_sched == 1) && g_rl_force_sched != 0 && (K % 64) == 0 && K >= 128;
   const dim3 grid((unsigned)blocks), blk(512);
   hipStream_t st = (hipStream_t)stream;
 #define RL_LAUNCH(ABL_, PP_, LDS_) do { if (int rc_ = sf_prepare_kernel((const void*)gemm_res_ln768_kernel<ABL_, PP_>, LDS_, "sf_gemm_res_ln768")) return rc_; \
@@ -604,15 +615,8 @@ extern "C" int sf_gemm_res_ln768(const bf16_t* A, int64_t lda, const bf16_t* W, 
 extern "C" int sf_gemm_res_ln768_periodic(const bf16_t* A, int64_t lda, const bf16_t* W, int64_t ldw, const float* bias, const float* R, int64_t ldr, int64_t period,
                                           float* X, int64_t ldx, const float* gamma, const float* beta, float eps, bf16_t* Y, int64_t ldy, int64_t M, int64_t K,
                                           void* stream) {
-  SF_CHECK_ARG(A && W && R && X && gamma && beta && Y, "sf_gemm_res_ln768_periodic: null pointer");
-  SF_CHECK_ARG(K > 0 && (K % RL_BK) == 0 && K < (1 << 20), "sf_gemm_res_ln768_periodic: K=%lld must be a positive multiple of 32", (long long)K);
-  const bool w_kmajor = ldw == RL_BK && K > RL_BK;
-  SF_CHECK_ARG((lda % 8) == 0 && (ldw % 8) == 0 && lda >= K && (ldw >= K || w_kmajor), "sf_gemm_res_ln768_periodic: lda/ldw must be >= K and multiples of 8 elements");
-  SF_CHECK_ARG((ldr % 4) == 0 && (ldx % 4) == 0 && (ldy % 4) == 0 && ldr >= RL_N && ldx >= RL_N && ldy >= RL_N,
-               "sf_gemm_res_ln768_periodic: ldr/ldx/ldy must be >= 768 and multiples of 4 elements");
-  SF_CHECK_ARG(((uintptr_t)A % 16) == 0 && ((uintptr_t)W % 16) == 0 && ((uintptr_t)R % 16) == 0 && ((uintptr_t)X % 16) == 0 &&
-                   ((uintptr_t)Y % 8) == 0 && ((uintptr_t)gamma % 16) == 0 && ((uintptr_t)beta % 16) == 0 && (!bias || ((uintptr_t)bias % 16) == 0),
-               "sf_gemm_res_ln768_periodic: operands must be 16-byte aligned");
+  if (int rc = rl_check_args("sf_gemm_res_ln768_periodic", A, lda, W, ldw, bias, R, ldr, X, ldx, gamma, beta, Y, ldy, K)) return rc;
+  const bool w_kmajor = rl_w_kmajor(ldw, K);
   SF_CHECK_ARG(period >= 64 && period * ldr * 4 < ((int64_t)1 << 32), "sf_gemm_res_ln768_periodic: period=%lld must be >= 64 rows and the table below 4 GiB", (long long)period);
   SF_CHECK_ARG((const void*)R != (const void*)X, "sf_gemm_res_ln768_periodic: the residual table cannot be X");
   if (M <= 0) return 0;
@@ -630,7 +634,7 @@ extern "C" int sf_gemm_res_ln768_periodic(const bf16_t* A, int64_t lda, const bf
   a.stagger = K >= 768 ? 12u : 0u;                                  // the late start of the workgroups that own one tile fewer, as in sf_gemm_res_ln768
   a.phases = 1u;
   a.r_period = (uint32_t)period;
-  const dim3 grid((unsigned)(tiles < n_cu ? tiles : n_cu)), blk(512);
+  const dim3 grid((unsigned)sf_cu_grid(n_cu, tiles)), blk(512);
   hipStream_t st = (hipStream_t)stream;
   if ((K % 64) == 0 && K >= 128) {
     if (int rc = sf_prepare_kernel((const void*)gemm_res_ln768_periodic_kernel<true>, RP_LDS, "sf_gemm_res_ln768_periodic")) return rc;

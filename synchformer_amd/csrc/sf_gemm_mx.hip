@@ -719,19 +719,10 @@ static int mx_launch(MxArgs a, hipStream_t s) {
   if (int rc = sf_prepare_kernel((const void*)kern_pp, MQ_LDS, "sf_gemm_mxfp8")) return rc;
   const int n_cu = sf_cu_count("sf_gemm_mxfp8");
   if (n_cu <= 0) return -1;
-  const int64_t tiles_m = (a.M + MXBM - 1) / MXBM;
-  a.tiles_n = (uint32_t)((a.N + MXBN - 1) / MXBN);
-  const int64_t total = tiles_m * a.tiles_n;
-  if (total >= ((int64_t)1 << 31)) { sf_set_error("sf_gemm_mxfp8: too many tiles"); return -1; }
-  a.tiles_total = (uint32_t)total;
-  // column-chunked sweeps as in the bf16 kernel: keep the weight slice of a sweep (nchunk * 256 rows * K bytes) within ~2.4 MB of the XCD's L2
-  a.nchunk = a.K <= 2048 ? (uint32_t)(2400000 / (256 * a.K) > 0 ? 2400000 / (256 * a.K) : 1) : 0u;
-  int64_t blocks = (n_cu / 8) * 8;
-  if (blocks < 8) blocks = 8;                                    // (a device / partition with fewer than 8 CUs: never an empty grid)
-  const int64_t need = ((total + 7) / 8) * 8;
-  if (blocks > need) blocks = need;
-  static int env_sched = -1;
-  if (env_sched < 0) { const char* e = getenv("SF_MX_SCHED"); env_sched = e ? atoi(e) : 1; }
+  if (!sf_tile_counts(a.M, a.N, MXBM, MXBN, &a.tiles_n, &a.tiles_total)) { sf_set_error("sf_gemm_mxfp8: too many tiles"); return -1; }
+  a.nchunk = sf_l2_nchunk(a.K, 256, 2048);                       // column-chunked sweeps as in the bf16 kernel, on rows of K bytes
+  const int64_t blocks = sf_xcd_grid(n_cu, a.tiles_total);
+  static const int env_sched = sf_env_int("SF_MX_SCHED", 1);
   // quadrant-phased: whole pairs of 128-deep k-tiles (static stage indices), 24-bit row offsets
   const bool pp = (g_mx_force_sched >= 0 ? g_mx_force_sched != 0 : env_sched != 0) && (a.K % 256) == 0 && a.lda < (1 << 23) && a.ldw < (1 << 23);
   if (pp) hipLaunchKernelGGL(kern_pp, dim3((unsigned)blocks), dim3(512), MQ_LDS, s, a);

@@ -456,20 +456,11 @@ static int launch_gemm_pp(GemmArgs a, hipStream_t s) {
   if (int rc = sf_prepare_kernel((const void*)kern, Q_LDS, "sf_gemm_bf16")) return rc;
   const int n_cus = sf_cu_count("sf_gemm_bf16");
   if (n_cus <= 0) return -1;
-  const int64_t tiles_m = (a.M + 255) / 256;
-  a.tiles_n = (uint32_t)((a.N + 255) / 256);
-  const int64_t total = tiles_m * a.tiles_n;
-  if (total >= ((int64_t)1 << 31)) { sf_set_error("sf_gemm_bf16: too many tiles"); return -1; }
-  a.tiles_total = (uint32_t)total;
-  static int env_chunk = -2;
-  if (env_chunk == -2) { const char* e = getenv("SF_GEMM_NCHUNK"); env_chunk = e ? atoi(e) : -1; }
-  { static int st = -1; if (st < 0) { const char* e = getenv("SF_PP_STAGGER"); st = e ? atoi(e) : 0; if (st < 0) st = 0; } a.stagger = (uint32_t)st; }
-  if (env_chunk >= 0) a.nchunk = (uint32_t)env_chunk;
-  else a.nchunk = a.K <= 1024 ? (uint32_t)(2400000 / (512 * a.K) > 0 ? 2400000 / (512 * a.K) : 1) : 0u;
-  int64_t blocks = (n_cus / 8) * 8;                          // one workgroup per CU, a multiple of the 8 XCDs
-  if (blocks < 8) blocks = 8;                                    // (a device / partition with fewer than 8 CUs: never an empty grid)
-  const int64_t need = ((total + 7) / 8) * 8;
-  if (blocks > need) blocks = need;
+  if (!sf_tile_counts(a.M, a.N, 256, 256, &a.tiles_n, &a.tiles_total)) { sf_set_error("sf_gemm_bf16: too many tiles"); return -1; }
+  static const int stagger = std::max(sf_env_int("SF_PP_STAGGER", 0), 0);
+  a.stagger = (uint32_t)stagger;
+  a.nchunk = sf_gemm_nchunk(a.K);
+  const int64_t blocks = sf_xcd_grid(n_cus, a.tiles_total);
 #if SF_PP_ABL & 32
   static unsigned long long zero[256 * 8 * 5] = {0};
   (void)hipMemcpyToSymbol(HIP_SYMBOL(g_pp_trace), zero, sizeof(zero));
@@ -504,10 +495,5 @@ int sf_gemm_pp_dispatch(const GemmArgs& a, bool out_bf16, bool gelu, bool res, h
     if (!(out_bf16 && gelu && !res)) { sf_set_error("sf_gemm_bf16: a second (pre-activation) output needs the bf16 GELU epilogue without residual"); return -1; }
     return launch_gemm_pp<true, true, false, true>(a, s);
   }
-  if (out_bf16) {
-    if (gelu) return res ? launch_gemm_pp<true, true, true>(a, s) : launch_gemm_pp<true, true, false>(a, s);
-    return res ? launch_gemm_pp<true, false, true>(a, s) : launch_gemm_pp<true, false, false>(a, s);
-  }
-  if (gelu) return res ? launch_gemm_pp<false, true, true>(a, s) : launch_gemm_pp<false, true, false>(a, s);
-  return res ? launch_gemm_pp<false, false, true>(a, s) : launch_gemm_pp<false, false, false>(a, s);
+  return sf_gemm_dispatch_epi(out_bf16, gelu, res, [&](auto O, auto G, auto R) { return launch_gemm_pp<O() != 0, G() != 0, R() != 0>(a, s); });
 }

@@ -347,9 +347,7 @@ extern "C" int sf_gemm_tn_pp(const bf16_t* dY, int64_t ldy, const bf16_t* X, int
   const int64_t items = (int64_t)a.tiles * split;
   SF_CHECK_ARG(items < ((int64_t)1 << 30), "sf_gemm_tn_pp: too many work items");
   a.items = (uint32_t)items;
-  int64_t blocks = n_cu & ~7;                                      // a whole number of workgroups per XCD
-  if (blocks < 8) blocks = 8;
-  hipLaunchKernelGGL(gemm_tn_pp_kernel, dim3((unsigned)blocks), dim3(512), TQ_LDS, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(gemm_tn_pp_kernel, dim3((unsigned)sf_xcd_grid(n_cu)),dim3(512), TQ_LDS, (hipStream_t)stream, a);
   SF_LAUNCH_CHECK();
   return 0;
 }

@@ -340,20 +340,9 @@ static int launch_gemm_r4(GemmArgs a, hipStream_t s) {
   if (int rc = sf_prepare_kernel((const void*)kern, R4_LDS, "sf_gemm_bf16")) return rc;
   const int n_cus = sf_cu_count("sf_gemm_bf16");
   if (n_cus <= 0) return -1;
-  const int64_t tiles_m = (a.M + 255) / 256;
-  a.tiles_n = (uint32_t)((a.N + 255) / 256);
-  const int64_t total = tiles_m * a.tiles_n;
-  if (total >= ((int64_t)1 << 31)) { sf_set_error("sf_gemm_bf16: too many tiles"); return -1; }
-  a.tiles_total = (uint32_t)total;
-  static int env_chunk = -2;
-  if (env_chunk == -2) { const char* e = getenv("SF_GEMM_NCHUNK"); env_chunk = e ? atoi(e) : -1; }
-  if (env_chunk >= 0) a.nchunk = (uint32_t)env_chunk;
-  else a.nchunk = a.K <= 1024 ? (uint32_t)(2400000 / (512 * a.K) > 0 ? 2400000 / (512 * a.K) : 1) : 0u;
-  int64_t blocks = (n_cus / 8) * 8;                              // one workgroup per CU, a multiple of the 8 XCDs
-  if (blocks < 8) blocks = 8;
-  const int64_t need = ((total + 7) / 8) * 8;
-  if (blocks > need) blocks = need;
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), R4_LDS, s, a);
+  if (!sf_tile_counts(a.M, a.N, 256, 256, &a.tiles_n, &a.tiles_total)) { sf_set_error("sf_gemm_bf16: too many tiles"); return -1; }
+  a.nchunk = sf_gemm_nchunk(a.K);
+  hipLaunchKernelGGL(kern, dim3((unsigned)sf_xcd_grid(n_cus, a.tiles_total)), dim3(256), R4_LDS, s, a);
   SF_LAUNCH_CHECK();
   return 0;
 }

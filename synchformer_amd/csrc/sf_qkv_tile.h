@@ -307,8 +307,7 @@ static int qkt_check_args(const QktLaunch& L, const Args& a, int64_t n_seq, int 
 }
 
 // The launch of either kernel in any form, on its argument struct with the operand fields filled: checks them, fills seq_rows and n_rt, prepares `kernel` for its
-// 160 KiB of LDS and sizes the grid - one workgroup per CU, a multiple of the 8 XCD slots of the schedule (blockIdx % 8), never an empty grid on a device /
-// partition with fewer than 8 CUs, no more workgroups than work items (rounded up to the 8 slots).  0 or the error (sf_last_error set).
+// 160 KiB of LDS and sizes the grid by the XCD rule (sf_xcd_grid) over n_rt * 6 work items.  0 or the error (sf_last_error set).
 template <class Args, class Kernel>
 static int qkt_launch(const QktLaunch& L, Kernel kernel, Args& a, int64_t n_seq, int n_tok, void* stream) {
   a.seq_rows = 1 + 8 * 196;
@@ -318,18 +317,14 @@ static int qkt_launch(const QktLaunch& L, Kernel kernel, Args& a, int64_t n_seq,
   const int n_cu = sf_cu_count(L.name);
   if (n_cu <= 0) return -1;
   a.n_rt = (uint32_t)(n_seq * L.items_per_seq);
-  int64_t blocks = (n_cu / 8) * 8;
-  if (blocks < 8) blocks = 8;
-  const int64_t need = (((int64_t)a.n_rt * 6 + 7) / 8) * 8;
-  if (blocks > need) blocks = need;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(512), QKT_LDS, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)sf_xcd_grid(n_cu, (int64_t)a.n_rt * 6)),dim3(512), QKT_LDS, (hipStream_t)stream, a);
   SF_LAUNCH_CHECK();
   return 0;
 }
 
-// SF_QS_PAIR_CHUNK / SF_QT2_PAIR_CHUNK: head pairs per sweep over an XCD's row tiles (a divisor of 6; default and fallback 6)
+// SF_QS_PAIR_CHUNK / SF_QT2_PAIR_CHUNK: head pairs per sweep over an XCD's row tiles (a divisor of 6; default and fallback 6).  The
+// initialiser of a `static const int` at its two call sites: read once per process, like every knob.
 static int qkt_env_pair_chunk(const char* var) {
-  const char* e = getenv(var);
-  const int hc = e ? atoi(e) : 6;
+  const int hc = sf_env_int(var, 6);
   return (hc < 1 || 6 % hc) ? 6 : hc;
 }

@@ -692,15 +692,11 @@ static int qkv_time_impl(const uint16_t* X, int64_t ldx, const uint16_t* W, int6
   const int64_t tiles_m = (n_seq * n_groups + 31) / 32;
   SF_CHECK_ARG(tiles_m * QT_HEADS < ((int64_t)1 << 31) && n_seq * n_groups < ((int64_t)1 << 31), "sf_qkv_time_attention: too many tiles");
   a.tiles_m = (uint32_t)tiles_m;
-  static int env_hc = -1;
-  if (env_hc < 0) { const char* e = getenv("SF_QT_HEAD_CHUNK"); env_hc = e ? atoi(e) : 12; if (env_hc < 1 || QT_HEADS % env_hc) env_hc = 12; }   // round 4: all 12 heads per sweep (1276-1283 us against 1288-1293 for chunks of 6 on the quadrant-phased loop; r02 measured the opposite on the old loop)
+  // round 4: all 12 heads per sweep (1276-1283 us against 1288-1293 for chunks of 6 on the quadrant-phased loop; r02 measured the opposite on the old loop)
+  static const int env_hc = [] { const int hc = sf_env_int("SF_QT_HEAD_CHUNK", 12); return (hc < 1 || QT_HEADS % hc) ? 12 : hc; }();
   a.head_chunk = (uint32_t)env_hc;
-  int64_t blocks = (n_cu / 8) * 8;
-  if (blocks < 8) blocks = 8;                                    // (a device / partition with fewer than 8 CUs: never an empty grid)
-  const int64_t need = ((tiles_m * QT_HEADS + 7) / 8) * 8;
-  if (blocks > need) blocks = need;
-  static int env_sched = -1;
-  if (env_sched < 0) { const char* e = getenv("SF_QT_SCHED"); env_sched = e ? atoi(e) : QT_PP; }
+  const int64_t blocks = sf_xcd_grid(n_cu, tiles_m * QT_HEADS);
+  static const int env_sched = sf_env_int("SF_QT_SCHED", QT_PP);
   const bool pp = g_qt_force_sched >= 0 ? g_qt_force_sched != 0 : env_sched != 0;
   if (pp) hipLaunchKernelGGL(qkv_time_attn_kernel<true>, dim3((unsigned)blocks), dim3(512), QT_LDS, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(qkv_time_attn_kernel<false>, dim3((unsigned)blocks), dim3(512), QT_LDS, (hipStream_t)stream, a);
@@ -765,11 +761,7 @@ static int qkv_time_mx_impl(const uint8_t* X, int64_t ldx, const uint8_t* sX, in
   SF_CHECK_ARG(tiles_m * QT_HEADS < ((int64_t)1 << 31) && n_seq * n_groups < ((int64_t)1 << 31), "sf_qkv_time_attention_mx: too many tiles");
   a.tiles_m = (uint32_t)tiles_m;
   a.head_chunk = 6;
-  int64_t blocks = (n_cu / 8) * 8;
-  if (blocks < 8) blocks = 8;                                    // (a device / partition with fewer than 8 CUs: never an empty grid)
-  const int64_t need = ((tiles_m * QT_HEADS + 7) / 8) * 8;
-  if (blocks > need) blocks = need;
-  hipLaunchKernelGGL((qkv_time_attn_kernel<true, true>), dim3((unsigned)blocks), dim3(512), QT_LDS, (hipStream_t)stream, a);
+  hipLaunchKernelGGL((qkv_time_attn_kernel<true, true>), dim3((unsigned)sf_xcd_grid(n_cu, tiles_m * QT_HEADS)),dim3(512), QT_LDS, (hipStream_t)stream, a);
   SF_LAUNCH_CHECK();
   return 0;
 }

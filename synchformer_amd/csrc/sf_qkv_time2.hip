@@ -458,8 +458,7 @@ static int qt2_launch_bf16(const uint16_t* X, int64_t ldx, const uint16_t* W, in
   a.scale = scale; a.key_keep = key_keep;
   static const int env_hc = qkt_env_pair_chunk("SF_QT2_PAIR_CHUNK");
   a.pair_chunk = (uint32_t)env_hc;
-  static int env_st = -1;
-  if (env_st < 0) { const char* e = getenv("SF_QT2_STAGGER"); env_st = e ? atoi(e) : 0; if (env_st < 0) env_st = 0; }
+  static const int env_st = std::max(sf_env_int("SF_QT2_STAGGER", 0), 0);
   a.stagger = (uint32_t)env_st;
   return qkt_launch(QT2_BF16, key_keep ? qkv_time2_attn_masked_kernel : qkv_time2_attn_kernel, a, n_seq, n_tok, stream);
 }
